@@ -14,10 +14,12 @@ Launch forms (one process per GPU, torch.distributed backend "nccl" = RCCL over 
                                                             WORLD_SIZE / MASTER_* in the environment).
 Fewer than N visible devices is an error (exit code 3), never a silent 1-GPU run.
 
-At N > 1 the same JSON line also carries `gather_hits`: the same K steps with the RCCL gatherv of every hit list to
-rank 0 inside each step (grouped point-to-point exchange, gather of step i under the search of step i+1).
+A plain run sets up, warms up, times the K steps and prints the headline.  Everything else the line can carry (the
+open-addressing, two-stream and host-API legs, the CPU baseline and the check against the oracle, configs 3-5 and the
+query-length probes, and at N > 1 `gather_hits`: the same K steps with the RCCL gatherv of every hit list to rank 0 inside
+each step) runs only with --full.  --dump-outputs DIR writes what the last timed step computed as .npy files.
 
-Prints ONE JSON line on rank 0 (see the bench contract in the task / DESIGN.md §6).
+Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -38,6 +40,12 @@ CFG = {2: (4, 100_000_000, [10], 10_000_000, [10], 0.0, 1002, 2002),
        3: (4, 100_000_000, [8, 10, 12], 10_000_000, [8, 10, 12, 20, 22, 24], 0.5, 1003, 2003),
        4: (5, 100_000_000, [10], 12_500_000, [10], 0.0, 1004, 2004),
        5: (20, 10_000_000, [5], 10_000_000, [5], 0.5, 1005, 2005)}
+
+# --dump-outputs: the whole output of config 2 is 3.8 GB of positions, so a fixed sample of it is written (<= 49 MB)
+DUMP_SEED = 4242
+DUMP_QUERIES = 1 << 15
+DUMP_POSITIONS = 1 << 22
+DUMP_OFFSETS = 1 << 21
 
 
 def parse_args(argv=None):
@@ -82,7 +90,18 @@ def parse_args(argv=None):
     ap.add_argument("--oversubscribe", action="store_true",
                     help="rehearsal only: allow more ranks than visible GPUs (ranks share devices; the exchange runs over gloo because "
                          "RCCL refuses two ranks on one device).  The JSON line says so.")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg and check beyond the headline (the --no-* options above skip single ones); a plain run "
+                         "reports `verified_vs_oracle` null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's shard) to DIR/*.npy: a seeded sample of "
+                         f"{DUMP_QUERIES} queries (sample_query, sample_hit_count, sample_status, sample_positions: their whole lists, "
+                         f"the sample cut at the last query within {DUMP_POSITIONS} positions) and hit_off_strided (hit_off at every "
+                         f"s-th query, s = ceil((nq + 1) / {DUMP_OFFSETS}), then hit_off[nq]); float64, status float32")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -182,6 +201,9 @@ def worker(args):
             dist.init_process_group(backend, rank=rank, world_size=world)
     comm_dev = dev if backend == "nccl" else None    # where collectives' tensors live
 
+    if not args.full:                                # a plain run: the headline alone
+        args.no_open_compare = args.no_two_streams = args.no_cpu_baseline = args.no_host_api = args.no_other_configs = True
+
     sigma, n_cfg, ks, nq_cfg, qlens, planted, tseed, qseed = CFG[args.config]
     args.sigma = sigma
     args.n = args.n or n_cfg
@@ -277,7 +299,8 @@ def worker(args):
         if collect_stats:
             stats = index.stats()
             index.stats_enable(False)
-        return elapsed, results, stats
+        last = (no[0] - 1) % depth                        # returned first: the handle of the last timed step
+        return elapsed, results[last:] + results[:last], stats
 
     # ------------------------------------------------------------------------------------------------------------
     # leg 2 — gather: every step ends with all hit lists on rank 0.  Two handles on two compute streams; the gather of
@@ -479,11 +502,41 @@ def worker(args):
         o["wall_s"] = round(time.time() - t_c, 1)
         return o
 
+    def dump_outputs(res_, out_dir):
+        # the device arrays the search hands its caller (hit_off, positions, status), sampled on the device (see --dump-outputs)
+        class _Dev:
+            def __init__(self, ptr, n, typestr):
+                self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+        t_off, t_pos = res_.device_tensors(dev)
+        nq_ = t_off.numel() - 1
+        t_st = torch.as_tensor(_Dev(res_.device_ptrs()[2], nq_, "|u1"), device=dev)
+        q = np.sort(np.random.default_rng(DUMP_SEED).choice(nq_, size=min(nq_, DUMP_QUERIES), replace=False))
+        tq = torch.from_numpy(q).to(dev)
+        lo = t_off[tq]
+        cnt = t_off[tq + 1] - lo
+        keep = int(np.searchsorted(np.cumsum(cnt.cpu().numpy()), DUMP_POSITIONS, side="right"))   # whole lists only
+        q, lo, cnt = q[:keep], lo[:keep], cnt[:keep]
+        n_pos = int(cnt.sum().item()) if keep else 0
+        at = torch.repeat_interleave(lo - (torch.cumsum(cnt, 0) - cnt), cnt) + torch.arange(n_pos, device=dev)
+        stride = -(-(nq_ + 1) // DUMP_OFFSETS)
+        arrays = {"sample_query": q.astype(np.float64),
+                  "sample_hit_count": cnt.cpu().numpy().astype(np.float64),
+                  "sample_status": t_st[tq[:keep]].cpu().numpy().astype(np.float32),
+                  "sample_positions": t_pos[at].cpu().numpy().view(np.uint32).astype(np.float64),
+                  "hit_off_strided": torch.cat([t_off[::stride], t_off[nq_:]]).cpu().numpy().astype(np.float64)}
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+        log(f"outputs of the last timed step written to {out_dir}: {sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB")
+
     # (KMX_BENCH_INIT_PG: a 1-rank process group, so that a 1-GPU box still drives the RCCL code path end to end)
-    want_gather = backend is not None and args.gather in ("both", "hits")
+    want_gather = backend is not None and (args.gather == "hits" or (args.gather == "both" and args.full))
     elapsed, results, stats = run_sharded(idx, args.steps, args.warmup, True, args.streams)
     res = results[0]
     counts = res.counts()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs)
     # the same K steps with the two result handles on TWO streams (step i+1's lookup, scan and fill may overlap step i's):
     # more queries per second, but concurrent kernels have no meaningful duration of their own, so the roofline line stays
     # with the one-stream leg above and this one is reported beside it
@@ -546,7 +599,7 @@ def worker(args):
     # ---- verification of a sample against the CPU oracle (after the timed region) ----
     verified = None
     cpu_baseline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import orc
         nv = min(args.verify, nq)
         hit_off, positions, status, kinds = res.host()

@@ -8,7 +8,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--text-len", "300000", "--nq", "40000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-open-compare"]
+PLAIN = ["--text-len", "300000", "--nq", "40000", "--steps", "3", "--warmup", "1"]
+SMALL = PLAIN + ["--full", "--no-cpu-baseline", "--no-open-compare"]       # --full: the oracle check and the gather leg
 
 
 def _run(args, env_extra=None, timeout=600):
@@ -37,6 +38,36 @@ def test_more_gpus_than_visible_is_refused_not_downgraded():
 def test_world_size_must_match_gpus():
     rc, out, err = _run(["--gpus", "1"] + SMALL, env_extra={"RANK": "0", "WORLD_SIZE": "2", "LOCAL_RANK": "0"})
     assert rc != 0 and out is None and "WORLD_SIZE" in err
+
+
+def test_steps_must_be_at_least_one():
+    rc, out, err = _run(["--gpus", "1"] + PLAIN + ["--steps", "0"])
+    assert rc != 0 and out is None and "--steps" in err
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_and_dumps_the_same_outputs_as_a_full_run(tmp_path):
+    """A plain run times the K steps and nothing else; --dump-outputs writes the last timed step's (sampled) outputs, which a
+    --full run of the same arguments — checked against the oracle — reproduces array for array."""
+    import numpy as np
+    rc, plain, err = _run(["--gpus", "1"] + PLAIN + ["--steps", "4", "--dump-outputs", str(tmp_path / "plain")])
+    assert rc == 0, err[-2000:]
+    assert plain["steps"] == 4 and plain["ms_per_step"] > 0 and plain["value"] > 0 and plain["higher_is_better"] is True
+    assert plain["verified_vs_oracle"] is None and plain["two_streams"] is None and plain["host_api"] is None
+    rc, full, err = _run(["--gpus", "1"] + PLAIN + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    assert rc == 0, err[-2000:]
+    assert full["verified_vs_oracle"] is True and full["two_streams"] is not None
+    names = ["sample_query", "sample_hit_count", "sample_status", "sample_positions", "hit_off_strided"]
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    off = np.load(tmp_path / "plain" / "hit_off_strided.npy")
+    cnt = np.load(tmp_path / "plain" / "sample_hit_count.npy")
+    assert off[-1] == plain["config"]["hits_per_step_per_gpu"] and cnt.sum() == np.load(tmp_path / "plain" / "sample_positions.npy").size
+    assert cnt.size == 1 << 15 and cnt.sum() > 0                     # short lists: the whole sample fits
 
 
 @pytest.mark.gpu

@@ -385,6 +385,68 @@ namespace kmer
             return std::move(search_approx(std::vector<std::vector<alphabet_t>>{query}, max_subst).front());
         }
 
+        // Edit-distance search (kmx_search_approx with KMX_APPROX_EDIT): per query the ascending start offsets of every window
+        // within max_edits (<= KMX_APPROX_MAX_SUBST) substitutions, insertions and deletions of it, the least distance from
+        // each start and the length of the window that reaches it (the nearest to the query's length, the shorter of two).
+        struct edit_hits
+        {
+            std::vector<position_t> positions;
+            std::vector<std::uint8_t> distances;
+            std::vector<std::uint32_t> lengths;
+        };
+        std::vector<edit_hits> search_edit(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_edits,
+                                           std::vector<std::uint8_t>& status_out) const
+        {
+            std::vector<std::uint8_t> ranks;
+            std::vector<std::uint64_t> off(queries.size() + 1, 0);
+            for (std::size_t i = 0; i < queries.size(); ++i) off[i + 1] = off[i] + queries[i].size();
+            ranks.reserve(off.back());
+            for (auto const& q : queries)
+                for (auto const& l : q) ranks.push_back(traits::to_rank(l));
+            kmx_approx_result* raw = nullptr;
+            detail::throw_on(kmx_search_approx(_index.get(), ranks.data(), off.data(), queries.size(), std::uint32_t(max_edits), KMX_APPROX_EDIT, &raw),
+                             "search_edit");
+            std::unique_ptr<kmx_approx_result, void (*)(kmx_approx_result*)> hold(raw, kmx_approx_free);
+            const std::uint64_t* hit_off; const std::uint32_t* positions; const std::uint8_t* distances; const std::uint8_t* status;
+            const std::uint32_t* lengths;
+            detail::throw_on(kmx_approx_view(raw, &hit_off, &positions, &distances, &status), "search_edit");
+            detail::throw_on(kmx_approx_lengths(raw, &lengths), "search_edit");
+            status_out.assign(status, status + queries.size());
+            std::vector<edit_hits> out(queries.size());
+            for (std::size_t i = 0; i < queries.size(); ++i)
+            {
+                out[i].positions.assign(positions + hit_off[i], positions + hit_off[i + 1]);
+                out[i].distances.assign(distances + hit_off[i], distances + hit_off[i + 1]);
+                out[i].lengths.assign(lengths + hit_off[i], lengths + hit_off[i + 1]);
+            }
+            return out;
+        }
+
+        // with search_approx's error behaviour; the error's results carry positions and distances (as mismatches) of the others
+        std::vector<edit_hits> search_edit(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_edits) const
+        {
+            std::vector<std::uint8_t> status;
+            std::vector<edit_hits> out = search_edit(queries, max_edits, status);
+            for (std::size_t i = 0; i < status.size(); ++i)
+            {
+                if (status[i] == KMX_Q_OK) continue;
+                const std::string what = query_status_message(status[i]);
+                std::vector<approx_hits> others(out.size());
+                for (std::size_t j = 0; j < out.size(); ++j)
+                {
+                    others[j].positions = std::move(out[j].positions);
+                    others[j].mismatches = std::move(out[j].distances);
+                }
+                throw approx_query_error(what, i, std::move(status), std::move(others));
+            }
+            return out;
+        }
+
+        edit_hits search_edit(const std::vector<alphabet_t>& query, std::size_t max_edits) const
+        {
+            return std::move(search_edit(std::vector<std::vector<alphabet_t>>{query}, max_edits).front());
+        }
+
         // the text, reconstructed on the device from the index (kmx_index_text; an extension, no reference interface)
         std::vector<alphabet_t> text() const
         {

@@ -317,8 +317,24 @@ void kmx_result_free(kmx_result* r);
  * environment variables KMX_APPROX_CHUNK_CANDIDATES and KMX_APPROX_CHUNK_PIECES, read at every call, lower the two
  * bounds); the views always cover the whole batch.  Each call
  * runs on a stream and device buffers of its own: concurrent calls on one index are safe.  On an index with several
- * replicas the call runs on the first replica (batches are not sharded over replicas).  flags: 0 (reserved). */
+ * replicas the call runs on the first replica (batches are not sharded over replicas).  flags: 0 or KMX_APPROX_EDIT; any
+ * other bit is refused.
+ *
+ * KMX_APPROX_EDIT (a caller detects the capability by the macro; KMX_VERSION is unchanged): edit distance with unit costs
+ * (substitution, insertion, deletion) in place of Hamming distance, max_subst read as the bound e on edits.  A start offset
+ * p (0 <= p < n) is a hit when some window text[p, p + L) with L >= 1 and p + L <= n has Levenshtein distance <= e to q
+ * (only L in [m - e, m + e] can qualify).  Per hit, mismatches[] of kmx_approx_view holds d(p), the least such distance, and
+ * kmx_approx_lengths gives L(p): among the L that reach d(p) the one nearest to m, the shorter of two equally near.  Per
+ * query the hits are strictly ascending in p, each once; every start is reported, the neighbours of a good alignment
+ * included (p +- 1 at distance d + 1, and so on).  Statuses and their precedence are those above; m > n is served and has
+ * hits when some window of at least m - e letters qualifies.  With e = 0 the positions are those of the call without the
+ * flag, distances 0 and lengths m; for every e the hits without the flag are a subset, none with a smaller mismatch
+ * count than its d(p).  The pieces and their exact search are the same: a window within e edits holds one piece exactly, at
+ * most e letters off its nominal offset, so every piece hit names 2e + 1 candidate starts, verified by a banded dynamic
+ * programme on the device, deduplicated and ordered there.  n_candidates still counts piece hits; each of them counts
+ * 2e + 1 times against the candidate budget of a chunk. */
 #define KMX_APPROX_MAX_SUBST 3
+#define KMX_APPROX_EDIT 1u
 typedef struct kmx_approx_result kmx_approx_result;
 kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq,
                              uint32_t max_subst, uint32_t flags, kmx_approx_result** out);
@@ -329,6 +345,9 @@ kmx_status kmx_approx_counts(const kmx_approx_result* r, uint64_t* nq, uint64_t*
  *   status[nq] (uint8).  Valid until kmx_approx_free. */
 kmx_status kmx_approx_view(kmx_approx_result* r, const uint64_t** hit_off, const uint32_t** positions,
                            const uint8_t** mismatches, const uint8_t** status);
+/*   lengths[n_hits] (uint32), parallel to positions: the window length L(p) of every hit of a KMX_APPROX_EDIT call;
+ *   KMX_ERR_INVALID_ARGUMENT on the result of a call without the flag.  Valid until kmx_approx_free. */
+kmx_status kmx_approx_lengths(kmx_approx_result* r, const uint32_t** lengths);
 void kmx_approx_free(kmx_approx_result* r);
 
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one

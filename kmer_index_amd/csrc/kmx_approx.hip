@@ -9,6 +9,8 @@
 // piece before j matches the window exactly (the first-exact-piece rule: every window is reported by exactly one piece,
 // so nothing needs deduplicating).  The survivors of each (query, piece) list stay ascending; k_approx_compact packs them
 // in candidate order and k_approx_merge places each at its rank among the survivors of the query's other lists.
+// With KMX_APPROX_EDIT (edit distance: insertions and deletions too) the piece search is the same and a second path follows
+// it: see "edit distance" below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -89,7 +91,8 @@ inline unsigned int grid_for(uint64_t n, uint64_t per_block) { return unsigned(s
 struct kmx_approx_result {
     uint64_t nq = 0, n_hits = 0, n_candidates = 0;
     uint32_t n_chunks = 0;
-    PinnedArr hit_off, positions, mismatches, status;
+    bool edit = false;                                   // KMX_APPROX_EDIT: mismatches holds distances, lengths is filled
+    PinnedArr hit_off, positions, mismatches, status, lengths;
 };
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -383,6 +386,307 @@ __global__ __launch_bounds__(kBlock) void k_approx_merge(const uint32_t* __restr
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
+// edit distance (KMX_APPROX_EDIT): the same pieces, a banded dynamic programme per piece hit instead of the XOR
+//
+// A window within e edits of the query holds one piece exactly, at most e letters off its nominal offset: piece hit h of
+// piece j names the diagonal D = h - o_j and the starts p = D - e .. D + e.  k_edit_verify computes d(p) for all of them in
+// one pass from the end of the query to its front (F[i][t] = least distance of q[i, m) to a window that starts at t; a path
+// of cost <= e from a start within e of D stays on the 4e + 1 diagonals around D), k_edit_emit turns the survivors into
+// (query, p) keys, the radix sort of kmx_build_sort.hip orders them, equal neighbours are dropped, and k_edit_lengths runs
+// a forward pass of 2e + 1 diagonals from every remaining start for its window length.
+
+constexpr uint32_t kEditInf = 8;                     // any distance > KMX_APPROX_MAX_SUBST; cells saturate here
+constexpr uint32_t kEditNone = 7;                    // 3-bit field of EditArgs::keep: the start is no hit
+
+struct EditArgs {
+    const uint64_t* phit;     // as VerifyArgs
+    const uint32_t* pos;
+    uint64_t n_cand, np;
+    const uint64_t* qoff;
+    uint64_t q0;
+    const uint8_t* qstat;
+    const uint64_t* qwords;
+    const uint64_t* text;
+    uint64_t n;
+    uint32_t e;
+    uint32_t* keep;           // [n_cand]: 3 bits per start D - e .. D + e, its distance or kEditNone
+    uint32_t* bcount;         // surviving starts per block
+};
+
+// Letters tlo + r (r = 0 .. NL - 1) of the packed text against letter c: bit r * W of f0 (r < 64 / W) or bit (r - 64 / W) * W of
+// f1 is set when they differ.  Letters in front of the text or past it come out arbitrary (the callers' cells there are
+// invalid); no word outside the allocation is read (tlo is clamped to [0, n], three words from there lie inside the padding).
+template <uint32_t W, uint32_t NL>
+__device__ __forceinline__ void window_neq(const uint64_t* __restrict__ text, int64_t tlo, uint64_t n, uint32_t c, uint64_t& f0, uint64_t& f1)
+{
+    constexpr bool two = NL * W > 64;
+    const int64_t tb = min(max(tlo, int64_t(0)), int64_t(n));
+    const uint64_t bit = uint64_t(tb) * W;
+    const uint64_t* __restrict__ tw = text + (bit >> 6);
+    const uint32_t sh = uint32_t(bit & 63);
+    const uint64_t w0 = tw[0], w1 = tw[1];
+    uint64_t x0 = sh ? (w0 >> sh) | (w1 << (64 - sh)) : w0, x1 = 0;
+    if (two) {
+        const uint64_t w2 = tw[2];
+        x1 = sh ? (w1 >> sh) | (w2 << (64 - sh)) : w1;
+    }
+    if (tlo < 0) {                                   // letter 0 of the text belongs at field -tlo
+        const uint64_t s = min(uint64_t(-tlo) * W, uint64_t(two ? 127 : 63));
+        if (two) {
+            if (s >= 64) { x1 = x0 << (s - 64); x0 = 0; }
+            else { x1 = (x1 << s) | (x0 >> (64 - s)); x0 <<= s; }
+        } else {
+            x0 <<= s;
+        }
+    }
+    const uint64_t rep = uint64_t(c) * (W == 2 ? 0x5555555555555555ull : W == 4 ? 0x1111111111111111ull : 0x0101010101010101ull);
+    f0 = fold(x0 ^ rep, W);
+    f1 = two ? fold(x1 ^ rep, W) : 0;
+}
+
+template <uint32_t W>
+__device__ __forceinline__ uint32_t neq_at(uint64_t f0, uint64_t f1, uint32_t r)
+{
+    constexpr uint32_t L = 64 / W;
+    return uint32_t((r < L ? f0 >> (r * W) : f1 >> ((r - L) * W)) & 1u);
+}
+
+template <uint32_t W>
+__device__ __forceinline__ uint32_t query_letter(const uint64_t* __restrict__ qw, uint64_t i)
+{
+    constexpr uint32_t L = 64 / W;
+    return uint32_t(qw[i / L] >> ((i % L) * W)) & ((1u << W) - 1);
+}
+
+// Candidate-parallel like k_approx_verify.  Cell r of a row is the diagonal D + r - 2E: row i, text offset t = i + D + r - 2E.
+//   F[m][t] = 0,  F[i][t] = min(F[i + 1][t + 1] + (q[i] != text[t]), F[i + 1][t] + 1, F[i][t + 1] + 1),  t <= n, nothing past n
+// so a row is updated in place from its last cell to its first; the row of 4E + 1 cells stays in registers (every index is a
+// compile-time constant).  A cell with t < 0 holds no meaning and feeds none with t >= 0 (a cell depends on t and t + 1 only).
+template <uint32_t E, uint32_t W>
+__global__ __launch_bounds__(kBlock) void k_edit_verify(EditArgs A)
+{
+    constexpr uint32_t NB = 4 * E + 1, L = 64 / W;
+    __shared__ uint64_t s_range[2];
+    __shared__ uint32_t s_kept;
+    const uint64_t c0 = uint64_t(blockIdx.x) * kVerifySpan;
+    const uint64_t c_end = min(c0 + kVerifySpan, A.n_cand);
+    if (threadIdx.x == 0) {
+        s_range[0] = piece_of(A.phit, 0, A.np, c0);
+        s_range[1] = piece_of(A.phit, s_range[0], A.np, c_end - 1) + 1;
+        s_kept = 0;
+    }
+    __syncthreads();
+    const uint64_t plo = s_range[0], phi = s_range[1];
+    const int64_t n = int64_t(A.n);
+    uint32_t kept_here = 0;
+    for (uint32_t it = 0; it < kVerifyCpt; ++it) {
+        const uint64_t c = c0 + uint64_t(it) * kBlock + threadIdx.x;
+        if (c >= c_end) break;
+        uint32_t out = 0;
+#pragma unroll
+        for (uint32_t k = 0; k <= 2 * E; ++k) out |= kEditNone << (3 * k);
+        const uint64_t P = piece_of(A.phit, plo, phi, c);
+        const uint64_t qi = A.q0 + P / (E + 1);
+        const uint32_t j = uint32_t(P % (E + 1));
+        const uint64_t a = A.qoff[qi], m = A.qoff[qi + 1] - a;
+        const int64_t D = int64_t(A.pos[c]) - int64_t(piece_start(m, E, j));
+        bool run = A.qstat[qi] == KMX_Q_OK && D + int64_t(E) >= 0;
+        // a diagonal that an earlier piece of the query names too is left to that piece
+        for (uint32_t jj = 0; jj < j && run; ++jj) {
+            const int64_t t = D + int64_t(piece_start(m, E, jj));
+            if (t < 0) continue;
+            const uint64_t lo = A.phit[P - j + jj], hi = A.phit[P - j + jj + 1];
+            const uint64_t at = lower_u32(A.pos, lo, hi, uint32_t(t));
+            if (at < hi && A.pos[at] == uint32_t(t)) run = false;
+        }
+        if (run) {
+            const uint64_t* __restrict__ qw = A.qwords + a / L + qi;
+            uint32_t cell[NB];
+#pragma unroll
+            for (uint32_t r = 0; r < NB; ++r) cell[r] = int64_t(m) + D + int64_t(r) - int64_t(2 * E) <= n ? 0u : kEditInf;
+            bool alive = true;
+            for (uint64_t i = m; alive && i-- > 0;) {
+                const int64_t base = int64_t(i) + D - int64_t(2 * E);
+                uint64_t f0, f1;
+                window_neq<W, NB>(A.text, base, A.n, query_letter<W>(qw, i), f0, f1);
+                const int64_t lim = n - base;              // cell r is inside the text (t <= n) when r <= lim
+                uint32_t row_min = kEditInf;
+#pragma unroll
+                for (int r = int(NB) - 1; r >= 0; --r) {
+                    uint32_t v = cell[r] + neq_at<W>(f0, f1, uint32_t(r));
+                    if (r > 0) v = min(v, cell[r - 1] + 1);
+                    if (r < int(NB) - 1) v = min(v, cell[r + 1] + 1);
+                    v = min(v, kEditInf);
+                    if (int64_t(r) > lim) v = kEditInf;
+                    cell[r] = v;
+                    row_min = min(row_min, v);
+                }
+                alive = row_min <= E;
+            }
+            if (alive) {
+                out = 0;
+#pragma unroll
+                for (uint32_t k = 0; k <= 2 * E; ++k) {
+                    const bool hit = D - int64_t(E) + int64_t(k) >= 0 && cell[E + k] <= E;
+                    out |= (hit ? cell[E + k] : kEditNone) << (3 * k);
+                    kept_here += hit;
+                }
+            }
+        }
+        A.keep[c] = out;
+    }
+    if (kept_here) atomicAdd(&s_kept, kept_here);
+    __syncthreads();
+    if (threadIdx.x == 0) A.bcount[blockIdx.x] = s_kept;
+}
+
+// The surviving starts as (query within the chunk << pbits | p, distance) pairs, block b from bscan[b] in any order (they are
+// sorted next).
+__global__ __launch_bounds__(kBlock) void k_edit_emit(EditArgs A, const uint64_t* __restrict__ bscan, uint32_t pbits,
+                                                      uint64_t* __restrict__ keys, uint32_t* __restrict__ vals)
+{
+    __shared__ uint64_t s_range[2];
+    __shared__ uint32_t s_at;
+    const uint64_t c0 = uint64_t(blockIdx.x) * kVerifySpan;
+    const uint64_t c_end = min(c0 + kVerifySpan, A.n_cand);
+    if (A.bcount[blockIdx.x] == 0) return;                      // (block-uniform)
+    if (threadIdx.x == 0) {
+        s_range[0] = piece_of(A.phit, 0, A.np, c0);
+        s_range[1] = piece_of(A.phit, s_range[0], A.np, c_end - 1) + 1;
+        s_at = 0;
+    }
+    __syncthreads();
+    const uint32_t e = A.e;
+    const uint64_t base = bscan[blockIdx.x];
+    for (uint32_t it = 0; it < kVerifyCpt; ++it) {
+        const uint64_t c = c0 + uint64_t(it) * kBlock + threadIdx.x;
+        if (c >= c_end) break;
+        const uint32_t k3 = A.keep[c];
+        uint32_t cnt = 0;
+        for (uint32_t k = 0; k <= 2 * e; ++k) cnt += ((k3 >> (3 * k)) & 7u) != kEditNone;
+        if (!cnt) continue;
+        const uint64_t P = piece_of(A.phit, s_range[0], s_range[1], c);
+        const uint64_t ql = P / (e + 1), qi = A.q0 + ql;
+        const uint64_t m = A.qoff[qi + 1] - A.qoff[qi];
+        const int64_t D = int64_t(A.pos[c]) - int64_t(piece_start(m, e, uint32_t(P % (e + 1))));
+        uint64_t at = base + atomicAdd(&s_at, cnt);
+        for (uint32_t k = 0; k <= 2 * e; ++k) {
+            const uint32_t d = (k3 >> (3 * k)) & 7u;
+            if (d == kEditNone) continue;
+            keys[at] = (ql << pbits) | uint64_t(D - int64_t(e) + int64_t(k));
+            vals[at] = d;
+            ++at;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_edit_heads(const uint64_t* __restrict__ keys, uint64_t n_s, uint32_t* __restrict__ head)
+{
+    const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (i < n_s) head[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
+}
+
+// the first of every run of equal keys (equal keys carry equal distances: d(p) does not depend on the diagonal that found it)
+__global__ __launch_bounds__(kBlock) void k_edit_unique(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                        const uint32_t* __restrict__ head, const uint64_t* __restrict__ rank, uint64_t n_s,
+                                                        uint32_t pbits, uint64_t* __restrict__ ukeys, uint32_t* __restrict__ out_pos,
+                                                        uint8_t* __restrict__ out_d)
+{
+    const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= n_s || !head[i]) return;
+    const uint64_t u = rank[i], key = keys[i];
+    ukeys[u] = key;
+    out_pos[u] = uint32_t(key & ((uint64_t(1) << pbits) - 1));
+    out_d[u] = uint8_t(vals[i]);
+}
+
+// hit_off of the chunk's queries: the first distinct key of each
+__global__ __launch_bounds__(kBlock) void k_edit_hit_off(const uint64_t* __restrict__ ukeys, uint64_t n_u, uint64_t nq, uint32_t pbits,
+                                                         uint64_t* __restrict__ hit_off)
+{
+    const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (i > nq) return;
+    uint64_t lo = 0, hi = n_u;
+    const uint64_t x = i << pbits;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (ukeys[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    hit_off[i] = lo;
+}
+
+// One thread per reported start p: G[i][c] = distance of q[0, i) to text[p, p + c) on the diagonals c - i = -E .. E (cell r:
+// c = i + r - E), updated in place from the first cell to the last; of the cells of row m that hold d(p), the one nearest to
+// the main diagonal gives the length, the shorter of two equally near.
+template <uint32_t E, uint32_t W>
+__global__ __launch_bounds__(kBlock) void k_edit_lengths(const uint64_t* __restrict__ ukeys, const uint8_t* __restrict__ out_d, uint64_t n_u,
+                                                         uint32_t pbits, EditArgs A, uint32_t* __restrict__ out_len)
+{
+    constexpr uint32_t NB = 2 * E + 1, L = 64 / W;
+    const uint64_t u = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (u >= n_u) return;
+    const uint64_t key = ukeys[u];
+    const uint64_t qi = A.q0 + (key >> pbits);
+    const int64_t p = int64_t(key & ((uint64_t(1) << pbits) - 1)), n = int64_t(A.n);
+    const uint64_t a = A.qoff[qi], m = A.qoff[qi + 1] - a;
+    const uint64_t* __restrict__ qw = A.qwords + a / L + qi;
+    const uint32_t d = out_d[u];
+    uint32_t cell[NB];
+#pragma unroll
+    for (uint32_t r = 0; r < NB; ++r) cell[r] = (r >= E && p + int64_t(r - E) <= n) ? r - E : kEditInf;
+    for (uint64_t i = 1; i <= m; ++i) {
+        uint64_t f0, f1;
+        window_neq<W, NB>(A.text, p + int64_t(i) - int64_t(E) - 1, A.n, query_letter<W>(qw, i - 1), f0, f1);
+        const int64_t lim = n - p - int64_t(i) + int64_t(E);      // cell r ends inside the text (p + c <= n) when r <= lim
+#pragma unroll
+        for (uint32_t r = 0; r < NB; ++r) {
+            uint32_t v = cell[r] + neq_at<W>(f0, f1, r);
+            if (r + 1 < NB) v = min(v, cell[r + 1] + 1);
+            if (r > 0) v = min(v, cell[r - 1] + 1);
+            v = min(v, kEditInf);
+            if (int64_t(r) > lim || i + r < E) v = kEditInf;       // (c < 0: no such cell)
+            cell[r] = v;
+        }
+    }
+    uint32_t len = 0;                                              // (d(p) is on row m: 0 is never written)
+#pragma unroll
+    for (int k = int(E); k >= 1; --k) {
+        if (cell[E + k] == d) len = uint32_t(m) + k;
+        if (cell[E - k] == d) len = uint32_t(m) - k;
+    }
+    if (cell[E] == d) len = uint32_t(m);
+    out_len[u] = len;
+}
+
+template <template <uint32_t, uint32_t> class F, typename... Args>
+static void edit_dispatch(uint32_t e, uint32_t w, Args&&... args)
+{
+    switch (e * 16 + w) {
+    case 0 * 16 + 2: F<0, 2>::launch(args...); break;
+    case 0 * 16 + 4: F<0, 4>::launch(args...); break;
+    case 0 * 16 + 8: F<0, 8>::launch(args...); break;
+    case 1 * 16 + 2: F<1, 2>::launch(args...); break;
+    case 1 * 16 + 4: F<1, 4>::launch(args...); break;
+    case 1 * 16 + 8: F<1, 8>::launch(args...); break;
+    case 2 * 16 + 2: F<2, 2>::launch(args...); break;
+    case 2 * 16 + 4: F<2, 4>::launch(args...); break;
+    case 2 * 16 + 8: F<2, 8>::launch(args...); break;
+    case 3 * 16 + 2: F<3, 2>::launch(args...); break;
+    case 3 * 16 + 4: F<3, 4>::launch(args...); break;
+    default: F<3, 8>::launch(args...); break;
+    }
+}
+template <uint32_t E, uint32_t W> struct LaunchEditVerify {
+    static void launch(hipStream_t s, unsigned nb, const EditArgs& A) { hipLaunchKernelGGL((k_edit_verify<E, W>), dim3(nb), dim3(kBlock), 0, s, A); }
+};
+template <uint32_t E, uint32_t W> struct LaunchEditLengths {
+    static void launch(hipStream_t s, const uint64_t* ukeys, const uint8_t* out_d, uint64_t n_u, uint32_t pbits, const EditArgs& A, uint32_t* out_len)
+    {
+        hipLaunchKernelGGL((k_edit_lengths<E, W>), dim3(grid_for(n_u, kBlock)), dim3(kBlock), 0, s, ukeys, out_d, n_u, pbits, A, out_len);
+    }
+};
+
+// ------------------------------------------------------------------------------------------------------------------------
 // host side
 
 void kmx::packed_text_release(PackedText* t)
@@ -465,6 +769,72 @@ struct ResultGuard {
 };
 } // namespace
 
+namespace {
+struct EditBufs {
+    Buf keep, bcount, bsum, bscan, total, ka, va, kb, vb, ukeys, olen;
+};
+inline uint32_t bit_width(uint64_t x) { uint32_t b = 0; while (x) { ++b; x >>= 1; } return b; }
+} // namespace
+
+// The edit path of one chunk behind the piece search: hit_off[nq + 1], positions, distances and lengths of its queries on the
+// device, *n_hits of them.
+static kmx_status edit_chunk(hipStream_t s, EditArgs V, uint32_t w, uint64_t nq, EditBufs& B, PinnedArr& h_total, Buf& d_hit_off, Buf& d_opos,
+                             Buf& d_od, uint64_t* n_hits)
+{
+    *n_hits = 0;
+    const uint32_t e = V.e;
+    const uint64_t nb = (V.n_cand + kVerifySpan - 1) / kVerifySpan;
+    AX_TRY(B.keep.ensure(V.n_cand * 4));
+    AX_TRY(B.bcount.ensure(nb * 4 + 16));
+    AX_TRY(B.bsum.ensure(kmx::scan_blocks(nb) * 8 + 16));
+    AX_TRY(B.bscan.ensure((nb + 1) * 8));
+    AX_TRY(B.total.ensure(16));
+    V.keep = B.keep.as<uint32_t>();
+    V.bcount = B.bcount.as<uint32_t>();
+    edit_dispatch<LaunchEditVerify>(e, w, s, unsigned(nb), V);
+    AX_TRY(hipGetLastError());
+    kmx::launch_scan(s, V.bcount, nb, B.bsum.as<uint64_t>(), B.bscan.as<uint64_t>(), B.total.as<unsigned long long>());
+    AX_TRY(hipGetLastError());
+    AX_TRY(hipMemcpyAsync(h_total.p, B.total.p, 8, hipMemcpyDeviceToHost, s));
+    AX_TRY(hipStreamSynchronize(s));
+    const uint64_t n_s = h_total.as<uint64_t>()[0];
+    if (!n_s) return KMX_OK;
+    const uint32_t pbits = std::max(bit_width(V.n - 1), 1u), key_bits = pbits + bit_width(nq - 1);
+    AX_TRY(B.ka.ensure((n_s + 1) * 8));                                      // (+ 1: whichever pair the sort leaves free takes a scan of
+    AX_TRY(B.kb.ensure((n_s + 1) * 8));                                      //  n_s entries and its total)
+    AX_TRY(B.va.ensure(n_s * 4));
+    AX_TRY(B.vb.ensure(n_s * 4));
+    hipLaunchKernelGGL(k_edit_emit, dim3(unsigned(nb)), dim3(kBlock), 0, s, V, B.bscan.as<uint64_t>(), pbits, B.ka.as<uint64_t>(), B.va.as<uint32_t>());
+    AX_TRY(hipGetLastError());
+    bool in_b = false;
+    AX_TRY(kmx::sort_pairs_u64(s, B.ka.as<uint64_t>(), B.va.as<uint32_t>(), B.kb.as<uint64_t>(), B.vb.as<uint32_t>(), n_s, key_bits, &in_b));
+    const uint64_t* keys = in_b ? B.kb.as<uint64_t>() : B.ka.as<uint64_t>();
+    const uint32_t* vals = in_b ? B.vb.as<uint32_t>() : B.va.as<uint32_t>();
+    uint64_t* rank = in_b ? B.ka.as<uint64_t>() : B.kb.as<uint64_t>();        // the other pair of arrays is free again
+    uint32_t* head = in_b ? B.va.as<uint32_t>() : B.vb.as<uint32_t>();
+    AX_TRY(B.bsum.ensure(kmx::scan_blocks(n_s) * 8 + 16));
+    hipLaunchKernelGGL(k_edit_heads, dim3(grid_for(n_s, kBlock)), dim3(kBlock), 0, s, keys, n_s, head);
+    AX_TRY(hipGetLastError());
+    kmx::launch_scan(s, head, n_s, B.bsum.as<uint64_t>(), rank, B.total.as<unsigned long long>());
+    AX_TRY(hipGetLastError());
+    AX_TRY(hipMemcpyAsync(h_total.p, B.total.p, 8, hipMemcpyDeviceToHost, s));
+    AX_TRY(hipStreamSynchronize(s));
+    const uint64_t n_u = h_total.as<uint64_t>()[0];
+    AX_TRY(B.ukeys.ensure(n_u * 8));
+    AX_TRY(d_opos.ensure(n_u * 4));
+    AX_TRY(d_od.ensure(n_u));
+    AX_TRY(B.olen.ensure(n_u * 4));
+    hipLaunchKernelGGL(k_edit_unique, dim3(grid_for(n_s, kBlock)), dim3(kBlock), 0, s, keys, vals, head, rank, n_s, pbits, B.ukeys.as<uint64_t>(),
+                       d_opos.as<uint32_t>(), d_od.as<uint8_t>());
+    AX_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_edit_hit_off, dim3(grid_for(nq + 1, kBlock)), dim3(kBlock), 0, s, B.ukeys.as<uint64_t>(), n_u, nq, pbits, d_hit_off.as<uint64_t>());
+    AX_TRY(hipGetLastError());
+    edit_dispatch<LaunchEditLengths>(e, w, s, B.ukeys.as<uint64_t>(), d_od.as<uint8_t>(), n_u, pbits, V, B.olen.as<uint32_t>());
+    AX_TRY(hipGetLastError());
+    *n_hits = n_u;
+    return KMX_OK;
+}
+
 extern "C" {
 
 kmx_status kmx_index_text(const kmx_index* index, uint8_t* out_ranks, uint64_t n, uint64_t* packed_bytes)
@@ -494,7 +864,7 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
 {
     if (!index || !out) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: NULL argument");
     if (max_subst > KMX_APPROX_MAX_SUBST) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: max_subst > KMX_APPROX_MAX_SUBST");
-    if (flags != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: flags must be 0");
+    if (flags & ~uint32_t(KMX_APPROX_EDIT)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: unknown flag bits");
     if (nq && !qoff) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: NULL query offsets");
     if (nq && qoff[0] != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: qoff[0] must be 0");
     for (uint64_t i = 0; i < nq; ++i)
@@ -507,6 +877,8 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
     uint64_t budget = kDefaultBudget, max_pieces = kMaxPieces;
     if (const char* env = getenv("KMX_APPROX_CHUNK_CANDIDATES")) { const long long v = atoll(env); if (v > 0) budget = uint64_t(v); }
     if (const char* env = getenv("KMX_APPROX_CHUNK_PIECES")) { const long long v = atoll(env); if (v > 0) max_pieces = std::min(uint64_t(v), kMaxPieces); }
+    const bool edit = (flags & KMX_APPROX_EDIT) != 0;
+    if (edit) budget = std::max<uint64_t>(budget / (2 * e + 1), 1);      // a piece hit names 2e + 1 starts: each counts against the budget
 
     DeviceGuard dg;
     AX_TRY(hipSetDevice(A.device));
@@ -520,12 +892,15 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
 
     std::unique_ptr<kmx_approx_result> R(new kmx_approx_result());
     R->nq = nq;
+    R->edit = edit;
+    if (edit && !R->lengths.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_search_approx: page-locked host memory");
     if (!R->hit_off.grow((nq + 1) * 8) || !R->status.grow(nq + 1) || !R->positions.grow(64) || !R->mismatches.grow(64))
         return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_search_approx: page-locked host memory");
     R->hit_off.as<uint64_t>()[0] = 0;
 
     Buf d_qr, d_qoff, d_poff, d_qstat, d_qwords, d_qcand, d_keep, d_bcount, d_bsum, d_bscan, d_total, d_spos, d_spiece, d_smm,
         d_hit_off, d_opos, d_omm;
+    EditBufs eb;
     PinnedArr h_qcand, h_total;
     if (!h_total.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_search_approx: page-locked host memory");
     ResultGuard pres;
@@ -582,7 +957,13 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
             AX_TRY(hipGetLastError());
             uint64_t n_s = 0;
             AX_TRY(d_hit_off.ensure((b - a + 1) * 8));
-            if (n_cand) {
+            if (edit) {
+                if (n_cand) {
+                    EditArgs V{phit, ppos, n_cand, np, d_qoff.as<uint64_t>(), a, d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>(), text, A.n, e, nullptr, nullptr};
+                    st = edit_chunk(s, V, w, b - a, eb, h_total, d_hit_off, d_opos, d_omm, &n_s);
+                    if (st != KMX_OK) return st;
+                }
+            } else if (n_cand) {
                 const uint64_t nb = (n_cand + kVerifySpan - 1) / kVerifySpan;
                 AX_TRY(d_keep.ensure(n_cand));
                 AX_TRY(d_bcount.ensure(nb * 4 + 16));
@@ -612,16 +993,18 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
                     AX_TRY(hipGetLastError());
                 }
             }
-            if (n_s) {
+            if (n_s && !edit) {                                  // (edit_chunk wrote the chunk's hit_off itself)
                 hipLaunchKernelGGL(k_approx_hit_off, dim3(grid_for(b - a + 1, kBlock)), dim3(kBlock), 0, s, d_spiece.as<uint32_t>(), n_s, b - a, e,
                                    d_hit_off.as<uint64_t>());
                 AX_TRY(hipGetLastError());
-            } else {
+            } else if (!n_s) {
                 AX_TRY(hipMemsetAsync(d_hit_off.p, 0, (b - a + 1) * 8, s));
             }
             // this chunk's part of the result to the host arrays
             const uint64_t q_at = Q0 + a, h_at = R->n_hits;
             if (!R->positions.grow((h_at + n_s) * 4 + 64) || !R->mismatches.grow(h_at + n_s + 64))
+                return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_search_approx: page-locked host memory");
+            if (edit && !R->lengths.grow((h_at + n_s) * 4 + 64))
                 return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_search_approx: page-locked host memory");
             uint64_t* ho = R->hit_off.as<uint64_t>() + q_at;     // (ho[0], the previous chunk's end, is rewritten with the same value)
             AX_TRY(hipMemcpyAsync(ho, d_hit_off.p, (b - a + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -629,6 +1012,7 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
             if (n_s) {
                 AX_TRY(hipMemcpyAsync(R->positions.as<uint32_t>() + h_at, d_opos.p, n_s * 4, hipMemcpyDeviceToHost, s));
                 AX_TRY(hipMemcpyAsync(R->mismatches.as<uint8_t>() + h_at, d_omm.p, n_s, hipMemcpyDeviceToHost, s));
+                if (edit) AX_TRY(hipMemcpyAsync(R->lengths.as<uint32_t>() + h_at, eb.olen.p, n_s * 4, hipMemcpyDeviceToHost, s));
             }
             AX_TRY(hipStreamSynchronize(s));
             for (uint64_t i = 0; i <= b - a; ++i) ho[i] += h_at;
@@ -660,6 +1044,14 @@ kmx_status kmx_approx_view(kmx_approx_result* r, const uint64_t** hit_off, const
     if (positions) *positions = r->positions.as<uint32_t>();
     if (mismatches) *mismatches = r->mismatches.as<uint8_t>();
     if (status) *status = r->status.as<uint8_t>();
+    return KMX_OK;
+}
+
+kmx_status kmx_approx_lengths(kmx_approx_result* r, const uint32_t** lengths)
+{
+    if (!r) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_approx_lengths: result is NULL");
+    if (!r->edit) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_approx_lengths: the result is not one of a KMX_APPROX_EDIT call");
+    if (lengths) *lengths = r->lengths.as<uint32_t>();
     return KMX_OK;
 }
 

@@ -191,6 +191,35 @@ static hipError_t sort_pairs(hipStream_t s, const uint8_t* d_text, uint64_t npos
     return e;
 }
 
+// the same passes over pairs the caller made: from (keys_a, vals_a), ping-pong with (keys_b, vals_b); *in_b tells where they ended
+hipError_t sort_pairs_u64(hipStream_t s, uint64_t* keys_a, uint32_t* vals_a, uint64_t* keys_b, uint32_t* vals_b, uint64_t n, uint32_t key_bits,
+                          bool* in_b)
+{
+    *in_b = false;
+    if (n == 0) return hipSuccess;
+    const uint32_t passes = std::max<uint32_t>(1, (key_bits + 7) / 8);
+    const uint32_t n_tiles = uint32_t((n + kSortTile - 1) / kSortTile);
+    Temp hist, offs, bsum;
+    hipError_t e = hist.alloc(size_t(256) * n_tiles * 4);
+    if (e == hipSuccess) e = offs.alloc((size_t(256) * n_tiles + 1) * 8);
+    if (e == hipSuccess) e = bsum.alloc((scan_blocks(uint64_t(256) * n_tiles) + 2) * 8);
+    if (e != hipSuccess) return e;
+    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(bsum.as<uint64_t>() + scan_blocks(uint64_t(256) * n_tiles));
+    uint64_t *kin = keys_a, *kout = keys_b;
+    uint32_t *vin = vals_a, *vout = vals_b;
+    for (uint32_t p = 0; p < passes; ++p) {
+        hipLaunchKernelGGL(k_rs_hist, dim3(n_tiles), dim3(kBlock), 0, s, kin, n, 8 * p, hist.as<uint32_t>(), n_tiles);
+        launch_scan(s, hist.as<uint32_t>(), uint64_t(256) * n_tiles, bsum.as<uint64_t>(), offs.as<uint64_t>(), d_total);
+        hipLaunchKernelGGL(k_rs_scatter, dim3(n_tiles), dim3(kBlock), 0, s, kin, vin, n, 8 * p, offs.as<uint64_t>(), n_tiles, kout, vout);
+        std::swap(kin, kout);
+        std::swap(vin, vout);
+    }
+    *in_b = (passes & 1u) != 0;
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);                      // the temporaries are released on return
+    return e;
+}
+
 hipError_t sort_kmer_positions(hipStream_t s, const uint8_t* d_text, uint64_t n, uint32_t k, uint32_t sigma, uint32_t key_bits,
                                uint32_t* d_positions)
 {

@@ -61,6 +61,10 @@ hipError_t sort_kmer_positions(hipStream_t s, const uint8_t* d_text, uint64_t n,
                                uint32_t* d_positions);
 hipError_t build_sparse_element(hipStream_t s, const uint8_t* d_text, uint64_t n, uint32_t k, uint32_t sigma, uint32_t key_bits,
                                 uint32_t* d_positions, SparseTables* out);
+// the stable LSD radix sort behind the two: n (u64 key, u32 value) pairs by the low key_bits bits of the key, from (keys_a, vals_a),
+// ping-pong with (keys_b, vals_b); *in_b: the sorted pairs are in the b arrays.  Synchronises the stream.
+hipError_t sort_pairs_u64(hipStream_t s, uint64_t* keys_a, uint32_t* vals_a, uint64_t* keys_b, uint32_t* vals_b, uint64_t n, uint32_t key_bits,
+                          bool* in_b);
 void launch_scan(hipStream_t s, const uint32_t* in, uint64_t n, uint64_t* bsum, uint64_t* out,
                  unsigned long long* total_out);
 // k_fill build variants: e = output slots per thread (tile = 256 * e), nt = non-temporal stores

@@ -18,6 +18,7 @@ SEARCH_DEFAULT, SEARCH_KEEP_MASKS, SEARCH_COUNT_ONLY, SEARCH_ASYNC, SEARCH_REFER
 KIND_NONE, KIND_EXACT, KIND_STITCH, KIND_PREFIX = 0, 1, 2, 3
 Q_OK, Q_TOO_LONG, Q_SUBK_FANOUT, Q_EMPTY_QUERY, Q_BAD_RANK, Q_TOO_SHORT = 0, 1, 2, 3, 4, 5
 APPROX_MAX_SUBST = 3
+APPROX_EDIT = 1
 
 # every symbol include/kmx.h declares
 EXPORTS = [
@@ -28,6 +29,7 @@ EXPORTS = [
     "kmx_index_devices", "kmx_result_parts", "kmx_result_part_view_device",
     "kmx_index_bucket_host", "kmx_index_levels", "kmx_result_gather_device",
     "kmx_search_approx", "kmx_approx_counts", "kmx_approx_view", "kmx_approx_free", "kmx_index_text",
+    "kmx_approx_lengths",
 ]
 
 
@@ -121,6 +123,8 @@ def lib():
         L.kmx_approx_counts.argtypes = [vp, P(u64), P(u64), P(u64), P(u32)]
         L.kmx_approx_view.restype = C.c_int
         L.kmx_approx_view.argtypes = [vp, P(vp), P(vp), P(vp), P(vp)]
+        L.kmx_approx_lengths.restype = C.c_int
+        L.kmx_approx_lengths.argtypes = [vp, P(vp)]
         L.kmx_approx_free.argtypes = [vp]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
@@ -302,6 +306,12 @@ class ApproxResult:
         out = (_view(a.value, nq + 1, np.uint64), _view(b.value, nh, np.uint32), _view(m.value, nh, np.uint8), _view(s.value, nq, np.uint8))
         return tuple(x.copy() for x in out)
 
+    def lengths(self):
+        """kmx_approx_lengths: the window length of every hit (u32, parallel to positions) of a search with edit=True."""
+        p = C.c_void_p()
+        _check(lib().kmx_approx_lengths(self._h, C.byref(p)))
+        return _view(p.value, self.counts()["n_hits"], np.uint32).copy()
+
     def close(self):
         if self._h:
             lib().kmx_approx_free(self._h)
@@ -414,13 +424,14 @@ class Index:
         r._index = self
         return r
 
-    def search_approx(self, qranks, qoff, max_subst):
-        """kmx_search_approx: every window within Hamming distance max_subst (<= APPROX_MAX_SUBST) of each query."""
+    def search_approx(self, qranks, qoff, max_subst, edit=False):
+        """kmx_search_approx: every window within Hamming distance max_subst (<= APPROX_MAX_SUBST) of each query; edit=True
+        (KMX_APPROX_EDIT): every start of a window within that many edits, its distance in `mismatches`, ApproxResult.lengths()."""
         qranks = np.ascontiguousarray(qranks, np.uint8)
         qoff = np.ascontiguousarray(qoff, np.uint64)
         r = ApproxResult()
         _check(lib().kmx_search_approx(self._h, qranks.ctypes.data if qranks.size else None, qoff.ctypes.data,
-                                       qoff.size - 1, int(max_subst), 0, C.byref(r._h)))
+                                       qoff.size - 1, int(max_subst), APPROX_EDIT if edit else 0, C.byref(r._h)))
         return r
 
     def text(self):

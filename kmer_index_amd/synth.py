@@ -101,3 +101,44 @@ def planted_reads(seed: int, text: np.ndarray, nq: int, m: int, sigma: int, max_
             q[sel, col] = ((q[sel, col].astype(np.int64) + shift) % sigma).astype(np.uint8)
     off = np.arange(nq + 1, dtype=np.uint64) * np.uint64(m)
     return np.ascontiguousarray(q.reshape(-1)), off
+
+
+def planted_reads_edit(seed: int, text: np.ndarray, nq: int, m: int, sigma: int, max_edits: int):
+    """nq reads of m letters, each the first m letters of text[s, s + m + max_edits) after a seeded number (0 .. max_edits)
+    of edits of seeded kinds (substitution to a different letter, deletion of a letter, insertion of a seeded letter), the
+    k-th edit inside the k-th of max_edits equal segments of the read: the start s of every read is within that many edits
+    of it.  (qranks[nq*m] u8, qoff[nq+1] u64, starts[nq] i64)"""
+    n = text.size
+    if m + max_edits > n:
+        raise ValueError("planted_reads_edit: m + max_edits > text length")
+    if max_edits > 0 and m < max_edits:
+        raise ValueError("planted_reads_edit: m < max_edits (a read cannot hold max_edits edits)")
+    if max_edits > 0 and sigma < 2:
+        raise ValueError("planted_reads_edit: substitutions need sigma >= 2")
+    z = u64_stream(seed, nq)
+    start = (z % np.uint64(n - m - max_edits + 1)).astype(np.int64)
+    width = m + max_edits + 1
+    cols = np.arange(width, dtype=np.int64)[None, :]
+    rows = np.minimum(start[:, None] + cols, n - 1)
+    q = text[rows].astype(np.uint8)                      # (nq, width): the source and some slack for deletions
+    if max_edits > 0:
+        d = (u64_stream(seed + 1, nq) % np.uint64(max_edits + 1)).astype(np.int64)
+        zz = u64_stream(seed + 2, nq * max_edits).reshape(nq, max_edits)
+        seg = m // max_edits
+        for k in range(max_edits):
+            sel = np.nonzero(d > k)[0]
+            if sel.size == 0:
+                continue
+            col = k * seg + (zz[sel, k] % np.uint64(seg)).astype(np.int64)
+            kind = ((zz[sel, k] >> np.uint64(24)) % np.uint64(3)).astype(np.int64)       # 0 substitution, 1 deletion, 2 insertion
+            shift = 1 + ((zz[sel, k] >> np.uint64(32)) % np.uint64(sigma - 1)).astype(np.int64)
+            sub = q[sel]
+            old = sub[np.arange(sel.size), col].astype(np.int64)
+            # deletion: columns from col on take their right neighbour; insertion: columns behind col take their left one
+            src = cols + ((kind[:, None] == 1) & (cols >= col[:, None])) - ((kind[:, None] == 2) & (cols > col[:, None]))
+            sub = np.take_along_axis(sub, np.clip(src, 0, width - 1), axis=1)
+            changed = kind != 1
+            sub[np.nonzero(changed)[0], col[changed]] = ((old[changed] + shift[changed]) % sigma).astype(np.uint8)
+            q[sel] = sub
+    off = np.arange(nq + 1, dtype=np.uint64) * np.uint64(m)
+    return np.ascontiguousarray(q[:, :m].reshape(-1)), off, start

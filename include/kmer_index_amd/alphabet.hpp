@@ -10,6 +10,7 @@
 // Rank tables follow seqan3 (dna4 ACGT = 0..3, dna5 ACGNT = 0..4, aa20 alphabetical, ...); they
 // only matter for char I/O — the engine sees ranks.  No reference test pins them.
 #pragma once
+#include <array>
 #include <cstddef>
 #include <cstdint>
 #include <string_view>
@@ -53,6 +54,46 @@ namespace kmer::alphabet
     using dna15 = rank_alphabet<15, dna15_chars>;
     using aa20 = rank_alphabet<20, aa20_chars>;
     using aa27 = rank_alphabet<27, aa27_chars>;
+
+    // the IUPAC complement of a nucleotide code (A-T, C-G, R-Y, K-M, B-V, D-H; S, W and N are their own)
+    constexpr char complement_char(char c) noexcept
+    {
+        constexpr std::string_view from = "ACGTRYKMBVDHSWN", to = "TGCAYRMKVBHDSWN";
+        for (std::size_t i = 0; i < from.size(); ++i)
+            if (from[i] == c) return to[i];
+        return c;
+    }
+
+    // The rank-to-rank complement table of a nucleotide alphabet (dna4, dna5, dna15), derived from its character table at
+    // compile time: what kmer_index::search_both_strands and kmx_search_approx_strands take.  Other alphabets have no natural
+    // complement; pass a table of your own there.
+    template<typename alphabet_t>
+    struct complement_ranks_of;
+    template<std::size_t sigma, const char* chars>
+    struct complement_ranks_of<rank_alphabet<sigma, chars>>
+    {
+        static constexpr std::array<std::uint8_t, sigma> make() noexcept
+        {
+            std::array<std::uint8_t, sigma> out{};
+            for (std::size_t r = 0; r < sigma; ++r)
+            {
+                out[r] = std::uint8_t(sigma);               // (no such letter: caught by the static_assert below)
+                for (std::size_t i = 0; i < sigma; ++i)
+                    if (chars[i] == complement_char(chars[r])) out[r] = std::uint8_t(i);
+            }
+            return out;
+        }
+    };
+    template<typename alphabet_t>
+    constexpr auto complement_ranks() noexcept
+    {
+        static_assert(std::is_same_v<alphabet_t, dna4> || std::is_same_v<alphabet_t, dna5> || std::is_same_v<alphabet_t, dna15>,
+                      "complement_ranks: only the nucleotide alphabets have a natural complement");
+        constexpr auto table = complement_ranks_of<alphabet_t>::make();
+        static_assert([&] { for (std::size_t r = 0; r < table.size(); ++r) if (table[r] >= table.size() || table[table[r]] != r) return false; return true; }(),
+                      "complement_ranks: the table is not an involution");
+        return table;
+    }
 } // namespace kmer::alphabet
 
 namespace kmer::detail

@@ -9,6 +9,7 @@
 // is too long (:507-509) or whose sub-k fan-out exceeds 1e7 (:119-122).  All searching happens on
 // the GPU; there is no host search path.  Link with kmer_index_amd/libkmx.so.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <memory>
 #include <mutex>
@@ -446,6 +447,94 @@ namespace kmer
         {
             return std::move(search_edit(std::vector<std::vector<alphabet_t>>{query}, max_edits).front());
         }
+
+        // Both strands (kmx_search_approx_strands): search_approx (edit = false) or search_edit (edit = true) of every query and
+        // of its reverse complement rc(q)[i] = complement[q[m - 1 - i]], per query ordered by (position, strand).  Positions are
+        // offsets into the indexed text; strands[h] is 0 for a hit of q, 1 for a hit of rc(q); lengths is filled for edit only.
+        // The overloads without a table take alphabet::complement_ranks<alphabet_t>() (dna4, dna5, dna15).
+        using complement_table = std::array<std::uint8_t, traits::size>;      // rank to rank, an involution
+        struct strand_hits
+        {
+            std::vector<position_t> positions;
+            std::vector<std::uint8_t> distances;
+            std::vector<std::uint32_t> lengths;
+            std::vector<std::uint8_t> strands;
+        };
+        std::vector<strand_hits> search_both_strands(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit,
+                                                     const complement_table& complement, std::vector<std::uint8_t>& status_out) const
+        {
+            std::vector<std::uint8_t> ranks;
+            std::vector<std::uint64_t> off(queries.size() + 1, 0);
+            for (std::size_t i = 0; i < queries.size(); ++i) off[i + 1] = off[i] + queries[i].size();
+            ranks.reserve(off.back());
+            for (auto const& q : queries)
+                for (auto const& l : q) ranks.push_back(traits::to_rank(l));
+            kmx_approx_result* raw = nullptr;
+            detail::throw_on(kmx_search_approx_strands(_index.get(), ranks.data(), off.data(), queries.size(), std::uint32_t(max_dist),
+                                                       edit ? KMX_APPROX_EDIT : 0u, complement.data(), &raw),
+                             "search_both_strands");
+            std::unique_ptr<kmx_approx_result, void (*)(kmx_approx_result*)> hold(raw, kmx_approx_free);
+            const std::uint64_t* hit_off; const std::uint32_t* positions; const std::uint8_t* distances; const std::uint8_t* status;
+            const std::uint32_t* lengths = nullptr; const std::uint8_t* strands;
+            detail::throw_on(kmx_approx_view(raw, &hit_off, &positions, &distances, &status), "search_both_strands");
+            detail::throw_on(kmx_approx_strands(raw, &strands), "search_both_strands");
+            if (edit) detail::throw_on(kmx_approx_lengths(raw, &lengths), "search_both_strands");
+            status_out.assign(status, status + queries.size());
+            std::vector<strand_hits> out(queries.size());
+            for (std::size_t i = 0; i < queries.size(); ++i)
+            {
+                out[i].positions.assign(positions + hit_off[i], positions + hit_off[i + 1]);
+                out[i].distances.assign(distances + hit_off[i], distances + hit_off[i + 1]);
+                out[i].strands.assign(strands + hit_off[i], strands + hit_off[i + 1]);
+                if (edit) out[i].lengths.assign(lengths + hit_off[i], lengths + hit_off[i + 1]);
+            }
+            return out;
+        }
+
+        // with search_approx's error behaviour; the error's results carry positions and distances (as mismatches) of the others
+        std::vector<strand_hits> search_both_strands(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit,
+                                                     const complement_table& complement) const
+        {
+            std::vector<std::uint8_t> status;
+            std::vector<strand_hits> out = search_both_strands(queries, max_dist, edit, complement, status);
+            for (std::size_t i = 0; i < status.size(); ++i)
+            {
+                if (status[i] == KMX_Q_OK) continue;
+                const std::string what = query_status_message(status[i]);
+                std::vector<approx_hits> others(out.size());
+                for (std::size_t j = 0; j < out.size(); ++j)
+                {
+                    others[j].positions = std::move(out[j].positions);
+                    others[j].mismatches = std::move(out[j].distances);
+                }
+                throw approx_query_error(what, i, std::move(status), std::move(others));
+            }
+            return out;
+        }
+
+        strand_hits search_both_strands(const std::vector<alphabet_t>& query, std::size_t max_dist, bool edit,
+                                        const complement_table& complement) const
+        {
+            return std::move(search_both_strands(std::vector<std::vector<alphabet_t>>{query}, max_dist, edit, complement).front());
+        }
+
+        std::vector<strand_hits> search_both_strands(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit,
+                                                     std::vector<std::uint8_t>& status_out) const
+        {
+            return search_both_strands(queries, max_dist, edit, natural_complement(), status_out);
+        }
+
+        std::vector<strand_hits> search_both_strands(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit = false) const
+        {
+            return search_both_strands(queries, max_dist, edit, natural_complement());
+        }
+
+        strand_hits search_both_strands(const std::vector<alphabet_t>& query, std::size_t max_dist, bool edit = false) const
+        {
+            return search_both_strands(query, max_dist, edit, natural_complement());
+        }
+
+        static constexpr complement_table natural_complement() { return alphabet::complement_ranks<alphabet_t>(); }
 
         // the text, reconstructed on the device from the index (kmx_index_text; an extension, no reference interface)
         std::vector<alphabet_t> text() const

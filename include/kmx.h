@@ -318,7 +318,8 @@ void kmx_result_free(kmx_result* r);
  * bounds); the views always cover the whole batch.  Each call
  * runs on a stream and device buffers of its own: concurrent calls on one index are safe.  On an index with several
  * replicas the call runs on the first replica (batches are not sharded over replicas).  flags: 0 or KMX_APPROX_EDIT; any
- * other bit is refused.
+ * other bit is refused.  The call searches the strand the index was built from; kmx_search_approx_strands (below)
+ * searches the reverse complement of every query as well.
  *
  * KMX_APPROX_EDIT (a caller detects the capability by the macro; KMX_VERSION is unchanged): edit distance with unit costs
  * (substitution, insertion, deletion) in place of Hamming distance, max_subst read as the bound e on edits.  A start offset
@@ -349,6 +350,41 @@ kmx_status kmx_approx_view(kmx_approx_result* r, const uint64_t** hit_off, const
  *   KMX_ERR_INVALID_ARGUMENT on the result of a call without the flag.  Valid until kmx_approx_free. */
 kmx_status kmx_approx_lengths(kmx_approx_result* r, const uint32_t** lengths);
 void kmx_approx_free(kmx_approx_result* r);
+
+/* ---- both strands: kmx_search_approx on every query AND on its reverse complement, in one call (an extension; a caller
+ *      detects the capability by the macro KMX_APPROX_BOTH_STRANDS, KMX_VERSION is unchanged).
+ *
+ * Complement table.  The engine knows ranks, not letters, so the caller supplies `complement`: sigma entries that map rank
+ * to rank.  It must be an involution on [0, sigma): complement[r] < sigma and complement[complement[r]] == r.  A NULL table,
+ * one that is not an involution, or an entry >= sigma returns KMX_ERR_INVALID_ARGUMENT.  The identity is allowed: it
+ * searches the plain reversal.
+ * Reverse complement.  For a query q of m letters, rc(q)[i] = complement[q[m - 1 - i]].
+ * What is reported.  Everything kmx_search_approx with the same max_subst and flags (0 or KMX_APPROX_EDIT; any other bit is
+ * refused) reports for q, tagged strand 0, and everything that call reports for rc(q), tagged strand 1.  Offsets are always
+ * offsets into the indexed (forward) text: for a reverse hit, the start of the window that rc(q) matches; its mismatch count
+ * or distance, and with KMX_APPROX_EDIT its length L(p), are those of rc(q) at that start.
+ * Order.  Per query the hits are strictly ascending in (position, strand): an offset may appear twice, forward first.
+ * Nothing is deduplicated across strands: a query equal to its own reverse complement reports every hit on both.
+ * Statuses and their precedence are those of kmx_search_approx.  A query is served only if both strands are: it takes the
+ * forward strand's status unless that is KMX_Q_OK, otherwise the reverse strand's (only KMX_Q_SUBK_FANOUT can differ between
+ * the two).  Every status but KMX_Q_OK comes without hits on either strand.
+ * Accessors.  kmx_approx_counts (n_hits and n_candidates cover both strands), kmx_approx_view and, for a KMX_APPROX_EDIT
+ * call, kmx_approx_lengths work on the result as on one of kmx_search_approx; kmx_approx_strands gives strands[n_hits]
+ * (uint8, parallel to positions: 0 = forward, 1 = reverse; valid until kmx_approx_free) and returns
+ * KMX_ERR_INVALID_ARGUMENT on a result of plain kmx_search_approx.
+ * Chunking.  The budgets and the two environment variables work as for kmx_search_approx; a query and its reverse complement
+ * are never split across chunks, KMX_APPROX_CHUNK_PIECES bounds the pieces of both strands together (2 (e + 1) per query),
+ * and a query counts the piece hits of both strands against the candidate budget.
+ * The reads cross to the device once; the reverse complements are made there, both strands go through the pipeline of
+ * kmx_search_approx as one batch of 2 nq queries and the two hit lists of a query are merged on the device.  Concurrent calls
+ * on one index are safe; the call runs on the first replica.  With e = 0 the strand-0 positions of a query are those
+ * kmx_search_batch gives for q and the strand-1 positions those it gives for rc(q), for every query that call answers with
+ * KMX_Q_OK. */
+#define KMX_APPROX_BOTH_STRANDS 1
+kmx_status kmx_search_approx_strands(const kmx_index* index, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq,
+                                     uint32_t max_subst, uint32_t flags, const uint8_t* complement,
+                                     kmx_approx_result** out);
+kmx_status kmx_approx_strands(kmx_approx_result* r, const uint8_t** strands);
 
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.

@@ -10,7 +10,8 @@
 // so nothing needs deduplicating).  The survivors of each (query, piece) list stay ascending; k_approx_compact packs them
 // in candidate order and k_approx_merge places each at its rank among the survivors of the query's other lists.
 // With KMX_APPROX_EDIT (edit distance: insertions and deletions too) the piece search is the same and a second path follows
-// it: see "edit distance" below.
+// it: see "edit distance" below.  kmx_search_approx_strands runs every query and its reverse complement through the same
+// pipeline as one batch of twice the queries: see "both strands" below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -92,7 +93,8 @@ struct kmx_approx_result {
     uint64_t nq = 0, n_hits = 0, n_candidates = 0;
     uint32_t n_chunks = 0;
     bool edit = false;                                   // KMX_APPROX_EDIT: mismatches holds distances, lengths is filled
-    PinnedArr hit_off, positions, mismatches, status, lengths;
+    bool strands = false;                                // kmx_search_approx_strands: strand is filled
+    PinnedArr hit_off, positions, mismatches, status, lengths, strand;
 };
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -687,6 +689,108 @@ template <uint32_t E, uint32_t W> struct LaunchEditLengths {
 };
 
 // ------------------------------------------------------------------------------------------------------------------------
+// both strands (kmx_search_approx_strands): every query goes through the pipeline above twice, as itself and as its reverse
+// complement rc(q)[r] = comp[q[m - 1 - r]], inside ONE internal batch of twice the queries: internal query 2i is q_i, 2i + 1
+// is rc(q_i), their letters side by side at 2 * qoff[i] and 2 * qoff[i] + m.  The uploaded letters are read once
+// (k_strand_prep), the two hit lists of a pair are interleaved by (position, strand) on the device (k_strand_merge).
+
+// One thread per public query: what k_approx_prep does, for both internal queries of the pair.  The statuses a query takes
+// from itself alone are those of its reverse complement too (the same length; comp maps the alphabet onto itself).
+__global__ __launch_bounds__(kBlock) void k_strand_prep(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ qoff, uint64_t nq,
+                                                        const uint8_t* __restrict__ comp, uint32_t sigma, uint32_t e, uint32_t range,
+                                                        uint32_t w, uint8_t* __restrict__ qr, uint64_t* __restrict__ iqoff,
+                                                        uint64_t* __restrict__ poff, uint8_t* __restrict__ qstat,
+                                                        uint64_t* __restrict__ qwords)
+{
+    const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= nq) return;
+    const uint64_t a = qoff[i], m = qoff[i + 1] - a;
+    const uint64_t a0 = 2 * a, a1 = a0 + m;
+    const uint32_t L = 64 / w;
+    uint8_t st = KMX_Q_OK;
+    if (m == 0) st = KMX_Q_EMPTY_QUERY;
+    else if (m <= e) st = KMX_Q_TOO_SHORT;
+    else if ((m + e) / (e + 1) >= range) st = KMX_Q_TOO_LONG;
+    if (st == KMX_Q_OK) {
+        uint64_t* qw0 = qwords + a0 / L + 2 * i;
+        uint64_t* qw1 = qwords + a1 / L + 2 * i + 1;
+        uint64_t v0 = 0, v1 = 0;
+        for (uint64_t r = 0; r < m; ++r) {
+            const uint32_t c0 = raw[a + r], cb = raw[a + m - 1 - r];
+            const uint32_t c1 = comp[cb];
+            if (c0 >= sigma) st = KMX_Q_BAD_RANK;
+            qr[a0 + r] = uint8_t(c0);
+            qr[a1 + r] = uint8_t(c1);
+            v0 |= uint64_t(c0 & ((1u << w) - 1)) << ((r % L) * w);
+            v1 |= uint64_t(c1 & ((1u << w) - 1)) << ((r % L) * w);
+            if (r % L == L - 1 || r + 1 == m) { qw0[r / L] = v0; qw1[r / L] = v1; v0 = 0; v1 = 0; }
+        }
+    }
+    qstat[2 * i] = st;
+    qstat[2 * i + 1] = st;
+    iqoff[2 * i] = a0;
+    iqoff[2 * i + 1] = a1;
+    for (uint32_t j = 0; j <= e; ++j) {
+        const uint64_t o = piece_start(m, e, j);
+        poff[2 * i * (e + 1) + j] = a0 + o;
+        poff[(2 * i + 1) * (e + 1) + j] = a1 + o;
+    }
+    if (i + 1 == nq) {
+        iqoff[2 * nq] = 2 * qoff[nq];
+        poff[2 * nq * (e + 1)] = 2 * qoff[nq];
+    }
+    if (st != KMX_Q_OK)                                   // (no letter of the pair costs the exact search anything)
+        for (uint64_t r = 0; r < 2 * m; ++r) qr[a0 + r] = sigma < 256 ? uint8_t(255) : raw[a + r % m];
+}
+
+// A pair is served only if both strands are: the forward strand's status unless that is KMX_Q_OK, else the reverse strand's.
+// Runs behind k_approx_status and in front of the verification, which skips every query that is not KMX_Q_OK.
+__global__ __launch_bounds__(kBlock) void k_strand_status(uint8_t* __restrict__ qstat, uint64_t n_pairs, uint8_t* __restrict__ pair_stat)
+{
+    const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= n_pairs) return;
+    const uint8_t s0 = qstat[2 * i], s1 = qstat[2 * i + 1];
+    const uint8_t s = s0 != KMX_Q_OK ? s0 : s1;
+    qstat[2 * i] = s;
+    qstat[2 * i + 1] = s;
+    pair_stat[i] = s;
+}
+
+// first index in [lo, hi) with a[i] > x
+__device__ __forceinline__ uint64_t upper_u32(const uint32_t* __restrict__ a, uint64_t lo, uint64_t hi, uint32_t x)
+{
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (a[mid] <= x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// One thread per internal hit t of internal query I (ihit_off[I] <= t < ihit_off[I + 1]): it goes to the pair's first slot +
+// its rank in its own list + the hits of the partner list in front of it in (position, strand) order: those below its
+// position for a forward hit, those at or below it for a reverse hit.  Both lists are strictly ascending.  Threads
+// 0 .. n_pairs also write the public hit_off (= the internal one at even indexes).  len_in is NULL for Hamming results.
+__global__ __launch_bounds__(kBlock) void k_strand_merge(const uint64_t* __restrict__ ihit_off, uint64_t n_pairs, uint64_t n_s,
+                                                         const uint32_t* __restrict__ pos_in, const uint8_t* __restrict__ d_in,
+                                                         const uint32_t* __restrict__ len_in, uint32_t* __restrict__ pos_out,
+                                                         uint8_t* __restrict__ d_out, uint32_t* __restrict__ len_out,
+                                                         uint8_t* __restrict__ strand_out, uint64_t* __restrict__ hit_off)
+{
+    const uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (t <= n_pairs) hit_off[t] = ihit_off[2 * t];
+    if (t >= n_s) return;
+    const uint64_t I = piece_of(ihit_off, 0, 2 * n_pairs, t);
+    const uint64_t lo = ihit_off[I ^ 1], hi = ihit_off[(I ^ 1) + 1];
+    const uint32_t p = pos_in[t];
+    const uint64_t before = ((I & 1) ? upper_u32(pos_in, lo, hi, p) : lower_u32(pos_in, lo, hi, p)) - lo;
+    const uint64_t dest = ihit_off[I & ~uint64_t(1)] + (t - ihit_off[I]) + before;
+    pos_out[dest] = p;
+    d_out[dest] = d_in[t];
+    if (len_in) len_out[dest] = len_in[t];
+    strand_out[dest] = uint8_t(I & 1);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
 // host side
 
 void kmx::packed_text_release(PackedText* t)
@@ -859,21 +963,39 @@ kmx_status kmx_index_text(const kmx_index* index, uint8_t* out_ranks, uint64_t n
     return KMX_OK;
 }
 
-kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq, uint32_t max_subst,
-                             uint32_t flags, kmx_approx_result** out)
+} // extern "C"
+
+// kmx_search_approx (complement == NULL) and kmx_search_approx_strands (the table given): S = 1 or 2 internal queries per
+// query of the caller.  `fn` names the entry point in error messages.
+static kmx_status approx_search(const char* fn, const kmx_index* index, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq,
+                                uint32_t max_subst, uint32_t flags, const uint8_t* complement, kmx_approx_result** out)
 {
-    if (!index || !out) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: NULL argument");
-    if (max_subst > KMX_APPROX_MAX_SUBST) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: max_subst > KMX_APPROX_MAX_SUBST");
-    if (flags & ~uint32_t(KMX_APPROX_EDIT)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: unknown flag bits");
-    if (nq && !qoff) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: NULL query offsets");
-    if (nq && qoff[0] != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: qoff[0] must be 0");
+    const std::string who = std::string(fn) + ": ";
+    if (max_subst > KMX_APPROX_MAX_SUBST) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "max_subst > KMX_APPROX_MAX_SUBST");
+    if (flags & ~uint32_t(KMX_APPROX_EDIT)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "unknown flag bits");
+    if (nq && !qoff) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "NULL query offsets");
+    if (nq && qoff[0] != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "qoff[0] must be 0");
     for (uint64_t i = 0; i < nq; ++i)
-        if (qoff[i + 1] < qoff[i]) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: qoff must be non-decreasing");
-    if (nq && !qranks && qoff[nq] != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: NULL query letters");
+        if (qoff[i + 1] < qoff[i]) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "qoff must be non-decreasing");
+    if (nq && !qranks && qoff[nq] != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "NULL query letters");
     *out = nullptr;
     const kmx::IndexAccess A = kmx::index_access(index);
     if (A.broken) return kmx::set_error(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
     const uint32_t e = max_subst, E1 = e + 1;
+    const uint32_t S = complement ? 2u : 1u;             // internal queries per query (both strands: q and rc(q))
+    uint8_t comp[256];
+    if (complement) {
+        for (uint32_t r = 0; r < 256; ++r) comp[r] = uint8_t(r);      // (letters outside the alphabet: the pair is KMX_Q_BAD_RANK)
+        for (uint32_t r = 0; r < A.sigma && r < 256; ++r)             // every entry's range first: an entry outside the alphabet is
+            if (complement[r] >= A.sigma)                             // reported as that, whichever rank maps to it
+                return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "complement[" + std::to_string(r) + "] is outside the alphabet");
+        for (uint32_t r = 0; r < A.sigma && r < 256; ++r) {
+            const uint32_t c = complement[r];
+            if (complement[c] != r)
+                return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "the complement table is not an involution at rank " + std::to_string(r));
+            comp[r] = uint8_t(c);
+        }
+    }
     uint64_t budget = kDefaultBudget, max_pieces = kMaxPieces;
     if (const char* env = getenv("KMX_APPROX_CHUNK_CANDIDATES")) { const long long v = atoll(env); if (v > 0) budget = uint64_t(v); }
     if (const char* env = getenv("KMX_APPROX_CHUNK_PIECES")) { const long long v = atoll(env); if (v > 0) max_pieces = std::min(uint64_t(v), kMaxPieces); }
@@ -893,20 +1015,27 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
     std::unique_ptr<kmx_approx_result> R(new kmx_approx_result());
     R->nq = nq;
     R->edit = edit;
-    if (edit && !R->lengths.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_search_approx: page-locked host memory");
+    R->strands = complement != nullptr;
+    if (complement && !R->strand.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
+    if (edit && !R->lengths.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
     if (!R->hit_off.grow((nq + 1) * 8) || !R->status.grow(nq + 1) || !R->positions.grow(64) || !R->mismatches.grow(64))
-        return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_search_approx: page-locked host memory");
+        return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
     R->hit_off.as<uint64_t>()[0] = 0;
 
     Buf d_qr, d_qoff, d_poff, d_qstat, d_qwords, d_qcand, d_keep, d_bcount, d_bsum, d_bscan, d_total, d_spos, d_spiece, d_smm,
         d_hit_off, d_opos, d_omm;
+    Buf d_raw, d_loc, d_comp, d_pair_stat, d_pub_off, d_mpos, d_md, d_mlen, d_mstrand;      // both strands only
+    if (complement) {
+        AX_TRY(d_comp.ensure(256));
+        AX_TRY(hipMemcpyAsync(d_comp.p, comp, 256, hipMemcpyHostToDevice, s));
+    }
     EditBufs eb;
     PinnedArr h_qcand, h_total;
-    if (!h_total.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_search_approx: page-locked host memory");
+    if (!h_total.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
     ResultGuard pres;
     pres.s = s;
     std::vector<uint64_t> loc;
-    const uint64_t chunk_q = std::max<uint64_t>(max_pieces / E1, 1);
+    const uint64_t chunk_q = std::max<uint64_t>(max_pieces / (uint64_t(E1) * S), 1);      // (a pair is never split)
 
     for (uint64_t Q0 = 0; Q0 < nq;) {
         const uint64_t Q1 = std::min(nq, Q0 + chunk_q), nqc = Q1 - Q0;
@@ -914,26 +1043,38 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
         // the chunk's letters (a copy the prep kernel may overwrite) and offsets, rebased to the chunk
         loc.resize(nqc + 1);
         for (uint64_t i = 0; i <= nqc; ++i) loc[i] = qoff[Q0 + i] - l0;
-        AX_TRY(d_qr.ensure(n_letters + 64));
-        AX_TRY(d_qoff.ensure((nqc + 1) * 8));
-        AX_TRY(d_poff.ensure((nqc * E1 + 1) * 8));
-        AX_TRY(d_qstat.ensure(nqc + 16));
-        AX_TRY(d_qwords.ensure((n_letters / L + nqc + 2) * 8));
+        const uint64_t nqi = nqc * S;                        // internal queries of the chunk
+        AX_TRY(d_qr.ensure(n_letters * S + 64));
+        AX_TRY(d_qoff.ensure((nqi + 1) * 8));
+        AX_TRY(d_poff.ensure((nqi * E1 + 1) * 8));
+        AX_TRY(d_qstat.ensure(nqi + 16));
+        AX_TRY(d_qwords.ensure((n_letters * S / L + nqi + 2) * 8));
         AX_TRY(d_qcand.ensure((nqc + 1) * 8));
-        if (n_letters) AX_TRY(hipMemcpyAsync(d_qr.p, qranks + l0, n_letters, hipMemcpyHostToDevice, s));
-        AX_TRY(hipMemcpyAsync(d_qoff.p, loc.data(), (nqc + 1) * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_approx_prep, dim3(grid_for(nqc, kBlock)), dim3(kBlock), 0, s, d_qr.as<uint8_t>(), d_qoff.as<uint64_t>(), nqc, A.sigma, e,
-                           A.range, w, d_poff.as<uint64_t>(), d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>());
+        if (S == 1) {
+            if (n_letters) AX_TRY(hipMemcpyAsync(d_qr.p, qranks + l0, n_letters, hipMemcpyHostToDevice, s));
+            AX_TRY(hipMemcpyAsync(d_qoff.p, loc.data(), (nqc + 1) * 8, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_approx_prep, dim3(grid_for(nqc, kBlock)), dim3(kBlock), 0, s, d_qr.as<uint8_t>(), d_qoff.as<uint64_t>(), nqc, A.sigma,
+                               e, A.range, w, d_poff.as<uint64_t>(), d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>());
+        } else {
+            AX_TRY(d_raw.ensure(n_letters + 64));
+            AX_TRY(d_loc.ensure((nqc + 1) * 8));
+            AX_TRY(d_pair_stat.ensure(nqc + 16));
+            if (n_letters) AX_TRY(hipMemcpyAsync(d_raw.p, qranks + l0, n_letters, hipMemcpyHostToDevice, s));
+            AX_TRY(hipMemcpyAsync(d_loc.p, loc.data(), (nqc + 1) * 8, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_strand_prep, dim3(grid_for(nqc, kBlock)), dim3(kBlock), 0, s, d_raw.as<uint8_t>(), d_loc.as<uint64_t>(), nqc,
+                               d_comp.as<uint8_t>(), A.sigma, e, A.range, w, d_qr.as<uint8_t>(), d_qoff.as<uint64_t>(), d_poff.as<uint64_t>(),
+                               d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>());
+        }
         AX_TRY(hipGetLastError());
-        // candidates per query: the pieces through the exact search, counts only
-        st = kmx_search_batch_device(index, d_qr.p, d_poff.p, nqc * E1, KMX_SEARCH_COUNT_ONLY, s, &pres.r);
+        // candidates per query (both strands: per pair): the pieces through the exact search, counts only
+        st = kmx_search_batch_device(index, d_qr.p, d_poff.p, nqi * E1, KMX_SEARCH_COUNT_ONLY, s, &pres.r);
         if (st != KMX_OK) return st;
         const uint64_t* d_phit = nullptr;
         st = kmx_result_view_device(pres.r, &d_phit, nullptr, nullptr);
         if (st != KMX_OK) return st;
-        hipLaunchKernelGGL(k_approx_query_cands, dim3(grid_for(nqc + 1, kBlock)), dim3(kBlock), 0, s, d_phit, nqc, e, d_qcand.as<uint64_t>());
+        hipLaunchKernelGGL(k_approx_query_cands, dim3(grid_for(nqc + 1, kBlock)), dim3(kBlock), 0, s, d_phit, nqc, S * E1 - 1, d_qcand.as<uint64_t>());
         AX_TRY(hipGetLastError());
-        if (!h_qcand.grow((nqc + 1) * 8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_search_approx: page-locked host memory");
+        if (!h_qcand.grow((nqc + 1) * 8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
         AX_TRY(hipMemcpyAsync(h_qcand.p, d_qcand.p, (nqc + 1) * 8, hipMemcpyDeviceToHost, s));
         AX_TRY(hipStreamSynchronize(s));
         const uint64_t* qc = h_qcand.as<uint64_t>();
@@ -942,9 +1083,10 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
             // the longest run of queries whose candidates fit the budget (at least one query)
             uint64_t b = uint64_t(std::upper_bound(qc + a + 1, qc + nqc + 1, qc[a] + budget) - qc) - 1;
             b = std::max(b, a + 1);
-            const uint64_t np = (b - a) * E1;
+            const uint64_t nqv = (b - a) * S, q0 = a * S;    // the chunk's internal queries [q0, q0 + nqv)
+            const uint64_t np = nqv * E1;
             R->n_chunks += 1;
-            st = kmx_search_batch_device(index, d_qr.p, d_poff.as<uint64_t>() + a * E1, np, KMX_SEARCH_DEFAULT, s, &pres.r);
+            st = kmx_search_batch_device(index, d_qr.p, d_poff.as<uint64_t>() + q0 * E1, np, KMX_SEARCH_DEFAULT, s, &pres.r);
             if (st != KMX_OK) return st;
             const uint64_t* phit = nullptr; const uint32_t* ppos = nullptr; const uint8_t* pstat = nullptr;
             st = kmx_result_view_device(pres.r, &phit, &ppos, &pstat);
@@ -953,14 +1095,19 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
             st = kmx_result_counts(pres.r, nullptr, &n_cand, nullptr, nullptr, nullptr, nullptr);
             if (st != KMX_OK) return st;
             R->n_candidates += n_cand;
-            hipLaunchKernelGGL(k_approx_status, dim3(grid_for(b - a, kBlock)), dim3(kBlock), 0, s, pstat, b - a, e, d_qstat.as<uint8_t>() + a);
+            hipLaunchKernelGGL(k_approx_status, dim3(grid_for(nqv, kBlock)), dim3(kBlock), 0, s, pstat, nqv, e, d_qstat.as<uint8_t>() + q0);
             AX_TRY(hipGetLastError());
+            if (S == 2) {
+                hipLaunchKernelGGL(k_strand_status, dim3(grid_for(b - a, kBlock)), dim3(kBlock), 0, s, d_qstat.as<uint8_t>() + q0, b - a,
+                                   d_pair_stat.as<uint8_t>() + a);
+                AX_TRY(hipGetLastError());
+            }
             uint64_t n_s = 0;
-            AX_TRY(d_hit_off.ensure((b - a + 1) * 8));
+            AX_TRY(d_hit_off.ensure((nqv + 1) * 8));
             if (edit) {
                 if (n_cand) {
-                    EditArgs V{phit, ppos, n_cand, np, d_qoff.as<uint64_t>(), a, d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>(), text, A.n, e, nullptr, nullptr};
-                    st = edit_chunk(s, V, w, b - a, eb, h_total, d_hit_off, d_opos, d_omm, &n_s);
+                    EditArgs V{phit, ppos, n_cand, np, d_qoff.as<uint64_t>(), q0, d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>(), text, A.n, e, nullptr, nullptr};
+                    st = edit_chunk(s, V, w, nqv, eb, h_total, d_hit_off, d_opos, d_omm, &n_s);
                     if (st != KMX_OK) return st;
                 }
             } else if (n_cand) {
@@ -970,7 +1117,7 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
                 AX_TRY(d_bsum.ensure(kmx::scan_blocks(nb) * 8 + 16));
                 AX_TRY(d_bscan.ensure((nb + 1) * 8));
                 AX_TRY(d_total.ensure(16));
-                VerifyArgs V{phit, ppos, n_cand, np, d_qoff.as<uint64_t>(), a, d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>(), text, A.n, w, e,
+                VerifyArgs V{phit, ppos, n_cand, np, d_qoff.as<uint64_t>(), q0, d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>(), text, A.n, w, e,
                              d_keep.as<uint8_t>(), d_bcount.as<uint32_t>()};
                 hipLaunchKernelGGL(k_approx_verify, dim3(unsigned(nb)), dim3(kBlock), 0, s, V);
                 AX_TRY(hipGetLastError());
@@ -994,25 +1141,46 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
                 }
             }
             if (n_s && !edit) {                                  // (edit_chunk wrote the chunk's hit_off itself)
-                hipLaunchKernelGGL(k_approx_hit_off, dim3(grid_for(b - a + 1, kBlock)), dim3(kBlock), 0, s, d_spiece.as<uint32_t>(), n_s, b - a, e,
+                hipLaunchKernelGGL(k_approx_hit_off, dim3(grid_for(nqv + 1, kBlock)), dim3(kBlock), 0, s, d_spiece.as<uint32_t>(), n_s, nqv, e,
                                    d_hit_off.as<uint64_t>());
                 AX_TRY(hipGetLastError());
             } else if (!n_s) {
-                AX_TRY(hipMemsetAsync(d_hit_off.p, 0, (b - a + 1) * 8, s));
+                AX_TRY(hipMemsetAsync(d_hit_off.p, 0, (nqv + 1) * 8, s));
+            }
+            // what goes to the host: the chunk's arrays as they are, or (both strands) each pair's two lists merged
+            const void *o_hit_off = d_hit_off.p, *o_pos = d_opos.p, *o_d = d_omm.p, *o_len = eb.olen.p, *o_stat = d_qstat.as<uint8_t>() + a;
+            if (S == 2) {
+                AX_TRY(d_pub_off.ensure((b - a + 1) * 8));
+                if (n_s) {
+                    AX_TRY(d_mpos.ensure(n_s * 4));
+                    AX_TRY(d_md.ensure(n_s));
+                    AX_TRY(d_mstrand.ensure(n_s));
+                    if (edit) AX_TRY(d_mlen.ensure(n_s * 4));
+                    hipLaunchKernelGGL(k_strand_merge, dim3(grid_for(std::max(n_s, b - a + 1), kBlock)), dim3(kBlock), 0, s, d_hit_off.as<uint64_t>(),
+                                       b - a, n_s, d_opos.as<uint32_t>(), d_omm.as<uint8_t>(), edit ? eb.olen.as<uint32_t>() : (const uint32_t*)nullptr,
+                                       d_mpos.as<uint32_t>(), d_md.as<uint8_t>(), d_mlen.as<uint32_t>(), d_mstrand.as<uint8_t>(),
+                                       d_pub_off.as<uint64_t>());
+                    AX_TRY(hipGetLastError());
+                } else {
+                    AX_TRY(hipMemsetAsync(d_pub_off.p, 0, (b - a + 1) * 8, s));
+                }
+                o_hit_off = d_pub_off.p; o_pos = d_mpos.p; o_d = d_md.p; o_len = d_mlen.p; o_stat = d_pair_stat.as<uint8_t>() + a;
             }
             // this chunk's part of the result to the host arrays
             const uint64_t q_at = Q0 + a, h_at = R->n_hits;
             if (!R->positions.grow((h_at + n_s) * 4 + 64) || !R->mismatches.grow(h_at + n_s + 64))
-                return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_search_approx: page-locked host memory");
+                return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
             if (edit && !R->lengths.grow((h_at + n_s) * 4 + 64))
-                return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_search_approx: page-locked host memory");
+                return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
+            if (S == 2 && !R->strand.grow(h_at + n_s + 64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
             uint64_t* ho = R->hit_off.as<uint64_t>() + q_at;     // (ho[0], the previous chunk's end, is rewritten with the same value)
-            AX_TRY(hipMemcpyAsync(ho, d_hit_off.p, (b - a + 1) * 8, hipMemcpyDeviceToHost, s));
-            AX_TRY(hipMemcpyAsync(R->status.as<uint8_t>() + q_at, d_qstat.as<uint8_t>() + a, b - a, hipMemcpyDeviceToHost, s));
+            AX_TRY(hipMemcpyAsync(ho, o_hit_off, (b - a + 1) * 8, hipMemcpyDeviceToHost, s));
+            AX_TRY(hipMemcpyAsync(R->status.as<uint8_t>() + q_at, o_stat, b - a, hipMemcpyDeviceToHost, s));
             if (n_s) {
-                AX_TRY(hipMemcpyAsync(R->positions.as<uint32_t>() + h_at, d_opos.p, n_s * 4, hipMemcpyDeviceToHost, s));
-                AX_TRY(hipMemcpyAsync(R->mismatches.as<uint8_t>() + h_at, d_omm.p, n_s, hipMemcpyDeviceToHost, s));
-                if (edit) AX_TRY(hipMemcpyAsync(R->lengths.as<uint32_t>() + h_at, eb.olen.p, n_s * 4, hipMemcpyDeviceToHost, s));
+                AX_TRY(hipMemcpyAsync(R->positions.as<uint32_t>() + h_at, o_pos, n_s * 4, hipMemcpyDeviceToHost, s));
+                AX_TRY(hipMemcpyAsync(R->mismatches.as<uint8_t>() + h_at, o_d, n_s, hipMemcpyDeviceToHost, s));
+                if (edit) AX_TRY(hipMemcpyAsync(R->lengths.as<uint32_t>() + h_at, o_len, n_s * 4, hipMemcpyDeviceToHost, s));
+                if (S == 2) AX_TRY(hipMemcpyAsync(R->strand.as<uint8_t>() + h_at, d_mstrand.p, n_s, hipMemcpyDeviceToHost, s));
             }
             AX_TRY(hipStreamSynchronize(s));
             for (uint64_t i = 0; i <= b - a; ++i) ho[i] += h_at;
@@ -1024,6 +1192,23 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
     if (R->n_chunks == 0) R->n_chunks = 1;
     *out = R.release();
     return KMX_OK;
+}
+
+extern "C" {
+
+kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq, uint32_t max_subst,
+                             uint32_t flags, kmx_approx_result** out)
+{
+    if (!index || !out) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: NULL argument");
+    return approx_search("kmx_search_approx", index, qranks, qoff, nq, max_subst, flags, nullptr, out);
+}
+
+kmx_status kmx_search_approx_strands(const kmx_index* index, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq, uint32_t max_subst,
+                                     uint32_t flags, const uint8_t* complement, kmx_approx_result** out)
+{
+    if (!index || !out) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx_strands: NULL argument");
+    if (!complement) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx_strands: NULL complement table");
+    return approx_search("kmx_search_approx_strands", index, qranks, qoff, nq, max_subst, flags, complement, out);
 }
 
 kmx_status kmx_approx_counts(const kmx_approx_result* r, uint64_t* nq, uint64_t* n_hits, uint64_t* n_candidates, uint32_t* n_chunks)
@@ -1052,6 +1237,14 @@ kmx_status kmx_approx_lengths(kmx_approx_result* r, const uint32_t** lengths)
     if (!r) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_approx_lengths: result is NULL");
     if (!r->edit) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_approx_lengths: the result is not one of a KMX_APPROX_EDIT call");
     if (lengths) *lengths = r->lengths.as<uint32_t>();
+    return KMX_OK;
+}
+
+kmx_status kmx_approx_strands(kmx_approx_result* r, const uint8_t** strands)
+{
+    if (!r) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_approx_strands: result is NULL");
+    if (!r->strands) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_approx_strands: the result is not one of kmx_search_approx_strands");
+    if (strands) *strands = r->strand.as<uint8_t>();
     return KMX_OK;
 }
 

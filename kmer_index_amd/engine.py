@@ -29,7 +29,7 @@ EXPORTS = [
     "kmx_index_devices", "kmx_result_parts", "kmx_result_part_view_device",
     "kmx_index_bucket_host", "kmx_index_levels", "kmx_result_gather_device",
     "kmx_search_approx", "kmx_approx_counts", "kmx_approx_view", "kmx_approx_free", "kmx_index_text",
-    "kmx_approx_lengths",
+    "kmx_approx_lengths", "kmx_search_approx_strands", "kmx_approx_strands",
 ]
 
 
@@ -126,6 +126,10 @@ def lib():
         L.kmx_approx_lengths.restype = C.c_int
         L.kmx_approx_lengths.argtypes = [vp, P(vp)]
         L.kmx_approx_free.argtypes = [vp]
+        L.kmx_search_approx_strands.restype = C.c_int
+        L.kmx_search_approx_strands.argtypes = [vp, vp, vp, u64, u32, u32, vp, P(vp)]
+        L.kmx_approx_strands.restype = C.c_int
+        L.kmx_approx_strands.argtypes = [vp, P(vp)]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -160,6 +164,18 @@ def _set_devices(o, devices):
 def _check(st):
     if st != 0:
         raise KmxError(st, lib().kmx_last_error().decode())
+
+
+# rank orders of include/kmer_index_amd/alphabet.hpp and the complement of each letter (dna15: the IUPAC codes)
+_COMPLEMENT_CHARS = {4: ("ACGT", "TGCA"), 5: ("ACGNT", "TGCNA"), 15: ("ABCDGHKMNRSTVWY", "TVGHCDMKNYSABWR")}
+
+
+def complement_table(sigma):
+    """The rank-to-rank complement table (uint8[sigma]) of dna4 (ACGT), dna5 (ACGNT, N maps to N) or dna15 (IUPAC)."""
+    if sigma not in _COMPLEMENT_CHARS:
+        raise ValueError(f"complement_table: no natural complement for an alphabet of {sigma} letters; pass a table")
+    chars, comp = _COMPLEMENT_CHARS[sigma]
+    return np.array([chars.index(c) for c in comp], np.uint8)
 
 
 def fast_pow(base, exp):
@@ -312,6 +328,13 @@ class ApproxResult:
         _check(lib().kmx_approx_lengths(self._h, C.byref(p)))
         return _view(p.value, self.counts()["n_hits"], np.uint32).copy()
 
+    def strands(self):
+        """kmx_approx_strands: the strand of every hit (u8, parallel to positions; 0 forward, 1 reverse) of a search with
+        strands=True."""
+        p = C.c_void_p()
+        _check(lib().kmx_approx_strands(self._h, C.byref(p)))
+        return _view(p.value, self.counts()["n_hits"], np.uint8).copy()
+
     def close(self):
         if self._h:
             lib().kmx_approx_free(self._h)
@@ -424,12 +447,21 @@ class Index:
         r._index = self
         return r
 
-    def search_approx(self, qranks, qoff, max_subst, edit=False):
+    def search_approx(self, qranks, qoff, max_subst, edit=False, strands=False, complement=None):
         """kmx_search_approx: every window within Hamming distance max_subst (<= APPROX_MAX_SUBST) of each query; edit=True
-        (KMX_APPROX_EDIT): every start of a window within that many edits, its distance in `mismatches`, ApproxResult.lengths()."""
+        (KMX_APPROX_EDIT): every start of a window within that many edits, its distance in `mismatches`, ApproxResult.lengths().
+        strands=True (kmx_search_approx_strands): the same for each query and its reverse complement under `complement`
+        (rank to rank, uint8[sigma]; default complement_table(sigma)), hits ordered by (position, strand), ApproxResult.strands()."""
         qranks = np.ascontiguousarray(qranks, np.uint8)
         qoff = np.ascontiguousarray(qoff, np.uint64)
         r = ApproxResult()
+        if strands:
+            comp = np.ascontiguousarray(complement_table(self.sigma) if complement is None else complement, np.uint8)
+            if comp.size != self.sigma:
+                raise ValueError("search_approx: the complement table needs sigma entries")
+            _check(lib().kmx_search_approx_strands(self._h, qranks.ctypes.data if qranks.size else None, qoff.ctypes.data,
+                                                   qoff.size - 1, int(max_subst), APPROX_EDIT if edit else 0, comp.ctypes.data, C.byref(r._h)))
+            return r
         _check(lib().kmx_search_approx(self._h, qranks.ctypes.data if qranks.size else None, qoff.ctypes.data,
                                        qoff.size - 1, int(max_subst), APPROX_EDIT if edit else 0, C.byref(r._h)))
         return r

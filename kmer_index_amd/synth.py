@@ -142,3 +142,43 @@ def planted_reads_edit(seed: int, text: np.ndarray, nq: int, m: int, sigma: int,
             q[sel] = sub
     off = np.arange(nq + 1, dtype=np.uint64) * np.uint64(m)
     return np.ascontiguousarray(q[:, :m].reshape(-1)), off, start
+
+
+def revcomp(qranks: np.ndarray, qoff: np.ndarray, complement: np.ndarray) -> np.ndarray:
+    """Every query of the batch reverse-complemented in place of itself: rc(q)[i] = complement[q[m - 1 - i]] (same offsets)."""
+    qranks = np.asarray(qranks, np.uint8)
+    qoff = np.asarray(qoff, np.uint64).astype(np.int64)
+    complement = np.asarray(complement, np.uint8)
+    if qranks.size == 0:
+        return qranks.copy()
+    lens = np.diff(qoff)
+    qi = np.repeat(np.arange(lens.size), lens)
+    src = qoff[qi] + qoff[qi + 1] - 1 - np.arange(qranks.size, dtype=np.int64)
+    return complement[qranks[src]]
+
+
+def _flip_half(seed: int, q: np.ndarray, off: np.ndarray, complement: np.ndarray):
+    """A seeded half of the reads replaced by their reverse complements: (qranks, strand[nq] u8)."""
+    nq = off.size - 1
+    strand = ((u64_stream(seed + 3, nq) >> np.uint64(17)) & np.uint64(1)).astype(np.uint8)
+    rc = revcomp(q, off, complement)
+    per_letter = np.repeat(strand, np.diff(off.astype(np.int64))).astype(bool)
+    return np.where(per_letter, rc, q).astype(np.uint8), strand
+
+
+def planted_reads_strands(seed: int, text: np.ndarray, nq: int, m: int, sigma: int, max_subst: int, complement: np.ndarray):
+    """planted_reads with a seeded half of the reads reverse-complemented (as a sequencer reads the other strand): the
+    reverse complement of read i lies within max_subst substitutions of text[start[i], start[i] + m) when strand[i] == 1,
+    the read itself when strand[i] == 0.  (qranks[nq*m] u8, qoff[nq+1] u64, strand[nq] u8, start[nq] i64)"""
+    q, off = planted_reads(seed, text, nq, m, sigma, max_subst)
+    start = (u64_stream(seed, nq) % np.uint64(text.size - m + 1)).astype(np.int64)
+    q, strand = _flip_half(seed, q, off, complement)
+    return q, off, strand, start
+
+
+def planted_reads_edit_strands(seed: int, text: np.ndarray, nq: int, m: int, sigma: int, max_edits: int, complement: np.ndarray):
+    """planted_reads_edit with a seeded half of the reads reverse-complemented: start[i] is within max_edits edits of read i
+    (strand[i] == 0) or of its reverse complement (strand[i] == 1).  (qranks, qoff, strand[nq] u8, start[nq] i64)"""
+    q, off, start = planted_reads_edit(seed, text, nq, m, sigma, max_edits)
+    q, strand = _flip_half(seed, q, off, complement)
+    return q, off, strand, start

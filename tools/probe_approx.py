@@ -11,6 +11,13 @@ hits.  Also: kmx_index_text's first derivation (time, packed bytes).  --json wri
 --edit adds to every leg the edit-distance search (KMX_APPROX_EDIT, same m and e, reads from synth.planted_reads_edit:
 substitutions, insertions and deletions) next to the Hamming figures of the same run: reads/s, candidates/s, band cells/s
 bound ((4e + 1) m cells per piece hit), hits, chunks, and the check that every read's source start is among its hits.
+--strands times the both-strand search (kmx_search_approx_strands) of every leg, reads from synth.planted_reads_strands (a
+seeded half reverse-complemented; with --edit also the edit form, reads from synth.planted_reads_edit_strands): reads/s end
+to end, piece hits, chunks, hits per strand, and the check that every read's source start is among its hits on its strand.
+--baseline times, on the same reads, what a caller does without that entry point: kmx_search_approx of the batch, the
+reverse complement of every read on the host, kmx_search_approx of that batch, and a numpy merge of the two results by
+(query, position, strand); it uses only kmx_search_approx, so it also runs against a library that lacks the new symbol.
+--no-plain skips the single-strand legs.
 For a kernel trace run one leg with --passes 1 under rocprofv3 --kernel-trace --stats."""
 import argparse
 import json
@@ -56,12 +63,107 @@ def sources_found(ho, pos, start):
     return int(np.sum((at < keys.size) & (keys[np.minimum(at, keys.size - 1)] == want)))
 
 
+def sources_found_strands(ho, pos, strands, start, strand):
+    """How many reads have (source start, strand) among their hits."""
+    nq = start.size
+    qi = np.repeat(np.arange(nq, dtype=np.uint64), np.diff(ho).astype(np.int64))
+    keys = (qi << np.uint64(33)) | (pos.astype(np.uint64) << np.uint64(1)) | strands.astype(np.uint64)
+    want = (np.arange(nq, dtype=np.uint64) << np.uint64(33)) | (start.astype(np.uint64) << np.uint64(1)) | strand.astype(np.uint64)
+    at = np.searchsorted(keys, want)
+    return int(np.sum((at < keys.size) & (keys[np.minimum(at, keys.size - 1)] == want)))
+
+
+def host_merge(nq, fwd, rev):
+    """Two results of kmx_search_approx (hit_off, positions, distances[, lengths]) as one, ordered by (query, position,
+    strand): what kmx_search_approx_strands returns, made with numpy."""
+    keys, cols = [], []
+    for strand, (ho, pos, *rest) in enumerate((fwd, rev)):
+        qi = np.repeat(np.arange(nq, dtype=np.uint64), np.diff(ho).astype(np.int64))
+        keys.append((qi << np.uint64(33)) | (pos.astype(np.uint64) << np.uint64(1)) | np.uint64(strand))
+        cols.append(rest)
+    keys = np.concatenate(keys)
+    order = np.argsort(keys, kind="stable")
+    keys = keys[order]
+    out_ho = np.zeros(nq + 1, np.uint64)
+    out_ho[1:] = fwd[0][1:] + rev[0][1:]
+    merged = [np.concatenate([c[k] for c in cols])[order] for k in range(len(cols[0]))]
+    return out_ho, ((keys >> np.uint64(1)) & np.uint64(0xFFFFFFFF)).astype(np.uint32), (keys & np.uint64(1)).astype(np.uint8), merged
+
+
+def strand_legs(idx, text, leg, edit, args, comp):
+    """The both-strand call and / or its two-call baseline on one leg's strand-planted reads."""
+    nq, m, e, seed = LEGS[leg]
+    n, sigma = text.size, 4
+    gen = synth.planted_reads_edit_strands if edit else synth.planted_reads_strands
+    q, off, strand, start = gen(seed, text, nq, m, sigma, e, comp)
+    rec = {}
+    box = {}
+    if args.strands:
+        def run():
+            r = idx.search_approx(q, off, e, edit=edit, strands=True, complement=comp)
+            box["host"] = r.host()
+            box["strands"] = r.strands()
+            if edit:
+                box["lengths"] = r.lengths()
+            box["counts"] = r.counts()
+            r.close()
+
+        t = median_time(run, args.passes)
+        t_min, t_max = median_time.spread
+        ho, pos, dist, st = box["host"]
+        sb, c = box["strands"], box["counts"]
+        rec["strands"] = {"median_s": round(t, 5), "min_s": round(t_min, 5), "max_s": round(t_max, 5), "reads_per_s": round(nq / t, 1),
+                          "n_candidates": c["n_candidates"], "n_hits": c["n_hits"], "n_chunks": c["n_chunks"],
+                          "hits_forward": int(np.sum(sb == 0)), "hits_reverse": int(np.sum(sb == 1)), "reads_reverse": int(strand.sum()),
+                          "status_ok": int(np.sum(st == engine.Q_OK)), "sources_found_on_strand": sources_found_strands(ho, pos, sb, start, strand)}
+    if args.baseline:
+        def two_calls():
+            t0 = time.perf_counter()
+            r = idx.search_approx(q, off, e, edit=edit)
+            f = r.host()[:3] + ((r.lengths(),) if edit else ())
+            r.close()
+            t1 = time.perf_counter()
+            rc = synth.revcomp(q, off, comp)
+            t2 = time.perf_counter()
+            r = idx.search_approx(rc, off, e, edit=edit)
+            v = r.host()[:3] + ((r.lengths(),) if edit else ())
+            r.close()
+            t3 = time.perf_counter()
+            box["merged"] = host_merge(nq, f, v)
+            t4 = time.perf_counter()
+            box["parts"] = (t1 - t0 + t3 - t2, t2 - t1, t4 - t3)
+
+        parts = []
+
+        def timed():
+            two_calls()
+            parts.append(box["parts"])
+
+        t = median_time(timed, args.passes)
+        t_min, t_max = median_time.spread
+        parts = np.array(parts[1:])                              # (without the warm-up)
+        ho, pos, sb, _ = box["merged"]
+        rec["baseline_two_calls"] = {"median_s": round(t, 5), "min_s": round(t_min, 5), "max_s": round(t_max, 5), "spread_s": round(t_max - t_min, 5),
+                                     "reads_per_s": round(nq / t, 1), "two_searches_median_s": round(float(np.median(parts[:, 0])), 5),
+                                     "host_revcomp_median_s": round(float(np.median(parts[:, 1])), 5),
+                                     "host_merge_median_s": round(float(np.median(parts[:, 2])), 5), "n_hits": int(pos.size),
+                                     "sources_found_on_strand": sources_found_strands(ho, pos, sb, start, strand)}
+        if args.strands:
+            same = np.array_equal(ho, box["host"][0]) and np.array_equal(pos, box["host"][1]) and np.array_equal(sb, box["strands"])
+            rec["baseline_two_calls"]["equals_strands_call"] = bool(same)
+            rec["strands"]["vs_baseline"] = round(rec["strands"]["median_s"] / t, 3)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default="abc")
     ap.add_argument("--passes", type=int, default=5)
     ap.add_argument("--no-pieces", action="store_true", help="skip the piece-search-alone timing")
     ap.add_argument("--edit", action="store_true", help="also time the edit-distance search of every leg")
+    ap.add_argument("--strands", action="store_true", help="time the both-strand search (kmx_search_approx_strands) of every leg")
+    ap.add_argument("--baseline", action="store_true", help="time two plain calls + host reverse complement + host merge on the strand reads")
+    ap.add_argument("--no-plain", action="store_true", help="skip the single-strand legs")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     n, sigma = 100_000_000, 4
@@ -73,8 +175,17 @@ def main():
     derive_ms = (time.perf_counter() - t0) * 1e3
     out = {"probe": "approx", "config": 2, "n": n, "k": 10, "text_derive_ms": round(derive_ms, 2), "packed_bytes": packed, "legs": {}}
     print(f"kmx_index_text: first derivation {derive_ms:.2f} ms, {packed} packed bytes", flush=True)
+    comp = np.array([3, 2, 1, 0], np.uint8)                   # ACGT
     for leg in args.legs:
         nq, m, e, seed = LEGS[leg]
+        if args.no_plain:
+            rec = {"nq": nq, "m": m, "e": e}
+            rec["both_strands"] = strand_legs(idx, text, leg, False, args, comp)
+            if args.edit:
+                rec["both_strands_edit"] = strand_legs(idx, text, leg, True, args, comp)
+            out["legs"][leg] = rec
+            print(f"leg {leg}: m={m} e={e} {json.dumps(rec)}", flush=True)
+            continue
         q, off = synth.planted_reads(seed, text, nq, m, sigma, e)
         box = {}
 
@@ -125,6 +236,10 @@ def main():
                            "hits_other_length": int(np.sum(box["lengths"] != m)), "n_chunks": c2["n_chunks"],
                            "status_ok": int(np.sum(st2 == engine.Q_OK)), "sources_found": sources_found(ho2, pos2, start2.astype(np.uint64)),
                            "slowdown_vs_hamming": round(t2 / t, 3)}
+        if args.strands or args.baseline:
+            rec["both_strands"] = strand_legs(idx, text, leg, False, args, comp)
+            if args.edit:
+                rec["both_strands_edit"] = strand_legs(idx, text, leg, True, args, comp)
         out["legs"][leg] = rec
         print(f"leg {leg}: m={m} e={e} {json.dumps(rec)}", flush=True)
     idx.close()

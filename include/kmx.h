@@ -296,6 +296,48 @@ kmx_status kmx_index_bucket_host(const kmx_index* index, uint32_t k, const uint8
  * of the element of ks[i] (kmx_index_info's order), 0 for elements without.  levels holds KMX_MAX_KS entries. */
 kmx_status kmx_index_levels(const kmx_index* index, uint32_t* levels);
 
+/* Which code path ran (an extension, read-only; a caller detects the capability by the macro KMX_PATH_INFO, KMX_VERSION is
+ * unchanged).  Several kernels of the exact search exist in variants chosen from the index (arena size, bucket density), from
+ * what the previous batch on the result handle held, or from tuning variables in the environment (KMX_FILL_VARIANT,
+ * KMX_FORCE_REC64, KMX_CELLS, KMX_CELL_SHIFT read when an index is installed; KMX_LOOKUP_ITEMS, KMX_NO_SMALL read once per
+ * process); a value those variables do not recognise leaves the default in place.  Results never depend on the choice; these
+ * two calls report it, so that a test or a tuning run knows what it measured.  The caller sets struct_size = sizeof(the
+ * struct); the library fills the fields that size covers. */
+#define KMX_PATH_INFO 1
+typedef struct kmx_index_path_info {
+    uint32_t struct_size;
+    uint32_t fill_slots;        /* output slots per thread of k_fill as launched: 4, 8, 12 or 16 (tile = 256 x this)          */
+    uint32_t fill_nontemporal;  /* k_fill writes the hit lists with non-temporal stores                                      */
+    uint32_t rec64;             /* k_fill keeps 64-bit records (arenas of 4 GiB or more; always 8 slots per thread)          */
+    uint32_t tiny_cells;        /* some element has cells and at most four positions per key: k_lookup takes 8 queries per
+                                   thread on batches without cross-referenced queries                                       */
+    uint32_t scan_tile;         /* queries per block of the scan over the hit counts (a multiple of every lookup block)      */
+    uint32_t n_ks;
+    uint32_t cell_shift[KMX_MAX_KS]; /* per element (kmx_index_info's order): log2 of its cell size in positions, 0 = no cells */
+} kmx_index_path_info;
+kmx_status kmx_index_paths(const kmx_index* index, kmx_index_path_info* out);
+
+/* The last finished search into `r` (a pending KMX_SEARCH_ASYNC search is completed first).  Refused for results of several
+ * parts (multi-device, chunk-streamed): every part ran a search of its own. */
+typedef struct kmx_result_path_info {
+    uint32_t struct_size;
+    uint32_t small;             /* the latency path answered (k_small): every field below is 0                               */
+    uint32_t lookup_items;      /* queries per thread of k_lookup: 4 or 8                                                    */
+    uint32_t lookup_pairs;      /* k_lookup ran the variant that interleaves cross-referenced (two-part) queries             */
+    uint32_t deferred_long;     /* queries of very many parts were listed by k_lookup and served by k_lookup_long            */
+    uint32_t tile_q_source;     /* who wrote the first query of every output tile for the k_fill whose output was kept:
+                                   KMX_TILE_Q_NONE (no fill: no hits, KMX_SEARCH_COUNT_ONLY), _PARTITION (k_partition: first
+                                   batch of a handle, or its tile table had to grow) or _SCAN (the scan's downsweep)          */
+    uint32_t spec_fill;         /* k_fill was launched behind the scan, before the host knew the hit total                   */
+    uint32_t spec_ok;           /* ... and its output was kept (no second k_fill; also when the batch has no hits at all)    */
+    uint32_t fill_blocks;       /* grid of the k_fill whose output was kept (blocks beyond the hit total leave at once)      */
+    uint32_t fill_tiles;        /* tiles that hold hits: ceil(n_hits / (256 x fill_slots))                                   */
+} kmx_result_path_info;
+#define KMX_TILE_Q_NONE 0u
+#define KMX_TILE_Q_PARTITION 1u
+#define KMX_TILE_Q_SCAN 2u
+kmx_status kmx_result_paths(const kmx_result* r, kmx_result_path_info* out);
+
 void kmx_result_free(kmx_result* r);
 
 /* ---- approximate search: an extension, no reference interface.  Every window of the text within Hamming distance

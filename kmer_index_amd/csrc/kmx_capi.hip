@@ -250,6 +250,8 @@ struct kmx_result {
     bool last_had_stitch = false;          // adaptive speculation: see kmx_search_batch_device
     bool last_had_long = false;            // ... or queries of very many parts (k_lookup_long)
     bool last_had_pairs = false;           // the previous batch held cross-referenced queries: k_lookup's variant (kmx_search_batch_device)
+    struct PathRec { uint32_t small = 0, items = 0, pairs = 0, defer_long = 0, tile_q_source = 0, spec_fill = 0, spec_ok = 0, fill_blocks = 0, fill_tiles = 0; };
+    PathRec path;                          // which variants the last search ran (kmx_result_paths)
     std::shared_ptr<ResultPool> pool;      // where kmx_result_free parks this result (set by the search that made it)
     SearchCtx ctx;                         // the half-done search of a KMX_SEARCH_ASYNC call (search_finish completes it)
     hipEvent_t done = nullptr;             // recorded behind the first half's counter read-back
@@ -1366,6 +1368,34 @@ kmx_status kmx_index_levels(const kmx_index* ix, uint32_t* levels)
     return KMX_OK;
 }
 
+kmx_status kmx_index_paths(const kmx_index* ix, kmx_index_path_info* out)
+{
+    if (!ix || !out || out->struct_size < sizeof(uint32_t)) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_index_paths: NULL argument or no struct_size");
+    const kmx::FillVariant fv = kmx::effective_fill_variant(ix->fill_variant, ix->rec32);
+    kmx_index_path_info v{};
+    v.fill_slots = uint32_t(fv.e); v.fill_nontemporal = fv.nt; v.rec64 = !ix->rec32; v.tiny_cells = ix->tiny_cells;
+    v.scan_tile = uint32_t(kmx::scan_tile());
+    v.n_ks = uint32_t(ix->ks.size());
+    for (size_t i = 0; i < ix->ks.size(); ++i) v.cell_shift[i] = ix->h_header.elems[i].cnt8 ? ix->h_header.elems[i].cell_shift : 0u;
+    v.struct_size = std::min<uint32_t>(out->struct_size, uint32_t(sizeof v));
+    memcpy(out, &v, v.struct_size);
+    return KMX_OK;
+}
+
+kmx_status kmx_result_paths(const kmx_result* r, kmx_result_path_info* out)
+{
+    if (!r || !out || out->struct_size < sizeof(uint32_t)) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_paths: NULL argument or no struct_size");
+    if (!r->parts.empty()) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_paths: a result of several parts has no single search to report");
+    if (r->ctx.pending) { kmx_status fs = search_finish(const_cast<kmx_result*>(r)); if (fs != KMX_OK) return fs; }
+    kmx_result_path_info v{};
+    v.small = r->path.small; v.lookup_items = r->path.items; v.lookup_pairs = r->path.pairs; v.deferred_long = r->path.defer_long;
+    v.tile_q_source = r->path.tile_q_source; v.spec_fill = r->path.spec_fill; v.spec_ok = r->path.spec_ok;
+    v.fill_blocks = r->path.fill_blocks; v.fill_tiles = r->path.fill_tiles;
+    v.struct_size = std::min<uint32_t>(out->struct_size, uint32_t(sizeof v));
+    memcpy(out, &v, v.struct_size);
+    return KMX_OK;
+}
+
 // KMX_CHECKED builds: copies the 16 violation-record words (word 0 = count).
 kmx_status kmx_debug_words(const kmx_index* ix, uint64_t* words16)
 {
@@ -1454,6 +1484,7 @@ kmx_status kmx_search_batch_device(const kmx_index* cix, const void* d_qranks, c
     r->n_hits = r->n_exact = r->n_stitch = r->n_prefix = r->n_error = r->n_none = r->n_mask_words = 0;
     r->host_valid = r->host_masks_valid = false;
     r->small_valid = false;
+    r->path = kmx_result::PathRec{};
     r->quiesced = false;
     if (!r->h_ctr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->h_ctr), KMX_CTR_COUNT * sizeof(unsigned long long), hipHostMallocDefault));
     HIP_TRY(r->hit_off.ensure((nq + 1) * 8));
@@ -1503,6 +1534,7 @@ kmx_status kmx_search_batch_device(const kmx_index* cix, const void* d_qranks, c
     // k_lookup_long gives each a wave (a lane per part) before the scan reads the counters
     const bool defer_long = r->last_had_long;
     const uint32_t lflags = (flags & ~KMX_SEARCH_INTERNAL_DEFER_LONG) | (defer_long ? KMX_SEARCH_INTERNAL_DEFER_LONG : 0u);
+    r->path.items = uint32_t(items); r->path.pairs = pairs; r->path.defer_long = defer_long;
     timed(ix, K_LOOKUP, s, [&] {
         kmx::launch_lookup(s, items, pairs, dix, qr, qo, nq, d, ctr, r->bsum.as<uint64_t>(), lflags);
         if (defer_long) kmx::launch_lookup_long(s, dix, qr, qo, nq, d, ctr, flags);
@@ -1535,6 +1567,7 @@ kmx_status kmx_search_batch_device(const kmx_index* cix, const void* d_qranks, c
             kmx::launch_fill(s, fv, ix->rec32, dix, ix->d_arena, r->hit_off.as<uint64_t>(), r->tile_q.as<uint32_t>(),
                              ctr + KMX_CTR_TOTAL_HITS, spec_tiles, d, r->out.as<uint32_t>());
         });
+    r->path.spec_fill = spec_fill;
     if (!published) HIP_TRY(hipMemcpyAsync(r->h_ctr, ctr, KMX_CTR_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     // everything after the read-back lives in search_finish: right away, or (KMX_SEARCH_ASYNC) when the result is next touched
     r->ctx = SearchCtx{ix, qr, qo, s, tile_cap, spec_tiles, spec_fill, true};
@@ -1620,7 +1653,11 @@ static kmx_status search_finish(kmx_result* r)
     if (flags & KMX_SEARCH_COUNT_ONLY) return KMX_OK;
 
     const uint64_t total = r->n_hits;
-    if (total == 0) return KMX_OK;
+    if (total == 0) {                                          // nothing to fill: a speculative k_fill found no tile of its own and stands
+        r->path.spec_ok = spec_fill;
+        r->path.fill_blocks = uint32_t(spec_fill ? spec_tiles : 0);
+        return KMX_OK;
+    }
     const uint64_t n_tiles = (total + tile - 1) / tile;
     if (n_tiles >= 0x7FFFFFFFull) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: result too large, split the batch");
     HIP_TRY(r->out.ensure(total * 4));
@@ -1628,6 +1665,10 @@ static kmx_status search_finish(kmx_result* r)
     uint32_t* out = r->out.as<uint32_t>();
     const uint64_t* hit_off = r->hit_off.as<uint64_t>();
     const bool spec_ok = spec_fill && n_stitch_pending == 0 && n_tiles <= spec_tiles;   // the early k_fill already did the work
+    r->path.spec_ok = spec_ok;
+    r->path.fill_tiles = uint32_t(n_tiles);
+    r->path.fill_blocks = uint32_t(spec_ok ? spec_tiles : n_tiles);
+    r->path.tile_q_source = (!spec_ok && n_tiles + 1 > tile_cap) ? KMX_TILE_Q_PARTITION : KMX_TILE_Q_SCAN;
     if (!spec_ok) {
         if (n_tiles + 1 > tile_cap)   // first batch / the table had to grow: the scan could not fill it
             timed(ix, K_PARTITION, s, [&] { kmx::launch_partition(s, hit_off, nq, tile, n_tiles, r->tile_q.as<uint32_t>()); });
@@ -1828,6 +1869,8 @@ static kmx_status search_host_one(kmx_index* ix, const uint8_t* qranks, const ui
             }
             r->host_valid = r->host_masks_valid = true;
             r->small_valid = true;
+            r->path = kmx_result::PathRec{};
+            r->path.small = 1;
             r->quiesced = true;
             r->last_had_stitch = false;
             r->last_had_pairs = false;

@@ -3762,6 +3762,7 @@ void launch_validate(hipStream_t s, const KmxIndexDev* ix, const uint32_t* arena
 }
 
 uint64_t scan_blocks(uint64_t n) { return blocks_for(n, KMX_SCAN_TILE); }
+uint64_t scan_tile() { return KMX_SCAN_TILE; }
 
 #define KMX_SCAN_FUSED_SPINE_BLOCKS 8192     // up to this many blocks the downsweep adds up the block sums itself
 

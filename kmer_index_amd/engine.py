@@ -19,6 +19,7 @@ KIND_NONE, KIND_EXACT, KIND_STITCH, KIND_PREFIX = 0, 1, 2, 3
 Q_OK, Q_TOO_LONG, Q_SUBK_FANOUT, Q_EMPTY_QUERY, Q_BAD_RANK, Q_TOO_SHORT = 0, 1, 2, 3, 4, 5
 APPROX_MAX_SUBST = 3
 APPROX_EDIT = 1
+TILE_Q_NONE, TILE_Q_PARTITION, TILE_Q_SCAN = 0, 1, 2
 
 # every symbol include/kmx.h declares
 EXPORTS = [
@@ -30,6 +31,7 @@ EXPORTS = [
     "kmx_index_bucket_host", "kmx_index_levels", "kmx_result_gather_device",
     "kmx_search_approx", "kmx_approx_counts", "kmx_approx_view", "kmx_approx_free", "kmx_index_text",
     "kmx_approx_lengths", "kmx_search_approx_strands", "kmx_approx_strands",
+    "kmx_index_paths", "kmx_result_paths",
 ]
 
 
@@ -48,6 +50,17 @@ class Options(C.Structure):
 
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_uint64), ("total_ms", C.c_double)]
+
+
+class IndexPathInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("fill_slots", C.c_uint32), ("fill_nontemporal", C.c_uint32), ("rec64", C.c_uint32),
+                ("tiny_cells", C.c_uint32), ("scan_tile", C.c_uint32), ("n_ks", C.c_uint32), ("cell_shift", C.c_uint32 * KMX_MAX_KS)]
+
+
+class ResultPathInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("small", C.c_uint32), ("lookup_items", C.c_uint32), ("lookup_pairs", C.c_uint32),
+                ("deferred_long", C.c_uint32), ("tile_q_source", C.c_uint32), ("spec_fill", C.c_uint32), ("spec_ok", C.c_uint32),
+                ("fill_blocks", C.c_uint32), ("fill_tiles", C.c_uint32)]
 
 
 _lib = None
@@ -130,6 +143,10 @@ def lib():
         L.kmx_search_approx_strands.argtypes = [vp, vp, vp, u64, u32, u32, vp, P(vp)]
         L.kmx_approx_strands.restype = C.c_int
         L.kmx_approx_strands.argtypes = [vp, P(vp)]
+        L.kmx_index_paths.restype = C.c_int
+        L.kmx_index_paths.argtypes = [vp, P(IndexPathInfo)]
+        L.kmx_result_paths.restype = C.c_int
+        L.kmx_result_paths.argtypes = [vp, P(ResultPathInfo)]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -241,6 +258,15 @@ class Result:
         v = [C.c_uint64() for _ in range(6)]
         _check(lib().kmx_result_counts(self._h, *[C.byref(x) for x in v]))
         return dict(zip(["nq", "n_hits", "n_exact", "n_stitch", "n_prefix", "n_error"], [int(x.value) for x in v]))
+
+    def paths(self):
+        """kmx_result_paths: which kernel variants the last finished search into this result ran."""
+        v = ResultPathInfo()
+        v.struct_size = C.sizeof(ResultPathInfo)
+        _check(lib().kmx_result_paths(self._h, C.byref(v)))
+        return {"small": bool(v.small), "lookup_items": int(v.lookup_items), "lookup_pairs": bool(v.lookup_pairs),
+                "deferred_long": bool(v.deferred_long), "tile_q_source": int(v.tile_q_source), "spec_fill": bool(v.spec_fill),
+                "spec_ok": bool(v.spec_ok), "fill_blocks": int(v.fill_blocks), "fill_tiles": int(v.fill_tiles)}
 
     def host(self, copy=True):
         """(hit_off[nq+1], positions, status[nq], kinds[nq]) as numpy arrays: copies, or with copy=False views of the
@@ -407,6 +433,15 @@ class Index:
         v = [C.c_uint64() for _ in range(5)]
         _check(lib().kmx_index_memory(self._h, *[C.byref(x) for x in v]))
         return dict(zip(["positions", "aligned_copy", "cells", "prefix_levels", "tables"], [int(x.value) for x in v]))
+
+    def paths(self):
+        """kmx_index_paths: the k_fill variant in effect (slots per thread, non-temporal stores, 64-bit records), tiny_cells, the
+        scan's tile in queries and the cell shift of every element (info()["ks"] order, 0 = no cells)."""
+        v = IndexPathInfo()
+        v.struct_size = C.sizeof(IndexPathInfo)
+        _check(lib().kmx_index_paths(self._h, C.byref(v)))
+        return {"fill_slots": int(v.fill_slots), "fill_nontemporal": bool(v.fill_nontemporal), "rec64": bool(v.rec64),
+                "tiny_cells": bool(v.tiny_cells), "scan_tile": int(v.scan_tile), "cell_shift": [int(v.cell_shift[i]) for i in range(v.n_ks)]}
 
     def devices(self):
         n = C.c_uint32()

@@ -11,6 +11,8 @@ int use_the_declarations(void)
     const uint8_t *status, *kinds;
     uint32_t n_parts = 0, n_dev = 0;
     int32_t devs[KMX_MAX_DEVICES];
+    kmx_index_path_info ip;
+    kmx_result_path_info rp;
     o.struct_size = (uint32_t)sizeof o;
     o.device = -1;
     o.n_devices = 0;
@@ -20,5 +22,9 @@ int use_the_declarations(void)
     (void)kmx_result_view(r, &hit_off, &positions, &status, &kinds);
     (void)kmx_result_parts(r, &n_parts);
     (void)kmx_index_devices(ix, &n_dev, devs);
+    ip.struct_size = (uint32_t)sizeof ip;
+    rp.struct_size = (uint32_t)sizeof rp;
+    (void)kmx_index_paths(ix, &ip);
+    if (kmx_result_paths(r, &rp) == KMX_OK && rp.tile_q_source == KMX_TILE_Q_SCAN) return 4;
     return (int)(kmx_fast_pow(4, 10) != 1048576u);
 }

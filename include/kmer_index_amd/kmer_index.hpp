@@ -331,6 +331,7 @@ namespace kmer
         {
             std::vector<position_t> positions;
             std::vector<std::uint8_t> mismatches;
+            std::size_t found = 0;                   // report_options overloads only: hits left in front of the max_hits cap
         };
         std::vector<approx_hits> search_approx(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_subst,
                                                std::vector<std::uint8_t>& status_out) const
@@ -394,6 +395,7 @@ namespace kmer
             std::vector<position_t> positions;
             std::vector<std::uint8_t> distances;
             std::vector<std::uint32_t> lengths;
+            std::size_t found = 0;                   // report_options overloads only: hits left in front of the max_hits cap
         };
         std::vector<edit_hits> search_edit(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_edits,
                                            std::vector<std::uint8_t>& status_out) const
@@ -459,6 +461,7 @@ namespace kmer
             std::vector<std::uint8_t> distances;
             std::vector<std::uint32_t> lengths;
             std::vector<std::uint8_t> strands;
+            std::size_t found = 0;                   // report_options overloads only: hits left in front of the max_hits cap
         };
         std::vector<strand_hits> search_both_strands(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit,
                                                      const complement_table& complement, std::vector<std::uint8_t>& status_out) const
@@ -535,6 +538,104 @@ namespace kmer
         }
 
         static constexpr complement_table natural_complement() { return alphabet::complement_ranks<alphabet_t>(); }
+
+        // Reporting options (kmx_search_approx_opts; the contract is in kmx.h): loci = one hit per alignment locus (search_edit
+        // and search_both_strands with edit only; the engine refuses it elsewhere), best = the hits of the least distance only,
+        // max_hits = at most that many per query (0: no cap), the first in (distance, position, strand) order.  Each query's
+        // `found` is the number of hits left after loci and best: more than it holds when the cap cut its list.  The overloads
+        // report statuses through status_out, as the status_out overloads above.
+        struct report_options
+        {
+            bool loci = false, best = false;
+            std::size_t max_hits = 0;
+        };
+        std::vector<approx_hits> search_approx(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_subst,
+                                               const report_options& report, std::vector<std::uint8_t>& status_out) const
+        {
+            std::vector<approx_hits> out(queries.size());
+            search_report("search_approx", queries, max_subst, 0u, report, nullptr, status_out,
+                          [&](std::size_t i, std::uint64_t a, std::uint64_t b, const report_views& v)
+                          {
+                              out[i].positions.assign(v.positions + a, v.positions + b);
+                              out[i].mismatches.assign(v.distances + a, v.distances + b);
+                              out[i].found = std::size_t(v.found[i]);
+                          });
+            return out;
+        }
+        std::vector<edit_hits> search_edit(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_edits,
+                                           const report_options& report, std::vector<std::uint8_t>& status_out) const
+        {
+            std::vector<edit_hits> out(queries.size());
+            search_report("search_edit", queries, max_edits, KMX_APPROX_EDIT, report, nullptr, status_out,
+                          [&](std::size_t i, std::uint64_t a, std::uint64_t b, const report_views& v)
+                          {
+                              out[i].positions.assign(v.positions + a, v.positions + b);
+                              out[i].distances.assign(v.distances + a, v.distances + b);
+                              out[i].lengths.assign(v.lengths + a, v.lengths + b);
+                              out[i].found = std::size_t(v.found[i]);
+                          });
+            return out;
+        }
+        std::vector<strand_hits> search_both_strands(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit,
+                                                     const complement_table& complement, const report_options& report,
+                                                     std::vector<std::uint8_t>& status_out) const
+        {
+            std::vector<strand_hits> out(queries.size());
+            search_report("search_both_strands", queries, max_dist, edit ? KMX_APPROX_EDIT : 0u, report, complement.data(), status_out,
+                          [&](std::size_t i, std::uint64_t a, std::uint64_t b, const report_views& v)
+                          {
+                              out[i].positions.assign(v.positions + a, v.positions + b);
+                              out[i].distances.assign(v.distances + a, v.distances + b);
+                              out[i].strands.assign(v.strands + a, v.strands + b);
+                              if (edit) out[i].lengths.assign(v.lengths + a, v.lengths + b);
+                              out[i].found = std::size_t(v.found[i]);
+                          });
+            return out;
+        }
+        std::vector<strand_hits> search_both_strands(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit,
+                                                     const report_options& report, std::vector<std::uint8_t>& status_out) const
+        {
+            return search_both_strands(queries, max_dist, edit, natural_complement(), report, status_out);
+        }
+
+        // the views of one kmx_search_approx_opts result (lengths: edit only, strands: both strands only)
+        struct report_views
+        {
+            const std::uint32_t* positions = nullptr;
+            const std::uint8_t* distances = nullptr;
+            const std::uint32_t* lengths = nullptr;
+            const std::uint8_t* strands = nullptr;
+            const std::uint64_t* found = nullptr;
+        };
+        // one kmx_search_approx_opts call; each(i, first hit, end of hits, views) fills query i of the caller's result
+        template<typename each_t>
+        void search_report(const char* who, const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, std::uint32_t edit_flag,
+                           const report_options& report, const std::uint8_t* complement, std::vector<std::uint8_t>& status_out, each_t&& each) const
+        {
+            std::vector<std::uint8_t> ranks;
+            std::vector<std::uint64_t> off(queries.size() + 1, 0);
+            for (std::size_t i = 0; i < queries.size(); ++i) off[i + 1] = off[i] + queries[i].size();
+            ranks.reserve(off.back());
+            for (auto const& q : queries)
+                for (auto const& l : q) ranks.push_back(traits::to_rank(l));
+            kmx_approx_options options;
+            options.struct_size = std::uint32_t(sizeof options);
+            options.max_subst = std::uint32_t(max_dist);
+            options.flags = edit_flag | (report.loci ? KMX_APPROX_LOCI : 0u) | (report.best ? KMX_APPROX_BEST : 0u);
+            options.max_hits = std::uint32_t(report.max_hits);
+            options.complement = complement;
+            kmx_approx_result* raw = nullptr;
+            detail::throw_on(kmx_search_approx_opts(_index.get(), ranks.data(), off.data(), queries.size(), &options, &raw), who);
+            std::unique_ptr<kmx_approx_result, void (*)(kmx_approx_result*)> hold(raw, kmx_approx_free);
+            const std::uint64_t* hit_off; const std::uint8_t* status;
+            report_views v;
+            detail::throw_on(kmx_approx_view(raw, &hit_off, &v.positions, &v.distances, &status), who);
+            detail::throw_on(kmx_approx_found(raw, &v.found), who);
+            if (edit_flag) detail::throw_on(kmx_approx_lengths(raw, &v.lengths), who);
+            if (complement) detail::throw_on(kmx_approx_strands(raw, &v.strands), who);
+            status_out.assign(status, status + queries.size());
+            for (std::size_t i = 0; i < queries.size(); ++i) each(i, hit_off[i], hit_off[i + 1], v);
+        }
 
         // the text, reconstructed on the device from the index (kmx_index_text; an extension, no reference interface)
         std::vector<alphabet_t> text() const

@@ -428,6 +428,59 @@ kmx_status kmx_search_approx_strands(const kmx_index* index, const uint8_t* qran
                                      kmx_approx_result** out);
 kmx_status kmx_approx_strands(kmx_approx_result* r, const uint8_t** strands);
 
+/* ---- reporting: one hit per alignment locus, the best stratum only, at most N hits per query (an extension; a caller
+ *      detects the capability by the macro KMX_APPROX_REPORT, KMX_VERSION is unchanged).  The familiar form is
+ *      `-k N --best --strata` of a read mapper.  The filtering runs on the device, in front of the copy to the host.
+ *
+ * kmx_search_approx_opts takes its arguments in a struct: max_subst as kmx_search_approx; flags, any of KMX_APPROX_EDIT,
+ * KMX_APPROX_LOCI and KMX_APPROX_BEST; max_hits, the cap (0 = none); complement, NULL for the strand the index was built
+ * from (kmx_search_approx), otherwise the table of kmx_search_approx_strands, and both strands are searched.  struct_size must
+ * be at least sizeof(kmx_approx_options).  Refused with KMX_ERR_INVALID_ARGUMENT before any device is touched: NULL
+ * options, a smaller struct_size, any other flag bit, KMX_APPROX_LOCI without KMX_APPROX_EDIT (Hamming hits cast no
+ * shadows), max_subst > KMX_APPROX_MAX_SUBST, and a bad complement table as kmx_search_approx_strands refuses it.
+ * kmx_search_approx and kmx_search_approx_strands keep refusing every flag bit but KMX_APPROX_EDIT.
+ *
+ * What is reported.  Let H(q) be the hit list of query q that the call reports with KMX_APPROX_LOCI and KMX_APPROX_BEST
+ * cleared and max_hits = 0: exactly the list of kmx_search_approx (complement == NULL) or kmx_search_approx_strands with the
+ * same max_subst and KMX_APPROX_EDIT bit; with no option set the call returns that result array for array and does no further
+ * work on the device.  A hit is (p, strand, d, L): offset, strand (0 throughout for one strand), mismatches or distance,
+ * window length (edit only).  e = max_subst.  Three steps, in this order:
+ *   1. KMX_APPROX_LOCI.  A hit (p, s, d) survives unless H(q) holds a hit (p', s, d') on the same strand with p' != p,
+ *      |p' - p| <= e and (d', p') < (d, p) lexicographically.  The rule looks at H(q), not at the survivors: a hit removed by
+ *      a better neighbour still removes its own worse neighbours.  A start at distance d casts its shadows (p +- i at distance
+ *      d + i) no farther than e - d away, so the radius e removes all of them; of equal distances within the radius the
+ *      leftmost stays.  Hits on different strands never suppress each other.  With e = 0 nothing is removed.
+ *   2. KMX_APPROX_BEST.  Of the survivors, those whose d equals the least d among the query's survivors; with both strands
+ *      the least d over both strands together.
+ *      Steps 1 and 2 commute: the least d of H(q) is always the d of a survivor of step 1 (on each strand the least (d, p)
+ *      has nothing below it), and a hit of that stratum can only be removed by a hit of that stratum, so step 1 applied to
+ *      the best stratum of H(q) leaves the same hits.
+ *   3. The cap.  found[q] (kmx_approx_found) is the number of hits left after steps 1 and 2.  With max_hits != 0 and
+ *      found[q] > max_hits, the max_hits hits that come first in (d, p, strand) order are kept.
+ * The hits kept are reported in the usual order, strictly ascending in (position, strand), each with the d, L and strand it
+ * has in H(q).  A caller sees truncation as found[q] > hit_off[q + 1] - hit_off[q].
+ * Unchanged: the statuses and their precedence, n_candidates, the chunk budgets and the two environment variables, and the
+ * rule that a query (both strands of it) is never split across chunks, so every step sees the whole of H(q).
+ * kmx_approx_counts gives in n_hits the hits returned (the length of positions[]); kmx_approx_view, kmx_approx_lengths and
+ * kmx_approx_strands work as on the results of the older entry points, the latter two refused without KMX_APPROX_EDIT /
+ * without a complement table.
+ * kmx_approx_found: found[nq] (uint64), valid until kmx_approx_free, on every result of kmx_search_approx_opts (without a
+ * cap it equals the list lengths); KMX_ERR_INVALID_ARGUMENT on a result of kmx_search_approx or kmx_search_approx_strands.
+ * Accessors of one result are not to be called concurrently. */
+#define KMX_APPROX_REPORT 1
+#define KMX_APPROX_LOCI 2u /* needs KMX_APPROX_EDIT */
+#define KMX_APPROX_BEST 4u
+typedef struct kmx_approx_options {
+    uint32_t struct_size;      /* = sizeof(kmx_approx_options) */
+    uint32_t max_subst;        /* as kmx_search_approx */
+    uint32_t flags;            /* KMX_APPROX_EDIT | KMX_APPROX_LOCI | KMX_APPROX_BEST */
+    uint32_t max_hits;         /* 0 = no cap; else at most this many hits per query */
+    const uint8_t* complement; /* NULL = one strand; else both, as kmx_search_approx_strands */
+} kmx_approx_options;
+kmx_status kmx_search_approx_opts(const kmx_index* index, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq,
+                                  const kmx_approx_options* options, kmx_approx_result** out);
+kmx_status kmx_approx_found(kmx_approx_result* r, const uint64_t** found /* [nq] */);
+
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.
  * Works on built, loaded and replicated indexes (this replica).  The first call derives a copy packed at 2, 4 or 8 bits per

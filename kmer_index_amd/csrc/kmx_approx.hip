@@ -94,7 +94,10 @@ struct kmx_approx_result {
     uint32_t n_chunks = 0;
     bool edit = false;                                   // KMX_APPROX_EDIT: mismatches holds distances, lengths is filled
     bool strands = false;                                // kmx_search_approx_strands: strand is filled
-    PinnedArr hit_off, positions, mismatches, status, lengths, strand;
+    bool opts = false;                                   // kmx_search_approx_opts: kmx_approx_found works
+    bool reported = false;                               // ... with a reporting option: found is filled by the device stage
+    PinnedArr hit_off, positions, mismatches, status, lengths, strand, found;
+    std::vector<uint64_t> found_lazy;                    // opts && !reported: the list lengths, made by the first kmx_approx_found
 };
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -791,6 +794,136 @@ __global__ __launch_bounds__(kBlock) void k_strand_merge(const uint64_t* __restr
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
+// reporting (kmx_search_approx_opts with KMX_APPROX_LOCI, KMX_APPROX_BEST or max_hits): the chunk's final hit lists, ordered by
+// (position, strand), are filtered on the device in front of the copy to the host.  A hit is a survivor unless the LOCI rule
+// removes it (a rule about the neighbours it has in the unfiltered list, so one pass decides it); the survivors of a query are
+// counted per distance (four strata), from which one thread per query derives found[q], the lowest stratum kept, the
+// threshold stratum t* and the quota left in it; only under a cap do the hits need ranks (a scan of "survivor of its query's
+// t*"); a scan of the keep flags then places every kept hit and gives the new hit_off.
+
+struct ReportArgs {
+    const uint64_t* hit_off;  // [nq + 1] the chunk's public lists
+    uint64_t nq, n_s;
+    const uint32_t* pos;      // [n_s]
+    const uint8_t* d;         // [n_s] mismatches or distances, <= KMX_APPROX_MAX_SUBST
+    const uint8_t* strand;    // [n_s], NULL for one strand
+    uint32_t e, loci, best, max_hits;
+};
+
+constexpr uint8_t kReportDead = 0xFF;
+constexpr uint32_t kStrata = KMX_APPROX_MAX_SUBST + 1;
+
+// One thread per hit: its query (the block's range of queries first, as the verify kernels find their pieces), the LOCI rule
+// against the neighbours within e letters on its strand (one strand: at most e list neighbours per side, both: 2e + 1), and a
+// survivor's count into its query's stratum.  A neighbour to the left suppresses with d' <= d, one to the right with d' < d.
+__global__ __launch_bounds__(kBlock) void k_report_mark(ReportArgs A, uint32_t* __restrict__ hq, uint8_t* __restrict__ code,
+                                                        uint32_t* __restrict__ qcnt)
+{
+    __shared__ uint64_t s_range[2];
+    const uint64_t t0 = uint64_t(blockIdx.x) * kBlock, t_end = min(t0 + kBlock, A.n_s);
+    if (threadIdx.x == 0) {
+        s_range[0] = piece_of(A.hit_off, 0, A.nq, t0);
+        s_range[1] = piece_of(A.hit_off, s_range[0], A.nq, t_end - 1) + 1;
+    }
+    __syncthreads();
+    const uint64_t t = t0 + threadIdx.x;
+    if (t >= A.n_s) return;
+    const uint64_t q = piece_of(A.hit_off, s_range[0], s_range[1], t);
+    const uint32_t p = A.pos[t], d = A.d[t], e = A.e;
+    bool alive = true;
+    if (A.loci && e) {
+        const uint64_t a = A.hit_off[q], b = A.hit_off[q + 1];
+        const uint8_t s = A.strand ? A.strand[t] : uint8_t(0);
+        for (uint64_t u = t; alive && u-- > a;) {
+            const uint32_t p2 = A.pos[u];
+            if (p - p2 > e) break;
+            if (p2 != p && (!A.strand || A.strand[u] == s) && A.d[u] <= d) alive = false;
+        }
+        for (uint64_t u = t + 1; alive && u < b; ++u) {
+            const uint32_t p2 = A.pos[u];
+            if (p2 - p > e) break;
+            if (p2 != p && (!A.strand || A.strand[u] == s) && A.d[u] < d) alive = false;
+        }
+    }
+    hq[t] = uint32_t(q);
+    code[t] = alive ? uint8_t(d) : kReportDead;
+    if (alive) atomicAdd(&qcnt[q * kStrata + d], 1u);
+}
+
+// rule word of a query: quota in the threshold stratum (bits 0 .. 31), the threshold stratum t* (32 .. 39), the lowest stratum
+// kept (40 .. 47).  A survivor at distance d is kept when lo <= d < t*, or d == t* and its rank among the query's survivors
+// of t* is below the quota.
+__device__ __forceinline__ uint32_t rule_quota(uint64_t r) { return uint32_t(r); }
+__device__ __forceinline__ uint32_t rule_tstar(uint64_t r) { return uint32_t(r >> 32) & 0xFFu; }
+__device__ __forceinline__ uint32_t rule_lo(uint64_t r) { return uint32_t(r >> 40) & 0xFFu; }
+
+// One thread per query: found[q] = survivors after LOCI and BEST, and the query's rule word.
+__global__ __launch_bounds__(kBlock) void k_report_query(const uint32_t* __restrict__ qcnt, uint64_t nq, uint32_t best, uint32_t max_hits,
+                                                         uint64_t* __restrict__ found, uint64_t* __restrict__ rule)
+{
+    const uint64_t q = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (q >= nq) return;
+    uint32_t c[kStrata];
+#pragma unroll
+    for (uint32_t d = 0; d < kStrata; ++d) c[d] = qcnt[q * kStrata + d];
+    uint32_t lo = 0, hi = kStrata - 1;
+    if (best) {
+        while (lo < hi && c[lo] == 0) ++lo;
+        hi = lo;
+    }
+    uint64_t n = 0;
+    for (uint32_t d = lo; d <= hi; ++d) n += c[d];
+    uint32_t tstar = hi, quota = 0xFFFFFFFFu;
+    if (max_hits && n > max_hits) {
+        uint32_t acc = 0;
+        for (uint32_t d = lo; d <= hi; ++d) {
+            if (acc + c[d] >= max_hits) { tstar = d; quota = max_hits - acc; break; }
+            acc += c[d];
+        }
+    }
+    found[q] = n;
+    rule[q] = uint64_t(quota) | (uint64_t(tstar) << 32) | (uint64_t(lo) << 40);
+}
+
+// ind[t] = 1 for a survivor of its query's threshold stratum (the only hits whose rank matters)
+__global__ __launch_bounds__(kBlock) void k_report_ind(const uint8_t* __restrict__ code, const uint32_t* __restrict__ hq,
+                                                       const uint64_t* __restrict__ rule, uint64_t n_s, uint32_t* __restrict__ ind)
+{
+    const uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (t < n_s) ind[t] = code[t] == rule_tstar(rule[hq[t]]) ? 1u : 0u;
+}
+
+// keep[t]; rscan is the exclusive scan of ind (NULL without a cap: no quota is finite)
+__global__ __launch_bounds__(kBlock) void k_report_keep(const uint8_t* __restrict__ code, const uint32_t* __restrict__ hq,
+                                                        const uint64_t* __restrict__ rule, const uint64_t* __restrict__ hit_off,
+                                                        const uint64_t* __restrict__ rscan, uint64_t n_s, uint32_t* __restrict__ keep)
+{
+    const uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (t >= n_s) return;
+    const uint32_t d = code[t], q = hq[t];
+    const uint64_t r = rule[q];
+    bool k = d != kReportDead && d >= rule_lo(r) && d <= rule_tstar(r);
+    if (k && rscan && d == rule_tstar(r)) k = rscan[t] - rscan[hit_off[q]] < rule_quota(r);
+    keep[t] = k ? 1u : 0u;
+}
+
+// dest is the exclusive scan of keep (dest[n_s] = the hits kept): every kept hit to its slot, threads 0 .. nq the new hit_off.
+__global__ __launch_bounds__(kBlock) void k_report_compact(ReportArgs A, const uint32_t* __restrict__ len_in, const uint32_t* __restrict__ keep,
+                                                           const uint64_t* __restrict__ dest, uint32_t* __restrict__ pos_out,
+                                                           uint8_t* __restrict__ d_out, uint32_t* __restrict__ len_out,
+                                                           uint8_t* __restrict__ strand_out, uint64_t* __restrict__ hit_off_out)
+{
+    const uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (t <= A.nq) hit_off_out[t] = dest[A.hit_off[t]];
+    if (t >= A.n_s || !keep[t]) return;
+    const uint64_t at = dest[t];
+    pos_out[at] = A.pos[t];
+    d_out[at] = A.d[t];
+    if (len_in) len_out[at] = len_in[t];
+    if (A.strand) strand_out[at] = A.strand[t];
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
 // host side
 
 void kmx::packed_text_release(PackedText* t)
@@ -877,6 +1010,15 @@ namespace {
 struct EditBufs {
     Buf keep, bcount, bsum, bscan, total, ka, va, kb, vb, ukeys, olen;
 };
+// what kmx_search_approx_opts asks for beyond the older entry points (they pass a default-constructed one)
+struct ReportOpts {
+    bool api = false, loci = false, best = false;
+    uint32_t max_hits = 0;
+    bool on() const { return loci || best || max_hits != 0; }
+};
+struct ReportBufs {
+    Buf hq, code, qcnt, rule, found, flag, rscan, dest, bsum, total, off, pos, d, len, strand;
+};
 inline uint32_t bit_width(uint64_t x) { uint32_t b = 0; while (x) { ++b; x >>= 1; } return b; }
 } // namespace
 
@@ -939,6 +1081,57 @@ static kmx_status edit_chunk(hipStream_t s, EditArgs V, uint32_t w, uint64_t nq,
     return KMX_OK;
 }
 
+// The reporting stage of one chunk with hits: the lists of P filtered into B.off / B.pos / B.d / B.len / B.strand, found[] of
+// the chunk's queries into B.found, *n_hits <- the hits kept.
+static kmx_status report_chunk(hipStream_t s, const ReportArgs& P, const uint32_t* len_in, ReportBufs& B, PinnedArr& h_total, uint64_t* n_hits)
+{
+    const uint64_t n_s = P.n_s, nq = P.nq;
+    AX_TRY(B.hq.ensure(n_s * 4));
+    AX_TRY(B.code.ensure(n_s));
+    AX_TRY(B.qcnt.ensure(nq * kStrata * 4));
+    AX_TRY(B.rule.ensure(nq * 8));
+    AX_TRY(B.found.ensure(nq * 8));
+    AX_TRY(B.flag.ensure(n_s * 4 + 16));
+    AX_TRY(B.dest.ensure((n_s + 1) * 8));
+    AX_TRY(B.bsum.ensure(kmx::scan_blocks(n_s) * 8 + 16));
+    AX_TRY(B.total.ensure(16));
+    AX_TRY(B.off.ensure((nq + 1) * 8));
+    const unsigned hit_blocks = grid_for(n_s, kBlock);
+    AX_TRY(hipMemsetAsync(B.qcnt.p, 0, nq * kStrata * 4, s));
+    hipLaunchKernelGGL(k_report_mark, dim3(hit_blocks), dim3(kBlock), 0, s, P, B.hq.as<uint32_t>(), B.code.as<uint8_t>(), B.qcnt.as<uint32_t>());
+    AX_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_report_query, dim3(grid_for(nq, kBlock)), dim3(kBlock), 0, s, B.qcnt.as<uint32_t>(), nq, P.best, P.max_hits,
+                       B.found.as<uint64_t>(), B.rule.as<uint64_t>());
+    AX_TRY(hipGetLastError());
+    const uint64_t* rscan = nullptr;
+    if (P.max_hits) {
+        AX_TRY(B.rscan.ensure((n_s + 1) * 8));
+        hipLaunchKernelGGL(k_report_ind, dim3(hit_blocks), dim3(kBlock), 0, s, B.code.as<uint8_t>(), B.hq.as<uint32_t>(), B.rule.as<uint64_t>(), n_s,
+                           B.flag.as<uint32_t>());
+        AX_TRY(hipGetLastError());
+        kmx::launch_scan(s, B.flag.as<uint32_t>(), n_s, B.bsum.as<uint64_t>(), B.rscan.as<uint64_t>(), B.total.as<unsigned long long>());
+        AX_TRY(hipGetLastError());
+        rscan = B.rscan.as<uint64_t>();
+    }
+    hipLaunchKernelGGL(k_report_keep, dim3(hit_blocks), dim3(kBlock), 0, s, B.code.as<uint8_t>(), B.hq.as<uint32_t>(), B.rule.as<uint64_t>(), P.hit_off,
+                       rscan, n_s, B.flag.as<uint32_t>());
+    AX_TRY(hipGetLastError());
+    kmx::launch_scan(s, B.flag.as<uint32_t>(), n_s, B.bsum.as<uint64_t>(), B.dest.as<uint64_t>(), B.total.as<unsigned long long>());
+    AX_TRY(hipGetLastError());
+    AX_TRY(hipMemcpyAsync(h_total.p, B.total.p, 8, hipMemcpyDeviceToHost, s));
+    AX_TRY(hipStreamSynchronize(s));
+    const uint64_t n_keep = h_total.as<uint64_t>()[0];
+    AX_TRY(B.pos.ensure(n_keep * 4 + 16));
+    AX_TRY(B.d.ensure(n_keep + 16));
+    if (len_in) AX_TRY(B.len.ensure(n_keep * 4 + 16));
+    if (P.strand) AX_TRY(B.strand.ensure(n_keep + 16));
+    hipLaunchKernelGGL(k_report_compact, dim3(grid_for(std::max(n_s, nq + 1), kBlock)), dim3(kBlock), 0, s, P, len_in, B.flag.as<uint32_t>(),
+                       B.dest.as<uint64_t>(), B.pos.as<uint32_t>(), B.d.as<uint8_t>(), B.len.as<uint32_t>(), B.strand.as<uint8_t>(), B.off.as<uint64_t>());
+    AX_TRY(hipGetLastError());
+    *n_hits = n_keep;
+    return KMX_OK;
+}
+
 extern "C" {
 
 kmx_status kmx_index_text(const kmx_index* index, uint8_t* out_ranks, uint64_t n, uint64_t* packed_bytes)
@@ -968,7 +1161,8 @@ kmx_status kmx_index_text(const kmx_index* index, uint8_t* out_ranks, uint64_t n
 // kmx_search_approx (complement == NULL) and kmx_search_approx_strands (the table given): S = 1 or 2 internal queries per
 // query of the caller.  `fn` names the entry point in error messages.
 static kmx_status approx_search(const char* fn, const kmx_index* index, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq,
-                                uint32_t max_subst, uint32_t flags, const uint8_t* complement, kmx_approx_result** out)
+                                uint32_t max_subst, uint32_t flags, const uint8_t* complement, const ReportOpts& rep,
+                                kmx_approx_result** out)
 {
     const std::string who = std::string(fn) + ": ";
     if (max_subst > KMX_APPROX_MAX_SUBST) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "max_subst > KMX_APPROX_MAX_SUBST");
@@ -1016,6 +1210,9 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
     R->nq = nq;
     R->edit = edit;
     R->strands = complement != nullptr;
+    R->opts = rep.api;
+    R->reported = rep.on();
+    if (rep.on() && !R->found.grow((nq + 1) * 8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
     if (complement && !R->strand.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
     if (edit && !R->lengths.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
     if (!R->hit_off.grow((nq + 1) * 8) || !R->status.grow(nq + 1) || !R->positions.grow(64) || !R->mismatches.grow(64))
@@ -1030,6 +1227,7 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
         AX_TRY(hipMemcpyAsync(d_comp.p, comp, 256, hipMemcpyHostToDevice, s));
     }
     EditBufs eb;
+    ReportBufs rb;
     PinnedArr h_qcand, h_total;
     if (!h_total.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
     ResultGuard pres;
@@ -1149,6 +1347,7 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
             }
             // what goes to the host: the chunk's arrays as they are, or (both strands) each pair's two lists merged
             const void *o_hit_off = d_hit_off.p, *o_pos = d_opos.p, *o_d = d_omm.p, *o_len = eb.olen.p, *o_stat = d_qstat.as<uint8_t>() + a;
+            const void* o_strand = nullptr;
             if (S == 2) {
                 AX_TRY(d_pub_off.ensure((b - a + 1) * 8));
                 if (n_s) {
@@ -1165,9 +1364,22 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
                     AX_TRY(hipMemsetAsync(d_pub_off.p, 0, (b - a + 1) * 8, s));
                 }
                 o_hit_off = d_pub_off.p; o_pos = d_mpos.p; o_d = d_md.p; o_len = d_mlen.p; o_stat = d_pair_stat.as<uint8_t>() + a;
+                o_strand = d_mstrand.p;
+            }
+            const uint64_t q_at = Q0 + a, h_at = R->n_hits;
+            if (rep.on() && n_s) {
+                // the reporting stage: the lists above filtered and compacted, found[] of the chunk's queries to the host
+                ReportArgs P{static_cast<const uint64_t*>(o_hit_off), b - a, n_s, static_cast<const uint32_t*>(o_pos),
+                             static_cast<const uint8_t*>(o_d), static_cast<const uint8_t*>(o_strand), e, rep.loci, rep.best, rep.max_hits};
+                st = report_chunk(s, P, edit ? static_cast<const uint32_t*>(o_len) : nullptr, rb, h_total, &n_s);
+                if (st != KMX_OK) return st;
+                o_hit_off = rb.off.p; o_pos = rb.pos.p; o_d = rb.d.p; o_len = rb.len.p;
+                if (S == 2) o_strand = rb.strand.p;
+                AX_TRY(hipMemcpyAsync(R->found.as<uint64_t>() + q_at, rb.found.p, (b - a) * 8, hipMemcpyDeviceToHost, s));
+            } else if (rep.on()) {
+                std::memset(R->found.as<uint64_t>() + q_at, 0, (b - a) * 8);
             }
             // this chunk's part of the result to the host arrays
-            const uint64_t q_at = Q0 + a, h_at = R->n_hits;
             if (!R->positions.grow((h_at + n_s) * 4 + 64) || !R->mismatches.grow(h_at + n_s + 64))
                 return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
             if (edit && !R->lengths.grow((h_at + n_s) * 4 + 64))
@@ -1180,7 +1392,7 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
                 AX_TRY(hipMemcpyAsync(R->positions.as<uint32_t>() + h_at, o_pos, n_s * 4, hipMemcpyDeviceToHost, s));
                 AX_TRY(hipMemcpyAsync(R->mismatches.as<uint8_t>() + h_at, o_d, n_s, hipMemcpyDeviceToHost, s));
                 if (edit) AX_TRY(hipMemcpyAsync(R->lengths.as<uint32_t>() + h_at, o_len, n_s * 4, hipMemcpyDeviceToHost, s));
-                if (S == 2) AX_TRY(hipMemcpyAsync(R->strand.as<uint8_t>() + h_at, d_mstrand.p, n_s, hipMemcpyDeviceToHost, s));
+                if (S == 2) AX_TRY(hipMemcpyAsync(R->strand.as<uint8_t>() + h_at, o_strand, n_s, hipMemcpyDeviceToHost, s));
             }
             AX_TRY(hipStreamSynchronize(s));
             for (uint64_t i = 0; i <= b - a; ++i) ho[i] += h_at;
@@ -1200,7 +1412,7 @@ kmx_status kmx_search_approx(const kmx_index* index, const uint8_t* qranks, cons
                              uint32_t flags, kmx_approx_result** out)
 {
     if (!index || !out) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx: NULL argument");
-    return approx_search("kmx_search_approx", index, qranks, qoff, nq, max_subst, flags, nullptr, out);
+    return approx_search("kmx_search_approx", index, qranks, qoff, nq, max_subst, flags, nullptr, ReportOpts(), out);
 }
 
 kmx_status kmx_search_approx_strands(const kmx_index* index, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq, uint32_t max_subst,
@@ -1208,7 +1420,40 @@ kmx_status kmx_search_approx_strands(const kmx_index* index, const uint8_t* qran
 {
     if (!index || !out) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx_strands: NULL argument");
     if (!complement) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx_strands: NULL complement table");
-    return approx_search("kmx_search_approx_strands", index, qranks, qoff, nq, max_subst, flags, complement, out);
+    return approx_search("kmx_search_approx_strands", index, qranks, qoff, nq, max_subst, flags, complement, ReportOpts(), out);
+}
+
+kmx_status kmx_search_approx_opts(const kmx_index* index, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq,
+                                  const kmx_approx_options* options, kmx_approx_result** out)
+{
+    if (!index || !out) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx_opts: NULL argument");
+    if (!options) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx_opts: NULL options");
+    if (options->struct_size < sizeof(kmx_approx_options))
+        return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx_opts: struct_size is smaller than kmx_approx_options");
+    const uint32_t flags = options->flags;
+    if (flags & ~uint32_t(KMX_APPROX_EDIT | KMX_APPROX_LOCI | KMX_APPROX_BEST))
+        return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx_opts: unknown flag bits");
+    if ((flags & KMX_APPROX_LOCI) && !(flags & KMX_APPROX_EDIT))
+        return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_search_approx_opts: KMX_APPROX_LOCI needs KMX_APPROX_EDIT");
+    ReportOpts rep;
+    rep.api = true;
+    rep.loci = (flags & KMX_APPROX_LOCI) != 0;
+    rep.best = (flags & KMX_APPROX_BEST) != 0;
+    rep.max_hits = options->max_hits;
+    return approx_search("kmx_search_approx_opts", index, qranks, qoff, nq, options->max_subst, flags & KMX_APPROX_EDIT, options->complement, rep, out);
+}
+
+kmx_status kmx_approx_found(kmx_approx_result* r, const uint64_t** found)
+{
+    if (!r) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_approx_found: result is NULL");
+    if (!r->opts) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_approx_found: the result is not one of kmx_search_approx_opts");
+    if (!r->reported && r->found_lazy.size() != r->nq + 1) {     // no option was set: the list lengths
+        const uint64_t* ho = r->hit_off.as<uint64_t>();
+        r->found_lazy.assign(r->nq + 1, 0);
+        for (uint64_t i = 0; i < r->nq; ++i) r->found_lazy[i] = ho[i + 1] - ho[i];
+    }
+    if (found) *found = r->reported ? r->found.as<uint64_t>() : r->found_lazy.data();
+    return KMX_OK;
 }
 
 kmx_status kmx_approx_counts(const kmx_approx_result* r, uint64_t* nq, uint64_t* n_hits, uint64_t* n_candidates, uint32_t* n_chunks)

@@ -19,6 +19,7 @@ KIND_NONE, KIND_EXACT, KIND_STITCH, KIND_PREFIX = 0, 1, 2, 3
 Q_OK, Q_TOO_LONG, Q_SUBK_FANOUT, Q_EMPTY_QUERY, Q_BAD_RANK, Q_TOO_SHORT = 0, 1, 2, 3, 4, 5
 APPROX_MAX_SUBST = 3
 APPROX_EDIT = 1
+APPROX_LOCI, APPROX_BEST = 2, 4
 TILE_Q_NONE, TILE_Q_PARTITION, TILE_Q_SCAN = 0, 1, 2
 
 # every symbol include/kmx.h declares
@@ -31,6 +32,7 @@ EXPORTS = [
     "kmx_index_bucket_host", "kmx_index_levels", "kmx_result_gather_device",
     "kmx_search_approx", "kmx_approx_counts", "kmx_approx_view", "kmx_approx_free", "kmx_index_text",
     "kmx_approx_lengths", "kmx_search_approx_strands", "kmx_approx_strands",
+    "kmx_search_approx_opts", "kmx_approx_found",
     "kmx_index_paths", "kmx_result_paths",
 ]
 
@@ -46,6 +48,11 @@ class Options(C.Structure):
                 ("n_threads", C.c_uint32), ("query_size_range", C.c_uint32), ("keep_host_arena", C.c_uint32),
                 ("host_flatten", C.c_uint32), ("no_aligned_copy", C.c_uint32),
                 ("n_devices", C.c_uint32), ("devices", C.c_int32 * KMX_MAX_DEVICES), ("prefix_levels", C.c_int32)]
+
+
+class ApproxOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_subst", C.c_uint32), ("flags", C.c_uint32), ("max_hits", C.c_uint32),
+                ("complement", C.c_void_p)]
 
 
 class KernelStat(C.Structure):
@@ -143,6 +150,10 @@ def lib():
         L.kmx_search_approx_strands.argtypes = [vp, vp, vp, u64, u32, u32, vp, P(vp)]
         L.kmx_approx_strands.restype = C.c_int
         L.kmx_approx_strands.argtypes = [vp, P(vp)]
+        L.kmx_search_approx_opts.restype = C.c_int
+        L.kmx_search_approx_opts.argtypes = [vp, vp, vp, u64, P(ApproxOptions), P(vp)]
+        L.kmx_approx_found.restype = C.c_int
+        L.kmx_approx_found.argtypes = [vp, P(vp)]
         L.kmx_index_paths.restype = C.c_int
         L.kmx_index_paths.argtypes = [vp, P(IndexPathInfo)]
         L.kmx_result_paths.restype = C.c_int
@@ -361,6 +372,13 @@ class ApproxResult:
         _check(lib().kmx_approx_strands(self._h, C.byref(p)))
         return _view(p.value, self.counts()["n_hits"], np.uint8).copy()
 
+    def found(self):
+        """kmx_approx_found: per query the hits left after loci / best and before the max_hits cap (u64[nq]) of a search with
+        any of the three reporting options; more than the query's list holds when the cap cut it."""
+        p = C.c_void_p()
+        _check(lib().kmx_approx_found(self._h, C.byref(p)))
+        return _view(p.value, self.counts()["nq"], np.uint64).copy()
+
     def close(self):
         if self._h:
             lib().kmx_approx_free(self._h)
@@ -482,18 +500,28 @@ class Index:
         r._index = self
         return r
 
-    def search_approx(self, qranks, qoff, max_subst, edit=False, strands=False, complement=None):
+    def search_approx(self, qranks, qoff, max_subst, edit=False, strands=False, complement=None, loci=False, best=False, max_hits=0):
         """kmx_search_approx: every window within Hamming distance max_subst (<= APPROX_MAX_SUBST) of each query; edit=True
         (KMX_APPROX_EDIT): every start of a window within that many edits, its distance in `mismatches`, ApproxResult.lengths().
         strands=True (kmx_search_approx_strands): the same for each query and its reverse complement under `complement`
-        (rank to rank, uint8[sigma]; default complement_table(sigma)), hits ordered by (position, strand), ApproxResult.strands()."""
+        (rank to rank, uint8[sigma]; default complement_table(sigma)), hits ordered by (position, strand), ApproxResult.strands().
+        loci / best / max_hits (kmx_search_approx_opts; any of them routes there): one hit per alignment locus (edit only), the
+        best stratum only, at most max_hits hits per query; ApproxResult.found() tells what the cap cut."""
         qranks = np.ascontiguousarray(qranks, np.uint8)
         qoff = np.ascontiguousarray(qoff, np.uint64)
         r = ApproxResult()
+        comp = None
         if strands:
             comp = np.ascontiguousarray(complement_table(self.sigma) if complement is None else complement, np.uint8)
             if comp.size != self.sigma:
                 raise ValueError("search_approx: the complement table needs sigma entries")
+        if loci or best or max_hits:
+            flags = (APPROX_EDIT if edit else 0) | (APPROX_LOCI if loci else 0) | (APPROX_BEST if best else 0)
+            o = ApproxOptions(C.sizeof(ApproxOptions), int(max_subst), flags, int(max_hits), comp.ctypes.data if strands else None)
+            _check(lib().kmx_search_approx_opts(self._h, qranks.ctypes.data if qranks.size else None, qoff.ctypes.data, qoff.size - 1,
+                                                C.byref(o), C.byref(r._h)))
+            return r
+        if strands:
             _check(lib().kmx_search_approx_strands(self._h, qranks.ctypes.data if qranks.size else None, qoff.ctypes.data,
                                                    qoff.size - 1, int(max_subst), APPROX_EDIT if edit else 0, comp.ctypes.data, C.byref(r._h)))
             return r

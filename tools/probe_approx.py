@@ -18,6 +18,10 @@ to end, piece hits, chunks, hits per strand, and the check that every read's sou
 reverse complement of every read on the host, kmx_search_approx of that batch, and a numpy merge of the two results by
 (query, position, strand); it uses only kmx_search_approx, so it also runs against a library that lacks the new symbol.
 --no-plain skips the single-strand legs.
+--report (with --edit) times, on every leg's edit reads, the reporting call (kmx_search_approx_opts) with loci + best and with
+loci + best + max_hits = 1 next to the plain KMX_APPROX_EDIT call of the same run and the numpy pass a caller runs on the
+plain result to get the same answer (host_report): end-to-end times, hits returned against the plain call's, bytes copied to
+the host, whether the arrays equal the host filter's, and how many reads have a returned hit within e of their planted start.
 For a kernel trace run one leg with --passes 1 under rocprofv3 --kernel-trace --stats."""
 import argparse
 import json
@@ -88,6 +92,77 @@ def host_merge(nq, fwd, rev):
     out_ho[1:] = fwd[0][1:] + rev[0][1:]
     merged = [np.concatenate([c[k] for c in cols])[order] for k in range(len(cols[0]))]
     return out_ho, ((keys >> np.uint64(1)) & np.uint64(0xFFFFFFFF)).astype(np.uint32), (keys & np.uint64(1)).astype(np.uint8), merged
+
+
+def host_report(nq, e, ho, pos, dist, lens, max_hits):
+    """loci + best (+ cap) of a one-strand KMX_APPROX_EDIT result with numpy, as a caller without kmx_search_approx_opts does
+    it: (hit_off, positions, distances, lengths, found).  One-strand lists ascend strictly, so the hits within e letters of a
+    hit are among its e list neighbours on each side."""
+    nh = pos.size
+    qi = np.repeat(np.arange(nq, dtype=np.int64), np.diff(ho).astype(np.int64))
+    p, d = pos.astype(np.int64), dist.astype(np.int64)
+    alive = np.ones(nh, bool)
+    for j in range(1, e + 1):
+        near = (qi[j:] == qi[:-j]) & (p[j:] - p[:-j] <= e)
+        alive[j:] &= ~(near & (d[:-j] <= d[j:]))             # a left neighbour at no greater distance
+        alive[:-j] &= ~(near & (d[j:] < d[:-j]))             # a right neighbour at a smaller one
+    least = np.full(nq, 255, np.int64)
+    np.minimum.at(least, qi[alive], d[alive])
+    keep = alive & (d == least[qi])
+    found = np.bincount(qi[keep], minlength=nq).astype(np.uint64)
+    if max_hits:                                             # one stratum is left: the first max_hits of each list
+        c = np.cumsum(keep) - keep
+        first = np.concatenate([[0], np.cumsum(np.bincount(qi, minlength=nq))])[:-1]
+        rank = c - np.where(first < nh, c[np.minimum(first, max(nh - 1, 0))], 0)[qi]
+        keep &= rank < max_hits
+    out_ho = np.zeros(nq + 1, np.uint64)
+    np.cumsum(np.bincount(qi[keep], minlength=nq), out=out_ho[1:])
+    return out_ho, pos[keep], dist[keep], lens[keep], found
+
+
+def sources_near(ho, pos, start, e):
+    """How many reads have a hit within e letters of their planted start."""
+    nq = start.size
+    qi = np.repeat(np.arange(nq, dtype=np.int64), np.diff(ho).astype(np.int64))
+    near = np.abs(pos.astype(np.int64) - start.astype(np.int64)[qi]) <= e
+    return int(np.count_nonzero(np.bincount(qi[near], minlength=nq)))
+
+
+def report_legs(idx, nq, m, e, q, off, start, passes):
+    """--report: the plain edit call + host_report against the reporting call, loci + best and loci + best + max_hits = 1."""
+    box = {}
+
+    def plain():
+        r = idx.search_approx(q, off, e, edit=True)
+        box["plain"] = r.host() + (r.lengths(),)
+        r.close()
+
+    t_plain = median_time(plain, passes)
+    p_min, p_max = median_time.spread
+    ho, pos, dist, st, lens = box["plain"]
+    rec = {"plain": {"median_s": round(t_plain, 5), "min_s": round(p_min, 5), "max_s": round(p_max, 5), "spread_s": round(p_max - p_min, 5),
+                     "n_hits": int(pos.size), "bytes_to_host": int((nq + 1) * 8 + nq + pos.size * 9),
+                     "sources_near": sources_near(ho, pos, start, e)}}
+    margin = max(0.03 * t_plain, p_max - p_min)
+    for name, max_hits in (("loci_best", 0), ("loci_best_max1", 1)):
+        def call():
+            r = idx.search_approx(q, off, e, edit=True, loci=True, best=True, max_hits=max_hits)
+            box["rep"] = r.host() + (r.lengths(), r.found())
+            box["counts"] = r.counts()
+            r.close()
+
+        t = median_time(call, passes)
+        t_min, t_max = median_time.spread
+        t_filter = median_time(lambda: box.__setitem__("want", host_report(nq, e, ho, pos, dist, lens, max_hits)), passes)
+        rho, rpos, rdist, rst, rlens, rfound = box["rep"]
+        same = all(np.array_equal(x, y) for x, y in zip(box["want"], (rho, rpos, rdist, rlens, rfound))) and np.array_equal(rst, st)
+        rec[name] = {"median_s": round(t, 5), "min_s": round(t_min, 5), "max_s": round(t_max, 5), "n_hits": int(rpos.size),
+                     "hits_vs_plain": round(rpos.size / max(pos.size, 1), 4), "bytes_to_host": int((nq + 1) * 8 + nq + rpos.size * 9 + nq * 8),
+                     "n_chunks": box["counts"]["n_chunks"], "reads_cut_by_cap": int(np.sum(rfound > np.diff(rho))),
+                     "sources_near": sources_near(rho, rpos, start, e), "host_filter_median_s": round(t_filter, 5),
+                     "plain_plus_host_filter_s": round(t_plain + t_filter, 5), "equals_host_filter": bool(same),
+                     "vs_plain": round(t / t_plain, 3), "within_margin_of_plain": bool(t <= t_plain + margin)}
+    return rec
 
 
 def strand_legs(idx, text, leg, edit, args, comp):
@@ -164,6 +239,7 @@ def main():
     ap.add_argument("--strands", action="store_true", help="time the both-strand search (kmx_search_approx_strands) of every leg")
     ap.add_argument("--baseline", action="store_true", help="time two plain calls + host reverse complement + host merge on the strand reads")
     ap.add_argument("--no-plain", action="store_true", help="skip the single-strand legs")
+    ap.add_argument("--report", action="store_true", help="with --edit: time the reporting call (loci + best, + max_hits = 1) against the plain call")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     n, sigma = 100_000_000, 4
@@ -236,6 +312,8 @@ def main():
                            "hits_other_length": int(np.sum(box["lengths"] != m)), "n_chunks": c2["n_chunks"],
                            "status_ok": int(np.sum(st2 == engine.Q_OK)), "sources_found": sources_found(ho2, pos2, start2.astype(np.uint64)),
                            "slowdown_vs_hamming": round(t2 / t, 3)}
+            if args.report:
+                rec["report"] = report_legs(idx, nq, m, e, q2, off2, start2, args.passes)
         if args.strands or args.baseline:
             rec["both_strands"] = strand_legs(idx, text, leg, False, args, comp)
             if args.edit:

@@ -332,6 +332,17 @@ typedef struct kmx_result_path_info {
     uint32_t spec_ok;           /* ... and its output was kept (no second k_fill; also when the batch has no hits at all)    */
     uint32_t fill_blocks;       /* grid of the k_fill whose output was kept (blocks beyond the hit total leave at once)      */
     uint32_t fill_tiles;        /* tiles that hold hits: ceil(n_hits / (256 x fill_slots))                                   */
+    /* The batch's sub-k (KMX_KIND_PREFIX) queries by the merger their slice went to (len = positions of the slice without the
+     * last-kmer positions, R = its runs), from the counters the search reads back anyway:                                    */
+    uint32_t prefix_plain;       /* R < 2 or len < 2: one list (a prefix level's, or the only key), copied as it lies        */
+    uint32_t prefix_small;       /* len <= 2048, not of the next class: k_prefix_sort_small (one wave)                        */
+    uint32_t prefix_merge_small; /* len <= 2048, 2 .. 32 runs of 8 positions or more on average, beyond 4 runs / 512
+                                    positions: k_prefix_merge_small                                                          */
+    uint32_t prefix_mid;         /* 2048 < len <= 8192: k_prefix_sort_block, a block per slice                                */
+    uint32_t prefix_long;        /* len > 8192: one chunk (len <= 32768) or, beyond, value bands, a spread by value or chunks
+                                    + merge passes — which of the three is decided on the device and not read back           */
+    uint32_t prefix_large_chunks;/* the most chunks of 32768 positions any slice of the batch has (0: no slice beyond one)    */
+    uint64_t prefix_large_elems; /* positions of the slices beyond one chunk (len > 32768), summed                            */
 } kmx_result_path_info;
 #define KMX_TILE_Q_NONE 0u
 #define KMX_TILE_Q_PARTITION 1u

@@ -250,7 +250,8 @@ struct kmx_result {
     bool last_had_stitch = false;          // adaptive speculation: see kmx_search_batch_device
     bool last_had_long = false;            // ... or queries of very many parts (k_lookup_long)
     bool last_had_pairs = false;           // the previous batch held cross-referenced queries: k_lookup's variant (kmx_search_batch_device)
-    struct PathRec { uint32_t small = 0, items = 0, pairs = 0, defer_long = 0, tile_q_source = 0, spec_fill = 0, spec_ok = 0, fill_blocks = 0, fill_tiles = 0; };
+    struct PathRec { uint32_t small = 0, items = 0, pairs = 0, defer_long = 0, tile_q_source = 0, spec_fill = 0, spec_ok = 0, fill_blocks = 0, fill_tiles = 0;
+                     uint32_t p_plain = 0, p_small = 0, p_merge = 0, p_mid = 0, p_long = 0, p_chunks = 0; uint64_t p_elems = 0; };
     PathRec path;                          // which variants the last search ran (kmx_result_paths)
     std::shared_ptr<ResultPool> pool;      // where kmx_result_free parks this result (set by the search that made it)
     SearchCtx ctx;                         // the half-done search of a KMX_SEARCH_ASYNC call (search_finish completes it)
@@ -1391,6 +1392,8 @@ kmx_status kmx_result_paths(const kmx_result* r, kmx_result_path_info* out)
     v.small = r->path.small; v.lookup_items = r->path.items; v.lookup_pairs = r->path.pairs; v.deferred_long = r->path.defer_long;
     v.tile_q_source = r->path.tile_q_source; v.spec_fill = r->path.spec_fill; v.spec_ok = r->path.spec_ok;
     v.fill_blocks = r->path.fill_blocks; v.fill_tiles = r->path.fill_tiles;
+    v.prefix_plain = r->path.p_plain; v.prefix_small = r->path.p_small; v.prefix_merge_small = r->path.p_merge; v.prefix_mid = r->path.p_mid;
+    v.prefix_long = r->path.p_long; v.prefix_large_chunks = r->path.p_chunks; v.prefix_large_elems = r->path.p_elems;
     v.struct_size = std::min<uint32_t>(out->struct_size, uint32_t(sizeof v));
     memcpy(out, &v, v.struct_size);
     return KMX_OK;
@@ -1631,6 +1634,16 @@ static kmx_status search_finish(kmx_result* r)
     r->n_exact = nq - r->n_stitch - r->n_prefix - r->n_error - r->n_none;
     const uint64_t prefix_elems = r->h_ctr[KMX_CTR_PREFIX_ELEMS];
     const uint64_t max_runs = r->h_ctr[KMX_CTR_MAX_RUNS];
+    {   // kmx_result_paths: the PREFIX slices by merger, as the dispatcher (k_lookup) counted them
+        const uint64_t n_merge = r->h_ctr[KMX_CTR_PREFIX_MERGE], n_mid = r->h_ctr[KMX_CTR_PREFIX_MID];
+        r->path.p_plain = uint32_t(r->h_ctr[KMX_CTR_PREFIX_PLAIN]);
+        r->path.p_merge = uint32_t(n_merge);
+        r->path.p_small = uint32_t(n_prefix_small - std::min(n_prefix_small, n_merge));
+        r->path.p_mid = uint32_t(n_mid);
+        r->path.p_long = uint32_t(n_prefix_big - std::min(n_prefix_big, n_mid));
+        r->path.p_chunks = uint32_t(prefix_elems ? max_runs : 0);
+        r->path.p_elems = prefix_elems;
+    }
 
     if (n_stitch_pending) {
         HIP_TRY(r->mask_words.ensure(r->n_mask_words * 8));

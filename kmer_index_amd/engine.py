@@ -67,7 +67,9 @@ class IndexPathInfo(C.Structure):
 class ResultPathInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("small", C.c_uint32), ("lookup_items", C.c_uint32), ("lookup_pairs", C.c_uint32),
                 ("deferred_long", C.c_uint32), ("tile_q_source", C.c_uint32), ("spec_fill", C.c_uint32), ("spec_ok", C.c_uint32),
-                ("fill_blocks", C.c_uint32), ("fill_tiles", C.c_uint32)]
+                ("fill_blocks", C.c_uint32), ("fill_tiles", C.c_uint32),
+                ("prefix_plain", C.c_uint32), ("prefix_small", C.c_uint32), ("prefix_merge_small", C.c_uint32), ("prefix_mid", C.c_uint32),
+                ("prefix_long", C.c_uint32), ("prefix_large_chunks", C.c_uint32), ("prefix_large_elems", C.c_uint64)]
 
 
 _lib = None
@@ -277,7 +279,10 @@ class Result:
         _check(lib().kmx_result_paths(self._h, C.byref(v)))
         return {"small": bool(v.small), "lookup_items": int(v.lookup_items), "lookup_pairs": bool(v.lookup_pairs),
                 "deferred_long": bool(v.deferred_long), "tile_q_source": int(v.tile_q_source), "spec_fill": bool(v.spec_fill),
-                "spec_ok": bool(v.spec_ok), "fill_blocks": int(v.fill_blocks), "fill_tiles": int(v.fill_tiles)}
+                "spec_ok": bool(v.spec_ok), "fill_blocks": int(v.fill_blocks), "fill_tiles": int(v.fill_tiles),
+                "prefix_plain": int(v.prefix_plain), "prefix_small": int(v.prefix_small), "prefix_merge_small": int(v.prefix_merge_small),
+                "prefix_mid": int(v.prefix_mid), "prefix_long": int(v.prefix_long), "prefix_large_chunks": int(v.prefix_large_chunks),
+                "prefix_large_elems": int(v.prefix_large_elems)}
 
     def host(self, copy=True):
         """(hit_off[nq+1], positions, status[nq], kinds[nq]) as numpy arrays: copies, or with copy=False views of the

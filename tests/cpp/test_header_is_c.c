@@ -26,5 +26,6 @@ int use_the_declarations(void)
     rp.struct_size = (uint32_t)sizeof rp;
     (void)kmx_index_paths(ix, &ip);
     if (kmx_result_paths(r, &rp) == KMX_OK && rp.tile_q_source == KMX_TILE_Q_SCAN) return 4;
+    if (rp.prefix_plain + rp.prefix_small + rp.prefix_merge_small + rp.prefix_mid + rp.prefix_long + rp.prefix_large_chunks + rp.prefix_large_elems == 1u) return 5;
     return (int)(kmx_fast_pow(4, 10) != 1048576u);
 }

@@ -314,6 +314,7 @@ typedef struct kmx_index_path_info {
     uint32_t scan_tile;         /* queries per block of the scan over the hit counts (a multiple of every lookup block)      */
     uint32_t n_ks;
     uint32_t cell_shift[KMX_MAX_KS]; /* per element (kmx_index_info's order): log2 of its cell size in positions, 0 = no cells */
+    uint32_t windows_tile;      /* windows per block of k_lookup_windows (kmx_search_windows): a divisor of scan_tile         */
 } kmx_index_path_info;
 kmx_status kmx_index_paths(const kmx_index* index, kmx_index_path_info* out);
 
@@ -491,6 +492,53 @@ typedef struct kmx_approx_options {
 kmx_status kmx_search_approx_opts(const kmx_index* index, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq,
                                   const kmx_approx_options* options, kmx_approx_result** out);
 kmx_status kmx_approx_found(kmx_approx_result* r, const uint64_t** found /* [nq] */);
+
+/* ---- every k-mer window of a batch of reads in one call: an extension, no reference interface (a caller detects the
+ *      capability by the macro KMX_SEARCH_WINDOWS, KMX_VERSION is unchanged).  What seeding a read mapper, k-mer containment and
+ *      read classification ask of the index is "where does this k-mer occur" for EVERY k-mer of every read; written out as
+ *      separate queries for kmx_search_batch that is len - k + 1 queries per read, each letter k times and 8 bytes of offset per
+ *      window.  These calls take the reads as they are.
+ *
+ *      ranks / roff[nr+1] are shaped like qranks / qoff: roff[0] = 0, ranks may be NULL when no read has a letter.  Read r has
+ *      len_r = roff[r+1] - roff[r] letters and contributes c_r = 0 windows if len_r < w, otherwise (len_r - w) / stride + 1;
+ *      window j of read r is ranks[roff[r] + j*stride, +w).  win_off[nr+1] is the exclusive prefix sum of c_r: window j of read
+ *      r is query win_off[r] + j of the result, and nq = win_off[nr].  The result is an ordinary kmx_result: kmx_result_counts,
+ *      kmx_result_view and kmx_result_view_device give hit_off[nq+1], positions, status[nq] and kinds[nq] array for array what
+ *      kmx_search_batch returns for the batch of those nq windows written out as separate queries, with the same flags.
+ *      Statuses are therefore KMX_Q_OK or KMX_Q_BAD_RANK (a window with a letter >= sigma), kinds KMX_KIND_EXACT or
+ *      KMX_KIND_NONE.  kmx_result_paths on such a result reports 0 in the k_lookup and prefix fields, the fill fields as usual.
+ *
+ *      Refused with KMX_ERR_INVALID_ARGUMENT before any device is touched: a NULL index, options or result pointer, a
+ *      struct_size that is too small, stride == 0, any flag bit other than KMX_SEARCH_COUNT_ONLY (KEEP_MASKS, ASYNC and
+ *      REFERENCE_PLAN have nothing to act on), a w that is not the k of an element of the index.  Refused after counting:
+ *      nq >= 2^32 - 1, and a single read with 2^32 or more windows.
+ *
+ *      Host form: uploads the reads and roff once — no copy with the windows written out is made on either side —, computes nq
+ *      on the host and runs the device form on a stream owned by the result.  It does not take the small-batch latency path and
+ *      does not stream in chunks: when the descriptors or hit lists do not fit the device it returns KMX_ERR_OUT_OF_MEMORY and
+ *      the caller splits the reads.  On an index with several replicas it runs on the first one.  *out as for kmx_search_batch
+ *      (NULL, or a handle to reuse).
+ *
+ *      Device form: d_ranks / d_roff are device pointers, all kernels go on `stream`, the replica is the one on the device
+ *      that owns d_ranks (as kmx_search_batch_device).  *inout reuses a handle's buffers; it is the handle type of
+ *      kmx_search_batch_device, and searches of both kinds may alternate on one handle.  The call costs one 8-byte read-back
+ *      (the window total) more than kmx_search_batch_device.
+ *
+ *      kmx_result_window_offsets: win_off on the host (copied on first use, valid until the handle is searched into again or
+ *      freed) and / or on the device, and nr; any pointer may be NULL.  KMX_ERR_INVALID_ARGUMENT on a result that is not from a
+ *      windows call. */
+#define KMX_SEARCH_WINDOWS 1
+typedef struct kmx_window_options {
+    uint32_t struct_size;   /* = sizeof(kmx_window_options) */
+    uint32_t w;             /* window length: must equal the k of one element of the index */
+    uint32_t stride;        /* >= 1: windows start at offsets 0, stride, 2*stride, ... of each read */
+    uint32_t flags;         /* KMX_SEARCH_DEFAULT or KMX_SEARCH_COUNT_ONLY */
+} kmx_window_options;
+kmx_status kmx_search_windows(const kmx_index* index, const uint8_t* ranks, const uint64_t* roff, uint64_t nr,
+                              const kmx_window_options* options, kmx_result** out);
+kmx_status kmx_search_windows_device(const kmx_index* index, const void* d_ranks, const void* d_roff, uint64_t nr,
+                                     const kmx_window_options* options, void* stream, kmx_result** inout);
+kmx_status kmx_result_window_offsets(kmx_result* r, const uint64_t** win_off, const uint64_t** d_win_off, uint64_t* nr);
 
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.

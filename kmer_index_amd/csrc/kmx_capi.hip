@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -112,11 +113,12 @@ struct HostBuf {
 
 enum KernelId {
     K_LOOKUP = 0, K_SCAN, K_PARTITION, K_FILL, K_VALIDATE, K_COMPACT, K_PREFIX_LEN, K_MERGE_PASS,
-    K_PREFIX_SORT_SMALL, K_PREFIX_MERGE_SMALL, K_PREFIX_SORT_BLOCK, K_SMALL, K_PREFIX_BANDS, K_PREFIX_SPLIT, K_COUNT
+    K_PREFIX_SORT_SMALL, K_PREFIX_MERGE_SMALL, K_PREFIX_SORT_BLOCK, K_SMALL, K_PREFIX_BANDS, K_PREFIX_SPLIT, K_LOOKUP_WINDOWS, K_COUNT
 };
+static_assert(K_COUNT <= KMX_N_KERNELS, "kmx_stats_get fills a caller's array of KMX_N_KERNELS entries");
 const char* const kKernelNames[K_COUNT] = {
     "k_lookup", "k_scan", "k_partition", "k_fill", "k_validate", "k_compact",
-    "k_prefix_len", "k_prefix_merge_pass", "k_prefix_sort_small", "k_prefix_merge_small", "k_prefix_sort_block", "k_small", "k_prefix_bands", "k_prefix_split"};
+    "k_prefix_len", "k_prefix_merge_pass", "k_prefix_sort_small", "k_prefix_merge_small", "k_prefix_sort_block", "k_small", "k_prefix_bands", "k_prefix_split", "k_lookup_windows"};
 
 struct Stats {
     bool enabled = false;
@@ -234,7 +236,7 @@ struct kmx_result {
     uint64_t n_mask_words = 0;
     // device
     DevBuf src, cnt, c0, aux, key, p1, kind, status, stitch_list, prefix_list, short_list, hit_off, bsum, ctr, tile_q, out,
-        mask_words, stitch_hits, plen, poff, ptmp, pitems, pbands, pcuts, pbanded, psplits, ptiles, pscnt, pscratch, pmid, in_qranks, in_qoff;
+        mask_words, stitch_hits, plen, poff, ptmp, pitems, pbands, pcuts, pbanded, psplits, ptiles, pscnt, pscratch, pmid, in_qranks, in_qoff, win_cnt, win_off;
     unsigned long long* h_ctr = nullptr;   // pinned
     // host mirrors
     HostBuf h_hit_off, h_positions, h_status, h_kinds, h_mask_base, h_mask_words, h_cand_count, h_cand_src, h_small;
@@ -247,6 +249,11 @@ struct kmx_result {
     DevBuf small_xchg;                     // the totals the workgroups of a multi-workgroup k_small launch exchange
     bool small_valid = false;              // the result of the last search lives in the mailbox only (no device buffers were written)
     bool host_valid = false, host_masks_valid = false;
+    // kmx_search_windows: the last search was one over the windows of win_nr reads — win_cnt (u32 per read) and win_off
+    // (win_nr + 1 window offsets, kmx_result_window_offsets) on the device, h_win_off their host copy once asked for
+    bool windows = false, h_win_valid = false;
+    uint64_t win_nr = 0;
+    HostBuf h_win_off;
     bool last_had_stitch = false;          // adaptive speculation: see kmx_search_batch_device
     bool last_had_long = false;            // ... or queries of very many parts (k_lookup_long)
     bool last_had_pairs = false;           // the previous batch held cross-referenced queries: k_lookup's variant (kmx_search_batch_device)
@@ -279,7 +286,7 @@ struct kmx_result {
     {
         size_t b = 0;
         for (const DevBuf* d : {&src, &cnt, &c0, &aux, &key, &p1, &kind, &status, &stitch_list, &prefix_list, &short_list, &hit_off, &bsum, &ctr,
-                                &tile_q, &out, &mask_words, &stitch_hits, &plen, &poff, &ptmp, &pitems, &pbands, &pcuts, &pbanded, &psplits, &ptiles, &pscnt, &pscratch, &pmid, &in_qranks, &in_qoff, &small_xchg})
+                                &tile_q, &out, &mask_words, &stitch_hits, &plen, &poff, &ptmp, &pitems, &pbands, &pcuts, &pbanded, &psplits, &ptiles, &pscnt, &pscratch, &pmid, &in_qranks, &in_qoff, &small_xchg, &win_cnt, &win_off})
             b += d->cap;
         return b;
     }
@@ -287,9 +294,9 @@ struct kmx_result {
     void release()
     {
         for (DevBuf* b : {&src, &cnt, &c0, &aux, &key, &p1, &kind, &status, &stitch_list, &prefix_list, &short_list, &hit_off, &bsum, &ctr,
-                          &tile_q, &out, &mask_words, &stitch_hits, &plen, &poff, &ptmp, &pitems, &pbands, &pcuts, &pbanded, &psplits, &ptiles, &pscnt, &pscratch, &pmid, &in_qranks, &in_qoff, &small_xchg})
+                          &tile_q, &out, &mask_words, &stitch_hits, &plen, &poff, &ptmp, &pitems, &pbands, &pcuts, &pbanded, &psplits, &ptiles, &pscnt, &pscratch, &pmid, &in_qranks, &in_qoff, &small_xchg, &win_cnt, &win_off})
             b->release();
-        for (HostBuf* b : {&h_hit_off, &h_positions, &h_status, &h_kinds, &h_mask_base, &h_mask_words, &h_cand_count, &h_cand_src, &h_small, &mailbox, &small_in})
+        for (HostBuf* b : {&h_hit_off, &h_positions, &h_status, &h_kinds, &h_mask_base, &h_mask_words, &h_cand_count, &h_cand_src, &h_small, &mailbox, &small_in, &h_win_off})
             b->release();
         if (h_ctr) (void)hipHostFree(h_ctr);
         h_ctr = nullptr;
@@ -1378,6 +1385,7 @@ kmx_status kmx_index_paths(const kmx_index* ix, kmx_index_path_info* out)
     v.scan_tile = uint32_t(kmx::scan_tile());
     v.n_ks = uint32_t(ix->ks.size());
     for (size_t i = 0; i < ix->ks.size(); ++i) v.cell_shift[i] = ix->h_header.elems[i].cnt8 ? ix->h_header.elems[i].cell_shift : 0u;
+    v.windows_tile = uint32_t(kmx::windows_tile());
     v.struct_size = std::min<uint32_t>(out->struct_size, uint32_t(sizeof v));
     memcpy(out, &v, v.struct_size);
     return KMX_OK;
@@ -1449,35 +1457,46 @@ kmx_status kmx_stats_reset(kmx_index* ix)
     return KMX_OK;
 }
 
-kmx_status kmx_search_batch_device(const kmx_index* cix, const void* d_qranks, const void* d_qoff, uint64_t nq,
-                                   uint32_t flags, void* stream, kmx_result** inout)
+// What every device-form search checks before it touches a buffer: the replica that serves the call (on an index with several,
+// the one on the device that owns `d_first`), and the result handle — a fresh one from the pool, or the caller's with its pending
+// search completed.  `fn` names the entry point in the error text.
+static kmx_status search_device_begin(const kmx_index* cix, const void* d_first, bool nonempty, kmx_result** inout, const char* fn, const char* what,
+                                      kmx_index** ix_out)
 {
-    if (!cix || !inout) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: NULL argument");
-    if (nq && (!d_qranks || !d_qoff)) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: NULL query buffers");
-    if (nq >= 0xFFFFFFFFull) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: at most 2^32-2 queries per batch");
+    const std::string f = std::string(fn) + ": ";
     kmx_index* ix = const_cast<kmx_index*>(cix);
     if (ix->broken) return fail(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
-    if (!ix->peers.empty() && nq) {
+    if (!ix->peers.empty() && nonempty) {
         // several replicas: the one that lives where the queries are
         hipPointerAttribute_t attr{};
-        if (hipPointerGetAttributes(&attr, d_qranks) != hipSuccess) { (void)hipGetLastError(); return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: d_qranks is not a device pointer"); }
+        if (hipPointerGetAttributes(&attr, d_first) != hipSuccess) { (void)hipGetLastError(); return fail(KMX_ERR_INVALID_ARGUMENT, f + what + " is not a device pointer"); }
         kmx_index* pick = nullptr;
         for (size_t i = 0; i < ix->n_replicas() && !pick; ++i)
             if (ix->replica(i)->device == attr.device) pick = ix->replica(i);
-        if (!pick) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: the queries live on a device that holds no replica of this index");
+        if (!pick) return fail(KMX_ERR_INVALID_ARGUMENT, f + "the queries live on a device that holds no replica of this index");
         ix = pick;
     }
     HIP_TRY(hipSetDevice(ix->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint8_t* qr = static_cast<const uint8_t*>(d_qranks);
-    const uint64_t* qo = static_cast<const uint64_t*>(d_qoff);
-
     kmx_result* r = *inout;
-    if (r && !r->parts.empty()) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: the result handle belongs to a multi-device search");
+    if (r && !r->parts.empty()) return fail(KMX_ERR_INVALID_ARGUMENT, f + "the result handle belongs to a multi-device search");
     if (r && r->device != ix->device && r->device_bytes())      // (whatever its last batch was: an empty one still owns buffers there)
-        return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: the result handle holds buffers on another device");
+        return fail(KMX_ERR_INVALID_ARGUMENT, f + "the result handle holds buffers on another device");
     if (!r) { r = take_result(ix); *inout = r; }
     else if (r->ctx.pending) { kmx_status fs = search_finish(r); if (fs != KMX_OK) return fs; }   // its buffers are about to be reused
+    *ix_out = ix;
+    return KMX_OK;
+}
+
+// First half of a device-form search of nq queries into r, on stream s: buffers, counter blocks, the LOOKUP STEP, the scan, the
+// speculative fill, the counter read-back; then search_finish (or, KMX_SEARCH_ASYNC, nothing more).  lookup(d, ctr, dix) enqueues
+// whatever writes QueryDesc::{src, cnt, kind, status, ...} and the counters, leaves block sums in r->bsum and returns the
+// queries-per-thread figure launch_scan_tiles needs to read them: k_lookup for kmx_search_batch_device (qr / qo: its queries,
+// which the stitch and prefix kernels of search_finish read again), k_lookup_windows for kmx_search_windows_device (no such
+// queries can come out of it: qr / qo are the reads and nothing looks at them).
+using LookupStep = std::function<int(const kmx::QueryDesc&, unsigned long long*, const KmxIndexDev*)>;
+static kmx_status search_device_run(kmx_index* ix, kmx_result* r, const uint8_t* qr, const uint64_t* qo, uint64_t nq, uint32_t flags, hipStream_t s,
+                                    const LookupStep& lookup)
+{
     r->index = ix;
     r->device = ix->device;
     r->stream = s;
@@ -1527,21 +1546,7 @@ kmx_status kmx_search_batch_device(const kmx_index* cix, const void* d_qranks, c
     auto* ctr_next = r->ctr.as<unsigned long long>() + (r->ctr_phase ^ 1u) * KMX_CTR_COUNT;
     const KmxIndexDev* dix = header_for(ix, flags);
 
-    // The k_lookup variant, from what the previous batch on this handle held (results do not depend on the choice): batches with
-    // two-part cross-referenced queries take the variant that interleaves and finishes them; without, the lean one — with eight
-    // queries per thread on an index of tiny cells (a query there is one byte of a table and one 32-byte cell).
-    static const int force_items = getenv("KMX_LOOKUP_ITEMS") ? atoi(getenv("KMX_LOOKUP_ITEMS")) : 0;      // (tuning / tests: 4 | 8, or -4: 4 with pairs)
-    const bool pairs = force_items ? force_items == -4 : r->last_had_pairs;
-    const int items = force_items ? (force_items == 8 ? 8 : 4) : (!pairs && ix->tiny_cells) ? 8 : 4;
-    // ... and queries of very many parts (5000-letter reads): when the batch before held some, k_lookup only lists them and
-    // k_lookup_long gives each a wave (a lane per part) before the scan reads the counters
-    const bool defer_long = r->last_had_long;
-    const uint32_t lflags = (flags & ~KMX_SEARCH_INTERNAL_DEFER_LONG) | (defer_long ? KMX_SEARCH_INTERNAL_DEFER_LONG : 0u);
-    r->path.items = uint32_t(items); r->path.pairs = pairs; r->path.defer_long = defer_long;
-    timed(ix, K_LOOKUP, s, [&] {
-        kmx::launch_lookup(s, items, pairs, dix, qr, qo, nq, d, ctr, r->bsum.as<uint64_t>(), lflags);
-        if (defer_long) kmx::launch_lookup_long(s, dix, qr, qo, nq, d, ctr, flags);
-    });
+    const int items = lookup(d, ctr, dix);
     // speculative scan: already final when the batch holds no STITCH query
     // The downsweep also records the first query of every output tile (k_partition's job) when the
     // tile table kept from an earlier batch is large enough — the steady state.
@@ -1583,6 +1588,187 @@ kmx_status kmx_search_batch_device(const kmx_index* cix, const void* d_qranks, c
         return KMX_OK;
     }
     return search_finish(r);
+}
+
+kmx_status kmx_search_batch_device(const kmx_index* cix, const void* d_qranks, const void* d_qoff, uint64_t nq,
+                                   uint32_t flags, void* stream, kmx_result** inout)
+{
+    if (!cix || !inout) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: NULL argument");
+    if (nq && (!d_qranks || !d_qoff)) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: NULL query buffers");
+    if (nq >= 0xFFFFFFFFull) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: at most 2^32-2 queries per batch");
+    kmx_index* ix = nullptr;
+    const kmx_status bs = search_device_begin(cix, d_qranks, nq != 0, inout, "kmx_search_batch_device", "d_qranks", &ix);
+    if (bs != KMX_OK) return bs;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint8_t* qr = static_cast<const uint8_t*>(d_qranks);
+    const uint64_t* qo = static_cast<const uint64_t*>(d_qoff);
+    kmx_result* r = *inout;
+    r->windows = false;
+    return search_device_run(ix, r, qr, qo, nq, flags, s, [&](const kmx::QueryDesc& d, unsigned long long* ctr, const KmxIndexDev* dix) {
+        // The k_lookup variant, from what the previous batch on this handle held (results do not depend on the choice): batches with
+        // two-part cross-referenced queries take the variant that interleaves and finishes them; without, the lean one — with eight
+        // queries per thread on an index of tiny cells (a query there is one byte of a table and one 32-byte cell).
+        static const int force_items = getenv("KMX_LOOKUP_ITEMS") ? atoi(getenv("KMX_LOOKUP_ITEMS")) : 0;      // (tuning / tests: 4 | 8, or -4: 4 with pairs)
+        const bool pairs = force_items ? force_items == -4 : r->last_had_pairs;
+        const int items = force_items ? (force_items == 8 ? 8 : 4) : (!pairs && ix->tiny_cells) ? 8 : 4;
+        // ... and queries of very many parts (5000-letter reads): when the batch before held some, k_lookup only lists them and
+        // k_lookup_long gives each a wave (a lane per part) before the scan reads the counters
+        const bool defer_long = r->last_had_long;
+        const uint32_t lflags = (flags & ~KMX_SEARCH_INTERNAL_DEFER_LONG) | (defer_long ? KMX_SEARCH_INTERNAL_DEFER_LONG : 0u);
+        r->path.items = uint32_t(items); r->path.pairs = pairs; r->path.defer_long = defer_long;
+        timed(ix, K_LOOKUP, s, [&] {
+            kmx::launch_lookup(s, items, pairs, dix, qr, qo, nq, d, ctr, r->bsum.as<uint64_t>(), lflags);
+            if (defer_long) kmx::launch_lookup_long(s, dix, qr, qo, nq, d, ctr, flags);
+        });
+        return items;
+    });
+}
+
+// ---- kmx_search_windows: every w-letter window of a batch of reads, one query each (an extension; the contract is in kmx.h).
+// The lookup step is k_lookup_windows; the scan, the fill and search_finish behind it are those of every exact search.
+
+// the refusals that need no device; *elem: the element whose k is the window length
+static kmx_status windows_check(const char* fn, const kmx_index* ix, const kmx_window_options* o, const void* out, uint32_t* elem)
+{
+    const std::string f = std::string(fn) + ": ";
+    if (!ix || !o || !out) return fail(KMX_ERR_INVALID_ARGUMENT, f + "NULL argument");
+    if (o->struct_size < sizeof(kmx_window_options)) return fail(KMX_ERR_INVALID_ARGUMENT, f + "options->struct_size is too small");
+    if (o->stride == 0) return fail(KMX_ERR_INVALID_ARGUMENT, f + "stride must be at least 1");
+    if (o->flags & ~uint32_t(KMX_SEARCH_COUNT_ONLY))
+        return fail(KMX_ERR_INVALID_ARGUMENT, f + "flags other than KMX_SEARCH_COUNT_ONLY have nothing to act on");
+    for (size_t i = 0; i < ix->ks.size(); ++i)
+        if (ix->ks[i] == o->w) { *elem = uint32_t(i); return KMX_OK; }
+    return fail(KMX_ERR_INVALID_ARGUMENT, f + "w = " + std::to_string(o->w) + " is not the k of an element of the index");
+}
+
+static uint64_t window_count(uint64_t len, uint32_t w, uint32_t stride) { return len < w ? 0 : (len - w) / stride + 1; }
+
+// the device form behind the checks; known_nq: the window total when the caller has it (the host form), else it is read back
+static kmx_status windows_device(const kmx_index* cix, const void* d_ranks, const void* d_roff, uint64_t nr, const kmx_window_options* o, uint32_t elem,
+                                 hipStream_t s, kmx_result** inout, const uint64_t* known_nq, const char* fn)
+{
+    kmx_index* ix = nullptr;
+    const kmx_status bs = search_device_begin(cix, d_ranks ? d_ranks : d_roff, nr != 0, inout, fn, "d_ranks", &ix);
+    if (bs != KMX_OK) return bs;
+    kmx_result* r = *inout;
+    const uint8_t* rk = static_cast<const uint8_t*>(d_ranks);
+    const uint64_t* ro = static_cast<const uint64_t*>(d_roff);
+    (void)hipGetLastError();
+    r->windows = true;
+    r->win_nr = nr;
+    r->h_win_valid = false;
+    HIP_TRY(r->win_off.ensure((nr + 1) * 8));
+    uint64_t nq = 0;
+    if (nr == 0) {
+        HIP_TRY(hipMemsetAsync(r->win_off.p, 0, 8, s));
+    } else {
+        HIP_TRY(r->win_cnt.ensure(nr * 4));
+        HIP_TRY(r->bsum.ensure(kmx::scan_blocks(nr) * 8));
+        if (!r->h_ctr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->h_ctr), KMX_CTR_COUNT * sizeof(unsigned long long), hipHostMallocDefault));
+        // windows per read and their exclusive scan: win_off[nr] is the number of queries of this search
+        timed(ix, K_SCAN, s, [&] {
+            kmx::launch_window_counts(s, ro, nr, o->w, o->stride, r->win_cnt.as<uint32_t>());
+            kmx::launch_scan(s, r->win_cnt.as<uint32_t>(), nr, r->bsum.as<uint64_t>(), r->win_off.as<uint64_t>(),
+                             r->win_off.as<unsigned long long>() + nr);
+        });
+        if (known_nq) {
+            nq = *known_nq;
+        } else {
+            HIP_TRY(hipMemcpyAsync(r->h_ctr, r->win_off.as<uint64_t>() + nr, 8, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            nq = r->h_ctr[0];
+        }
+    }
+    auto lookup = [&](const kmx::QueryDesc& d, unsigned long long* ctr, const KmxIndexDev* dix) {
+        timed(ix, K_LOOKUP_WINDOWS, s, [&] {
+            kmx::launch_lookup_windows(s, dix, elem, rk, ro, r->win_off.as<uint64_t>(), nr, nq, o->stride, d, ctr, r->bsum.as<uint64_t>());
+        });
+        return kmx::windows_items();
+    };
+    if (nq >= 0xFFFFFFFFull) {                                  // (a read of 2^32 or more windows counts as 2^32 - 1: it lands here too)
+        (void)search_device_run(ix, r, rk, ro, 0, o->flags, s, lookup);     // the handle holds an empty result, not half of this one
+        r->windows = false;
+        return fail(KMX_ERR_INVALID_ARGUMENT, std::string(fn) + ": at most 2^32-2 windows per batch (and fewer than 2^32 per read): split the reads");
+    }
+    return search_device_run(ix, r, rk, ro, nq, o->flags, s, lookup);
+}
+
+kmx_status kmx_search_windows_device(const kmx_index* cix, const void* d_ranks, const void* d_roff, uint64_t nr, const kmx_window_options* o,
+                                     void* stream, kmx_result** inout)
+{
+    uint32_t elem = 0;
+    const kmx_status cs = windows_check("kmx_search_windows_device", cix, o, inout, &elem);
+    if (cs != KMX_OK) return cs;
+    if (nr && !d_roff) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows_device: NULL read offsets");
+    return windows_device(cix, d_ranks, d_roff, nr, o, elem, static_cast<hipStream_t>(stream), inout, nullptr, "kmx_search_windows_device");
+}
+
+kmx_status kmx_search_windows(const kmx_index* cix, const uint8_t* ranks, const uint64_t* roff, uint64_t nr, const kmx_window_options* o,
+                              kmx_result** out)
+{
+    uint32_t elem = 0;
+    const kmx_status cs = windows_check("kmx_search_windows", cix, o, out, &elem);
+    if (cs != KMX_OK) return cs;
+    if (nr && !roff) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: NULL read offsets");
+    if (nr && roff[0] != 0) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: roff[0] must be 0");
+    uint64_t nq = 0;
+    for (uint64_t i = 0; i < nr; ++i) {
+        if (roff[i + 1] < roff[i]) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: roff must be non-decreasing");
+        const uint64_t c = window_count(roff[i + 1] - roff[i], o->w, o->stride);
+        if (c > 0xFFFFFFFFull) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: a read of 2^32 or more windows: split the reads");
+        nq += c;
+        if (nq >= 0xFFFFFFFFull) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: at most 2^32-2 windows per batch: split the reads");
+    }
+    const uint64_t n_letters = nr ? roff[nr] : 0;
+    if (n_letters && !ranks) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: NULL read letters");
+    kmx_index* ix = const_cast<kmx_index*>(cix);                // (several replicas: the first one)
+    if (*out && !(*out)->parts.empty()) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: the result handle belongs to a search of several parts");
+    const kmx_status ds = check_device();
+    if (ds != KMX_OK) return ds;
+    HIP_TRY(hipSetDevice(ix->device));
+    kmx_result* r = *out ? *out : take_result(ix);
+    *out = r;
+    if (r->ctx.pending) { kmx_status fs = search_finish(r); if (fs != KMX_OK) return fs; }
+    if (r->device != ix->device && r->device_bytes())
+        return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: the result handle holds buffers on another device");
+    r->device = ix->device;
+    if (!r->own_stream) HIP_TRY(hipStreamCreateWithFlags(&r->own_stream, hipStreamNonBlocking));
+    // the reads and their offsets go up once, as they are: no window is written out on either side
+    HIP_TRY(r->in_qranks.ensure(std::max<uint64_t>(n_letters, 1) + 16));
+    HIP_TRY(r->in_qoff.ensure((nr + 1) * 8));
+    if (n_letters) HIP_TRY(hipMemcpyAsync(r->in_qranks.p, ranks, n_letters, hipMemcpyHostToDevice, r->own_stream));
+    if (nr) HIP_TRY(hipMemcpyAsync(r->in_qoff.p, roff, (nr + 1) * 8, hipMemcpyHostToDevice, r->own_stream));
+    const kmx_status st = windows_device(ix, r->in_qranks.p, r->in_qoff.p, nr, o, elem, r->own_stream, out, &nq, "kmx_search_windows");
+    if (st != KMX_OK) return st;
+    HIP_TRY(hipStreamSynchronize(r->own_stream));
+    r->quiesced = true;
+    if (!r->h_win_off.ensure((nr + 1) * 8)) return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_search_windows: host allocation failed");
+    uint64_t* wo = r->h_win_off.as<uint64_t>();
+    wo[0] = 0;
+    for (uint64_t i = 0; i < nr; ++i) wo[i + 1] = wo[i] + window_count(roff[i + 1] - roff[i], o->w, o->stride);
+    r->h_win_valid = true;
+    return KMX_OK;
+}
+
+kmx_status kmx_result_window_offsets(kmx_result* r, const uint64_t** win_off, const uint64_t** d_win_off, uint64_t* nr)
+{
+    if (!r) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_window_offsets: result is NULL");
+    if (r->ctx.pending) { kmx_status fs = search_finish(r); if (fs != KMX_OK) return fs; }
+    if (!r->windows || !r->parts.empty())
+        return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_window_offsets: the result is not one of kmx_search_windows / kmx_search_windows_device");
+    if (win_off) {
+        if (!r->h_win_valid) {
+            if (!r->h_win_off.ensure((r->win_nr + 1) * 8)) return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_result_window_offsets: host allocation failed");
+            HIP_TRY(hipSetDevice(r->device));
+            HIP_TRY(hipMemcpyAsync(r->h_win_off.p, r->win_off.p, (r->win_nr + 1) * 8, hipMemcpyDeviceToHost, r->stream));
+            HIP_TRY(hipStreamSynchronize(r->stream));
+            r->h_win_valid = true;
+        }
+        *win_off = r->h_win_off.as<uint64_t>();
+    }
+    if (d_win_off) *d_win_off = r->win_off.as<uint64_t>();
+    if (nr) *nr = r->win_nr;
+    return KMX_OK;
 }
 
 // Second half of a search: waits for the counters of the first half, then validates / fills / sorts whatever the
@@ -1882,6 +2068,7 @@ static kmx_status search_host_one(kmx_index* ix, const uint8_t* qranks, const ui
             }
             r->host_valid = r->host_masks_valid = true;
             r->small_valid = true;
+            r->windows = false;
             r->path = kmx_result::PathRec{};
             r->path.small = 1;
             r->quiesced = true;

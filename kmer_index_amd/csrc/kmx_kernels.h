@@ -32,6 +32,16 @@ void launch_lookup(hipStream_t s, int items, bool pairs, const KmxIndexDev* ix, 
 // behind launch_lookup with KMX_SEARCH_INTERNAL_DEFER_LONG in its flags: the queries of very many parts it listed, a wave each
 void launch_lookup_long(hipStream_t s, const KmxIndexDev* ix, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq, const QueryDesc& d,
                         unsigned long long* ctr, uint32_t flags);
+// kmx_search_windows: every w-letter window of nr reads (ranks / roff[nr + 1], shaped like qranks / qoff), w = the k of element `elem`.
+// launch_window_counts: cnt[r] = windows of read r (saturated at 2^32 - 1); launch_scan over it gives win_off[nr + 1], nq = win_off[nr].
+// launch_lookup_windows writes src / cnt / kind / status of the nq windows as launch_lookup does for m == k queries, counts
+// KMX_CTR_ERROR / KMX_CTR_NONE, and leaves lookup_blocks(nq, windows_items()) sums in block_hits: the scan behind it is
+// launch_scan_tiles(..., lookup_items = windows_items()).  windows_tile(): windows per workgroup.
+uint64_t windows_tile();
+int windows_items();
+void launch_window_counts(hipStream_t s, const uint64_t* roff, uint64_t nr, uint32_t w, uint32_t stride, uint32_t* cnt);
+void launch_lookup_windows(hipStream_t s, const KmxIndexDev* ix, uint32_t elem, const uint8_t* ranks, const uint64_t* roff, const uint64_t* win_off,
+                           uint64_t nr, uint64_t nq, uint32_t stride, const QueryDesc& d, unsigned long long* ctr, uint64_t* block_hits);
 void launch_validate(hipStream_t s, const KmxIndexDev* ix, const uint32_t* arena, const uint8_t* qranks, const uint64_t* qoff,
                      const QueryDesc& d, uint64_t n_stitch, uint64_t n_more, uint64_t n_tiny, const uint32_t* tiny_list, uint64_t n_short,
                      uint64_t* mask_words, bool direct);   // direct: tiny queries whose survivors are one run of the first bucket leave as plain copies

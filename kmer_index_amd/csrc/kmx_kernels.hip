@@ -1095,6 +1095,202 @@ void launch_lookup_long(hipStream_t s, const KmxIndexDev* ix, const uint8_t* qra
 }
 
 // ---------------------------------------------------------------------------
+// k_window_counts / k_lookup_windows — every w-letter window of a batch of reads (kmx_search_windows; w is the k of ONE
+// element, which the host resolved): the lookup step of the exact pipeline for a batch nobody wrote out.  Read r of len_r
+// letters holds c_r = (len_r - w) / stride + 1 windows (0 when it is shorter than w); win_off, the exclusive scan of c_r,
+// numbers them, and window win_off[r] + j — the letters [roff[r] + j * stride, + w) — is query win_off[r] + j of the result.
+//
+// k_lookup_windows is window-centric: a block owns KMX_WIN_TILE consecutive windows, whatever reads they belong to, a thread
+// KMX_WIN_ITEMS consecutive ones of them.  Thread 0 narrows the reads of the tile by two binary searches in win_off; every
+// thread then finds the read of its first window inside that range and walks on from there.  The tile's letters are one
+// contiguous piece of `ranks` (reads lie back to back): when it fits KMX_WIN_STAGE bytes the block copies it to LDS once, with
+// 16-byte loads that stay inside the piece, and the threads read letters from there — every letter crosses the memory system
+// once per block; a longer piece (large strides, many reads too short for a window) is read in place.
+// Inside a read a thread ROLLS the rank-hash when stride < w: the `stride` leading letters leave (h - r * sigma^(w-1), before the
+// multiply, so the running value never exceeds sigma^w - 1 < 2^64: rank_hash's no-wrap guarantee holds), `stride` new ones are
+// shifted in; with stride >= w, and at the first window a thread has in a read, it is Horner's rule as rank_hash does it.  A
+// letter >= sigma enters the hash as 0 and its place is remembered (one past the LAST such letter seen): a window is
+// KMX_Q_BAD_RANK exactly while that place lies inside it.  No letter is looked at again to decide that.
+// The eight hashes are probed (probe(): cells, aligned copy, plain dense table or open addressing) and the descriptors written as
+// k_lookup writes them for an m == k query — 16-byte stores, a thread's eight windows are adjacent.  A block's hit sum goes to
+// block_hits[blockIdx.x]: the layout of the eight-queries-per-thread k_lookup, so the scan behind takes it as its first level.
+// ---------------------------------------------------------------------------
+#define KMX_WIN_ITEMS 8
+#define KMX_WIN_TILE (KMX_BLOCK * KMX_WIN_ITEMS)
+#define KMX_WIN_STAGE 16384
+
+__global__ __launch_bounds__(KMX_BLOCK) void k_window_counts(const uint64_t* __restrict__ roff, uint64_t nr, uint32_t w, uint32_t stride,
+                                                             uint32_t* __restrict__ cnt)
+{
+    const uint64_t r = uint64_t(blockIdx.x) * KMX_BLOCK + threadIdx.x;
+    if (r >= nr) return;
+    const uint64_t len = roff[r + 1] - roff[r];
+    const uint64_t c = len < w ? 0 : (len - w) / stride + 1;
+    cnt[r] = c > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(c);    // (saturated: the total then reaches the limit of a batch and the call is refused)
+}
+
+__global__ __launch_bounds__(KMX_BLOCK) void k_lookup_windows(const KmxIndexDev* __restrict__ ix, uint32_t elem, const uint8_t* __restrict__ ranks,
+                                                              const uint64_t* __restrict__ roff, const uint64_t* __restrict__ win_off, uint64_t nr,
+                                                              uint64_t nq, uint32_t stride, QueryDesc d, unsigned long long* __restrict__ ctr,
+                                                              uint64_t* __restrict__ block_hits)
+{
+    __shared__ KmxElemDev el_s;
+    __shared__ uint64_t s_first, s_last, s_lo, s_hi;          // reads of the tile (first, last), its letters [lo, hi)
+    __shared__ unsigned int s_err, s_none;
+    __shared__ unsigned long long s_hits;
+    __shared__ __attribute__((aligned(16))) uint8_t s_let[KMX_WIN_STAGE];
+    const uint64_t tile_base = uint64_t(blockIdx.x) * KMX_WIN_TILE;
+    const uint64_t tile_end = min(nq, tile_base + KMX_WIN_TILE);      // (the grid has no block behind the last window: tile_base < nq)
+    {
+        const uint64_t* __restrict__ srcw = reinterpret_cast<const uint64_t*>(&ix->elems[elem]);
+        uint64_t* dstw = reinterpret_cast<uint64_t*>(&el_s);
+        for (uint32_t i = threadIdx.x; i < uint32_t(sizeof(KmxElemDev) / 8); i += KMX_BLOCK) dstw[i] = srcw[i];
+    }
+    if (threadIdx.x == 0) {
+        s_err = s_none = 0;
+        s_hits = 0;
+        // the read of window q: the last r with win_off[r] <= q (reads without a window share their offset with the next one)
+        const uint64_t first = upper_bound_dev<uint64_t>(win_off, nr + 1, tile_base) - 1;
+        const uint64_t last = first + upper_bound_dev<uint64_t>(win_off + first, nr + 1 - first, tile_end - 1) - 1;
+        s_first = first;
+        s_last = last;
+        s_lo = roff[first] + (tile_base - win_off[first]) * stride;
+        s_hi = roff[last] + (tile_end - 1 - win_off[last]) * stride + ix->elems[elem].k;
+    }
+    __syncthreads();
+    const uint32_t w = el_s.k, sigma = ix->sigma;
+    const uint64_t top = ix->pw[w - 1];                       // sigma^(w-1): the weight of the letter that leaves
+    const uint64_t r_first = s_first, r_last = s_last, lo = s_lo, hi = s_hi;
+    const bool staged = hi - lo <= KMX_WIN_STAGE;
+    if (staged) {
+        const uint32_t len = uint32_t(hi - lo);
+        for (uint32_t i = threadIdx.x * 16u; i < len; i += KMX_BLOCK * 16u) {
+            if (i + 16u <= len) {
+                *reinterpret_cast<u32x4*>(s_let + i) = *reinterpret_cast<const u32x4_a1*>(ranks + lo + i);
+            } else {
+                for (uint32_t j = i; j < len; ++j) s_let[j] = ranks[lo + j];
+            }
+        }
+        __syncthreads();
+    }
+
+    const uint64_t q0 = tile_base + uint64_t(threadIdx.x) * KMX_WIN_ITEMS;
+    uint64_t hs[KMX_WIN_ITEMS];
+    bool ok[KMX_WIN_ITEMS];
+#pragma unroll
+    for (int i = 0; i < KMX_WIN_ITEMS; ++i) { hs[i] = 0; ok[i] = false; }
+    auto hashes = [&](auto fetch) {
+        if (q0 >= tile_end) return;
+        uint64_t r = r_first + upper_bound_dev<uint64_t>(win_off + r_first, r_last - r_first + 1, q0) - 1;
+        uint64_t next = win_off[r + 1];                       // the first window behind read r
+        uint64_t pos = roff[r] + (q0 - win_off[r]) * stride;  // first letter of the window
+        uint64_t h = 0;
+        uint64_t bad_end = 0;                                 // one past the last letter >= sigma seen so far (0: none)
+        bool fresh = true;
+#pragma unroll
+        for (int i = 0; i < KMX_WIN_ITEMS; ++i) {
+            const uint64_t q = q0 + i;
+            if (q < tile_end) {
+                if (q >= next) {                              // the read is used up: q is the first window of the next read that has one
+                    do { ++r; next = win_off[r + 1]; } while (q >= next);
+                    pos = roff[r];
+                    fresh = true;
+                }
+                if (fresh || stride >= w) {
+                    h = 0;
+                    for (uint32_t t = 0; t < w; ++t) {
+                        const uint32_t c = fetch(pos + t);
+                        const bool bad = c >= sigma;
+                        bad_end = bad ? pos + t + 1 : bad_end;
+                        h = h * sigma + (bad ? 0u : c);
+                    }
+                    fresh = false;
+                } else {
+                    const uint64_t old = pos - stride;        // the window before this one, same read
+                    for (uint32_t t = 0; t < stride; ++t) {
+                        const uint32_t a = fetch(old + t), c = fetch(old + w + t);
+                        const bool bad = c >= sigma;
+                        bad_end = bad ? old + w + t + 1 : bad_end;
+                        h = (h - (a >= sigma ? 0u : a) * top) * sigma + (bad ? 0u : c);
+                    }
+                }
+                hs[i] = h;
+                ok[i] = bad_end <= pos;
+                pos += stride;
+            }
+        }
+    };
+    if (staged) hashes([&](uint64_t p) -> uint32_t { return s_let[uint32_t(p - lo)]; });
+    else hashes([&](uint64_t p) -> uint32_t { return ranks[p]; });
+
+    Run runs[KMX_WIN_ITEMS];
+#pragma unroll
+    for (int i = 0; i < KMX_WIN_ITEMS; ++i) {
+        runs[i].src = 0; runs[i].cnt = 0;
+        if (ok[i]) runs[i] = probe(&el_s, hs[i]);
+    }
+    unsigned int my_err = 0, my_none = 0;
+    uint64_t my_hits = 0;
+    uint8_t kind[KMX_WIN_ITEMS], status[KMX_WIN_ITEMS];
+#pragma unroll
+    for (int i = 0; i < KMX_WIN_ITEMS; ++i) {
+        const bool live = q0 + i < tile_end;
+        status[i] = (live && !ok[i]) ? uint8_t(KMX_Q_BAD_RANK) : uint8_t(KMX_Q_OK);
+        kind[i] = runs[i].cnt ? uint8_t(KMX_KIND_EXACT) : uint8_t(KMX_KIND_NONE);
+        if (!runs[i].cnt) runs[i].src = 0;
+        my_err += live && !ok[i];
+        my_none += live && ok[i] && !runs[i].cnt;
+        my_hits += runs[i].cnt;
+    }
+    if (q0 + KMX_WIN_ITEMS <= tile_end) {
+        // q0 is a multiple of eight: 64 bytes of src, 32 of cnt, 8 of kind and of status, all aligned
+#pragma unroll
+        for (int i = 0; i < KMX_WIN_ITEMS; i += 2) {
+            u64x2 v;
+            v.x = runs[i].src; v.y = runs[i + 1].src;
+            *reinterpret_cast<u64x2*>(d.src + q0 + i) = v;
+        }
+#pragma unroll
+        for (int i = 0; i < KMX_WIN_ITEMS; i += 4) {
+            u32x4 v;
+            v.x = runs[i].cnt; v.y = runs[i + 1].cnt; v.z = runs[i + 2].cnt; v.w = runs[i + 3].cnt;
+            *reinterpret_cast<u32x4*>(d.cnt + q0 + i) = v;
+        }
+        uint64_t kw = 0, sw = 0;
+#pragma unroll
+        for (int i = 0; i < KMX_WIN_ITEMS; ++i) { kw |= uint64_t(kind[i]) << (8 * i); sw |= uint64_t(status[i]) << (8 * i); }
+        *reinterpret_cast<uint64_t*>(d.kind + q0) = kw;
+        *reinterpret_cast<uint64_t*>(d.status + q0) = sw;
+    } else {
+#pragma unroll
+        for (int i = 0; i < KMX_WIN_ITEMS; ++i) {
+            if (q0 + i < tile_end) {
+                d.src[q0 + i] = runs[i].src;
+                d.cnt[q0 + i] = runs[i].cnt;
+                d.kind[q0 + i] = kind[i];
+                d.status[q0 + i] = status[i];
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        my_hits += __shfl_xor(my_hits, off);
+        my_err += __shfl_xor(my_err, off);
+        my_none += __shfl_xor(my_none, off);
+    }
+    if (lane_id() == 0) {
+        if (my_hits) atomicAdd(&s_hits, (unsigned long long)my_hits);
+        if (my_err) atomicAdd(&s_err, my_err);
+        if (my_none) atomicAdd(&s_none, my_none);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        block_hits[blockIdx.x] = s_hits;
+        if (s_err) atomicAdd(&ctr[KMX_CTR_ERROR], (unsigned long long)s_err);
+        if (s_none) atomicAdd(&ctr[KMX_CTR_NONE], (unsigned long long)s_none);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // k_validate — STITCH queries.
 //
 // Candidates are the positions of the first part's bucket (kmer_index.hpp:272,
@@ -3720,6 +3916,23 @@ void launch_lookup(hipStream_t s, int items, bool pairs, const KmxIndexDev* ix, 
     if (pairs) hipLaunchKernelGGL((k_lookup<4, true>), grid, block, 0, s, ix, qranks, qoff, nq, d, ctr, block_hits, flags);
     else if (items == 8) hipLaunchKernelGGL((k_lookup<8, false>), grid, block, 0, s, ix, qranks, qoff, nq, d, ctr, block_hits, flags);
     else hipLaunchKernelGGL((k_lookup<4, false>), grid, block, 0, s, ix, qranks, qoff, nq, d, ctr, block_hits, flags);
+}
+
+uint64_t windows_tile() { return KMX_WIN_TILE; }
+int windows_items() { return KMX_WIN_ITEMS; }
+
+void launch_window_counts(hipStream_t s, const uint64_t* roff, uint64_t nr, uint32_t w, uint32_t stride, uint32_t* cnt)
+{
+    hipLaunchKernelGGL(k_window_counts, dim3(blocks_for(nr, KMX_BLOCK)), dim3(KMX_BLOCK), 0, s, roff, nr, w, stride, cnt);
+}
+
+void launch_lookup_windows(hipStream_t s, const KmxIndexDev* ix, uint32_t elem, const uint8_t* ranks, const uint64_t* roff, const uint64_t* win_off,
+                           uint64_t nr, uint64_t nq, uint32_t stride, const QueryDesc& d, unsigned long long* ctr, uint64_t* block_hits)
+{
+    static_assert(KMX_WIN_ITEMS == 8, "block_hits is laid out as the eight-queries-per-thread k_lookup leaves it (launch_scan_tiles)");
+    if (!nq) return;
+    hipLaunchKernelGGL(k_lookup_windows, dim3(blocks_for(nq, KMX_WIN_TILE)), dim3(KMX_BLOCK), 0, s, ix, elem, ranks, roff, win_off, nr, nq, stride, d,
+                       ctr, block_hits);
 }
 
 // The STITCH work list holds n_stitch queries from its front and n_tiny "tiny" ones from its back (list_end = one past

@@ -34,6 +34,7 @@ EXPORTS = [
     "kmx_approx_lengths", "kmx_search_approx_strands", "kmx_approx_strands",
     "kmx_search_approx_opts", "kmx_approx_found",
     "kmx_index_paths", "kmx_result_paths",
+    "kmx_search_windows", "kmx_search_windows_device", "kmx_result_window_offsets",
 ]
 
 
@@ -55,13 +56,18 @@ class ApproxOptions(C.Structure):
                 ("complement", C.c_void_p)]
 
 
+class WindowOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("w", C.c_uint32), ("stride", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
 
 class IndexPathInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("fill_slots", C.c_uint32), ("fill_nontemporal", C.c_uint32), ("rec64", C.c_uint32),
-                ("tiny_cells", C.c_uint32), ("scan_tile", C.c_uint32), ("n_ks", C.c_uint32), ("cell_shift", C.c_uint32 * KMX_MAX_KS)]
+                ("tiny_cells", C.c_uint32), ("scan_tile", C.c_uint32), ("n_ks", C.c_uint32), ("cell_shift", C.c_uint32 * KMX_MAX_KS),
+                ("windows_tile", C.c_uint32)]
 
 
 class ResultPathInfo(C.Structure):
@@ -160,6 +166,12 @@ def lib():
         L.kmx_index_paths.argtypes = [vp, P(IndexPathInfo)]
         L.kmx_result_paths.restype = C.c_int
         L.kmx_result_paths.argtypes = [vp, P(ResultPathInfo)]
+        L.kmx_search_windows.restype = C.c_int
+        L.kmx_search_windows.argtypes = [vp, vp, vp, u64, P(WindowOptions), P(vp)]
+        L.kmx_search_windows_device.restype = C.c_int
+        L.kmx_search_windows_device.argtypes = [vp, vp, vp, u64, P(WindowOptions), vp, P(vp)]
+        L.kmx_result_window_offsets.restype = C.c_int
+        L.kmx_result_window_offsets.argtypes = [vp, P(vp), P(vp), P(u64)]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -321,6 +333,14 @@ class Result:
         _check(lib().kmx_result_gather_device(self._h, int(dst_device), C.byref(a), C.byref(b), C.byref(s)))
         return a.value, b.value, s.value
 
+    def window_offsets(self, device=False):
+        """kmx_result_window_offsets of a windows search: win_off[nr+1] as a numpy array (window j of read r is query
+        win_off[r] + j); device=True: (win_off, device pointer of the same array, nr)."""
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _check(lib().kmx_result_window_offsets(self._h, C.byref(a), C.byref(b), C.byref(n)))
+        win_off = _view(a.value, n.value + 1, np.uint64).copy()
+        return (win_off, b.value, int(n.value)) if device else win_off
+
     def masks(self):
         c = self.counts()
         a, b, cc, d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -464,7 +484,8 @@ class Index:
         v.struct_size = C.sizeof(IndexPathInfo)
         _check(lib().kmx_index_paths(self._h, C.byref(v)))
         return {"fill_slots": int(v.fill_slots), "fill_nontemporal": bool(v.fill_nontemporal), "rec64": bool(v.rec64),
-                "tiny_cells": bool(v.tiny_cells), "scan_tile": int(v.scan_tile), "cell_shift": [int(v.cell_shift[i]) for i in range(v.n_ks)]}
+                "tiny_cells": bool(v.tiny_cells), "scan_tile": int(v.scan_tile), "cell_shift": [int(v.cell_shift[i]) for i in range(v.n_ks)],
+                "windows_tile": int(v.windows_tile)}
 
     def devices(self):
         n = C.c_uint32()
@@ -551,6 +572,27 @@ class Index:
         """Device-buffer batch search (kmx_search_batch_device) on a caller-owned hipStream_t."""
         r = result or Result()
         _check(lib().kmx_search_batch_device(self._h, d_qranks_ptr, d_qoff_ptr, nq, flags, stream or None, C.byref(r._h)))
+        r._index = self
+        return r
+
+    def search_windows(self, ranks, roff, w, stride=1, flags=SEARCH_DEFAULT, result=None):
+        """kmx_search_windows: every w-letter window of every read (ranks / roff shaped like qranks / qoff), at offsets 0, stride,
+        2 * stride ... of each read, as one query each; w must be one of the index's ks.  Result.window_offsets() maps reads to
+        queries; everything else is an ordinary Result."""
+        ranks = np.ascontiguousarray(ranks, np.uint8)
+        roff = np.ascontiguousarray(roff, np.uint64)
+        r = result or Result()
+        o = WindowOptions(C.sizeof(WindowOptions), int(w), int(stride), int(flags))
+        _check(lib().kmx_search_windows(self._h, ranks.ctypes.data if ranks.size else None, roff.ctypes.data, roff.size - 1,
+                                        C.byref(o), C.byref(r._h)))
+        r._index = self
+        return r
+
+    def search_windows_device(self, d_ranks_ptr, d_roff_ptr, nr, w, stride=1, flags=SEARCH_DEFAULT, stream=0, result=None):
+        """kmx_search_windows_device on a caller-owned hipStream_t; `result` may be a handle of search_device and the other way round."""
+        r = result or Result()
+        o = WindowOptions(C.sizeof(WindowOptions), int(w), int(stride), int(flags))
+        _check(lib().kmx_search_windows_device(self._h, d_ranks_ptr, d_roff_ptr, nr, C.byref(o), stream or None, C.byref(r._h)))
         r._index = self
         return r
 

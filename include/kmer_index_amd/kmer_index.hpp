@@ -17,6 +17,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -137,6 +138,23 @@ namespace kmer
             }
         };
 
+        // a batch as the engine takes it: the ranks of all queries in one array, query i at [off[i], off[i + 1])
+        struct flat_queries
+        {
+            std::vector<std::uint8_t> ranks;
+            std::vector<std::uint64_t> off;
+        };
+        static flat_queries flatten(const std::vector<std::vector<alphabet_t>>& queries)
+        {
+            flat_queries f;
+            f.off.assign(queries.size() + 1, 0);
+            for (std::size_t i = 0; i < queries.size(); ++i) f.off[i + 1] = f.off[i] + queries[i].size();
+            f.ranks.reserve(f.off.back());
+            for (auto const& q : queries)
+                for (auto const& l : q) f.ranks.push_back(traits::to_rank(l));
+            return f;
+        }
+
     public:
         using result_t = detail::kmer_index_result<position_t>;
         template<std::size_t k>
@@ -213,16 +231,11 @@ namespace kmer
         // the reference would throw for (too long :507-509, sub-k fan-out :119-122, empty :195) gets an empty result.
         std::vector<result_t> search(const std::vector<std::vector<alphabet_t>>& queries, std::vector<std::uint8_t>& status_out) const
         {
-            std::vector<std::uint8_t> ranks;
-            std::vector<std::uint64_t> off(queries.size() + 1, 0);
-            for (std::size_t i = 0; i < queries.size(); ++i) off[i + 1] = off[i] + queries[i].size();
-            ranks.reserve(off.back());
-            for (auto const& q : queries)
-                for (auto const& l : q) ranks.push_back(traits::to_rank(l));
+            flat_queries f = flatten(queries);
 
             const bool eager = _mask_mode == mask_mode::eager;
             kmx_result* raw = nullptr;
-            detail::throw_on(kmx_search_batch(_index.get(), ranks.data(), off.data(), queries.size(),
+            detail::throw_on(kmx_search_batch(_index.get(), f.ranks.data(), f.off.data(), queries.size(),
                                               eager ? KMX_SEARCH_KEEP_MASKS : KMX_SEARCH_DEFAULT, &raw), "search");
             std::shared_ptr<kmx_result> handle(raw, detail::result_deleter{});
             const std::uint64_t* hit_off; const std::uint32_t* positions; const std::uint8_t* status; const std::uint8_t* kinds;
@@ -267,7 +280,7 @@ namespace kmer
                     out.emplace_back(handle, hits, n_hits, lazy, i);
                 }
             }
-            if (lazy) { lazy->ranks = std::move(ranks); lazy->off = std::move(off); }
+            if (lazy) { lazy->ranks = std::move(f.ranks); lazy->off = std::move(f.off); }
             return out;
         }
 
@@ -336,26 +349,7 @@ namespace kmer
         std::vector<approx_hits> search_approx(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_subst,
                                                std::vector<std::uint8_t>& status_out) const
         {
-            std::vector<std::uint8_t> ranks;
-            std::vector<std::uint64_t> off(queries.size() + 1, 0);
-            for (std::size_t i = 0; i < queries.size(); ++i) off[i + 1] = off[i] + queries[i].size();
-            ranks.reserve(off.back());
-            for (auto const& q : queries)
-                for (auto const& l : q) ranks.push_back(traits::to_rank(l));
-            kmx_approx_result* raw = nullptr;
-            detail::throw_on(kmx_search_approx(_index.get(), ranks.data(), off.data(), queries.size(), std::uint32_t(max_subst), 0, &raw),
-                             "search_approx");
-            std::unique_ptr<kmx_approx_result, void (*)(kmx_approx_result*)> hold(raw, kmx_approx_free);
-            const std::uint64_t* hit_off; const std::uint32_t* positions; const std::uint8_t* mismatches; const std::uint8_t* status;
-            detail::throw_on(kmx_approx_view(raw, &hit_off, &positions, &mismatches, &status), "search_approx");
-            status_out.assign(status, status + queries.size());
-            std::vector<approx_hits> out(queries.size());
-            for (std::size_t i = 0; i < queries.size(); ++i)
-            {
-                out[i].positions.assign(positions + hit_off[i], positions + hit_off[i + 1]);
-                out[i].mismatches.assign(mismatches + hit_off[i], mismatches + hit_off[i + 1]);
-            }
-            return out;
+            return approx_batch(queries, max_subst, nullptr, status_out);
         }
 
         // the same, with the batch overload's error behaviour: an approx_query_error (std::invalid_argument) for the first
@@ -373,12 +367,7 @@ namespace kmer
         {
             std::vector<std::uint8_t> status;
             std::vector<approx_hits> out = search_approx(queries, max_subst, status);
-            for (std::size_t i = 0; i < status.size(); ++i)
-            {
-                if (status[i] == KMX_Q_OK) continue;
-                const std::string what = query_status_message(status[i]);
-                throw approx_query_error(what, i, std::move(status), std::move(out));
-            }
+            throw_unserved(status, out);
             return out;
         }
 
@@ -400,29 +389,7 @@ namespace kmer
         std::vector<edit_hits> search_edit(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_edits,
                                            std::vector<std::uint8_t>& status_out) const
         {
-            std::vector<std::uint8_t> ranks;
-            std::vector<std::uint64_t> off(queries.size() + 1, 0);
-            for (std::size_t i = 0; i < queries.size(); ++i) off[i + 1] = off[i] + queries[i].size();
-            ranks.reserve(off.back());
-            for (auto const& q : queries)
-                for (auto const& l : q) ranks.push_back(traits::to_rank(l));
-            kmx_approx_result* raw = nullptr;
-            detail::throw_on(kmx_search_approx(_index.get(), ranks.data(), off.data(), queries.size(), std::uint32_t(max_edits), KMX_APPROX_EDIT, &raw),
-                             "search_edit");
-            std::unique_ptr<kmx_approx_result, void (*)(kmx_approx_result*)> hold(raw, kmx_approx_free);
-            const std::uint64_t* hit_off; const std::uint32_t* positions; const std::uint8_t* distances; const std::uint8_t* status;
-            const std::uint32_t* lengths;
-            detail::throw_on(kmx_approx_view(raw, &hit_off, &positions, &distances, &status), "search_edit");
-            detail::throw_on(kmx_approx_lengths(raw, &lengths), "search_edit");
-            status_out.assign(status, status + queries.size());
-            std::vector<edit_hits> out(queries.size());
-            for (std::size_t i = 0; i < queries.size(); ++i)
-            {
-                out[i].positions.assign(positions + hit_off[i], positions + hit_off[i + 1]);
-                out[i].distances.assign(distances + hit_off[i], distances + hit_off[i + 1]);
-                out[i].lengths.assign(lengths + hit_off[i], lengths + hit_off[i + 1]);
-            }
-            return out;
+            return edit_batch(queries, max_edits, nullptr, status_out);
         }
 
         // with search_approx's error behaviour; the error's results carry positions and distances (as mismatches) of the others
@@ -430,18 +397,7 @@ namespace kmer
         {
             std::vector<std::uint8_t> status;
             std::vector<edit_hits> out = search_edit(queries, max_edits, status);
-            for (std::size_t i = 0; i < status.size(); ++i)
-            {
-                if (status[i] == KMX_Q_OK) continue;
-                const std::string what = query_status_message(status[i]);
-                std::vector<approx_hits> others(out.size());
-                for (std::size_t j = 0; j < out.size(); ++j)
-                {
-                    others[j].positions = std::move(out[j].positions);
-                    others[j].mismatches = std::move(out[j].distances);
-                }
-                throw approx_query_error(what, i, std::move(status), std::move(others));
-            }
+            throw_unserved(status, out);
             return out;
         }
 
@@ -466,32 +422,7 @@ namespace kmer
         std::vector<strand_hits> search_both_strands(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit,
                                                      const complement_table& complement, std::vector<std::uint8_t>& status_out) const
         {
-            std::vector<std::uint8_t> ranks;
-            std::vector<std::uint64_t> off(queries.size() + 1, 0);
-            for (std::size_t i = 0; i < queries.size(); ++i) off[i + 1] = off[i] + queries[i].size();
-            ranks.reserve(off.back());
-            for (auto const& q : queries)
-                for (auto const& l : q) ranks.push_back(traits::to_rank(l));
-            kmx_approx_result* raw = nullptr;
-            detail::throw_on(kmx_search_approx_strands(_index.get(), ranks.data(), off.data(), queries.size(), std::uint32_t(max_dist),
-                                                       edit ? KMX_APPROX_EDIT : 0u, complement.data(), &raw),
-                             "search_both_strands");
-            std::unique_ptr<kmx_approx_result, void (*)(kmx_approx_result*)> hold(raw, kmx_approx_free);
-            const std::uint64_t* hit_off; const std::uint32_t* positions; const std::uint8_t* distances; const std::uint8_t* status;
-            const std::uint32_t* lengths = nullptr; const std::uint8_t* strands;
-            detail::throw_on(kmx_approx_view(raw, &hit_off, &positions, &distances, &status), "search_both_strands");
-            detail::throw_on(kmx_approx_strands(raw, &strands), "search_both_strands");
-            if (edit) detail::throw_on(kmx_approx_lengths(raw, &lengths), "search_both_strands");
-            status_out.assign(status, status + queries.size());
-            std::vector<strand_hits> out(queries.size());
-            for (std::size_t i = 0; i < queries.size(); ++i)
-            {
-                out[i].positions.assign(positions + hit_off[i], positions + hit_off[i + 1]);
-                out[i].distances.assign(distances + hit_off[i], distances + hit_off[i + 1]);
-                out[i].strands.assign(strands + hit_off[i], strands + hit_off[i + 1]);
-                if (edit) out[i].lengths.assign(lengths + hit_off[i], lengths + hit_off[i + 1]);
-            }
-            return out;
+            return strand_batch(queries, max_dist, edit, complement, nullptr, status_out);
         }
 
         // with search_approx's error behaviour; the error's results carry positions and distances (as mismatches) of the others
@@ -500,18 +431,7 @@ namespace kmer
         {
             std::vector<std::uint8_t> status;
             std::vector<strand_hits> out = search_both_strands(queries, max_dist, edit, complement, status);
-            for (std::size_t i = 0; i < status.size(); ++i)
-            {
-                if (status[i] == KMX_Q_OK) continue;
-                const std::string what = query_status_message(status[i]);
-                std::vector<approx_hits> others(out.size());
-                for (std::size_t j = 0; j < out.size(); ++j)
-                {
-                    others[j].positions = std::move(out[j].positions);
-                    others[j].mismatches = std::move(out[j].distances);
-                }
-                throw approx_query_error(what, i, std::move(status), std::move(others));
-            }
+            throw_unserved(status, out);
             return out;
         }
 
@@ -552,45 +472,18 @@ namespace kmer
         std::vector<approx_hits> search_approx(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_subst,
                                                const report_options& report, std::vector<std::uint8_t>& status_out) const
         {
-            std::vector<approx_hits> out(queries.size());
-            search_report("search_approx", queries, max_subst, 0u, report, nullptr, status_out,
-                          [&](std::size_t i, std::uint64_t a, std::uint64_t b, const report_views& v)
-                          {
-                              out[i].positions.assign(v.positions + a, v.positions + b);
-                              out[i].mismatches.assign(v.distances + a, v.distances + b);
-                              out[i].found = std::size_t(v.found[i]);
-                          });
-            return out;
+            return approx_batch(queries, max_subst, &report, status_out);
         }
         std::vector<edit_hits> search_edit(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_edits,
                                            const report_options& report, std::vector<std::uint8_t>& status_out) const
         {
-            std::vector<edit_hits> out(queries.size());
-            search_report("search_edit", queries, max_edits, KMX_APPROX_EDIT, report, nullptr, status_out,
-                          [&](std::size_t i, std::uint64_t a, std::uint64_t b, const report_views& v)
-                          {
-                              out[i].positions.assign(v.positions + a, v.positions + b);
-                              out[i].distances.assign(v.distances + a, v.distances + b);
-                              out[i].lengths.assign(v.lengths + a, v.lengths + b);
-                              out[i].found = std::size_t(v.found[i]);
-                          });
-            return out;
+            return edit_batch(queries, max_edits, &report, status_out);
         }
         std::vector<strand_hits> search_both_strands(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit,
                                                      const complement_table& complement, const report_options& report,
                                                      std::vector<std::uint8_t>& status_out) const
         {
-            std::vector<strand_hits> out(queries.size());
-            search_report("search_both_strands", queries, max_dist, edit ? KMX_APPROX_EDIT : 0u, report, complement.data(), status_out,
-                          [&](std::size_t i, std::uint64_t a, std::uint64_t b, const report_views& v)
-                          {
-                              out[i].positions.assign(v.positions + a, v.positions + b);
-                              out[i].distances.assign(v.distances + a, v.distances + b);
-                              out[i].strands.assign(v.strands + a, v.strands + b);
-                              if (edit) out[i].lengths.assign(v.lengths + a, v.lengths + b);
-                              out[i].found = std::size_t(v.found[i]);
-                          });
-            return out;
+            return strand_batch(queries, max_dist, edit, complement, &report, status_out);
         }
         std::vector<strand_hits> search_both_strands(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit,
                                                      const report_options& report, std::vector<std::uint8_t>& status_out) const
@@ -598,8 +491,9 @@ namespace kmer
             return search_both_strands(queries, max_dist, edit, natural_complement(), report, status_out);
         }
 
-        // the views of one kmx_search_approx_opts result (lengths: edit only, strands: both strands only)
-        struct report_views
+    private:
+        // the views of one approximate result (lengths: edit only, strands: both strands only, found: report_options only)
+        struct approx_views
         {
             const std::uint32_t* positions = nullptr;
             const std::uint8_t* distances = nullptr;
@@ -607,36 +501,105 @@ namespace kmer
             const std::uint8_t* strands = nullptr;
             const std::uint64_t* found = nullptr;
         };
-        // one kmx_search_approx_opts call; each(i, first hit, end of hits, views) fills query i of the caller's result
+        // One call of the engine: kmx_search_approx_opts with report_options, else the older entry point (kmx_search_approx, or
+        // kmx_search_approx_strands with a complement); each(i, first hit, end of hits, views) fills query i of the caller's result.
         template<typename each_t>
-        void search_report(const char* who, const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, std::uint32_t edit_flag,
-                           const report_options& report, const std::uint8_t* complement, std::vector<std::uint8_t>& status_out, each_t&& each) const
+        void approx_call(const char* who, const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit,
+                         const std::uint8_t* complement, const report_options* report, std::vector<std::uint8_t>& status_out, each_t&& each) const
         {
-            std::vector<std::uint8_t> ranks;
-            std::vector<std::uint64_t> off(queries.size() + 1, 0);
-            for (std::size_t i = 0; i < queries.size(); ++i) off[i + 1] = off[i] + queries[i].size();
-            ranks.reserve(off.back());
-            for (auto const& q : queries)
-                for (auto const& l : q) ranks.push_back(traits::to_rank(l));
-            kmx_approx_options options;
-            options.struct_size = std::uint32_t(sizeof options);
-            options.max_subst = std::uint32_t(max_dist);
-            options.flags = edit_flag | (report.loci ? KMX_APPROX_LOCI : 0u) | (report.best ? KMX_APPROX_BEST : 0u);
-            options.max_hits = std::uint32_t(report.max_hits);
-            options.complement = complement;
+            const flat_queries f = flatten(queries);
+            const std::uint32_t d = std::uint32_t(max_dist), edit_flag = edit ? KMX_APPROX_EDIT : 0u;
             kmx_approx_result* raw = nullptr;
-            detail::throw_on(kmx_search_approx_opts(_index.get(), ranks.data(), off.data(), queries.size(), &options, &raw), who);
+            if (report)
+            {
+                kmx_approx_options options;
+                options.struct_size = std::uint32_t(sizeof options);
+                options.max_subst = d;
+                options.flags = edit_flag | (report->loci ? KMX_APPROX_LOCI : 0u) | (report->best ? KMX_APPROX_BEST : 0u);
+                options.max_hits = std::uint32_t(report->max_hits);
+                options.complement = complement;
+                detail::throw_on(kmx_search_approx_opts(_index.get(), f.ranks.data(), f.off.data(), queries.size(), &options, &raw), who);
+            }
+            else if (complement)
+                detail::throw_on(kmx_search_approx_strands(_index.get(), f.ranks.data(), f.off.data(), queries.size(), d, edit_flag, complement, &raw), who);
+            else
+                detail::throw_on(kmx_search_approx(_index.get(), f.ranks.data(), f.off.data(), queries.size(), d, edit_flag, &raw), who);
             std::unique_ptr<kmx_approx_result, void (*)(kmx_approx_result*)> hold(raw, kmx_approx_free);
             const std::uint64_t* hit_off; const std::uint8_t* status;
-            report_views v;
+            approx_views v;
             detail::throw_on(kmx_approx_view(raw, &hit_off, &v.positions, &v.distances, &status), who);
-            detail::throw_on(kmx_approx_found(raw, &v.found), who);
-            if (edit_flag) detail::throw_on(kmx_approx_lengths(raw, &v.lengths), who);
+            if (report) detail::throw_on(kmx_approx_found(raw, &v.found), who);
+            if (edit) detail::throw_on(kmx_approx_lengths(raw, &v.lengths), who);
             if (complement) detail::throw_on(kmx_approx_strands(raw, &v.strands), who);
             status_out.assign(status, status + queries.size());
             for (std::size_t i = 0; i < queries.size(); ++i) each(i, hit_off[i], hit_off[i + 1], v);
         }
 
+        // the status_out overloads of each search, with report_options or (report == nullptr: `found` stays 0) without
+        std::vector<approx_hits> approx_batch(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_subst,
+                                              const report_options* report, std::vector<std::uint8_t>& status_out) const
+        {
+            std::vector<approx_hits> out(queries.size());
+            approx_call("search_approx", queries, max_subst, false, nullptr, report, status_out,
+                        [&](std::size_t i, std::uint64_t a, std::uint64_t b, const approx_views& v)
+                        {
+                            out[i].positions.assign(v.positions + a, v.positions + b);
+                            out[i].mismatches.assign(v.distances + a, v.distances + b);
+                            if (v.found) out[i].found = std::size_t(v.found[i]);
+                        });
+            return out;
+        }
+        std::vector<edit_hits> edit_batch(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_edits,
+                                          const report_options* report, std::vector<std::uint8_t>& status_out) const
+        {
+            std::vector<edit_hits> out(queries.size());
+            approx_call("search_edit", queries, max_edits, true, nullptr, report, status_out,
+                        [&](std::size_t i, std::uint64_t a, std::uint64_t b, const approx_views& v)
+                        {
+                            out[i].positions.assign(v.positions + a, v.positions + b);
+                            out[i].distances.assign(v.distances + a, v.distances + b);
+                            out[i].lengths.assign(v.lengths + a, v.lengths + b);
+                            if (v.found) out[i].found = std::size_t(v.found[i]);
+                        });
+            return out;
+        }
+        std::vector<strand_hits> strand_batch(const std::vector<std::vector<alphabet_t>>& queries, std::size_t max_dist, bool edit,
+                                              const complement_table& complement, const report_options* report,
+                                              std::vector<std::uint8_t>& status_out) const
+        {
+            std::vector<strand_hits> out(queries.size());
+            approx_call("search_both_strands", queries, max_dist, edit, complement.data(), report, status_out,
+                        [&](std::size_t i, std::uint64_t a, std::uint64_t b, const approx_views& v)
+                        {
+                            out[i].positions.assign(v.positions + a, v.positions + b);
+                            out[i].distances.assign(v.distances + a, v.distances + b);
+                            out[i].strands.assign(v.strands + a, v.strands + b);
+                            if (edit) out[i].lengths.assign(v.lengths + a, v.lengths + b);
+                            if (v.found) out[i].found = std::size_t(v.found[i]);
+                        });
+            return out;
+        }
+
+        // approx_query_error for the first query that was not served; its results are the others' positions and distances
+        template<typename hits_t>
+        void throw_unserved(std::vector<std::uint8_t>& status, std::vector<hits_t>& out) const
+        {
+            for (std::size_t i = 0; i < status.size(); ++i)
+            {
+                if (status[i] == KMX_Q_OK) continue;
+                const std::string what = query_status_message(status[i]);   // (before status is moved into the exception)
+                std::vector<approx_hits> others(out.size());
+                for (std::size_t j = 0; j < out.size(); ++j)
+                {
+                    others[j].positions = std::move(out[j].positions);
+                    if constexpr (std::is_same_v<hits_t, approx_hits>) others[j].mismatches = std::move(out[j].mismatches);
+                    else others[j].mismatches = std::move(out[j].distances);
+                }
+                throw approx_query_error(what, i, std::move(status), std::move(others));
+            }
+        }
+
+    public:
         // the text, reconstructed on the device from the index (kmx_index_text; an extension, no reference interface)
         std::vector<alphabet_t> text() const
         {

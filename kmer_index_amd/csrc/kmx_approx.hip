@@ -1004,31 +1004,157 @@ struct ResultGuard {
         kmx_result_free(r);
     }
 };
-} // namespace
 
-namespace {
-struct EditBufs {
-    Buf keep, bcount, bsum, bscan, total, ka, va, kb, vb, ukeys, olen;
+#define AX_OK(expr) do { const kmx_status st__ = (expr); if (st__ != KMX_OK) return st__; } while (0)
+// a launch and its launch error; AX_LAUNCH: a kernel on `blocks` blocks of kBlock threads on stream s
+#define AX_RUN(...) do { __VA_ARGS__; AX_TRY(hipGetLastError()); } while (0)
+#define AX_LAUNCH(kernel, blocks, s, ...) AX_RUN(hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, s, __VA_ARGS__))
+
+// One chunk's hit lists on the device, as one stage hands them to the next: the statuses of its nq queries, hit_off[nq + 1],
+// n_hits positions and distances (Hamming: mismatches); len is NULL unless KMX_APPROX_EDIT, strand is NULL for one strand.
+struct ChunkLists {
+    uint64_t nq = 0, n_hits = 0;
+    const uint8_t* stat = nullptr;
+    const uint64_t* hit_off = nullptr;
+    const uint32_t* pos = nullptr;
+    const uint8_t* dist = nullptr;
+    const uint32_t* len = nullptr;
+    const uint8_t* strand = nullptr;
 };
+struct PrepBufs {
+    std::vector<uint64_t> loc;                           // the chunk's query offsets on the host, rebased to the chunk
+    Buf qr, qoff, poff, qstat, qwords, qcand, raw, d_loc, comp, pair_stat;      // (the last four: both strands only)
+};
+struct SubstBufs { Buf keep, bcount, bsum, bscan, total, spos, spiece, smm, hit_off, opos, omm; };
+struct EditBufs { Buf keep, bcount, bsum, bscan, total, ka, va, kb, vb, ukeys, hit_off, opos, od, olen; };
+struct StrandBufs { Buf off, pos, d, len, strand; };
+struct ReportBufs { Buf hq, code, qcnt, rule, found, flag, rscan, dest, bsum, total, off, pos, d, len, strand; };
 // what kmx_search_approx_opts asks for beyond the older entry points (they pass a default-constructed one)
 struct ReportOpts {
     bool api = false, loci = false, best = false;
     uint32_t max_hits = 0;
     bool on() const { return loci || best || max_hits != 0; }
 };
-struct ReportBufs {
-    Buf hq, code, qcnt, rule, found, flag, rscan, dest, bsum, total, off, pos, d, len, strand;
-};
 inline uint32_t bit_width(uint64_t x) { uint32_t b = 0; while (x) { ++b; x >>= 1; } return b; }
 } // namespace
 
-// The edit path of one chunk behind the piece search: hit_off[nq + 1], positions, distances and lengths of its queries on the
-// device, *n_hits of them.
-static kmx_status edit_chunk(hipStream_t s, EditArgs V, uint32_t w, uint64_t nq, EditBufs& B, PinnedArr& h_total, Buf& d_hit_off, Buf& d_opos,
-                             Buf& d_od, uint64_t* n_hits)
+// *n <- the total a scan left on the device; the stream is drained
+static kmx_status read_total(hipStream_t s, const Buf& d_total, PinnedArr& h_total, uint64_t* n)
 {
-    *n_hits = 0;
-    const uint32_t e = V.e;
+    AX_TRY(hipMemcpyAsync(h_total.p, d_total.p, 8, hipMemcpyDeviceToHost, s));
+    AX_TRY(hipStreamSynchronize(s));
+    *n = h_total.as<uint64_t>()[0];
+    return KMX_OK;
+}
+
+static kmx_status grow_pinned(PinnedArr& a, size_t bytes, const std::string& who)
+{
+    return a.grow(bytes) ? KMX_OK : kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
+}
+
+static kmx_status check_queries(const std::string& who, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq)
+{
+    if (nq && !qoff) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "NULL query offsets");
+    if (nq && qoff[0] != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "qoff[0] must be 0");
+    for (uint64_t i = 0; i < nq; ++i)
+        if (qoff[i + 1] < qoff[i]) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "qoff must be non-decreasing");
+    if (nq && !qranks && qoff[nq] != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "NULL query letters");
+    return KMX_OK;
+}
+
+// comp[256] <- the complement table, the identity outside the alphabet (letters there: the pair is KMX_Q_BAD_RANK)
+static kmx_status check_complement(const std::string& who, const uint8_t* complement, uint32_t sigma, uint8_t* comp)
+{
+    for (uint32_t r = 0; r < 256; ++r) comp[r] = uint8_t(r);
+    for (uint32_t r = 0; r < sigma && r < 256; ++r)                   // every entry's range first: an entry outside the alphabet is
+        if (complement[r] >= sigma)                                   // reported as that, whichever rank maps to it
+            return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "complement[" + std::to_string(r) + "] is outside the alphabet");
+    for (uint32_t r = 0; r < sigma && r < 256; ++r) {
+        const uint32_t c = complement[r];
+        if (complement[c] != r)
+            return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "the complement table is not an involution at rank " + std::to_string(r));
+        comp[r] = uint8_t(c);
+    }
+    return KMX_OK;
+}
+
+// The letters of queries [Q0, Q1) (a copy the prep kernel may overwrite) and their offsets, rebased, to the device; from them
+// the chunk's internal queries (S = 2: every query and its reverse complement), their pieces, statuses and packed words.
+static kmx_status prep_chunk(hipStream_t s, const kmx::IndexAccess& A, const uint8_t* qranks, const uint64_t* qoff, uint64_t Q0, uint64_t Q1,
+                             uint32_t S, uint32_t e, PrepBufs& B)
+{
+    const uint64_t nqc = Q1 - Q0, nqi = nqc * S, l0 = qoff[Q0], n_letters = qoff[Q1] - l0;
+    const uint32_t E1 = e + 1, w = A.text->w, L = 64 / w;
+    B.loc.resize(nqc + 1);
+    for (uint64_t i = 0; i <= nqc; ++i) B.loc[i] = qoff[Q0 + i] - l0;
+    AX_TRY(B.qr.ensure(n_letters * S + 64));
+    AX_TRY(B.qoff.ensure((nqi + 1) * 8));
+    AX_TRY(B.poff.ensure((nqi * E1 + 1) * 8));
+    AX_TRY(B.qstat.ensure(nqi + 16));
+    AX_TRY(B.qwords.ensure((n_letters * S / L + nqi + 2) * 8));
+    AX_TRY(B.qcand.ensure((nqc + 1) * 8));
+    if (S == 2) {
+        AX_TRY(B.raw.ensure(n_letters + 64));
+        AX_TRY(B.d_loc.ensure((nqc + 1) * 8));
+        AX_TRY(B.pair_stat.ensure(nqc + 16));
+    }
+    const Buf &letters = S == 1 ? B.qr : B.raw, &offs = S == 1 ? B.qoff : B.d_loc;      // what the prep kernel reads
+    if (n_letters) AX_TRY(hipMemcpyAsync(letters.p, qranks + l0, n_letters, hipMemcpyHostToDevice, s));
+    AX_TRY(hipMemcpyAsync(offs.p, B.loc.data(), (nqc + 1) * 8, hipMemcpyHostToDevice, s));
+    if (S == 1)
+        AX_LAUNCH(k_approx_prep, grid_for(nqc, kBlock), s, B.qr.as<uint8_t>(), B.qoff.as<uint64_t>(), nqc, A.sigma, e, A.range, w,
+                  B.poff.as<uint64_t>(), B.qstat.as<uint8_t>(), B.qwords.as<uint64_t>());
+    else
+        AX_LAUNCH(k_strand_prep, grid_for(nqc, kBlock), s, B.raw.as<uint8_t>(), B.d_loc.as<uint64_t>(), nqc, B.comp.as<uint8_t>(), A.sigma, e, A.range,
+                  w, B.qr.as<uint8_t>(), B.qoff.as<uint64_t>(), B.poff.as<uint64_t>(), B.qstat.as<uint8_t>(), B.qwords.as<uint64_t>());
+    return KMX_OK;
+}
+
+// a chunk without a hit: L <- hit_off all zero
+static kmx_status no_hits(hipStream_t s, const Buf& hit_off, ChunkLists& L)
+{
+    AX_TRY(hipMemsetAsync(hit_off.p, 0, (L.nq + 1) * 8, s));
+    L = ChunkLists{L.nq, 0, L.stat, hit_off.as<uint64_t>()};
+    return KMX_OK;
+}
+
+// The substitution path of one chunk behind the piece search: L <- hit_off, positions and mismatches of its L.nq queries.
+static kmx_status subst_chunk(hipStream_t s, VerifyArgs V, SubstBufs& B, PinnedArr& h_total, ChunkLists& L)
+{
+    AX_TRY(B.hit_off.ensure((L.nq + 1) * 8));
+    if (!V.n_cand) return no_hits(s, B.hit_off, L);
+    const uint64_t nb = (V.n_cand + kVerifySpan - 1) / kVerifySpan;
+    AX_TRY(B.keep.ensure(V.n_cand));
+    AX_TRY(B.bcount.ensure(nb * 4 + 16));
+    AX_TRY(B.bsum.ensure(kmx::scan_blocks(nb) * 8 + 16));
+    AX_TRY(B.bscan.ensure((nb + 1) * 8));
+    AX_TRY(B.total.ensure(16));
+    V.keep = B.keep.as<uint8_t>();
+    V.bcount = B.bcount.as<uint32_t>();
+    AX_LAUNCH(k_approx_verify, unsigned(nb), s, V);
+    AX_RUN(kmx::launch_scan(s, V.bcount, nb, B.bsum.as<uint64_t>(), B.bscan.as<uint64_t>(), B.total.as<unsigned long long>()));
+    uint64_t n_s = 0;
+    AX_OK(read_total(s, B.total, h_total, &n_s));
+    if (!n_s) return no_hits(s, B.hit_off, L);
+    AX_TRY(B.spos.ensure(n_s * 4));
+    AX_TRY(B.spiece.ensure(n_s * 4));
+    AX_TRY(B.smm.ensure(n_s));
+    AX_TRY(B.opos.ensure(n_s * 4));
+    AX_TRY(B.omm.ensure(n_s));
+    AX_LAUNCH(k_approx_compact, unsigned(nb), s, V, B.bscan.as<uint64_t>(), B.spos.as<uint32_t>(), B.spiece.as<uint32_t>(), B.smm.as<uint8_t>());
+    AX_LAUNCH(k_approx_merge, grid_for(n_s, kBlock), s, B.spos.as<uint32_t>(), B.spiece.as<uint32_t>(), B.smm.as<uint8_t>(), n_s, V.e,
+              B.opos.as<uint32_t>(), B.omm.as<uint8_t>());
+    AX_LAUNCH(k_approx_hit_off, grid_for(L.nq + 1, kBlock), s, B.spiece.as<uint32_t>(), n_s, L.nq, V.e, B.hit_off.as<uint64_t>());
+    L = ChunkLists{L.nq, n_s, L.stat, B.hit_off.as<uint64_t>(), B.opos.as<uint32_t>(), B.omm.as<uint8_t>()};
+    return KMX_OK;
+}
+
+// The edit path of one chunk behind the piece search: L <- hit_off, positions, distances and lengths of its L.nq queries.
+static kmx_status edit_chunk(hipStream_t s, EditArgs V, uint32_t w, EditBufs& B, PinnedArr& h_total, ChunkLists& L)
+{
+    const uint64_t nq = L.nq;
+    AX_TRY(B.hit_off.ensure((nq + 1) * 8));
+    if (!V.n_cand) return no_hits(s, B.hit_off, L);
     const uint64_t nb = (V.n_cand + kVerifySpan - 1) / kVerifySpan;
     AX_TRY(B.keep.ensure(V.n_cand * 4));
     AX_TRY(B.bcount.ensure(nb * 4 + 16));
@@ -1037,21 +1163,17 @@ static kmx_status edit_chunk(hipStream_t s, EditArgs V, uint32_t w, uint64_t nq,
     AX_TRY(B.total.ensure(16));
     V.keep = B.keep.as<uint32_t>();
     V.bcount = B.bcount.as<uint32_t>();
-    edit_dispatch<LaunchEditVerify>(e, w, s, unsigned(nb), V);
-    AX_TRY(hipGetLastError());
-    kmx::launch_scan(s, V.bcount, nb, B.bsum.as<uint64_t>(), B.bscan.as<uint64_t>(), B.total.as<unsigned long long>());
-    AX_TRY(hipGetLastError());
-    AX_TRY(hipMemcpyAsync(h_total.p, B.total.p, 8, hipMemcpyDeviceToHost, s));
-    AX_TRY(hipStreamSynchronize(s));
-    const uint64_t n_s = h_total.as<uint64_t>()[0];
-    if (!n_s) return KMX_OK;
+    AX_RUN(edit_dispatch<LaunchEditVerify>(V.e, w, s, unsigned(nb), V));
+    AX_RUN(kmx::launch_scan(s, V.bcount, nb, B.bsum.as<uint64_t>(), B.bscan.as<uint64_t>(), B.total.as<unsigned long long>()));
+    uint64_t n_s = 0, n_u = 0;
+    AX_OK(read_total(s, B.total, h_total, &n_s));
+    if (!n_s) return no_hits(s, B.hit_off, L);
     const uint32_t pbits = std::max(bit_width(V.n - 1), 1u), key_bits = pbits + bit_width(nq - 1);
     AX_TRY(B.ka.ensure((n_s + 1) * 8));                                      // (+ 1: whichever pair the sort leaves free takes a scan of
     AX_TRY(B.kb.ensure((n_s + 1) * 8));                                      //  n_s entries and its total)
     AX_TRY(B.va.ensure(n_s * 4));
     AX_TRY(B.vb.ensure(n_s * 4));
-    hipLaunchKernelGGL(k_edit_emit, dim3(unsigned(nb)), dim3(kBlock), 0, s, V, B.bscan.as<uint64_t>(), pbits, B.ka.as<uint64_t>(), B.va.as<uint32_t>());
-    AX_TRY(hipGetLastError());
+    AX_LAUNCH(k_edit_emit, unsigned(nb), s, V, B.bscan.as<uint64_t>(), pbits, B.ka.as<uint64_t>(), B.va.as<uint32_t>());
     bool in_b = false;
     AX_TRY(kmx::sort_pairs_u64(s, B.ka.as<uint64_t>(), B.va.as<uint32_t>(), B.kb.as<uint64_t>(), B.vb.as<uint32_t>(), n_s, key_bits, &in_b));
     const uint64_t* keys = in_b ? B.kb.as<uint64_t>() : B.ka.as<uint64_t>();
@@ -1059,33 +1181,46 @@ static kmx_status edit_chunk(hipStream_t s, EditArgs V, uint32_t w, uint64_t nq,
     uint64_t* rank = in_b ? B.ka.as<uint64_t>() : B.kb.as<uint64_t>();        // the other pair of arrays is free again
     uint32_t* head = in_b ? B.va.as<uint32_t>() : B.vb.as<uint32_t>();
     AX_TRY(B.bsum.ensure(kmx::scan_blocks(n_s) * 8 + 16));
-    hipLaunchKernelGGL(k_edit_heads, dim3(grid_for(n_s, kBlock)), dim3(kBlock), 0, s, keys, n_s, head);
-    AX_TRY(hipGetLastError());
-    kmx::launch_scan(s, head, n_s, B.bsum.as<uint64_t>(), rank, B.total.as<unsigned long long>());
-    AX_TRY(hipGetLastError());
-    AX_TRY(hipMemcpyAsync(h_total.p, B.total.p, 8, hipMemcpyDeviceToHost, s));
-    AX_TRY(hipStreamSynchronize(s));
-    const uint64_t n_u = h_total.as<uint64_t>()[0];
+    AX_LAUNCH(k_edit_heads, grid_for(n_s, kBlock), s, keys, n_s, head);
+    AX_RUN(kmx::launch_scan(s, head, n_s, B.bsum.as<uint64_t>(), rank, B.total.as<unsigned long long>()));
+    AX_OK(read_total(s, B.total, h_total, &n_u));                             // (n_u >= 1: the first key heads a run)
     AX_TRY(B.ukeys.ensure(n_u * 8));
-    AX_TRY(d_opos.ensure(n_u * 4));
-    AX_TRY(d_od.ensure(n_u));
+    AX_TRY(B.opos.ensure(n_u * 4));
+    AX_TRY(B.od.ensure(n_u));
     AX_TRY(B.olen.ensure(n_u * 4));
-    hipLaunchKernelGGL(k_edit_unique, dim3(grid_for(n_s, kBlock)), dim3(kBlock), 0, s, keys, vals, head, rank, n_s, pbits, B.ukeys.as<uint64_t>(),
-                       d_opos.as<uint32_t>(), d_od.as<uint8_t>());
-    AX_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_edit_hit_off, dim3(grid_for(nq + 1, kBlock)), dim3(kBlock), 0, s, B.ukeys.as<uint64_t>(), n_u, nq, pbits, d_hit_off.as<uint64_t>());
-    AX_TRY(hipGetLastError());
-    edit_dispatch<LaunchEditLengths>(e, w, s, B.ukeys.as<uint64_t>(), d_od.as<uint8_t>(), n_u, pbits, V, B.olen.as<uint32_t>());
-    AX_TRY(hipGetLastError());
-    *n_hits = n_u;
+    AX_LAUNCH(k_edit_unique, grid_for(n_s, kBlock), s, keys, vals, head, rank, n_s, pbits, B.ukeys.as<uint64_t>(), B.opos.as<uint32_t>(),
+              B.od.as<uint8_t>());
+    AX_LAUNCH(k_edit_hit_off, grid_for(nq + 1, kBlock), s, B.ukeys.as<uint64_t>(), n_u, nq, pbits, B.hit_off.as<uint64_t>());
+    AX_RUN(edit_dispatch<LaunchEditLengths>(V.e, w, s, B.ukeys.as<uint64_t>(), B.od.as<uint8_t>(), n_u, pbits, V, B.olen.as<uint32_t>()));
+    L = ChunkLists{nq, n_u, L.stat, B.hit_off.as<uint64_t>(), B.opos.as<uint32_t>(), B.od.as<uint8_t>(), B.olen.as<uint32_t>()};
     return KMX_OK;
 }
 
-// The reporting stage of one chunk with hits: the lists of P filtered into B.off / B.pos / B.d / B.len / B.strand, found[] of
-// the chunk's queries into B.found, *n_hits <- the hits kept.
-static kmx_status report_chunk(hipStream_t s, const ReportArgs& P, const uint32_t* len_in, ReportBufs& B, PinnedArr& h_total, uint64_t* n_hits)
+// Both strands: each pair's two lists of L merged into the pair's one, ordered by (position, strand), with the pairs' statuses.
+static kmx_status strand_merge_chunk(hipStream_t s, const uint8_t* pair_stat, StrandBufs& B, ChunkLists& L)
 {
-    const uint64_t n_s = P.n_s, nq = P.nq;
+    const uint64_t n_pairs = L.nq / 2, n_s = L.n_hits;
+    AX_TRY(B.off.ensure((n_pairs + 1) * 8));
+    if (!n_s) AX_TRY(hipMemsetAsync(B.off.p, 0, (n_pairs + 1) * 8, s));
+    if (n_s) {
+        AX_TRY(B.pos.ensure(n_s * 4));
+        AX_TRY(B.d.ensure(n_s));
+        AX_TRY(B.strand.ensure(n_s));
+        if (L.len) AX_TRY(B.len.ensure(n_s * 4));
+        AX_LAUNCH(k_strand_merge, grid_for(std::max(n_s, n_pairs + 1), kBlock), s, L.hit_off, n_pairs, n_s, L.pos, L.dist, L.len, B.pos.as<uint32_t>(),
+                  B.d.as<uint8_t>(), B.len.as<uint32_t>(), B.strand.as<uint8_t>(), B.off.as<uint64_t>());
+    }
+    L = ChunkLists{n_pairs, n_s, pair_stat, B.off.as<uint64_t>(), B.pos.as<uint32_t>(), B.d.as<uint8_t>(), L.len ? B.len.as<uint32_t>() : nullptr,
+                   B.strand.as<uint8_t>()};
+    return KMX_OK;
+}
+
+// The reporting stage of one chunk: the lists of L filtered and compacted on the device, found[] of its queries to h_found.
+static kmx_status report_chunk(hipStream_t s, const ReportOpts& rep, uint32_t e, ReportBufs& B, PinnedArr& h_total, uint64_t* h_found, ChunkLists& L)
+{
+    const uint64_t n_s = L.n_hits, nq = L.nq;
+    if (!n_s) { std::memset(h_found, 0, nq * 8); return KMX_OK; }
+    const ReportArgs P{L.hit_off, nq, n_s, L.pos, L.dist, L.strand, e, rep.loci, rep.best, rep.max_hits};
     AX_TRY(B.hq.ensure(n_s * 4));
     AX_TRY(B.code.ensure(n_s));
     AX_TRY(B.qcnt.ensure(nq * kStrata * 4));
@@ -1098,37 +1233,53 @@ static kmx_status report_chunk(hipStream_t s, const ReportArgs& P, const uint32_
     AX_TRY(B.off.ensure((nq + 1) * 8));
     const unsigned hit_blocks = grid_for(n_s, kBlock);
     AX_TRY(hipMemsetAsync(B.qcnt.p, 0, nq * kStrata * 4, s));
-    hipLaunchKernelGGL(k_report_mark, dim3(hit_blocks), dim3(kBlock), 0, s, P, B.hq.as<uint32_t>(), B.code.as<uint8_t>(), B.qcnt.as<uint32_t>());
-    AX_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_report_query, dim3(grid_for(nq, kBlock)), dim3(kBlock), 0, s, B.qcnt.as<uint32_t>(), nq, P.best, P.max_hits,
-                       B.found.as<uint64_t>(), B.rule.as<uint64_t>());
-    AX_TRY(hipGetLastError());
+    AX_LAUNCH(k_report_mark, hit_blocks, s, P, B.hq.as<uint32_t>(), B.code.as<uint8_t>(), B.qcnt.as<uint32_t>());
+    AX_LAUNCH(k_report_query, grid_for(nq, kBlock), s, B.qcnt.as<uint32_t>(), nq, P.best, P.max_hits, B.found.as<uint64_t>(), B.rule.as<uint64_t>());
     const uint64_t* rscan = nullptr;
     if (P.max_hits) {
         AX_TRY(B.rscan.ensure((n_s + 1) * 8));
-        hipLaunchKernelGGL(k_report_ind, dim3(hit_blocks), dim3(kBlock), 0, s, B.code.as<uint8_t>(), B.hq.as<uint32_t>(), B.rule.as<uint64_t>(), n_s,
-                           B.flag.as<uint32_t>());
-        AX_TRY(hipGetLastError());
-        kmx::launch_scan(s, B.flag.as<uint32_t>(), n_s, B.bsum.as<uint64_t>(), B.rscan.as<uint64_t>(), B.total.as<unsigned long long>());
-        AX_TRY(hipGetLastError());
+        AX_LAUNCH(k_report_ind, hit_blocks, s, B.code.as<uint8_t>(), B.hq.as<uint32_t>(), B.rule.as<uint64_t>(), n_s, B.flag.as<uint32_t>());
+        AX_RUN(kmx::launch_scan(s, B.flag.as<uint32_t>(), n_s, B.bsum.as<uint64_t>(), B.rscan.as<uint64_t>(), B.total.as<unsigned long long>()));
         rscan = B.rscan.as<uint64_t>();
     }
-    hipLaunchKernelGGL(k_report_keep, dim3(hit_blocks), dim3(kBlock), 0, s, B.code.as<uint8_t>(), B.hq.as<uint32_t>(), B.rule.as<uint64_t>(), P.hit_off,
-                       rscan, n_s, B.flag.as<uint32_t>());
-    AX_TRY(hipGetLastError());
-    kmx::launch_scan(s, B.flag.as<uint32_t>(), n_s, B.bsum.as<uint64_t>(), B.dest.as<uint64_t>(), B.total.as<unsigned long long>());
-    AX_TRY(hipGetLastError());
-    AX_TRY(hipMemcpyAsync(h_total.p, B.total.p, 8, hipMemcpyDeviceToHost, s));
-    AX_TRY(hipStreamSynchronize(s));
-    const uint64_t n_keep = h_total.as<uint64_t>()[0];
+    AX_LAUNCH(k_report_keep, hit_blocks, s, B.code.as<uint8_t>(), B.hq.as<uint32_t>(), B.rule.as<uint64_t>(), P.hit_off, rscan, n_s,
+              B.flag.as<uint32_t>());
+    AX_RUN(kmx::launch_scan(s, B.flag.as<uint32_t>(), n_s, B.bsum.as<uint64_t>(), B.dest.as<uint64_t>(), B.total.as<unsigned long long>()));
+    uint64_t n_keep = 0;
+    AX_OK(read_total(s, B.total, h_total, &n_keep));
     AX_TRY(B.pos.ensure(n_keep * 4 + 16));
     AX_TRY(B.d.ensure(n_keep + 16));
-    if (len_in) AX_TRY(B.len.ensure(n_keep * 4 + 16));
-    if (P.strand) AX_TRY(B.strand.ensure(n_keep + 16));
-    hipLaunchKernelGGL(k_report_compact, dim3(grid_for(std::max(n_s, nq + 1), kBlock)), dim3(kBlock), 0, s, P, len_in, B.flag.as<uint32_t>(),
-                       B.dest.as<uint64_t>(), B.pos.as<uint32_t>(), B.d.as<uint8_t>(), B.len.as<uint32_t>(), B.strand.as<uint8_t>(), B.off.as<uint64_t>());
-    AX_TRY(hipGetLastError());
-    *n_hits = n_keep;
+    if (L.len) AX_TRY(B.len.ensure(n_keep * 4 + 16));
+    if (L.strand) AX_TRY(B.strand.ensure(n_keep + 16));
+    AX_LAUNCH(k_report_compact, grid_for(std::max(n_s, nq + 1), kBlock), s, P, L.len, B.flag.as<uint32_t>(), B.dest.as<uint64_t>(), B.pos.as<uint32_t>(),
+              B.d.as<uint8_t>(), B.len.as<uint32_t>(), B.strand.as<uint8_t>(), B.off.as<uint64_t>());
+    AX_TRY(hipMemcpyAsync(h_found, B.found.p, nq * 8, hipMemcpyDeviceToHost, s));
+    L = ChunkLists{nq, n_keep, L.stat, B.off.as<uint64_t>(), B.pos.as<uint32_t>(), B.d.as<uint8_t>(), L.len ? B.len.as<uint32_t>() : nullptr,
+                   L.strand ? B.strand.as<uint8_t>() : nullptr};
+    return KMX_OK;
+}
+
+// The chunk's lists to the host arrays of R, for the queries from q_at on: the copies, one wait for them, hit_off rebased to the
+// hits of the chunks before.
+static kmx_status publish_chunk(hipStream_t s, const std::string& who, const ChunkLists& L, uint64_t q_at, kmx_approx_result& R)
+{
+    const uint64_t h_at = R.n_hits, n = L.n_hits;
+    AX_OK(grow_pinned(R.positions, (h_at + n) * 4 + 64, who));
+    AX_OK(grow_pinned(R.mismatches, h_at + n + 64, who));
+    if (R.edit) AX_OK(grow_pinned(R.lengths, (h_at + n) * 4 + 64, who));
+    if (R.strands) AX_OK(grow_pinned(R.strand, h_at + n + 64, who));
+    uint64_t* ho = R.hit_off.as<uint64_t>() + q_at;          // (ho[0], the previous chunk's end, is rewritten with the same value)
+    AX_TRY(hipMemcpyAsync(ho, L.hit_off, (L.nq + 1) * 8, hipMemcpyDeviceToHost, s));
+    AX_TRY(hipMemcpyAsync(R.status.as<uint8_t>() + q_at, L.stat, L.nq, hipMemcpyDeviceToHost, s));
+    if (n) {
+        AX_TRY(hipMemcpyAsync(R.positions.as<uint32_t>() + h_at, L.pos, n * 4, hipMemcpyDeviceToHost, s));
+        AX_TRY(hipMemcpyAsync(R.mismatches.as<uint8_t>() + h_at, L.dist, n, hipMemcpyDeviceToHost, s));
+        if (R.edit) AX_TRY(hipMemcpyAsync(R.lengths.as<uint32_t>() + h_at, L.len, n * 4, hipMemcpyDeviceToHost, s));
+        if (R.strands) AX_TRY(hipMemcpyAsync(R.strand.as<uint8_t>() + h_at, L.strand, n, hipMemcpyDeviceToHost, s));
+    }
+    AX_TRY(hipStreamSynchronize(s));
+    for (uint64_t i = 0; i <= L.nq; ++i) ho[i] += h_at;
+    R.n_hits += n;
     return KMX_OK;
 }
 
@@ -1143,14 +1294,12 @@ kmx_status kmx_index_text(const kmx_index* index, uint8_t* out_ranks, uint64_t n
     AX_TRY(hipSetDevice(A.device));
     StreamGuard sg;
     AX_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-    kmx_status st = ensure_text(A, sg.s);
-    if (st != KMX_OK) return st;
+    AX_OK(ensure_text(A, sg.s));
     if (packed_bytes) *packed_bytes = A.text->n_words * 8;
     if (!out_ranks || n == 0) return KMX_OK;
     Buf out;
     AX_TRY(out.ensure(n));
-    hipLaunchKernelGGL(k_text_unpack, dim3(std::min<unsigned>(grid_for(n, kBlock), 65536u)), dim3(kBlock), 0, sg.s, A.text->d_words, n, A.text->w, out.as<uint8_t>());
-    AX_TRY(hipGetLastError());
+    AX_LAUNCH(k_text_unpack, std::min<unsigned>(grid_for(n, kBlock), 65536u), sg.s, A.text->d_words, n, A.text->w, out.as<uint8_t>());
     AX_TRY(hipMemcpyAsync(out_ranks, out.p, n, hipMemcpyDeviceToHost, sg.s));
     AX_TRY(hipStreamSynchronize(sg.s));
     return KMX_OK;
@@ -1167,29 +1316,14 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
     const std::string who = std::string(fn) + ": ";
     if (max_subst > KMX_APPROX_MAX_SUBST) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "max_subst > KMX_APPROX_MAX_SUBST");
     if (flags & ~uint32_t(KMX_APPROX_EDIT)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "unknown flag bits");
-    if (nq && !qoff) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "NULL query offsets");
-    if (nq && qoff[0] != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "qoff[0] must be 0");
-    for (uint64_t i = 0; i < nq; ++i)
-        if (qoff[i + 1] < qoff[i]) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "qoff must be non-decreasing");
-    if (nq && !qranks && qoff[nq] != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "NULL query letters");
+    AX_OK(check_queries(who, qranks, qoff, nq));
     *out = nullptr;
     const kmx::IndexAccess A = kmx::index_access(index);
     if (A.broken) return kmx::set_error(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
     const uint32_t e = max_subst, E1 = e + 1;
     const uint32_t S = complement ? 2u : 1u;             // internal queries per query (both strands: q and rc(q))
     uint8_t comp[256];
-    if (complement) {
-        for (uint32_t r = 0; r < 256; ++r) comp[r] = uint8_t(r);      // (letters outside the alphabet: the pair is KMX_Q_BAD_RANK)
-        for (uint32_t r = 0; r < A.sigma && r < 256; ++r)             // every entry's range first: an entry outside the alphabet is
-            if (complement[r] >= A.sigma)                             // reported as that, whichever rank maps to it
-                return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "complement[" + std::to_string(r) + "] is outside the alphabet");
-        for (uint32_t r = 0; r < A.sigma && r < 256; ++r) {
-            const uint32_t c = complement[r];
-            if (complement[c] != r)
-                return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "the complement table is not an involution at rank " + std::to_string(r));
-            comp[r] = uint8_t(c);
-        }
-    }
+    if (complement) AX_OK(check_complement(who, complement, A.sigma, comp));
     uint64_t budget = kDefaultBudget, max_pieces = kMaxPieces;
     if (const char* env = getenv("KMX_APPROX_CHUNK_CANDIDATES")) { const long long v = atoll(env); if (v > 0) budget = uint64_t(v); }
     if (const char* env = getenv("KMX_APPROX_CHUNK_PIECES")) { const long long v = atoll(env); if (v > 0) max_pieces = std::min(uint64_t(v), kMaxPieces); }
@@ -1201,79 +1335,43 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
     StreamGuard sg;
     AX_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
     hipStream_t s = sg.s;
-    kmx_status st = ensure_text(A, s);
-    if (st != KMX_OK) return st;
+    AX_OK(ensure_text(A, s));
     const uint64_t* text = A.text->d_words;
-    const uint32_t w = A.text->w, L = 64 / w;
+    const uint32_t w = A.text->w;
 
     std::unique_ptr<kmx_approx_result> R(new kmx_approx_result());
-    R->nq = nq;
-    R->edit = edit;
-    R->strands = complement != nullptr;
-    R->opts = rep.api;
-    R->reported = rep.on();
-    if (rep.on() && !R->found.grow((nq + 1) * 8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
-    if (complement && !R->strand.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
-    if (edit && !R->lengths.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
-    if (!R->hit_off.grow((nq + 1) * 8) || !R->status.grow(nq + 1) || !R->positions.grow(64) || !R->mismatches.grow(64))
-        return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
+    R->nq = nq; R->edit = edit; R->strands = complement != nullptr;
+    R->opts = rep.api; R->reported = rep.on();
+    if (rep.on()) AX_OK(grow_pinned(R->found, (nq + 1) * 8, who));
+    if (complement) AX_OK(grow_pinned(R->strand, 64, who));
+    if (edit) AX_OK(grow_pinned(R->lengths, 64, who));
+    AX_OK(grow_pinned(R->hit_off, (nq + 1) * 8, who));
+    AX_OK(grow_pinned(R->status, nq + 1, who));
+    AX_OK(grow_pinned(R->positions, 64, who));
+    AX_OK(grow_pinned(R->mismatches, 64, who));
     R->hit_off.as<uint64_t>()[0] = 0;
 
-    Buf d_qr, d_qoff, d_poff, d_qstat, d_qwords, d_qcand, d_keep, d_bcount, d_bsum, d_bscan, d_total, d_spos, d_spiece, d_smm,
-        d_hit_off, d_opos, d_omm;
-    Buf d_raw, d_loc, d_comp, d_pair_stat, d_pub_off, d_mpos, d_md, d_mlen, d_mstrand;      // both strands only
+    PrepBufs pb;
+    SubstBufs sb; EditBufs eb; StrandBufs mb; ReportBufs rb;      // each stage's own
     if (complement) {
-        AX_TRY(d_comp.ensure(256));
-        AX_TRY(hipMemcpyAsync(d_comp.p, comp, 256, hipMemcpyHostToDevice, s));
+        AX_TRY(pb.comp.ensure(256));
+        AX_TRY(hipMemcpyAsync(pb.comp.p, comp, 256, hipMemcpyHostToDevice, s));
     }
-    EditBufs eb;
-    ReportBufs rb;
     PinnedArr h_qcand, h_total;
-    if (!h_total.grow(64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
-    ResultGuard pres;
-    pres.s = s;
-    std::vector<uint64_t> loc;
+    AX_OK(grow_pinned(h_total, 64, who));
+    ResultGuard pres{nullptr, s};
     const uint64_t chunk_q = std::max<uint64_t>(max_pieces / (uint64_t(E1) * S), 1);      // (a pair is never split)
 
     for (uint64_t Q0 = 0; Q0 < nq;) {
         const uint64_t Q1 = std::min(nq, Q0 + chunk_q), nqc = Q1 - Q0;
-        const uint64_t l0 = qoff[Q0], n_letters = qoff[Q1] - l0;
-        // the chunk's letters (a copy the prep kernel may overwrite) and offsets, rebased to the chunk
-        loc.resize(nqc + 1);
-        for (uint64_t i = 0; i <= nqc; ++i) loc[i] = qoff[Q0 + i] - l0;
-        const uint64_t nqi = nqc * S;                        // internal queries of the chunk
-        AX_TRY(d_qr.ensure(n_letters * S + 64));
-        AX_TRY(d_qoff.ensure((nqi + 1) * 8));
-        AX_TRY(d_poff.ensure((nqi * E1 + 1) * 8));
-        AX_TRY(d_qstat.ensure(nqi + 16));
-        AX_TRY(d_qwords.ensure((n_letters * S / L + nqi + 2) * 8));
-        AX_TRY(d_qcand.ensure((nqc + 1) * 8));
-        if (S == 1) {
-            if (n_letters) AX_TRY(hipMemcpyAsync(d_qr.p, qranks + l0, n_letters, hipMemcpyHostToDevice, s));
-            AX_TRY(hipMemcpyAsync(d_qoff.p, loc.data(), (nqc + 1) * 8, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_approx_prep, dim3(grid_for(nqc, kBlock)), dim3(kBlock), 0, s, d_qr.as<uint8_t>(), d_qoff.as<uint64_t>(), nqc, A.sigma,
-                               e, A.range, w, d_poff.as<uint64_t>(), d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>());
-        } else {
-            AX_TRY(d_raw.ensure(n_letters + 64));
-            AX_TRY(d_loc.ensure((nqc + 1) * 8));
-            AX_TRY(d_pair_stat.ensure(nqc + 16));
-            if (n_letters) AX_TRY(hipMemcpyAsync(d_raw.p, qranks + l0, n_letters, hipMemcpyHostToDevice, s));
-            AX_TRY(hipMemcpyAsync(d_loc.p, loc.data(), (nqc + 1) * 8, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_strand_prep, dim3(grid_for(nqc, kBlock)), dim3(kBlock), 0, s, d_raw.as<uint8_t>(), d_loc.as<uint64_t>(), nqc,
-                               d_comp.as<uint8_t>(), A.sigma, e, A.range, w, d_qr.as<uint8_t>(), d_qoff.as<uint64_t>(), d_poff.as<uint64_t>(),
-                               d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>());
-        }
-        AX_TRY(hipGetLastError());
+        AX_OK(prep_chunk(s, A, qranks, qoff, Q0, Q1, S, e, pb));
         // candidates per query (both strands: per pair): the pieces through the exact search, counts only
-        st = kmx_search_batch_device(index, d_qr.p, d_poff.p, nqi * E1, KMX_SEARCH_COUNT_ONLY, s, &pres.r);
-        if (st != KMX_OK) return st;
+        AX_OK(kmx_search_batch_device(index, pb.qr.p, pb.poff.p, nqc * S * E1, KMX_SEARCH_COUNT_ONLY, s, &pres.r));
         const uint64_t* d_phit = nullptr;
-        st = kmx_result_view_device(pres.r, &d_phit, nullptr, nullptr);
-        if (st != KMX_OK) return st;
-        hipLaunchKernelGGL(k_approx_query_cands, dim3(grid_for(nqc + 1, kBlock)), dim3(kBlock), 0, s, d_phit, nqc, S * E1 - 1, d_qcand.as<uint64_t>());
-        AX_TRY(hipGetLastError());
-        if (!h_qcand.grow((nqc + 1) * 8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
-        AX_TRY(hipMemcpyAsync(h_qcand.p, d_qcand.p, (nqc + 1) * 8, hipMemcpyDeviceToHost, s));
+        AX_OK(kmx_result_view_device(pres.r, &d_phit, nullptr, nullptr));
+        AX_LAUNCH(k_approx_query_cands, grid_for(nqc + 1, kBlock), s, d_phit, nqc, S * E1 - 1, pb.qcand.as<uint64_t>());
+        AX_OK(grow_pinned(h_qcand, (nqc + 1) * 8, who));
+        AX_TRY(hipMemcpyAsync(h_qcand.p, pb.qcand.p, (nqc + 1) * 8, hipMemcpyDeviceToHost, s));
         AX_TRY(hipStreamSynchronize(s));
         const uint64_t* qc = h_qcand.as<uint64_t>();
 
@@ -1281,122 +1379,24 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
             // the longest run of queries whose candidates fit the budget (at least one query)
             uint64_t b = uint64_t(std::upper_bound(qc + a + 1, qc + nqc + 1, qc[a] + budget) - qc) - 1;
             b = std::max(b, a + 1);
-            const uint64_t nqv = (b - a) * S, q0 = a * S;    // the chunk's internal queries [q0, q0 + nqv)
-            const uint64_t np = nqv * E1;
+            const uint64_t nqv = (b - a) * S, q0 = a * S, np = nqv * E1;     // the chunk's internal queries [q0, q0 + nqv), their pieces
             R->n_chunks += 1;
-            st = kmx_search_batch_device(index, d_qr.p, d_poff.as<uint64_t>() + q0 * E1, np, KMX_SEARCH_DEFAULT, s, &pres.r);
-            if (st != KMX_OK) return st;
+            AX_OK(kmx_search_batch_device(index, pb.qr.p, pb.poff.as<uint64_t>() + q0 * E1, np, KMX_SEARCH_DEFAULT, s, &pres.r));
             const uint64_t* phit = nullptr; const uint32_t* ppos = nullptr; const uint8_t* pstat = nullptr;
-            st = kmx_result_view_device(pres.r, &phit, &ppos, &pstat);
-            if (st != KMX_OK) return st;
+            AX_OK(kmx_result_view_device(pres.r, &phit, &ppos, &pstat));
             uint64_t n_cand = 0;
-            st = kmx_result_counts(pres.r, nullptr, &n_cand, nullptr, nullptr, nullptr, nullptr);
-            if (st != KMX_OK) return st;
+            AX_OK(kmx_result_counts(pres.r, nullptr, &n_cand, nullptr, nullptr, nullptr, nullptr));
             R->n_candidates += n_cand;
-            hipLaunchKernelGGL(k_approx_status, dim3(grid_for(nqv, kBlock)), dim3(kBlock), 0, s, pstat, nqv, e, d_qstat.as<uint8_t>() + q0);
-            AX_TRY(hipGetLastError());
-            if (S == 2) {
-                hipLaunchKernelGGL(k_strand_status, dim3(grid_for(b - a, kBlock)), dim3(kBlock), 0, s, d_qstat.as<uint8_t>() + q0, b - a,
-                                   d_pair_stat.as<uint8_t>() + a);
-                AX_TRY(hipGetLastError());
-            }
-            uint64_t n_s = 0;
-            AX_TRY(d_hit_off.ensure((nqv + 1) * 8));
-            if (edit) {
-                if (n_cand) {
-                    EditArgs V{phit, ppos, n_cand, np, d_qoff.as<uint64_t>(), q0, d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>(), text, A.n, e, nullptr, nullptr};
-                    st = edit_chunk(s, V, w, nqv, eb, h_total, d_hit_off, d_opos, d_omm, &n_s);
-                    if (st != KMX_OK) return st;
-                }
-            } else if (n_cand) {
-                const uint64_t nb = (n_cand + kVerifySpan - 1) / kVerifySpan;
-                AX_TRY(d_keep.ensure(n_cand));
-                AX_TRY(d_bcount.ensure(nb * 4 + 16));
-                AX_TRY(d_bsum.ensure(kmx::scan_blocks(nb) * 8 + 16));
-                AX_TRY(d_bscan.ensure((nb + 1) * 8));
-                AX_TRY(d_total.ensure(16));
-                VerifyArgs V{phit, ppos, n_cand, np, d_qoff.as<uint64_t>(), q0, d_qstat.as<uint8_t>(), d_qwords.as<uint64_t>(), text, A.n, w, e,
-                             d_keep.as<uint8_t>(), d_bcount.as<uint32_t>()};
-                hipLaunchKernelGGL(k_approx_verify, dim3(unsigned(nb)), dim3(kBlock), 0, s, V);
-                AX_TRY(hipGetLastError());
-                kmx::launch_scan(s, d_bcount.as<uint32_t>(), nb, d_bsum.as<uint64_t>(), d_bscan.as<uint64_t>(), d_total.as<unsigned long long>());
-                AX_TRY(hipGetLastError());
-                AX_TRY(hipMemcpyAsync(h_total.p, d_total.p, 8, hipMemcpyDeviceToHost, s));
-                AX_TRY(hipStreamSynchronize(s));
-                n_s = h_total.as<uint64_t>()[0];
-                if (n_s) {
-                    AX_TRY(d_spos.ensure(n_s * 4));
-                    AX_TRY(d_spiece.ensure(n_s * 4));
-                    AX_TRY(d_smm.ensure(n_s));
-                    AX_TRY(d_opos.ensure(n_s * 4));
-                    AX_TRY(d_omm.ensure(n_s));
-                    hipLaunchKernelGGL(k_approx_compact, dim3(unsigned(nb)), dim3(kBlock), 0, s, V, d_bscan.as<uint64_t>(), d_spos.as<uint32_t>(),
-                                       d_spiece.as<uint32_t>(), d_smm.as<uint8_t>());
-                    AX_TRY(hipGetLastError());
-                    hipLaunchKernelGGL(k_approx_merge, dim3(grid_for(n_s, kBlock)), dim3(kBlock), 0, s, d_spos.as<uint32_t>(), d_spiece.as<uint32_t>(),
-                                       d_smm.as<uint8_t>(), n_s, e, d_opos.as<uint32_t>(), d_omm.as<uint8_t>());
-                    AX_TRY(hipGetLastError());
-                }
-            }
-            if (n_s && !edit) {                                  // (edit_chunk wrote the chunk's hit_off itself)
-                hipLaunchKernelGGL(k_approx_hit_off, dim3(grid_for(nqv + 1, kBlock)), dim3(kBlock), 0, s, d_spiece.as<uint32_t>(), n_s, nqv, e,
-                                   d_hit_off.as<uint64_t>());
-                AX_TRY(hipGetLastError());
-            } else if (!n_s) {
-                AX_TRY(hipMemsetAsync(d_hit_off.p, 0, (nqv + 1) * 8, s));
-            }
-            // what goes to the host: the chunk's arrays as they are, or (both strands) each pair's two lists merged
-            const void *o_hit_off = d_hit_off.p, *o_pos = d_opos.p, *o_d = d_omm.p, *o_len = eb.olen.p, *o_stat = d_qstat.as<uint8_t>() + a;
-            const void* o_strand = nullptr;
-            if (S == 2) {
-                AX_TRY(d_pub_off.ensure((b - a + 1) * 8));
-                if (n_s) {
-                    AX_TRY(d_mpos.ensure(n_s * 4));
-                    AX_TRY(d_md.ensure(n_s));
-                    AX_TRY(d_mstrand.ensure(n_s));
-                    if (edit) AX_TRY(d_mlen.ensure(n_s * 4));
-                    hipLaunchKernelGGL(k_strand_merge, dim3(grid_for(std::max(n_s, b - a + 1), kBlock)), dim3(kBlock), 0, s, d_hit_off.as<uint64_t>(),
-                                       b - a, n_s, d_opos.as<uint32_t>(), d_omm.as<uint8_t>(), edit ? eb.olen.as<uint32_t>() : (const uint32_t*)nullptr,
-                                       d_mpos.as<uint32_t>(), d_md.as<uint8_t>(), d_mlen.as<uint32_t>(), d_mstrand.as<uint8_t>(),
-                                       d_pub_off.as<uint64_t>());
-                    AX_TRY(hipGetLastError());
-                } else {
-                    AX_TRY(hipMemsetAsync(d_pub_off.p, 0, (b - a + 1) * 8, s));
-                }
-                o_hit_off = d_pub_off.p; o_pos = d_mpos.p; o_d = d_md.p; o_len = d_mlen.p; o_stat = d_pair_stat.as<uint8_t>() + a;
-                o_strand = d_mstrand.p;
-            }
-            const uint64_t q_at = Q0 + a, h_at = R->n_hits;
-            if (rep.on() && n_s) {
-                // the reporting stage: the lists above filtered and compacted, found[] of the chunk's queries to the host
-                ReportArgs P{static_cast<const uint64_t*>(o_hit_off), b - a, n_s, static_cast<const uint32_t*>(o_pos),
-                             static_cast<const uint8_t*>(o_d), static_cast<const uint8_t*>(o_strand), e, rep.loci, rep.best, rep.max_hits};
-                st = report_chunk(s, P, edit ? static_cast<const uint32_t*>(o_len) : nullptr, rb, h_total, &n_s);
-                if (st != KMX_OK) return st;
-                o_hit_off = rb.off.p; o_pos = rb.pos.p; o_d = rb.d.p; o_len = rb.len.p;
-                if (S == 2) o_strand = rb.strand.p;
-                AX_TRY(hipMemcpyAsync(R->found.as<uint64_t>() + q_at, rb.found.p, (b - a) * 8, hipMemcpyDeviceToHost, s));
-            } else if (rep.on()) {
-                std::memset(R->found.as<uint64_t>() + q_at, 0, (b - a) * 8);
-            }
-            // this chunk's part of the result to the host arrays
-            if (!R->positions.grow((h_at + n_s) * 4 + 64) || !R->mismatches.grow(h_at + n_s + 64))
-                return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
-            if (edit && !R->lengths.grow((h_at + n_s) * 4 + 64))
-                return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
-            if (S == 2 && !R->strand.grow(h_at + n_s + 64)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host memory");
-            uint64_t* ho = R->hit_off.as<uint64_t>() + q_at;     // (ho[0], the previous chunk's end, is rewritten with the same value)
-            AX_TRY(hipMemcpyAsync(ho, o_hit_off, (b - a + 1) * 8, hipMemcpyDeviceToHost, s));
-            AX_TRY(hipMemcpyAsync(R->status.as<uint8_t>() + q_at, o_stat, b - a, hipMemcpyDeviceToHost, s));
-            if (n_s) {
-                AX_TRY(hipMemcpyAsync(R->positions.as<uint32_t>() + h_at, o_pos, n_s * 4, hipMemcpyDeviceToHost, s));
-                AX_TRY(hipMemcpyAsync(R->mismatches.as<uint8_t>() + h_at, o_d, n_s, hipMemcpyDeviceToHost, s));
-                if (edit) AX_TRY(hipMemcpyAsync(R->lengths.as<uint32_t>() + h_at, o_len, n_s * 4, hipMemcpyDeviceToHost, s));
-                if (S == 2) AX_TRY(hipMemcpyAsync(R->strand.as<uint8_t>() + h_at, o_strand, n_s, hipMemcpyDeviceToHost, s));
-            }
-            AX_TRY(hipStreamSynchronize(s));
-            for (uint64_t i = 0; i <= b - a; ++i) ho[i] += h_at;
-            R->n_hits += n_s;
+            AX_LAUNCH(k_approx_status, grid_for(nqv, kBlock), s, pstat, nqv, e, pb.qstat.as<uint8_t>() + q0);
+            if (S == 2) AX_LAUNCH(k_strand_status, grid_for(b - a, kBlock), s, pb.qstat.as<uint8_t>() + q0, b - a, pb.pair_stat.as<uint8_t>() + a);
+            // the stages: the internal queries' lists, (both strands) each pair's two merged, (reporting) filtered, then to the host
+            ChunkLists L{nqv, 0, pb.qstat.as<uint8_t>() + q0};
+            const uint64_t* d_qoff = pb.qoff.as<uint64_t>(); const uint8_t* d_qstat = pb.qstat.as<uint8_t>(); const uint64_t* d_qwords = pb.qwords.as<uint64_t>();
+            if (edit) AX_OK(edit_chunk(s, EditArgs{phit, ppos, n_cand, np, d_qoff, q0, d_qstat, d_qwords, text, A.n, e, nullptr, nullptr}, w, eb, h_total, L));
+            else AX_OK(subst_chunk(s, VerifyArgs{phit, ppos, n_cand, np, d_qoff, q0, d_qstat, d_qwords, text, A.n, w, e, nullptr, nullptr}, sb, h_total, L));
+            if (S == 2) AX_OK(strand_merge_chunk(s, pb.pair_stat.as<uint8_t>() + a, mb, L));
+            if (rep.on()) AX_OK(report_chunk(s, rep, e, rb, h_total, R->found.as<uint64_t>() + Q0 + a, L));
+            AX_OK(publish_chunk(s, who, L, Q0 + a, *R));
             a = b;
         }
         Q0 = Q1;

@@ -16,6 +16,7 @@
 #include <string>
 #include <system_error>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "kmx_approx.h"
@@ -42,6 +43,8 @@ kmx_status fail(kmx_status st, const std::string& msg)
         }                                                                                      \
     } while (0)
 
+// the same for a call that reports a kmx_status (and has set the error text itself)
+#define KMX_TRY(expr) do { const kmx_status try_st__ = (expr); if (try_st__ != KMX_OK) return try_st__; } while (0)
 // grow-only device buffer
 struct DevBuf {
     void* p = nullptr;
@@ -226,14 +229,22 @@ struct SearchCtx {
     bool pending = false;
 };
 
-struct kmx_result {
+// What a search counted: its hits, its queries by kind, the mask words its STITCH queries own.
+struct Tallies {
+    uint64_t n_hits = 0, n_exact = 0, n_stitch = 0, n_prefix = 0, n_error = 0, n_none = 0, n_mask_words = 0;
+    void reset() { *this = Tallies{}; }
+    void operator+=(const Tallies& o) { n_hits += o.n_hits; n_exact += o.n_exact; n_stitch += o.n_stitch; n_prefix += o.n_prefix; n_error += o.n_error; n_none += o.n_none; n_mask_words += o.n_mask_words; }
+    void derive_exact(uint64_t nq) { n_exact = nq - n_stitch - n_prefix - n_error - n_none; }   // every query that is none of the others
+};
+constexpr size_t kCtrBytes = KMX_CTR_COUNT * sizeof(unsigned long long);   // one counter block
+
+struct kmx_result : Tallies {
     const kmx_index* index = nullptr;   // the index of the last search; dereferenced only while that search is pending (ctx.pending),
                                         // and kmx_index_free completes pending searches before the index goes away
     int device = 0;
     hipStream_t stream = nullptr;
     uint32_t flags = 0;
-    uint64_t nq = 0, n_hits = 0, n_exact = 0, n_stitch = 0, n_prefix = 0, n_error = 0, n_none = 0;
-    uint64_t n_mask_words = 0;
+    uint64_t nq = 0;
     // device
     DevBuf src, cnt, c0, aux, key, p1, kind, status, stitch_list, prefix_list, short_list, hit_off, bsum, ctr, tile_q, out,
         mask_words, stitch_hits, plen, poff, ptmp, pitems, pbands, pcuts, pbanded, psplits, ptiles, pscnt, pscratch, pmid, in_qranks, in_qoff, win_cnt, win_off;
@@ -282,20 +293,51 @@ struct kmx_result {
     int gather_device = -1;
     hipStream_t gather_stream = nullptr;
 
-    size_t device_bytes() const
+    Tallies& tally() { return *this; }
+    // every device buffer a search or a view allocates (the gather buffers live on another device and are not among them)
+    template <typename R, typename F> static void each_device_buffer(R& r, F&& f)
     {
-        size_t b = 0;
-        for (const DevBuf* d : {&src, &cnt, &c0, &aux, &key, &p1, &kind, &status, &stitch_list, &prefix_list, &short_list, &hit_off, &bsum, &ctr,
-                                &tile_q, &out, &mask_words, &stitch_hits, &plen, &poff, &ptmp, &pitems, &pbands, &pcuts, &pbanded, &psplits, &ptiles, &pscnt, &pscratch, &pmid, &in_qranks, &in_qoff, &small_xchg, &win_cnt, &win_off})
-            b += d->cap;
-        return b;
+        for (auto* b : {&r.src, &r.cnt, &r.c0, &r.aux, &r.key, &r.p1, &r.kind, &r.status, &r.stitch_list, &r.prefix_list, &r.short_list, &r.hit_off, &r.bsum,
+                        &r.ctr, &r.tile_q, &r.out, &r.mask_words, &r.stitch_hits, &r.plen, &r.poff, &r.ptmp, &r.pitems, &r.pbands, &r.pcuts, &r.pbanded, &r.psplits,
+                        &r.ptiles, &r.pscnt, &r.pscratch, &r.pmid, &r.in_qranks, &r.in_qoff, &r.small_xchg, &r.win_cnt, &r.win_off})
+            f(*b);
+    }
+    size_t device_bytes() const { size_t b = 0; each_device_buffer(*this, [&](const DevBuf& d) { b += d.cap; }); return b; }
+    kmx::QueryDesc query_desc() const
+    {
+        return kmx::QueryDesc{src.as<uint64_t>(), cnt.as<uint32_t>(), c0.as<uint32_t>(), aux.as<uint64_t>(), key.as<uint64_t>(), p1.as<uint64_t>(),
+                              kind.as<uint8_t>(), status.as<uint8_t>(), stitch_list.as<uint32_t>(), prefix_list.as<uint32_t>(), short_list.as<uint32_t>(), nullptr};
+    }
+    // two counter blocks per handle, used in turn (ctr_phase): the scan of a batch zeroes the block of the next one
+    unsigned long long* ctr_block(uint32_t phase) const { return ctr.as<unsigned long long>() + phase * KMX_CTR_COUNT; }
+    hipError_t ensure_h_ctr() { return h_ctr ? hipSuccess : hipHostMalloc(reinterpret_cast<void**>(&h_ctr), kCtrBytes, hipHostMallocDefault); }
+    // the host views / mask views are the result's own buffers; size_*: sized for nq queries, pos_bytes of positions / n_mask_words words first
+    void view_own() { v_hit_off = h_hit_off.as<uint64_t>(); v_positions = h_positions.as<uint32_t>(); v_status = h_status.as<uint8_t>(); v_kinds = h_kinds.as<uint8_t>(); }
+    void mask_view_own() { m_base = h_mask_base.as<uint64_t>(); m_words = h_mask_words.as<uint64_t>(); m_ccnt = h_cand_count.as<uint32_t>(); m_csrc = h_cand_src.as<uint64_t>(); }
+    bool size_views(uint64_t pos_bytes)
+    {
+        const uint64_t nq1 = std::max<uint64_t>(nq, 1);
+        const bool ok = h_hit_off.ensure((nq + 1) * 8) && h_status.ensure(nq1) && h_kinds.ensure(nq1) && h_positions.ensure(std::max<uint64_t>(pos_bytes, 4));
+        if (ok) view_own();
+        return ok;
+    }
+    bool size_mask_buffers()
+    {
+        const uint64_t nq1 = std::max<uint64_t>(nq, 1);
+        return h_mask_base.ensure(nq1 * 8) && h_cand_count.ensure(nq1 * 4) && h_cand_src.ensure(nq1 * 8) &&
+               h_mask_words.ensure(std::max<uint64_t>(n_mask_words, 1) * 8);
     }
 
+    void release_gather()                   // (leaves gather_device current)
+    {
+        (void)hipSetDevice(gather_device);
+        g_hit_off.release(); g_out.release(); g_status.release();
+        if (gather_stream) (void)hipStreamDestroy(gather_stream);
+        gather_stream = nullptr;
+    }
     void release()
     {
-        for (DevBuf* b : {&src, &cnt, &c0, &aux, &key, &p1, &kind, &status, &stitch_list, &prefix_list, &short_list, &hit_off, &bsum, &ctr,
-                          &tile_q, &out, &mask_words, &stitch_hits, &plen, &poff, &ptmp, &pitems, &pbands, &pcuts, &pbanded, &psplits, &ptiles, &pscnt, &pscratch, &pmid, &in_qranks, &in_qoff, &small_xchg, &win_cnt, &win_off})
-            b->release();
+        each_device_buffer(*this, [](DevBuf& b) { b.release(); });
         for (HostBuf* b : {&h_hit_off, &h_positions, &h_status, &h_kinds, &h_mask_base, &h_mask_words, &h_cand_count, &h_cand_src, &h_small, &mailbox, &small_in, &h_win_off})
             b->release();
         if (h_ctr) (void)hipHostFree(h_ctr);
@@ -307,10 +349,7 @@ struct kmx_result {
         if (gather_device >= 0) {
             int cur = 0;
             const bool have = hipGetDevice(&cur) == hipSuccess;
-            (void)hipSetDevice(gather_device);
-            g_hit_off.release(); g_out.release(); g_status.release();
-            if (gather_stream) (void)hipStreamDestroy(gather_stream);
-            gather_stream = nullptr;
+            release_gather();
             gather_device = -1;
             if (have) (void)hipSetDevice(cur);
         }
@@ -318,6 +357,14 @@ struct kmx_result {
 };
 
 namespace {
+
+// results parked in the pool hold device memory: give it back
+void release_idle(ResultPool& pool)
+{
+    std::vector<kmx_result*> idle;
+    { std::lock_guard<std::mutex> lock(pool.mu); idle.swap(pool.idle); }
+    for (kmx_result* r : idle) { r->release(); delete r; }
+}
 
 kmx_result* take_result(kmx_index* ix)
 {
@@ -794,12 +841,7 @@ static kmx_status add_prefix_levels_impl(kmx_index* ix, const kmx_options& o)
             if (he != hipSuccess) return fail(KMX_ERR_HIP, std::string("prefix level header: ") + hipGetErrorString(he));
         }
     }
-    // the results the level searches parked in the pool hold device memory of the size of the index: give it back
-    {
-        std::vector<kmx_result*> idle;
-        { std::lock_guard<std::mutex> lock(ix->pool->mu); idle.swap(ix->pool->idle); }
-        for (kmx_result* r : idle) { r->release(); delete r; }
-    }
+    release_idle(*ix->pool);   // the results the level searches parked there hold device memory of the size of the index
     return KMX_OK;
 }
 
@@ -1172,8 +1214,6 @@ kmx_status kmx_index_build(const uint8_t* ranks, uint64_t n, uint32_t sigma, con
     return st;
 }
 
-static kmx_status search_finish(kmx_result* r);
-
 void kmx_index_free(kmx_index* ix)
 {
     if (!ix) return;
@@ -1395,7 +1435,7 @@ kmx_status kmx_result_paths(const kmx_result* r, kmx_result_path_info* out)
 {
     if (!r || !out || out->struct_size < sizeof(uint32_t)) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_paths: NULL argument or no struct_size");
     if (!r->parts.empty()) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_paths: a result of several parts has no single search to report");
-    if (r->ctx.pending) { kmx_status fs = search_finish(const_cast<kmx_result*>(r)); if (fs != KMX_OK) return fs; }
+    KMX_TRY(search_finish(const_cast<kmx_result*>(r)));
     kmx_result_path_info v{};
     v.small = r->path.small; v.lookup_items = r->path.items; v.lookup_pairs = r->path.pairs; v.deferred_long = r->path.defer_long;
     v.tile_q_source = r->path.tile_q_source; v.spec_fill = r->path.spec_fill; v.spec_ok = r->path.spec_ok;
@@ -1482,9 +1522,22 @@ static kmx_status search_device_begin(const kmx_index* cix, const void* d_first,
     if (r && r->device != ix->device && r->device_bytes())      // (whatever its last batch was: an empty one still owns buffers there)
         return fail(KMX_ERR_INVALID_ARGUMENT, f + "the result handle holds buffers on another device");
     if (!r) { r = take_result(ix); *inout = r; }
-    else if (r->ctx.pending) { kmx_status fs = search_finish(r); if (fs != KMX_OK) return fs; }   // its buffers are about to be reused
+    else KMX_TRY(search_finish(r));                             // its buffers are about to be reused
     *ix_out = ix;
     return KMX_OK;
+}
+
+// The scan of the hit counts into hit_off; it also records the first query of every output tile (k_partition's job) when the tile
+// table kept from an earlier batch is large enough — the steady state.  Returns whether it published the counters (pub).
+static bool scan_hits(kmx_index* ix, kmx_result* r, hipStream_t s, uint64_t tile, uint64_t tile_cap, int items, const kmx::CounterPub& pub)
+{
+    bool published = false;
+    timed(ix, K_SCAN, s, [&] {
+        published = kmx::launch_scan_tiles(s, r->cnt.as<uint32_t>(), r->nq, r->bsum.as<uint64_t>(), r->hit_off.as<uint64_t>(),
+                                           r->ctr_block(r->ctr_phase) + KMX_CTR_TOTAL_HITS, tile, tile_cap >= 2 ? tile_cap - 1 : 0,
+                                           tile_cap >= 2 ? r->tile_q.as<uint32_t>() : nullptr, items, pub);
+    });
+    return published;
 }
 
 // First half of a device-form search of nq queries into r, on stream s: buffers, counter blocks, the LOOKUP STEP, the scan, the
@@ -1497,71 +1550,51 @@ using LookupStep = std::function<int(const kmx::QueryDesc&, unsigned long long*,
 static kmx_status search_device_run(kmx_index* ix, kmx_result* r, const uint8_t* qr, const uint64_t* qo, uint64_t nq, uint32_t flags, hipStream_t s,
                                     const LookupStep& lookup)
 {
-    r->index = ix;
-    r->device = ix->device;
-    r->stream = s;
+    r->index = ix; r->device = ix->device; r->stream = s;
     (void)hipGetLastError();   // do not inherit a stale error from an earlier, unrelated call
     r->flags = flags;
     r->nq = nq;
-    r->n_hits = r->n_exact = r->n_stitch = r->n_prefix = r->n_error = r->n_none = r->n_mask_words = 0;
+    r->tally().reset();
     r->host_valid = r->host_masks_valid = false;
     r->small_valid = false;
     r->path = kmx_result::PathRec{};
     r->quiesced = false;
-    if (!r->h_ctr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->h_ctr), KMX_CTR_COUNT * sizeof(unsigned long long), hipHostMallocDefault));
+    HIP_TRY(r->ensure_h_ctr());
     HIP_TRY(r->hit_off.ensure((nq + 1) * 8));
     if (nq == 0) {
         HIP_TRY(hipMemsetAsync(r->hit_off.p, 0, 8, s));
         return KMX_OK;
     }
-    HIP_TRY(r->src.ensure(nq * 8));
-    HIP_TRY(r->cnt.ensure(nq * 4));
-    HIP_TRY(r->c0.ensure(nq * 4));
-    HIP_TRY(r->aux.ensure(nq * 8));
-    HIP_TRY(r->key.ensure(nq * 8));
-    HIP_TRY(r->p1.ensure(nq * 8));
-    HIP_TRY(r->kind.ensure(nq));
-    HIP_TRY(r->status.ensure(nq));
-    HIP_TRY(r->stitch_list.ensure(nq * 4));
-    HIP_TRY(r->prefix_list.ensure(nq * 4));
-    HIP_TRY(r->short_list.ensure(nq * 4));
+    const std::pair<DevBuf*, size_t> per_query[] = {{&r->src, 8}, {&r->cnt, 4}, {&r->c0, 4}, {&r->aux, 8}, {&r->key, 8}, {&r->p1, 8}, {&r->kind, 1},
+                                                    {&r->status, 1}, {&r->stitch_list, 4}, {&r->prefix_list, 4}, {&r->short_list, 4}};
+    for (const auto& b : per_query) HIP_TRY(b.first->ensure(nq * b.second));
     HIP_TRY(r->bsum.ensure(std::max(kmx::scan_blocks(nq), kmx::lookup_blocks(nq, 4)) * 8));
-    if (r->ctr.cap < 2 * KMX_CTR_COUNT * sizeof(unsigned long long)) {
-        // two counter blocks per handle, used in turn: the scan of a batch zeroes the block of the next one
-        HIP_TRY(r->ctr.ensure(2 * KMX_CTR_COUNT * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(r->ctr.p, 0, 2 * KMX_CTR_COUNT * sizeof(unsigned long long), s));
+    if (r->ctr.cap < 2 * kCtrBytes) {
+        HIP_TRY(r->ctr.ensure(2 * kCtrBytes));
+        HIP_TRY(hipMemsetAsync(r->ctr.p, 0, 2 * kCtrBytes, s));
         r->ctr_phase = 0;
         r->ctr_clean = true;
     }
-    kmx::QueryDesc d{r->src.as<uint64_t>(), r->cnt.as<uint32_t>(), r->c0.as<uint32_t>(), r->aux.as<uint64_t>(),
-                     r->key.as<uint64_t>(), r->p1.as<uint64_t>(), r->kind.as<uint8_t>(), r->status.as<uint8_t>(),
-                     r->stitch_list.as<uint32_t>(), r->prefix_list.as<uint32_t>(), r->short_list.as<uint32_t>(), nullptr};
+    const kmx::QueryDesc d = r->query_desc();
     // this batch's counter block, and the one of the next batch on this handle
     if (!r->ctr_clean) {                                        // (after a batch whose scan did not reset it: the stream does)
-        HIP_TRY(hipMemsetAsync(r->ctr.p, 0, 2 * KMX_CTR_COUNT * sizeof(unsigned long long), s));
+        HIP_TRY(hipMemsetAsync(r->ctr.p, 0, 2 * kCtrBytes, s));
         r->ctr_clean = true;
     }
     r->ctr_phase ^= 1u;
-    auto* ctr = r->ctr.as<unsigned long long>() + r->ctr_phase * KMX_CTR_COUNT;
-    auto* ctr_next = r->ctr.as<unsigned long long>() + (r->ctr_phase ^ 1u) * KMX_CTR_COUNT;
+    auto* ctr = r->ctr_block(r->ctr_phase);
+    auto* ctr_next = r->ctr_block(r->ctr_phase ^ 1u);
     const KmxIndexDev* dix = header_for(ix, flags);
 
     const int items = lookup(d, ctr, dix);
     // speculative scan: already final when the batch holds no STITCH query
-    // The downsweep also records the first query of every output tile (k_partition's job) when the
-    // tile table kept from an earlier batch is large enough — the steady state.
     const kmx::FillVariant fv = kmx::effective_fill_variant(ix->fill_variant, ix->rec32);
     const uint64_t tile = kmx::fill_tile(fv);
     const uint64_t tile_cap = r->tile_q.cap / 4;            // entries available while the scan runs
     // the block sums k_lookup left in bsum are the first level of this scan
     // (steady state: the scan's last block also hands the counters to the host and zeroes the next batch's block — no
     //  memset and no copy operation on the stream)
-    bool published = false;
-    timed(ix, K_SCAN, s, [&] {
-        published = kmx::launch_scan_tiles(s, d.cnt, nq, r->bsum.as<uint64_t>(), r->hit_off.as<uint64_t>(), ctr + KMX_CTR_TOTAL_HITS, tile,
-                                           tile_cap >= 2 ? tile_cap - 1 : 0, tile_cap >= 2 ? r->tile_q.as<uint32_t>() : nullptr, items,
-                                           kmx::CounterPub{ctr, ctr_next, r->h_ctr});
-    });
+    const bool published = scan_hits(ix, r, s, tile, tile_cap, items, kmx::CounterPub{ctr, ctr_next, r->h_ctr});
     r->ctr_clean = published;
     // Steady state (tile table and output buffer kept from an earlier batch): k_fill goes out right behind the
     // scan, before the host knows the hit total — it reads the total from device memory and its grid is sized
@@ -1576,7 +1609,7 @@ static kmx_status search_device_run(kmx_index* ix, kmx_result* r, const uint8_t*
                              ctr + KMX_CTR_TOTAL_HITS, spec_tiles, d, r->out.as<uint32_t>());
         });
     r->path.spec_fill = spec_fill;
-    if (!published) HIP_TRY(hipMemcpyAsync(r->h_ctr, ctr, KMX_CTR_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (!published) HIP_TRY(hipMemcpyAsync(r->h_ctr, ctr, kCtrBytes, hipMemcpyDeviceToHost, s));
     // everything after the read-back lives in search_finish: right away, or (KMX_SEARCH_ASYNC) when the result is next touched
     r->ctx = SearchCtx{ix, qr, qo, s, tile_cap, spec_tiles, spec_fill, true};
     if (flags & KMX_SEARCH_ASYNC) {
@@ -1597,8 +1630,7 @@ kmx_status kmx_search_batch_device(const kmx_index* cix, const void* d_qranks, c
     if (nq && (!d_qranks || !d_qoff)) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: NULL query buffers");
     if (nq >= 0xFFFFFFFFull) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: at most 2^32-2 queries per batch");
     kmx_index* ix = nullptr;
-    const kmx_status bs = search_device_begin(cix, d_qranks, nq != 0, inout, "kmx_search_batch_device", "d_qranks", &ix);
-    if (bs != KMX_OK) return bs;
+    KMX_TRY(search_device_begin(cix, d_qranks, nq != 0, inout, "kmx_search_batch_device", "d_qranks", &ix));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint8_t* qr = static_cast<const uint8_t*>(d_qranks);
     const uint64_t* qo = static_cast<const uint64_t*>(d_qoff);
@@ -1648,8 +1680,7 @@ static kmx_status windows_device(const kmx_index* cix, const void* d_ranks, cons
                                  hipStream_t s, kmx_result** inout, const uint64_t* known_nq, const char* fn)
 {
     kmx_index* ix = nullptr;
-    const kmx_status bs = search_device_begin(cix, d_ranks ? d_ranks : d_roff, nr != 0, inout, fn, "d_ranks", &ix);
-    if (bs != KMX_OK) return bs;
+    KMX_TRY(search_device_begin(cix, d_ranks ? d_ranks : d_roff, nr != 0, inout, fn, "d_ranks", &ix));
     kmx_result* r = *inout;
     const uint8_t* rk = static_cast<const uint8_t*>(d_ranks);
     const uint64_t* ro = static_cast<const uint64_t*>(d_roff);
@@ -1664,7 +1695,7 @@ static kmx_status windows_device(const kmx_index* cix, const void* d_ranks, cons
     } else {
         HIP_TRY(r->win_cnt.ensure(nr * 4));
         HIP_TRY(r->bsum.ensure(kmx::scan_blocks(nr) * 8));
-        if (!r->h_ctr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->h_ctr), KMX_CTR_COUNT * sizeof(unsigned long long), hipHostMallocDefault));
+        HIP_TRY(r->ensure_h_ctr());
         // windows per read and their exclusive scan: win_off[nr] is the number of queries of this search
         timed(ix, K_SCAN, s, [&] {
             kmx::launch_window_counts(s, ro, nr, o->w, o->stride, r->win_cnt.as<uint32_t>());
@@ -1697,18 +1728,46 @@ kmx_status kmx_search_windows_device(const kmx_index* cix, const void* d_ranks, 
                                      void* stream, kmx_result** inout)
 {
     uint32_t elem = 0;
-    const kmx_status cs = windows_check("kmx_search_windows_device", cix, o, inout, &elem);
-    if (cs != KMX_OK) return cs;
+    KMX_TRY(windows_check("kmx_search_windows_device", cix, o, inout, &elem));
     if (nr && !d_roff) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows_device: NULL read offsets");
     return windows_device(cix, d_ranks, d_roff, nr, o, elem, static_cast<hipStream_t>(stream), inout, nullptr, "kmx_search_windows_device");
+}
+
+// Both host forms: the caller's handle (or one from the pool), its pending search completed, with its own stream.  `fn`: the entry
+// point that refuses a handle with buffers on another device here (nullptr: kmx_search_batch, where the device form behind does).
+static kmx_status host_handle(kmx_index* ix, kmx_result** inout, const char* fn)
+{
+    HIP_TRY(hipSetDevice(ix->device));
+    kmx_result* r = *inout ? *inout : take_result(ix);
+    *inout = r;
+    KMX_TRY(search_finish(r));
+    if (fn && r->device != ix->device && r->device_bytes())
+        return fail(KMX_ERR_INVALID_ARGUMENT, std::string(fn) + ": the result handle holds buffers on another device");
+    if (fn) r->device = ix->device;
+    if (!r->own_stream) HIP_TRY(hipStreamCreateWithFlags(&r->own_stream, hipStreamNonBlocking));
+    return KMX_OK;
+}
+
+// room for n queries (or reads) of n_letters letters; upload_queries also sends them up on the handle's own stream, as they are
+static kmx_status query_room(kmx_result* r, uint64_t n_letters, uint64_t n)
+{
+    HIP_TRY(r->in_qranks.ensure(std::max<uint64_t>(n_letters, 1) + 16));
+    HIP_TRY(r->in_qoff.ensure((n + 1) * 8));
+    return KMX_OK;
+}
+static kmx_status upload_queries(kmx_result* r, const uint8_t* letters, uint64_t n_letters, const uint64_t* offsets, uint64_t n)
+{
+    KMX_TRY(query_room(r, n_letters, n));
+    if (n_letters) HIP_TRY(hipMemcpyAsync(r->in_qranks.p, letters, n_letters, hipMemcpyHostToDevice, r->own_stream));
+    if (n) HIP_TRY(hipMemcpyAsync(r->in_qoff.p, offsets, (n + 1) * 8, hipMemcpyHostToDevice, r->own_stream));
+    return KMX_OK;
 }
 
 kmx_status kmx_search_windows(const kmx_index* cix, const uint8_t* ranks, const uint64_t* roff, uint64_t nr, const kmx_window_options* o,
                               kmx_result** out)
 {
     uint32_t elem = 0;
-    const kmx_status cs = windows_check("kmx_search_windows", cix, o, out, &elem);
-    if (cs != KMX_OK) return cs;
+    KMX_TRY(windows_check("kmx_search_windows", cix, o, out, &elem));
     if (nr && !roff) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: NULL read offsets");
     if (nr && roff[0] != 0) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: roff[0] must be 0");
     uint64_t nq = 0;
@@ -1723,23 +1782,12 @@ kmx_status kmx_search_windows(const kmx_index* cix, const uint8_t* ranks, const 
     if (n_letters && !ranks) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: NULL read letters");
     kmx_index* ix = const_cast<kmx_index*>(cix);                // (several replicas: the first one)
     if (*out && !(*out)->parts.empty()) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: the result handle belongs to a search of several parts");
-    const kmx_status ds = check_device();
-    if (ds != KMX_OK) return ds;
-    HIP_TRY(hipSetDevice(ix->device));
-    kmx_result* r = *out ? *out : take_result(ix);
-    *out = r;
-    if (r->ctx.pending) { kmx_status fs = search_finish(r); if (fs != KMX_OK) return fs; }
-    if (r->device != ix->device && r->device_bytes())
-        return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_windows: the result handle holds buffers on another device");
-    r->device = ix->device;
-    if (!r->own_stream) HIP_TRY(hipStreamCreateWithFlags(&r->own_stream, hipStreamNonBlocking));
+    KMX_TRY(check_device());
+    KMX_TRY(host_handle(ix, out, "kmx_search_windows"));
+    kmx_result* r = *out;
     // the reads and their offsets go up once, as they are: no window is written out on either side
-    HIP_TRY(r->in_qranks.ensure(std::max<uint64_t>(n_letters, 1) + 16));
-    HIP_TRY(r->in_qoff.ensure((nr + 1) * 8));
-    if (n_letters) HIP_TRY(hipMemcpyAsync(r->in_qranks.p, ranks, n_letters, hipMemcpyHostToDevice, r->own_stream));
-    if (nr) HIP_TRY(hipMemcpyAsync(r->in_qoff.p, roff, (nr + 1) * 8, hipMemcpyHostToDevice, r->own_stream));
-    const kmx_status st = windows_device(ix, r->in_qranks.p, r->in_qoff.p, nr, o, elem, r->own_stream, out, &nq, "kmx_search_windows");
-    if (st != KMX_OK) return st;
+    KMX_TRY(upload_queries(r, ranks, n_letters, roff, nr));
+    KMX_TRY(windows_device(ix, r->in_qranks.p, r->in_qoff.p, nr, o, elem, r->own_stream, out, &nq, "kmx_search_windows"));
     HIP_TRY(hipStreamSynchronize(r->own_stream));
     r->quiesced = true;
     if (!r->h_win_off.ensure((nr + 1) * 8)) return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_search_windows: host allocation failed");
@@ -1753,7 +1801,7 @@ kmx_status kmx_search_windows(const kmx_index* cix, const uint8_t* ranks, const 
 kmx_status kmx_result_window_offsets(kmx_result* r, const uint64_t** win_off, const uint64_t** d_win_off, uint64_t* nr)
 {
     if (!r) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_window_offsets: result is NULL");
-    if (r->ctx.pending) { kmx_status fs = search_finish(r); if (fs != KMX_OK) return fs; }
+    KMX_TRY(search_finish(r));
     if (!r->windows || !r->parts.empty())
         return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_window_offsets: the result is not one of kmx_search_windows / kmx_search_windows_device");
     if (win_off) {
@@ -1771,169 +1819,174 @@ kmx_status kmx_result_window_offsets(kmx_result* r, const uint64_t** win_off, co
     return KMX_OK;
 }
 
-// Second half of a search: waits for the counters of the first half, then validates / fills / sorts whatever the
-// speculative steady-state path has not already done.  A no-op when nothing is pending.
-static kmx_status search_finish(kmx_result* r)
-{
-    if (!r->ctx.pending) return KMX_OK;
-    r->ctx.pending = false;
-    kmx_index* ix = r->ctx.ix;
-    if (r->flags & KMX_SEARCH_ASYNC) {
-        std::lock_guard<std::mutex> lock(ix->pool->mu);
-        auto& pend = ix->pool->pending;
-        pend.erase(std::remove(pend.begin(), pend.end(), r), pend.end());
-    }
-    const uint8_t* qr = r->ctx.qr;
-    const uint64_t* qo = r->ctx.qo;
-    hipStream_t s = r->ctx.s;
-    const uint64_t nq = r->nq, tile_cap = r->ctx.tile_cap, spec_tiles = r->ctx.spec_tiles;
-    const uint32_t flags = r->flags;
-    const bool spec_fill = r->ctx.spec_fill;
-    HIP_TRY(hipSetDevice(r->device));
-    if (r->done && (flags & KMX_SEARCH_ASYNC)) HIP_TRY(hipEventSynchronize(r->done));
-    else HIP_TRY(hipStreamSynchronize(s));
-    kmx::QueryDesc d{r->src.as<uint64_t>(), r->cnt.as<uint32_t>(), r->c0.as<uint32_t>(), r->aux.as<uint64_t>(),
-                     r->key.as<uint64_t>(), r->p1.as<uint64_t>(), r->kind.as<uint8_t>(), r->status.as<uint8_t>(),
-                     r->stitch_list.as<uint32_t>(), r->prefix_list.as<uint32_t>(), r->short_list.as<uint32_t>(), nullptr};
-    auto* ctr = r->ctr.as<unsigned long long>() + r->ctr_phase * KMX_CTR_COUNT;     // the counter block this search counts into
-    const KmxIndexDev* dix = header_for(ix, flags);
-    const kmx::FillVariant fv = kmx::effective_fill_variant(ix->fill_variant, ix->rec32);
-    const uint64_t tile = kmx::fill_tile(fv);
-    auto scan_hits = [&] {                                     // (k_validate changed the counts: a full scan)
-        timed(ix, K_SCAN, s, [&] {
-            kmx::launch_scan_tiles(s, d.cnt, nq, r->bsum.as<uint64_t>(), r->hit_off.as<uint64_t>(), ctr + KMX_CTR_TOTAL_HITS, tile,
-                                   tile_cap >= 2 ? tile_cap - 1 : 0, tile_cap >= 2 ? r->tile_q.as<uint32_t>() : nullptr, 0);
-        });
-    };
-    const uint64_t n_stitch_groups = r->h_ctr[KMX_CTR_STITCH], n_stitch_tiny = r->h_ctr[KMX_CTR_STITCH_TINY];   // front / back of stitch_list
-    const uint64_t n_stitch_short = r->h_ctr[KMX_CTR_STITCH_SHORT];                                     // short_list
-    const uint64_t n_stitch_pending = n_stitch_groups + n_stitch_tiny + n_stitch_short;                 // still to be validated
-    r->n_stitch = n_stitch_pending + r->h_ctr[KMX_CTR_STITCH_RESOLVED];                                  // (k_lookup resolved the others itself)
-    r->last_had_stitch = n_stitch_pending != 0;
-    r->last_had_long = r->h_ctr[KMX_CTR_LONG] != 0;
-    r->last_had_pairs = r->n_stitch != 0;                        // (resolved ones included: they are what the pairs variant of k_lookup is for)
-    const uint64_t n_prefix_small = r->h_ctr[KMX_CTR_PREFIX], n_prefix_big = r->h_ctr[KMX_CTR_PREFIX_BIG];
-    r->n_prefix = n_prefix_small + n_prefix_big + r->h_ctr[KMX_CTR_PREFIX_PLAIN];
-    r->n_error = r->h_ctr[KMX_CTR_ERROR];
-    r->n_none = r->h_ctr[KMX_CTR_NONE];
-    r->n_mask_words = r->h_ctr[KMX_CTR_MASK_WORDS];
-    r->n_exact = nq - r->n_stitch - r->n_prefix - r->n_error - r->n_none;
-    const uint64_t prefix_elems = r->h_ctr[KMX_CTR_PREFIX_ELEMS];
-    const uint64_t max_runs = r->h_ctr[KMX_CTR_MAX_RUNS];
-    {   // kmx_result_paths: the PREFIX slices by merger, as the dispatcher (k_lookup) counted them
-        const uint64_t n_merge = r->h_ctr[KMX_CTR_PREFIX_MERGE], n_mid = r->h_ctr[KMX_CTR_PREFIX_MID];
-        r->path.p_plain = uint32_t(r->h_ctr[KMX_CTR_PREFIX_PLAIN]);
-        r->path.p_merge = uint32_t(n_merge);
-        r->path.p_small = uint32_t(n_prefix_small - std::min(n_prefix_small, n_merge));
-        r->path.p_mid = uint32_t(n_mid);
-        r->path.p_long = uint32_t(n_prefix_big - std::min(n_prefix_big, n_mid));
-        r->path.p_chunks = uint32_t(prefix_elems ? max_runs : 0);
-        r->path.p_elems = prefix_elems;
-    }
+// ---- search_finish.  The counter block of a batch, decoded once (read_counts).  STITCH queries still to be validated: groups from
+// the front of stitch_list, tiny ones from its back, short ones in short_list.  PREFIX queries: small from the front of prefix_list
+// (merge: k_prefix_merge_small's class), big from its back (mid: the 256-thread shape of k_prefix_sort_block).
+struct BatchCounts {
+    uint64_t stitch_groups, stitch_tiny, stitch_short, stitch_pending, stitch_more;   // more: survivors need their further parts checked
+    uint64_t prefix_small, prefix_big, prefix_merge, prefix_mid, prefix_plain;
+    uint64_t prefix_elems, max_runs;     // positions / most runs of the slices beyond one chunk
+    uint64_t total_hits, mask_words;     // (total_hits: final once validate_stitch has run)
+};
 
-    if (n_stitch_pending) {
-        HIP_TRY(r->mask_words.ensure(r->n_mask_words * 8));
+// the result leaves the pool's pending list; the counters of the first half arrive
+static kmx_status wait_counters(kmx_result* r)
+{
+    if (r->flags & KMX_SEARCH_ASYNC) {
+        ResultPool& pool = *r->ctx.ix->pool;
+        std::lock_guard<std::mutex> lock(pool.mu);
+        pool.pending.erase(std::remove(pool.pending.begin(), pool.pending.end(), r), pool.pending.end());
+    }
+    HIP_TRY(hipSetDevice(r->device));
+    if (r->done && (r->flags & KMX_SEARCH_ASYNC)) HIP_TRY(hipEventSynchronize(r->done));
+    else HIP_TRY(hipStreamSynchronize(r->ctx.s));
+    return KMX_OK;
+}
+
+// h_ctr into BatchCounts, the tallies (but the hits: validation may change them), the last_had_* hints and the path.p_* records
+static BatchCounts read_counts(kmx_result* r)
+{
+    const unsigned long long* h = r->h_ctr;
+    BatchCounts c{};
+    c.stitch_groups = h[KMX_CTR_STITCH]; c.stitch_tiny = h[KMX_CTR_STITCH_TINY]; c.stitch_short = h[KMX_CTR_STITCH_SHORT];
+    c.stitch_pending = c.stitch_groups + c.stitch_tiny + c.stitch_short; c.stitch_more = h[KMX_CTR_STITCH_MORE];
+    c.prefix_small = h[KMX_CTR_PREFIX]; c.prefix_big = h[KMX_CTR_PREFIX_BIG]; c.prefix_merge = h[KMX_CTR_PREFIX_MERGE];
+    c.prefix_mid = h[KMX_CTR_PREFIX_MID]; c.prefix_plain = h[KMX_CTR_PREFIX_PLAIN]; c.prefix_elems = h[KMX_CTR_PREFIX_ELEMS]; c.max_runs = h[KMX_CTR_MAX_RUNS];
+    c.total_hits = h[KMX_CTR_TOTAL_HITS]; c.mask_words = h[KMX_CTR_MASK_WORDS];
+    r->n_stitch = c.stitch_pending + h[KMX_CTR_STITCH_RESOLVED];   // (k_lookup resolved the others itself)
+    r->n_prefix = c.prefix_small + c.prefix_big + c.prefix_plain;
+    r->n_error = h[KMX_CTR_ERROR]; r->n_none = h[KMX_CTR_NONE]; r->n_mask_words = c.mask_words;
+    r->derive_exact(r->nq);
+    r->last_had_stitch = c.stitch_pending != 0;
+    r->last_had_long = h[KMX_CTR_LONG] != 0;
+    r->last_had_pairs = r->n_stitch != 0;                        // (resolved ones included: they are what the pairs variant of k_lookup is for)
+    r->path.p_plain = uint32_t(c.prefix_plain); r->path.p_merge = uint32_t(c.prefix_merge); r->path.p_mid = uint32_t(c.prefix_mid);
+    r->path.p_small = uint32_t(c.prefix_small - std::min(c.prefix_small, c.prefix_merge));
+    r->path.p_long = uint32_t(c.prefix_big - std::min(c.prefix_big, c.prefix_mid));
+    r->path.p_chunks = uint32_t(c.prefix_elems ? c.max_runs : 0); r->path.p_elems = c.prefix_elems;
+    return c;
+}
+
+// What prefix_big allocates and launches for, from the counts and the KMX_NO_BANDS / KMX_NO_SPLIT knobs alone.
+struct PrefixBigSizes {
+    bool large, split_ok, bands_possible;
+    uint64_t n_long, max_tiles, cap_items, cap_bands, cap_cuts;
+    kmx::PrefixSplitRoom room;   // capacities only
+};
+static PrefixBigSizes prefix_big_sizes(const BatchCounts& c)
+{
+    static const bool no_bands = getenv("KMX_NO_BANDS") != nullptr;                 // (experiments: everything as chunks)
+    static const bool no_split = getenv("KMX_NO_SPLIT") != nullptr || no_bands;     // (... no slice spread by value)
+    PrefixBigSizes z{};
+    const uint64_t np = c.prefix_big, elems = c.prefix_elems;
+    // slices beyond the block kernel's capacity are rows of sorted chunks behind it, merged pairwise in global memory:
+    // their tiles are counted first (the chunks of a slice with an odd number of passes start in the scratch buffer)
+    z.large = c.max_runs > 1 && elems > 0;
+    z.max_tiles = z.large ? elems / kmx::prefix_merge_tile() + np : 0;
+    // the slices beyond the 256-thread shape: cut into bands where that works (k_prefix_bands: cut tables + one record per band), the
+    // others as chunks (k_prefix_items: one record per chunk — one per slice + one per full chunk at most)
+    z.n_long = np > c.prefix_mid ? np - c.prefix_mid : 0;
+    // room for the slices spread by value (k_prefix_split_*): only slices beyond one chunk go there, prefix_elems holds their positions
+    z.split_ok = z.large && !no_split;
+    const uint64_t n_large_max = elems / KMX_PSORT_BLOCK_CAP + 1;
+    if (z.split_ok) {
+        z.room.cap_splits = n_large_max; z.room.cap_tiles = elems / kmx::prefix_split_tile() + n_large_max;
+        z.room.cap_counters = 3 * (elems / kmx::prefix_split_target() + n_large_max); z.room.cap_scratch = elems + 4 * n_large_max;
+    }
+    z.cap_items = z.n_long ? z.n_long + elems / KMX_PSORT_BLOCK_CAP + (z.split_ok ? elems / kmx::prefix_split_target() + n_large_max : 0) : 0;
+    // (bands are for slices beyond prefix_band_min() positions — one chunk in the build as it ships: a batch without such slices
+    //  needs no room for bands and no k_prefix_bands launch)
+    const bool chunks_banded = kmx::prefix_band_min() < KMX_PSORT_BLOCK_CAP;
+    z.bands_possible = !no_bands && z.n_long && (z.large || chunks_banded);
+    z.cap_bands = !z.bands_possible ? 0
+                  : chunks_banded   ? z.n_long * (KMX_PSORT_BLOCK_CAP / kmx::prefix_band_target() + 1) + elems / kmx::prefix_band_target()
+                                    : elems / kmx::prefix_band_target() + n_large_max;
+    z.cap_cuts = std::min<uint64_t>((z.cap_bands + (chunks_banded ? z.n_long : n_large_max)) * kmx::prefix_band_runs(), uint64_t(1) << 26);
+    return z;
+}
+
+// the stages of search_finish and what they share (r->ctx holds the queries and what the first half left)
+struct Finish {
+    kmx_result* r; kmx_index* ix; hipStream_t s;
+    kmx::QueryDesc d;                    // (validate_stitch sets d.stitch_hits)
+    unsigned long long* ctr; const KmxIndexDev* dix; kmx::FillVariant fv; uint64_t tile;
+    BatchCounts c;
+    const uint64_t* hit_off() const { return r->hit_off.as<uint64_t>(); }
+    uint32_t* out() const { return r->out.as<uint32_t>(); }
+    // k_validate over the pending STITCH queries; it changes their counts, so a full scan and a second counter read-back follow
+    kmx_status validate_stitch()
+    {
+        HIP_TRY(r->mask_words.ensure(c.mask_words * 8));
         // room for every candidate to survive (64 slots per mask word); without it k_compact decodes the masks
         static const bool no_survivors = getenv("KMX_NO_STITCH_HITS") != nullptr;
-        const uint64_t n_more = r->h_ctr[KMX_CTR_STITCH_MORE];   // queries whose survivors need their further parts checked
-        if ((!(flags & KMX_SEARCH_COUNT_ONLY) || n_more) && !no_survivors && r->stitch_hits.ensure(r->n_mask_words * 64 * 4) == hipSuccess)
+        if ((!(r->flags & KMX_SEARCH_COUNT_ONLY) || c.stitch_more) && !no_survivors && r->stitch_hits.ensure(c.mask_words * 64 * 4) == hipSuccess)
             d.stitch_hits = r->stitch_hits.as<uint32_t>();
         else
             (void)hipGetLastError();
         timed(ix, K_VALIDATE, s, [&] {
-            kmx::launch_validate(s, dix, ix->d_arena, qr, qo, d, n_stitch_groups, n_more, n_stitch_tiny, d.stitch_list + (nq - n_stitch_tiny),
-                                 n_stitch_short, r->mask_words.as<uint64_t>(), !(flags & KMX_SEARCH_KEEP_MASKS));
+            kmx::launch_validate(s, dix, ix->d_arena, r->ctx.qr, r->ctx.qo, d, c.stitch_groups, c.stitch_more, c.stitch_tiny, d.stitch_list + (r->nq - c.stitch_tiny),
+                                 c.stitch_short, r->mask_words.as<uint64_t>(), !(r->flags & KMX_SEARCH_KEEP_MASKS));
         });
-        scan_hits();
-        HIP_TRY(hipMemcpyAsync(r->h_ctr, ctr, KMX_CTR_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        scan_hits(ix, r, s, tile, r->ctx.tile_cap, 0, kmx::CounterPub());
+        HIP_TRY(hipMemcpyAsync(r->h_ctr, ctr, kCtrBytes, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-    }
-    r->n_hits = r->h_ctr[KMX_CTR_TOTAL_HITS];
-    if (flags & KMX_SEARCH_COUNT_ONLY) return KMX_OK;
-
-    const uint64_t total = r->n_hits;
-    if (total == 0) {                                          // nothing to fill: a speculative k_fill found no tile of its own and stands
-        r->path.spec_ok = spec_fill;
-        r->path.fill_blocks = uint32_t(spec_fill ? spec_tiles : 0);
+        c.total_hits = r->h_ctr[KMX_CTR_TOTAL_HITS];
         return KMX_OK;
     }
-    const uint64_t n_tiles = (total + tile - 1) / tile;
-    if (n_tiles >= 0x7FFFFFFFull) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: result too large, split the batch");
-    HIP_TRY(r->out.ensure(total * 4));
-    HIP_TRY(r->tile_q.ensure((n_tiles + 1) * 4));
-    uint32_t* out = r->out.as<uint32_t>();
-    const uint64_t* hit_off = r->hit_off.as<uint64_t>();
-    const bool spec_ok = spec_fill && n_stitch_pending == 0 && n_tiles <= spec_tiles;   // the early k_fill already did the work
-    r->path.spec_ok = spec_ok;
-    r->path.fill_tiles = uint32_t(n_tiles);
-    r->path.fill_blocks = uint32_t(spec_ok ? spec_tiles : n_tiles);
-    r->path.tile_q_source = (!spec_ok && n_tiles + 1 > tile_cap) ? KMX_TILE_Q_PARTITION : KMX_TILE_Q_SCAN;
-    if (!spec_ok) {
+    // room for the hits and the tile table; k_partition + k_fill, unless the speculative k_fill of the first half already did the work
+    kmx_status fill_hits()
+    {
+        const uint64_t tile_cap = r->ctx.tile_cap, spec_tiles = r->ctx.spec_tiles, n_tiles = (c.total_hits + tile - 1) / tile;
+        if (n_tiles >= 0x7FFFFFFFull) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch_device: result too large, split the batch");
+        HIP_TRY(r->out.ensure(c.total_hits * 4));
+        HIP_TRY(r->tile_q.ensure((n_tiles + 1) * 4));
+        const bool spec_ok = r->ctx.spec_fill && c.stitch_pending == 0 && n_tiles <= spec_tiles;
+        r->path.spec_ok = spec_ok; r->path.fill_tiles = uint32_t(n_tiles); r->path.fill_blocks = uint32_t(spec_ok ? spec_tiles : n_tiles);
+        r->path.tile_q_source = (!spec_ok && n_tiles + 1 > tile_cap) ? KMX_TILE_Q_PARTITION : KMX_TILE_Q_SCAN;
+        if (spec_ok) return KMX_OK;
         if (n_tiles + 1 > tile_cap)   // first batch / the table had to grow: the scan could not fill it
-            timed(ix, K_PARTITION, s, [&] { kmx::launch_partition(s, hit_off, nq, tile, n_tiles, r->tile_q.as<uint32_t>()); });
+            timed(ix, K_PARTITION, s, [&] { kmx::launch_partition(s, hit_off(), r->nq, tile, n_tiles, r->tile_q.as<uint32_t>()); });
         timed(ix, K_FILL, s, [&] {
-            kmx::launch_fill(s, fv, ix->rec32, dix, ix->d_arena, hit_off, r->tile_q.as<uint32_t>(), ctr + KMX_CTR_TOTAL_HITS, n_tiles, d, out);
+            kmx::launch_fill(s, fv, ix->rec32, dix, ix->d_arena, hit_off(), r->tile_q.as<uint32_t>(), ctr + KMX_CTR_TOTAL_HITS, n_tiles, d, out());
+        });
+        return KMX_OK;
+    }
+    // without room for the survivors (validate_stitch), k_compact decodes the masks of each of the three lists
+    void compact_stitch()
+    {
+        timed(ix, K_COMPACT, s, [&] {
+            auto compact = [&](uint32_t* list, uint64_t n) {
+                if (!n) return;
+                kmx::QueryDesc dl = d; dl.stitch_list = list;
+                kmx::launch_compact(s, ix->d_arena, dl, n, r->mask_words.as<uint64_t>(), hit_off(), out());
+            };
+            compact(d.stitch_list, c.stitch_groups);
+            compact(d.stitch_list + (r->nq - c.stitch_tiny), c.stitch_tiny);
+            compact(d.short_list, c.stitch_short);
         });
     }
-    if (n_stitch_pending && !d.stitch_hits)
-        timed(ix, K_COMPACT, s, [&] {
-            if (n_stitch_groups) kmx::launch_compact(s, ix->d_arena, d, n_stitch_groups, r->mask_words.as<uint64_t>(), hit_off, out);
-            if (n_stitch_tiny) {
-                kmx::QueryDesc dt = d;
-                dt.stitch_list = d.stitch_list + (nq - n_stitch_tiny);
-                kmx::launch_compact(s, ix->d_arena, dt, n_stitch_tiny, r->mask_words.as<uint64_t>(), hit_off, out);
-            }
-            if (n_stitch_short) {
-                kmx::QueryDesc dt = d;
-                dt.stitch_list = d.short_list;
-                kmx::launch_compact(s, ix->d_arena, dt, n_stitch_short, r->mask_words.as<uint64_t>(), hit_off, out);
-            }
-        });
-
-    // PREFIX work list: small queries from the front of prefix_list, the others from its back
-    kmx::QueryDesc d_big = d;
-    d_big.prefix_list = d.prefix_list + (nq - n_prefix_big);
-    const uint64_t n_prefix_merge = r->h_ctr[KMX_CTR_PREFIX_MERGE];       // of the small ones: k_prefix_merge_small's class
-    if (n_prefix_small > n_prefix_merge)
-        timed(ix, K_PREFIX_SORT_SMALL, s, [&] { kmx::launch_prefix_sort_small(s, dix, qo, d, n_prefix_small, hit_off, ix->d_arena, out); });
-    if (n_prefix_merge)
-        timed(ix, K_PREFIX_MERGE_SMALL, s, [&] { kmx::launch_prefix_merge_small(s, dix, qo, d, n_prefix_small, hit_off, ix->d_arena, out); });
-    if (n_prefix_big) {
-        // slices beyond the block kernel's capacity are rows of sorted chunks behind it, merged pairwise in global memory:
-        // their tiles are counted first (the chunks of a slice with an odd number of passes start in the scratch buffer)
-        const bool large = max_runs > 1 && prefix_elems > 0;
-        const uint64_t np = n_prefix_big, T = kmx::prefix_merge_tile();
-        const uint64_t max_tiles = large ? prefix_elems / T + np : 0;
-        // the slices beyond the 256-thread shape: cut into bands where that works (k_prefix_bands: cut tables + one record per band), the
-        // others as chunks (k_prefix_items: one record per chunk — one per slice + one per full chunk at most)
-        const uint64_t n_mid = r->h_ctr[KMX_CTR_PREFIX_MID], n_long = np > n_mid ? np - n_mid : 0;
-        static const bool no_bands = getenv("KMX_NO_BANDS") != nullptr;                 // (experiments: everything as chunks)
-        static const bool no_split = getenv("KMX_NO_SPLIT") != nullptr || no_bands;     // (... no slice spread by value)
-        // room for the slices spread by value (k_prefix_split_*): only slices beyond one chunk go there, prefix_elems holds their positions
-        const bool split_ok = large && !no_split;
-        const uint64_t n_large_max = prefix_elems / KMX_PSORT_BLOCK_CAP + 1;
-        kmx::PrefixSplitRoom sr{};
-        if (split_ok) {
-            sr.cap_splits = n_large_max;
-            sr.cap_tiles = prefix_elems / kmx::prefix_split_tile() + n_large_max;
-            sr.cap_counters = 3 * (prefix_elems / kmx::prefix_split_target() + n_large_max);
-            sr.cap_scratch = prefix_elems + 4 * n_large_max;
-        }
-        const uint64_t cap_items = n_long ? n_long + prefix_elems / KMX_PSORT_BLOCK_CAP + (split_ok ? prefix_elems / kmx::prefix_split_target() + n_large_max : 0) : 0;
-        // (bands are for slices beyond prefix_band_min() positions — one chunk in the build as it ships: a batch without such slices
-        //  needs no room for bands and no k_prefix_bands launch)
-        const bool chunks_banded = kmx::prefix_band_min() < KMX_PSORT_BLOCK_CAP;
-        const bool bands_possible = !no_bands && n_long && (large || chunks_banded);
-        const uint64_t cap_bands = !bands_possible ? 0
-                                   : chunks_banded ? n_long * (KMX_PSORT_BLOCK_CAP / kmx::prefix_band_target() + 1) + prefix_elems / kmx::prefix_band_target()
-                                                   : prefix_elems / kmx::prefix_band_target() + n_large_max;
-        const uint64_t cap_cuts = std::min<uint64_t>((cap_bands + (chunks_banded ? n_long : n_large_max)) * kmx::prefix_band_runs(), uint64_t(1) << 26);
-        if (n_long) {
-            HIP_TRY(r->pitems.ensure(cap_items * kmx::prefix_item_bytes()));
-            HIP_TRY(r->pbands.ensure(cap_bands * kmx::prefix_item_bytes()));
-            HIP_TRY(r->pcuts.ensure(cap_cuts * 4));
+    // the PREFIX queries with a short slice: each kernel takes its class and skips the other's
+    void prefix_small()
+    {
+        if (c.prefix_small > c.prefix_merge)
+            timed(ix, K_PREFIX_SORT_SMALL, s, [&] { kmx::launch_prefix_sort_small(s, dix, r->ctx.qo, d, c.prefix_small, hit_off(), ix->d_arena, out()); });
+        if (c.prefix_merge)
+            timed(ix, K_PREFIX_MERGE_SMALL, s, [&] { kmx::launch_prefix_merge_small(s, dix, r->ctx.qo, d, c.prefix_small, hit_off(), ix->d_arena, out()); });
+    }
+    // the other PREFIX queries (back of prefix_list): bands and splits, the block sort, the merge passes over the chunk rows
+    kmx_status prefix_big()
+    {
+        const uint64_t np = c.prefix_big, n_mid = c.prefix_mid, T = kmx::prefix_merge_tile();
+        const uint64_t* qo = r->ctx.qo;
+        kmx::QueryDesc d_big = d; d_big.prefix_list = d.prefix_list + (r->nq - np);
+        const PrefixBigSizes z = prefix_big_sizes(c);
+        kmx::PrefixSplitRoom sr = z.room;
+        if (z.n_long) {
+            HIP_TRY(r->pitems.ensure(z.cap_items * kmx::prefix_item_bytes()));
+            HIP_TRY(r->pbands.ensure(z.cap_bands * kmx::prefix_item_bytes()));
+            HIP_TRY(r->pcuts.ensure(z.cap_cuts * 4));
             HIP_TRY(r->pbanded.ensure(np * 4));
-            if (split_ok) {
+            if (z.split_ok) {
                 if (r->psplits.ensure(sr.cap_splits * kmx::prefix_split_bytes(0)) == hipSuccess && r->ptiles.ensure(sr.cap_tiles * kmx::prefix_split_bytes(1)) == hipSuccess &&
                     r->pscnt.ensure(sr.cap_counters * 4) == hipSuccess && r->pscratch.ensure(sr.cap_scratch * 4) == hipSuccess) {
                     sr.splits = r->psplits.p; sr.tiles = r->ptiles.p; sr.counters = r->pscnt.as<uint32_t>(); sr.scratch = r->pscratch.as<uint32_t>();
@@ -1945,24 +1998,24 @@ static kmx_status search_finish(kmx_result* r)
                     sr = kmx::PrefixSplitRoom{};
                 }
             }
-            if (!bands_possible && !sr.splits) HIP_TRY(hipMemsetAsync(r->pbanded.p, 0, np * 4, s));
+            if (!z.bands_possible && !sr.splits) HIP_TRY(hipMemsetAsync(r->pbanded.p, 0, np * 4, s));
             else {
                 timed(ix, K_PREFIX_BANDS, s, [&] {
-                    kmx::launch_prefix_bands(s, dix, qo, d_big, np, hit_off, ix->d_arena, r->pbanded.as<uint32_t>(), r->pbands.p, cap_bands,
-                                             r->pcuts.as<uint32_t>(), cap_cuts, ctr + KMX_CTR_PSB_BANDS, sr);
+                    kmx::launch_prefix_bands(s, dix, qo, d_big, np, hit_off(), ix->d_arena, r->pbanded.as<uint32_t>(), r->pbands.p, z.cap_bands,
+                                             r->pcuts.as<uint32_t>(), z.cap_cuts, ctr + KMX_CTR_PSB_BANDS, sr);
                 });
                 if (sr.splits)
                     timed(ix, K_PREFIX_SPLIT, s, [&] {
-                        kmx::launch_prefix_split(s, sr, ctr + KMX_CTR_PSB_BANDS, ix->d_arena, r->pbanded.as<uint32_t>(), ix->h_header.n, r->pitems.p, cap_items,
+                        kmx::launch_prefix_split(s, sr, ctr + KMX_CTR_PSB_BANDS, ix->d_arena, r->pbanded.as<uint32_t>(), ix->h_header.n, r->pitems.p, z.cap_items,
                                                  ctr + KMX_CTR_PSB_OTHER);
                     });
             }
         }
-        if (large) {
+        if (z.large) {
             HIP_TRY(r->plen.ensure(np * 4));
             HIP_TRY(r->poff.ensure((np + 1) * 8));
-            HIP_TRY(r->ptmp.ensure(max_tiles * T * 4));
-            HIP_TRY(r->bsum.ensure(std::max(kmx::scan_blocks(np), kmx::scan_blocks(nq)) * 8));
+            HIP_TRY(r->ptmp.ensure(z.max_tiles * T * 4));
+            HIP_TRY(r->bsum.ensure(std::max(kmx::scan_blocks(np), kmx::scan_blocks(r->nq)) * 8));
             timed(ix, K_PREFIX_LEN, s, [&] { kmx::launch_prefix_len(s, d_big, np, r->pbanded.as<uint32_t>(), r->plen.as<uint32_t>()); });
             timed(ix, K_SCAN, s, [&] {
                 kmx::launch_scan(s, r->plen.as<uint32_t>(), np, r->bsum.as<uint64_t>(), r->poff.as<uint64_t>(), ctr + KMX_CTR_PREFIX_TOTAL);
@@ -1970,38 +2023,54 @@ static kmx_status search_finish(kmx_result* r)
         }
         if (n_mid) HIP_TRY(r->pmid.ensure(np * kmx::prefix_item_bytes()));
         timed(ix, K_PREFIX_SORT_BLOCK, s, [&] {
-            kmx::launch_prefix_sort_block(s, dix, qo, d_big, np, n_mid, hit_off, ix->d_arena, out, large ? r->poff.as<uint64_t>() : nullptr,
-                                          large ? r->ptmp.as<uint32_t>() : nullptr, r->pitems.p, cap_items, ctr + KMX_CTR_PSB_MERGE,
-                                          r->pbanded.as<uint32_t>(), r->pbands.p, cap_bands, r->pcuts.as<uint32_t>(), ctr + KMX_CTR_PSB_BANDS, sr.scratch, r->pmid.p, ix->h_header.n, ix->d_dbg);
+            kmx::launch_prefix_sort_block(s, dix, qo, d_big, np, n_mid, hit_off(), ix->d_arena, out(), z.large ? r->poff.as<uint64_t>() : nullptr,
+                                          z.large ? r->ptmp.as<uint32_t>() : nullptr, r->pitems.p, z.cap_items, ctr + KMX_CTR_PSB_MERGE,
+                                          r->pbanded.as<uint32_t>(), r->pbands.p, z.cap_bands, r->pcuts.as<uint32_t>(), ctr + KMX_CTR_PSB_BANDS, sr.scratch, r->pmid.p, ix->h_header.n, ix->d_dbg);
         });
-        if (large) {
+        if (z.large) {
             uint32_t passes = 0;
-            while ((uint64_t(1) << passes) < max_runs) ++passes;
+            while ((uint64_t(1) << passes) < c.max_runs) ++passes;
             for (uint32_t p = 0; p < passes; ++p)
                 timed(ix, K_MERGE_PASS, s, [&] {
-                    kmx::launch_prefix_merge_pass(s, d_big, np, r->poff.as<uint64_t>(), max_tiles, hit_off, out, r->ptmp.as<uint32_t>(), p);
+                    kmx::launch_prefix_merge_pass(s, d_big, np, r->poff.as<uint64_t>(), z.max_tiles, hit_off(), out(), r->ptmp.as<uint32_t>(), p);
                 });
         }
+        return KMX_OK;
     }
+};
+
+// Second half of a search: waits for the counters of the first half, then validates / fills / sorts whatever the
+// speculative steady-state path has not already done.  A no-op when nothing is pending.
+static kmx_status search_finish(kmx_result* r)
+{
+    if (!r->ctx.pending) return KMX_OK;
+    r->ctx.pending = false;
+    KMX_TRY(wait_counters(r));
+    kmx_index* ix = r->ctx.ix;
+    const kmx::FillVariant fv = kmx::effective_fill_variant(ix->fill_variant, ix->rec32);
+    Finish f{r, ix, r->ctx.s, r->query_desc(), r->ctr_block(r->ctr_phase), header_for(ix, r->flags), fv, kmx::fill_tile(fv), read_counts(r)};
+    if (f.c.stitch_pending) KMX_TRY(f.validate_stitch());
+    r->n_hits = f.c.total_hits;
+    if (r->flags & KMX_SEARCH_COUNT_ONLY) return KMX_OK;
+    if (r->n_hits == 0) {                                      // nothing to fill: a speculative k_fill found no tile of its own and stands
+        r->path.spec_ok = r->ctx.spec_fill; r->path.fill_blocks = uint32_t(r->ctx.spec_fill ? r->ctx.spec_tiles : 0);
+        return KMX_OK;
+    }
+    KMX_TRY(f.fill_hits());
+    if (f.c.stitch_pending && !f.d.stitch_hits) f.compact_stitch();
+    f.prefix_small();
+    if (f.c.prefix_big) KMX_TRY(f.prefix_big());
     HIP_TRY(hipGetLastError());
     return KMX_OK;
 }
 
-// host-buffer search of one replica: inputs to the device on the result's own stream, the device form behind them.
-// `wait`: return with the search complete; otherwise its second half stays pending (multi-device: every replica is
-// started before any is waited for).
-static kmx_status search_host_one(kmx_index* ix, const uint8_t* qranks, const uint64_t* qoff, uint64_t q0, uint64_t q1, uint32_t flags,
-                                  kmx_result** inout, bool wait)
+// The latency path.  A handful of queries (kmer_index::search(query) is a batch of one; up to 8192 queries in 32 workgroups): one
+// launch that reads the queries from and writes the whole result to page-locked blocks — no copies, no counter read-back, one
+// wait.  *served stays false for a batch that is not one for the small kernel (or that it declined): the general path has to run.
+static kmx_status try_small(kmx_index* ix, kmx_result* r, const uint8_t* qranks, const uint64_t* qoff, uint64_t q0, uint64_t q1, uint32_t flags, bool* served)
 {
-    HIP_TRY(hipSetDevice(ix->device));
-    kmx_result* r = *inout ? *inout : take_result(ix);
-    *inout = r;
-    if (r->ctx.pending) { kmx_status fs = search_finish(r); if (fs != KMX_OK) return fs; }
-    if (!r->own_stream) HIP_TRY(hipStreamCreateWithFlags(&r->own_stream, hipStreamNonBlocking));
+    *served = false;
     const uint64_t nq = q1 - q0;
-    const uint64_t l0 = nq ? qoff[q0] : 0, n_letters = nq ? qoff[q1] - l0 : 0;
-    // A handful of queries (kmer_index::search(query) is a batch of one; up to 8192 queries in 32 workgroups): one launch that
-    // reads the queries from and writes the whole result to page-locked blocks — no copies, no counter read-back, one wait.
     static const bool no_small = getenv("KMX_NO_SMALL") != nullptr;
     const uint32_t n_sb = uint32_t((nq + KMX_SMALL_NQ - 1) / KMX_SMALL_NQ);
     bool small = nq && n_sb <= KMX_SMALL_BLOCKS && !(flags & KMX_SEARCH_COUNT_ONLY) && !no_small;
@@ -2022,85 +2091,157 @@ static kmx_status search_host_one(kmx_index* ix, const uint8_t* qranks, const ui
     // the mailbox is laid out for 1, 4 or 32 workgroups (7 MB page-locked for the largest: allocated once per result handle)
     const KmxSmallLayout L = kmx_small_layout(n_sb <= 1 ? 1u : n_sb <= 4 ? 4u : uint32_t(KMX_SMALL_BLOCKS));
     if (small && n_sb > 1 && r->small_xchg.ensure(KMX_SMALL_BLOCKS * 8) != hipSuccess) { (void)hipGetLastError(); small = false; }
-    if (small && r->mailbox.ensure_pinned(L.bytes)) {
-        unsigned char* mb0 = r->mailbox.as<unsigned char>();
-        for (uint32_t b = 0; b < n_sb; ++b) {
-            unsigned char* in = mb0 + size_t(b) * KMX_SMALL_IN_BYTES;
-            const uint64_t b0 = q0 + uint64_t(b) * KMX_SMALL_NQ, lb = qoff[b0];
-            uint64_t* in_off = reinterpret_cast<uint64_t*>(in);
-            for (uint32_t i = 0; i <= sargs.nq[b]; ++i) in_off[i] = qoff[b0 + i] - lb;
-            if (sargs.n_letters[b]) memcpy(in + (size_t(sargs.nq[b]) + 1) * 8, qranks + lb, sargs.n_letters[b]);
-            reinterpret_cast<KmxSmallHeader*>(mb0 + L.off_header)[b].fallback = 2;          // (overwritten by the kernel)
-        }
-        (void)hipGetLastError();
-        unsigned long long* xchg = n_sb > 1 ? r->small_xchg.as<unsigned long long>() : nullptr;
-        if (xchg) HIP_TRY(hipMemsetAsync(xchg, 0, KMX_SMALL_BLOCKS * 8, r->own_stream));
-        timed(ix, K_SMALL, r->own_stream, [&] { kmx::launch_small(r->own_stream, header_for(ix, flags), ix->d_arena, mb0, L, n_sb, sargs, uint32_t(nq), xchg, flags); });
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(r->own_stream));
-        const KmxSmallHeader* hdrs = reinterpret_cast<const KmxSmallHeader*>(mb0 + L.off_header);
-        bool all_ok = true;
-        for (uint32_t b = 0; b < n_sb; ++b) all_ok = all_ok && hdrs[b].fallback == 0;
-        if (all_ok) {
-            r->index = ix; r->device = ix->device; r->stream = r->own_stream; r->flags = flags & ~KMX_SEARCH_ASYNC;
-            r->nq = nq;
-            r->n_hits = r->n_mask_words = r->n_stitch = r->n_prefix = r->n_error = r->n_none = 0;
-            for (uint32_t b = 0; b < n_sb; ++b) {
-                r->n_hits += hdrs[b].n_hits; r->n_mask_words += hdrs[b].n_mask_words;
-                r->n_stitch += hdrs[b].n_stitch; r->n_prefix += hdrs[b].n_prefix; r->n_error += hdrs[b].n_error; r->n_none += hdrs[b].n_none;
-            }
-            r->n_exact = nq - r->n_stitch - r->n_prefix - r->n_error - r->n_none;
-            // the workgroups wrote into ONE set of arrays: the views are the mailbox
-            r->v_hit_off = reinterpret_cast<uint64_t*>(mb0 + L.off_hitoff);
-            r->v_positions = reinterpret_cast<uint32_t*>(mb0 + L.off_pos);
-            r->v_status = mb0 + L.off_status;
-            r->v_kinds = mb0 + L.off_kinds;
-            r->m_base = reinterpret_cast<const uint64_t*>(mb0 + L.off_mbase);
-            r->m_words = reinterpret_cast<const uint64_t*>(mb0 + L.off_words);
-            r->m_ccnt = reinterpret_cast<const uint32_t*>(mb0 + L.off_ccnt);
-            r->m_csrc = reinterpret_cast<const uint64_t*>(mb0 + L.off_csrc);
-            // the queries themselves, should device views be asked for later (kmx_result_view_device runs the device form then)
-            if (!r->small_in.ensure_pageable((nq + 1) * 8 + n_letters + 16)) return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_search_batch: host allocation failed");
-            {
-                uint64_t* io = r->small_in.as<uint64_t>();
-                for (uint64_t i = 0; i <= nq; ++i) io[i] = qoff[q0 + i] - l0;
-                if (n_letters) memcpy(r->small_in.as<unsigned char>() + (nq + 1) * 8, qranks + l0, n_letters);
-            }
-            r->host_valid = r->host_masks_valid = true;
-            r->small_valid = true;
-            r->windows = false;
-            r->path = kmx_result::PathRec{};
-            r->path.small = 1;
-            r->quiesced = true;
-            r->last_had_stitch = false;
-            r->last_had_pairs = false;
-            r->last_had_long = false;
-            r->pool = ix->pool;                                 // (kmx_result_view_device asks it whether the index is still there)
-            return KMX_OK;
-        }
-        // not a batch for the small kernel (too many hits, long candidate lists): the general path below
+    if (!small || !r->mailbox.ensure_pinned(L.bytes)) return KMX_OK;
+    unsigned char* mb0 = r->mailbox.as<unsigned char>();
+    KmxSmallHeader* hdrs = reinterpret_cast<KmxSmallHeader*>(mb0 + L.off_header);
+    for (uint32_t b = 0; b < n_sb; ++b) {
+        unsigned char* in = mb0 + size_t(b) * KMX_SMALL_IN_BYTES;
+        const uint64_t b0 = q0 + uint64_t(b) * KMX_SMALL_NQ, lb = qoff[b0];
+        uint64_t* in_off = reinterpret_cast<uint64_t*>(in);
+        for (uint32_t i = 0; i <= sargs.nq[b]; ++i) in_off[i] = qoff[b0 + i] - lb;
+        if (sargs.n_letters[b]) memcpy(in + (size_t(sargs.nq[b]) + 1) * 8, qranks + lb, sargs.n_letters[b]);
+        hdrs[b].fallback = 2;                                   // (overwritten by the kernel)
     }
-    HIP_TRY(r->in_qranks.ensure(std::max<uint64_t>(n_letters, 1) + 16));
-    HIP_TRY(r->in_qoff.ensure((nq + 1) * 8));
-    if (n_letters) HIP_TRY(hipMemcpyAsync(r->in_qranks.p, qranks + l0, n_letters, hipMemcpyHostToDevice, r->own_stream));
-    if (nq) {
-        if (l0 == 0) {
-            HIP_TRY(hipMemcpyAsync(r->in_qoff.p, qoff + q0, (nq + 1) * 8, hipMemcpyHostToDevice, r->own_stream));
-        } else {
-            // a shard's offsets are rebased to its own letters
-            std::vector<uint64_t> local(nq + 1);
-            for (uint64_t i = 0; i <= nq; ++i) local[i] = qoff[q0 + i] - l0;
-            HIP_TRY(hipMemcpyAsync(r->in_qoff.p, local.data(), (nq + 1) * 8, hipMemcpyHostToDevice, r->own_stream));
-            HIP_TRY(hipStreamSynchronize(r->own_stream));           // `local` goes out of scope
-        }
+    (void)hipGetLastError();
+    unsigned long long* xchg = n_sb > 1 ? r->small_xchg.as<unsigned long long>() : nullptr;
+    if (xchg) HIP_TRY(hipMemsetAsync(xchg, 0, KMX_SMALL_BLOCKS * 8, r->own_stream));
+    timed(ix, K_SMALL, r->own_stream, [&] { kmx::launch_small(r->own_stream, header_for(ix, flags), ix->d_arena, mb0, L, n_sb, sargs, uint32_t(nq), xchg, flags); });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(r->own_stream));
+    for (uint32_t b = 0; b < n_sb; ++b)
+        if (hdrs[b].fallback != 0) return KMX_OK;
+    r->index = ix; r->device = ix->device; r->stream = r->own_stream; r->flags = flags & ~KMX_SEARCH_ASYNC; r->nq = nq;
+    r->tally().reset();
+    for (uint32_t b = 0; b < n_sb; ++b)
+        r->tally() += Tallies{hdrs[b].n_hits, 0, hdrs[b].n_stitch, hdrs[b].n_prefix, hdrs[b].n_error, hdrs[b].n_none, hdrs[b].n_mask_words};
+    r->derive_exact(nq);
+    // the workgroups wrote into ONE set of arrays: the views are the mailbox
+    r->v_hit_off = reinterpret_cast<uint64_t*>(mb0 + L.off_hitoff); r->v_positions = reinterpret_cast<uint32_t*>(mb0 + L.off_pos);
+    r->v_status = mb0 + L.off_status; r->v_kinds = mb0 + L.off_kinds;
+    r->m_base = reinterpret_cast<const uint64_t*>(mb0 + L.off_mbase); r->m_words = reinterpret_cast<const uint64_t*>(mb0 + L.off_words);
+    r->m_ccnt = reinterpret_cast<const uint32_t*>(mb0 + L.off_ccnt); r->m_csrc = reinterpret_cast<const uint64_t*>(mb0 + L.off_csrc);
+    // the queries themselves, should device views be asked for later (kmx_result_view_device runs the device form then)
+    const uint64_t l0 = qoff[q0], n_letters = qoff[q1] - l0;
+    if (!r->small_in.ensure_pageable((nq + 1) * 8 + n_letters + 16)) return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_search_batch: host allocation failed");
+    uint64_t* io = r->small_in.as<uint64_t>();
+    for (uint64_t i = 0; i <= nq; ++i) io[i] = qoff[q0 + i] - l0;
+    if (n_letters) memcpy(r->small_in.as<unsigned char>() + (nq + 1) * 8, qranks + l0, n_letters);
+    r->host_valid = r->host_masks_valid = r->small_valid = r->quiesced = true;
+    r->windows = false; r->path = kmx_result::PathRec{}; r->path.small = 1;
+    r->last_had_stitch = r->last_had_pairs = r->last_had_long = false;
+    r->pool = ix->pool;                                     // (kmx_result_view_device asks it whether the index is still there)
+    *served = true;
+    return KMX_OK;
+}
+
+// host-buffer search of one replica: the latency path where it serves; otherwise the inputs to the device on the result's own
+// stream, the device form behind them.  `wait`: return with the search complete; otherwise its second half stays pending
+// (multi-device: every replica is started before any is waited for).
+static kmx_status search_host_one(kmx_index* ix, const uint8_t* qranks, const uint64_t* qoff, uint64_t q0, uint64_t q1, uint32_t flags,
+                                  kmx_result** inout, bool wait)
+{
+    KMX_TRY(host_handle(ix, inout, nullptr));
+    kmx_result* r = *inout;
+    bool served = false;
+    KMX_TRY(try_small(ix, r, qranks, qoff, q0, q1, flags, &served));
+    if (served) return KMX_OK;
+    const uint64_t nq = q1 - q0;
+    const uint64_t l0 = nq ? qoff[q0] : 0, n_letters = nq ? qoff[q1] - l0 : 0;
+    if (l0 == 0) KMX_TRY(upload_queries(r, qranks, n_letters, qoff + q0, nq));
+    else {
+        // a shard's offsets are rebased to its own letters
+        std::vector<uint64_t> local(nq + 1);
+        for (uint64_t i = 0; i <= nq; ++i) local[i] = qoff[q0 + i] - l0;
+        KMX_TRY(upload_queries(r, qranks + l0, n_letters, local.data(), nq));
+        HIP_TRY(hipStreamSynchronize(r->own_stream));           // `local` goes out of scope
     }
     const uint32_t f = wait ? (flags & ~KMX_SEARCH_ASYNC) : (flags | KMX_SEARCH_ASYNC);
-    kmx_status st = kmx_search_batch_device(ix, r->in_qranks.p, r->in_qoff.p, nq, f, r->own_stream, inout);
-    if (st != KMX_OK) return st;
+    KMX_TRY(kmx_search_batch_device(ix, r->in_qranks.p, r->in_qoff.p, nq, f, r->own_stream, inout));
     if (wait) {
         HIP_TRY(hipStreamSynchronize(r->own_stream));
         r->quiesced = true;
     }
+    return KMX_OK;
+}
+
+// One part (a chunk, a replica's share) into its slices of the parent's host views; h0: the hits of the parts in front.  A latency-path
+// part is host memory already; any other leaves its device on its own stream (waited for by the caller before rebase_part).
+static void append_part_host(kmx_result* parent, const kmx_result* p, uint64_t q0, uint64_t nqp, uint64_t h0, bool want_pos)
+{
+    memcpy(parent->v_hit_off + q0 + 1, p->v_hit_off + 1, nqp * 8);
+    memcpy(parent->v_status + q0, p->v_status, nqp);
+    memcpy(parent->v_kinds + q0, p->v_kinds, nqp);
+    if (want_pos && p->n_hits) memcpy(parent->v_positions + h0, p->v_positions, p->n_hits * 4);
+}
+static hipError_t append_part_async(kmx_result* parent, const kmx_result* p, uint64_t q0, uint64_t nqp, uint64_t h0, bool want_pos)
+{
+    hipError_t e = hipSuccess;
+    if (nqp) e = hipMemcpyAsync(parent->v_hit_off + q0 + 1, p->hit_off.as<uint64_t>() + 1, nqp * 8, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess && nqp) e = hipMemcpyAsync(parent->v_status + q0, p->status.p, nqp, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess && nqp) e = hipMemcpyAsync(parent->v_kinds + q0, p->kind.p, nqp, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess && want_pos && p->n_hits) e = hipMemcpyAsync(parent->v_positions + h0, p->out.p, p->n_hits * 4, hipMemcpyDeviceToHost, p->stream);
+    return e;
+}
+static void rebase_part(kmx_result* parent, uint64_t q0, uint64_t q1, uint64_t h0)
+{
+    for (uint64_t q = q0 + 1; h0 && q <= q1; ++q) parent->v_hit_off[q] += h0;
+}
+// search_host_chunked: what leaves a worker for the host does so on a helper thread, one per worker
+struct CopyTask { std::thread th; kmx_status st = KMX_OK; std::string err; bool running = false; };
+static kmx_status join_task(CopyTask& t)
+{
+    if (t.running) { t.th.join(); t.running = false; }
+    if (t.st != KMX_OK) { g_err = t.err; const kmx_status st = t.st; t.st = KMX_OK; return st; }
+    return KMX_OK;
+}
+static kmx_status join_tasks(CopyTask (&tasks)[2], kmx_status st)         // no task outlives the call; the first failure is the call's
+{
+    for (CopyTask& t : tasks) { const kmx_status js = join_task(t); if (st == KMX_OK) st = js; }
+    return st;
+}
+static void start_task(CopyTask& t, const std::function<void()>& work)
+{
+    try { t.th = std::thread(work); t.running = true; }
+    catch (const std::system_error&) { work(); }                // no thread to be had: the work runs here, in line
+}
+// the masks of the chunk worker w just searched (cq queries) into pageable buffers of the chunk's part
+static void copy_part_masks(CopyTask& t, kmx_result* w, kmx_result* part, uint64_t cq)
+{
+    const uint64_t* mb = nullptr; const uint64_t* mw = nullptr; const uint32_t* cc = nullptr; const uint64_t* cs = nullptr;
+    const kmx_status st = kmx_result_masks(w, &mb, &mw, &cc, &cs);
+    if (st != KMX_OK) { t.st = st; t.err = g_err; return; }
+    if (!part->h_mask_base.ensure_pageable((cq + 1) * 8) || !part->h_cand_count.ensure_pageable((cq + 1) * 4) ||
+        !part->h_cand_src.ensure_pageable((cq + 1) * 8) || !part->h_mask_words.ensure_pageable((w->n_mask_words + 1) * 8)) {
+        t.st = KMX_ERR_OUT_OF_MEMORY; t.err = "kmx_search_batch: host allocation for a chunk's masks failed"; return;
+    }
+    memcpy(part->h_mask_base.p, mb, cq * 8); memcpy(part->h_cand_count.p, cc, cq * 4); memcpy(part->h_cand_src.p, cs, cq * 8);
+    if (w->n_mask_words) memcpy(part->h_mask_words.p, mw, w->n_mask_words * 8);
+    part->mask_view_own();
+}
+// the positions view proved short: room for `sofar` hits (up to query q1) and, by their hits per query, for the rest of the batch
+static kmx_status grow_positions(kmx_result* parent, CopyTask (&tasks)[2], uint64_t h0, uint64_t sofar, uint64_t q1)
+{
+    KMX_TRY(join_tasks(tasks, KMX_OK));
+    const uint64_t nq = parent->nq, guess = q1 < nq ? sofar + (sofar / std::max<uint64_t>(q1, 1) + 1) * (nq - q1) * 9 / 8 : sofar;
+    HostBuf bigger;
+    if (!bigger.ensure(std::max<uint64_t>(guess, 1) * 4)) return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_search_batch: host allocation for the hit lists failed");
+    if (h0) memcpy(bigger.p, parent->h_positions.p, h0 * 4);
+    parent->h_positions.release();
+    parent->h_positions = bigger;                           // (moved: `bigger` has no destructor)
+    parent->v_positions = parent->h_positions.as<uint32_t>();
+    return KMX_OK;
+}
+// A chunk search ran out of device memory.  First the second set of device buffers goes (both copy tasks joined, worker2 released
+// whichever worker was being searched into: its grow-only buffers from the larger chunks would starve the retry) and the SAME
+// chunk size is tried with one worker; only if one worker alone does not fit either are the chunks halved, down to 1024 queries.
+static kmx_status shrink_after_oom(kmx_index* ix, kmx_result* parent, CopyTask (&tasks)[2], bool* single_worker, uint64_t* chunk_q)
+{
+    (void)hipGetLastError();
+    KMX_TRY(join_tasks(tasks, KMX_OK));
+    if (*single_worker) *chunk_q = std::max<uint64_t>(*chunk_q / 2, 1024);
+    *single_worker = true;
+    if (parent->worker2) { kmx_result_free(parent->worker2); parent->worker2 = nullptr; }
+    release_idle(*ix->pool);
     return KMX_OK;
 }
 
@@ -2125,7 +2266,7 @@ static kmx_status search_host_chunked(kmx_index* ix, const uint8_t* qranks, cons
     parent->part_q0.assign(1, 0);
     parent->index = ix; parent->device = ix->device; parent->flags = flags & ~KMX_SEARCH_ASYNC; parent->nq = nq;
     parent->host_valid = parent->host_masks_valid = false;
-    parent->n_hits = parent->n_exact = parent->n_stitch = parent->n_prefix = parent->n_error = parent->n_none = parent->n_mask_words = 0;
+    parent->tally().reset();
     const bool masks = (flags & KMX_SEARCH_KEEP_MASKS) != 0;
     chunk_q = std::max<uint64_t>(chunk_q, 1);
 
@@ -2139,53 +2280,17 @@ static kmx_status search_host_chunked(kmx_index* ix, const uint8_t* qranks, cons
     const uint64_t nq1 = std::max<uint64_t>(nq, 1);
     if (!parent->h_hit_off.ensure((nq + 1) * 8) || !parent->h_status.ensure(nq1) || !parent->h_kinds.ensure(nq1))
         return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_search_batch: host allocation failed");
-    parent->v_hit_off = parent->h_hit_off.as<uint64_t>();
-    parent->v_status = parent->h_status.as<uint8_t>();
-    parent->v_kinds = parent->h_kinds.as<uint8_t>();
-    parent->v_positions = parent->h_positions.as<uint32_t>();
+    parent->view_own();
     parent->v_hit_off[0] = 0;
-    struct CopyTask {
-        std::thread th;
-        kmx_status st = KMX_OK;
-        std::string err;
-        bool running = false;
-    } tasks[2];
-    auto join = [&](int w) -> kmx_status {
-        if (tasks[w].running) { tasks[w].th.join(); tasks[w].running = false; }
-        if (tasks[w].st != KMX_OK) { g_err = tasks[w].err; const kmx_status st = tasks[w].st; tasks[w].st = KMX_OK; return st; }
-        return KMX_OK;
-    };
-    auto finish = [&](kmx_status st) -> kmx_status {         // no task outlives the call
-        for (int w = 0; w < 2; ++w) { const kmx_status js = join(w); if (st == KMX_OK) st = js; }
-        return st;
-    };
-    auto copy_out = [&](int wi, kmx_result* w, kmx_result* part, uint64_t q0, uint64_t cq, uint64_t h0) {
-        CopyTask& t = tasks[wi];
-        hipError_t e = hipSetDevice(ix->device);
-        hipStream_t cs = w->stream;
+    CopyTask tasks[2];                                        // (their work refers to this frame: nothing returns without join_tasks)
+    auto copy_out = [&](CopyTask& t, kmx_result* w, kmx_result* part, uint64_t q0, uint64_t cq, uint64_t h0) {
         // (search_host_one left the worker complete: counters read, every kernel of the chunk done)
-        if (e == hipSuccess && cq) e = hipMemcpyAsync(parent->v_hit_off + q0 + 1, w->hit_off.as<uint64_t>() + 1, cq * 8, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess && cq) e = hipMemcpyAsync(parent->v_status + q0, w->status.p, cq, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess && cq) e = hipMemcpyAsync(parent->v_kinds + q0, w->kind.p, cq, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess && want_pos && w->n_hits) e = hipMemcpyAsync(parent->v_positions + h0, w->out.p, w->n_hits * 4, hipMemcpyDeviceToHost, cs);
-        if (e == hipSuccess) e = hipStreamSynchronize(cs);
+        hipError_t e = hipSetDevice(ix->device);
+        if (e == hipSuccess) e = append_part_async(parent, w, q0, cq, h0, want_pos);
+        if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
         if (e != hipSuccess) { t.st = KMX_ERR_HIP; t.err = std::string("kmx_search_batch: chunk copy: ") + hipGetErrorString(e); return; }
-        if (h0)
-            for (uint64_t q = q0 + 1; q <= q0 + cq; ++q) parent->v_hit_off[q] += h0;
-        if (masks) {
-            const uint64_t* mb = nullptr; const uint64_t* mw = nullptr; const uint32_t* cc = nullptr; const uint64_t* cs2 = nullptr;
-            const kmx_status st = kmx_result_masks(w, &mb, &mw, &cc, &cs2);
-            if (st != KMX_OK) { t.st = st; t.err = g_err; return; }
-            if (!part->h_mask_base.ensure_pageable((cq + 1) * 8) || !part->h_cand_count.ensure_pageable((cq + 1) * 4) ||
-                !part->h_cand_src.ensure_pageable((cq + 1) * 8) || !part->h_mask_words.ensure_pageable((w->n_mask_words + 1) * 8)) {
-                t.st = KMX_ERR_OUT_OF_MEMORY; t.err = "kmx_search_batch: host allocation for a chunk's masks failed";
-                return;
-            }
-            memcpy(part->h_mask_base.p, mb, cq * 8); memcpy(part->h_cand_count.p, cc, cq * 4); memcpy(part->h_cand_src.p, cs2, cq * 8);
-            if (w->n_mask_words) memcpy(part->h_mask_words.p, mw, w->n_mask_words * 8);
-            part->m_base = part->h_mask_base.as<uint64_t>(); part->m_words = part->h_mask_words.as<uint64_t>();
-            part->m_ccnt = part->h_cand_count.as<uint32_t>(); part->m_csrc = part->h_cand_src.as<uint64_t>();
-        }
+        rebase_part(parent, q0, q0 + cq, h0);
+        if (masks) copy_part_masks(t, w, part, cq);
     };
     int turn = 0;
     bool single_worker = false;                               // after an out-of-memory: ONE set of device buffers from there on
@@ -2193,138 +2298,53 @@ static kmx_status search_host_chunked(kmx_index* ix, const uint8_t* qranks, cons
     long long n_searches = 0;
     uint64_t h0 = 0;                                          // hits of the chunks in front
     for (uint64_t q0 = 0; q0 < nq;) {
-        const uint64_t q1 = std::min(nq, q0 + chunk_q);
+        const uint64_t q1 = std::min(nq, q0 + chunk_q), cq = q1 - q0;
         kmx_result*& wr = turn ? parent->worker2 : parent->worker;
-        kmx_status st = join(turn);                          // the worker's previous chunk has left it
-        if (st != KMX_OK) return finish(st);
+        CopyTask& t = tasks[turn];
+        kmx_status st = join_task(t);                        // the worker's previous chunk has left it
+        if (st != KMX_OK) return join_tasks(tasks, st);
         st = (inject_oom && ++n_searches == inject_oom) ? fail(KMX_ERR_OUT_OF_MEMORY, "kmx_search_batch: injected out-of-memory (KMX_TEST_INJECT_CHUNK_OOM)")
                                                         : search_host_one(ix, qranks, qoff, q0, q1, flags, &wr, true);
         if (st == KMX_ERR_OUT_OF_MEMORY && (chunk_q > 1024 || !single_worker)) {
-            // Out of device memory.  First the second set of device buffers goes (both copy tasks joined, worker2 released whichever
-            // worker was being searched into: its grow-only buffers from the larger chunks would starve the retry) and the SAME chunk
-            // size is tried with one worker; only if one worker alone does not fit either are the chunks halved.
-            (void)hipGetLastError();
-            const kmx_status js = finish(KMX_OK);
-            if (js != KMX_OK) return js;
-            if (single_worker) chunk_q = std::max<uint64_t>(chunk_q / 2, 1024);
-            single_worker = true;
-            if (parent->worker2) { kmx_result_free(parent->worker2); parent->worker2 = nullptr; }
+            KMX_TRY(shrink_after_oom(ix, parent, tasks, &single_worker, &chunk_q));
             turn = 0;
-            {
-                // results parked in the pool hold device memory too
-                std::vector<kmx_result*> idle;
-                { std::lock_guard<std::mutex> lock(ix->pool->mu); idle.swap(ix->pool->idle); }
-                for (kmx_result* r : idle) { r->release(); delete r; }
-            }
             continue;
         }
-        if (st != KMX_OK) return finish(st);
+        if (st != KMX_OK) return join_tasks(tasks, st);
         kmx_result* w = wr;
         if (w->small_valid) {
             // (a chunk small enough for the one-launch latency path leaves nothing in HBM: its views are host memory already)
             const uint64_t* ho; const uint32_t* pos; const uint8_t* stt; const uint8_t* kd;
-            if ((st = kmx_result_view(w, &ho, &pos, &stt, &kd)) != KMX_OK) return finish(st);
+            if ((st = kmx_result_view(w, &ho, &pos, &stt, &kd)) != KMX_OK) return join_tasks(tasks, st);
         }
-        const uint64_t cq = q1 - q0;
-        if (want_pos && (h0 + w->n_hits) * 4 > parent->h_positions.cap) {
-            // the positions view: room for this chunk and, by its hits per query so far, for the rest of the batch
-            if ((st = finish(KMX_OK)) != KMX_OK) return st;  // (copies into the old buffer are done)
-            const uint64_t sofar = h0 + w->n_hits;
-            const uint64_t guess = q1 < nq ? sofar + (sofar / std::max<uint64_t>(q1, 1) + 1) * (nq - q1) * 9 / 8 : sofar;
-            HostBuf bigger;
-            if (!bigger.ensure(std::max<uint64_t>(guess, 1) * 4)) return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_search_batch: host allocation for the hit lists failed");
-            if (h0) memcpy(bigger.p, parent->h_positions.p, h0 * 4);
-            parent->h_positions.release();
-            parent->h_positions = bigger;
-            bigger.p = nullptr; bigger.cap = 0;               // (moved)
-            parent->v_positions = parent->h_positions.as<uint32_t>();
-        }
+        if (want_pos && (h0 + w->n_hits) * 4 > parent->h_positions.cap) KMX_TRY(grow_positions(parent, tasks, h0, h0 + w->n_hits, q1));
         auto* part = new kmx_result();
-        parent->parts.push_back(part);
-        parent->part_q0.push_back(q1);
+        parent->parts.push_back(part); parent->part_q0.push_back(q1);
         part->host_chunk = true; part->host_valid = true; part->host_masks_valid = masks; part->quiesced = true;
         part->device = ix->device; part->flags = parent->flags; part->nq = cq;
-        part->n_hits = w->n_hits; part->n_exact = w->n_exact; part->n_stitch = w->n_stitch; part->n_prefix = w->n_prefix;
-        part->n_error = w->n_error; part->n_none = w->n_none; part->n_mask_words = w->n_mask_words;
-        parent->n_hits += part->n_hits; parent->n_exact += part->n_exact; parent->n_stitch += part->n_stitch; parent->n_prefix += part->n_prefix;
-        parent->n_error += part->n_error; parent->n_none += part->n_none;
-        if (w->small_valid) {                                // host to host, here and now
-            memcpy(parent->v_hit_off + q0 + 1, w->v_hit_off + 1, cq * 8);
-            memcpy(parent->v_status + q0, w->v_status, cq);
-            memcpy(parent->v_kinds + q0, w->v_kinds, cq);
-            if (want_pos && w->n_hits) memcpy(parent->v_positions + h0, w->v_positions, w->n_hits * 4);
-            if (h0)
-                for (uint64_t q = q0 + 1; q <= q1; ++q) parent->v_hit_off[q] += h0;
-            if (masks) {
-                auto masks_only = [&, turn, w, part, q0, cq] {
-                    // (masks only: reuse the copy task with nothing else left to move)
-                    CopyTask& t = tasks[turn];
-                    const uint64_t* mb = nullptr; const uint64_t* mw = nullptr; const uint32_t* cc = nullptr; const uint64_t* cs2 = nullptr;
-                    const kmx_status ms = kmx_result_masks(w, &mb, &mw, &cc, &cs2);
-                    if (ms != KMX_OK) { t.st = ms; t.err = g_err; return; }
-                    if (!part->h_mask_base.ensure_pageable((cq + 1) * 8) || !part->h_cand_count.ensure_pageable((cq + 1) * 4) ||
-                        !part->h_cand_src.ensure_pageable((cq + 1) * 8) || !part->h_mask_words.ensure_pageable((w->n_mask_words + 1) * 8)) {
-                        t.st = KMX_ERR_OUT_OF_MEMORY; t.err = "kmx_search_batch: host allocation for a chunk's masks failed"; return;
-                    }
-                    memcpy(part->h_mask_base.p, mb, cq * 8); memcpy(part->h_cand_count.p, cc, cq * 4); memcpy(part->h_cand_src.p, cs2, cq * 8);
-                    if (w->n_mask_words) memcpy(part->h_mask_words.p, mw, w->n_mask_words * 8);
-                    part->m_base = part->h_mask_base.as<uint64_t>(); part->m_words = part->h_mask_words.as<uint64_t>();
-                    part->m_ccnt = part->h_cand_count.as<uint32_t>(); part->m_csrc = part->h_cand_src.as<uint64_t>();
-                    (void)q0;
-                };
-                try {
-                    tasks[turn].th = std::thread(masks_only);
-                    tasks[turn].running = true;
-                } catch (const std::system_error&) {
-                    masks_only();
-                }
-            }
+        part->tally() = w->tally();
+        parent->tally() += part->tally();
+        if (w->small_valid) {                                // host to host, here and now; the masks alone are left for the copy task
+            append_part_host(parent, w, q0, cq, h0, want_pos);
+            rebase_part(parent, q0, q1, h0);
+            if (masks) start_task(t, [&t, w, part, cq] { copy_part_masks(t, w, part, cq); });
         } else {
-            try {
-                tasks[turn].th = std::thread(copy_out, turn, w, part, q0, cq, h0);
-                tasks[turn].running = true;
-            } catch (const std::system_error&) {                // no thread to be had: the copies run here, in line
-                copy_out(turn, w, part, q0, cq, h0);
-            }
+            start_task(t, [&copy_out, &t, w, part, q0, cq, h0] { copy_out(t, w, part, q0, cq, h0); });
         }
         h0 += w->n_hits;
         q0 = q1;
         if (!single_worker) turn ^= 1;                       // (one worker: its copy task is joined at the top of the loop before it is searched into again)
     }
-    const kmx_status fs = finish(KMX_OK);
-    if (fs != KMX_OK) return fs;
+    KMX_TRY(join_tasks(tasks, KMX_OK));
     parent->host_valid = true;                               // the merged views ARE the chunks' destination
     return KMX_OK;
 }
 
-kmx_status kmx_search_batch(const kmx_index* cix, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq,
-                            uint32_t flags, kmx_result** out)
+// Several replicas: replica r searches the contiguous range [nq*r/W, nq*(r+1)/W) on its own device and
+// stream; all of them are started before the first is waited for.  The parent result presents the parts as one.
+static kmx_status search_host_replicas(kmx_index* ix, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq, uint32_t flags, kmx_result** out)
 {
-    if (!cix || !out) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: NULL argument");
-    if (nq && !qoff) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: NULL query offsets");
-    if (nq && qoff[0] != 0) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: qoff[0] must be 0");
-    for (uint64_t i = 0; i < nq; ++i)
-        if (qoff[i + 1] < qoff[i]) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: qoff must be non-decreasing");
-    if (nq && !qranks && qoff[nq] != 0) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: NULL query letters");   // (a batch of empty queries has none)
-    kmx_index* ix = const_cast<kmx_index*>(cix);
-    if (ix->broken) return fail(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
     const size_t W = ix->n_replicas();
-    if (W == 1) {
-        if (*out && !(*out)->parts.empty() && !(*out)->chunked) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: the result handle belongs to a multi-device search");
-        uint64_t chunk_q = uint64_t(1) << 25;                   // queries per pass; KMX_HOST_CHUNK overrides (tests)
-        if (const char* e = getenv("KMX_HOST_CHUNK")) { const long long v = atoll(e); if (v > 0) chunk_q = uint64_t(v); }
-        if (nq > chunk_q || (*out && (*out)->chunked)) return search_host_chunked(ix, qranks, qoff, nq, flags, out, chunk_q);
-        const bool fresh = *out == nullptr;
-        kmx_status st = search_host_one(ix, qranks, qoff, 0, nq, flags, out, true);
-        if (st == KMX_ERR_OUT_OF_MEMORY && nq > 4096) {          // the batch does not fit the device in one pass: stream it
-            (void)hipGetLastError();
-            if (fresh && *out) { kmx_result_free(*out); *out = nullptr; }
-            return search_host_chunked(ix, qranks, qoff, nq, flags, out, std::max<uint64_t>(nq / 4, 1024));
-        }
-        return st;
-    }
-    // several replicas: replica r searches the contiguous range [nq*r/W, nq*(r+1)/W) on its own device and
-    // stream; all of them are started before the first is waited for.  The parent result presents the parts as one.
     int caller_device = 0;
     (void)hipGetDevice(&caller_device);
     kmx_result* parent = *out;
@@ -2333,10 +2353,7 @@ kmx_status kmx_search_batch(const kmx_index* cix, const uint8_t* qranks, const u
         if (!parent->parts.empty() || parent->device_bytes()) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: the result handle was made by a search of another shape");
     }
     if (!parent) { parent = new kmx_result(); *out = parent; }
-    parent->index = ix;
-    parent->device = ix->device;
-    parent->flags = flags & ~KMX_SEARCH_ASYNC;
-    parent->nq = nq;
+    parent->index = ix; parent->device = ix->device; parent->flags = flags & ~KMX_SEARCH_ASYNC; parent->nq = nq;
     parent->host_valid = parent->host_masks_valid = false;
     parent->parts.resize(W, nullptr);
     parent->part_q0.assign(W + 1, 0);
@@ -2364,16 +2381,40 @@ kmx_status kmx_search_batch(const kmx_index* cix, const uint8_t* qranks, const u
         for (size_t r = 0; r < W && st == KMX_OK; ++r)
             if (sts[r] != KMX_OK) st = fail(sts[r], msgs[r]);
     }
-    parent->n_hits = parent->n_exact = parent->n_stitch = parent->n_prefix = parent->n_error = parent->n_none = parent->n_mask_words = 0;
-    for (size_t r = 0; r < W; ++r) {
-        kmx_result* p = parent->parts[r];
+    parent->tally().reset();
+    for (kmx_result* p : parent->parts) {
         if (!p) continue;
         const kmx_status fs = search_finish(p);
         if (st == KMX_OK) st = fs;
-        parent->n_hits += p->n_hits; parent->n_exact += p->n_exact; parent->n_stitch += p->n_stitch; parent->n_prefix += p->n_prefix;
-        parent->n_error += p->n_error; parent->n_none += p->n_none;
+        parent->tally() += p->tally();
     }
     (void)hipSetDevice(caller_device);
+    return st;
+}
+
+kmx_status kmx_search_batch(const kmx_index* cix, const uint8_t* qranks, const uint64_t* qoff, uint64_t nq,
+                            uint32_t flags, kmx_result** out)
+{
+    if (!cix || !out) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: NULL argument");
+    if (nq && !qoff) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: NULL query offsets");
+    if (nq && qoff[0] != 0) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: qoff[0] must be 0");
+    for (uint64_t i = 0; i < nq; ++i)
+        if (qoff[i + 1] < qoff[i]) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: qoff must be non-decreasing");
+    if (nq && !qranks && qoff[nq] != 0) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: NULL query letters");   // (a batch of empty queries has none)
+    kmx_index* ix = const_cast<kmx_index*>(cix);
+    if (ix->broken) return fail(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    if (ix->n_replicas() > 1) return search_host_replicas(ix, qranks, qoff, nq, flags, out);
+    if (*out && !(*out)->parts.empty() && !(*out)->chunked) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: the result handle belongs to a multi-device search");
+    uint64_t chunk_q = uint64_t(1) << 25;                   // queries per pass; KMX_HOST_CHUNK overrides (tests)
+    if (const char* e = getenv("KMX_HOST_CHUNK")) { const long long v = atoll(e); if (v > 0) chunk_q = uint64_t(v); }
+    if (nq > chunk_q || (*out && (*out)->chunked)) return search_host_chunked(ix, qranks, qoff, nq, flags, out, chunk_q);
+    const bool fresh = *out == nullptr;
+    const kmx_status st = search_host_one(ix, qranks, qoff, 0, nq, flags, out, true);
+    if (st == KMX_ERR_OUT_OF_MEMORY && nq > 4096) {          // the batch does not fit the device in one pass: stream it
+        (void)hipGetLastError();
+        if (fresh && *out) { kmx_result_free(*out); *out = nullptr; }
+        return search_host_chunked(ix, qranks, qoff, nq, flags, out, std::max<uint64_t>(nq / 4, 1024));
+    }
     return st;
 }
 
@@ -2381,7 +2422,7 @@ kmx_status kmx_result_counts(const kmx_result* r, uint64_t* nq, uint64_t* n_hits
                              uint64_t* n_prefix, uint64_t* n_error)
 {
     if (!r) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_counts: result is NULL");
-    if (r->ctx.pending) { kmx_status fs = search_finish(const_cast<kmx_result*>(r)); if (fs != KMX_OK) return fs; }
+    KMX_TRY(search_finish(const_cast<kmx_result*>(r)));
     if (nq) *nq = r->nq;
     if (n_hits) *n_hits = r->n_hits;
     if (n_exact) *n_exact = r->n_exact;
@@ -2419,8 +2460,8 @@ kmx_status kmx_result_view_device(const kmx_result* r, const uint64_t** d_hit_of
     if (!r->parts.empty()) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_view_device: the result spans several devices: use kmx_result_part_view_device");
     if (r->host_chunk) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_view_device: the batch was streamed through the device in chunks: its result lives in host memory only");
     if (r->small_valid) {
-        // the last search ran on the latency path and left nothing in HBM: run the same queries (they are still in the
-        // mailbox) through the device form now
+        // the last search ran on the latency path and left nothing in HBM: run the same queries (try_small kept them in
+        // small_in: offsets, then letters) through the device form now
         kmx_result* rr = const_cast<kmx_result*>(r);
         {
             bool gone = !rr->pool;
@@ -2431,15 +2472,13 @@ kmx_status kmx_result_view_device(const kmx_result* r, const uint64_t** d_hit_of
         const unsigned char* mb = rr->small_in.as<unsigned char>();
         const uint64_t nq = rr->nq, n_letters = reinterpret_cast<const uint64_t*>(mb)[nq];
         HIP_TRY(hipSetDevice(rr->device));
-        HIP_TRY(rr->in_qranks.ensure(std::max<uint64_t>(n_letters, 1) + 16));
-        HIP_TRY(rr->in_qoff.ensure((nq + 1) * 8));
+        KMX_TRY(query_room(rr, n_letters, nq));
         HIP_TRY(hipMemcpyAsync(rr->in_qoff.p, mb, (nq + 1) * 8, hipMemcpyHostToDevice, rr->own_stream));
         if (n_letters) HIP_TRY(hipMemcpyAsync(rr->in_qranks.p, mb + (nq + 1) * 8, n_letters, hipMemcpyHostToDevice, rr->own_stream));
         kmx_result* self = rr;
-        const kmx_status st = kmx_search_batch_device(ix, rr->in_qranks.p, rr->in_qoff.p, nq, rr->flags, rr->own_stream, &self);
-        if (st != KMX_OK) return st;
+        KMX_TRY(kmx_search_batch_device(ix, rr->in_qranks.p, rr->in_qoff.p, nq, rr->flags, rr->own_stream, &self));
     }
-    if (r->ctx.pending) { kmx_status fs = search_finish(const_cast<kmx_result*>(r)); if (fs != KMX_OK) return fs; }
+    KMX_TRY(search_finish(const_cast<kmx_result*>(r)));
     if (d_hit_off) *d_hit_off = r->hit_off.as<uint64_t>();
     if (d_positions) *d_positions = r->out.as<uint32_t>();
     if (d_status) *d_status = r->status.as<uint8_t>();
@@ -2455,7 +2494,7 @@ kmx_status kmx_result_gather_device(kmx_result* r, int32_t dst_device, const uin
     int n_dev = 0;
     HIP_TRY(hipGetDeviceCount(&n_dev));
     if (dst_device < 0 || dst_device >= n_dev) return fail(KMX_ERR_NO_DEVICE, "kmx_result_gather_device: no such device");
-    if (r->ctx.pending) { kmx_status fs = search_finish(r); if (fs != KMX_OK) return fs; }
+    KMX_TRY(search_finish(r));
     if (r->parts.empty() && r->device == dst_device) return kmx_result_view_device(r, d_hit_off, d_positions, d_status);   // already there
     int caller_device = 0;
     (void)hipGetDevice(&caller_device);
@@ -2480,10 +2519,7 @@ kmx_status kmx_result_gather_device(kmx_result* r, int32_t dst_device, const uin
     hipError_t e = hipSetDevice(dst_device);
     if (e == hipSuccess && r->gather_device >= 0 && r->gather_device != dst_device) {
         // (buffers of an earlier gather to another device)
-        (void)hipSetDevice(r->gather_device);
-        r->g_hit_off.release(); r->g_out.release(); r->g_status.release();
-        if (r->gather_stream) (void)hipStreamDestroy(r->gather_stream);
-        r->gather_stream = nullptr;
+        r->release_gather();
         e = hipSetDevice(dst_device);
     }
     r->gather_device = dst_device;
@@ -2531,19 +2567,14 @@ kmx_status kmx_result_view(kmx_result* r, const uint64_t** hit_off, const uint32
                            const uint8_t** kinds)
 {
     if (!r) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_view: result is NULL");
-    if (r->ctx.pending) { kmx_status fs = search_finish(r); if (fs != KMX_OK) return fs; }
+    KMX_TRY(search_finish(r));
+    const bool have_pos = !(r->flags & KMX_SEARCH_COUNT_ONLY) && r->n_hits;
+    const size_t b_off = (r->nq + 1) * 8, b_pos = have_pos ? r->n_hits * 4 : 0, b_st = r->nq;
     if ((!r->parts.empty() || r->chunked) && !r->host_valid) {
         // the parts of a multi-device result, concatenated in replica order: every device copies straight into its slice
         // of the one host buffer (all links at once), the offsets are rebased on the host
-        const bool have_pos = !(r->flags & KMX_SEARCH_COUNT_ONLY) && r->n_hits;
         // (a chunk-streamed batch never gets here: its chunks were copied into the parent's views as they were searched)
-        if (!r->h_hit_off.ensure((r->nq + 1) * 8) || !r->h_status.ensure(std::max<uint64_t>(r->nq, 1)) ||
-            !r->h_kinds.ensure(std::max<uint64_t>(r->nq, 1)) || !r->h_positions.ensure(std::max<uint64_t>(have_pos ? r->n_hits * 4 : 0, 4)))
-            return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_result_view: host allocation failed");
-        r->v_hit_off = r->h_hit_off.as<uint64_t>();
-        r->v_positions = r->h_positions.as<uint32_t>();
-        r->v_status = r->h_status.as<uint8_t>();
-        r->v_kinds = r->h_kinds.as<uint8_t>();
+        if (!r->size_views(b_pos)) return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_result_view: host allocation failed");
         int caller_device = 0;
         (void)hipGetDevice(&caller_device);
         uint64_t h0 = 0;
@@ -2552,20 +2583,8 @@ kmx_status kmx_result_view(kmx_result* r, const uint64_t** hit_off, const uint32
             kmx_result* p = r->parts[i];
             const uint64_t q0 = r->part_q0[i], nqp = r->part_q0[i + 1] - q0;
             HIP_TRY(hipSetDevice(p->device));
-            if (p->small_valid) {                                   // the part's result already is on the host
-                memcpy(r->v_hit_off + q0 + 1, p->v_hit_off + 1, nqp * 8);
-                memcpy(r->v_status + q0, p->v_status, nqp);
-                memcpy(r->v_kinds + q0, p->v_kinds, nqp);
-                if (have_pos && p->n_hits) memcpy(r->v_positions + h0, p->v_positions, p->n_hits * 4);
-                h0 += p->n_hits;
-                continue;
-            }
-            if (nqp) {
-                HIP_TRY(hipMemcpyAsync(r->v_hit_off + q0 + 1, p->hit_off.as<uint64_t>() + 1, nqp * 8, hipMemcpyDeviceToHost, p->stream));
-                HIP_TRY(hipMemcpyAsync(r->v_status + q0, p->status.p, nqp, hipMemcpyDeviceToHost, p->stream));
-                HIP_TRY(hipMemcpyAsync(r->v_kinds + q0, p->kind.p, nqp, hipMemcpyDeviceToHost, p->stream));
-            }
-            if (have_pos && p->n_hits) HIP_TRY(hipMemcpyAsync(r->v_positions + h0, p->out.p, p->n_hits * 4, hipMemcpyDeviceToHost, p->stream));
+            if (p->small_valid) append_part_host(r, p, q0, nqp, h0, have_pos);   // the part's result already is on the host
+            else HIP_TRY(append_part_async(r, p, q0, nqp, h0, have_pos));
             h0 += p->n_hits;
         }
         h0 = 0;
@@ -2574,8 +2593,7 @@ kmx_status kmx_result_view(kmx_result* r, const uint64_t** hit_off, const uint32
             HIP_TRY(hipSetDevice(p->device));
             if (!p->small_valid && r->part_q0[i + 1] > r->part_q0[i]) HIP_TRY(hipStreamSynchronize(p->stream));
             p->quiesced = true;
-            if (h0)
-                for (uint64_t q = r->part_q0[i] + 1; q <= r->part_q0[i + 1]; ++q) r->v_hit_off[q] += h0;
+            rebase_part(r, r->part_q0[i], r->part_q0[i + 1], h0);
             h0 += p->n_hits;
         }
         (void)hipSetDevice(caller_device);
@@ -2583,44 +2601,34 @@ kmx_status kmx_result_view(kmx_result* r, const uint64_t** hit_off, const uint32
     }
     if (!r->host_valid) {
         HIP_TRY(hipSetDevice(r->device));
-        const bool have_pos = !(r->flags & KMX_SEARCH_COUNT_ONLY) && r->n_hits;
-        const size_t b_off = (r->nq + 1) * 8, b_pos = have_pos ? r->n_hits * 4 : 0, b_st = r->nq;
         const size_t small_total = b_off + ((b_pos + 7) & ~size_t(7)) + 2 * ((b_st + 7) & ~size_t(7));
-        if (small_total <= kSmallView && r->h_small.ensure_pinned(kSmallView)) {
-            // small result: the four arrays share one page-locked block, four async copies, one wait
+        // small result: the four arrays share one page-locked block, four async copies, one wait; any other: a wait, plain copies
+        const bool one_block = small_total <= kSmallView && r->h_small.ensure_pinned(kSmallView);
+        if (one_block) {
             char* base = r->h_small.as<char>();
             r->v_hit_off = reinterpret_cast<uint64_t*>(base);
             r->v_positions = reinterpret_cast<uint32_t*>(base + b_off);
             r->v_status = reinterpret_cast<uint8_t*>(base + b_off + ((b_pos + 7) & ~size_t(7)));
             r->v_kinds = r->v_status + ((b_st + 7) & ~size_t(7));
-            HIP_TRY(hipMemcpyAsync(r->v_hit_off, r->hit_off.p, b_off, hipMemcpyDeviceToHost, r->stream));
-            if (r->nq) {
-                HIP_TRY(hipMemcpyAsync(r->v_status, r->status.p, r->nq, hipMemcpyDeviceToHost, r->stream));
-                HIP_TRY(hipMemcpyAsync(r->v_kinds, r->kind.p, r->nq, hipMemcpyDeviceToHost, r->stream));
-            }
-            if (have_pos) HIP_TRY(hipMemcpyAsync(r->v_positions, r->out.p, b_pos, hipMemcpyDeviceToHost, r->stream));
-            HIP_TRY(hipStreamSynchronize(r->stream));
         } else {
             HIP_TRY(hipStreamSynchronize(r->stream));
-            if (!r->h_hit_off.ensure(b_off) || !r->h_status.ensure(std::max<uint64_t>(r->nq, 1)) ||
-                !r->h_kinds.ensure(std::max<uint64_t>(r->nq, 1)) || !r->h_positions.ensure(std::max<uint64_t>(b_pos, 4)))
-                return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_result_view: host allocation failed");
-            r->v_hit_off = r->h_hit_off.as<uint64_t>();
-            r->v_positions = r->h_positions.as<uint32_t>();
-            r->v_status = r->h_status.as<uint8_t>();
-            r->v_kinds = r->h_kinds.as<uint8_t>();
-            HIP_TRY(hipMemcpy(r->v_hit_off, r->hit_off.p, b_off, hipMemcpyDeviceToHost));
-            if (r->nq) {
-                HIP_TRY(hipMemcpy(r->v_status, r->status.p, r->nq, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(r->v_kinds, r->kind.p, r->nq, hipMemcpyDeviceToHost));
-            }
-            if (have_pos) HIP_TRY(hipMemcpy(r->v_positions, r->out.p, b_pos, hipMemcpyDeviceToHost));
+            if (!r->size_views(b_pos)) return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_result_view: host allocation failed");
         }
+        auto down = [&](void* dst, const void* src, size_t bytes) {
+            return one_block ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, r->stream) : hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+        };
+        HIP_TRY(down(r->v_hit_off, r->hit_off.p, b_off));
+        if (r->nq) {
+            HIP_TRY(down(r->v_status, r->status.p, r->nq));
+            HIP_TRY(down(r->v_kinds, r->kind.p, r->nq));
+        }
+        if (have_pos) HIP_TRY(down(r->v_positions, r->out.p, b_pos));
+        if (one_block) HIP_TRY(hipStreamSynchronize(r->stream));
         r->quiesced = true;
         r->host_valid = true;
     }
     if (hit_off) *hit_off = r->v_hit_off;
-    if (positions) *positions = ((r->flags & KMX_SEARCH_COUNT_ONLY) || !r->n_hits) ? nullptr : r->v_positions;
+    if (positions) *positions = have_pos ? r->v_positions : nullptr;
     if (status) *status = r->v_status;
     if (kinds) *kinds = r->v_kinds;
     return KMX_OK;
@@ -2630,7 +2638,7 @@ kmx_status kmx_result_masks(kmx_result* r, const uint64_t** mask_base, const uin
                             const uint32_t** cand_count, const uint64_t** cand_src)
 {
     if (!r) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_masks: result is NULL");
-    if (r->ctx.pending) { kmx_status fs = search_finish(r); if (fs != KMX_OK) return fs; }
+    KMX_TRY(search_finish(r));
     if (!(r->flags & KMX_SEARCH_KEEP_MASKS)) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_result_masks: search ran without KMX_SEARCH_KEEP_MASKS");
     if ((!r->parts.empty() || r->chunked) && !r->host_masks_valid) {
         // per-part mask views, concatenated; a part's mask_base counts from its own first word, cand_src is an arena
@@ -2639,10 +2647,7 @@ kmx_status kmx_result_masks(kmx_result* r, const uint64_t** mask_base, const uin
         r->part_w0.assign(r->parts.size() + 1, 0);
         for (size_t i = 0; i < r->parts.size(); ++i) { n_words += r->parts[i]->n_mask_words; r->part_w0[i + 1] = n_words; }
         r->n_mask_words = n_words;
-        const uint64_t nq1 = std::max<uint64_t>(r->nq, 1);
-        if (!r->h_mask_base.ensure(nq1 * 8) || !r->h_cand_count.ensure(nq1 * 4) || !r->h_cand_src.ensure(nq1 * 8) ||
-            !r->h_mask_words.ensure(std::max<uint64_t>(n_words, 1) * 8))
-            return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_result_masks: host allocation failed");
+        if (!r->size_mask_buffers()) return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_result_masks: host allocation failed");
         int caller_device = 0;
         (void)hipGetDevice(&caller_device);
         for (size_t i = 0; i < r->parts.size(); ++i) {
@@ -2660,10 +2665,7 @@ kmx_status kmx_result_masks(kmx_result* r, const uint64_t** mask_base, const uin
     if (!r->host_masks_valid) {
         HIP_TRY(hipSetDevice(r->device));
         HIP_TRY(hipStreamSynchronize(r->stream));
-        const uint64_t nq1 = std::max<uint64_t>(r->nq, 1);
-        if (!r->h_mask_base.ensure(nq1 * 8) || !r->h_cand_count.ensure(nq1 * 4) || !r->h_cand_src.ensure(nq1 * 8) ||
-            !r->h_mask_words.ensure(std::max<uint64_t>(r->n_mask_words, 1) * 8))
-            return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_result_masks: host allocation failed");
+        if (!r->size_mask_buffers()) return fail(KMX_ERR_OUT_OF_MEMORY, "kmx_result_masks: host allocation failed");
         if (r->nq) {
             HIP_TRY(hipMemcpy(r->h_mask_base.p, r->aux.p, r->nq * 8, hipMemcpyDeviceToHost));
             HIP_TRY(hipMemcpy(r->h_cand_count.p, r->c0.p, r->nq * 4, hipMemcpyDeviceToHost));
@@ -2673,10 +2675,7 @@ kmx_status kmx_result_masks(kmx_result* r, const uint64_t** mask_base, const uin
         if (r->n_mask_words) HIP_TRY(hipMemcpy(r->h_mask_words.p, r->mask_words.p, r->n_mask_words * 8, hipMemcpyDeviceToHost));
         r->host_masks_valid = true;
     }
-    if (!r->small_valid) {
-        r->m_base = r->h_mask_base.as<uint64_t>(); r->m_words = r->h_mask_words.as<uint64_t>();
-        r->m_ccnt = r->h_cand_count.as<uint32_t>(); r->m_csrc = r->h_cand_src.as<uint64_t>();
-    }
+    if (!r->small_valid) r->mask_view_own();                    // (a latency-path result: its mask views are the mailbox)
     if (mask_base) *mask_base = r->m_base;
     if (mask_words) *mask_words = r->m_words;
     if (cand_count) *cand_count = r->m_ccnt;
@@ -2697,7 +2696,7 @@ void kmx_result_free(kmx_result* r)
         delete r;
         return;
     }
-    if (r->ctx.pending) (void)search_finish(r);
+    (void)search_finish(r);
     if (r->pool && r->device_bytes() <= kPoolMaxBytes) {
         if (!r->quiesced) {                                  // its buffers are about to serve another stream
             (void)hipSetDevice(r->device);

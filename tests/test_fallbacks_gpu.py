@@ -93,6 +93,80 @@ def test_chunked_search_survives_an_out_of_memory_with_one_worker():
     assert outs[0] == outs[1] == outs[2], outs           # same number of chunks (no halving), same hits
 
 
+PARTS_CHILD = r"""
+import ctypes as C
+import os
+import sys
+sys.path.insert(0, %(root)r)
+import numpy as np
+from kmer_index_amd import engine, synth
+from tests.helpers import make_queries
+
+text = synth.ranks(1003, 400_000, 4)
+idx = engine.Index(text, 4, [8, 10, 12])
+q, off = make_queries(text, 4, [3, 6, 8, 9, 10, 12, 13, 20, 22, 24, 31, 36], 400, seed=17)
+nq = off.size - 1
+# make_queries groups the queries by length, and a chunk is for the one-launch path only with at most 40 queries per 256 whose
+# length is none of the ks: as they come, no chunk of 1000 is.  The same 4800 queries, reordered: the first chunk holds 232
+# queries of 8, 10 or 12 letters and 24 of 20, 22 or 24 (STITCH: their masks leave through the mailbox) in every 256.
+lens = np.diff(off.astype(np.int64))
+fast = np.flatnonzero(np.isin(lens, [8, 10, 12]))
+slow = np.flatnonzero(np.isin(lens, [20, 22, 24]))[::11]
+head = np.array([(slow[i // 256 * 24 + i %% 256 - 232] if i %% 256 >= 232 else fast[i // 256 * 232 + i %% 256]) for i in range(1000)])
+order = np.concatenate([head, np.setdiff1d(np.arange(nq), head)])
+assert np.array_equal(np.sort(order), np.arange(nq))
+q = np.concatenate([q[int(off[i]):int(off[i + 1])] for i in order])
+off = np.concatenate([[0], np.cumsum(lens[order])]).astype(np.uint64)
+
+def everything(res):
+    counts = res.counts()
+    ho, pos, st, kd = res.host()
+    base, words_ptr, cand_cnt, cand_src = res.masks()
+    stitch = np.flatnonzero(kd == engine.KIND_STITCH)
+    words = []
+    for i in stitch:                                     # EVERY stitch query: its mask words (mask_base itself counts chunk by chunk)
+        nw = int(cand_cnt[i]) // 64 + 1
+        words.append(np.ctypeslib.as_array(C.cast(words_ptr, C.POINTER(C.c_uint64)), shape=(int(base[i]) + nw,))[int(base[i]):].copy())
+    return counts, ho, pos, st, kd, stitch, cand_cnt[stitch], cand_src[stitch], words
+
+one = idx.search(q, off, flags=engine.SEARCH_KEEP_MASKS)     # one pass: KMX_HOST_CHUNK is read by every call, and not set yet
+assert one.n_parts() == 1
+want = everything(one)
+os.environ["KMX_HOST_CHUNK"] = "1000"
+idx.stats_enable(True)
+res = idx.search(q, off, flags=engine.SEARCH_KEEP_MASKS)
+assert res.n_parts() == 5, res.n_parts()
+got = everything(res)
+n_small, n_lookup = idx.stats()["k_small"]["launches"], idx.stats()["k_lookup"]["launches"]
+assert got[0] == want[0], (got[0], want[0])
+for name, g, w in zip(("hit_off", "positions", "status", "kinds", "stitch", "cand_count", "cand_src"), got[1:8], want[1:8]):
+    assert np.array_equal(g, w), name
+assert len(got[8]) == len(want[8]) == want[5].size and want[5].size > 0
+for i, g, w in zip(want[5], got[8], want[8]):
+    assert np.array_equal(g, w), ("mask words", int(i))
+print("parts child ok", n_small, n_lookup, want[5].size, want[0]["n_hits"])
+"""
+
+
+@pytest.mark.gpu
+def test_chunked_search_with_masks_equals_the_one_pass_search():
+    """A chunk-streamed KEEP_MASKS batch (KMX_HOST_CHUNK=1000, five chunks) presents, through the parent's merged views, what
+    the one-pass search of the same child does: counts, the four host arrays and, for every STITCH query, cand_count, cand_src
+    and the mask words.  Child A: the first chunk is served by the one-launch latency path (host-to-host part copy, the masks
+    alone on the copy task): k_small ran and k_lookup for four chunks only.  Child B: KMX_NO_SMALL as well, so every chunk
+    takes the device path and leaves through the copy task: no k_small, five k_lookup."""
+    for no_small in (False, True):
+        e = dict(os.environ)
+        e.pop("KMX_HOST_CHUNK", None)
+        if no_small:
+            e["KMX_NO_SMALL"] = "1"
+        res = subprocess.run([sys.executable, "-c", PARTS_CHILD % {"root": ROOT}], capture_output=True, text=True, timeout=600, env=e)
+        assert res.returncode == 0 and "parts child ok" in res.stdout, res.stdout[-2000:] + res.stderr[-4000:]
+        n_small, n_lookup = (int(v) for v in res.stdout.strip().splitlines()[-1].split()[3:5])
+        print(res.stdout.strip().splitlines()[-1])
+        assert (n_small, n_lookup) == ((0, 5) if no_small else (1, 4)), (no_small, n_small, n_lookup)
+
+
 SUBK_CHILD = r"""
 import sys
 sys.path.insert(0, %(root)r)

@@ -540,6 +540,63 @@ kmx_status kmx_search_windows_device(const kmx_index* index, const void* d_ranks
                                      const kmx_window_options* options, void* stream, kmx_result** inout);
 kmx_status kmx_result_window_offsets(kmx_result* r, const uint64_t** win_off, const uint64_t** d_win_off, uint64_t* nr);
 
+/* ---- seed voting: the candidate loci of every read, from the hit lists of a windows search (an extension, no reference
+ *      interface; a caller detects the capability by the macro KMX_WINDOWS_VOTE, KMX_VERSION is unchanged).  What a read mapper,
+ *      containment and classification want of kmx_search_windows is not every hit but the places in the text where many windows
+ *      of a read agree: the diagonals p - o (text offset minus window offset in the read) that collect votes.  The reduction from
+ *      hits to loci runs on the device, on the hit lists where they lie; a few dozen bytes per read cross to the host.
+ *
+ *      `windows` is the result of the last kmx_search_windows or kmx_search_windows_device into that handle (the handle remembers
+ *      that search's w and stride).  For read r with windows j = 0 .. c_r - 1 at read offsets o = j * stride:
+ *        - a window VOTES if its status is KMX_Q_OK, it has at least one hit and (max_occ == 0 or its hit count <= max_occ); a
+ *          window with hits that fails the max_occ test is counted in skipped[r]; windows without hits and KMX_Q_BAD_RANK windows
+ *          (they have no hits) are neither voting nor skipped;
+ *        - every hit p of a voting window is one vote on the diagonal D = (int64)p - o.  D is negative when the read would overhang
+ *          the start of the text, and D + len_r > n when it overhangs the end: both are reported, never clamped;
+ *        - the read's votes are sorted by D; a LOCUS is a maximal run in which each D is at most `band` above the one before it.  It
+ *          has diag = its smallest D, span = largest - smallest D (saturated at 2^32 - 1, which only a read of about 2^32 letters
+ *          can reach) and votes = the number of votes in it;
+ *        - the loci with votes >= min_votes are reported per read in ascending diag: locus_off[nr + 1] is the exclusive prefix sum
+ *          of the per-read counts, diag[n_loci] (int64), span[n_loci], votes[n_loci], skipped[nr];
+ *        - n_votes is the number of votes cast over the batch; n_small / n_large count the reads by the code path that served
+ *          them (a read whose votes fit one workgroup's LDS and whose diagonals fit 32 bits is small; KMX_VOTE_SMALL_CAP in the
+ *          environment, read at every call, lowers the cap on the votes, 0 sends every read to the large class); reads that cast
+ *          no vote are in neither.  Results never depend on the class.
+ *      tests/vote_naive.py is this contract in executable form.
+ *
+ *      The call runs on the stream of the windows search: the result's own for the host form, the caller's for the device form.
+ *      It only reads the result: the views of `windows` are unchanged afterwards and it can be voted on again with other options.
+ *      The loci handle owns its buffers, so the result may be searched into again as soon as the call returns.  *inout == NULL
+ *      allocates; a handle from an earlier call is reused and its earlier views end.  The device arrays (kmx_loci_view_device;
+ *      diag / span / votes are NULL when there is no locus) are complete in stream order when the call returns; kmx_loci_view
+ *      copies to page-locked host memory on first use and synchronises.  The votes of over-frequent windows are never
+ *      materialised.  The kernel statistics (k_vote) are collected while the index of the search exists.
+ *
+ *      Refused with KMX_ERR_INVALID_ARGUMENT before the result handle is looked at: a NULL windows, options or inout, a
+ *      struct_size that is too small, flags != 0, min_votes == 0.  Refused after looking at the handle: a result that is not
+ *      from a windows call or has been searched into by an ordinary search since, a KMX_SEARCH_COUNT_ONLY result (it has no
+ *      positions), a result of several parts.  KMX_ERR_TOO_LARGE: a read with 2^32 or more votes, 2^31 or more reads, a read
+ *      number and diagonal that do not fit a 64-bit sort key together.  KMX_ERR_OUT_OF_MEMORY when the buffers do not fit: the
+ *      caller splits the reads, as for kmx_search_windows.  After a refusal or an error the loci handle, when there is one,
+ *      holds an empty result.  The accessors refuse a NULL handle; any of their output pointers may be NULL. */
+#define KMX_WINDOWS_VOTE 1
+typedef struct kmx_vote_options {
+    uint32_t struct_size;  /* = sizeof(kmx_vote_options) */
+    uint32_t band;         /* diagonals at most this far from their sorted neighbour join one locus; 0 = exact diagonals */
+    uint32_t min_votes;    /* >= 1: loci with fewer votes are not reported */
+    uint32_t max_occ;      /* 0 = none; else a window with more than this many hits casts no vote (repeat filter) */
+    uint32_t flags;        /* 0 */
+} kmx_vote_options;
+typedef struct kmx_loci kmx_loci;
+kmx_status kmx_windows_vote(kmx_result* windows, const kmx_vote_options* options, kmx_loci** inout);
+kmx_status kmx_loci_counts(const kmx_loci* l, uint64_t* nr, uint64_t* n_loci, uint64_t* n_votes,
+                           uint64_t* n_small, uint64_t* n_large);
+kmx_status kmx_loci_view(kmx_loci* l, const uint64_t** locus_off, const int64_t** diag, const uint32_t** span,
+                         const uint32_t** votes, const uint32_t** skipped);
+kmx_status kmx_loci_view_device(const kmx_loci* l, const uint64_t** d_locus_off, const int64_t** d_diag,
+                                const uint32_t** d_span, const uint32_t** d_votes, const uint32_t** d_skipped);
+void kmx_loci_free(kmx_loci* l);
+
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.
  * Works on built, loaded and replicated indexes (this replica).  The first call derives a copy packed at 2, 4 or 8 bits per

@@ -44,46 +44,8 @@ inline uint32_t bits_per_letter(uint32_t sigma) { return sigma <= 4 ? 2u : sigma
         }                                                                                              \
     } while (0)
 
-// grow-only device buffer, released with its owner
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return e; }
-        cap = want;
-        return hipSuccess;
-    }
-    ~Buf() { if (p) (void)hipFree(p); }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-
-// page-locked host array that keeps its contents when it grows; freed with its owner
-struct PinnedArr {
-    void* p = nullptr;
-    size_t cap = 0;
-    PinnedArr() = default;
-    PinnedArr(const PinnedArr&) = delete;
-    PinnedArr& operator=(const PinnedArr&) = delete;
-    ~PinnedArr() { release(); }
-    bool grow(size_t bytes)
-    {
-        if (bytes <= cap) return true;
-        const size_t want = std::max(bytes, cap * 2) + 64;
-        void* q = nullptr;
-        if (hipHostMalloc(&q, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return false; }
-        if (p) { std::memcpy(q, p, cap); (void)hipHostFree(p); }
-        p = q; cap = want;
-        return true;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
+using kmx::Buf;
+using kmx::PinnedArr;
 
 inline unsigned int grid_for(uint64_t n, uint64_t per_block) { return unsigned(std::max<uint64_t>((n + per_block - 1) / per_block, 1)); }
 

@@ -22,6 +22,7 @@
 #include "kmx_approx.h"
 #include "kmx_host.h"
 #include "kmx_kernels.h"
+#include "kmx_vote.h"
 
 namespace {
 
@@ -116,12 +117,12 @@ struct HostBuf {
 
 enum KernelId {
     K_LOOKUP = 0, K_SCAN, K_PARTITION, K_FILL, K_VALIDATE, K_COMPACT, K_PREFIX_LEN, K_MERGE_PASS,
-    K_PREFIX_SORT_SMALL, K_PREFIX_MERGE_SMALL, K_PREFIX_SORT_BLOCK, K_SMALL, K_PREFIX_BANDS, K_PREFIX_SPLIT, K_LOOKUP_WINDOWS, K_COUNT
+    K_PREFIX_SORT_SMALL, K_PREFIX_MERGE_SMALL, K_PREFIX_SORT_BLOCK, K_SMALL, K_PREFIX_BANDS, K_PREFIX_SPLIT, K_LOOKUP_WINDOWS, K_VOTE, K_COUNT
 };
 static_assert(K_COUNT <= KMX_N_KERNELS, "kmx_stats_get fills a caller's array of KMX_N_KERNELS entries");
 const char* const kKernelNames[K_COUNT] = {
     "k_lookup", "k_scan", "k_partition", "k_fill", "k_validate", "k_compact",
-    "k_prefix_len", "k_prefix_merge_pass", "k_prefix_sort_small", "k_prefix_merge_small", "k_prefix_sort_block", "k_small", "k_prefix_bands", "k_prefix_split", "k_lookup_windows"};
+    "k_prefix_len", "k_prefix_merge_pass", "k_prefix_sort_small", "k_prefix_merge_small", "k_prefix_sort_block", "k_small", "k_prefix_bands", "k_prefix_split", "k_lookup_windows", "k_vote"};
 
 struct Stats {
     bool enabled = false;
@@ -262,8 +263,10 @@ struct kmx_result : Tallies {
     bool host_valid = false, host_masks_valid = false;
     // kmx_search_windows: the last search was one over the windows of win_nr reads — win_cnt (u32 per read) and win_off
     // (win_nr + 1 window offsets, kmx_result_window_offsets) on the device, h_win_off their host copy once asked for
+    // win_w / win_stride: that search's window length and stride, win_n: the text length of its index (kmx_windows_vote)
     bool windows = false, h_win_valid = false;
-    uint64_t win_nr = 0;
+    uint64_t win_nr = 0, win_n = 0;
+    uint32_t win_w = 0, win_stride = 0;
     HostBuf h_win_off;
     bool last_had_stitch = false;          // adaptive speculation: see kmx_search_batch_device
     bool last_had_long = false;            // ... or queries of very many parts (k_lookup_long)
@@ -1687,6 +1690,7 @@ static kmx_status windows_device(const kmx_index* cix, const void* d_ranks, cons
     (void)hipGetLastError();
     r->windows = true;
     r->win_nr = nr;
+    r->win_w = o->w; r->win_stride = o->stride; r->win_n = ix->n;
     r->h_win_valid = false;
     HIP_TRY(r->win_off.ensure((nr + 1) * 8));
     uint64_t nq = 0;
@@ -2956,4 +2960,27 @@ kmx_status kmx::set_error(kmx_status st, const std::string& msg) { return fail(s
 void kmx::result_quiesced(kmx_result* r)
 {
     if (r && !r->ctx.pending) r->quiesced = true;
+}
+
+// ---- what kmx_vote.hip needs from the result of a windows search (kmx_vote.h) ----
+kmx_status kmx::windows_access(kmx_result* r, kmx::WindowsAccess* out)
+{
+    KMX_TRY(search_finish(r));
+    if (!r->parts.empty() || r->chunked || r->host_chunk)
+        return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_windows_vote: the result has several parts");
+    if (!r->windows || r->small_valid)
+        return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_windows_vote: the result is not one of kmx_search_windows / kmx_search_windows_device (or has been searched into since)");
+    if (r->flags & KMX_SEARCH_COUNT_ONLY)
+        return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_windows_vote: a KMX_SEARCH_COUNT_ONLY result has no positions to vote with");
+    bool gone = !r->pool;                                     // stats live in the index: none once it has been freed
+    if (r->pool) { std::lock_guard<std::mutex> lock(r->pool->mu); gone = r->pool->closed; }
+    *out = kmx::WindowsAccess{r->device, r->stream, gone ? nullptr : r->index, r->win_nr, r->nq, r->n_hits, r->win_n, r->win_w, r->win_stride,
+                              r->win_off.as<uint64_t>(), r->hit_off.as<uint64_t>(), r->out.as<uint32_t>()};
+    return KMX_OK;
+}
+
+void kmx::vote_timed(const kmx_index* ix, hipStream_t s, const std::function<void()>& launch)
+{
+    if (!ix) { launch(); return; }
+    timed(const_cast<kmx_index*>(ix), K_VOTE, s, launch);
 }

@@ -1,0 +1,30 @@
+// What seed voting (kmx_vote.hip) needs from the result of a windows search (kmx_capi.hip owns struct kmx_result).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <functional>
+
+#include "kmx_approx.h"   // set_error
+
+namespace kmx {
+
+// The last search into a result, when it was a windows search with positions on one device (all pointers are device pointers
+// that belong to the result and stay as they are: voting only reads them).
+struct WindowsAccess {
+    int device;
+    hipStream_t stream;            // the stream of that search: the result's own (host form) or the caller's (device form)
+    const kmx_index* index;        // for the kernel statistics only; nullptr once the index has been freed
+    uint64_t nr, nq, n_hits;       // reads, windows, hits
+    uint64_t n;                    // text length of the index that was searched
+    uint32_t w, stride;
+    const uint64_t* win_off;       // [nr + 1]
+    const uint64_t* hit_off;       // [nq + 1]
+    const uint32_t* positions;     // [n_hits]
+};
+// kmx_capi.hip: completes a pending search; the refusals "after looking at the handle" of kmx_windows_vote
+kmx_status windows_access(kmx_result* r, WindowsAccess* out);
+// kmx_capi.hip: launch() timed under the name k_vote when the index collects statistics
+void vote_timed(const kmx_index* ix, hipStream_t s, const std::function<void()>& launch);
+
+} // namespace kmx

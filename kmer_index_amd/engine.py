@@ -35,6 +35,7 @@ EXPORTS = [
     "kmx_search_approx_opts", "kmx_approx_found",
     "kmx_index_paths", "kmx_result_paths",
     "kmx_search_windows", "kmx_search_windows_device", "kmx_result_window_offsets",
+    "kmx_windows_vote", "kmx_loci_counts", "kmx_loci_view", "kmx_loci_view_device", "kmx_loci_free",
 ]
 
 
@@ -58,6 +59,10 @@ class ApproxOptions(C.Structure):
 
 class WindowOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("w", C.c_uint32), ("stride", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class VoteOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("band", C.c_uint32), ("min_votes", C.c_uint32), ("max_occ", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class KernelStat(C.Structure):
@@ -172,6 +177,15 @@ def lib():
         L.kmx_search_windows_device.argtypes = [vp, vp, vp, u64, P(WindowOptions), vp, P(vp)]
         L.kmx_result_window_offsets.restype = C.c_int
         L.kmx_result_window_offsets.argtypes = [vp, P(vp), P(vp), P(u64)]
+        L.kmx_windows_vote.restype = C.c_int
+        L.kmx_windows_vote.argtypes = [vp, P(VoteOptions), P(vp)]
+        L.kmx_loci_counts.restype = C.c_int
+        L.kmx_loci_counts.argtypes = [vp, P(u64), P(u64), P(u64), P(u64), P(u64)]
+        L.kmx_loci_view.restype = C.c_int
+        L.kmx_loci_view.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]
+        L.kmx_loci_view_device.restype = C.c_int
+        L.kmx_loci_view_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]
+        L.kmx_loci_free.argtypes = [vp]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -341,6 +355,13 @@ class Result:
         win_off = _view(a.value, n.value + 1, np.uint64).copy()
         return (win_off, b.value, int(n.value)) if device else win_off
 
+    def vote(self, band=0, min_votes=1, max_occ=0, loci=None):
+        """kmx_windows_vote on the result of a windows search: the candidate loci of every read (a Loci; `loci` reuses one)."""
+        l = loci or Loci()
+        o = VoteOptions(C.sizeof(VoteOptions), int(band), int(min_votes), int(max_occ), 0)
+        _check(lib().kmx_windows_vote(self._h, C.byref(o), C.byref(l._h)))
+        return l
+
     def masks(self):
         c = self.counts()
         a, b, cc, d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -356,6 +377,45 @@ class Result:
             lib().kmx_result_free(self._h)
             self._h = C.c_void_p()
         self._index = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Loci:
+    """Owns a kmx_loci handle (kmx_windows_vote)."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+
+    def counts(self):
+        v = [C.c_uint64() for _ in range(5)]
+        _check(lib().kmx_loci_counts(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(["nr", "n_loci", "n_votes", "n_small", "n_large"], [int(x.value) for x in v]))
+
+    def host(self):
+        """(locus_off[nr+1] u64, diag i64, span u32, votes u32, skipped[nr] u32) as numpy copies."""
+        c = self.counts()
+        p = [C.c_void_p() for _ in range(5)]
+        _check(lib().kmx_loci_view(self._h, *[C.byref(x) for x in p]))
+        nr, nl = c["nr"], c["n_loci"]
+        out = (_view(p[0].value, nr + 1, np.uint64), _view(p[1].value, nl, np.int64), _view(p[2].value, nl, np.uint32),
+               _view(p[3].value, nl, np.uint32), _view(p[4].value, nr, np.uint32))
+        return tuple(x.copy() for x in out)
+
+    def device_ptrs(self):
+        """(d_locus_off, d_diag, d_span, d_votes, d_skipped): kmx_loci_view_device."""
+        p = [C.c_void_p() for _ in range(5)]
+        _check(lib().kmx_loci_view_device(self._h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def close(self):
+        if self._h:
+            lib().kmx_loci_free(self._h)
+            self._h = C.c_void_p()
 
     def __del__(self):
         try:
@@ -595,6 +655,14 @@ class Index:
         _check(lib().kmx_search_windows_device(self._h, d_ranks_ptr, d_roff_ptr, nr, C.byref(o), stream or None, C.byref(r._h)))
         r._index = self
         return r
+
+    def vote_windows(self, ranks, roff, w, stride=1, band=0, min_votes=1, max_occ=0):
+        """kmx_search_windows and kmx_windows_vote in a row: the Loci of a batch of reads."""
+        r = self.search_windows(ranks, roff, w, stride)
+        try:
+            return r.vote(band, min_votes, max_occ)
+        finally:
+            r.close()
 
     def debug_words(self):
         w = np.zeros(16, np.uint64)

@@ -597,6 +597,72 @@ kmx_status kmx_loci_view_device(const kmx_loci* l, const uint64_t** d_locus_off,
                                 const uint32_t** d_span, const uint32_t** d_votes, const uint32_t** d_skipped);
 void kmx_loci_free(kmx_loci* l);
 
+/* ---- alignment at the voted loci: every read against the text around each of its loci (an extension, no reference
+ *      interface; a caller detects the capability by the macro KMX_LOCI_ALIGN, KMX_VERSION is unchanged).  It joins the seeds
+ *      (kmx_search_windows, kmx_windows_vote) to a verified placement: reads in, (distance, start, end) per locus out, nine
+ *      bytes per locus and eight per read to the host.  No edit script is produced.
+ *
+ *      The contract.  ranks / roff[nr + 1] are the reads that were given to the windows search; nr must equal the loci
+ *      handle's.  For locus l of read r let q be the read, of m letters, D = diag[l], S = span[l], E = max_edits, n the text
+ *      length; all arithmetic in int64:
+ *        - S > max_span or m > KMX_ALIGN_MAX_READ: dist[l] = KMX_ALIGN_SKIPPED, start[l] = end[l] = 0;
+ *        - otherwise lo = max(0, D - E), hi = max(lo, min(n, D + S + m + E)), T = text[lo, hi) and d = the least Levenshtein
+ *          distance (unit costs) between q and any substring of T, the empty one included: the read end to end, the text free
+ *          at both ends, no band inside T.  A read letter >= sigma equals no text letter (there is no status for it);
+ *        - d > E: dist[l] = KMX_ALIGN_NONE, start[l] = end[l] = 0;
+ *        - else dist[l] = d, end[l] = the smallest offset e in [lo, hi] at which a substring of T at distance d ends, start[l] =
+ *          the largest s in [lo, e] with lev(q, text[s, e)) == d.  A read that overhangs the text comes out with the overhang
+ *          deleted: start = 0 or end = n;
+ *        - dist / start / end [n_loci] are parallel to the loci arrays; aligned[nr] = the loci of the read with dist <= E;
+ *          best[nr] = the index, relative to locus_off[r], of the aligned locus with the least (dist, index), 0xFFFFFFFF when
+ *          the read has none.  Nothing is deduplicated: two loci of a read whose windows overlap may report the same alignment.
+ *          n_aligned / n_skipped are the batch totals.
+ *      tests/align_naive.py is this contract in executable form.
+ *
+ *      The handle cannot check that the reads are those of the loci: every access is bounded by roff, n and the loci count
+ *      alone, so foreign reads give meaningless but harmless results (the letters [roff[r], roff[r + 1]) must be readable; the
+ *      host form refuses a roff that does not start at 0 or decreases, and NULL ranks with roff[nr] != 0).
+ *
+ *      kmx_loci_align uploads the reads on the stream of the vote that filled the loci handle; kmx_loci_align_device runs on
+ *      `stream`, which must be that stream or one the caller has ordered behind it.  The call only reads the loci handle.  The
+ *      device arrays (kmx_alignments_view_device; dist / start / end are NULL when there is no locus) are complete in stream
+ *      order when the call returns; kmx_alignments_view copies to page-locked host memory on first use and synchronises, on
+ *      the stream of the call that filled the handle: after kmx_loci_align_device the caller's stream must still exist at the
+ *      first kmx_alignments_view (as for kmx_loci_view after a vote on a device-form result).
+ *      *inout == NULL allocates; a handle from an earlier call is reused and its earlier views end.  After a refusal or an error
+ *      the handle, when there is one, holds an empty result.  Accessors refuse a NULL handle; any output pointer may be NULL.
+ *
+ *      KMX_ERR_INVALID_ARGUMENT before any handle is looked at: NULL index, loci, options or inout, NULL roff, a struct_size
+ *      that is too small, flags != 0, max_edits > KMX_ALIGN_MAX_EDITS.  After looking at the handles: nr differs from the loci's,
+ *      the loci live on a device that holds no replica of the index, an index that kmx_index_extend_query_size_range broke
+ *      (KMX_ERR_HIP), 2^32 or more loci (KMX_ERR_TOO_LARGE).
+ *
+ *      kmx_stats_get is not extended: all KMX_N_KERNELS slots are taken and the size of that array is ABI, so the k_align_*
+ *      kernels are not timed by the index; tools/probe_align.py times the call from outside. */
+#define KMX_LOCI_ALIGN 1
+#define KMX_ALIGN_MAX_EDITS 250u
+#define KMX_ALIGN_MAX_READ  1024u
+#define KMX_ALIGN_SKIPPED   254u
+#define KMX_ALIGN_NONE      255u
+typedef struct kmx_align_options {
+    uint32_t struct_size;  /* = sizeof(kmx_align_options): 16 */
+    uint32_t max_edits;    /* E <= KMX_ALIGN_MAX_EDITS */
+    uint32_t max_span;     /* loci with span > max_span are not aligned (KMX_ALIGN_SKIPPED); 0 = exact diagonals only */
+    uint32_t flags;        /* 0 */
+} kmx_align_options;
+typedef struct kmx_alignments kmx_alignments;
+kmx_status kmx_loci_align(const kmx_index* index, const kmx_loci* loci, const uint8_t* ranks, const uint64_t* roff, uint64_t nr,
+                          const kmx_align_options* options, kmx_alignments** inout);
+kmx_status kmx_loci_align_device(const kmx_index* index, const kmx_loci* loci, const void* d_ranks, const void* d_roff,
+                                 uint64_t nr, const kmx_align_options* options, void* stream, kmx_alignments** inout);
+kmx_status kmx_alignments_counts(const kmx_alignments* a, uint64_t* nr, uint64_t* n_loci, uint64_t* n_aligned,
+                                 uint64_t* n_skipped);
+kmx_status kmx_alignments_view(kmx_alignments* a, const uint8_t** dist, const uint32_t** start, const uint32_t** end,
+                               const uint32_t** best, const uint32_t** aligned);
+kmx_status kmx_alignments_view_device(const kmx_alignments* a, const uint8_t** d_dist, const uint32_t** d_start,
+                                      const uint32_t** d_end, const uint32_t** d_best, const uint32_t** d_aligned);
+void kmx_alignments_free(kmx_alignments* a);
+
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.
  * Works on built, loaded and replicated indexes (this replica).  The first call derives a copy packed at 2, 4 or 8 bits per

@@ -78,6 +78,10 @@ struct IndexAccess {
     PackedText* text;
 };
 IndexAccess index_access(const kmx_index* ix);                  // kmx_capi.hip
+// kmx_capi.hip: the replica of ix that lives on `device`; false when there is none
+bool index_access_on(const kmx_index* ix, int device, IndexAccess* out);
+// kmx_approx.hip: derives the replica's packed text on first use (the index's device is current; synchronises s when it derives)
+kmx_status ensure_text(const IndexAccess& A, hipStream_t s);
 kmx_status set_error(kmx_status st, const std::string& msg);    // kmx_capi.hip: kmx_last_error's message
 // kmx_capi.hip: the caller has synchronised the stream of r's last search (no device-wide wait when r is freed)
 void result_quiesced(kmx_result* r);

@@ -898,7 +898,7 @@ void kmx::packed_text_release(PackedText* t)
 }
 
 // Derives the replica's packed text (once; retried after a failure).  The index's device is current.
-static kmx_status ensure_text(const kmx::IndexAccess& A, hipStream_t s)
+kmx_status kmx::ensure_text(const kmx::IndexAccess& A, hipStream_t s)
 {
     kmx::PackedText& T = *A.text;
     std::lock_guard<std::mutex> lock(T.mu);

@@ -2955,6 +2955,18 @@ kmx::IndexAccess kmx::index_access(const kmx_index* ix)
     return kmx::IndexAccess{ix->device, ix->n, ix->sigma, ix->range, ix->broken, &ix->h_header, ix->text.get()};
 }
 
+bool kmx::index_access_on(const kmx_index* cix, int device, kmx::IndexAccess* out)
+{
+    kmx_index* ix = const_cast<kmx_index*>(cix);
+    for (size_t i = 0; i < ix->n_replicas(); ++i)
+        if (ix->replica(i)->device == device) {
+            *out = kmx::index_access(ix->replica(i));
+            out->broken = ix->broken;                          // (the flag lives in replica 0)
+            return true;
+        }
+    return false;
+}
+
 kmx_status kmx::set_error(kmx_status st, const std::string& msg) { return fail(st, msg); }
 
 void kmx::result_quiesced(kmx_result* r)

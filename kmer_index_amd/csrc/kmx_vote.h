@@ -27,4 +27,17 @@ kmx_status windows_access(kmx_result* r, WindowsAccess* out);
 // kmx_capi.hip: launch() timed under the name k_vote when the index collects statistics
 void vote_timed(const kmx_index* ix, hipStream_t s, const std::function<void()>& launch);
 
+// What alignment at the loci (kmx_align.hip) needs from a loci handle (kmx_vote.hip owns struct kmx_loci): device pointers that
+// belong to the handle and stay as they are (aligning only reads them).  A handle that no vote has filled yet has nr = 0.
+struct LociAccess {
+    int device;
+    hipStream_t stream;            // the stream of the vote that filled the handle
+    uint64_t nr, n_loci;
+    const uint64_t* locus_off;     // [nr + 1]
+    const int64_t* diag;           // [n_loci]
+    const uint32_t* span;
+    const uint32_t* votes;
+};
+LociAccess loci_access(const kmx_loci* l);   // kmx_vote.hip
+
 } // namespace kmx

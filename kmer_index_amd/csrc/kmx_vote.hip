@@ -561,6 +561,13 @@ kmx_status vote_run(const kmx::WindowsAccess& W, const kmx_vote_options& o, kmx_
 
 } // namespace
 
+kmx::LociAccess kmx::loci_access(const kmx_loci* l)
+{
+    const bool filled = l->locus_off.p != nullptr;
+    return kmx::LociAccess{l->device, l->stream, filled ? l->nr : 0, filled ? l->n_loci : 0, l->locus_off.as<uint64_t>(),
+                           l->diag.as<int64_t>(), l->span.as<uint32_t>(), l->votes.as<uint32_t>()};
+}
+
 extern "C" {
 
 kmx_status kmx_windows_vote(kmx_result* windows, const kmx_vote_options* o, kmx_loci** inout)

@@ -21,6 +21,7 @@ APPROX_MAX_SUBST = 3
 APPROX_EDIT = 1
 APPROX_LOCI, APPROX_BEST = 2, 4
 TILE_Q_NONE, TILE_Q_PARTITION, TILE_Q_SCAN = 0, 1, 2
+ALIGN_MAX_EDITS, ALIGN_MAX_READ, ALIGN_SKIPPED, ALIGN_NONE = 250, 1024, 254, 255
 
 # every symbol include/kmx.h declares
 EXPORTS = [
@@ -36,6 +37,8 @@ EXPORTS = [
     "kmx_index_paths", "kmx_result_paths",
     "kmx_search_windows", "kmx_search_windows_device", "kmx_result_window_offsets",
     "kmx_windows_vote", "kmx_loci_counts", "kmx_loci_view", "kmx_loci_view_device", "kmx_loci_free",
+    "kmx_loci_align", "kmx_loci_align_device", "kmx_alignments_counts", "kmx_alignments_view", "kmx_alignments_view_device",
+    "kmx_alignments_free",
 ]
 
 
@@ -63,6 +66,10 @@ class WindowOptions(C.Structure):
 
 class VoteOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("band", C.c_uint32), ("min_votes", C.c_uint32), ("max_occ", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class AlignOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_edits", C.c_uint32), ("max_span", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class KernelStat(C.Structure):
@@ -186,6 +193,17 @@ def lib():
         L.kmx_loci_view_device.restype = C.c_int
         L.kmx_loci_view_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]
         L.kmx_loci_free.argtypes = [vp]
+        L.kmx_loci_align.restype = C.c_int
+        L.kmx_loci_align.argtypes = [vp, vp, vp, vp, u64, P(AlignOptions), P(vp)]
+        L.kmx_loci_align_device.restype = C.c_int
+        L.kmx_loci_align_device.argtypes = [vp, vp, vp, vp, u64, P(AlignOptions), vp, P(vp)]
+        L.kmx_alignments_counts.restype = C.c_int
+        L.kmx_alignments_counts.argtypes = [vp, P(u64), P(u64), P(u64), P(u64)]
+        L.kmx_alignments_view.restype = C.c_int
+        L.kmx_alignments_view.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]
+        L.kmx_alignments_view_device.restype = C.c_int
+        L.kmx_alignments_view_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]
+        L.kmx_alignments_free.argtypes = [vp]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -412,9 +430,66 @@ class Loci:
         _check(lib().kmx_loci_view_device(self._h, *[C.byref(x) for x in p]))
         return tuple(x.value for x in p)
 
+    def align(self, index, ranks, roff, max_edits, max_span=0, alignments=None):
+        """kmx_loci_align: every read (the reads of the windows search) against the text around each of its loci, within
+        max_edits edits; loci with span > max_span are skipped.  Returns an Alignments (`alignments` reuses one)."""
+        ranks = np.ascontiguousarray(ranks, np.uint8)
+        roff = np.ascontiguousarray(roff, np.uint64)
+        a = alignments or Alignments()
+        o = AlignOptions(C.sizeof(AlignOptions), int(max_edits), int(max_span), 0)
+        _check(lib().kmx_loci_align(index._h, self._h, ranks.ctypes.data if ranks.size else None, roff.ctypes.data, roff.size - 1,
+                                    C.byref(o), C.byref(a._h)))
+        return a
+
+    def align_device(self, index, d_ranks_ptr, d_roff_ptr, nr, max_edits, max_span=0, stream=0, alignments=None):
+        """kmx_loci_align_device on a caller-owned hipStream_t: the stream of the vote, or one ordered behind it."""
+        a = alignments or Alignments()
+        o = AlignOptions(C.sizeof(AlignOptions), int(max_edits), int(max_span), 0)
+        _check(lib().kmx_loci_align_device(index._h, self._h, d_ranks_ptr, d_roff_ptr, nr, C.byref(o), stream or None, C.byref(a._h)))
+        return a
+
     def close(self):
         if self._h:
             lib().kmx_loci_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Alignments:
+    """Owns a kmx_alignments handle (kmx_loci_align)."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+
+    def counts(self):
+        v = [C.c_uint64() for _ in range(4)]
+        _check(lib().kmx_alignments_counts(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(["nr", "n_loci", "n_aligned", "n_skipped"], [int(x.value) for x in v]))
+
+    def host(self):
+        """(dist[n_loci] u8, start u32, end u32, best[nr] u32, aligned[nr] u32) as numpy copies."""
+        c = self.counts()
+        p = [C.c_void_p() for _ in range(5)]
+        _check(lib().kmx_alignments_view(self._h, *[C.byref(x) for x in p]))
+        nr, nl = c["nr"], c["n_loci"]
+        out = (_view(p[0].value, nl, np.uint8), _view(p[1].value, nl, np.uint32), _view(p[2].value, nl, np.uint32),
+               _view(p[3].value, nr, np.uint32), _view(p[4].value, nr, np.uint32))
+        return tuple(x.copy() for x in out)
+
+    def device_ptrs(self):
+        """(d_dist, d_start, d_end, d_best, d_aligned): kmx_alignments_view_device."""
+        p = [C.c_void_p() for _ in range(5)]
+        _check(lib().kmx_alignments_view_device(self._h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def close(self):
+        if self._h:
+            lib().kmx_alignments_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -663,6 +738,24 @@ class Index:
             return r.vote(band, min_votes, max_occ)
         finally:
             r.close()
+
+    def map_reads(self, ranks, roff, w, stride=1, band=0, min_votes=1, max_occ=0, max_edits=0, max_span=None):
+        """kmx_search_windows, kmx_windows_vote and kmx_loci_align in a row: (Loci, Alignments) of a batch of reads.  max_span=None
+        sets no limit on the span of the loci that are aligned."""
+        ranks = np.ascontiguousarray(ranks, np.uint8)
+        roff = np.ascontiguousarray(roff, np.uint64)
+        if max_span is None:
+            max_span = 0xFFFFFFFF
+        r = self.search_windows(ranks, roff, w, stride)
+        try:
+            loci = r.vote(band, min_votes, max_occ)
+        finally:
+            r.close()
+        try:
+            return loci, loci.align(self, ranks, roff, max_edits, max_span)
+        except Exception:
+            loci.close()
+            raise
 
     def debug_words(self):
         w = np.zeros(16, np.uint64)

@@ -600,7 +600,7 @@ void kmx_loci_free(kmx_loci* l);
 /* ---- alignment at the voted loci: every read against the text around each of its loci (an extension, no reference
  *      interface; a caller detects the capability by the macro KMX_LOCI_ALIGN, KMX_VERSION is unchanged).  It joins the seeds
  *      (kmx_search_windows, kmx_windows_vote) to a verified placement: reads in, (distance, start, end) per locus out, nine
- *      bytes per locus and eight per read to the host.  No edit script is produced.
+ *      bytes per locus and eight per read to the host.  The edit scripts are a call of their own: kmx_alignments_scripts.
  *
  *      The contract.  ranks / roff[nr + 1] are the reads that were given to the windows search; nr must equal the loci
  *      handle's.  For locus l of read r let q be the read, of m letters, D = diag[l], S = span[l], E = max_edits, n the text
@@ -662,6 +662,78 @@ kmx_status kmx_alignments_view(kmx_alignments* a, const uint8_t** dist, const ui
 kmx_status kmx_alignments_view_device(const kmx_alignments* a, const uint8_t** d_dist, const uint32_t** d_start,
                                       const uint32_t** d_end, const uint32_t** d_best, const uint32_t** d_aligned);
 void kmx_alignments_free(kmx_alignments* a);
+
+/* ---- edit scripts of the alignments: the CIGAR of every read's best alignment, or of every aligned locus (an extension, no
+ *      reference interface; a caller detects the capability by the macro KMX_ALIGN_SCRIPTS, KMX_VERSION is unchanged).  It
+ *      turns (dist, start, end) into the column-by-column alignment a SAM/BAM record, a pile-up or a variant caller needs,
+ *      on the device, from what kmx_loci_align left there.
+ *
+ *      Selection.  ranks / roff[nr + 1] are the reads that were given to kmx_loci_align.  Locus l of read r is selected when
+ *      best[r] != 0xFFFFFFFF and l == locus_off[r] + best[r]; with KMX_SCRIPT_ALL when dist[l] < KMX_ALIGN_SKIPPED.  sel[n_sel]
+ *      holds the selected loci as indices into the loci arrays, ascending; read_sel_off[nr + 1] is the exclusive prefix sum of
+ *      the per-read counts: the entries of read r are sel[read_sel_off[r] .. read_sel_off[r + 1]).
+ *
+ *      The script of an entry.  q is the read (m letters), t = text[start[l], end[l]) (L letters); a read letter >= sigma
+ *      equals nothing.  H[i][j] is the unit-cost Levenshtein distance of q[0, i) and t[0, j), both ends anchored: H[0][j] = j,
+ *      H[i][0] = i.  The script is read off by walking from (m, L) to (0, 0); at (i, j) the first of these that applies:
+ *        1. i > 0, j > 0 and H[i-1][j-1] + c == H[i][j] with c = 0 if q[i-1] == t[j-1], else 1: the op is '=' when c == 0 and
+ *           'X' when c == 1; go to (i-1, j-1);
+ *        2. j > 0 and H[i][j-1] + 1 == H[i][j]: 'D' (a text letter the read lacks); go to (i, j-1);
+ *        3. otherwise 'I' (a read letter the text lacks); go to (i-1, j).
+ *      The ops in forward order are run-length encoded the BAM way: cigar[x] = len << 4 | op with I = 1, D = 2, '=' = 7,
+ *      X = 8; with KMX_SCRIPT_M '=' and 'X' both become M = 0 before the runs are formed.  cig_off[n_sel + 1] delimits the
+ *      runs of each entry; n_ops = cig_off[n_sel].  So gaps come out left-aligned, the lengths of X + I + D sum to dist[l],
+ *      those of '=' X I to m and those of '=' X D to L, and a script has at most 2 * dist[l] + 1 runs.
+ *      tests/script_naive.py is this contract in executable form.
+ *
+ *      The handle cannot check that the reads are those of the alignment: every access is bounded by roff, n,
+ *      m <= KMX_ALIGN_MAX_READ, L <= m + dist and the run reservation alone.  An entry whose read is longer than
+ *      KMX_ALIGN_MAX_READ, or with |m - L| > dist[l], or whose DP ends at another distance than dist[l], gets an empty script
+ *      and is counted in n_mismatched; with the right reads n_mismatched is 0.  (The letters [roff[r], roff[r + 1]) must be
+ *      readable; the host form refuses a roff that does not start at 0 or decreases, and NULL ranks with roff[nr] != 0.)
+ *
+ *      scratch_bytes bounds the device memory that holds the traceback state (two bits per cell of the band, in rows of 64
+ *      diagonals); 0 = 256 MiB.  It is clamped up to what the largest entry of the batch needs, and the entries are processed in
+ *      as many chunks as it takes: the result never depends on it.
+ *
+ *      kmx_alignments_scripts uploads the reads on the stream of the call that filled the alignments handle;
+ *      kmx_alignments_scripts_device runs on `stream`, which must be that stream or one the caller has ordered behind it.  The
+ *      call only reads the loci and the alignments handle.  The device arrays (kmx_scripts_view_device; sel is NULL when there is
+ *      no entry, cigar when there is no run, all four after a refusal or an error) are complete in stream order when the call
+ *      returns; kmx_scripts_view copies to page-locked host memory on first use and synchronises, on the stream of the call that
+ *      filled the handle: after kmx_alignments_scripts_device the caller's stream must still exist at the first
+ *      kmx_scripts_view.
+ *      *inout == NULL allocates; a handle from an earlier call is reused and its earlier views end.  After a refusal or an error
+ *      the handle, when there is one, holds an empty result.  Accessors refuse a NULL handle; any output pointer may be NULL.
+ *
+ *      KMX_ERR_INVALID_ARGUMENT before any handle is looked at: NULL index, loci, alignments, options or inout, NULL roff, a
+ *      struct_size that is too small, a flag bit other than the two.  After looking at the handles: nr differs from the loci's
+ *      or the alignments', the alignments' n_loci differs from the loci's, the two handles live on different devices, the loci
+ *      live on a device that holds no replica of the index, an index that kmx_index_extend_query_size_range broke
+ *      (KMX_ERR_HIP).  KMX_ERR_OUT_OF_MEMORY when the buffers do not fit.
+ *
+ *      kmx_stats_get is not extended (see kmx_loci_align); tools/probe_script.py times the call from outside. */
+#define KMX_ALIGN_SCRIPTS 1
+#define KMX_SCRIPT_ALL 1u   /* every aligned locus, not only the best one of each read */
+#define KMX_SCRIPT_M   2u   /* '=' and 'X' both reported as M, neighbouring runs joined */
+typedef struct kmx_script_options {
+    uint32_t struct_size;    /* = sizeof(kmx_script_options): 16 */
+    uint32_t flags;          /* 0 or any of the two bits above */
+    uint64_t scratch_bytes;  /* cap on the device scratch of the traceback; 0 = the default */
+} kmx_script_options;
+typedef struct kmx_scripts kmx_scripts;
+kmx_status kmx_alignments_scripts(const kmx_index* index, const kmx_loci* loci, const kmx_alignments* alignments,
+                                  const uint8_t* ranks, const uint64_t* roff, uint64_t nr, const kmx_script_options* options,
+                                  kmx_scripts** inout);
+kmx_status kmx_alignments_scripts_device(const kmx_index* index, const kmx_loci* loci, const kmx_alignments* alignments,
+                                         const void* d_ranks, const void* d_roff, uint64_t nr,
+                                         const kmx_script_options* options, void* stream, kmx_scripts** inout);
+kmx_status kmx_scripts_counts(const kmx_scripts* s, uint64_t* nr, uint64_t* n_sel, uint64_t* n_ops, uint64_t* n_mismatched);
+kmx_status kmx_scripts_view(kmx_scripts* s, const uint64_t** read_sel_off, const uint32_t** sel, const uint64_t** cig_off,
+                            const uint32_t** cigar);
+kmx_status kmx_scripts_view_device(const kmx_scripts* s, const uint64_t** d_read_sel_off, const uint32_t** d_sel,
+                                   const uint64_t** d_cig_off, const uint32_t** d_cigar);
+void kmx_scripts_free(kmx_scripts* s);
 
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.

@@ -368,6 +368,12 @@ struct kmx_alignments {
     void clear() { nr = n_loci = n_aligned = n_skipped = 0; host_valid = false; }
 };
 
+kmx::AlignAccess kmx::alignments_access(const kmx_alignments* a)
+{
+    return AlignAccess{a->device, a->stream, a->nr, a->n_loci, a->dist.as<uint8_t>(), a->start.as<uint32_t>(), a->end.as<uint32_t>(),
+                       a->best.as<uint32_t>()};
+}
+
 namespace {
 
 kmx_status read_counters(hipStream_t s, const void* d, Pinned& h)

@@ -40,4 +40,18 @@ struct LociAccess {
 };
 LociAccess loci_access(const kmx_loci* l);   // kmx_vote.hip
 
+// What the edit scripts (kmx_script.hip) need from an alignments handle (kmx_align.hip owns struct kmx_alignments): device
+// pointers that belong to the handle and stay as they are (the scripts only read them).  dist / start / end are only looked at
+// when n_loci > 0.  A handle that no call has filled yet has nr = 0.
+struct AlignAccess {
+    int device;
+    hipStream_t stream;            // the stream of the call that filled the handle
+    uint64_t nr, n_loci;
+    const uint8_t* dist;           // [n_loci]
+    const uint32_t* start;
+    const uint32_t* end;
+    const uint32_t* best;          // [nr]
+};
+AlignAccess alignments_access(const kmx_alignments* a);   // kmx_align.hip
+
 } // namespace kmx

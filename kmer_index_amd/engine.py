@@ -22,6 +22,8 @@ APPROX_EDIT = 1
 APPROX_LOCI, APPROX_BEST = 2, 4
 TILE_Q_NONE, TILE_Q_PARTITION, TILE_Q_SCAN = 0, 1, 2
 ALIGN_MAX_EDITS, ALIGN_MAX_READ, ALIGN_SKIPPED, ALIGN_NONE = 250, 1024, 254, 255
+SCRIPT_ALL, SCRIPT_M = 1, 2
+CIGAR_OPS = "MIDNSHP=X"
 
 # every symbol include/kmx.h declares
 EXPORTS = [
@@ -39,6 +41,8 @@ EXPORTS = [
     "kmx_windows_vote", "kmx_loci_counts", "kmx_loci_view", "kmx_loci_view_device", "kmx_loci_free",
     "kmx_loci_align", "kmx_loci_align_device", "kmx_alignments_counts", "kmx_alignments_view", "kmx_alignments_view_device",
     "kmx_alignments_free",
+    "kmx_alignments_scripts", "kmx_alignments_scripts_device", "kmx_scripts_counts", "kmx_scripts_view", "kmx_scripts_view_device",
+    "kmx_scripts_free",
 ]
 
 
@@ -70,6 +74,10 @@ class VoteOptions(C.Structure):
 
 class AlignOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_edits", C.c_uint32), ("max_span", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ScriptOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("scratch_bytes", C.c_uint64)]
 
 
 class KernelStat(C.Structure):
@@ -204,6 +212,17 @@ def lib():
         L.kmx_alignments_view_device.restype = C.c_int
         L.kmx_alignments_view_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]
         L.kmx_alignments_free.argtypes = [vp]
+        L.kmx_alignments_scripts.restype = C.c_int
+        L.kmx_alignments_scripts.argtypes = [vp, vp, vp, vp, vp, u64, P(ScriptOptions), P(vp)]
+        L.kmx_alignments_scripts_device.restype = C.c_int
+        L.kmx_alignments_scripts_device.argtypes = [vp, vp, vp, vp, vp, u64, P(ScriptOptions), vp, P(vp)]
+        L.kmx_scripts_counts.restype = C.c_int
+        L.kmx_scripts_counts.argtypes = [vp, P(u64), P(u64), P(u64), P(u64)]
+        L.kmx_scripts_view.restype = C.c_int
+        L.kmx_scripts_view.argtypes = [vp, P(vp), P(vp), P(vp), P(vp)]
+        L.kmx_scripts_view_device.restype = C.c_int
+        L.kmx_scripts_view_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp)]
+        L.kmx_scripts_free.argtypes = [vp]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -487,9 +506,76 @@ class Alignments:
         _check(lib().kmx_alignments_view_device(self._h, *[C.byref(x) for x in p]))
         return tuple(x.value for x in p)
 
+    @staticmethod
+    def _script_options(all, m, scratch_bytes):
+        return ScriptOptions(C.sizeof(ScriptOptions), (SCRIPT_ALL if all else 0) | (SCRIPT_M if m else 0), int(scratch_bytes))
+
+    def scripts(self, index, loci, ranks, roff, all=False, m=False, scratch_bytes=0, scripts=None):
+        """kmx_alignments_scripts: the CIGAR of every read's best alignment (all: of every aligned locus; m: '=' and 'X' as M), from
+        the index, the loci and the reads that were aligned.  scratch_bytes bounds the device scratch of the traceback (0: the
+        default).  Returns a Scripts (`scripts` reuses one)."""
+        ranks = np.ascontiguousarray(ranks, np.uint8)
+        roff = np.ascontiguousarray(roff, np.uint64)
+        s = scripts or Scripts()
+        o = self._script_options(all, m, scratch_bytes)
+        _check(lib().kmx_alignments_scripts(index._h, loci._h, self._h, ranks.ctypes.data if ranks.size else None, roff.ctypes.data, roff.size - 1,
+                                            C.byref(o), C.byref(s._h)))
+        return s
+
+    def scripts_device(self, index, loci, d_ranks_ptr, d_roff_ptr, nr, all=False, m=False, scratch_bytes=0, stream=0, scripts=None):
+        """kmx_alignments_scripts_device on a caller-owned hipStream_t: the stream of the alignment, or one ordered behind it."""
+        s = scripts or Scripts()
+        o = self._script_options(all, m, scratch_bytes)
+        _check(lib().kmx_alignments_scripts_device(index._h, loci._h, self._h, d_ranks_ptr, d_roff_ptr, nr, C.byref(o), stream or None, C.byref(s._h)))
+        return s
+
     def close(self):
         if self._h:
             lib().kmx_alignments_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Scripts:
+    """Owns a kmx_scripts handle (kmx_alignments_scripts)."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+
+    def counts(self):
+        v = [C.c_uint64() for _ in range(4)]
+        _check(lib().kmx_scripts_counts(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(["nr", "n_sel", "n_ops", "n_mismatched"], [int(x.value) for x in v]))
+
+    def host(self):
+        """(read_sel_off[nr+1] u64, sel[n_sel] u32, cig_off[n_sel+1] u64, cigar[n_ops] u32) as numpy copies."""
+        c = self.counts()
+        p = [C.c_void_p() for _ in range(4)]
+        _check(lib().kmx_scripts_view(self._h, *[C.byref(x) for x in p]))
+        out = (_view(p[0].value, c["nr"] + 1, np.uint64), _view(p[1].value, c["n_sel"], np.uint32),
+               _view(p[2].value, c["n_sel"] + 1, np.uint64), _view(p[3].value, c["n_ops"], np.uint32))
+        return tuple(x.copy() for x in out)
+
+    def device_ptrs(self):
+        """(d_read_sel_off, d_sel, d_cig_off, d_cigar): kmx_scripts_view_device."""
+        p = [C.c_void_p() for _ in range(4)]
+        _check(lib().kmx_scripts_view_device(self._h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def strings(self):
+        """One CIGAR string per entry, e.g. "50=1X30=1D69=" ("" for an entry without a script)."""
+        _, _, cig_off, cigar = self.host()
+        runs = [f"{int(v) >> 4}{CIGAR_OPS[int(v) & 15]}" for v in cigar]
+        return ["".join(runs[int(a):int(b)]) for a, b in zip(cig_off[:-1], cig_off[1:])]
+
+    def close(self):
+        if self._h:
+            lib().kmx_scripts_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -739,9 +825,10 @@ class Index:
         finally:
             r.close()
 
-    def map_reads(self, ranks, roff, w, stride=1, band=0, min_votes=1, max_occ=0, max_edits=0, max_span=None):
+    def map_reads(self, ranks, roff, w, stride=1, band=0, min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False):
         """kmx_search_windows, kmx_windows_vote and kmx_loci_align in a row: (Loci, Alignments) of a batch of reads.  max_span=None
-        sets no limit on the span of the loci that are aligned."""
+        sets no limit on the span of the loci that are aligned.  scripts=True adds kmx_alignments_scripts (the CIGAR of every read's
+        best alignment): (Loci, Alignments, Scripts)."""
         ranks = np.ascontiguousarray(ranks, np.uint8)
         roff = np.ascontiguousarray(roff, np.uint64)
         if max_span is None:
@@ -752,9 +839,17 @@ class Index:
         finally:
             r.close()
         try:
-            return loci, loci.align(self, ranks, roff, max_edits, max_span)
+            al = loci.align(self, ranks, roff, max_edits, max_span)
         except Exception:
             loci.close()
+            raise
+        if not scripts:
+            return loci, al
+        try:
+            return loci, al, al.scripts(self, loci, ranks, roff)
+        except Exception:
+            loci.close()
+            al.close()
             raise
 
     def debug_words(self):

@@ -1,0 +1,543 @@
+"""kmx_alignments_scripts on the GPU.  The oracle throughout is tests/script_naive.scripts applied to the host arrays of the engine's
+own loci and alignments: read_sel_off, sel, cig_off and cigar must be equal array for array, dtypes included, and the counts equal."""
+import functools
+
+import numpy as np
+import pytest
+
+from kmer_index_amd import synth
+from tests import script_naive as sn
+from tests.helpers import pack
+
+pytestmark = pytest.mark.gpu
+
+NAMES = ("read_sel_off", "sel", "cig_off", "cigar")
+# the two workloads of tests/test_align_gpu.py (restated, not imported): (sigma, k, text length, reads of the generator)
+WORKLOADS = {"dna4_k10": (4, 10, 50_000, 3000), "aa20_k5": (20, 5, 50_000, 3000)}
+N_READS = 600
+VOTE = (8, 2, 0)                  # (band, min_votes, max_occ)
+MAX_SPAN = 64
+# at E = 8, best only: entries (exact), then floors: scripts with I, with D, with both, with X, all '='
+FLOORS_E8 = {"dna4_k10": (369, 123, 117, 117, 93, 158), "aa20_k5": (374, 126, 123, 123, 89, 162)}
+# at E = 24, best only: entries (exact), scripts that begin with I, that end with I (the reads that overhang the text)
+FLOORS_E24 = {"dna4_k10": (440, 14, 17), "aa20_k5": (440, 13, 15)}
+
+
+@functools.lru_cache(maxsize=None)
+def text_of(sigma, n):
+    t = synth.ranks(7 + sigma, n, sigma)
+    t.setflags(write=False)
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def reads_of(name):
+    """The first N_READS reads of the workload of that name.  Read i has m = z % 301 letters and kind i % 4: 3 is random letters, the
+    others are cut from the text (at 0 when i % 40 == 0, flush with its end when i % 40 == 4, else anywhere); kind 1 with m > 40 gets
+    a substitution at letters 12, 37, 62, ...; kind 2 with m > 60 loses the letter at m / 3 and has the one at 2m / 3 twice.
+    i % 40 == 8 / 12 with m >= 40: 20 random letters in front of text[:m - 20] / behind text[n - (m - 20):].  Every 50th read
+    carries one letter >= sigma, at its first, last and middle letter in turn."""
+    sigma, _, n, n_reads = WORKLOADS[name]
+    text = text_of(sigma, n)
+    z = synth.u64_stream(4241 + sigma + n_reads, 2 * n_reads).astype(np.int64) & 0x7FFFFFFF
+    reads = []
+    n_bad = 0
+    for i in range(N_READS):
+        m, kind = int(z[2 * i] % 301), i % 4
+        if kind == 3:
+            q = synth.ranks(900_001 + i, m, sigma)
+        elif i % 40 == 8 and m >= 40:
+            q = np.concatenate([synth.ranks(700_001 + i, 20, sigma), text[:m - 20]])
+        elif i % 40 == 12 and m >= 40:
+            q = np.concatenate([text[n - (m - 20):], synth.ranks(800_001 + i, 20, sigma)])
+        else:
+            s = 0 if i % 40 == 0 else n - m if i % 40 == 4 else int(z[2 * i + 1] % (n - m - 1 + 1))
+            if kind == 2 and m > 60:
+                q = text[s:s + m + 1].copy()
+                q = np.delete(q, m // 3)[:m]
+                q = np.insert(q, 2 * m // 3, q[2 * m // 3])[:m]
+            else:
+                q = text[s:s + m].copy()
+                if kind == 1 and m > 40:
+                    q[12::25] = (q[12::25] + 1) % sigma
+        if i % 50 == 7 and m > 0:
+            q[(0, m - 1, m // 2)[n_bad % 3]] = (sigma, 255)[(n_bad // 3) % 2]
+            n_bad += 1
+        reads.append(np.asarray(q, np.uint8))
+    ranks, roff = pack(reads)
+    ranks.setflags(write=False)
+    roff.setflags(write=False)
+    return ranks, roff
+
+
+class Mapped:
+    """The loci and the alignments of a batch of reads with their host arrays, and the oracle's scripts of them (made once)."""
+
+    def __init__(self, idx, sigma, n, ranks, roff, k, vote, E, max_span=MAX_SPAN, align_ranks=None):
+        self.idx, self.sigma, self.n, self.roff = idx, sigma, n, roff
+        self.ranks = ranks if align_ranks is None else align_ranks       # the reads given to kmx_loci_align
+        self.loci = idx.vote_windows(ranks, roff, k, 1, *vote)
+        self.al = self.loci.align(idx, self.ranks, roff, E, max_span)
+        self.h_loci, self.h_al = self.loci.host(), self.al.host()
+        self.wants = {}
+
+    def want(self, all=False, m=False, ranks=None):
+        key = (all, m) if ranks is None else None
+        if key is None or key not in self.wants:
+            dist, start, end, best, _ = self.h_al
+            got = sn.scripts(text_of(self.sigma, self.n), self.ranks if ranks is None else ranks, self.roff, self.h_loci[0], dist, start, end, best,
+                             self.sigma, all, m)
+            if key is None:
+                return got
+            self.wants[key] = got
+        return self.wants[key]
+
+    def scripts(self, **kw):
+        return self.al.scripts(self.idx, self.loci, kw.pop("ranks", self.ranks), self.roff, **kw)
+
+    def entries(self, want):
+        """(read, locus, q, t, dist) of every entry of an oracle result"""
+        read_of = np.repeat(np.arange(self.roff.size - 1), np.diff(want[0].astype(np.int64)))
+        for r, l in zip(read_of, want[1]):
+            yield (int(r), int(l), self.ranks[int(self.roff[r]):int(self.roff[r + 1])],
+                   text_of(self.sigma, self.n)[int(self.h_al[1][l]):int(self.h_al[2][l])], int(self.h_al[0][l]))
+
+    def close(self):
+        self.al.close()
+        self.loci.close()
+
+
+class Work:
+    def __init__(self, engine):
+        self.engine = engine
+        self.indexes, self.mapped = {}, {}
+
+    def index(self, name):
+        if name not in self.indexes:
+            sigma, k, n, _ = WORKLOADS[name]
+            self.indexes[name] = self.engine.Index(text_of(sigma, n), sigma, [k], table=2)
+        return self.indexes[name]
+
+    def workload(self, name, E):
+        if (name, E) not in self.mapped:
+            sigma, k, n, _ = WORKLOADS[name]
+            self.mapped[(name, E)] = Mapped(self.index(name), sigma, n, *reads_of(name), k, VOTE, E)
+        return self.mapped[(name, E)]
+
+    def boundary(self):
+        if "boundary" not in self.mapped:
+            sigma, k, n, _ = WORKLOADS["dna4_k10"]
+            (ranks, roff), _ = boundary_reads()
+            self.mapped["boundary"] = Mapped(self.index("dna4_k10"), sigma, n, ranks, roff, k, VOTE, 250)
+        return self.mapped["boundary"]
+
+    def close(self):
+        for m in self.mapped.values():
+            m.close()
+        for idx in self.indexes.values():
+            idx.close()
+
+
+@pytest.fixture(scope="module")
+def work(engine):
+    w = Work(engine)
+    yield w
+    w.close()
+
+
+def assert_same(scr, want, nr):
+    got, counts = scr.host(), scr.counts()
+    for name, g, x in zip(NAMES, got, want[:4]):
+        assert g.dtype == x.dtype and g.shape == x.shape, (name, g.shape, x.shape)
+        bad = np.flatnonzero(g != x)
+        assert bad.size == 0, (name, bad[:5], g[bad[:5]], x[bad[:5]])
+    assert counts == {"nr": nr, "n_sel": want[1].size, "n_ops": want[3].size, "n_mismatched": want[4]}, counts
+    return got
+
+
+# ---- 1. the align-test workloads -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("all", [False, True])
+@pytest.mark.parametrize("E", [0, 8, 24])
+@pytest.mark.parametrize("name", list(WORKLOADS))
+def test_workloads(work, name, E, all):
+    mp = work.workload(name, E)
+    want = mp.want(all)
+    scr = mp.scripts(all=all)
+    got = assert_same(scr, want, N_READS)
+    strings = scr.strings()
+    scr.close()
+    assert want[4] == 0 and strings == sn.strings(got[2], got[3])
+    print(name, E, all, want[1].size, want[3].size)
+    if all:
+        assert want[1].size == int(np.count_nonzero(mp.h_al[0] < 254))
+        return
+    has = lambda c: sum(c in s for s in strings)                                            # noqa: E731
+    if E == 8:
+        entries, n_i, n_d, n_both, n_x, n_eq = FLOORS_E8[name]
+        assert want[1].size == entries
+        assert has("I") >= n_i and has("D") >= n_d and sum("I" in s and "D" in s for s in strings) >= n_both and has("X") >= n_x
+        assert sum(s != "" and set(s) <= set("0123456789=") for s in strings) >= n_eq
+    if E == 24:
+        entries, n_begin, n_end = FLOORS_E24[name]
+        assert want[1].size == entries
+        assert sum(s.lstrip("0123456789")[:1] == "I" for s in strings) >= n_begin and sum(s.endswith("I") for s in strings) >= n_end
+
+
+# ---- 2. independent of the naive ---------------------------------------------------------------------------------------------------------
+def test_replay_consumes_read_and_text(work):
+    mp = work.workload("dna4_k10", 24)
+    scr = mp.scripts(all=True)
+    read_sel_off, sel, cig_off, cigar = scr.host()
+    scr.close()
+    assert sel.size >= 440
+    read_of = np.repeat(np.arange(N_READS), np.diff(read_sel_off.astype(np.int64)))
+    dist, start, end = mp.h_al[:3]
+    text = text_of(mp.sigma, mp.n)
+    for e, (r, l) in enumerate(zip(read_of, sel)):
+        assert mp.h_loci[0][r] <= l < mp.h_loci[0][r + 1]
+        q = mp.ranks[int(mp.roff[r]):int(mp.roff[r + 1])]
+        runs = cigar[int(cig_off[e]):int(cig_off[e + 1])]
+        assert sn.replay(q, text[int(start[l]):int(end[l])], runs, mp.sigma) == (int(dist[l]), True), (e, r, l)
+        assert len(runs) <= 2 * int(dist[l]) + 1
+
+
+# ---- 3. shapes where the kernel can go wrong -------------------------------------------------------------------------------------------------
+LENGTHS = (63, 64, 65, 127, 128, 129, 511, 513, 1024)
+PLANTED = ((511, 31), (513, 32), (513, 33), (1024, 63), (1024, 64))      # (letters, substitutions): the band at 63, 65, 67, 127, 129 diagonals
+OVERHANG = 250                                                           # ... and at 501
+
+
+def homopolymer(text, least=5, after=1000):
+    """(first letter, length) of a maximal run of one letter"""
+    same = np.flatnonzero(text[1:] != text[:-1]) + 1                       # the starts of the runs (but the first)
+    lens = np.diff(same)
+    i = int(np.flatnonzero((lens >= least) & (same[:-1] > after))[0])
+    return int(same[i]), int(lens[i])
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_reads():
+    """Reads cut from the DNA4 text.  Per length of LENGTHS: unedited; a substitution at letter 0; one at letter 0 and one at letter
+    m - 1; three letters inserted from letter 62 on (m > 70) and one deleted at letter 127 (m > 135); flush with the start and
+    with the end of the text.  Per (m, d) of PLANTED: d substitutions spread over the read.  1024 letters of which OVERHANG hang
+    over the end / the start of the text.  128 letters with a letter >= sigma at the first, the middle, the last letter.  A
+    deletion and an insertion inside a run of one letter of the text.  Reads of 1 and 2 letters (no window: no locus).
+    Returns ((ranks, roff), per read the planted distance or None and the expected CIGAR or None)."""
+    sigma, k, n, _ = WORKLOADS["dna4_k10"]
+    text = text_of(sigma, n)
+    z = synth.u64_stream(78, 8 * len(LENGTHS) + 16).astype(np.int64) & 0x7FFFFFFF
+    reads, meta = [], []
+
+    def add(q, planted=None, cigar=None):
+        reads.append(np.asarray(q, np.uint8))
+        meta.append((planted, cigar))
+
+    for li, m in enumerate(LENGTHS):
+        s = [1500 + int(z[8 * li + j] % (n - m - 3000)) for j in range(4)]
+        add(text[s[0]:s[0] + m], 0, f"{m}=")
+        q = text[s[1]:s[1] + m].copy()
+        q[0] = (q[0] + 1) % sigma
+        add(q, 1, f"1I{m - 1}=")                                               # (start is the largest there is: the letter is inserted)
+        q = text[s[2]:s[2] + m].copy()
+        q[0] = (q[0] + 1) % sigma
+        q[m - 1] = (q[m - 1] + 2) % sigma
+        add(q, 2)                                                              # (the new last letter may equal the text's next one)
+        q = text[s[3]:s[3] + m + 8].copy()
+        planted = 0
+        if m > 70:
+            q = np.insert(q, 62, synth.ranks(5000 + m, 3, sigma))
+            planted = 3
+        if m > 135:
+            q = np.delete(q, 127)
+            planted = 4
+        add(q[:m], planted)
+        add(text[:m], 0, f"{m}=")
+        add(text[n - m:], 0, f"{m}=")
+    for m, d in PLANTED:
+        s = 1500 + int(z[8 * len(LENGTHS) + d % 7] % (n - m - 3000))
+        q = text[s:s + m].copy()
+        at = 3 + np.arange(d) * (m // d)
+        q[at] = (q[at] + 1) % sigma
+        add(q, d)
+    add(np.concatenate([text[n - (1024 - OVERHANG):], synth.ranks(601, OVERHANG, sigma)]), OVERHANG)
+    add(np.concatenate([synth.ranks(602, OVERHANG, sigma), text[:1024 - OVERHANG]]), OVERHANG, f"{OVERHANG}I{1024 - OVERHANG}=")
+    for at, letter in ((0, sigma), (64, 255), (127, sigma)):
+        q = text[7000:7128].copy()
+        q[at] = letter
+        add(q, 1, {0: "1I127=", 64: "64=1X63=", 127: "127=1I"}[at])
+    p, run = homopolymer(text)
+    add(np.delete(text[p - 40:p + run + 40], 40 + run // 2), 1, f"40=1D{run - 1 + 40}=")                 # left-aligned on the device too
+    add(np.insert(text[p - 40:p + run + 40], 40 + run // 2, text[p]), 1, f"40=1I{run + 40}=")
+    add(text[300:301])
+    add(text[300:302])
+    return pack(reads), meta
+
+
+def test_boundary_shapes(work):
+    (ranks, roff), meta = boundary_reads()
+    mp = work.boundary()
+    want = mp.want()
+    scr = mp.scripts()
+    got = assert_same(scr, want, len(meta))
+    strings = scr.strings()
+    scr.close()
+    assert want[4] == 0
+    dist = mp.h_al[0]
+    n_checked = 0
+    dists = set()
+    for e, r in enumerate(np.repeat(np.arange(len(meta)), np.diff(got[0].astype(np.int64)))):
+        planted, cigar = meta[r]
+        d = int(dist[got[1][e]])
+        dists.add(d)
+        assert planted is not None and d <= planted, (r, d, planted)
+        if cigar is not None:
+            assert strings[e] == cigar, (r, strings[e], cigar)
+            n_checked += 1
+    # properties of the inputs: every read with a window has an entry, the distances hit both sides of every class boundary
+    assert got[1].size == len(meta) - 2 and n_checked >= 4 * len(LENGTHS) + 6
+    assert {0, 1, 31, 32, 33, 63, 64, 250} <= dists, sorted(dists)
+    # ... every aligned locus, and M
+    for kw in ({"all": True}, {"m": True}, {"all": True, "m": True}):
+        scr = mp.scripts(**kw)
+        assert_same(scr, mp.want(**kw), len(meta))
+        scr.close()
+
+
+def test_tiny_reads(work, engine):
+    """Reads of 1 and 2 letters (and a few more) against an index of single letters: every locus a script of one or two columns."""
+    sigma, n = 4, 300
+    text = synth.ranks(91, n, sigma)
+    idx = engine.Index(text, sigma, [1], table=2)
+    reads = [text[5:6], text[n - 1:], text[0:1], text[17:19], text[n - 2:], np.asarray([text[40], (text[41] + 1) % sigma], np.uint8), text[60:63],
+             np.asarray([sigma], np.uint8)]
+    ranks, roff = pack(reads)
+    loci = idx.vote_windows(ranks, roff, 1, 1, 0, 1, 0)
+    al = loci.align(idx, ranks, roff, 1, 0)
+    off = loci.host()[0]
+    dist, start, end, best, _ = al.host()
+    n_all = 0
+    for all in (False, True):
+        want = sn.scripts(text, ranks, roff, off, dist, start, end, best, sigma, all)
+        scr = al.scripts(idx, loci, ranks, roff, all=all)
+        assert_same(scr, want, len(reads))
+        assert want[4] == 0 and want[1].size >= (7, 150)[all]
+        n_all = want[1].size
+        scr.close()
+    assert n_all == int(np.count_nonzero(dist < 254))
+    for h in (al, loci, idx):
+        h.close()
+
+
+def test_read_of_nothing_but_insertions(work):
+    """dist == m with L = 0: the reads given to kmx_loci_align (and to the scripts) hold no letter of the alphabet, so every read of at
+    most E letters aligns with the empty substring: the single run mI."""
+    sigma, k, n, _ = WORKLOADS["dna4_k10"]
+    ranks, roff = reads_of("dna4_k10")
+    nr = 120
+    few = (ranks[:int(roff[nr])], roff[:nr + 1])
+    blank = np.full(few[0].size, 255, np.uint8)
+    mp = Mapped(work.index("dna4_k10"), sigma, n, *few, k, VOTE, 250, align_ranks=blank)
+    want = mp.want(all=True)
+    scr = mp.scripts(all=True)
+    assert_same(scr, want, nr)
+    strings = scr.strings()
+    scr.close()
+    lens = np.diff(few[1].astype(np.int64))
+    n_runs = 0
+    for e, (r, l, q, t, d) in enumerate(mp.entries(want)):
+        assert d == lens[r] and t.size == 0 and strings[e] == (f"{d}I" if d else "")
+        n_runs += d > 0
+    assert want[4] == 0 and n_runs >= 50
+    mp.close()
+
+
+# ---- 4. scratch_bytes ----------------------------------------------------------------------------------------------------------------------
+def test_scratch_bytes_changes_nothing(work):
+    for mp, all in ((work.workload("dna4_k10", 24), True), (work.boundary(), False)):
+        want = mp.want(all)
+        d = mp.h_al[0][want[1]].astype(np.int64)
+        lens = np.diff(mp.roff.astype(np.int64))[np.repeat(np.arange(mp.roff.size - 1), np.diff(want[0].astype(np.int64)))]
+        # the traceback codes of an entry: 16 bytes per row and 64 diagonals of the band
+        code = 16 * np.select([d < 32, d < 64, d < 128], [1, 2, 4], 8) * lens
+        small = max(int(code.sum()) // 4, int(code.max()))
+        assert int(code.sum()) > 2 * small                                                   # at least 3 chunks: none holds more than `small`
+        nr = mp.roff.size - 1
+        for scratch in (0, small, 1):
+            scr = mp.scripts(all=all, scratch_bytes=scratch)
+            assert_same(scr, want, nr)
+            scr.close()
+
+
+# ---- 5. KMX_SCRIPT_M -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("all", [False, True])
+def test_m_joins_equal_and_substituted(work, all):
+    mp = work.workload("aa20_k5", 8)
+    want = mp.want(all, m=True)
+    scr = mp.scripts(all=all, m=True)
+    got = assert_same(scr, want, N_READS)
+    scr.close()
+    plain = mp.want(all)
+    assert set((got[3] & 15).tolist()) == {sn.OP_M, sn.OP_I, sn.OP_D} and got[3].size < plain[3].size
+    for e, (r, l, q, t, d) in enumerate(mp.entries(want)):
+        assert sn.replay(q, t, got[3][int(got[2][e]):int(got[2][e + 1])], mp.sigma) == (d, True)
+
+
+# ---- 6. foreign reads --------------------------------------------------------------------------------------------------------------------------
+def test_foreign_reads(work):
+    """Defined behaviour, bounded by construction: the letters of 20 reads replaced after the align call."""
+    mp = work.workload("dna4_k10", 8)
+    before = mp.want()
+    has = np.flatnonzero(np.diff(before[0].astype(np.int64)) > 0)
+    lens = np.diff(mp.roff.astype(np.int64))
+    text = text_of(mp.sigma, mp.n)
+    old_strings = sn.strings(before[2], before[3])
+    with_x = [int(r) for r in has if lens[r] >= 30 and "X" in old_strings[int(before[0][r])]][::5][:4]
+    swapped = with_x + [int(r) for r in has if lens[r] >= 30 and r not in with_x][::7][:16]
+    assert len(with_x) == 4 and len(swapped) == 20
+    ranks = np.array(mp.ranks)
+    for i, r in enumerate(swapped):
+        a, b = int(mp.roff[r]), int(mp.roff[r + 1])
+        if r in with_x:                                                       # another wrong letter at the first substitution: the read fits as before
+            e = int(before[0][r])
+            i_q = j_t = 0
+            for v in before[3][int(before[2][e]):int(before[2][e + 1])]:
+                if int(v) & 15 == sn.OP_X:
+                    break
+                i_q += (int(v) >> 4) * (int(v) & 15 != sn.OP_D)
+                j_t += (int(v) >> 4) * (int(v) & 15 != sn.OP_I)
+            there = int(text[int(mp.h_al[1][before[1][e]]) + j_t])
+            ranks[a + i_q] = next(c for c in range(mp.sigma) if c not in (there, int(ranks[a + i_q])))
+        else:
+            ranks[a:b] = synth.ranks(333 + i, b - a, mp.sigma)
+    want = mp.want(ranks=ranks)
+    scr = mp.scripts(ranks=ranks)
+    got = assert_same(scr, want, N_READS)
+    scr.close()
+    assert 10 <= want[4] <= 16
+    assert sum(want[2][int(want[0][r]) + 1] > want[2][int(want[0][r])] for r in with_x) >= 2
+    for r in range(N_READS):
+        e = int(got[0][r])
+        if got[0][r + 1] == e:
+            continue
+        runs = got[3][int(got[2][e]):int(got[2][e + 1])]
+        old = before[3][int(before[2][e]):int(before[2][e + 1])]
+        if r not in swapped:
+            assert np.array_equal(runs, old)
+            continue
+        l = int(got[1][e])
+        q, t = ranks[int(mp.roff[r]):int(mp.roff[r + 1])], text[int(mp.h_al[1][l]):int(mp.h_al[2][l])]
+        assert runs.size == 0 or sn.replay(q, t, runs, mp.sigma) == (int(mp.h_al[0][l]), True)
+
+
+# ---- 7. plumbing ---------------------------------------------------------------------------------------------------------------------------------
+def assert_empty(scr, nr):
+    read_sel_off, sel, cig_off, cigar = scr.host()
+    assert read_sel_off.dtype == np.uint64 and np.array_equal(read_sel_off, np.zeros(nr + 1, np.uint64))
+    assert sel.dtype == np.uint32 and sel.size == 0 and cigar.dtype == np.uint32 and cigar.size == 0
+    assert cig_off.dtype == np.uint64 and np.array_equal(cig_off, np.zeros(1, np.uint64))
+    assert scr.counts() == {"nr": nr, "n_sel": 0, "n_ops": 0, "n_mismatched": 0} and scr.strings() == []
+
+
+def test_degenerate_batches_and_refusals(work):
+    engine, idx = work.engine, work.index("dna4_k10")
+    none = (np.zeros(0, np.uint8), np.zeros(1, np.uint64))
+    loci, al, scr = idx.map_reads(*none, 10, max_edits=3, scripts=True)                                       # nr = 0
+    assert_empty(scr, 0)
+    ranks, roff = pack([synth.ranks(i, i % 10, 4) for i in range(300)])                                      # no read has a window
+    loci2 = idx.vote_windows(ranks, roff, 10)
+    al2 = loci2.align(idx, ranks, roff, 3)
+    assert loci2.counts()["n_loci"] == 0
+    scr = al2.scripts(idx, loci2, ranks, roff, scripts=scr)
+    assert_empty(scr, 300)
+    random = pack([synth.ranks(50 + i, 80, 4) for i in range(40)])                                           # loci, none of them aligned
+    text = text_of(4, 50_000)
+    seeded = pack([np.concatenate([text[100 * i:100 * i + 12], synth.ranks(90 + i, 70, 4)]) for i in range(40)])
+    loci3 = idx.vote_windows(*seeded, 10, 1, *VOTE)
+    al3 = loci3.align(idx, *seeded, 2, MAX_SPAN)
+    assert loci3.counts()["n_loci"] >= 30 and al3.counts()["n_aligned"] == 0
+    for all in (False, True):
+        scr = al3.scripts(idx, loci3, *seeded, all=all, scripts=scr)
+        assert_empty(scr, 40)
+    # nr or n_loci differ between the handles and the call: refused, and the handle holds an empty result
+    mp = work.workload("dna4_k10", 8)
+    filled = mp.scripts(scripts=scr)
+    assert filled is scr and scr.counts()["n_sel"] == FLOORS_E8["dna4_k10"][0]
+    for args, word in (((idx, loci2, ranks[:int(roff[299])], roff[:300]), "nr"), ((idx, loci3, *seeded), "nr")):
+        with pytest.raises(engine.KmxError) as e:
+            al2.scripts(*args, scripts=scr)
+        assert e.value.status == 1 and word in str(e.value)
+        assert_empty(scr, 0)
+        assert scr.device_ptrs() == (None, None, None, None)
+        mp.scripts(scripts=scr)
+    loci4 = idx.vote_windows(*random, 10, 1, *VOTE)                                                          # 40 reads as loci3, other loci
+    assert loci4.counts()["n_loci"] != loci3.counts()["n_loci"]
+    with pytest.raises(engine.KmxError) as e:
+        al3.scripts(idx, loci4, *seeded, scripts=scr)
+    assert e.value.status == 1 and "n_loci" in str(e.value)
+    assert_empty(scr, 0)
+    for h in (loci, loci2, loci3, loci4, al, al2, al3, scr):
+        h.close()
+
+
+def test_one_handle_for_batches_of_different_sizes(work):
+    small = work.boundary()
+    large = work.workload("dna4_k10", 24)
+    scr = None
+    for mp, all in ((small, False), (large, True), (small, False)):
+        scr = mp.scripts(all=all, scripts=scr)
+        assert_same(scr, mp.want(all), mp.roff.size - 1)
+    scr.close()
+
+
+def device_array(torch, ptr, n, dtype):
+    if n == 0:
+        return np.zeros(0, dtype)
+
+    class _Arr:
+        def __init__(self):
+            self.__cuda_array_interface__ = {"shape": (int(n) * np.dtype(dtype).itemsize,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+    out = torch.as_tensor(_Arr(), device="cuda").clone()
+    torch.cuda.synchronize()
+    return out.cpu().numpy().view(dtype)
+
+
+def test_device_form_on_a_callers_stream_and_device_view(work):
+    import torch
+    idx = work.index("dna4_k10")
+    ranks, roff = reads_of("dna4_k10")
+    stream = torch.cuda.Stream()
+    d_r = torch.from_numpy(np.array(ranks)).cuda()
+    d_o = torch.from_numpy(np.array(roff).view(np.int64)).cuda()
+    torch.cuda.synchronize()
+    r = idx.search_windows_device(d_r.data_ptr(), d_o.data_ptr(), N_READS, 10, 1, stream=stream.cuda_stream)
+    loci = r.vote(*VOTE)
+    al = loci.align_device(idx, d_r.data_ptr(), d_o.data_ptr(), N_READS, 8, MAX_SPAN, stream=stream.cuda_stream)
+    before = loci.host(), al.host(), loci.device_ptrs(), al.device_ptrs()
+    scr = al.scripts_device(idx, loci, d_r.data_ptr(), d_o.data_ptr(), N_READS, all=True, stream=stream.cuda_stream)
+    stream.synchronize()
+    want = work.workload("dna4_k10", 8).want(all=True)
+    c = scr.counts()
+    sizes = (c["nr"] + 1, c["n_sel"], c["n_sel"] + 1, c["n_ops"])
+    for name, ptr, n, x in zip(NAMES, scr.device_ptrs(), sizes, want):
+        assert np.array_equal(device_array(torch, ptr, n, x.dtype), x), name
+    assert_same(scr, want, N_READS)
+    # the call only reads the two handles
+    assert (loci.device_ptrs(), al.device_ptrs()) == before[2:]
+    for g, x in zip(loci.host() + al.host(), before[0] + before[1]):
+        assert g.dtype == x.dtype and np.array_equal(g, x)
+    for h in (scr, al, loci, r):
+        h.close()
+
+
+def test_map_reads_with_scripts_equals_the_four_calls(work):
+    idx = work.index("aa20_k5")
+    ranks, roff = reads_of("aa20_k5")
+    mp = work.workload("aa20_k5", 8)
+    loci, al, scr = idx.map_reads(ranks, roff, 5, 1, *VOTE, max_edits=8, max_span=MAX_SPAN, scripts=True)
+    for g, x in zip(loci.host() + al.host(), mp.h_loci + mp.h_al):
+        assert g.dtype == x.dtype and np.array_equal(g, x)
+    assert_same(scr, mp.want(), N_READS)
+    pair = idx.map_reads(ranks, roff, 5, 1, *VOTE, max_edits=8, max_span=MAX_SPAN)
+    assert len(pair) == 2 and isinstance(pair[0], work.engine.Loci) and isinstance(pair[1], work.engine.Alignments)
+    for h in (loci, al, scr) + pair:
+        h.close()

@@ -735,6 +735,93 @@ kmx_status kmx_scripts_view_device(const kmx_scripts* s, const uint64_t** d_read
                                    const uint64_t** d_cig_off, const uint32_t** d_cigar);
 void kmx_scripts_free(kmx_scripts* s);
 
+/* ---- both strands of the mapping chain: the reverse complements made on the device, the two strands of every read folded into
+ *      one placement (an extension, no reference interface; a caller detects the capability by the macro KMX_MAP_STRANDS,
+ *      KMX_VERSION is unchanged).  The reverse complement of a read is just another read, and an alignment of rc(read) against
+ *      the forward text is what SAM reports for a reverse-strand read: the leftmost forward-text position and the CIGAR of the
+ *      reverse-complemented read.  So the four stages stay as they are: the reads go up once, a doubled batch is made on the
+ *      device and handed to kmx_search_windows_device, kmx_windows_vote, kmx_loci_align_device; kmx_alignments_fold_strands
+ *      picks one placement per read, and kmx_placements_scripts makes the scripts of the winners only.
+ *
+ *      The doubled batch.  `complement` is the table of kmx_search_approx_strands (sigma entries on the host, an involution on
+ *      [0, sigma), the identity allowed; NULL, a non-involution or an entry >= sigma: KMX_ERR_INVALID_ARGUMENT before any device
+ *      is touched).  For read i of m letters at roff[i], rc(q)[j] = complement[c] if c < sigma, else c, with c = q[m - 1 - j]: a
+ *      letter outside the alphabet stays outside it and matches nothing on either strand.  The internal batch has nr2 = 2 nr
+ *      reads: internal read 2i is read i, internal read 2i + 1 is rc(read i), their letters side by side:
+ *      roff2[2i] = 2 roff[i], roff2[2i + 1] = 2 roff[i] + m, roff2[2 nr] = 2 roff[nr].
+ *      kmx_reads_strands uploads ranks / roff[nr + 1] (shaped as for kmx_search_windows) once, on a stream the handle owns, on
+ *      the first replica; it refuses a roff that does not start at 0 or decreases and NULL ranks with roff[nr] != 0.
+ *      kmx_reads_strands_device takes device arrays, runs on `stream` on the replica of the device that owns d_ranks (as
+ *      kmx_search_windows_device) and costs one 8-byte read-back; reads whose offsets decrease or pass roff[nr] come out empty.
+ *      kmx_strand_reads_view_device gives d_ranks2 / d_roff2 / nr2 and the stream the handle was filled on: these four go to
+ *      kmx_search_windows_device, kmx_loci_align_device and kmx_alignments_scripts_device as they are (kmx_windows_vote runs on
+ *      the stream of its search).  After kmx_reads_strands the handle OWNS that stream: free it after the last *_view of
+ *      anything computed on it (the rule written under kmx_loci_align_device, with the handle as the caller).
+ *      nr >= 2^30 or more than 2^62 letters: KMX_ERR_TOO_LARGE.  *inout == NULL allocates; a handle passed in is reused and its
+ *      earlier views end; after a refusal or an error it holds an empty batch (nr2 = 0).
+ *
+ *      The fold.  `loci` and `alignments` are those of a doubled batch (nr2 reads, nr2 even; nr = nr2 / 2 public reads); the
+ *      reads are not needed.  `stream` is the stream of the align call or one ordered behind it, NULL: the stream that filled
+ *      the alignments handle.  For public read i, in int64: a = locus_off[2i], b = locus_off[2i + 1], c = locus_off[2i + 2];
+ *      locus l in [a, c) has strand s(l) = 0 if l < b, else 1, and is ALIGNED when dist[l] < KMX_ALIGN_SKIPPED.
+ *        - the winner w is the aligned locus with the least (dist, strand, l): the better of a + best[2i] and b + best[2i + 1],
+ *          the forward strand winning a tie;
+ *        - locus[i] = w (an index into the loci arrays), strand[i] = s(w), dist[i] / start[i] / end[i] those of w; a read without
+ *          an aligned locus gets 0xFFFFFFFF, 255, KMX_ALIGN_NONE, 0, 0;
+ *        - second[i] = the least dist[l] over the aligned l in [a, c), l != w, that lie ELSEWHERE: s(l) != s(w), or
+ *          max(start[l], start[w]) >= min(end[l], end[w]) (no text letter shared with the winner's interval); 255 when there is
+ *          none or the read is unplaced.  Two loci of a read often describe one placement (nothing is deduplicated, and a
+ *          truncated window yields a worse shadow of the same place): the overlap rule keeps both out of `second`.  A read equal
+ *          to its own reverse complement gets second == dist: its strand is ambiguous;
+ *        - best2[nr2] is best[] with the loser's entry cleared: best2[2i + s] = best[2i + s] if s == strand[i], else 0xFFFFFFFF;
+ *        - n_placed counts the reads with a winner, n_reverse those of them with strand 1, n_ambiguous the placed reads with
+ *          second == dist.
+ *      tests/fold_naive.py is this contract in executable form.
+ *      Every index is bounded by n_loci and every best[] by its read's range: foreign handles give meaningless but harmless
+ *      results.  The call only reads the two handles.  The device arrays (kmx_placements_view_device; all NULL when nr == 0)
+ *      are complete in stream order when the call returns; kmx_placements_view copies to page-locked host memory on first use
+ *      and synchronises, on the stream of the fold (15 bytes per read; best2 only when it is asked for).  *inout and the
+ *      accessors as for the other handles; after a refusal or an error the handle holds an empty result.
+ *      KMX_ERR_INVALID_ARGUMENT before any handle is looked at: NULL loci, alignments, options or inout, a struct_size that is
+ *      too small, flags != 0.  After looking: nr2 odd, the two handles disagree in nr or n_loci or live on different devices.
+ *
+ *      Scripts of the winners.  kmx_placements_scripts is kmx_alignments_scripts_device over the doubled reads of `reads`, on
+ *      the stream that handle was filled on, with the placements' best2 in the place of the alignments' best.  The result is an
+ *      ordinary kmx_scripts: read_sel_off[nr2 + 1] runs over the internal reads, with at most one entry per public read, at
+ *      internal read 2i + strand[i] and with sel = locus[i]; for a reverse placement the CIGAR is the script of rc(read i)
+ *      against text[start, end), the SAM convention.  KMX_SCRIPT_ALL is refused (it ignores best); KMX_SCRIPT_M and
+ *      scratch_bytes work as before.  Refused like kmx_alignments_scripts_device, and: NULL reads or placements, placements
+ *      whose 2 nr differs from the reads' nr2 or that live on another device. */
+#define KMX_MAP_STRANDS 1
+typedef struct kmx_strand_reads kmx_strand_reads;
+kmx_status kmx_reads_strands(const kmx_index* index, const uint8_t* ranks, const uint64_t* roff, uint64_t nr,
+                             const uint8_t* complement, kmx_strand_reads** inout);
+kmx_status kmx_reads_strands_device(const kmx_index* index, const void* d_ranks, const void* d_roff, uint64_t nr,
+                                    const uint8_t* complement /* host, sigma entries */, void* stream,
+                                    kmx_strand_reads** inout);
+kmx_status kmx_strand_reads_view_device(const kmx_strand_reads* s, const uint8_t** d_ranks2, const uint64_t** d_roff2,
+                                        uint64_t* nr2, void** stream);
+void kmx_strand_reads_free(kmx_strand_reads* s);
+typedef struct kmx_fold_options {
+    uint32_t struct_size;  /* = sizeof(kmx_fold_options): 8 */
+    uint32_t flags;        /* 0 */
+} kmx_fold_options;
+typedef struct kmx_placements kmx_placements;
+kmx_status kmx_alignments_fold_strands(const kmx_loci* loci, const kmx_alignments* alignments,
+                                       const kmx_fold_options* options, void* stream, kmx_placements** inout);
+kmx_status kmx_placements_counts(const kmx_placements* p, uint64_t* nr, uint64_t* n_placed, uint64_t* n_reverse,
+                                 uint64_t* n_ambiguous);
+kmx_status kmx_placements_view(kmx_placements* p, const uint32_t** locus, const uint8_t** strand, const uint8_t** dist,
+                               const uint32_t** start, const uint32_t** end, const uint8_t** second,
+                               const uint32_t** best2);
+kmx_status kmx_placements_view_device(const kmx_placements* p, const uint32_t** d_locus, const uint8_t** d_strand,
+                                      const uint8_t** d_dist, const uint32_t** d_start, const uint32_t** d_end,
+                                      const uint8_t** d_second, const uint32_t** d_best2);
+void kmx_placements_free(kmx_placements* p);
+kmx_status kmx_placements_scripts(const kmx_index* index, const kmx_strand_reads* reads, const kmx_loci* loci,
+                                  const kmx_alignments* alignments, const kmx_placements* placements,
+                                  const kmx_script_options* options, kmx_scripts** inout);
+
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.
  * Works on built, loaded and replicated indexes (this replica).  The first call derives a copy packed at 2, 4 or 8 bits per

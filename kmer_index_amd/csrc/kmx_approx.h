@@ -83,6 +83,9 @@ bool index_access_on(const kmx_index* ix, int device, IndexAccess* out);
 // kmx_approx.hip: derives the replica's packed text on first use (the index's device is current; synchronises s when it derives)
 kmx_status ensure_text(const IndexAccess& A, hipStream_t s);
 kmx_status set_error(kmx_status st, const std::string& msg);    // kmx_capi.hip: kmx_last_error's message
+// kmx_approx.hip: the refusals of a complement table (kmx_search_approx_strands, kmx_reads_strands); comp[256] <- the table, the
+// identity outside the alphabet
+kmx_status check_complement(const std::string& who, const uint8_t* complement, uint32_t sigma, uint8_t* comp);
 // kmx_capi.hip: the caller has synchronised the stream of r's last search (no device-wide wait when r is freed)
 void result_quiesced(kmx_result* r);
 void packed_text_release(PackedText* t);                        // kmx_approx.hip (the index's device is current)

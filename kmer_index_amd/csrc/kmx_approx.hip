@@ -1025,7 +1025,7 @@ static kmx_status check_queries(const std::string& who, const uint8_t* qranks, c
 }
 
 // comp[256] <- the complement table, the identity outside the alphabet (letters there: the pair is KMX_Q_BAD_RANK)
-static kmx_status check_complement(const std::string& who, const uint8_t* complement, uint32_t sigma, uint8_t* comp)
+kmx_status kmx::check_complement(const std::string& who, const uint8_t* complement, uint32_t sigma, uint8_t* comp)
 {
     for (uint32_t r = 0; r < 256; ++r) comp[r] = uint8_t(r);
     for (uint32_t r = 0; r < sigma && r < 256; ++r)                   // every entry's range first: an entry outside the alphabet is
@@ -1285,7 +1285,7 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
     const uint32_t e = max_subst, E1 = e + 1;
     const uint32_t S = complement ? 2u : 1u;             // internal queries per query (both strands: q and rc(q))
     uint8_t comp[256];
-    if (complement) AX_OK(check_complement(who, complement, A.sigma, comp));
+    if (complement) AX_OK(kmx::check_complement(who, complement, A.sigma, comp));
     uint64_t budget = kDefaultBudget, max_pieces = kMaxPieces;
     if (const char* env = getenv("KMX_APPROX_CHUNK_CANDIDATES")) { const long long v = atoll(env); if (v > 0) budget = uint64_t(v); }
     if (const char* env = getenv("KMX_APPROX_CHUNK_PIECES")) { const long long v = atoll(env); if (v > 0) max_pieces = std::min(uint64_t(v), kMaxPieces); }

@@ -402,9 +402,10 @@ void launch_dp(hipStream_t s, int cls, const ScriptIn& S, const Entries& C)
     }
 }
 
-// d_ranks / d_roff: the reads on the device of the handles; ranks_len: the letters that may be read
+// d_ranks / d_roff: the reads on the device of the handles; ranks_len: the letters that may be read; best: what selects the
+// entries, the alignments' own or a caller's in its place (kmx_placements_scripts)
 kmx_status script_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const kmx::AlignAccess& A, const void* d_ranks, const void* d_roff,
-                      uint64_t ranks_len, const kmx_script_options& o, hipStream_t s, kmx_scripts* h)
+                      uint64_t ranks_len, const uint32_t* best, const kmx_script_options& o, hipStream_t s, kmx_scripts* h)
 {
     const uint64_t nr = L.nr, nl = L.n_loci;
     h->device = L.device; h->stream = s;
@@ -433,7 +434,7 @@ kmx_status script_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const
     unsigned long long* ctr = h->ctr.as<unsigned long long>();
     SC_TRY(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
     for (Buf* b : {&h->ecode, &h->eres, &h->eruns}) SC_TRY(hipMemsetAsync(b->p, 0, cap_e * 4, s));   // the scans run over cap_e entries
-    const ScriptIn S{static_cast<const uint8_t*>(d_ranks), static_cast<const uint64_t*>(d_roff), ranks_len, L.locus_off, A.dist, A.start, A.end, A.best,
+    const ScriptIn S{static_cast<const uint8_t*>(d_ranks), static_cast<const uint64_t*>(d_roff), ranks_len, L.locus_off, A.dist, A.start, A.end, best,
                      nr, nl, X.n, X.text->d_words, X.text->w, X.sigma, o.flags};
     uint64_t* bsum = h->bsum.as<uint64_t>();
     hipLaunchKernelGGL(k_script_count, dim3(grid_for(nr, kBlock)), dim3(kBlock), 0, s, S, h->cnt.as<uint32_t>());
@@ -501,12 +502,15 @@ kmx_status check_front(const char* fn, const kmx_index* index, const kmx_loci* l
 }
 
 // host == true: ranks / roff are host arrays that go up on the stream of the call that filled the alignments; else device arrays
-// and the caller's stream
+// and the caller's stream.  P != nullptr: its best2 selects in the place of the alignments' best (device form; ranks_len letters may
+// be read)
 kmx_status script_call(const char* fn, const kmx_index* index, const kmx_loci* loci, const kmx_alignments* al, const void* ranks, const void* roff,
-                       uint64_t nr, const kmx_script_options* o, bool host, hipStream_t stream, kmx_scripts** inout)
+                       uint64_t nr, const kmx_script_options* o, bool host, hipStream_t stream, kmx_scripts** inout,
+                       const kmx::PlacementsAccess* P = nullptr, uint64_t ranks_len = ~uint64_t(0))
 {
     SC_OK(check_front(fn, index, loci, al, roff, o, inout));
     const std::string who = std::string(fn) + ": ";
+    if (P && (o->flags & KMX_SCRIPT_ALL)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "KMX_SCRIPT_ALL ignores best: not for the winners of a fold");
     const kmx::LociAccess L = kmx::loci_access(loci);
     const kmx::AlignAccess A = kmx::alignments_access(al);
     kmx_scripts* h = *inout;
@@ -518,10 +522,12 @@ kmx_status script_call(const char* fn, const kmx_index* index, const kmx_loci* l
     if (nr != A.nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "nr differs from the alignments handle's");
     if (A.n_loci != L.n_loci) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments handle's n_loci differs from the loci handle's");
     if (A.device != L.device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the loci and the alignments live on different devices");
+    if (P && P->nr2 != nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "the placements are not those of these reads: nr differs");
+    if (P && nr && P->device != L.device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the placements and the loci live on different devices");
     kmx::IndexAccess X{};
     if (!kmx::index_access_on(index, L.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the loci live on a device that holds no replica of this index");
     if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
-    uint64_t n_letters = ~uint64_t(0);
+    uint64_t n_letters = ranks_len;
     if (host) {
         const uint64_t* ro = static_cast<const uint64_t*>(roff);
         if (nr && ro[0] != 0) return refuse(KMX_ERR_INVALID_ARGUMENT, "roff[0] must be 0");
@@ -556,13 +562,20 @@ kmx_status script_call(const char* fn, const kmx_index* index, const kmx_loci* l
         d_ranks = h->ranks.p;
         d_roff = h->roff.p;
     }
-    if (st == KMX_OK) st = script_run(X, L, A, d_ranks, d_roff, n_letters, *o, s, h);
+    if (st == KMX_OK) st = script_run(X, L, A, d_ranks, d_roff, n_letters, P ? P->best2 : A.best, *o, s, h);
     if (host || st != KMX_OK) (void)hipStreamSynchronize(s);   // the caller's arrays are free again; a failed call leaves nothing in flight
     if (st != KMX_OK) h->clear();                              // the handle holds an empty result, not half of this one
     return st;
 }
 
 } // namespace
+
+kmx_status kmx::scripts_with_best(const char* fn, const kmx_index* index, const kmx_loci* loci, const kmx_alignments* alignments, const void* d_ranks,
+                                  const void* d_roff, uint64_t nr, uint64_t ranks_len, const kmx_script_options* options, hipStream_t stream,
+                                  const kmx::PlacementsAccess& P, kmx_scripts** inout)
+{
+    return script_call(fn, index, loci, alignments, d_ranks, d_roff, nr, options, false, stream, inout, &P, ranks_len);
+}
 
 extern "C" {
 

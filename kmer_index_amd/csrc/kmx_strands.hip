@@ -1,0 +1,488 @@
+// Both strands of the read-mapping chain (kmx_reads_strands, kmx_alignments_fold_strands, kmx_placements_scripts; include/kmx.h).
+// The reverse complement of a read is just another read: the doubled batch goes through kmx_search_windows_device,
+// kmx_windows_vote, kmx_loci_align_device and kmx_alignments_scripts_device as they are, and the two strands of every read are
+// folded into one placement on the device.
+//
+//   k_strand_reads     a wave per public read: lane j copies letter j to internal read 2i and the complement of letter m - 1 - j
+//                      to internal read 2i + 1, 64 neighbouring bytes per load and per store; lane 0 writes the two offsets
+//   k_strand_fold      a wave per public read: the winner from best[2i] / best[2i + 1], then the lanes stride over the loci of both
+//                      strands and min-reduce the distances of those that lie elsewhere; lane 0 writes; the batch totals go
+//                      through LDS and one atomic per workgroup
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+#include "kmx_kernels.h"
+#include "kmx_vote.h"
+
+namespace {
+
+constexpr uint32_t kBlock = 256;
+constexpr uint32_t kWave = 64;
+constexpr uint32_t kNoBest = 0xFFFFFFFFu;
+constexpr uint64_t kMaxReads = uint64_t(1) << 30;
+constexpr uint64_t kMaxLetters = uint64_t(1) << 62;
+enum { CTR_N_PLACED = 0, CTR_N_REVERSE, CTR_N_AMBIGUOUS, CTR_COUNT };
+
+#define ST_TRY(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t e__ = (expr);                                                                       \
+        if (e__ != hipSuccess) {                                                                       \
+            (void)hipGetLastError();                                                                   \
+            return kmx::set_error(e__ == hipErrorOutOfMemory ? KMX_ERR_OUT_OF_MEMORY : KMX_ERR_HIP,    \
+                                  std::string(#expr) + ": " + hipGetErrorString(e__));                 \
+        }                                                                                              \
+    } while (0)
+#define ST_OK(expr) do { const kmx_status st__ = (expr); if (st__ != KMX_OK) return st__; } while (0)
+
+using kmx::Buf;
+using Pinned = kmx::PinnedArr;
+
+struct DeviceGuard {
+    int prev = -1;
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+inline unsigned int grid_for(uint64_t n, uint64_t per_block) { return unsigned(std::max<uint64_t>((n + per_block - 1) / per_block, 1)); }
+
+// the complement table as kernel arguments: 256 entries, the identity outside the alphabet
+struct CompWords { uint32_t w[64]; };
+
+// ---- the doubled batch ---------------------------------------------------------------------------------------------------------------
+// total = roff[nr]: a read whose offsets decrease or leave [0, total] is written as an empty pair (device form: foreign offsets), so
+// every store lands inside ranks2[2 * total]
+__global__ __launch_bounds__(kBlock) void k_strand_reads(const uint8_t* __restrict__ ranks, const uint64_t* __restrict__ roff, uint64_t nr,
+                                                         uint64_t total, CompWords comp, uint8_t* __restrict__ ranks2, uint64_t* __restrict__ roff2)
+{
+    __shared__ uint32_t s_comp[64];
+    if (threadIdx.x < 64) s_comp[threadIdx.x] = comp.w[threadIdx.x];
+    __syncthreads();
+    const uint8_t* table = reinterpret_cast<const uint8_t*>(s_comp);
+    const uint32_t lane = threadIdx.x % kWave;
+    const uint64_t i = uint64_t(blockIdx.x) * (kBlock / kWave) + threadIdx.x / kWave;
+    if (i >= nr) return;
+    const uint64_t a = min(roff[i], total), b = roff[i + 1];
+    const uint64_t m = b >= a && b <= total ? b - a : 0;
+    const uint8_t* q = ranks + a;
+    uint8_t* fw = ranks2 + 2 * a;
+    uint8_t* rv = fw + m;
+    for (uint64_t j = lane; j < m; j += kWave) {
+        fw[j] = q[j];
+        rv[j] = table[q[m - 1 - j]];
+    }
+    if (lane == 0) {
+        roff2[2 * i] = 2 * a;
+        roff2[2 * i + 1] = 2 * a + m;
+        if (i + 1 == nr) roff2[2 * nr] = 2 * total;
+    }
+}
+
+// ---- the fold ------------------------------------------------------------------------------------------------------------------------
+struct FoldIn {
+    const uint64_t* locus_off;     // [nr2 + 1]
+    const uint8_t* dist;           // [n_loci]
+    const uint32_t* start;
+    const uint32_t* end;
+    const uint32_t* best;          // [nr2]
+    uint64_t nr, n_loci;           // public reads
+};
+
+struct FoldOut {
+    uint32_t* locus;               // [nr]
+    uint8_t* strand;
+    uint8_t* dist;
+    uint32_t* start;
+    uint32_t* end;
+    uint8_t* second;
+    uint32_t* best2;               // [nr2]
+    unsigned long long* ctr;
+};
+
+__global__ __launch_bounds__(kBlock) void k_strand_fold(FoldIn F, FoldOut O)
+{
+    __shared__ unsigned int s_placed, s_rev, s_amb;
+    if (threadIdx.x == 0) { s_placed = 0; s_rev = 0; s_amb = 0; }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x % kWave;
+    const uint64_t i = uint64_t(blockIdx.x) * (kBlock / kWave) + threadIdx.x / kWave;
+    if (i < F.nr) {
+        // the loci of the two strands: [a, b) forward, [b, c) reverse, inside the arrays whatever the offsets hold
+        const uint64_t a = min(F.locus_off[2 * i], F.n_loci);
+        const uint64_t b = min(max(F.locus_off[2 * i + 1], a), F.n_loci);
+        const uint64_t c = min(max(F.locus_off[2 * i + 2], b), F.n_loci);
+        const uint32_t bf = F.best[2 * i], br = F.best[2 * i + 1];
+        // step 1: the winner, the better of the two bests; the forward strand wins a tie
+        uint32_t df = KMX_ALIGN_NONE, dr = KMX_ALIGN_NONE;
+        if (bf != kNoBest && bf < b - a) df = F.dist[a + bf];
+        if (br != kNoBest && br < c - b) dr = F.dist[b + br];
+        const bool okf = df < KMX_ALIGN_SKIPPED, okr = dr < KMX_ALIGN_SKIPPED;
+        const bool placed = okf || okr;
+        const uint32_t sw = okf && (!okr || df <= dr) ? 0u : 1u;
+        const uint64_t w = sw == 0 ? a + bf : b + br;
+        uint32_t wd = KMX_ALIGN_NONE, ws = 0, we = 0;
+        if (placed) { wd = sw == 0 ? df : dr; ws = F.start[w]; we = F.end[w]; }
+        // step 2: the least distance of an aligned locus elsewhere
+        uint32_t second = KMX_ALIGN_NONE;
+        if (placed)
+            for (uint64_t l = a + lane; l < c; l += kWave) {
+                const uint32_t d = F.dist[l];
+                if (d >= KMX_ALIGN_SKIPPED || l == w) continue;
+                const uint32_t s = l < b ? 0u : 1u;
+                if (s != sw || max(F.start[l], ws) >= min(F.end[l], we)) second = min(second, d);
+            }
+        for (int off = kWave / 2; off > 0; off >>= 1) second = min(second, uint32_t(__shfl_xor(second, off)));
+        if (lane == 0) {
+            O.locus[i] = placed ? uint32_t(w) : kNoBest;
+            O.strand[i] = placed ? uint8_t(sw) : uint8_t(255);
+            O.dist[i] = uint8_t(wd);
+            O.start[i] = ws;
+            O.end[i] = we;
+            O.second[i] = uint8_t(second);
+            O.best2[2 * i] = placed && sw == 0 ? bf : kNoBest;
+            O.best2[2 * i + 1] = placed && sw == 1 ? br : kNoBest;
+            if (placed) {
+                atomicAdd(&s_placed, 1u);
+                if (sw) atomicAdd(&s_rev, 1u);
+                if (second == wd) atomicAdd(&s_amb, 1u);
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_placed) atomicAdd(&O.ctr[CTR_N_PLACED], (unsigned long long)s_placed);
+        if (s_rev) atomicAdd(&O.ctr[CTR_N_REVERSE], (unsigned long long)s_rev);
+        if (s_amb) atomicAdd(&O.ctr[CTR_N_AMBIGUOUS], (unsigned long long)s_amb);
+    }
+}
+
+} // namespace
+
+struct kmx_strand_reads {
+    int device = 0;
+    hipStream_t stream = nullptr;          // the stream of the call that filled the handle
+    hipStream_t own = nullptr;             // the stream of the host form, created at its first call
+    uint64_t nr2 = 0, letters2 = 0;        // internal reads and their letters
+    Buf raw, roff, ranks2, roff2;
+    Pinned h_total;
+    void release()
+    {
+        for (Buf* b : {&raw, &roff, &ranks2, &roff2}) b->release();
+        h_total.release();
+        if (own) (void)hipStreamDestroy(own);
+        own = nullptr;
+    }
+    void clear() { nr2 = 0; letters2 = 0; }
+};
+
+struct kmx_placements {
+    int device = 0;
+    hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
+    uint64_t nr = 0, n_placed = 0, n_reverse = 0, n_ambiguous = 0;
+    Buf locus, strand, dist, start, end, second, best2, ctr;
+    Pinned h_ctr, h_locus, h_strand, h_dist, h_start, h_end, h_second, h_best2;
+    bool host_valid = false, host_best2_valid = false;
+    void release()
+    {
+        for (Buf* b : {&locus, &strand, &dist, &start, &end, &second, &best2, &ctr}) b->release();
+        for (Pinned* b : {&h_ctr, &h_locus, &h_strand, &h_dist, &h_start, &h_end, &h_second, &h_best2}) b->release();
+    }
+    void clear() { nr = n_placed = n_reverse = n_ambiguous = 0; host_valid = false; host_best2_valid = false; }
+};
+
+kmx::PlacementsAccess kmx::placements_access(const kmx_placements* p)
+{
+    return PlacementsAccess{p->device, p->stream, 2 * p->nr, p->best2.as<uint32_t>()};
+}
+
+namespace {
+
+// host == true: ranks / roff are host arrays that go up on the handle's own stream; else device arrays and the caller's stream
+kmx_status strands_call(const char* fn, const kmx_index* index, const void* ranks, const void* roff, uint64_t nr, const uint8_t* complement,
+                        bool host, hipStream_t stream, kmx_strand_reads** inout)
+{
+    const std::string who = std::string(fn) + ": ";
+    if (!index) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "index is NULL");
+    if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
+    kmx_strand_reads* h = *inout;
+    auto refuse = [&](kmx_status st, const std::string& msg) {
+        if (h) h->clear();
+        return kmx::set_error(st, who + msg);
+    };
+    if (!complement) return refuse(KMX_ERR_INVALID_ARGUMENT, "NULL complement table");
+    kmx::IndexAccess X = kmx::index_access(index);
+    uint8_t comp[256];
+    if (kmx::check_complement(who, complement, X.sigma, comp) != KMX_OK) { if (h) h->clear(); return KMX_ERR_INVALID_ARGUMENT; }
+    if (nr && !roff) return refuse(KMX_ERR_INVALID_ARGUMENT, "roff is NULL");
+    if (nr >= kMaxReads) return refuse(KMX_ERR_TOO_LARGE, "2^30 or more reads: split the batch");
+    uint64_t total = 0;
+    if (host) {
+        const uint64_t* ro = static_cast<const uint64_t*>(roff);
+        if (nr && ro[0] != 0) return refuse(KMX_ERR_INVALID_ARGUMENT, "roff[0] must be 0");
+        for (uint64_t i = 0; i < nr; ++i)
+            if (ro[i + 1] < ro[i]) return refuse(KMX_ERR_INVALID_ARGUMENT, "roff must be non-decreasing");
+        total = nr ? ro[nr] : 0;
+        if (total && !ranks) return refuse(KMX_ERR_INVALID_ARGUMENT, "NULL read letters (ranks)");
+        if (total > kMaxLetters) return refuse(KMX_ERR_TOO_LARGE, "more than 2^62 letters: split the batch");
+    } else if (nr) {                                           // the replica on the device that owns the reads
+        hipPointerAttribute_t attr{};
+        if (hipPointerGetAttributes(&attr, ranks ? ranks : roff) != hipSuccess) {
+            (void)hipGetLastError();
+            return refuse(KMX_ERR_INVALID_ARGUMENT, "d_ranks is not a device pointer");
+        }
+        if (!kmx::index_access_on(index, attr.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the reads live on a device that holds no replica of this index");
+    }
+    DeviceGuard dg;
+    ST_TRY(hipGetDevice(&dg.prev));
+    if (h && h->device != X.device) {                          // buffers of another device: start afresh on this one
+        (void)hipSetDevice(h->device);
+        h->release();
+    }
+    ST_TRY(hipSetDevice(X.device));
+    if (!h) h = new kmx_strand_reads();
+    *inout = h;
+    h->device = X.device;
+    h->clear();
+    auto run = [&]() -> kmx_status {
+        (void)hipGetLastError();
+        if (host && !h->own) ST_TRY(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
+        hipStream_t s = host ? h->own : stream;
+        h->stream = s;
+        ST_TRY(h->roff2.ensure((2 * nr + 1) * 8));
+        if (nr == 0) {
+            ST_TRY(h->ranks2.ensure(1));
+            ST_TRY(hipMemsetAsync(h->roff2.p, 0, 8, s));
+            return KMX_OK;
+        }
+        const uint8_t* d_ranks = static_cast<const uint8_t*>(ranks);
+        const uint64_t* d_roff = static_cast<const uint64_t*>(roff);
+        if (host) {
+            ST_TRY(h->raw.ensure(std::max<uint64_t>(total, 1)));
+            ST_TRY(h->roff.ensure((nr + 1) * 8));
+            if (total) ST_TRY(hipMemcpyAsync(h->raw.p, ranks, total, hipMemcpyHostToDevice, s));
+            ST_TRY(hipMemcpyAsync(h->roff.p, roff, (nr + 1) * 8, hipMemcpyHostToDevice, s));
+            d_ranks = h->raw.as<uint8_t>();
+            d_roff = h->roff.as<uint64_t>();
+        } else {                                               // one 8-byte read-back: the letters of the batch
+            if (!h->h_total.grow(8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host allocation failed");
+            ST_TRY(hipMemcpyAsync(h->h_total.p, d_roff + nr, 8, hipMemcpyDeviceToHost, s));
+            ST_TRY(hipStreamSynchronize(s));
+            total = h->h_total.as<uint64_t>()[0];
+            if (total > kMaxLetters) return kmx::set_error(KMX_ERR_TOO_LARGE, who + "more than 2^62 letters: split the batch");
+        }
+        ST_TRY(h->ranks2.ensure(std::max<uint64_t>(2 * total, 1)));
+        CompWords cw;
+        std::memcpy(cw.w, comp, sizeof cw.w);
+        hipLaunchKernelGGL(k_strand_reads, dim3(grid_for(nr, kBlock / kWave)), dim3(kBlock), 0, s, d_ranks, d_roff, nr, total, cw, h->ranks2.as<uint8_t>(),
+                           h->roff2.as<uint64_t>());
+        ST_TRY(hipGetLastError());
+        h->letters2 = 2 * total;
+        return KMX_OK;
+    };
+    const kmx_status st = run();
+    if ((host || st != KMX_OK) && h->stream) (void)hipStreamSynchronize(h->stream);   // the caller's arrays are free again
+    if (st == KMX_OK) h->nr2 = 2 * nr;
+    else h->clear();
+    return st;
+}
+
+kmx_status read_counters(hipStream_t s, const void* d, Pinned& h)
+{
+    if (!h.grow(CTR_COUNT * 8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_alignments_fold_strands: page-locked host allocation failed");
+    ST_TRY(hipMemcpyAsync(h.p, d, CTR_COUNT * 8, hipMemcpyDeviceToHost, s));
+    ST_TRY(hipStreamSynchronize(s));
+    return KMX_OK;
+}
+
+kmx_status fold_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, hipStream_t s, kmx_placements* p)
+{
+    const uint64_t nr = L.nr / 2;
+    p->device = L.device; p->stream = s;
+    p->clear();
+    (void)hipGetLastError();
+    if (nr == 0) return KMX_OK;
+    for (Buf* b : {&p->locus, &p->start, &p->end}) ST_TRY(b->ensure(nr * 4));
+    for (Buf* b : {&p->strand, &p->dist, &p->second}) ST_TRY(b->ensure(nr));
+    ST_TRY(p->best2.ensure(2 * nr * 4));
+    ST_TRY(p->ctr.ensure(CTR_COUNT * 8));
+    unsigned long long* ctr = p->ctr.as<unsigned long long>();
+    ST_TRY(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
+    const FoldIn F{L.locus_off, A.dist, A.start, A.end, A.best, nr, L.n_loci};
+    const FoldOut O{p->locus.as<uint32_t>(), p->strand.as<uint8_t>(), p->dist.as<uint8_t>(), p->start.as<uint32_t>(), p->end.as<uint32_t>(),
+                    p->second.as<uint8_t>(), p->best2.as<uint32_t>(), ctr};
+    hipLaunchKernelGGL(k_strand_fold, dim3(grid_for(nr, kBlock / kWave)), dim3(kBlock), 0, s, F, O);
+    ST_TRY(hipGetLastError());
+    ST_OK(read_counters(s, ctr, p->h_ctr));
+    p->nr = nr;
+    p->n_placed = p->h_ctr.as<uint64_t>()[CTR_N_PLACED];
+    p->n_reverse = p->h_ctr.as<uint64_t>()[CTR_N_REVERSE];
+    p->n_ambiguous = p->h_ctr.as<uint64_t>()[CTR_N_AMBIGUOUS];
+    return KMX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+kmx_status kmx_reads_strands(const kmx_index* index, const uint8_t* ranks, const uint64_t* roff, uint64_t nr, const uint8_t* complement,
+                             kmx_strand_reads** inout)
+{
+    return strands_call("kmx_reads_strands", index, ranks, roff, nr, complement, true, nullptr, inout);
+}
+
+kmx_status kmx_reads_strands_device(const kmx_index* index, const void* d_ranks, const void* d_roff, uint64_t nr, const uint8_t* complement,
+                                    void* stream, kmx_strand_reads** inout)
+{
+    return strands_call("kmx_reads_strands_device", index, d_ranks, d_roff, nr, complement, false, static_cast<hipStream_t>(stream), inout);
+}
+
+kmx_status kmx_strand_reads_view_device(const kmx_strand_reads* h, const uint8_t** d_ranks2, const uint64_t** d_roff2, uint64_t* nr2, void** stream)
+{
+    if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_strand_reads_view_device: strand reads handle is NULL");
+    if (d_ranks2) *d_ranks2 = h->ranks2.as<uint8_t>();
+    if (d_roff2) *d_roff2 = h->roff2.as<uint64_t>();
+    if (nr2) *nr2 = h->nr2;
+    if (stream) *stream = h->stream;
+    return KMX_OK;
+}
+
+void kmx_strand_reads_free(kmx_strand_reads* h)
+{
+    if (!h) return;
+    int prev = -1;
+    const bool have = hipGetDevice(&prev) == hipSuccess;
+    (void)hipSetDevice(h->device);
+    if (h->own) (void)hipStreamSynchronize(h->own);            // nothing of this handle's is in flight on the stream that goes
+    h->release();
+    if (have) (void)hipSetDevice(prev);
+    delete h;
+}
+
+kmx_status kmx_alignments_fold_strands(const kmx_loci* loci, const kmx_alignments* alignments, const kmx_fold_options* o, void* stream,
+                                       kmx_placements** inout)
+{
+    const std::string who = "kmx_alignments_fold_strands: ";
+    if (!loci) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "loci handle is NULL");
+    if (!alignments) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "alignments handle is NULL");
+    if (!o) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options is NULL");
+    if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
+    if (o->struct_size < sizeof(kmx_fold_options)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
+    if (o->flags != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "flags must be 0");
+    const kmx::LociAccess L = kmx::loci_access(loci);
+    const kmx::AlignAccess A = kmx::alignments_access(alignments);
+    kmx_placements* p = *inout;
+    auto refuse = [&](kmx_status st, const std::string& msg) {
+        if (p) p->clear();
+        return kmx::set_error(st, who + msg);
+    };
+    if (L.nr != A.nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments handle's nr differs from the loci handle's");
+    if (L.nr & 1) return refuse(KMX_ERR_INVALID_ARGUMENT, "an odd number of reads: not the loci of a doubled batch");
+    if (A.n_loci != L.n_loci) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments handle's n_loci differs from the loci handle's");
+    if (A.device != L.device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the loci and the alignments live on different devices");
+    DeviceGuard dg;
+    ST_TRY(hipGetDevice(&dg.prev));
+    ST_TRY(hipSetDevice(L.device));
+    if (p && p->device != L.device) {                          // buffers of another device: start afresh on this one
+        (void)hipSetDevice(p->device);
+        p->release();
+        (void)hipSetDevice(L.device);
+    }
+    if (!p) p = new kmx_placements();
+    *inout = p;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : A.stream;
+    const kmx_status st = fold_run(L, A, s, p);
+    if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
+        (void)hipStreamSynchronize(s);
+        p->clear();
+    }
+    return st;
+}
+
+kmx_status kmx_placements_counts(const kmx_placements* p, uint64_t* nr, uint64_t* n_placed, uint64_t* n_reverse, uint64_t* n_ambiguous)
+{
+    if (!p) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_placements_counts: placements handle is NULL");
+    if (nr) *nr = p->nr;
+    if (n_placed) *n_placed = p->n_placed;
+    if (n_reverse) *n_reverse = p->n_reverse;
+    if (n_ambiguous) *n_ambiguous = p->n_ambiguous;
+    return KMX_OK;
+}
+
+kmx_status kmx_placements_view_device(const kmx_placements* p, const uint32_t** d_locus, const uint8_t** d_strand, const uint8_t** d_dist,
+                                      const uint32_t** d_start, const uint32_t** d_end, const uint8_t** d_second, const uint32_t** d_best2)
+{
+    if (!p) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_placements_view_device: placements handle is NULL");
+    const bool any = p->nr != 0;
+    if (d_locus) *d_locus = any ? p->locus.as<uint32_t>() : nullptr;
+    if (d_strand) *d_strand = any ? p->strand.as<uint8_t>() : nullptr;
+    if (d_dist) *d_dist = any ? p->dist.as<uint8_t>() : nullptr;
+    if (d_start) *d_start = any ? p->start.as<uint32_t>() : nullptr;
+    if (d_end) *d_end = any ? p->end.as<uint32_t>() : nullptr;
+    if (d_second) *d_second = any ? p->second.as<uint8_t>() : nullptr;
+    if (d_best2) *d_best2 = any ? p->best2.as<uint32_t>() : nullptr;
+    return KMX_OK;
+}
+
+kmx_status kmx_placements_view(kmx_placements* p, const uint32_t** locus, const uint8_t** strand, const uint8_t** dist, const uint32_t** start,
+                               const uint32_t** end, const uint8_t** second, const uint32_t** best2)
+{
+    if (!p) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_placements_view: placements handle is NULL");
+    const uint64_t nr = p->nr, room = std::max<uint64_t>(nr, 1);
+    const bool want_best2 = best2 && !p->host_best2_valid;
+    if (!p->host_valid || want_best2) {
+        if (!p->h_locus.grow(room * 4) || !p->h_start.grow(room * 4) || !p->h_end.grow(room * 4) || !p->h_strand.grow(room) || !p->h_dist.grow(room) ||
+            !p->h_second.grow(room) || (best2 && !p->h_best2.grow(2 * room * 4)))
+            return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_placements_view: page-locked host allocation failed");
+        if (nr) {
+            DeviceGuard dg;
+            ST_TRY(hipGetDevice(&dg.prev));
+            ST_TRY(hipSetDevice(p->device));
+            hipStream_t s = p->stream;
+            if (!p->host_valid) {                              // 15 bytes per read
+                ST_TRY(hipMemcpyAsync(p->h_locus.p, p->locus.p, nr * 4, hipMemcpyDeviceToHost, s));
+                ST_TRY(hipMemcpyAsync(p->h_start.p, p->start.p, nr * 4, hipMemcpyDeviceToHost, s));
+                ST_TRY(hipMemcpyAsync(p->h_end.p, p->end.p, nr * 4, hipMemcpyDeviceToHost, s));
+                ST_TRY(hipMemcpyAsync(p->h_strand.p, p->strand.p, nr, hipMemcpyDeviceToHost, s));
+                ST_TRY(hipMemcpyAsync(p->h_dist.p, p->dist.p, nr, hipMemcpyDeviceToHost, s));
+                ST_TRY(hipMemcpyAsync(p->h_second.p, p->second.p, nr, hipMemcpyDeviceToHost, s));
+            }
+            if (want_best2) ST_TRY(hipMemcpyAsync(p->h_best2.p, p->best2.p, 2 * nr * 4, hipMemcpyDeviceToHost, s));   // only when asked for
+            ST_TRY(hipStreamSynchronize(s));
+        }
+        p->host_valid = true;
+        if (best2) p->host_best2_valid = true;
+    }
+    if (locus) *locus = p->h_locus.as<uint32_t>();
+    if (strand) *strand = p->h_strand.as<uint8_t>();
+    if (dist) *dist = p->h_dist.as<uint8_t>();
+    if (start) *start = p->h_start.as<uint32_t>();
+    if (end) *end = p->h_end.as<uint32_t>();
+    if (second) *second = p->h_second.as<uint8_t>();
+    if (best2) *best2 = p->h_best2.as<uint32_t>();
+    return KMX_OK;
+}
+
+void kmx_placements_free(kmx_placements* p)
+{
+    if (!p) return;
+    int prev = -1;
+    const bool have = hipGetDevice(&prev) == hipSuccess;
+    (void)hipSetDevice(p->device);
+    p->release();                                              // (hipFree waits for the kernels of the last call)
+    if (have) (void)hipSetDevice(prev);
+    delete p;
+}
+
+kmx_status kmx_placements_scripts(const kmx_index* index, const kmx_strand_reads* reads, const kmx_loci* loci, const kmx_alignments* alignments,
+                                  const kmx_placements* placements, const kmx_script_options* options, kmx_scripts** inout)
+{
+    const std::string who = "kmx_placements_scripts: ";
+    if (!reads) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "strand reads handle is NULL");
+    if (!placements) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "placements handle is NULL");
+    const kmx::PlacementsAccess P = kmx::placements_access(placements);
+    return kmx::scripts_with_best("kmx_placements_scripts", index, loci, alignments, reads->ranks2.p, reads->roff2.p, reads->nr2, reads->letters2, options,
+                                  reads->stream, P, inout);
+}
+
+} // extern "C"

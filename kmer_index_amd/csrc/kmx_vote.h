@@ -54,4 +54,20 @@ struct AlignAccess {
 };
 AlignAccess alignments_access(const kmx_alignments* a);   // kmx_align.hip
 
+// What the scripts of the winners (kmx_placements_scripts) need from a placements handle (kmx_strands.hip owns struct
+// kmx_placements): best2 belongs to the handle and stays as it is (the scripts only read it).  A handle that no fold has filled yet
+// has nr2 = 0.
+struct PlacementsAccess {
+    int device;
+    hipStream_t stream;            // the stream of the fold that filled the handle
+    uint64_t nr2;                  // internal reads: twice the public ones
+    const uint32_t* best2;         // [nr2]: best[] of the alignments with the losing strand's entry cleared
+};
+PlacementsAccess placements_access(const kmx_placements* p);   // kmx_strands.hip
+// kmx_script.hip: kmx_alignments_scripts_device on the reads d_ranks / d_roff (at most ranks_len letters) with P.best2 in the place
+// of the alignments' best; `fn` names the entry point in the error text
+kmx_status scripts_with_best(const char* fn, const kmx_index* index, const kmx_loci* loci, const kmx_alignments* alignments, const void* d_ranks,
+                             const void* d_roff, uint64_t nr, uint64_t ranks_len, const kmx_script_options* options, hipStream_t stream,
+                             const PlacementsAccess& P, kmx_scripts** inout);
+
 } // namespace kmx

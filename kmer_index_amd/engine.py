@@ -43,6 +43,9 @@ EXPORTS = [
     "kmx_alignments_free",
     "kmx_alignments_scripts", "kmx_alignments_scripts_device", "kmx_scripts_counts", "kmx_scripts_view", "kmx_scripts_view_device",
     "kmx_scripts_free",
+    "kmx_reads_strands", "kmx_reads_strands_device", "kmx_strand_reads_view_device", "kmx_strand_reads_free",
+    "kmx_alignments_fold_strands", "kmx_placements_counts", "kmx_placements_view", "kmx_placements_view_device", "kmx_placements_free",
+    "kmx_placements_scripts",
 ]
 
 
@@ -78,6 +81,10 @@ class AlignOptions(C.Structure):
 
 class ScriptOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("scratch_bytes", C.c_uint64)]
+
+
+class FoldOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class KernelStat(C.Structure):
@@ -223,6 +230,24 @@ def lib():
         L.kmx_scripts_view_device.restype = C.c_int
         L.kmx_scripts_view_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp)]
         L.kmx_scripts_free.argtypes = [vp]
+        L.kmx_reads_strands.restype = C.c_int
+        L.kmx_reads_strands.argtypes = [vp, vp, vp, u64, vp, P(vp)]
+        L.kmx_reads_strands_device.restype = C.c_int
+        L.kmx_reads_strands_device.argtypes = [vp, vp, vp, u64, vp, vp, P(vp)]
+        L.kmx_strand_reads_view_device.restype = C.c_int
+        L.kmx_strand_reads_view_device.argtypes = [vp, P(vp), P(vp), P(u64), P(vp)]
+        L.kmx_strand_reads_free.argtypes = [vp]
+        L.kmx_alignments_fold_strands.restype = C.c_int
+        L.kmx_alignments_fold_strands.argtypes = [vp, vp, P(FoldOptions), vp, P(vp)]
+        L.kmx_placements_counts.restype = C.c_int
+        L.kmx_placements_counts.argtypes = [vp, P(u64), P(u64), P(u64), P(u64)]
+        L.kmx_placements_view.restype = C.c_int
+        L.kmx_placements_view.argtypes = [vp] + [P(vp)] * 7
+        L.kmx_placements_view_device.restype = C.c_int
+        L.kmx_placements_view_device.argtypes = [vp] + [P(vp)] * 7
+        L.kmx_placements_free.argtypes = [vp]
+        L.kmx_placements_scripts.restype = C.c_int
+        L.kmx_placements_scripts.argtypes = [vp, vp, vp, vp, vp, P(ScriptOptions), P(vp)]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -529,6 +554,14 @@ class Alignments:
         _check(lib().kmx_alignments_scripts_device(index._h, loci._h, self._h, d_ranks_ptr, d_roff_ptr, nr, C.byref(o), stream or None, C.byref(s._h)))
         return s
 
+    def fold_strands(self, loci, stream=0, placements=None):
+        """kmx_alignments_fold_strands: these are the alignments of a doubled batch (StrandReads) and `loci` its loci; one placement
+        per public read.  stream=0: the stream that filled this handle.  Returns a Placements (`placements` reuses one)."""
+        p = placements or Placements()
+        o = FoldOptions(C.sizeof(FoldOptions), 0)
+        _check(lib().kmx_alignments_fold_strands(loci._h, self._h, C.byref(o), stream or None, C.byref(p._h)))
+        return p
+
     def close(self):
         if self._h:
             lib().kmx_alignments_free(self._h)
@@ -577,6 +610,97 @@ class Scripts:
         if self._h:
             lib().kmx_scripts_free(self._h)
             self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class StrandReads:
+    """Owns a kmx_strand_reads handle (kmx_reads_strands): every read and its reverse complement, on the device.  After
+    Index.strand_reads the handle owns the stream everything behind it runs on: close it last."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+
+    def counts(self):
+        _, _, nr2, _ = self.device_ptrs()
+        return {"nr": nr2 // 2, "nr2": nr2}
+
+    def device_ptrs(self):
+        """(d_ranks2, d_roff2, nr2, stream): kmx_strand_reads_view_device."""
+        a, b, n, s = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_void_p()
+        _check(lib().kmx_strand_reads_view_device(self._h, C.byref(a), C.byref(b), C.byref(n), C.byref(s)))
+        return a.value, b.value, int(n.value), s.value
+
+    def close(self):
+        if self._h:
+            lib().kmx_strand_reads_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Placements:
+    """Owns a kmx_placements handle (kmx_alignments_fold_strands): one placement per public read of a doubled batch."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        self._reads = None          # the StrandReads whose stream the fold ran on: it must outlive the views
+
+    def counts(self):
+        v = [C.c_uint64() for _ in range(4)]
+        _check(lib().kmx_placements_counts(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(["nr", "n_placed", "n_reverse", "n_ambiguous"], [int(x.value) for x in v]))
+
+    def host(self, best2=True):
+        """(locus[nr] u32, strand u8, dist u8, start u32, end u32, second u8, best2[2 nr] u32) as numpy copies; best2=False
+        leaves that array on the device (the tuple then has six entries)."""
+        nr = self.counts()["nr"]
+        p = [C.c_void_p() for _ in range(7)]
+        _check(lib().kmx_placements_view(self._h, *[C.byref(x) for x in p[:6]], C.byref(p[6]) if best2 else None))
+        dt = [np.uint32, np.uint8, np.uint8, np.uint32, np.uint32, np.uint8]
+        out = [_view(x.value, nr, d) for x, d in zip(p, dt)]
+        if best2:
+            out.append(_view(p[6].value, 2 * nr, np.uint32))
+        return tuple(x.copy() for x in out)
+
+    def device_ptrs(self):
+        """(d_locus, d_strand, d_dist, d_start, d_end, d_second, d_best2): kmx_placements_view_device."""
+        p = [C.c_void_p() for _ in range(7)]
+        _check(lib().kmx_placements_view_device(self._h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def scripts(self, index, reads, loci, alignments, m=False, scratch_bytes=0, scripts=None):
+        """kmx_placements_scripts: the CIGAR of every placed read's winner (for a reverse placement that of the reverse complement
+        against the forward text, as SAM has it), on the stream of `reads`.  Returns a Scripts over the internal reads."""
+        s = scripts or Scripts()
+        o = Alignments._script_options(False, m, scratch_bytes)
+        _check(lib().kmx_placements_scripts(index._h, reads._h, loci._h, alignments._h, self._h, C.byref(o), C.byref(s._h)))
+        return s
+
+    def cigars(self, scripts):
+        """One CIGAR string per public read from the Scripts of scripts(): "" where the read is unplaced."""
+        strand = self.host(best2=False)[1]
+        read_sel_off = scripts.host()[0]
+        strings = scripts.strings()
+        out = []
+        for i, s in enumerate(strand):
+            r = 2 * i + int(s)
+            out.append(strings[int(read_sel_off[r])] if s != 255 and read_sel_off[r + 1] > read_sel_off[r] else "")
+        return out
+
+    def close(self):
+        if self._h:
+            lib().kmx_placements_free(self._h)
+            self._h = C.c_void_p()
+        self._reads = None
 
     def __del__(self):
         try:
@@ -850,6 +974,56 @@ class Index:
         except Exception:
             loci.close()
             al.close()
+            raise
+
+    def strand_reads(self, ranks, roff, complement, reads=None):
+        """kmx_reads_strands: the reads go up once and the doubled batch (read i, then its reverse complement under the rank table
+        `complement`) is made on the device, on a stream the returned StrandReads owns (`reads` reuses one)."""
+        ranks = np.ascontiguousarray(ranks, np.uint8)
+        roff = np.ascontiguousarray(roff, np.uint64)
+        comp = None if complement is None else np.ascontiguousarray(complement, np.uint8)
+        s = reads or StrandReads()
+        _check(lib().kmx_reads_strands(self._h, ranks.ctypes.data if ranks.size else None, roff.ctypes.data, roff.size - 1,
+                                       comp.ctypes.data if comp is not None else None, C.byref(s._h)))
+        return s
+
+    def strand_reads_device(self, d_ranks_ptr, d_roff_ptr, nr, complement, stream=0, reads=None):
+        """kmx_reads_strands_device: the doubled batch from reads that are on the device already, on a caller-owned hipStream_t."""
+        comp = None if complement is None else np.ascontiguousarray(complement, np.uint8)
+        s = reads or StrandReads()
+        _check(lib().kmx_reads_strands_device(self._h, d_ranks_ptr, d_roff_ptr, nr, comp.ctypes.data if comp is not None else None,
+                                              stream or None, C.byref(s._h)))
+        return s
+
+    def map_reads_strands(self, ranks, roff, w, complement, stride=1, band=0, min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False):
+        """map_reads on both strands: kmx_reads_strands, kmx_search_windows_device, kmx_windows_vote, kmx_loci_align_device and
+        kmx_alignments_fold_strands in a row, all on the stream of the StrandReads.  Returns (StrandReads, Loci, Alignments,
+        Placements): the loci and alignments are those of the doubled batch (internal read 2i is read i, 2i + 1 its reverse
+        complement), the placements one per read.  scripts=True appends kmx_placements_scripts (the CIGARs of the winners)."""
+        if max_span is None:
+            max_span = 0xFFFFFFFF
+        opened = []
+        try:
+            reads = self.strand_reads(ranks, roff, complement)
+            opened.append(reads)
+            d_ranks2, d_roff2, nr2, stream = reads.device_ptrs()
+            r = self.search_windows_device(d_ranks2, d_roff2, nr2, w, stride, stream=stream)
+            try:
+                loci = r.vote(band, min_votes, max_occ)
+            finally:
+                r.close()
+            opened.append(loci)
+            al = loci.align_device(self, d_ranks2, d_roff2, nr2, max_edits, max_span, stream=stream)
+            opened.append(al)
+            pl = al.fold_strands(loci, stream=stream)
+            pl._reads = reads
+            opened.append(pl)
+            if not scripts:
+                return reads, loci, al, pl
+            return reads, loci, al, pl, pl.scripts(self, reads, loci, al)
+        except Exception:
+            for h in reversed(opened):
+                h.close()
             raise
 
     def debug_words(self):

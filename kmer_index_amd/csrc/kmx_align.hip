@@ -22,6 +22,7 @@
 #include <cstring>
 #include <string>
 
+#include "kmx_approx.h"
 #include "kmx_kernels.h"
 #include "kmx_vote.h"
 
@@ -34,26 +35,9 @@ constexpr int kClasses = 5;               // NW = 1, 2, 4, 8, 16
 constexpr uint8_t CLS_OUT = 255;          // a locus that no pass looks at (skipped, or an empty read)
 enum { CTR_CLASS = 0, CTR_ALIGNED_CLASS = kClasses, CTR_CURSOR = 2 * kClasses, CTR_N_ALIGNED = 3 * kClasses, CTR_N_SKIPPED, CTR_PEQ_WORDS, CTR_COUNT };
 
-#define AL_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) {                                                                       \
-            (void)hipGetLastError();                                                                   \
-            return kmx::set_error(e__ == hipErrorOutOfMemory ? KMX_ERR_OUT_OF_MEMORY : KMX_ERR_HIP,    \
-                                  std::string(#expr) + ": " + hipGetErrorString(e__));                 \
-        }                                                                                              \
-    } while (0)
-#define AL_OK(expr) do { const kmx_status st__ = (expr); if (st__ != KMX_OK) return st__; } while (0)
-
 using kmx::Buf;
 using Pinned = kmx::PinnedArr;
-
-struct DeviceGuard {
-    int prev = -1;
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-inline unsigned int grid_for(uint64_t n, uint64_t per_block) { return unsigned(std::max<uint64_t>((n + per_block - 1) / per_block, 1)); }
+using kmx::grid_for;
 
 // what every kernel reads
 struct AlignIn {
@@ -376,14 +360,6 @@ kmx::AlignAccess kmx::alignments_access(const kmx_alignments* a)
 
 namespace {
 
-kmx_status read_counters(hipStream_t s, const void* d, Pinned& h)
-{
-    if (!h.grow(CTR_COUNT * 8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_loci_align: page-locked host allocation failed");
-    AL_TRY(hipMemcpyAsync(h.p, d, CTR_COUNT * 8, hipMemcpyDeviceToHost, s));
-    AL_TRY(hipStreamSynchronize(s));
-    return KMX_OK;
-}
-
 template <int NW>
 void launch_passes(hipStream_t s, const AlignIn& A, const PassIn& F, const PassIn& R, const uint32_t* list, uint32_t* alist, uint64_t cnt,
                    unsigned long long* acnt, kmx_alignments* a)
@@ -399,39 +375,39 @@ kmx_status align_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const 
                      const kmx_align_options& o, hipStream_t s, kmx_alignments* a)
 {
     const uint64_t nr = L.nr, nl = L.n_loci;
-    a->device = L.device; a->stream = s;
+    a->stream = s;
     a->clear();
     (void)hipGetLastError();
-    AL_TRY(a->best.ensure(std::max<uint64_t>(nr, 1) * 4));
-    AL_TRY(a->aligned.ensure(std::max<uint64_t>(nr, 1) * 4));
+    TRY_HIP(a->best.ensure(std::max<uint64_t>(nr, 1) * 4));
+    TRY_HIP(a->aligned.ensure(std::max<uint64_t>(nr, 1) * 4));
     a->nr = nr;
     if (nr == 0) return KMX_OK;
     if (nl == 0) {                                             // no locus: no launch indexes an empty array
-        AL_TRY(hipMemsetAsync(a->best.p, 0xFF, nr * 4, s));
-        AL_TRY(hipMemsetAsync(a->aligned.p, 0, nr * 4, s));
+        TRY_HIP(hipMemsetAsync(a->best.p, 0xFF, nr * 4, s));
+        TRY_HIP(hipMemsetAsync(a->aligned.p, 0, nr * 4, s));
         return KMX_OK;
     }
     if (nl > 0xFFFFFFFFull) return kmx::set_error(KMX_ERR_TOO_LARGE, "kmx_loci_align: 2^32 or more loci: split the reads");
-    AL_OK(kmx::ensure_text(X, s));
-    AL_TRY(a->dist.ensure(nl));
-    AL_TRY(a->start.ensure(nl * 4));
-    AL_TRY(a->end.ensure(nl * 4));
-    AL_TRY(a->lread.ensure(nl * 4));
-    AL_TRY(a->cls.ensure(nl));
-    AL_TRY(a->pcnt.ensure(nr * 4 + 16));
-    AL_TRY(a->peq_off.ensure((nr + 1) * 8));
-    AL_TRY(a->bsum.ensure(kmx::scan_blocks(nr) * 8 + 16));
-    AL_TRY(a->ctr.ensure(CTR_COUNT * 8));
+    TRY_KMX(kmx::ensure_text(X, s));
+    TRY_HIP(a->dist.ensure(nl));
+    TRY_HIP(a->start.ensure(nl * 4));
+    TRY_HIP(a->end.ensure(nl * 4));
+    TRY_HIP(a->lread.ensure(nl * 4));
+    TRY_HIP(a->cls.ensure(nl));
+    TRY_HIP(a->pcnt.ensure(nr * 4 + 16));
+    TRY_HIP(a->peq_off.ensure((nr + 1) * 8));
+    TRY_HIP(a->bsum.ensure(kmx::scan_blocks(nr) * 8 + 16));
+    TRY_HIP(a->ctr.ensure(CTR_COUNT * 8));
     unsigned long long* ctr = a->ctr.as<unsigned long long>();
-    AL_TRY(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
+    TRY_HIP(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
     const AlignIn A{static_cast<const uint8_t*>(d_ranks), static_cast<const uint64_t*>(d_roff), ranks_len, L.locus_off, L.diag, L.span, nr, nl, X.n,
                     X.text->d_words, X.text->w, X.sigma, o.max_edits, o.max_span};
     hipLaunchKernelGGL(k_align_count, dim3(grid_for(nr, kBlock)), dim3(kBlock), 0, s, A, a->pcnt.as<uint32_t>());
     kmx::launch_scan(s, a->pcnt.as<uint32_t>(), nr, a->bsum.as<uint64_t>(), a->peq_off.as<uint64_t>(), ctr + CTR_PEQ_WORDS);
     hipLaunchKernelGGL(k_align_classify, dim3(grid_for(nl, kBlock)), dim3(kBlock), 0, s, A, a->lread.as<uint32_t>(), a->cls.as<uint8_t>(),
                        a->dist.as<uint8_t>(), a->start.as<uint32_t>(), a->end.as<uint32_t>(), ctr);
-    AL_TRY(hipGetLastError());
-    AL_OK(read_counters(s, ctr, a->h_ctr));
+    TRY_HIP(hipGetLastError());
+    TRY_KMX(kmx::read_back("kmx_loci_align", s, ctr, a->h_ctr, CTR_COUNT * 8));
     uint64_t c[CTR_COUNT];
     std::memcpy(c, a->h_ctr.p, sizeof c);
     ClassBase base{};
@@ -440,9 +416,9 @@ kmx_status align_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const 
     if (listed > nl) return kmx::set_error(KMX_ERR_HIP, "kmx_loci_align: the class counts exceed the loci");     // (never: a guard for the lists)
     if (listed) {
         const uint64_t n_words = c[CTR_PEQ_WORDS];
-        AL_TRY(a->peq.ensure(std::max<uint64_t>(n_words, 1) * 16));
-        AL_TRY(a->list.ensure(listed * 4));
-        AL_TRY(a->alist.ensure(listed * 4));
+        TRY_HIP(a->peq.ensure(std::max<uint64_t>(n_words, 1) * 16));
+        TRY_HIP(a->list.ensure(listed * 4));
+        TRY_HIP(a->alist.ensure(listed * 4));
         if (n_words)
             hipLaunchKernelGGL(k_align_peq, dim3(grid_for(n_words, kBlock)), dim3(kBlock), 0, s, A, a->peq_off.as<uint64_t>(), n_words, a->peq.as<uint64_t>());
         hipLaunchKernelGGL(k_align_place, dim3(grid_for(nl, kBlock)), dim3(kBlock), 0, s, nl, a->cls.as<uint8_t>(), base, ctr, a->list.as<uint32_t>());
@@ -465,8 +441,8 @@ kmx_status align_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const 
     }
     hipLaunchKernelGGL(k_align_best, dim3(grid_for(nr, kBlock / kWave)), dim3(kBlock), 0, s, nr, L.locus_off, a->dist.as<uint8_t>(), o.max_edits,
                        a->best.as<uint32_t>(), a->aligned.as<uint32_t>(), ctr);
-    AL_TRY(hipGetLastError());
-    AL_OK(read_counters(s, ctr, a->h_ctr));
+    TRY_HIP(hipGetLastError());
+    TRY_KMX(kmx::read_back("kmx_loci_align", s, ctr, a->h_ctr, CTR_COUNT * 8));
     a->n_loci = nl;
     a->n_aligned = a->h_ctr.as<uint64_t>()[CTR_N_ALIGNED];
     a->n_skipped = a->h_ctr.as<uint64_t>()[CTR_N_SKIPPED];
@@ -492,7 +468,7 @@ kmx_status check_front(const char* fn, const kmx_index* index, const kmx_loci* l
 kmx_status align_call(const char* fn, const kmx_index* index, const kmx_loci* loci, const void* ranks, const void* roff, uint64_t nr,
                       const kmx_align_options* o, bool host, hipStream_t stream, kmx_alignments** inout)
 {
-    AL_OK(check_front(fn, index, loci, roff, o, inout));
+    TRY_KMX(check_front(fn, index, loci, roff, o, inout));
     const std::string who = std::string(fn) + ": ";
     const kmx::LociAccess L = kmx::loci_access(loci);
     kmx_alignments* a = *inout;
@@ -506,36 +482,18 @@ kmx_status align_call(const char* fn, const kmx_index* index, const kmx_loci* lo
     if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
     uint64_t n_letters = ~uint64_t(0);
     if (host) {
-        const uint64_t* ro = static_cast<const uint64_t*>(roff);
-        if (nr && ro[0] != 0) return refuse(KMX_ERR_INVALID_ARGUMENT, "roff[0] must be 0");
-        for (uint64_t i = 0; i < nr; ++i)
-            if (ro[i + 1] < ro[i]) return refuse(KMX_ERR_INVALID_ARGUMENT, "roff must be non-decreasing");
-        n_letters = nr ? ro[nr] : 0;
-        if (n_letters && !ranks) return refuse(KMX_ERR_INVALID_ARGUMENT, "NULL read letters (ranks)");
+        const char* why = kmx::check_host_reads(ranks, static_cast<const uint64_t*>(roff), nr, &n_letters);
+        if (why) return refuse(KMX_ERR_INVALID_ARGUMENT, why);
     }
-    DeviceGuard dg;
-    AL_TRY(hipGetDevice(&dg.prev));
-    AL_TRY(hipSetDevice(L.device));
-    if (a && a->device != L.device) {                          // buffers of another device: start afresh on this one
-        (void)hipSetDevice(a->device);
-        a->release();
-        (void)hipSetDevice(L.device);
-    }
-    if (!a) a = new kmx_alignments();
-    *inout = a;
+    kmx::DeviceGuard dg;
+    TRY_KMX(kmx::bind_handle(inout, L.device));
+    a = *inout;
     hipStream_t s = host ? L.stream : stream;
     kmx_status st = KMX_OK;
     const void* d_ranks = ranks;
     const void* d_roff = roff;
     if (host && nr && L.n_loci) {
-        auto upload = [&]() -> kmx_status {
-            AL_TRY(a->ranks.ensure(std::max<uint64_t>(n_letters, 1)));
-            AL_TRY(a->roff.ensure((nr + 1) * 8));
-            if (n_letters) AL_TRY(hipMemcpyAsync(a->ranks.p, ranks, n_letters, hipMemcpyHostToDevice, s));
-            AL_TRY(hipMemcpyAsync(a->roff.p, roff, (nr + 1) * 8, hipMemcpyHostToDevice, s));
-            return KMX_OK;
-        };
-        st = upload();
+        st = kmx::upload_reads(ranks, roff, nr, n_letters, a->ranks, a->roff, s);
         d_ranks = a->ranks.p;
         d_roff = a->roff.p;
     }
@@ -589,23 +547,9 @@ kmx_status kmx_alignments_view(kmx_alignments* a, const uint8_t** dist, const ui
     if (!a) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_alignments_view: alignments handle is NULL");
     if (!a->host_valid) {
         const uint64_t nr = a->nr, nl = a->n_loci;
-        if (!a->h_dist.grow(std::max<uint64_t>(nl, 1)) || !a->h_start.grow(std::max<uint64_t>(nl, 1) * 4) || !a->h_end.grow(std::max<uint64_t>(nl, 1) * 4) ||
-            !a->h_best.grow(std::max<uint64_t>(nr, 1) * 4) || !a->h_aligned.grow(std::max<uint64_t>(nr, 1) * 4))
-            return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_alignments_view: page-locked host allocation failed");
-        if (nr) {
-            DeviceGuard dg;
-            AL_TRY(hipGetDevice(&dg.prev));
-            AL_TRY(hipSetDevice(a->device));
-            hipStream_t s = a->stream;
-            AL_TRY(hipMemcpyAsync(a->h_best.p, a->best.p, nr * 4, hipMemcpyDeviceToHost, s));
-            AL_TRY(hipMemcpyAsync(a->h_aligned.p, a->aligned.p, nr * 4, hipMemcpyDeviceToHost, s));
-            if (nl) {
-                AL_TRY(hipMemcpyAsync(a->h_dist.p, a->dist.p, nl, hipMemcpyDeviceToHost, s));
-                AL_TRY(hipMemcpyAsync(a->h_start.p, a->start.p, nl * 4, hipMemcpyDeviceToHost, s));
-                AL_TRY(hipMemcpyAsync(a->h_end.p, a->end.p, nl * 4, hipMemcpyDeviceToHost, s));
-            }
-            AL_TRY(hipStreamSynchronize(s));
-        }
+        const kmx::HostCopy items[] = {{a->h_dist, a->dist, nl, 1}, {a->h_start, a->start, nl, 4}, {a->h_end, a->end, nl, 4},
+                                       {a->h_best, a->best, nr, 4}, {a->h_aligned, a->aligned, nr, 4}};
+        TRY_KMX(kmx::host_view("kmx_alignments_view", a->device, a->stream, items, std::size(items)));
         a->host_valid = true;
     }
     if (dist) *dist = a->h_dist.as<uint8_t>();
@@ -616,15 +560,6 @@ kmx_status kmx_alignments_view(kmx_alignments* a, const uint8_t** dist, const ui
     return KMX_OK;
 }
 
-void kmx_alignments_free(kmx_alignments* a)
-{
-    if (!a) return;
-    int prev = -1;
-    const bool have = hipGetDevice(&prev) == hipSuccess;
-    (void)hipSetDevice(a->device);
-    a->release();                                              // (hipFree waits for the kernels of the last call)
-    if (have) (void)hipSetDevice(prev);
-    delete a;
-}
+void kmx_alignments_free(kmx_alignments* a) { kmx::free_handle(a); }
 
 } // extern "C"

@@ -3,8 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-#include <cstring>
 #include <mutex>
 #include <string>
 
@@ -24,50 +22,6 @@ struct PackedText {
 };
 #define KMX_TEXT_PAD_WORDS 4   // a window read of two words past any offset stays inside the allocation
 
-// grow-only device buffer, released with its owner (kmx_approx.hip, kmx_vote.hip)
-struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-    Buf() = default;
-    Buf(const Buf&) = delete;
-    Buf& operator=(const Buf&) = delete;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        release();
-        const size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return e; }
-        cap = want;
-        return hipSuccess;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    ~Buf() { release(); }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-
-// page-locked host array that keeps its contents when it grows; freed with its owner
-struct PinnedArr {
-    void* p = nullptr;
-    size_t cap = 0;
-    PinnedArr() = default;
-    PinnedArr(const PinnedArr&) = delete;
-    PinnedArr& operator=(const PinnedArr&) = delete;
-    ~PinnedArr() { release(); }
-    bool grow(size_t bytes)
-    {
-        if (bytes <= cap) return true;
-        const size_t want = std::max(bytes, cap * 2) + 64;
-        void* q = nullptr;
-        if (hipHostMalloc(&q, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return false; }
-        if (p) { std::memcpy(q, p, cap); (void)hipHostFree(p); }
-        p = q; cap = want;
-        return true;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-
 struct IndexAccess {
     int device;
     uint64_t n;
@@ -82,7 +36,6 @@ IndexAccess index_access(const kmx_index* ix);                  // kmx_capi.hip
 bool index_access_on(const kmx_index* ix, int device, IndexAccess* out);
 // kmx_approx.hip: derives the replica's packed text on first use (the index's device is current; synchronises s when it derives)
 kmx_status ensure_text(const IndexAccess& A, hipStream_t s);
-kmx_status set_error(kmx_status st, const std::string& msg);    // kmx_capi.hip: kmx_last_error's message
 // kmx_approx.hip: the refusals of a complement table (kmx_search_approx_strands, kmx_reads_strands); comp[256] <- the table, the
 // identity outside the alphabet
 kmx_status check_complement(const std::string& who, const uint8_t* complement, uint32_t sigma, uint8_t* comp);

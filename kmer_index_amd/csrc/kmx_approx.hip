@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "kmx_approx.h"
+#include "kmx_handle.h"
 #include "kmx_kernels.h"
 
 namespace {
@@ -34,20 +35,10 @@ constexpr uint64_t kDefaultBudget = uint64_t(1) << 29;   // piece hits (candidat
 
 inline uint32_t bits_per_letter(uint32_t sigma) { return sigma <= 4 ? 2u : sigma <= 16 ? 4u : 8u; }
 
-#define AX_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) {                                                                       \
-            (void)hipGetLastError();                                                                   \
-            return kmx::set_error(e__ == hipErrorOutOfMemory ? KMX_ERR_OUT_OF_MEMORY : KMX_ERR_HIP,    \
-                                  std::string(#expr) + ": " + hipGetErrorString(e__));                 \
-        }                                                                                              \
-    } while (0)
-
 using kmx::Buf;
+using kmx::DeviceGuard;
 using kmx::PinnedArr;
-
-inline unsigned int grid_for(uint64_t n, uint64_t per_block) { return unsigned(std::max<uint64_t>((n + per_block - 1) / per_block, 1)); }
+using kmx::grid_for;
 
 } // namespace
 
@@ -915,9 +906,9 @@ kmx_status kmx::ensure_text(const kmx::IndexAccess& A, hipStream_t s)
     const uint32_t w = bits_per_letter(A.sigma);
     const uint64_t n_words = (n * w + 63) / 64 + KMX_TEXT_PAD_WORDS;
     Buf t8;
-    AX_TRY(t8.ensure(n + 64));
+    TRY_HIP(t8.ensure(n + 64));
     uint64_t* words = nullptr;
-    AX_TRY(hipMalloc(&words, n_words * 8));
+    TRY_HIP(hipMalloc(&words, n_words * 8));
     auto fail_free = [&](hipError_t e) {
         (void)hipFree(words);
         (void)hipGetLastError();
@@ -942,13 +933,6 @@ kmx_status kmx::ensure_text(const kmx::IndexAccess& A, hipStream_t s)
 }
 
 namespace {
-// the caller's current device, restored at scope exit
-struct DeviceGuard {
-    int cur = 0;
-    bool have = false;
-    DeviceGuard() { have = hipGetDevice(&cur) == hipSuccess; if (!have) (void)hipGetLastError(); }
-    ~DeviceGuard() { if (have) (void)hipSetDevice(cur); }
-};
 struct StreamGuard {
     hipStream_t s = nullptr;
     ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
@@ -967,9 +951,8 @@ struct ResultGuard {
     }
 };
 
-#define AX_OK(expr) do { const kmx_status st__ = (expr); if (st__ != KMX_OK) return st__; } while (0)
 // a launch and its launch error; AX_LAUNCH: a kernel on `blocks` blocks of kBlock threads on stream s
-#define AX_RUN(...) do { __VA_ARGS__; AX_TRY(hipGetLastError()); } while (0)
+#define AX_RUN(...) do { __VA_ARGS__; TRY_HIP(hipGetLastError()); } while (0)
 #define AX_LAUNCH(kernel, blocks, s, ...) AX_RUN(hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), 0, s, __VA_ARGS__))
 
 // One chunk's hit lists on the device, as one stage hands them to the next: the statuses of its nq queries, hit_off[nq + 1],
@@ -1003,8 +986,8 @@ inline uint32_t bit_width(uint64_t x) { uint32_t b = 0; while (x) { ++b; x >>= 1
 // *n <- the total a scan left on the device; the stream is drained
 static kmx_status read_total(hipStream_t s, const Buf& d_total, PinnedArr& h_total, uint64_t* n)
 {
-    AX_TRY(hipMemcpyAsync(h_total.p, d_total.p, 8, hipMemcpyDeviceToHost, s));
-    AX_TRY(hipStreamSynchronize(s));
+    TRY_HIP(hipMemcpyAsync(h_total.p, d_total.p, 8, hipMemcpyDeviceToHost, s));
+    TRY_HIP(hipStreamSynchronize(s));
     *n = h_total.as<uint64_t>()[0];
     return KMX_OK;
 }
@@ -1049,20 +1032,20 @@ static kmx_status prep_chunk(hipStream_t s, const kmx::IndexAccess& A, const uin
     const uint32_t E1 = e + 1, w = A.text->w, L = 64 / w;
     B.loc.resize(nqc + 1);
     for (uint64_t i = 0; i <= nqc; ++i) B.loc[i] = qoff[Q0 + i] - l0;
-    AX_TRY(B.qr.ensure(n_letters * S + 64));
-    AX_TRY(B.qoff.ensure((nqi + 1) * 8));
-    AX_TRY(B.poff.ensure((nqi * E1 + 1) * 8));
-    AX_TRY(B.qstat.ensure(nqi + 16));
-    AX_TRY(B.qwords.ensure((n_letters * S / L + nqi + 2) * 8));
-    AX_TRY(B.qcand.ensure((nqc + 1) * 8));
+    TRY_HIP(B.qr.ensure(n_letters * S + 64));
+    TRY_HIP(B.qoff.ensure((nqi + 1) * 8));
+    TRY_HIP(B.poff.ensure((nqi * E1 + 1) * 8));
+    TRY_HIP(B.qstat.ensure(nqi + 16));
+    TRY_HIP(B.qwords.ensure((n_letters * S / L + nqi + 2) * 8));
+    TRY_HIP(B.qcand.ensure((nqc + 1) * 8));
     if (S == 2) {
-        AX_TRY(B.raw.ensure(n_letters + 64));
-        AX_TRY(B.d_loc.ensure((nqc + 1) * 8));
-        AX_TRY(B.pair_stat.ensure(nqc + 16));
+        TRY_HIP(B.raw.ensure(n_letters + 64));
+        TRY_HIP(B.d_loc.ensure((nqc + 1) * 8));
+        TRY_HIP(B.pair_stat.ensure(nqc + 16));
     }
     const Buf &letters = S == 1 ? B.qr : B.raw, &offs = S == 1 ? B.qoff : B.d_loc;      // what the prep kernel reads
-    if (n_letters) AX_TRY(hipMemcpyAsync(letters.p, qranks + l0, n_letters, hipMemcpyHostToDevice, s));
-    AX_TRY(hipMemcpyAsync(offs.p, B.loc.data(), (nqc + 1) * 8, hipMemcpyHostToDevice, s));
+    if (n_letters) TRY_HIP(hipMemcpyAsync(letters.p, qranks + l0, n_letters, hipMemcpyHostToDevice, s));
+    TRY_HIP(hipMemcpyAsync(offs.p, B.loc.data(), (nqc + 1) * 8, hipMemcpyHostToDevice, s));
     if (S == 1)
         AX_LAUNCH(k_approx_prep, grid_for(nqc, kBlock), s, B.qr.as<uint8_t>(), B.qoff.as<uint64_t>(), nqc, A.sigma, e, A.range, w,
                   B.poff.as<uint64_t>(), B.qstat.as<uint8_t>(), B.qwords.as<uint64_t>());
@@ -1075,7 +1058,7 @@ static kmx_status prep_chunk(hipStream_t s, const kmx::IndexAccess& A, const uin
 // a chunk without a hit: L <- hit_off all zero
 static kmx_status no_hits(hipStream_t s, const Buf& hit_off, ChunkLists& L)
 {
-    AX_TRY(hipMemsetAsync(hit_off.p, 0, (L.nq + 1) * 8, s));
+    TRY_HIP(hipMemsetAsync(hit_off.p, 0, (L.nq + 1) * 8, s));
     L = ChunkLists{L.nq, 0, L.stat, hit_off.as<uint64_t>()};
     return KMX_OK;
 }
@@ -1083,26 +1066,26 @@ static kmx_status no_hits(hipStream_t s, const Buf& hit_off, ChunkLists& L)
 // The substitution path of one chunk behind the piece search: L <- hit_off, positions and mismatches of its L.nq queries.
 static kmx_status subst_chunk(hipStream_t s, VerifyArgs V, SubstBufs& B, PinnedArr& h_total, ChunkLists& L)
 {
-    AX_TRY(B.hit_off.ensure((L.nq + 1) * 8));
+    TRY_HIP(B.hit_off.ensure((L.nq + 1) * 8));
     if (!V.n_cand) return no_hits(s, B.hit_off, L);
     const uint64_t nb = (V.n_cand + kVerifySpan - 1) / kVerifySpan;
-    AX_TRY(B.keep.ensure(V.n_cand));
-    AX_TRY(B.bcount.ensure(nb * 4 + 16));
-    AX_TRY(B.bsum.ensure(kmx::scan_blocks(nb) * 8 + 16));
-    AX_TRY(B.bscan.ensure((nb + 1) * 8));
-    AX_TRY(B.total.ensure(16));
+    TRY_HIP(B.keep.ensure(V.n_cand));
+    TRY_HIP(B.bcount.ensure(nb * 4 + 16));
+    TRY_HIP(B.bsum.ensure(kmx::scan_blocks(nb) * 8 + 16));
+    TRY_HIP(B.bscan.ensure((nb + 1) * 8));
+    TRY_HIP(B.total.ensure(16));
     V.keep = B.keep.as<uint8_t>();
     V.bcount = B.bcount.as<uint32_t>();
     AX_LAUNCH(k_approx_verify, unsigned(nb), s, V);
     AX_RUN(kmx::launch_scan(s, V.bcount, nb, B.bsum.as<uint64_t>(), B.bscan.as<uint64_t>(), B.total.as<unsigned long long>()));
     uint64_t n_s = 0;
-    AX_OK(read_total(s, B.total, h_total, &n_s));
+    TRY_KMX(read_total(s, B.total, h_total, &n_s));
     if (!n_s) return no_hits(s, B.hit_off, L);
-    AX_TRY(B.spos.ensure(n_s * 4));
-    AX_TRY(B.spiece.ensure(n_s * 4));
-    AX_TRY(B.smm.ensure(n_s));
-    AX_TRY(B.opos.ensure(n_s * 4));
-    AX_TRY(B.omm.ensure(n_s));
+    TRY_HIP(B.spos.ensure(n_s * 4));
+    TRY_HIP(B.spiece.ensure(n_s * 4));
+    TRY_HIP(B.smm.ensure(n_s));
+    TRY_HIP(B.opos.ensure(n_s * 4));
+    TRY_HIP(B.omm.ensure(n_s));
     AX_LAUNCH(k_approx_compact, unsigned(nb), s, V, B.bscan.as<uint64_t>(), B.spos.as<uint32_t>(), B.spiece.as<uint32_t>(), B.smm.as<uint8_t>());
     AX_LAUNCH(k_approx_merge, grid_for(n_s, kBlock), s, B.spos.as<uint32_t>(), B.spiece.as<uint32_t>(), B.smm.as<uint8_t>(), n_s, V.e,
               B.opos.as<uint32_t>(), B.omm.as<uint8_t>());
@@ -1115,41 +1098,41 @@ static kmx_status subst_chunk(hipStream_t s, VerifyArgs V, SubstBufs& B, PinnedA
 static kmx_status edit_chunk(hipStream_t s, EditArgs V, uint32_t w, EditBufs& B, PinnedArr& h_total, ChunkLists& L)
 {
     const uint64_t nq = L.nq;
-    AX_TRY(B.hit_off.ensure((nq + 1) * 8));
+    TRY_HIP(B.hit_off.ensure((nq + 1) * 8));
     if (!V.n_cand) return no_hits(s, B.hit_off, L);
     const uint64_t nb = (V.n_cand + kVerifySpan - 1) / kVerifySpan;
-    AX_TRY(B.keep.ensure(V.n_cand * 4));
-    AX_TRY(B.bcount.ensure(nb * 4 + 16));
-    AX_TRY(B.bsum.ensure(kmx::scan_blocks(nb) * 8 + 16));
-    AX_TRY(B.bscan.ensure((nb + 1) * 8));
-    AX_TRY(B.total.ensure(16));
+    TRY_HIP(B.keep.ensure(V.n_cand * 4));
+    TRY_HIP(B.bcount.ensure(nb * 4 + 16));
+    TRY_HIP(B.bsum.ensure(kmx::scan_blocks(nb) * 8 + 16));
+    TRY_HIP(B.bscan.ensure((nb + 1) * 8));
+    TRY_HIP(B.total.ensure(16));
     V.keep = B.keep.as<uint32_t>();
     V.bcount = B.bcount.as<uint32_t>();
     AX_RUN(edit_dispatch<LaunchEditVerify>(V.e, w, s, unsigned(nb), V));
     AX_RUN(kmx::launch_scan(s, V.bcount, nb, B.bsum.as<uint64_t>(), B.bscan.as<uint64_t>(), B.total.as<unsigned long long>()));
     uint64_t n_s = 0, n_u = 0;
-    AX_OK(read_total(s, B.total, h_total, &n_s));
+    TRY_KMX(read_total(s, B.total, h_total, &n_s));
     if (!n_s) return no_hits(s, B.hit_off, L);
     const uint32_t pbits = std::max(bit_width(V.n - 1), 1u), key_bits = pbits + bit_width(nq - 1);
-    AX_TRY(B.ka.ensure((n_s + 1) * 8));                                      // (+ 1: whichever pair the sort leaves free takes a scan of
-    AX_TRY(B.kb.ensure((n_s + 1) * 8));                                      //  n_s entries and its total)
-    AX_TRY(B.va.ensure(n_s * 4));
-    AX_TRY(B.vb.ensure(n_s * 4));
+    TRY_HIP(B.ka.ensure((n_s + 1) * 8));                                      // (+ 1: whichever pair the sort leaves free takes a scan of
+    TRY_HIP(B.kb.ensure((n_s + 1) * 8));                                      //  n_s entries and its total)
+    TRY_HIP(B.va.ensure(n_s * 4));
+    TRY_HIP(B.vb.ensure(n_s * 4));
     AX_LAUNCH(k_edit_emit, unsigned(nb), s, V, B.bscan.as<uint64_t>(), pbits, B.ka.as<uint64_t>(), B.va.as<uint32_t>());
     bool in_b = false;
-    AX_TRY(kmx::sort_pairs_u64(s, B.ka.as<uint64_t>(), B.va.as<uint32_t>(), B.kb.as<uint64_t>(), B.vb.as<uint32_t>(), n_s, key_bits, &in_b));
+    TRY_HIP(kmx::sort_pairs_u64(s, B.ka.as<uint64_t>(), B.va.as<uint32_t>(), B.kb.as<uint64_t>(), B.vb.as<uint32_t>(), n_s, key_bits, &in_b));
     const uint64_t* keys = in_b ? B.kb.as<uint64_t>() : B.ka.as<uint64_t>();
     const uint32_t* vals = in_b ? B.vb.as<uint32_t>() : B.va.as<uint32_t>();
     uint64_t* rank = in_b ? B.ka.as<uint64_t>() : B.kb.as<uint64_t>();        // the other pair of arrays is free again
     uint32_t* head = in_b ? B.va.as<uint32_t>() : B.vb.as<uint32_t>();
-    AX_TRY(B.bsum.ensure(kmx::scan_blocks(n_s) * 8 + 16));
+    TRY_HIP(B.bsum.ensure(kmx::scan_blocks(n_s) * 8 + 16));
     AX_LAUNCH(k_edit_heads, grid_for(n_s, kBlock), s, keys, n_s, head);
     AX_RUN(kmx::launch_scan(s, head, n_s, B.bsum.as<uint64_t>(), rank, B.total.as<unsigned long long>()));
-    AX_OK(read_total(s, B.total, h_total, &n_u));                             // (n_u >= 1: the first key heads a run)
-    AX_TRY(B.ukeys.ensure(n_u * 8));
-    AX_TRY(B.opos.ensure(n_u * 4));
-    AX_TRY(B.od.ensure(n_u));
-    AX_TRY(B.olen.ensure(n_u * 4));
+    TRY_KMX(read_total(s, B.total, h_total, &n_u));                             // (n_u >= 1: the first key heads a run)
+    TRY_HIP(B.ukeys.ensure(n_u * 8));
+    TRY_HIP(B.opos.ensure(n_u * 4));
+    TRY_HIP(B.od.ensure(n_u));
+    TRY_HIP(B.olen.ensure(n_u * 4));
     AX_LAUNCH(k_edit_unique, grid_for(n_s, kBlock), s, keys, vals, head, rank, n_s, pbits, B.ukeys.as<uint64_t>(), B.opos.as<uint32_t>(),
               B.od.as<uint8_t>());
     AX_LAUNCH(k_edit_hit_off, grid_for(nq + 1, kBlock), s, B.ukeys.as<uint64_t>(), n_u, nq, pbits, B.hit_off.as<uint64_t>());
@@ -1162,13 +1145,13 @@ static kmx_status edit_chunk(hipStream_t s, EditArgs V, uint32_t w, EditBufs& B,
 static kmx_status strand_merge_chunk(hipStream_t s, const uint8_t* pair_stat, StrandBufs& B, ChunkLists& L)
 {
     const uint64_t n_pairs = L.nq / 2, n_s = L.n_hits;
-    AX_TRY(B.off.ensure((n_pairs + 1) * 8));
-    if (!n_s) AX_TRY(hipMemsetAsync(B.off.p, 0, (n_pairs + 1) * 8, s));
+    TRY_HIP(B.off.ensure((n_pairs + 1) * 8));
+    if (!n_s) TRY_HIP(hipMemsetAsync(B.off.p, 0, (n_pairs + 1) * 8, s));
     if (n_s) {
-        AX_TRY(B.pos.ensure(n_s * 4));
-        AX_TRY(B.d.ensure(n_s));
-        AX_TRY(B.strand.ensure(n_s));
-        if (L.len) AX_TRY(B.len.ensure(n_s * 4));
+        TRY_HIP(B.pos.ensure(n_s * 4));
+        TRY_HIP(B.d.ensure(n_s));
+        TRY_HIP(B.strand.ensure(n_s));
+        if (L.len) TRY_HIP(B.len.ensure(n_s * 4));
         AX_LAUNCH(k_strand_merge, grid_for(std::max(n_s, n_pairs + 1), kBlock), s, L.hit_off, n_pairs, n_s, L.pos, L.dist, L.len, B.pos.as<uint32_t>(),
                   B.d.as<uint8_t>(), B.len.as<uint32_t>(), B.strand.as<uint8_t>(), B.off.as<uint64_t>());
     }
@@ -1183,23 +1166,23 @@ static kmx_status report_chunk(hipStream_t s, const ReportOpts& rep, uint32_t e,
     const uint64_t n_s = L.n_hits, nq = L.nq;
     if (!n_s) { std::memset(h_found, 0, nq * 8); return KMX_OK; }
     const ReportArgs P{L.hit_off, nq, n_s, L.pos, L.dist, L.strand, e, rep.loci, rep.best, rep.max_hits};
-    AX_TRY(B.hq.ensure(n_s * 4));
-    AX_TRY(B.code.ensure(n_s));
-    AX_TRY(B.qcnt.ensure(nq * kStrata * 4));
-    AX_TRY(B.rule.ensure(nq * 8));
-    AX_TRY(B.found.ensure(nq * 8));
-    AX_TRY(B.flag.ensure(n_s * 4 + 16));
-    AX_TRY(B.dest.ensure((n_s + 1) * 8));
-    AX_TRY(B.bsum.ensure(kmx::scan_blocks(n_s) * 8 + 16));
-    AX_TRY(B.total.ensure(16));
-    AX_TRY(B.off.ensure((nq + 1) * 8));
+    TRY_HIP(B.hq.ensure(n_s * 4));
+    TRY_HIP(B.code.ensure(n_s));
+    TRY_HIP(B.qcnt.ensure(nq * kStrata * 4));
+    TRY_HIP(B.rule.ensure(nq * 8));
+    TRY_HIP(B.found.ensure(nq * 8));
+    TRY_HIP(B.flag.ensure(n_s * 4 + 16));
+    TRY_HIP(B.dest.ensure((n_s + 1) * 8));
+    TRY_HIP(B.bsum.ensure(kmx::scan_blocks(n_s) * 8 + 16));
+    TRY_HIP(B.total.ensure(16));
+    TRY_HIP(B.off.ensure((nq + 1) * 8));
     const unsigned hit_blocks = grid_for(n_s, kBlock);
-    AX_TRY(hipMemsetAsync(B.qcnt.p, 0, nq * kStrata * 4, s));
+    TRY_HIP(hipMemsetAsync(B.qcnt.p, 0, nq * kStrata * 4, s));
     AX_LAUNCH(k_report_mark, hit_blocks, s, P, B.hq.as<uint32_t>(), B.code.as<uint8_t>(), B.qcnt.as<uint32_t>());
     AX_LAUNCH(k_report_query, grid_for(nq, kBlock), s, B.qcnt.as<uint32_t>(), nq, P.best, P.max_hits, B.found.as<uint64_t>(), B.rule.as<uint64_t>());
     const uint64_t* rscan = nullptr;
     if (P.max_hits) {
-        AX_TRY(B.rscan.ensure((n_s + 1) * 8));
+        TRY_HIP(B.rscan.ensure((n_s + 1) * 8));
         AX_LAUNCH(k_report_ind, hit_blocks, s, B.code.as<uint8_t>(), B.hq.as<uint32_t>(), B.rule.as<uint64_t>(), n_s, B.flag.as<uint32_t>());
         AX_RUN(kmx::launch_scan(s, B.flag.as<uint32_t>(), n_s, B.bsum.as<uint64_t>(), B.rscan.as<uint64_t>(), B.total.as<unsigned long long>()));
         rscan = B.rscan.as<uint64_t>();
@@ -1208,14 +1191,14 @@ static kmx_status report_chunk(hipStream_t s, const ReportOpts& rep, uint32_t e,
               B.flag.as<uint32_t>());
     AX_RUN(kmx::launch_scan(s, B.flag.as<uint32_t>(), n_s, B.bsum.as<uint64_t>(), B.dest.as<uint64_t>(), B.total.as<unsigned long long>()));
     uint64_t n_keep = 0;
-    AX_OK(read_total(s, B.total, h_total, &n_keep));
-    AX_TRY(B.pos.ensure(n_keep * 4 + 16));
-    AX_TRY(B.d.ensure(n_keep + 16));
-    if (L.len) AX_TRY(B.len.ensure(n_keep * 4 + 16));
-    if (L.strand) AX_TRY(B.strand.ensure(n_keep + 16));
+    TRY_KMX(read_total(s, B.total, h_total, &n_keep));
+    TRY_HIP(B.pos.ensure(n_keep * 4 + 16));
+    TRY_HIP(B.d.ensure(n_keep + 16));
+    if (L.len) TRY_HIP(B.len.ensure(n_keep * 4 + 16));
+    if (L.strand) TRY_HIP(B.strand.ensure(n_keep + 16));
     AX_LAUNCH(k_report_compact, grid_for(std::max(n_s, nq + 1), kBlock), s, P, L.len, B.flag.as<uint32_t>(), B.dest.as<uint64_t>(), B.pos.as<uint32_t>(),
               B.d.as<uint8_t>(), B.len.as<uint32_t>(), B.strand.as<uint8_t>(), B.off.as<uint64_t>());
-    AX_TRY(hipMemcpyAsync(h_found, B.found.p, nq * 8, hipMemcpyDeviceToHost, s));
+    TRY_HIP(hipMemcpyAsync(h_found, B.found.p, nq * 8, hipMemcpyDeviceToHost, s));
     L = ChunkLists{nq, n_keep, L.stat, B.off.as<uint64_t>(), B.pos.as<uint32_t>(), B.d.as<uint8_t>(), L.len ? B.len.as<uint32_t>() : nullptr,
                    L.strand ? B.strand.as<uint8_t>() : nullptr};
     return KMX_OK;
@@ -1226,20 +1209,20 @@ static kmx_status report_chunk(hipStream_t s, const ReportOpts& rep, uint32_t e,
 static kmx_status publish_chunk(hipStream_t s, const std::string& who, const ChunkLists& L, uint64_t q_at, kmx_approx_result& R)
 {
     const uint64_t h_at = R.n_hits, n = L.n_hits;
-    AX_OK(grow_pinned(R.positions, (h_at + n) * 4 + 64, who));
-    AX_OK(grow_pinned(R.mismatches, h_at + n + 64, who));
-    if (R.edit) AX_OK(grow_pinned(R.lengths, (h_at + n) * 4 + 64, who));
-    if (R.strands) AX_OK(grow_pinned(R.strand, h_at + n + 64, who));
+    TRY_KMX(grow_pinned(R.positions, (h_at + n) * 4 + 64, who));
+    TRY_KMX(grow_pinned(R.mismatches, h_at + n + 64, who));
+    if (R.edit) TRY_KMX(grow_pinned(R.lengths, (h_at + n) * 4 + 64, who));
+    if (R.strands) TRY_KMX(grow_pinned(R.strand, h_at + n + 64, who));
     uint64_t* ho = R.hit_off.as<uint64_t>() + q_at;          // (ho[0], the previous chunk's end, is rewritten with the same value)
-    AX_TRY(hipMemcpyAsync(ho, L.hit_off, (L.nq + 1) * 8, hipMemcpyDeviceToHost, s));
-    AX_TRY(hipMemcpyAsync(R.status.as<uint8_t>() + q_at, L.stat, L.nq, hipMemcpyDeviceToHost, s));
+    TRY_HIP(hipMemcpyAsync(ho, L.hit_off, (L.nq + 1) * 8, hipMemcpyDeviceToHost, s));
+    TRY_HIP(hipMemcpyAsync(R.status.as<uint8_t>() + q_at, L.stat, L.nq, hipMemcpyDeviceToHost, s));
     if (n) {
-        AX_TRY(hipMemcpyAsync(R.positions.as<uint32_t>() + h_at, L.pos, n * 4, hipMemcpyDeviceToHost, s));
-        AX_TRY(hipMemcpyAsync(R.mismatches.as<uint8_t>() + h_at, L.dist, n, hipMemcpyDeviceToHost, s));
-        if (R.edit) AX_TRY(hipMemcpyAsync(R.lengths.as<uint32_t>() + h_at, L.len, n * 4, hipMemcpyDeviceToHost, s));
-        if (R.strands) AX_TRY(hipMemcpyAsync(R.strand.as<uint8_t>() + h_at, L.strand, n, hipMemcpyDeviceToHost, s));
+        TRY_HIP(hipMemcpyAsync(R.positions.as<uint32_t>() + h_at, L.pos, n * 4, hipMemcpyDeviceToHost, s));
+        TRY_HIP(hipMemcpyAsync(R.mismatches.as<uint8_t>() + h_at, L.dist, n, hipMemcpyDeviceToHost, s));
+        if (R.edit) TRY_HIP(hipMemcpyAsync(R.lengths.as<uint32_t>() + h_at, L.len, n * 4, hipMemcpyDeviceToHost, s));
+        if (R.strands) TRY_HIP(hipMemcpyAsync(R.strand.as<uint8_t>() + h_at, L.strand, n, hipMemcpyDeviceToHost, s));
     }
-    AX_TRY(hipStreamSynchronize(s));
+    TRY_HIP(hipStreamSynchronize(s));
     for (uint64_t i = 0; i <= L.nq; ++i) ho[i] += h_at;
     R.n_hits += n;
     return KMX_OK;
@@ -1253,17 +1236,17 @@ kmx_status kmx_index_text(const kmx_index* index, uint8_t* out_ranks, uint64_t n
     const kmx::IndexAccess A = kmx::index_access(index);
     if (out_ranks && n != A.n) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_index_text: n differs from the index's text length");
     DeviceGuard dg;
-    AX_TRY(hipSetDevice(A.device));
+    TRY_HIP(hipSetDevice(A.device));
     StreamGuard sg;
-    AX_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-    AX_OK(ensure_text(A, sg.s));
+    TRY_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    TRY_KMX(ensure_text(A, sg.s));
     if (packed_bytes) *packed_bytes = A.text->n_words * 8;
     if (!out_ranks || n == 0) return KMX_OK;
     Buf out;
-    AX_TRY(out.ensure(n));
+    TRY_HIP(out.ensure(n));
     AX_LAUNCH(k_text_unpack, std::min<unsigned>(grid_for(n, kBlock), 65536u), sg.s, A.text->d_words, n, A.text->w, out.as<uint8_t>());
-    AX_TRY(hipMemcpyAsync(out_ranks, out.p, n, hipMemcpyDeviceToHost, sg.s));
-    AX_TRY(hipStreamSynchronize(sg.s));
+    TRY_HIP(hipMemcpyAsync(out_ranks, out.p, n, hipMemcpyDeviceToHost, sg.s));
+    TRY_HIP(hipStreamSynchronize(sg.s));
     return KMX_OK;
 }
 
@@ -1278,14 +1261,14 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
     const std::string who = std::string(fn) + ": ";
     if (max_subst > KMX_APPROX_MAX_SUBST) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "max_subst > KMX_APPROX_MAX_SUBST");
     if (flags & ~uint32_t(KMX_APPROX_EDIT)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "unknown flag bits");
-    AX_OK(check_queries(who, qranks, qoff, nq));
+    TRY_KMX(check_queries(who, qranks, qoff, nq));
     *out = nullptr;
     const kmx::IndexAccess A = kmx::index_access(index);
     if (A.broken) return kmx::set_error(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
     const uint32_t e = max_subst, E1 = e + 1;
     const uint32_t S = complement ? 2u : 1u;             // internal queries per query (both strands: q and rc(q))
     uint8_t comp[256];
-    if (complement) AX_OK(kmx::check_complement(who, complement, A.sigma, comp));
+    if (complement) TRY_KMX(kmx::check_complement(who, complement, A.sigma, comp));
     uint64_t budget = kDefaultBudget, max_pieces = kMaxPieces;
     if (const char* env = getenv("KMX_APPROX_CHUNK_CANDIDATES")) { const long long v = atoll(env); if (v > 0) budget = uint64_t(v); }
     if (const char* env = getenv("KMX_APPROX_CHUNK_PIECES")) { const long long v = atoll(env); if (v > 0) max_pieces = std::min(uint64_t(v), kMaxPieces); }
@@ -1293,48 +1276,48 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
     if (edit) budget = std::max<uint64_t>(budget / (2 * e + 1), 1);      // a piece hit names 2e + 1 starts: each counts against the budget
 
     DeviceGuard dg;
-    AX_TRY(hipSetDevice(A.device));
+    TRY_HIP(hipSetDevice(A.device));
     StreamGuard sg;
-    AX_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    TRY_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
     hipStream_t s = sg.s;
-    AX_OK(ensure_text(A, s));
+    TRY_KMX(ensure_text(A, s));
     const uint64_t* text = A.text->d_words;
     const uint32_t w = A.text->w;
 
     std::unique_ptr<kmx_approx_result> R(new kmx_approx_result());
     R->nq = nq; R->edit = edit; R->strands = complement != nullptr;
     R->opts = rep.api; R->reported = rep.on();
-    if (rep.on()) AX_OK(grow_pinned(R->found, (nq + 1) * 8, who));
-    if (complement) AX_OK(grow_pinned(R->strand, 64, who));
-    if (edit) AX_OK(grow_pinned(R->lengths, 64, who));
-    AX_OK(grow_pinned(R->hit_off, (nq + 1) * 8, who));
-    AX_OK(grow_pinned(R->status, nq + 1, who));
-    AX_OK(grow_pinned(R->positions, 64, who));
-    AX_OK(grow_pinned(R->mismatches, 64, who));
+    if (rep.on()) TRY_KMX(grow_pinned(R->found, (nq + 1) * 8, who));
+    if (complement) TRY_KMX(grow_pinned(R->strand, 64, who));
+    if (edit) TRY_KMX(grow_pinned(R->lengths, 64, who));
+    TRY_KMX(grow_pinned(R->hit_off, (nq + 1) * 8, who));
+    TRY_KMX(grow_pinned(R->status, nq + 1, who));
+    TRY_KMX(grow_pinned(R->positions, 64, who));
+    TRY_KMX(grow_pinned(R->mismatches, 64, who));
     R->hit_off.as<uint64_t>()[0] = 0;
 
     PrepBufs pb;
     SubstBufs sb; EditBufs eb; StrandBufs mb; ReportBufs rb;      // each stage's own
     if (complement) {
-        AX_TRY(pb.comp.ensure(256));
-        AX_TRY(hipMemcpyAsync(pb.comp.p, comp, 256, hipMemcpyHostToDevice, s));
+        TRY_HIP(pb.comp.ensure(256));
+        TRY_HIP(hipMemcpyAsync(pb.comp.p, comp, 256, hipMemcpyHostToDevice, s));
     }
     PinnedArr h_qcand, h_total;
-    AX_OK(grow_pinned(h_total, 64, who));
+    TRY_KMX(grow_pinned(h_total, 64, who));
     ResultGuard pres{nullptr, s};
     const uint64_t chunk_q = std::max<uint64_t>(max_pieces / (uint64_t(E1) * S), 1);      // (a pair is never split)
 
     for (uint64_t Q0 = 0; Q0 < nq;) {
         const uint64_t Q1 = std::min(nq, Q0 + chunk_q), nqc = Q1 - Q0;
-        AX_OK(prep_chunk(s, A, qranks, qoff, Q0, Q1, S, e, pb));
+        TRY_KMX(prep_chunk(s, A, qranks, qoff, Q0, Q1, S, e, pb));
         // candidates per query (both strands: per pair): the pieces through the exact search, counts only
-        AX_OK(kmx_search_batch_device(index, pb.qr.p, pb.poff.p, nqc * S * E1, KMX_SEARCH_COUNT_ONLY, s, &pres.r));
+        TRY_KMX(kmx_search_batch_device(index, pb.qr.p, pb.poff.p, nqc * S * E1, KMX_SEARCH_COUNT_ONLY, s, &pres.r));
         const uint64_t* d_phit = nullptr;
-        AX_OK(kmx_result_view_device(pres.r, &d_phit, nullptr, nullptr));
+        TRY_KMX(kmx_result_view_device(pres.r, &d_phit, nullptr, nullptr));
         AX_LAUNCH(k_approx_query_cands, grid_for(nqc + 1, kBlock), s, d_phit, nqc, S * E1 - 1, pb.qcand.as<uint64_t>());
-        AX_OK(grow_pinned(h_qcand, (nqc + 1) * 8, who));
-        AX_TRY(hipMemcpyAsync(h_qcand.p, pb.qcand.p, (nqc + 1) * 8, hipMemcpyDeviceToHost, s));
-        AX_TRY(hipStreamSynchronize(s));
+        TRY_KMX(grow_pinned(h_qcand, (nqc + 1) * 8, who));
+        TRY_HIP(hipMemcpyAsync(h_qcand.p, pb.qcand.p, (nqc + 1) * 8, hipMemcpyDeviceToHost, s));
+        TRY_HIP(hipStreamSynchronize(s));
         const uint64_t* qc = h_qcand.as<uint64_t>();
 
         for (uint64_t a = 0; a < nqc;) {
@@ -1343,22 +1326,22 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
             b = std::max(b, a + 1);
             const uint64_t nqv = (b - a) * S, q0 = a * S, np = nqv * E1;     // the chunk's internal queries [q0, q0 + nqv), their pieces
             R->n_chunks += 1;
-            AX_OK(kmx_search_batch_device(index, pb.qr.p, pb.poff.as<uint64_t>() + q0 * E1, np, KMX_SEARCH_DEFAULT, s, &pres.r));
+            TRY_KMX(kmx_search_batch_device(index, pb.qr.p, pb.poff.as<uint64_t>() + q0 * E1, np, KMX_SEARCH_DEFAULT, s, &pres.r));
             const uint64_t* phit = nullptr; const uint32_t* ppos = nullptr; const uint8_t* pstat = nullptr;
-            AX_OK(kmx_result_view_device(pres.r, &phit, &ppos, &pstat));
+            TRY_KMX(kmx_result_view_device(pres.r, &phit, &ppos, &pstat));
             uint64_t n_cand = 0;
-            AX_OK(kmx_result_counts(pres.r, nullptr, &n_cand, nullptr, nullptr, nullptr, nullptr));
+            TRY_KMX(kmx_result_counts(pres.r, nullptr, &n_cand, nullptr, nullptr, nullptr, nullptr));
             R->n_candidates += n_cand;
             AX_LAUNCH(k_approx_status, grid_for(nqv, kBlock), s, pstat, nqv, e, pb.qstat.as<uint8_t>() + q0);
             if (S == 2) AX_LAUNCH(k_strand_status, grid_for(b - a, kBlock), s, pb.qstat.as<uint8_t>() + q0, b - a, pb.pair_stat.as<uint8_t>() + a);
             // the stages: the internal queries' lists, (both strands) each pair's two merged, (reporting) filtered, then to the host
             ChunkLists L{nqv, 0, pb.qstat.as<uint8_t>() + q0};
             const uint64_t* d_qoff = pb.qoff.as<uint64_t>(); const uint8_t* d_qstat = pb.qstat.as<uint8_t>(); const uint64_t* d_qwords = pb.qwords.as<uint64_t>();
-            if (edit) AX_OK(edit_chunk(s, EditArgs{phit, ppos, n_cand, np, d_qoff, q0, d_qstat, d_qwords, text, A.n, e, nullptr, nullptr}, w, eb, h_total, L));
-            else AX_OK(subst_chunk(s, VerifyArgs{phit, ppos, n_cand, np, d_qoff, q0, d_qstat, d_qwords, text, A.n, w, e, nullptr, nullptr}, sb, h_total, L));
-            if (S == 2) AX_OK(strand_merge_chunk(s, pb.pair_stat.as<uint8_t>() + a, mb, L));
-            if (rep.on()) AX_OK(report_chunk(s, rep, e, rb, h_total, R->found.as<uint64_t>() + Q0 + a, L));
-            AX_OK(publish_chunk(s, who, L, Q0 + a, *R));
+            if (edit) TRY_KMX(edit_chunk(s, EditArgs{phit, ppos, n_cand, np, d_qoff, q0, d_qstat, d_qwords, text, A.n, e, nullptr, nullptr}, w, eb, h_total, L));
+            else TRY_KMX(subst_chunk(s, VerifyArgs{phit, ppos, n_cand, np, d_qoff, q0, d_qstat, d_qwords, text, A.n, w, e, nullptr, nullptr}, sb, h_total, L));
+            if (S == 2) TRY_KMX(strand_merge_chunk(s, pb.pair_stat.as<uint8_t>() + a, mb, L));
+            if (rep.on()) TRY_KMX(report_chunk(s, rep, e, rb, h_total, R->found.as<uint64_t>() + Q0 + a, L));
+            TRY_KMX(publish_chunk(s, who, L, Q0 + a, *R));
             a = b;
         }
         Q0 = Q1;

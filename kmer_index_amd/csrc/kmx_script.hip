@@ -22,6 +22,7 @@
 #include <cstring>
 #include <string>
 
+#include "kmx_approx.h"
 #include "kmx_kernels.h"
 #include "kmx_vote.h"
 
@@ -39,26 +40,9 @@ constexpr uint64_t kMaxChunk = uint64_t(1) << 30;             // entries of one 
 enum { OP_M = 0, OP_I = 1, OP_D = 2, OP_EQ = 7, OP_X = 8, OP_NONE = 15 };
 enum { CTR_N_SEL = 0, CTR_CODE_BYTES, CTR_RES_RUNS, CTR_MAX_CODE, CTR_CUT, CTR_CLASS, CTR_N_OPS = CTR_CLASS + kClasses, CTR_N_MISMATCHED, CTR_COUNT };
 
-#define SC_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) {                                                                       \
-            (void)hipGetLastError();                                                                   \
-            return kmx::set_error(e__ == hipErrorOutOfMemory ? KMX_ERR_OUT_OF_MEMORY : KMX_ERR_HIP,    \
-                                  std::string(#expr) + ": " + hipGetErrorString(e__));                 \
-        }                                                                                              \
-    } while (0)
-#define SC_OK(expr) do { const kmx_status st__ = (expr); if (st__ != KMX_OK) return st__; } while (0)
-
 using kmx::Buf;
 using Pinned = kmx::PinnedArr;
-
-struct DeviceGuard {
-    int prev = -1;
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-inline unsigned int grid_for(uint64_t n, uint64_t per_block) { return unsigned(std::max<uint64_t>((n + per_block - 1) / per_block, 1)); }
+using kmx::grid_for;
 
 // what every kernel reads
 struct ScriptIn {
@@ -383,14 +367,6 @@ struct kmx_scripts {
 
 namespace {
 
-kmx_status read_counters(hipStream_t s, const void* d, Pinned& h)
-{
-    if (!h.grow(CTR_COUNT * 8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_alignments_scripts: page-locked host allocation failed");
-    SC_TRY(hipMemcpyAsync(h.p, d, CTR_COUNT * 8, hipMemcpyDeviceToHost, s));
-    SC_TRY(hipStreamSynchronize(s));
-    return KMX_OK;
-}
-
 void launch_dp(hipStream_t s, int cls, const ScriptIn& S, const Entries& C)
 {
     const dim3 grid(unsigned(C.e1 - C.e0)), block(kWave);
@@ -408,32 +384,32 @@ kmx_status script_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const
                       uint64_t ranks_len, const uint32_t* best, const kmx_script_options& o, hipStream_t s, kmx_scripts* h)
 {
     const uint64_t nr = L.nr, nl = L.n_loci;
-    h->device = L.device; h->stream = s;
+    h->stream = s;
     h->clear();
     (void)hipGetLastError();
-    SC_TRY(h->read_sel_off.ensure((nr + 1) * 8));
+    TRY_HIP(h->read_sel_off.ensure((nr + 1) * 8));
     if (nr == 0 || nl == 0) {                                  // no entry: no launch indexes an empty array
-        SC_TRY(h->cig_off.ensure(8));
-        SC_TRY(hipMemsetAsync(h->read_sel_off.p, 0, (nr + 1) * 8, s));
-        SC_TRY(hipMemsetAsync(h->cig_off.p, 0, 8, s));
+        TRY_HIP(h->cig_off.ensure(8));
+        TRY_HIP(hipMemsetAsync(h->read_sel_off.p, 0, (nr + 1) * 8, s));
+        TRY_HIP(hipMemsetAsync(h->cig_off.p, 0, 8, s));
         h->nr = nr;
         h->filled = true;
         return KMX_OK;
     }
-    SC_OK(kmx::ensure_text(X, s));
+    TRY_KMX(kmx::ensure_text(X, s));
     const bool all = (o.flags & KMX_SCRIPT_ALL) != 0;
     const uint64_t cap_e = all ? nl : std::min(nr, nl);       // entries at the most (nl < 2^32: kmx_loci_align)
-    SC_TRY(h->cnt.ensure(nr * 4 + 16));
-    SC_TRY(h->bsum.ensure(kmx::scan_blocks(std::max(nr, cap_e)) * 8 + 16));
-    SC_TRY(h->sel.ensure(cap_e * 4));
-    SC_TRY(h->eread.ensure(cap_e * 4));
-    SC_TRY(h->estat.ensure(cap_e));
-    for (Buf* b : {&h->ecode, &h->eres, &h->eruns}) SC_TRY(b->ensure(cap_e * 4 + 16));
-    for (Buf* b : {&h->code_off, &h->run_off, &h->cig_off}) SC_TRY(b->ensure((cap_e + 1) * 8));
-    SC_TRY(h->ctr.ensure(CTR_COUNT * 8));
+    TRY_HIP(h->cnt.ensure(nr * 4 + 16));
+    TRY_HIP(h->bsum.ensure(kmx::scan_blocks(std::max(nr, cap_e)) * 8 + 16));
+    TRY_HIP(h->sel.ensure(cap_e * 4));
+    TRY_HIP(h->eread.ensure(cap_e * 4));
+    TRY_HIP(h->estat.ensure(cap_e));
+    for (Buf* b : {&h->ecode, &h->eres, &h->eruns}) TRY_HIP(b->ensure(cap_e * 4 + 16));
+    for (Buf* b : {&h->code_off, &h->run_off, &h->cig_off}) TRY_HIP(b->ensure((cap_e + 1) * 8));
+    TRY_HIP(h->ctr.ensure(CTR_COUNT * 8));
     unsigned long long* ctr = h->ctr.as<unsigned long long>();
-    SC_TRY(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
-    for (Buf* b : {&h->ecode, &h->eres, &h->eruns}) SC_TRY(hipMemsetAsync(b->p, 0, cap_e * 4, s));   // the scans run over cap_e entries
+    TRY_HIP(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
+    for (Buf* b : {&h->ecode, &h->eres, &h->eruns}) TRY_HIP(hipMemsetAsync(b->p, 0, cap_e * 4, s));   // the scans run over cap_e entries
     const ScriptIn S{static_cast<const uint8_t*>(d_ranks), static_cast<const uint64_t*>(d_roff), ranks_len, L.locus_off, A.dist, A.start, A.end, best,
                      nr, nl, X.n, X.text->d_words, X.text->w, X.sigma, o.flags};
     uint64_t* bsum = h->bsum.as<uint64_t>();
@@ -445,17 +421,17 @@ kmx_status script_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const
     kmx::launch_scan(s, h->eres.as<uint32_t>(), cap_e, bsum, h->run_off.as<uint64_t>(), ctr + CTR_RES_RUNS);
     const uint64_t want = o.scratch_bytes ? o.scratch_bytes : kDefaultScratch;
     hipLaunchKernelGGL(k_script_cut, dim3(1), dim3(1), 0, s, h->code_off.as<uint64_t>(), uint64_t(0), want, ctr);
-    SC_TRY(hipGetLastError());
-    SC_OK(read_counters(s, ctr, h->h_ctr));
+    TRY_HIP(hipGetLastError());
+    TRY_KMX(kmx::read_back("kmx_alignments_scripts", s, ctr, h->h_ctr, CTR_COUNT * 8));
     uint64_t c[CTR_COUNT];
     std::memcpy(c, h->h_ctr.p, sizeof c);
     const uint64_t n_sel = c[CTR_N_SEL];
     if (n_sel > cap_e) return kmx::set_error(KMX_ERR_HIP, "kmx_alignments_scripts: more entries than loci");      // (never: a guard for the arrays)
     if (n_sel) {
         const uint64_t cap = std::max(want, c[CTR_MAX_CODE]);
-        SC_TRY(ensure_exact(h->arena, std::max<uint64_t>(std::min(cap, c[CTR_CODE_BYTES]), 16)));
-        SC_TRY(h->runs.ensure(std::max<uint64_t>(c[CTR_RES_RUNS], 1) * 4));
-        SC_TRY(h->cigar.ensure(std::max<uint64_t>(c[CTR_RES_RUNS], 1) * 4));  // a script fills its reservation at the most
+        TRY_HIP(ensure_exact(h->arena, std::max<uint64_t>(std::min(cap, c[CTR_CODE_BYTES]), 16)));
+        TRY_HIP(h->runs.ensure(std::max<uint64_t>(c[CTR_RES_RUNS], 1) * 4));
+        TRY_HIP(h->cigar.ensure(std::max<uint64_t>(c[CTR_RES_RUNS], 1) * 4));  // a script fills its reservation at the most
         Entries C{h->sel.as<uint32_t>(), h->eread.as<uint32_t>(), h->estat.as<uint8_t>(), h->code_off.as<uint64_t>(), h->arena.as<uint64_t>(), ctr, 0, c[CTR_CUT]};
         while (C.e0 < n_sel) {
             if (C.e1 <= C.e0 || C.e1 > n_sel) return kmx::set_error(KMX_ERR_HIP, "kmx_alignments_scripts: an empty chunk");  // (never: the bound is clamped)
@@ -466,8 +442,8 @@ kmx_status script_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const
             C.e0 = C.e1;
             if (C.e0 < n_sel) {                                // one more read-back per further chunk: where it ends
                 hipLaunchKernelGGL(k_script_cut, dim3(1), dim3(1), 0, s, h->code_off.as<uint64_t>(), C.e0, want, ctr);
-                SC_TRY(hipGetLastError());
-                SC_OK(read_counters(s, ctr, h->h_ctr));
+                TRY_HIP(hipGetLastError());
+                TRY_KMX(kmx::read_back("kmx_alignments_scripts", s, ctr, h->h_ctr, CTR_COUNT * 8));
                 C.e1 = h->h_ctr.as<uint64_t>()[CTR_CUT];
             }
         }
@@ -476,8 +452,8 @@ kmx_status script_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const
     if (n_sel)
         hipLaunchKernelGGL(k_script_compact, dim3(grid_for(n_sel, kBlock)), dim3(kBlock), 0, s, ctr, h->run_off.as<uint64_t>(), h->runs.as<uint32_t>(),
                            h->cig_off.as<uint64_t>(), h->cigar.as<uint32_t>());
-    SC_TRY(hipGetLastError());
-    SC_OK(read_counters(s, ctr, h->h_ctr));
+    TRY_HIP(hipGetLastError());
+    TRY_KMX(kmx::read_back("kmx_alignments_scripts", s, ctr, h->h_ctr, CTR_COUNT * 8));
     h->nr = nr;
     h->n_sel = n_sel;
     h->n_ops = h->h_ctr.as<uint64_t>()[CTR_N_OPS];
@@ -508,7 +484,7 @@ kmx_status script_call(const char* fn, const kmx_index* index, const kmx_loci* l
                        uint64_t nr, const kmx_script_options* o, bool host, hipStream_t stream, kmx_scripts** inout,
                        const kmx::PlacementsAccess* P = nullptr, uint64_t ranks_len = ~uint64_t(0))
 {
-    SC_OK(check_front(fn, index, loci, al, roff, o, inout));
+    TRY_KMX(check_front(fn, index, loci, al, roff, o, inout));
     const std::string who = std::string(fn) + ": ";
     if (P && (o->flags & KMX_SCRIPT_ALL)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "KMX_SCRIPT_ALL ignores best: not for the winners of a fold");
     const kmx::LociAccess L = kmx::loci_access(loci);
@@ -529,36 +505,18 @@ kmx_status script_call(const char* fn, const kmx_index* index, const kmx_loci* l
     if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
     uint64_t n_letters = ranks_len;
     if (host) {
-        const uint64_t* ro = static_cast<const uint64_t*>(roff);
-        if (nr && ro[0] != 0) return refuse(KMX_ERR_INVALID_ARGUMENT, "roff[0] must be 0");
-        for (uint64_t i = 0; i < nr; ++i)
-            if (ro[i + 1] < ro[i]) return refuse(KMX_ERR_INVALID_ARGUMENT, "roff must be non-decreasing");
-        n_letters = nr ? ro[nr] : 0;
-        if (n_letters && !ranks) return refuse(KMX_ERR_INVALID_ARGUMENT, "NULL read letters (ranks)");
+        const char* why = kmx::check_host_reads(ranks, static_cast<const uint64_t*>(roff), nr, &n_letters);
+        if (why) return refuse(KMX_ERR_INVALID_ARGUMENT, why);
     }
-    DeviceGuard dg;
-    SC_TRY(hipGetDevice(&dg.prev));
-    SC_TRY(hipSetDevice(L.device));
-    if (h && h->device != L.device) {                          // buffers of another device: start afresh on this one
-        (void)hipSetDevice(h->device);
-        h->release();
-        (void)hipSetDevice(L.device);
-    }
-    if (!h) h = new kmx_scripts();
-    *inout = h;
+    kmx::DeviceGuard dg;
+    TRY_KMX(kmx::bind_handle(inout, L.device));
+    h = *inout;
     hipStream_t s = host ? A.stream : stream;
     kmx_status st = KMX_OK;
     const void* d_ranks = ranks;
     const void* d_roff = roff;
     if (host && nr && L.n_loci) {
-        auto upload = [&]() -> kmx_status {
-            SC_TRY(h->ranks.ensure(std::max<uint64_t>(n_letters, 1)));
-            SC_TRY(h->roff.ensure((nr + 1) * 8));
-            if (n_letters) SC_TRY(hipMemcpyAsync(h->ranks.p, ranks, n_letters, hipMemcpyHostToDevice, s));
-            SC_TRY(hipMemcpyAsync(h->roff.p, roff, (nr + 1) * 8, hipMemcpyHostToDevice, s));
-            return KMX_OK;
-        };
-        st = upload();
+        st = kmx::upload_reads(ranks, roff, nr, n_letters, h->ranks, h->roff, s);
         d_ranks = h->ranks.p;
         d_roff = h->roff.p;
     }
@@ -618,22 +576,11 @@ kmx_status kmx_scripts_view(kmx_scripts* h, const uint64_t** read_sel_off, const
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_scripts_view: scripts handle is NULL");
     if (!h->host_valid) {
         const uint64_t nr = h->nr, ns = h->n_sel, no = h->n_ops;
-        if (!h->h_read_sel_off.grow((nr + 1) * 8) || !h->h_sel.grow(std::max<uint64_t>(ns, 1) * 4) || !h->h_cig_off.grow((ns + 1) * 8) ||
-            !h->h_cigar.grow(std::max<uint64_t>(no, 1) * 4))
-            return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_scripts_view: page-locked host allocation failed");
-        h->h_read_sel_off.as<uint64_t>()[0] = 0;               // the empty result: one offset each
-        h->h_cig_off.as<uint64_t>()[0] = 0;
-        if (h->filled) {
-            DeviceGuard dg;
-            SC_TRY(hipGetDevice(&dg.prev));
-            SC_TRY(hipSetDevice(h->device));
-            hipStream_t s = h->stream;
-            SC_TRY(hipMemcpyAsync(h->h_read_sel_off.p, h->read_sel_off.p, (nr + 1) * 8, hipMemcpyDeviceToHost, s));
-            SC_TRY(hipMemcpyAsync(h->h_cig_off.p, h->cig_off.p, (ns + 1) * 8, hipMemcpyDeviceToHost, s));
-            if (ns) SC_TRY(hipMemcpyAsync(h->h_sel.p, h->sel.p, ns * 4, hipMemcpyDeviceToHost, s));
-            if (no) SC_TRY(hipMemcpyAsync(h->h_cigar.p, h->cigar.p, no * 4, hipMemcpyDeviceToHost, s));
-            SC_TRY(hipStreamSynchronize(s));
-        }
+        const bool f = h->filled;                              // else the empty result: one offset each, 0
+        const kmx::HostCopy items[] = {{h->h_read_sel_off, h->read_sel_off, f ? nr + 1 : 0, 8}, {h->h_sel, h->sel, ns, 4},
+                                       {h->h_cig_off, h->cig_off, f ? ns + 1 : 0, 8}, {h->h_cigar, h->cigar, no, 4}};
+        TRY_KMX(kmx::host_view("kmx_scripts_view", h->device, h->stream, items, std::size(items)));
+        if (!f) h->h_read_sel_off.as<uint64_t>()[0] = h->h_cig_off.as<uint64_t>()[0] = 0;
         h->host_valid = true;
     }
     if (read_sel_off) *read_sel_off = h->h_read_sel_off.as<uint64_t>();
@@ -643,15 +590,6 @@ kmx_status kmx_scripts_view(kmx_scripts* h, const uint64_t** read_sel_off, const
     return KMX_OK;
 }
 
-void kmx_scripts_free(kmx_scripts* h)
-{
-    if (!h) return;
-    int prev = -1;
-    const bool have = hipGetDevice(&prev) == hipSuccess;
-    (void)hipSetDevice(h->device);
-    h->release();                                              // (hipFree waits for the kernels of the last call)
-    if (have) (void)hipSetDevice(prev);
-    delete h;
-}
+void kmx_scripts_free(kmx_scripts* h) { kmx::free_handle(h); }
 
 } // extern "C"

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <string>
 
+#include "kmx_approx.h"
 #include "kmx_kernels.h"
 #include "kmx_vote.h"
 
@@ -26,26 +27,9 @@ constexpr uint64_t kMaxReads = uint64_t(1) << 30;
 constexpr uint64_t kMaxLetters = uint64_t(1) << 62;
 enum { CTR_N_PLACED = 0, CTR_N_REVERSE, CTR_N_AMBIGUOUS, CTR_COUNT };
 
-#define ST_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) {                                                                       \
-            (void)hipGetLastError();                                                                   \
-            return kmx::set_error(e__ == hipErrorOutOfMemory ? KMX_ERR_OUT_OF_MEMORY : KMX_ERR_HIP,    \
-                                  std::string(#expr) + ": " + hipGetErrorString(e__));                 \
-        }                                                                                              \
-    } while (0)
-#define ST_OK(expr) do { const kmx_status st__ = (expr); if (st__ != KMX_OK) return st__; } while (0)
-
 using kmx::Buf;
 using Pinned = kmx::PinnedArr;
-
-struct DeviceGuard {
-    int prev = -1;
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-inline unsigned int grid_for(uint64_t n, uint64_t per_block) { return unsigned(std::max<uint64_t>((n + per_block - 1) / per_block, 1)); }
+using kmx::grid_for;
 
 // the complement table as kernel arguments: 256 entries, the identity outside the alphabet
 struct CompWords { uint32_t w[64]; };
@@ -170,8 +154,11 @@ struct kmx_strand_reads {
     {
         for (Buf* b : {&raw, &roff, &ranks2, &roff2}) b->release();
         h_total.release();
-        if (own) (void)hipStreamDestroy(own);
-        own = nullptr;
+        if (own) {                                             // nothing of this handle's is in flight on the stream that goes
+            (void)hipStreamSynchronize(own);
+            (void)hipStreamDestroy(own);
+        }
+        own = stream = nullptr;
     }
     void clear() { nr2 = 0; letters2 = 0; }
 };
@@ -218,12 +205,8 @@ kmx_status strands_call(const char* fn, const kmx_index* index, const void* rank
     if (nr >= kMaxReads) return refuse(KMX_ERR_TOO_LARGE, "2^30 or more reads: split the batch");
     uint64_t total = 0;
     if (host) {
-        const uint64_t* ro = static_cast<const uint64_t*>(roff);
-        if (nr && ro[0] != 0) return refuse(KMX_ERR_INVALID_ARGUMENT, "roff[0] must be 0");
-        for (uint64_t i = 0; i < nr; ++i)
-            if (ro[i + 1] < ro[i]) return refuse(KMX_ERR_INVALID_ARGUMENT, "roff must be non-decreasing");
-        total = nr ? ro[nr] : 0;
-        if (total && !ranks) return refuse(KMX_ERR_INVALID_ARGUMENT, "NULL read letters (ranks)");
+        const char* why = kmx::check_host_reads(ranks, static_cast<const uint64_t*>(roff), nr, &total);
+        if (why) return refuse(KMX_ERR_INVALID_ARGUMENT, why);
         if (total > kMaxLetters) return refuse(KMX_ERR_TOO_LARGE, "more than 2^62 letters: split the batch");
     } else if (nr) {                                           // the replica on the device that owns the reads
         hipPointerAttribute_t attr{};
@@ -233,50 +216,38 @@ kmx_status strands_call(const char* fn, const kmx_index* index, const void* rank
         }
         if (!kmx::index_access_on(index, attr.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the reads live on a device that holds no replica of this index");
     }
-    DeviceGuard dg;
-    ST_TRY(hipGetDevice(&dg.prev));
-    if (h && h->device != X.device) {                          // buffers of another device: start afresh on this one
-        (void)hipSetDevice(h->device);
-        h->release();
-    }
-    ST_TRY(hipSetDevice(X.device));
-    if (!h) h = new kmx_strand_reads();
-    *inout = h;
-    h->device = X.device;
+    kmx::DeviceGuard dg;
+    TRY_KMX(kmx::bind_handle(inout, X.device));
+    h = *inout;
     h->clear();
     auto run = [&]() -> kmx_status {
         (void)hipGetLastError();
-        if (host && !h->own) ST_TRY(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
+        if (host && !h->own) TRY_HIP(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
         hipStream_t s = host ? h->own : stream;
         h->stream = s;
-        ST_TRY(h->roff2.ensure((2 * nr + 1) * 8));
+        TRY_HIP(h->roff2.ensure((2 * nr + 1) * 8));
         if (nr == 0) {
-            ST_TRY(h->ranks2.ensure(1));
-            ST_TRY(hipMemsetAsync(h->roff2.p, 0, 8, s));
+            TRY_HIP(h->ranks2.ensure(1));
+            TRY_HIP(hipMemsetAsync(h->roff2.p, 0, 8, s));
             return KMX_OK;
         }
         const uint8_t* d_ranks = static_cast<const uint8_t*>(ranks);
         const uint64_t* d_roff = static_cast<const uint64_t*>(roff);
         if (host) {
-            ST_TRY(h->raw.ensure(std::max<uint64_t>(total, 1)));
-            ST_TRY(h->roff.ensure((nr + 1) * 8));
-            if (total) ST_TRY(hipMemcpyAsync(h->raw.p, ranks, total, hipMemcpyHostToDevice, s));
-            ST_TRY(hipMemcpyAsync(h->roff.p, roff, (nr + 1) * 8, hipMemcpyHostToDevice, s));
+            TRY_KMX(kmx::upload_reads(ranks, roff, nr, total, h->raw, h->roff, s));
             d_ranks = h->raw.as<uint8_t>();
             d_roff = h->roff.as<uint64_t>();
         } else {                                               // one 8-byte read-back: the letters of the batch
-            if (!h->h_total.grow(8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, who + "page-locked host allocation failed");
-            ST_TRY(hipMemcpyAsync(h->h_total.p, d_roff + nr, 8, hipMemcpyDeviceToHost, s));
-            ST_TRY(hipStreamSynchronize(s));
+            TRY_KMX(kmx::read_back(fn, s, d_roff + nr, h->h_total, 8));
             total = h->h_total.as<uint64_t>()[0];
             if (total > kMaxLetters) return kmx::set_error(KMX_ERR_TOO_LARGE, who + "more than 2^62 letters: split the batch");
         }
-        ST_TRY(h->ranks2.ensure(std::max<uint64_t>(2 * total, 1)));
+        TRY_HIP(h->ranks2.ensure(std::max<uint64_t>(2 * total, 1)));
         CompWords cw;
         std::memcpy(cw.w, comp, sizeof cw.w);
         hipLaunchKernelGGL(k_strand_reads, dim3(grid_for(nr, kBlock / kWave)), dim3(kBlock), 0, s, d_ranks, d_roff, nr, total, cw, h->ranks2.as<uint8_t>(),
                            h->roff2.as<uint64_t>());
-        ST_TRY(hipGetLastError());
+        TRY_HIP(hipGetLastError());
         h->letters2 = 2 * total;
         return KMX_OK;
     };
@@ -287,33 +258,25 @@ kmx_status strands_call(const char* fn, const kmx_index* index, const void* rank
     return st;
 }
 
-kmx_status read_counters(hipStream_t s, const void* d, Pinned& h)
-{
-    if (!h.grow(CTR_COUNT * 8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_alignments_fold_strands: page-locked host allocation failed");
-    ST_TRY(hipMemcpyAsync(h.p, d, CTR_COUNT * 8, hipMemcpyDeviceToHost, s));
-    ST_TRY(hipStreamSynchronize(s));
-    return KMX_OK;
-}
-
 kmx_status fold_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, hipStream_t s, kmx_placements* p)
 {
     const uint64_t nr = L.nr / 2;
-    p->device = L.device; p->stream = s;
+    p->stream = s;
     p->clear();
     (void)hipGetLastError();
     if (nr == 0) return KMX_OK;
-    for (Buf* b : {&p->locus, &p->start, &p->end}) ST_TRY(b->ensure(nr * 4));
-    for (Buf* b : {&p->strand, &p->dist, &p->second}) ST_TRY(b->ensure(nr));
-    ST_TRY(p->best2.ensure(2 * nr * 4));
-    ST_TRY(p->ctr.ensure(CTR_COUNT * 8));
+    for (Buf* b : {&p->locus, &p->start, &p->end}) TRY_HIP(b->ensure(nr * 4));
+    for (Buf* b : {&p->strand, &p->dist, &p->second}) TRY_HIP(b->ensure(nr));
+    TRY_HIP(p->best2.ensure(2 * nr * 4));
+    TRY_HIP(p->ctr.ensure(CTR_COUNT * 8));
     unsigned long long* ctr = p->ctr.as<unsigned long long>();
-    ST_TRY(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
+    TRY_HIP(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
     const FoldIn F{L.locus_off, A.dist, A.start, A.end, A.best, nr, L.n_loci};
     const FoldOut O{p->locus.as<uint32_t>(), p->strand.as<uint8_t>(), p->dist.as<uint8_t>(), p->start.as<uint32_t>(), p->end.as<uint32_t>(),
                     p->second.as<uint8_t>(), p->best2.as<uint32_t>(), ctr};
     hipLaunchKernelGGL(k_strand_fold, dim3(grid_for(nr, kBlock / kWave)), dim3(kBlock), 0, s, F, O);
-    ST_TRY(hipGetLastError());
-    ST_OK(read_counters(s, ctr, p->h_ctr));
+    TRY_HIP(hipGetLastError());
+    TRY_KMX(kmx::read_back("kmx_alignments_fold_strands", s, ctr, p->h_ctr, CTR_COUNT * 8));
     p->nr = nr;
     p->n_placed = p->h_ctr.as<uint64_t>()[CTR_N_PLACED];
     p->n_reverse = p->h_ctr.as<uint64_t>()[CTR_N_REVERSE];
@@ -347,17 +310,7 @@ kmx_status kmx_strand_reads_view_device(const kmx_strand_reads* h, const uint8_t
     return KMX_OK;
 }
 
-void kmx_strand_reads_free(kmx_strand_reads* h)
-{
-    if (!h) return;
-    int prev = -1;
-    const bool have = hipGetDevice(&prev) == hipSuccess;
-    (void)hipSetDevice(h->device);
-    if (h->own) (void)hipStreamSynchronize(h->own);            // nothing of this handle's is in flight on the stream that goes
-    h->release();
-    if (have) (void)hipSetDevice(prev);
-    delete h;
-}
+void kmx_strand_reads_free(kmx_strand_reads* h) { kmx::free_handle(h); }
 
 kmx_status kmx_alignments_fold_strands(const kmx_loci* loci, const kmx_alignments* alignments, const kmx_fold_options* o, void* stream,
                                        kmx_placements** inout)
@@ -380,16 +333,9 @@ kmx_status kmx_alignments_fold_strands(const kmx_loci* loci, const kmx_alignment
     if (L.nr & 1) return refuse(KMX_ERR_INVALID_ARGUMENT, "an odd number of reads: not the loci of a doubled batch");
     if (A.n_loci != L.n_loci) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments handle's n_loci differs from the loci handle's");
     if (A.device != L.device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the loci and the alignments live on different devices");
-    DeviceGuard dg;
-    ST_TRY(hipGetDevice(&dg.prev));
-    ST_TRY(hipSetDevice(L.device));
-    if (p && p->device != L.device) {                          // buffers of another device: start afresh on this one
-        (void)hipSetDevice(p->device);
-        p->release();
-        (void)hipSetDevice(L.device);
-    }
-    if (!p) p = new kmx_placements();
-    *inout = p;
+    kmx::DeviceGuard dg;
+    TRY_KMX(kmx::bind_handle(inout, L.device));
+    p = *inout;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : A.stream;
     const kmx_status st = fold_run(L, A, s, p);
     if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
@@ -428,28 +374,13 @@ kmx_status kmx_placements_view(kmx_placements* p, const uint32_t** locus, const 
                                const uint32_t** end, const uint8_t** second, const uint32_t** best2)
 {
     if (!p) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_placements_view: placements handle is NULL");
-    const uint64_t nr = p->nr, room = std::max<uint64_t>(nr, 1);
     const bool want_best2 = best2 && !p->host_best2_valid;
     if (!p->host_valid || want_best2) {
-        if (!p->h_locus.grow(room * 4) || !p->h_start.grow(room * 4) || !p->h_end.grow(room * 4) || !p->h_strand.grow(room) || !p->h_dist.grow(room) ||
-            !p->h_second.grow(room) || (best2 && !p->h_best2.grow(2 * room * 4)))
-            return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_placements_view: page-locked host allocation failed");
-        if (nr) {
-            DeviceGuard dg;
-            ST_TRY(hipGetDevice(&dg.prev));
-            ST_TRY(hipSetDevice(p->device));
-            hipStream_t s = p->stream;
-            if (!p->host_valid) {                              // 15 bytes per read
-                ST_TRY(hipMemcpyAsync(p->h_locus.p, p->locus.p, nr * 4, hipMemcpyDeviceToHost, s));
-                ST_TRY(hipMemcpyAsync(p->h_start.p, p->start.p, nr * 4, hipMemcpyDeviceToHost, s));
-                ST_TRY(hipMemcpyAsync(p->h_end.p, p->end.p, nr * 4, hipMemcpyDeviceToHost, s));
-                ST_TRY(hipMemcpyAsync(p->h_strand.p, p->strand.p, nr, hipMemcpyDeviceToHost, s));
-                ST_TRY(hipMemcpyAsync(p->h_dist.p, p->dist.p, nr, hipMemcpyDeviceToHost, s));
-                ST_TRY(hipMemcpyAsync(p->h_second.p, p->second.p, nr, hipMemcpyDeviceToHost, s));
-            }
-            if (want_best2) ST_TRY(hipMemcpyAsync(p->h_best2.p, p->best2.p, 2 * nr * 4, hipMemcpyDeviceToHost, s));   // only when asked for
-            ST_TRY(hipStreamSynchronize(s));
-        }
+        const uint64_t nr = p->host_valid ? 0 : p->nr;         // 15 bytes per read; best2 (a pair per read) only when asked for
+        const kmx::HostCopy items[] = {{p->h_locus, p->locus, nr, 4},   {p->h_start, p->start, nr, 4}, {p->h_end, p->end, nr, 4},
+                                       {p->h_strand, p->strand, nr, 1}, {p->h_dist, p->dist, nr, 1},   {p->h_second, p->second, nr, 1},
+                                       {p->h_best2, p->best2, p->nr, 8}};
+        TRY_KMX(kmx::host_view("kmx_placements_view", p->device, p->stream, items, best2 ? 7 : 6));
         p->host_valid = true;
         if (best2) p->host_best2_valid = true;
     }
@@ -463,16 +394,7 @@ kmx_status kmx_placements_view(kmx_placements* p, const uint32_t** locus, const 
     return KMX_OK;
 }
 
-void kmx_placements_free(kmx_placements* p)
-{
-    if (!p) return;
-    int prev = -1;
-    const bool have = hipGetDevice(&prev) == hipSuccess;
-    (void)hipSetDevice(p->device);
-    p->release();                                              // (hipFree waits for the kernels of the last call)
-    if (have) (void)hipSetDevice(prev);
-    delete p;
-}
+void kmx_placements_free(kmx_placements* p) { kmx::free_handle(p); }
 
 kmx_status kmx_placements_scripts(const kmx_index* index, const kmx_strand_reads* reads, const kmx_loci* loci, const kmx_alignments* alignments,
                                   const kmx_placements* placements, const kmx_script_options* options, kmx_scripts** inout)

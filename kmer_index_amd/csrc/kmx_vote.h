@@ -5,7 +5,7 @@
 
 #include <functional>
 
-#include "kmx_approx.h"   // set_error
+#include "kmx_handle.h"
 
 namespace kmx {
 

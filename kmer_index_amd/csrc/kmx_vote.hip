@@ -35,26 +35,10 @@ constexpr uint32_t kCountReads = 8;       // reads per wave of k_vote_count
 enum : uint8_t { CLS_NONE = 0, CLS_SMALL_A = 1, CLS_SMALL_B = 2, CLS_LARGE = 3 };
 enum { CTR_VOTES = 0, CTR_SMALL_A, CTR_SMALL_B, CTR_LARGE, CTR_LARGE_VOTES, CTR_LARGE_MAXB, CTR_OVERFLOW, CTR_SMALL_BOUND, CTR_COUNT };
 
-#define VT_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e__ = (expr);                                                                       \
-        if (e__ != hipSuccess) {                                                                       \
-            (void)hipGetLastError();                                                                   \
-            return kmx::set_error(e__ == hipErrorOutOfMemory ? KMX_ERR_OUT_OF_MEMORY : KMX_ERR_HIP,    \
-                                  std::string(#expr) + ": " + hipGetErrorString(e__));                 \
-        }                                                                                              \
-    } while (0)
-#define VT_OK(expr) do { const kmx_status st__ = (expr); if (st__ != KMX_OK) return st__; } while (0)
-
 using kmx::Buf;
 using Pinned = kmx::PinnedArr;
+using kmx::grid_for;
 
-struct DeviceGuard {
-    int prev = -1;
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-inline unsigned int grid_for(uint64_t n, uint64_t per_block) { return unsigned(std::max<uint64_t>((n + per_block - 1) / per_block, 1)); }
 inline uint32_t bit_width(uint64_t x) { uint32_t b = 0; while (x) { ++b; x >>= 1; } return b; }
 
 // what every kernel reads of the windows result and the options
@@ -392,6 +376,7 @@ struct kmx_loci {
             b->release();
         for (Pinned* b : {&h_ctr, &h_locus_off, &h_diag, &h_span, &h_votes, &h_skipped}) b->release();
     }
+    void clear() { nr = n_loci = n_votes = n_small = n_large = 0; host_valid = false; }
 };
 
 namespace {
@@ -407,40 +392,32 @@ uint32_t small_cap()
     return uint32_t(std::min<unsigned long long>(x, kCapB));
 }
 
-kmx_status read_words(hipStream_t s, const void* d, Pinned& h, size_t n_words)
-{
-    if (!h.grow(CTR_COUNT * 8)) return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_windows_vote: page-locked host allocation failed");
-    VT_TRY(hipMemcpyAsync(h.p, d, n_words * 8, hipMemcpyDeviceToHost, s));
-    VT_TRY(hipStreamSynchronize(s));
-    return KMX_OK;
-}
-
 // the large reads: keys, sort, heads, starts, keep + its scan (lcount[r] counts their kept loci; the final write follows the scan)
 kmx_status vote_large(const kmx::WindowsAccess& W, const VoteIn& A, kmx_loci* L, uint64_t n_v, uint32_t dbits, uint64_t* n_u_out)
 {
     hipStream_t s = W.stream;
     const uint64_t nr = A.nr;
     unsigned long long* d_total = L->ctr.as<unsigned long long>() + CTR_COUNT;
-    VT_TRY(L->lvote_off.ensure(nr * 8));
-    VT_TRY(L->ka.ensure((n_v + 1) * 8));
-    VT_TRY(L->kb.ensure((n_v + 1) * 8));
-    VT_TRY(L->va.ensure(n_v * 4 + 16));
-    VT_TRY(L->vb.ensure(n_v * 4 + 16));
-    VT_TRY(L->ufirst.ensure(nr * 8));
-    VT_TRY(L->bsum.ensure(std::max(kmx::scan_blocks(n_v), kmx::scan_blocks(nr)) * 8 + 16));
+    TRY_HIP(L->lvote_off.ensure(nr * 8));
+    TRY_HIP(L->ka.ensure((n_v + 1) * 8));
+    TRY_HIP(L->kb.ensure((n_v + 1) * 8));
+    TRY_HIP(L->va.ensure(n_v * 4 + 16));
+    TRY_HIP(L->vb.ensure(n_v * 4 + 16));
+    TRY_HIP(L->ufirst.ensure(nr * 8));
+    TRY_HIP(L->bsum.ensure(std::max(kmx::scan_blocks(n_v), kmx::scan_blocks(nr)) * 8 + 16));
     kmx::vote_timed(W.index, s, [&] {
         kmx::launch_scan(s, L->lcnt.as<uint32_t>(), nr, L->bsum.as<uint64_t>(), L->lvote_off.as<uint64_t>(), d_total);
         hipLaunchKernelGGL(k_vote_emit, dim3(unsigned(nr)), dim3(kBlock), 0, s, A, L->cls.as<uint8_t>(), L->vcnt.as<uint32_t>(),
                            L->lvote_off.as<uint64_t>(), dbits, L->ka.as<uint64_t>());
     });
-    VT_TRY(hipGetLastError());
+    TRY_HIP(hipGetLastError());
     bool in_b = false;
     hipError_t se = hipSuccess;
     kmx::vote_timed(W.index, s, [&] {                          // (the value arrays carry nothing: only the keys are read afterwards)
         se = kmx::sort_pairs_u64(s, L->ka.as<uint64_t>(), L->va.as<uint32_t>(), L->kb.as<uint64_t>(), L->vb.as<uint32_t>(), n_v,
                                  dbits + std::max(bit_width(nr - 1), 1u), &in_b);
     });
-    VT_TRY(se);
+    TRY_HIP(se);
     const uint64_t* keys = L->sorted_keys = in_b ? L->kb.as<uint64_t>() : L->ka.as<uint64_t>();
     uint64_t* rank = in_b ? L->ka.as<uint64_t>() : L->kb.as<uint64_t>();          // the other pair of arrays is free again
     uint32_t* head = L->va.as<uint32_t>();
@@ -448,20 +425,20 @@ kmx_status vote_large(const kmx::WindowsAccess& W, const VoteIn& A, kmx_loci* L,
         hipLaunchKernelGGL(k_vote_heads, dim3(grid_for(n_v, kBlock)), dim3(kBlock), 0, s, keys, n_v, dbits, A.band, head);
         kmx::launch_scan(s, head, n_v, L->bsum.as<uint64_t>(), rank, d_total);
     });
-    VT_TRY(hipGetLastError());
-    VT_OK(read_words(s, d_total, L->h_ctr, 1));
+    TRY_HIP(hipGetLastError());
+    TRY_KMX(kmx::read_back("kmx_windows_vote", s, d_total, L->h_ctr, 8));
     const uint64_t n_u = L->h_ctr.as<uint64_t>()[0];          // (>= 1: the first vote heads a locus)
-    VT_TRY(L->hstart.ensure(n_u * 8));
-    VT_TRY(L->keep.ensure(n_u * 4 + 16));
-    VT_TRY(L->krank.ensure((n_u + 1) * 8));
-    VT_TRY(L->bsum.ensure(std::max(kmx::scan_blocks(n_u), kmx::scan_blocks(nr)) * 8 + 16));
+    TRY_HIP(L->hstart.ensure(n_u * 8));
+    TRY_HIP(L->keep.ensure(n_u * 4 + 16));
+    TRY_HIP(L->krank.ensure((n_u + 1) * 8));
+    TRY_HIP(L->bsum.ensure(std::max(kmx::scan_blocks(n_u), kmx::scan_blocks(nr)) * 8 + 16));
     kmx::vote_timed(W.index, s, [&] {
         hipLaunchKernelGGL(k_vote_starts, dim3(grid_for(n_v, kBlock)), dim3(kBlock), 0, s, head, rank, n_v, L->hstart.as<uint64_t>());
         hipLaunchKernelGGL(k_vote_keep, dim3(grid_for(n_u, kBlock)), dim3(kBlock), 0, s, keys, L->hstart.as<uint64_t>(), n_u, n_v, dbits,
                            A.min_votes, L->keep.as<uint32_t>(), L->lcount.as<uint32_t>(), L->ufirst.as<uint64_t>());
         kmx::launch_scan(s, L->keep.as<uint32_t>(), n_u, L->bsum.as<uint64_t>(), L->krank.as<uint64_t>(), d_total);
     });
-    VT_TRY(hipGetLastError());
+    TRY_HIP(hipGetLastError());
     *n_u_out = n_u;
     return KMX_OK;
 }
@@ -470,38 +447,38 @@ kmx_status vote_run(const kmx::WindowsAccess& W, const kmx_vote_options& o, kmx_
 {
     hipStream_t s = W.stream;
     const uint64_t nr = W.nr;
-    L->device = W.device; L->stream = s;
-    L->nr = nr; L->n_loci = L->n_votes = L->n_small = L->n_large = 0;
-    L->host_valid = false;
+    L->stream = s;
+    L->clear();
+    L->nr = nr;
     (void)hipGetLastError();
-    VT_TRY(L->locus_off.ensure((nr + 1) * 8));
-    VT_TRY(L->skipped.ensure(std::max<uint64_t>(nr, 1) * 4));
-    VT_TRY(hipMemsetAsync(L->locus_off.p, 0, (nr + 1) * 8, s));
+    TRY_HIP(L->locus_off.ensure((nr + 1) * 8));
+    TRY_HIP(L->skipped.ensure(std::max<uint64_t>(nr, 1) * 4));
+    TRY_HIP(hipMemsetAsync(L->locus_off.p, 0, (nr + 1) * 8, s));
     if (nr == 0) return KMX_OK;
     if (nr >= (uint64_t(1) << 31))
         return kmx::set_error(KMX_ERR_TOO_LARGE, "kmx_windows_vote: at most 2^31-1 reads per call (a workgroup per read): split the reads");
     if (W.nq == 0) {                                           // no read has a window
-        VT_TRY(hipMemsetAsync(L->skipped.p, 0, nr * 4, s));
+        TRY_HIP(hipMemsetAsync(L->skipped.p, 0, nr * 4, s));
         return KMX_OK;
     }
     const VoteIn A{W.win_off, W.hit_off, W.positions, nr, W.n, W.stride, o.band, o.min_votes, o.max_occ};
     const uint32_t cap = small_cap(), cap_a = std::min(cap, kCapA);
-    for (Buf* b : {&L->vcnt, &L->smax, &L->lcnt, &L->lcount}) VT_TRY(b->ensure(nr * 4 + 16));
-    VT_TRY(L->cls.ensure(nr));
-    VT_TRY(L->sc_off.ensure(nr * 8));
-    VT_TRY(L->bsum.ensure(kmx::scan_blocks(nr) * 8 + 16));
-    VT_TRY(L->ctr.ensure((CTR_COUNT + 1) * 8));
+    for (Buf* b : {&L->vcnt, &L->smax, &L->lcnt, &L->lcount}) TRY_HIP(b->ensure(nr * 4 + 16));
+    TRY_HIP(L->cls.ensure(nr));
+    TRY_HIP(L->sc_off.ensure(nr * 8));
+    TRY_HIP(L->bsum.ensure(kmx::scan_blocks(nr) * 8 + 16));
+    TRY_HIP(L->ctr.ensure((CTR_COUNT + 1) * 8));
     unsigned long long* ctr = L->ctr.as<unsigned long long>();
     unsigned long long* d_total = ctr + CTR_COUNT;
-    VT_TRY(hipMemsetAsync(ctr, 0, (CTR_COUNT + 1) * 8, s));
-    VT_TRY(hipMemsetAsync(L->lcount.p, 0, nr * 4, s));
+    TRY_HIP(hipMemsetAsync(ctr, 0, (CTR_COUNT + 1) * 8, s));
+    TRY_HIP(hipMemsetAsync(L->lcount.p, 0, nr * 4, s));
     kmx::vote_timed(W.index, s, [&] {
         hipLaunchKernelGGL(k_vote_count, dim3(grid_for(nr, (kBlock / kWave) * kCountReads)), dim3(kBlock), 0, s, A, cap, cap_a,
                            L->vcnt.as<uint32_t>(), L->skipped.as<uint32_t>(), L->cls.as<uint8_t>(), L->smax.as<uint32_t>(),
                            L->lcnt.as<uint32_t>(), ctr);
     });
-    VT_TRY(hipGetLastError());
-    VT_OK(read_words(s, ctr, L->h_ctr, CTR_COUNT));
+    TRY_HIP(hipGetLastError());
+    TRY_KMX(kmx::read_back("kmx_windows_vote", s, ctr, L->h_ctr, CTR_COUNT * 8));
     uint64_t c[CTR_COUNT];
     std::memcpy(c, L->h_ctr.p, sizeof c);
     if (c[CTR_OVERFLOW]) return kmx::set_error(KMX_ERR_TOO_LARGE, "kmx_windows_vote: a read casts 2^32 or more votes: set max_occ or split the read");
@@ -512,9 +489,9 @@ kmx_status vote_run(const kmx::WindowsAccess& W, const kmx_vote_options& o, kmx_
 
     if (L->n_small) {
         const uint64_t bound = std::max<uint64_t>(c[CTR_SMALL_BOUND], 1);
-        VT_TRY(L->sc_diag.ensure(bound * 8));
-        VT_TRY(L->sc_span.ensure(bound * 4));
-        VT_TRY(L->sc_votes.ensure(bound * 4));
+        TRY_HIP(L->sc_diag.ensure(bound * 8));
+        TRY_HIP(L->sc_span.ensure(bound * 4));
+        TRY_HIP(L->sc_votes.ensure(bound * 4));
         const SmallOut O{L->vcnt.as<uint32_t>(), L->cls.as<uint8_t>(), L->sc_off.as<uint64_t>(), L->sc_diag.as<int64_t>(), L->sc_span.as<uint32_t>(),
                          L->sc_votes.as<uint32_t>(), L->lcount.as<uint32_t>()};
         kmx::vote_timed(W.index, s, [&] {
@@ -524,7 +501,7 @@ kmx_status vote_run(const kmx::WindowsAccess& W, const kmx_vote_options& o, kmx_
             if (c[CTR_SMALL_B])
                 hipLaunchKernelGGL((k_vote_small<kBigThreads, kCapB, CLS_SMALL_B>), dim3(unsigned(nr)), dim3(kBigThreads), 0, s, A, O);
         });
-        VT_TRY(hipGetLastError());
+        TRY_HIP(hipGetLastError());
     }
     uint64_t n_u = 0;
     uint32_t dbits = 0;
@@ -532,19 +509,19 @@ kmx_status vote_run(const kmx::WindowsAccess& W, const kmx_vote_options& o, kmx_
         dbits = std::max(bit_width(W.n - 1 + c[CTR_LARGE_MAXB]), 1u);
         if (dbits + std::max(bit_width(nr - 1), 1u) > 64)
             return kmx::set_error(KMX_ERR_TOO_LARGE, "kmx_windows_vote: read number and diagonal do not fit a 64-bit sort key: split the reads");
-        VT_OK(vote_large(W, A, L, c[CTR_LARGE_VOTES], dbits, &n_u));
+        TRY_KMX(vote_large(W, A, L, c[CTR_LARGE_VOTES], dbits, &n_u));
     }
     kmx::vote_timed(W.index, s, [&] {
         kmx::launch_scan(s, L->lcount.as<uint32_t>(), nr, L->bsum.as<uint64_t>(), L->locus_off.as<uint64_t>(),
                          L->locus_off.as<unsigned long long>() + nr);
     });
-    VT_TRY(hipGetLastError());
-    VT_OK(read_words(s, L->locus_off.as<uint64_t>() + nr, L->h_ctr, 1));
+    TRY_HIP(hipGetLastError());
+    TRY_KMX(kmx::read_back("kmx_windows_vote", s, L->locus_off.as<uint64_t>() + nr, L->h_ctr, 8));
     L->n_loci = L->h_ctr.as<uint64_t>()[0];
     if (!L->n_loci) return KMX_OK;
-    VT_TRY(L->diag.ensure(L->n_loci * 8));
-    VT_TRY(L->span.ensure(L->n_loci * 4));
-    VT_TRY(L->votes.ensure(L->n_loci * 4));
+    TRY_HIP(L->diag.ensure(L->n_loci * 8));
+    TRY_HIP(L->span.ensure(L->n_loci * 4));
+    TRY_HIP(L->votes.ensure(L->n_loci * 4));
     kmx::vote_timed(W.index, s, [&] {
         if (L->n_small)
             hipLaunchKernelGGL(k_vote_compact, dim3(grid_for(nr, kBlock / kWave)), dim3(kBlock), 0, s, nr, L->cls.as<uint8_t>(), L->sc_off.as<uint64_t>(),
@@ -555,7 +532,7 @@ kmx_status vote_run(const kmx::WindowsAccess& W, const kmx_vote_options& o, kmx_
                                c[CTR_LARGE_VOTES], dbits, L->keep.as<uint32_t>(), L->krank.as<uint64_t>(), L->ufirst.as<uint64_t>(),
                                L->locus_off.as<uint64_t>(), L->diag.as<int64_t>(), L->span.as<uint32_t>(), L->votes.as<uint32_t>());
     });
-    VT_TRY(hipGetLastError());
+    TRY_HIP(hipGetLastError());
     return KMX_OK;
 }
 
@@ -577,22 +554,13 @@ kmx_status kmx_windows_vote(kmx_result* windows, const kmx_vote_options* o, kmx_
     if (o->flags != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_windows_vote: flags must be 0");
     if (o->min_votes == 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_windows_vote: min_votes must be at least 1");
     kmx::WindowsAccess W{};
-    VT_OK(kmx::windows_access(windows, &W));
-    DeviceGuard dg;
-    VT_TRY(hipGetDevice(&dg.prev));
-    VT_TRY(hipSetDevice(W.device));
+    TRY_KMX(kmx::windows_access(windows, &W));
+    kmx::DeviceGuard dg;
+    TRY_KMX(kmx::bind_handle(inout, W.device));
     kmx_loci* L = *inout;
-    if (L && L->device != W.device) {                          // buffers of another device: start afresh on this one
-        (void)hipSetDevice(L->device);
-        L->release();
-        (void)hipSetDevice(W.device);
-    }
-    if (!L) L = new kmx_loci();
-    *inout = L;
     const kmx_status st = vote_run(W, *o, L);
     if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
-        L->nr = L->n_loci = L->n_votes = L->n_small = L->n_large = 0;
-        L->host_valid = false;
+        L->clear();
         if (L->locus_off.p) (void)hipMemsetAsync(L->locus_off.p, 0, 8, W.stream);
         (void)hipStreamSynchronize(W.stream);
     }
@@ -628,25 +596,11 @@ kmx_status kmx_loci_view(kmx_loci* l, const uint64_t** locus_off, const int64_t*
     if (!l) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_loci_view: loci handle is NULL");
     if (!l->host_valid) {
         const uint64_t nr = l->nr, nl = l->n_loci;
-        if (!l->h_locus_off.grow((nr + 1) * 8) || !l->h_skipped.grow(std::max<uint64_t>(nr, 1) * 4) || !l->h_diag.grow(std::max<uint64_t>(nl, 1) * 8) ||
-            !l->h_span.grow(std::max<uint64_t>(nl, 1) * 4) || !l->h_votes.grow(std::max<uint64_t>(nl, 1) * 4))
-            return kmx::set_error(KMX_ERR_OUT_OF_MEMORY, "kmx_loci_view: page-locked host allocation failed");
-        if (!l->locus_off.p) {                                 // a handle that no vote has filled yet
-            l->h_locus_off.as<uint64_t>()[0] = 0;
-        } else {
-            DeviceGuard dg;
-            VT_TRY(hipGetDevice(&dg.prev));
-            VT_TRY(hipSetDevice(l->device));
-            hipStream_t s = l->stream;
-            VT_TRY(hipMemcpyAsync(l->h_locus_off.p, l->locus_off.p, (nr + 1) * 8, hipMemcpyDeviceToHost, s));
-            if (nr) VT_TRY(hipMemcpyAsync(l->h_skipped.p, l->skipped.p, nr * 4, hipMemcpyDeviceToHost, s));
-            if (nl) {
-                VT_TRY(hipMemcpyAsync(l->h_diag.p, l->diag.p, nl * 8, hipMemcpyDeviceToHost, s));
-                VT_TRY(hipMemcpyAsync(l->h_span.p, l->span.p, nl * 4, hipMemcpyDeviceToHost, s));
-                VT_TRY(hipMemcpyAsync(l->h_votes.p, l->votes.p, nl * 4, hipMemcpyDeviceToHost, s));
-            }
-            VT_TRY(hipStreamSynchronize(s));
-        }
+        const bool filled = l->locus_off.p != nullptr;         // else no vote has filled the handle yet: one offset, 0
+        const kmx::HostCopy items[] = {{l->h_locus_off, l->locus_off, filled ? nr + 1 : 0, 8}, {l->h_skipped, l->skipped, nr, 4},
+                                       {l->h_diag, l->diag, nl, 8}, {l->h_span, l->span, nl, 4}, {l->h_votes, l->votes, nl, 4}};
+        TRY_KMX(kmx::host_view("kmx_loci_view", l->device, l->stream, items, std::size(items)));
+        if (!filled) l->h_locus_off.as<uint64_t>()[0] = 0;
         l->host_valid = true;
     }
     if (locus_off) *locus_off = l->h_locus_off.as<uint64_t>();
@@ -657,15 +611,6 @@ kmx_status kmx_loci_view(kmx_loci* l, const uint64_t** locus_off, const int64_t*
     return KMX_OK;
 }
 
-void kmx_loci_free(kmx_loci* l)
-{
-    if (!l) return;
-    int prev = -1;
-    const bool have = hipGetDevice(&prev) == hipSuccess;
-    (void)hipSetDevice(l->device);
-    l->release();                                              // (hipFree waits for the kernels of the last vote)
-    if (have) (void)hipSetDevice(prev);
-    delete l;
-}
+void kmx_loci_free(kmx_loci* l) { kmx::free_handle(l); }
 
 } // extern "C"

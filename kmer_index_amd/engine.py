@@ -447,16 +447,44 @@ class Result:
             pass
 
 
-class Loci:
-    """Owns a kmx_loci handle (kmx_windows_vote)."""
+class _Handle:
+    """What the owners of a C handle share: the empty handle, close() through the class's free function, and the two calls that
+    fill a run of out-parameters of one type."""
+
+    _free = None                    # the name of the handle's kmx_*_free
 
     def __init__(self):
         self._h = C.c_void_p()
 
+    def _counts(self, fn, *names):
+        v = [C.c_uint64() for _ in names]
+        _check(getattr(lib(), fn)(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(names, [int(x.value) for x in v]))
+
+    def _device_ptrs(self, fn, n):
+        p = [C.c_void_p() for _ in range(n)]
+        _check(getattr(lib(), fn)(self._h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._free)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Loci(_Handle):
+    """Owns a kmx_loci handle (kmx_windows_vote)."""
+
+    _free = "kmx_loci_free"
+
     def counts(self):
-        v = [C.c_uint64() for _ in range(5)]
-        _check(lib().kmx_loci_counts(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(["nr", "n_loci", "n_votes", "n_small", "n_large"], [int(x.value) for x in v]))
+        return self._counts("kmx_loci_counts", "nr", "n_loci", "n_votes", "n_small", "n_large")
 
     def host(self):
         """(locus_off[nr+1] u64, diag i64, span u32, votes u32, skipped[nr] u32) as numpy copies."""
@@ -470,9 +498,7 @@ class Loci:
 
     def device_ptrs(self):
         """(d_locus_off, d_diag, d_span, d_votes, d_skipped): kmx_loci_view_device."""
-        p = [C.c_void_p() for _ in range(5)]
-        _check(lib().kmx_loci_view_device(self._h, *[C.byref(x) for x in p]))
-        return tuple(x.value for x in p)
+        return self._device_ptrs("kmx_loci_view_device", 5)
 
     def align(self, index, ranks, roff, max_edits, max_span=0, alignments=None):
         """kmx_loci_align: every read (the reads of the windows search) against the text around each of its loci, within
@@ -492,28 +518,14 @@ class Loci:
         _check(lib().kmx_loci_align_device(index._h, self._h, d_ranks_ptr, d_roff_ptr, nr, C.byref(o), stream or None, C.byref(a._h)))
         return a
 
-    def close(self):
-        if self._h:
-            lib().kmx_loci_free(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Alignments:
+class Alignments(_Handle):
     """Owns a kmx_alignments handle (kmx_loci_align)."""
 
-    def __init__(self):
-        self._h = C.c_void_p()
+    _free = "kmx_alignments_free"
 
     def counts(self):
-        v = [C.c_uint64() for _ in range(4)]
-        _check(lib().kmx_alignments_counts(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(["nr", "n_loci", "n_aligned", "n_skipped"], [int(x.value) for x in v]))
+        return self._counts("kmx_alignments_counts", "nr", "n_loci", "n_aligned", "n_skipped")
 
     def host(self):
         """(dist[n_loci] u8, start u32, end u32, best[nr] u32, aligned[nr] u32) as numpy copies."""
@@ -527,9 +539,7 @@ class Alignments:
 
     def device_ptrs(self):
         """(d_dist, d_start, d_end, d_best, d_aligned): kmx_alignments_view_device."""
-        p = [C.c_void_p() for _ in range(5)]
-        _check(lib().kmx_alignments_view_device(self._h, *[C.byref(x) for x in p]))
-        return tuple(x.value for x in p)
+        return self._device_ptrs("kmx_alignments_view_device", 5)
 
     @staticmethod
     def _script_options(all, m, scratch_bytes):
@@ -562,28 +572,14 @@ class Alignments:
         _check(lib().kmx_alignments_fold_strands(loci._h, self._h, C.byref(o), stream or None, C.byref(p._h)))
         return p
 
-    def close(self):
-        if self._h:
-            lib().kmx_alignments_free(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Scripts:
+class Scripts(_Handle):
     """Owns a kmx_scripts handle (kmx_alignments_scripts)."""
 
-    def __init__(self):
-        self._h = C.c_void_p()
+    _free = "kmx_scripts_free"
 
     def counts(self):
-        v = [C.c_uint64() for _ in range(4)]
-        _check(lib().kmx_scripts_counts(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(["nr", "n_sel", "n_ops", "n_mismatched"], [int(x.value) for x in v]))
+        return self._counts("kmx_scripts_counts", "nr", "n_sel", "n_ops", "n_mismatched")
 
     def host(self):
         """(read_sel_off[nr+1] u64, sel[n_sel] u32, cig_off[n_sel+1] u64, cigar[n_ops] u32) as numpy copies."""
@@ -596,9 +592,7 @@ class Scripts:
 
     def device_ptrs(self):
         """(d_read_sel_off, d_sel, d_cig_off, d_cigar): kmx_scripts_view_device."""
-        p = [C.c_void_p() for _ in range(4)]
-        _check(lib().kmx_scripts_view_device(self._h, *[C.byref(x) for x in p]))
-        return tuple(x.value for x in p)
+        return self._device_ptrs("kmx_scripts_view_device", 4)
 
     def strings(self):
         """One CIGAR string per entry, e.g. "50=1X30=1D69=" ("" for an entry without a script)."""
@@ -606,24 +600,12 @@ class Scripts:
         runs = [f"{int(v) >> 4}{CIGAR_OPS[int(v) & 15]}" for v in cigar]
         return ["".join(runs[int(a):int(b)]) for a, b in zip(cig_off[:-1], cig_off[1:])]
 
-    def close(self):
-        if self._h:
-            lib().kmx_scripts_free(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class StrandReads:
+class StrandReads(_Handle):
     """Owns a kmx_strand_reads handle (kmx_reads_strands): every read and its reverse complement, on the device.  After
     Index.strand_reads the handle owns the stream everything behind it runs on: close it last."""
 
-    def __init__(self):
-        self._h = C.c_void_p()
+    _free = "kmx_strand_reads_free"
 
     def counts(self):
         _, _, nr2, _ = self.device_ptrs()
@@ -635,29 +617,18 @@ class StrandReads:
         _check(lib().kmx_strand_reads_view_device(self._h, C.byref(a), C.byref(b), C.byref(n), C.byref(s)))
         return a.value, b.value, int(n.value), s.value
 
-    def close(self):
-        if self._h:
-            lib().kmx_strand_reads_free(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Placements:
+class Placements(_Handle):
     """Owns a kmx_placements handle (kmx_alignments_fold_strands): one placement per public read of a doubled batch."""
 
+    _free = "kmx_placements_free"
+
     def __init__(self):
-        self._h = C.c_void_p()
+        super().__init__()
         self._reads = None          # the StrandReads whose stream the fold ran on: it must outlive the views
 
     def counts(self):
-        v = [C.c_uint64() for _ in range(4)]
-        _check(lib().kmx_placements_counts(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(["nr", "n_placed", "n_reverse", "n_ambiguous"], [int(x.value) for x in v]))
+        return self._counts("kmx_placements_counts", "nr", "n_placed", "n_reverse", "n_ambiguous")
 
     def host(self, best2=True):
         """(locus[nr] u32, strand u8, dist u8, start u32, end u32, second u8, best2[2 nr] u32) as numpy copies; best2=False
@@ -673,9 +644,7 @@ class Placements:
 
     def device_ptrs(self):
         """(d_locus, d_strand, d_dist, d_start, d_end, d_second, d_best2): kmx_placements_view_device."""
-        p = [C.c_void_p() for _ in range(7)]
-        _check(lib().kmx_placements_view_device(self._h, *[C.byref(x) for x in p]))
-        return tuple(x.value for x in p)
+        return self._device_ptrs("kmx_placements_view_device", 7)
 
     def scripts(self, index, reads, loci, alignments, m=False, scratch_bytes=0, scripts=None):
         """kmx_placements_scripts: the CIGAR of every placed read's winner (for a reverse placement that of the reverse complement
@@ -697,23 +666,14 @@ class Placements:
         return out
 
     def close(self):
-        if self._h:
-            lib().kmx_placements_free(self._h)
-            self._h = C.c_void_p()
+        super().close()
         self._reads = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
-
-class ApproxResult:
+class ApproxResult(_Handle):
     """Owns a kmx_approx_result handle (kmx_search_approx)."""
 
-    def __init__(self):
-        self._h = C.c_void_p()
+    _free = "kmx_approx_free"
 
     def counts(self):
         nq, hits, cand, chunks = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
@@ -748,17 +708,6 @@ class ApproxResult:
         p = C.c_void_p()
         _check(lib().kmx_approx_found(self._h, C.byref(p)))
         return _view(p.value, self.counts()["nq"], np.uint64).copy()
-
-    def close(self):
-        if self._h:
-            lib().kmx_approx_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Index:

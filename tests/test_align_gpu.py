@@ -362,6 +362,17 @@ def test_degenerate_batches(work):
         loci2.align(idx, ranks[:int(roff[299])], roff[:300], 3, alignments=al)
     assert e.value.status == 1 and "nr" in str(e.value)
     assert_empty(al, 0)
+    # host reads that do not hold together: refused as well, and the filled handle holds an empty result
+    from_one, decreasing = np.array(roff), np.array(roff)
+    from_one[0] = 1
+    decreasing[3] = decreasing[5]
+    for bad_ranks, bad_roff, word in ((ranks, from_one, "roff[0]"), (ranks, decreasing, "non-decreasing"), (np.zeros(0, np.uint8), roff, "ranks")):
+        loci2.align(idx, ranks, roff, 3, alignments=al)
+        assert al.counts()["nr"] == 300
+        with pytest.raises(engine.KmxError) as e:
+            loci2.align(idx, bad_ranks, bad_roff, 3, alignments=al)
+        assert e.value.status == 1 and word in str(e.value)
+        assert_empty(al, 0)
     for h in (loci, loci2, al):
         h.close()
 

@@ -340,3 +340,74 @@ def test_gather_device_returns_the_single_device_arrays_byte_for_byte(engine, de
     r1.close()
     many.close()
     one.close()
+
+
+def _device_of(engine, ptr):
+    """The device whose memory holds `ptr` (hipPointerGetAttributes of the runtime the library runs on)."""
+    import ctypes as C
+
+    class Attr(C.Structure):
+        _fields_ = [("type", C.c_int), ("device", C.c_int), ("devicePointer", C.c_void_p), ("hostPointer", C.c_void_p),
+                    ("isManaged", C.c_int), ("allocationFlags", C.c_uint)]
+
+    a = Attr()
+    assert engine.lib().hipPointerGetAttributes(C.byref(a), C.c_void_p(ptr)) == 0
+    return a.device
+
+
+def test_chain_handles_move_between_devices(engine):
+    """One Loci, Alignments, Scripts, StrandReads and Placements through the whole read-mapping chain on device 0, on device 1 and
+    on device 0 again: a handle that holds buffers of another device starts afresh on the device of the call, returns what fresh
+    handles return there, and leaves the caller's current device alone."""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    k, comp = 10, np.array([3, 2, 1, 0], np.uint8)
+    text = synth.ranks(1501, 4000, 4)
+    cuts = [(100, 60), (400, 75), (800, 90), (1200, 101), (1700, 117), (2200, 128), (2800, 139), (3400, 150)]
+    reads = [text[a:a + m].copy() for a, m in cuts]
+    for i in (2, 5):
+        reads[i] = comp[reads[i][::-1]]
+    reads[6][[40, 90]] = (reads[6][[40, 90]] + 1) % 4
+    ranks, roff = pack(reads)
+    kw = dict(band=8, min_votes=2)
+    idx = [engine.Index(text, 4, [k], device=d) for d in (0, 1)]
+
+    def chain(ix, h):
+        """h: (StrandReads, Loci, Alignments, Placements, Scripts) to reuse, or five times None"""
+        sr = ix.strand_reads(ranks, roff, comp, reads=h[0])
+        d_ranks2, d_roff2, nr2, stream = sr.device_ptrs()
+        r = ix.search_windows_device(d_ranks2, d_roff2, nr2, k, stream=stream)
+        loci = r.vote(**kw, loci=h[1])
+        r.close()
+        al = loci.align_device(ix, d_ranks2, d_roff2, nr2, 4, stream=stream, alignments=h[2])
+        pl = al.fold_strands(loci, stream=stream, placements=h[3])
+        pl._reads = sr
+        return sr, loci, al, pl, pl.scripts(ix, sr, loci, al, scripts=h[4])
+
+    kept, before = (None,) * 5, torch.cuda.current_device()
+    try:
+        for dev in (0, 1, 0):
+            torch.cuda.set_device(1 - dev)
+            got = chain(idx[dev], kept)
+            assert all(g is x for g, x in zip(got, kept) if x is not None)
+            kept = got
+            fresh = chain(idx[dev], (None,) * 5)
+            assert torch.cuda.current_device() == 1 - dev
+            assert kept[3].counts()["n_placed"] == 8 and kept[3].counts()["n_reverse"] == 2
+            for g, x in zip(kept[1:], fresh[1:]):
+                assert g.counts() == x.counts()
+                assert _same(g.host(), x.host()) and len(g.host()) == len(x.host())
+                ptrs = [p for p in g.device_ptrs() if p]
+                assert ptrs and all(_device_of(engine, p) == dev for p in ptrs)
+            assert kept[0].counts() == fresh[0].counts() == {"nr": 8, "nr2": 16}
+            assert all(_device_of(engine, p) == dev for p in kept[0].device_ptrs()[:2])
+            assert torch.cuda.current_device() == 1 - dev
+            for h in reversed(fresh):
+                h.close()
+    finally:
+        torch.cuda.set_device(before)
+    for h in reversed(kept):
+        h.close()
+    for ix in idx:
+        ix.close()

@@ -469,6 +469,17 @@ def test_degenerate_batches_and_refusals(work):
         assert_empty(scr, 0)
         assert scr.device_ptrs() == (None, None, None, None)
         mp.scripts(scripts=scr)
+    # host reads that do not hold together: refused as well, and the filled handle holds an empty result
+    from_one, decreasing = np.array(roff), np.array(roff)
+    from_one[0] = 1
+    decreasing[3] = decreasing[5]
+    for bad_ranks, bad_roff, word in ((ranks, from_one, "roff[0]"), (ranks, decreasing, "non-decreasing"), (np.zeros(0, np.uint8), roff, "ranks")):
+        assert scr.counts()["n_sel"] == FLOORS_E8["dna4_k10"][0]
+        with pytest.raises(engine.KmxError) as e:
+            al2.scripts(idx, loci2, bad_ranks, bad_roff, scripts=scr)
+        assert e.value.status == 1 and word in str(e.value)
+        assert_empty(scr, 0)
+        mp.scripts(scripts=scr)
     loci4 = idx.vote_windows(*random, 10, 1, *VOTE)                                                          # 40 reads as loci3, other loci
     assert loci4.counts()["n_loci"] != loci3.counts()["n_loci"]
     with pytest.raises(engine.KmxError) as e:

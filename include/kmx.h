@@ -900,6 +900,114 @@ kmx_status kmx_pairs_view_device(const kmx_pairs* p, const uint8_t** d_cls, cons
                                  const uint16_t** d_score, const uint16_t** d_second_score);
 void kmx_pairs_free(kmx_pairs* p);
 
+/* ---- mate rescue: an unplaced mate aligned in the insert window of its placed partner (an extension, no reference interface; a
+ *      caller detects the capability by the macro KMX_PAIR_RESCUE, KMX_VERSION is unchanged).  kmx_alignments_fold_pairs can
+ *      only choose among loci that the seeds voted for: a mate in which sequencing errors or variants leave no intact
+ *      w-letter window has none, and its pair comes out KMX_PAIR_MATE1_ONLY / _MATE2_ONLY although the partner pins it to a
+ *      few hundred letters of text (or DISCORDANT with a wrong placement, when the mate has an exact copy elsewhere).  The
+ *      rescue aligns such a mate against the window that the partner implies, without seeds, and rewrites the placements and
+ *      the pairs IN PLACE where the result is concordant.
+ *
+ *      Input.  `reads`, `loci`, `alignments`, `placements` and `pairs` are those of one doubled batch of interleaved mates after
+ *      kmx_alignments_fold_pairs (nr2 = 4 np internal reads); `index` is the index that was searched.  The call runs on the
+ *      stream the reads handle was filled on (the stream of the chain), reads the reads, the loci and the alignments, and
+ *      writes the placements, the pairs and *inout.  min_insert, max_insert and orientation have the meaning of
+ *      kmx_pair_options and normally are the values given to the pair fold; E = max_edits.
+ *
+ *      Jobs, in int64.  Pair p has mates a (the anchor) and b = 1 - a, public reads 2p + a and 2p + b.  A job (p, b) exists
+ *      when cls[p] is the ONLY class in which a is the placed mate (MATE1_ONLY: a = 0, MATE2_ONLY: a = 1), or when
+ *      cls[p] == KMX_PAIR_DISCORDANT and KMX_RESCUE_DISCORDANT is set, then for both b.  With s_a, S_a, E_a the strand, start
+ *      and end of the anchor in the placements handle, the looked-for strand is s_b = 1 - s_a for KMX_PAIR_FR and _RF and
+ *      s_b = s_a for _FF, and the anchor is UPSTREAM iff s_a == 0 (FR), s_a == 1 (RF), (a is mate 1) == (s_a == 0) (FF).  The
+ *      job's read q is internal read 4p + 2b + s_b, of m letters; its window is [lo, hi) with lo = S_a,
+ *      hi = min(n, S_a + max_insert) when the anchor is upstream, and hi = E_a, lo = max(0, E_a - max_insert) when it is
+ *      downstream.  Jobs are ordered by internal read, which is the order of (pair, looked-for mate); an internal read has
+ *      at most one.  job_off[nr2 + 1] is the exclusive prefix sum of the jobs per internal read, so the job arrays are shaped
+ *      like the loci of the doubled batch: read[j] (the internal read), lo[j], hi[j], dist[j], start[j], end[j], status[j].
+ *
+ *      The alignment of a job is that of kmx_loci_align with the window given:
+ *        - m == 0, m > KMX_ALIGN_MAX_READ or m <= E: dist = KMX_ALIGN_SKIPPED, start = end = 0 (a read of at most E letters
+ *          aligns with the empty substring anywhere: that places nothing);
+ *        - otherwise d = the least Levenshtein distance (unit costs) between q and any substring of text[lo, hi); a read
+ *          letter >= sigma equals no text letter.  d > E: dist = KMX_ALIGN_NONE, start = end = 0;
+ *        - else dist = d, end = the smallest e in [lo, hi] at which a substring at distance d ends, start = the largest s in
+ *          [lo, e] with lev(q, text[s, e)) == d.
+ *
+ *      Concordance and the choice.  A found job (dist <= E) is CONCORDANT by the test of kmx_alignments_fold_pairs itself,
+ *      applied to the anchor's interval and [start, end) with the strands s_a, s_b: start[u] <= start[v], end[u] <= end[v]
+ *      and min_insert <= T <= max_insert with T = end[v] - start[u].  (The window guarantees one inequality and the upper
+ *      bound; the rest is tested.)  Its score is dist[anchor] + d.  The limit of the method: the best alignment of a window
+ *      that is not concordant (the mate inside the anchor's interval, a dovetail, T < min_insert) is NOT replaced by a worse
+ *      one that would be.
+ *        - an ONLY pair takes its concordant job;
+ *        - a DISCORDANT pair takes the concordant job with the least (score, b) when
+ *          score <= dist[mate 1] + dist[mate 2] + unpaired_penalty (the placements' distances, compared without overflow;
+ *          0xFFFFFFFF: a rescued pair always wins).  unpaired_penalty is not looked at for ONLY pairs;
+ *        - status[j] = 0 skipped or none, 1 found but not concordant, 2 concordant but not taken, 3 taken.
+ *      A taken job writes, for pair p: cls = KMX_PAIR_CONCORDANT, tlen = +T if the upstream one is mate 1, else -T, score =
+ *      the job's score, second_score = 0xFFFF (no runner-up pair is searched for: a rescued pair never counts as ambiguous);
+ *      and for public read 2p + b: locus = 0xFFFFFFFF (the placement is no locus: read it from strand / dist / start / end),
+ *      strand = s_b, dist / start / end the job's, both best2 entries 0xFFFFFFFF (kmx_placements_scripts has no entry for the
+ *      read; kmx_rescues_scripts has), second = the least dist[l] over the ALIGNED loci l of the read that lie ELSEWHERE
+ *      from (s_b, [start, end)) by the rule of kmx_alignments_fold_strands: s(l) != s_b, or
+ *      max(start[l], start) >= min(end[l], end); 255 when there is none.  The anchor's entries and every other pair stay byte
+ *      for byte.  All counters of the two handles (n_placed, n_reverse, n_ambiguous; n_concordant, n_discordant, n_single,
+ *      n_unplaced, the pairs' n_ambiguous) are recounted from the final arrays, and the host views of both handles are
+ *      taken anew at their next kmx_*_view (earlier host views end).  A second rescue of the same handles with the same
+ *      options takes nothing.  tests/rescue_naive.py is this contract in executable form.
+ *
+ *      `segment` = G only shapes the work: a thread per (job, G end columns), each starting with a fresh state m + E columns
+ *      before its own range; 0 = 512.  The result never depends on it.
+ *
+ *      The rescues handle.  n_jobs, n_found (status >= 1), n_concordant (>= 2), n_taken (== 3) are the batch totals.  The
+ *      device arrays (kmx_rescues_view_device; job_off is NULL after a refusal or an error, the job arrays when there is no
+ *      job) are complete in stream order when the call returns; kmx_rescues_view copies to page-locked host memory on first
+ *      use and synchronises, on the stream of the call.  *inout == NULL allocates; a handle passed in is reused and its
+ *      earlier views end.  The placements and the pairs are written by the last kernel only: after a refusal, or an error
+ *      before that kernel, they are untouched and the rescues handle, when there is one, holds an empty result; after an
+ *      error behind it all three hold an empty result.  Every index is bounded by n, n_loci, nr2 and the job count: foreign
+ *      handles give meaningless but harmless results.
+ *
+ *      kmx_rescues_scripts is kmx_alignments_scripts_device over the doubled reads of `reads` with the job arrays in the place
+ *      of the loci and their alignments and only the taken jobs selected.  The result is an ordinary kmx_scripts over the
+ *      internal reads: at most one entry per rescued read, at internal read 4p + 2b + s_b, with sel = the job's index; for a
+ *      reverse placement the CIGAR is that of the reverse complement against text[start, end), the SAM convention.
+ *      KMX_SCRIPT_ALL is refused; KMX_SCRIPT_M and scratch_bytes work as before.
+ *
+ *      KMX_ERR_INVALID_ARGUMENT before any handle is looked at: a NULL argument, a struct_size that is too small, a flag bit
+ *      other than KMX_RESCUE_DISCORDANT, orientation > 2, min_insert > max_insert, max_insert > KMX_RESCUE_MAX_INSERT,
+ *      max_edits > KMX_ALIGN_MAX_EDITS.  After looking: the handles disagree in nr / nr2 / np / n_loci or live on different
+ *      devices, nr2 is no multiple of 4, the device holds no replica of the index, an index that
+ *      kmx_index_extend_query_size_range broke (KMX_ERR_HIP).  kmx_stats_get is not extended (see kmx_loci_align). */
+#define KMX_PAIR_RESCUE 1
+#define KMX_RESCUE_DISCORDANT 1u      /* also try DISCORDANT pairs, both ways round */
+#define KMX_RESCUE_MAX_INSERT 65536u
+typedef struct kmx_rescue_options {
+    uint32_t struct_size;       /* = sizeof(kmx_rescue_options): 32 */
+    uint32_t min_insert;        /* as kmx_pair_options */
+    uint32_t max_insert;        /* min_insert <= max_insert <= KMX_RESCUE_MAX_INSERT: the columns of a window */
+    uint32_t orientation;       /* KMX_PAIR_FR / _RF / _FF */
+    uint32_t max_edits;         /* E <= KMX_ALIGN_MAX_EDITS */
+    uint32_t unpaired_penalty;  /* only looked at for DISCORDANT pairs; 0xFFFFFFFF = a rescued pair always wins */
+    uint32_t segment;           /* end columns per thread of the forward pass; 0 = the default (512) */
+    uint32_t flags;             /* 0 or KMX_RESCUE_DISCORDANT */
+} kmx_rescue_options;
+typedef struct kmx_rescues kmx_rescues;
+kmx_status kmx_pairs_rescue(const kmx_index* index, const kmx_strand_reads* reads, const kmx_loci* loci,
+                            const kmx_alignments* alignments, const kmx_rescue_options* options, kmx_placements* placements,
+                            kmx_pairs* pairs, kmx_rescues** inout);
+kmx_status kmx_rescues_counts(const kmx_rescues* r, uint64_t* nr2, uint64_t* n_jobs, uint64_t* n_found, uint64_t* n_concordant,
+                              uint64_t* n_taken);
+kmx_status kmx_rescues_view(kmx_rescues* r, const uint64_t** job_off, const uint32_t** read, const uint32_t** lo,
+                            const uint32_t** hi, const uint8_t** dist, const uint32_t** start, const uint32_t** end,
+                            const uint8_t** status);
+kmx_status kmx_rescues_view_device(const kmx_rescues* r, const uint64_t** d_job_off, const uint32_t** d_read,
+                                   const uint32_t** d_lo, const uint32_t** d_hi, const uint8_t** d_dist, const uint32_t** d_start,
+                                   const uint32_t** d_end, const uint8_t** d_status);
+kmx_status kmx_rescues_scripts(const kmx_index* index, const kmx_strand_reads* reads, const kmx_rescues* rescues,
+                               const kmx_script_options* options, kmx_scripts** inout);
+void kmx_rescues_free(kmx_rescues* r);
+
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.
  * Works on built, loaded and replicated indexes (this replica).  The first call derives a copy packed at 2, 4 or 8 bits per

@@ -14,6 +14,7 @@
 //   k_align_rev<NW>    the same recurrence on the reversed read and the text read backwards from `end`, carry-in +1 (anchored): stops
 //                      at the first column whose score equals d
 //   k_align_best       a wave per read: aligned[r], best[r]; the batch totals
+// k_align_count, k_align_peq and the column of the recurrence live in kmx_align_core.h, which kmx_rescue.hip shares.
 // Pv / Mv live in registers under compile-time indices; the words of a class beyond the read's own get Eq = 0 and are never looked
 // at (carries only travel upwards).
 #include <hip/hip_runtime.h>
@@ -23,47 +24,17 @@
 #include <string>
 
 #include "kmx_approx.h"
+#include "kmx_align_core.h"
 #include "kmx_kernels.h"
 #include "kmx_vote.h"
 
 namespace {
 
-constexpr uint32_t kBlock = 256;
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kAlignBlock = 64;      // a wave per workgroup in the passes: the lanes run loops of different length
-constexpr int kClasses = 5;               // NW = 1, 2, 4, 8, 16
-constexpr uint8_t CLS_OUT = 255;          // a locus that no pass looks at (skipped, or an empty read)
 enum { CTR_CLASS = 0, CTR_ALIGNED_CLASS = kClasses, CTR_CURSOR = 2 * kClasses, CTR_N_ALIGNED = 3 * kClasses, CTR_N_SKIPPED, CTR_PEQ_WORDS, CTR_COUNT };
 
 using kmx::Buf;
 using Pinned = kmx::PinnedArr;
 using kmx::grid_for;
-
-// what every kernel reads
-struct AlignIn {
-    const uint8_t* ranks;
-    const uint64_t* roff;          // [nr + 1]
-    uint64_t ranks_len;            // letters that may be read (host form: roff[nr]; device form: no bound of ours)
-    const uint64_t* locus_off;     // [nr + 1]
-    const int64_t* diag;
-    const uint32_t* span;
-    uint64_t nr, n_loci, n;
-    const uint64_t* text;          // packed at w bits per letter
-    uint32_t w, sigma, max_edits, max_span;
-};
-
-// letters of read r, 0 when the read is not served: empty, longer than KMX_ALIGN_MAX_READ or outside the letters that may be read
-// (*too_long tells the last two from the first)
-__device__ __forceinline__ uint32_t read_letters(const AlignIn& A, uint64_t r, uint64_t* r0_out, bool* too_long)
-{
-    const uint64_t r0 = A.roff[r], r1 = A.roff[r + 1];
-    *r0_out = r0;
-    const bool ok = r1 >= r0 && r1 <= A.ranks_len && r1 - r0 <= KMX_ALIGN_MAX_READ;
-    *too_long = !ok;
-    return ok ? uint32_t(r1 - r0) : 0u;
-}
-
-__device__ __forceinline__ uint32_t class_of(uint32_t nw) { return nw <= 1 ? 0u : nw <= 2 ? 1u : nw <= 4 ? 2u : nw <= 8 ? 3u : 4u; }
 
 // T = text[lo, hi) of a locus (kmx.h); lo <= hi <= n
 __device__ __forceinline__ void text_window(const AlignIn& A, int64_t D, uint32_t S, uint32_t m, uint64_t* lo, uint64_t* hi)
@@ -73,46 +44,6 @@ __device__ __forceinline__ void text_window(const AlignIn& A, int64_t D, uint32_
     const int64_t h = max(l, min(n, D + int64_t(S) + int64_t(m) + E));
     *lo = uint64_t(l);
     *hi = uint64_t(h);
-}
-
-// ---- the match tables ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_align_count(AlignIn A, uint32_t* __restrict__ pcnt)
-{
-    const uint64_t r = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
-    if (r >= A.nr) return;
-    uint64_t r0;
-    bool too_long;
-    const uint32_t m = read_letters(A, r, &r0, &too_long);
-    const bool has_loci = A.locus_off[r + 1] > A.locus_off[r];  // (a read without loci needs no tables)
-    pcnt[r] = has_loci ? A.sigma * ((m + 63) / 64) : 0u;
-}
-
-// thread t owns word t of the forward table and of the reverse table (the second half of peq)
-__global__ __launch_bounds__(kBlock) void k_align_peq(AlignIn A, const uint64_t* __restrict__ peq_off, uint64_t n_words, uint64_t* __restrict__ peq)
-{
-    const uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
-    if (t >= n_words) return;
-    uint64_t lo = 0, hi = A.nr;                                // the last read whose table starts at or before t (it has one)
-    while (hi - lo > 1) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (peq_off[mid] <= t) lo = mid; else hi = mid;
-    }
-    uint64_t r0;
-    bool too_long;
-    const uint32_t m = read_letters(A, lo, &r0, &too_long);
-    const uint32_t nw = (m + 63) / 64;
-    const uint64_t rem = t - peq_off[lo];
-    if (nw == 0 || rem >= uint64_t(A.sigma) * nw) return;      // (cannot happen: the scan counted these very words)
-    const uint32_t c = uint32_t(rem / nw), b = uint32_t(rem % nw);
-    const uint8_t* q = A.ranks + r0;
-    uint64_t fw = 0, rv = 0;
-    const uint32_t i0 = b * 64, i1 = min(i0 + 64, m);
-    for (uint32_t i = i0; i < i1; ++i) {
-        fw |= uint64_t(q[i] == c) << (i - i0);
-        rv |= uint64_t(q[m - 1 - i] == c) << (i - i0);
-    }
-    peq[t] = fw;
-    peq[n_words + t] = rv;
 }
 
 // ---- classes -------------------------------------------------------------------------------------------------------------------------
@@ -178,33 +109,6 @@ __global__ __launch_bounds__(kBlock) void k_align_place(uint64_t n_loci, const u
     if (c < kClasses) list[s_base[c] + rank] = uint32_t(l);
 }
 
-// ---- the recurrence ------------------------------------------------------------------------------------------------------------------
-// One column of the block recurrence over NW words: eq(b) is the match word of the column's letter, (hp, hm) the horizontal delta
-// that enters word 0 (+1, -1 or neither).  Returns the delta of the score row: bit `lastbit` of word `lastw`.
-template <int NW, typename Eq>
-__device__ __forceinline__ int column(uint64_t (&Pv)[NW], uint64_t (&Mv)[NW], Eq eq, uint64_t hp, uint64_t hm, uint32_t lastw, uint32_t lastbit)
-{
-    uint64_t ph_last = 0, mh_last = 0;
-#pragma unroll
-    for (int b = 0; b < NW; ++b) {
-        uint64_t e = eq(b);
-        const uint64_t pv = Pv[b], mv = Mv[b];
-        const uint64_t xv = e | mv;
-        e |= hm;
-        const uint64_t xh = (((e & pv) + pv) ^ pv) | e;
-        uint64_t ph = mv | ~(xh | pv);
-        uint64_t mh = pv & xh;
-        if (uint32_t(b) == lastw) { ph_last = ph; mh_last = mh; }
-        const uint64_t op = ph >> 63, om = mh >> 63;
-        ph = (ph << 1) | hp;
-        mh = (mh << 1) | hm;
-        Pv[b] = mh | ~(xv | ph);
-        Mv[b] = ph & xv;
-        hp = op;
-        hm = om;
-    }
-    return int((ph_last >> lastbit) & 1) - int((mh_last >> lastbit) & 1);
-}
 
 struct PassIn {
     const uint32_t* lread;

@@ -205,25 +205,7 @@ __global__ __launch_bounds__(kBlock) void k_pair_fold(PairIn P, PairOut O)
     if (threadIdx.x < CTR_COUNT && s_ctr[threadIdx.x]) atomicAdd(&O.ctr[threadIdx.x], (unsigned long long)s_ctr[threadIdx.x]);
 }
 
-} // namespace
-
-struct kmx_pairs {
-    int device = 0;
-    hipStream_t stream = nullptr;          // the stream of the fold that filled the handle (the host view copies on it)
-    uint64_t np = 0, n_concordant = 0, n_discordant = 0, n_single = 0, n_unplaced = 0, n_ambiguous = 0;
-    Buf cls, tlen, score, second_score, ctr;
-    Pinned h_ctr, h_cls, h_tlen, h_score, h_second_score;
-    bool host_valid = false;
-    void release()
-    {
-        for (Buf* b : {&cls, &tlen, &score, &second_score, &ctr}) b->release();
-        for (Pinned* b : {&h_ctr, &h_cls, &h_tlen, &h_score, &h_second_score}) b->release();
-    }
-    void clear() { np = n_concordant = n_discordant = n_single = n_unplaced = n_ambiguous = 0; host_valid = false; }
-};
-
-namespace {
-
+// ---- the host side ----------------------------------------------------------------------------------------------------------------
 kmx_status pair_fold_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, const kmx_pair_options& o, hipStream_t s, kmx_placements* pl, kmx_pairs* pr)
 {
     const uint64_t np = L.nr / 4;

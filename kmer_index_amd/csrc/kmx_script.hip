@@ -535,6 +535,36 @@ kmx_status kmx::scripts_with_best(const char* fn, const kmx_index* index, const 
     return script_call(fn, index, loci, alignments, d_ranks, d_roff, nr, options, false, stream, inout, &P, ranks_len);
 }
 
+kmx_status kmx::scripts_on_arrays(const char* fn, const kmx_index* index, const kmx::LociAccess& L, const kmx::AlignAccess& A, const void* d_ranks,
+                                  const void* d_roff, uint64_t ranks_len, const uint32_t* best, const kmx_script_options* o, hipStream_t stream,
+                                  kmx_scripts** inout)
+{
+    const std::string who = std::string(fn) + ": ";
+    if (!index) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "index is NULL");
+    if (!o) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options is NULL");
+    if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
+    if (o->struct_size < sizeof(kmx_script_options)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
+    if (o->flags & ~(KMX_SCRIPT_ALL | KMX_SCRIPT_M)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "unknown flags");
+    if (o->flags & KMX_SCRIPT_ALL) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "KMX_SCRIPT_ALL ignores best: not for the taken jobs of a rescue");
+    kmx_scripts* h = *inout;
+    auto refuse = [&](kmx_status st, const std::string& msg) {
+        if (h) h->clear();
+        return kmx::set_error(st, who + msg);
+    };
+    kmx::IndexAccess X{};
+    if (!kmx::index_access_on(index, L.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the arrays live on a device that holds no replica of this index");
+    if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    kmx::DeviceGuard dg;
+    TRY_KMX(kmx::bind_handle(inout, L.device));
+    h = *inout;
+    const kmx_status st = script_run(X, L, A, d_ranks, d_roff, ranks_len, best, *o, stream, h);
+    if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
+        (void)hipStreamSynchronize(stream);
+        h->clear();
+    }
+    return st;
+}
+
 extern "C" {
 
 kmx_status kmx_alignments_scripts(const kmx_index* index, const kmx_loci* loci, const kmx_alignments* alignments, const uint8_t* ranks,

@@ -1,5 +1,6 @@
 // The placements handle, which two folds fill: kmx_alignments_fold_strands (kmx_strands.hip, which owns the accessors and the scripts
-// of the winners) and kmx_alignments_fold_pairs (kmx_pairs.hip).  Private to the library.
+// of the winners) and kmx_alignments_fold_pairs (kmx_pairs.hip); the doubled reads (kmx_strands.hip) and the pairs (kmx_pairs.hip),
+// which the mate rescue (kmx_rescue.hip) reads and, with the placements, rewrites.  Private to the library.
 #pragma once
 #include "kmx_handle.h"
 
@@ -30,4 +31,41 @@ struct kmx_placements {
             if (hipError_t e = b->ensure(n); e != hipSuccess) return e;
         return best2.ensure(2 * n * 4);
     }
+};
+
+// the doubled batch of kmx_reads_strands
+struct kmx_strand_reads {
+    int device = 0;
+    hipStream_t stream = nullptr;          // the stream of the call that filled the handle
+    hipStream_t own = nullptr;             // the stream of the host form, created at its first call
+    uint64_t nr2 = 0, letters2 = 0;        // internal reads and their letters
+    kmx::Buf raw, roff, ranks2, roff2;
+    kmx::PinnedArr h_total;
+    void release()
+    {
+        for (kmx::Buf* b : {&raw, &roff, &ranks2, &roff2}) b->release();
+        h_total.release();
+        if (own) {                                             // nothing of this handle's is in flight on the stream that goes
+            (void)hipStreamSynchronize(own);
+            (void)hipStreamDestroy(own);
+        }
+        own = stream = nullptr;
+    }
+    void clear() { nr2 = 0; letters2 = 0; }
+};
+
+// one entry per pair: kmx_alignments_fold_pairs fills it
+struct kmx_pairs {
+    int device = 0;
+    hipStream_t stream = nullptr;          // the stream of the fold that filled the handle (the host view copies on it)
+    uint64_t np = 0, n_concordant = 0, n_discordant = 0, n_single = 0, n_unplaced = 0, n_ambiguous = 0;
+    kmx::Buf cls, tlen, score, second_score, ctr;
+    kmx::PinnedArr h_ctr, h_cls, h_tlen, h_score, h_second_score;
+    bool host_valid = false;
+    void release()
+    {
+        for (kmx::Buf* b : {&cls, &tlen, &score, &second_score, &ctr}) b->release();
+        for (kmx::PinnedArr* b : {&h_ctr, &h_cls, &h_tlen, &h_score, &h_second_score}) b->release();
+    }
+    void clear() { np = n_concordant = n_discordant = n_single = n_unplaced = n_ambiguous = 0; host_valid = false; }
 };

@@ -144,26 +144,6 @@ __global__ __launch_bounds__(kBlock) void k_strand_fold(FoldIn F, FoldOut O)
 
 } // namespace
 
-struct kmx_strand_reads {
-    int device = 0;
-    hipStream_t stream = nullptr;          // the stream of the call that filled the handle
-    hipStream_t own = nullptr;             // the stream of the host form, created at its first call
-    uint64_t nr2 = 0, letters2 = 0;        // internal reads and their letters
-    Buf raw, roff, ranks2, roff2;
-    Pinned h_total;
-    void release()
-    {
-        for (Buf* b : {&raw, &roff, &ranks2, &roff2}) b->release();
-        h_total.release();
-        if (own) {                                             // nothing of this handle's is in flight on the stream that goes
-            (void)hipStreamSynchronize(own);
-            (void)hipStreamDestroy(own);
-        }
-        own = stream = nullptr;
-    }
-    void clear() { nr2 = 0; letters2 = 0; }
-};
-
 kmx::PlacementsAccess kmx::placements_access(const kmx_placements* p)
 {
     return PlacementsAccess{p->device, p->stream, 2 * p->nr, p->best2.as<uint32_t>()};

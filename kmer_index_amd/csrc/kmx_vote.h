@@ -69,5 +69,11 @@ PlacementsAccess placements_access(const kmx_placements* p);   // kmx_strands.hi
 kmx_status scripts_with_best(const char* fn, const kmx_index* index, const kmx_loci* loci, const kmx_alignments* alignments, const void* d_ranks,
                              const void* d_roff, uint64_t nr, uint64_t ranks_len, const kmx_script_options* options, hipStream_t stream,
                              const PlacementsAccess& P, kmx_scripts** inout);
+// kmx_script.hip: the scripts of the entries that best[L.nr] selects among arrays shaped like loci and alignments (L: nr, n_loci and
+// locus_off; A: dist / start / end) over the reads d_ranks / d_roff, on `stream`; the refusals of the options and of the index are
+// those of kmx_alignments_scripts_device, and KMX_SCRIPT_ALL is refused.  kmx_rescues_scripts (kmx_rescue.hip) is its caller.
+kmx_status scripts_on_arrays(const char* fn, const kmx_index* index, const LociAccess& L, const AlignAccess& A, const void* d_ranks,
+                             const void* d_roff, uint64_t ranks_len, const uint32_t* best, const kmx_script_options* options,
+                             hipStream_t stream, kmx_scripts** inout);
 
 } // namespace kmx

@@ -27,6 +27,8 @@ CIGAR_OPS = "MIDNSHP=X"
 PAIR_FR, PAIR_RF, PAIR_FF = 0, 1, 2
 PAIR_UNPLACED, PAIR_CONCORDANT, PAIR_DISCORDANT, PAIR_MATE1_ONLY, PAIR_MATE2_ONLY = 0, 1, 2, 3, 4
 PAIR_NO_PENALTY, PAIR_NO_SCORE = 0xFFFFFFFF, 0xFFFF
+RESCUE_DISCORDANT, RESCUE_MAX_INSERT = 1, 65536
+RESCUE_NONE, RESCUE_FOUND, RESCUE_CONCORDANT, RESCUE_TAKEN = 0, 1, 2, 3
 
 # every symbol include/kmx.h declares
 EXPORTS = [
@@ -50,6 +52,7 @@ EXPORTS = [
     "kmx_alignments_fold_strands", "kmx_placements_counts", "kmx_placements_view", "kmx_placements_view_device", "kmx_placements_free",
     "kmx_placements_scripts",
     "kmx_alignments_fold_pairs", "kmx_pairs_counts", "kmx_pairs_view", "kmx_pairs_view_device", "kmx_pairs_free",
+    "kmx_pairs_rescue", "kmx_rescues_counts", "kmx_rescues_view", "kmx_rescues_view_device", "kmx_rescues_scripts", "kmx_rescues_free",
 ]
 
 
@@ -94,6 +97,11 @@ class FoldOptions(C.Structure):
 class PairOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_insert", C.c_uint32), ("max_insert", C.c_uint32), ("orientation", C.c_uint32),
                 ("unpaired_penalty", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RescueOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_insert", C.c_uint32), ("max_insert", C.c_uint32), ("orientation", C.c_uint32),
+                ("max_edits", C.c_uint32), ("unpaired_penalty", C.c_uint32), ("segment", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class KernelStat(C.Structure):
@@ -266,6 +274,17 @@ def lib():
         L.kmx_pairs_view_device.restype = C.c_int
         L.kmx_pairs_view_device.argtypes = [vp] + [P(vp)] * 4
         L.kmx_pairs_free.argtypes = [vp]
+        L.kmx_pairs_rescue.restype = C.c_int
+        L.kmx_pairs_rescue.argtypes = [vp, vp, vp, vp, P(RescueOptions), vp, vp, P(vp)]
+        L.kmx_rescues_counts.restype = C.c_int
+        L.kmx_rescues_counts.argtypes = [vp] + [P(u64)] * 5
+        L.kmx_rescues_view.restype = C.c_int
+        L.kmx_rescues_view.argtypes = [vp] + [P(vp)] * 8
+        L.kmx_rescues_view_device.restype = C.c_int
+        L.kmx_rescues_view_device.argtypes = [vp] + [P(vp)] * 8
+        L.kmx_rescues_scripts.restype = C.c_int
+        L.kmx_rescues_scripts.argtypes = [vp, vp, vp, P(ScriptOptions), P(vp)]
+        L.kmx_rescues_free.argtypes = [vp]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -723,6 +742,70 @@ class Pairs(_Handle):
         """(d_cls, d_tlen, d_score, d_second_score): kmx_pairs_view_device."""
         return self._device_ptrs("kmx_pairs_view_device", 4)
 
+    def rescue(self, index, reads, loci, alignments, placements, min_insert, max_insert, max_edits, orientation=PAIR_FR, discordant=False,
+               unpaired_penalty=None, segment=0, rescues=None):
+        """kmx_pairs_rescue: every mate that the pair fold left without a locus (the ONLY classes; discordant=True: the mates of
+        DISCORDANT pairs too) is aligned within max_edits edits against the insert window that its placed partner implies, and where
+        that alignment is concordant `placements` and these pairs are rewritten in place.  The handles are those of one map_pairs
+        chain; min_insert / max_insert / orientation as for fold_pairs.  unpaired_penalty=None: a rescued pair always wins (it is only
+        looked at for DISCORDANT pairs).  segment: end columns per thread, 0 = the default; the result never depends on it.  Returns a
+        Rescues (`rescues` reuses one)."""
+        r = rescues or Rescues()
+        o = RescueOptions(C.sizeof(RescueOptions), int(min_insert), int(max_insert), int(orientation), int(max_edits),
+                          PAIR_NO_PENALTY if unpaired_penalty is None else int(unpaired_penalty), int(segment), RESCUE_DISCORDANT if discordant else 0)
+        _check(lib().kmx_pairs_rescue(index._h, reads._h, loci._h, alignments._h, C.byref(o), placements._h, self._h, C.byref(r._h)))
+        r._reads = reads
+        return r
+
+    def close(self):
+        super().close()
+        self._reads = None
+
+
+class Rescues(_Handle):
+    """Owns a kmx_rescues handle (kmx_pairs_rescue): one job per mate that was looked for in its partner's insert window."""
+
+    _free = "kmx_rescues_free"
+
+    def __init__(self):
+        super().__init__()
+        self._reads = None          # the StrandReads whose stream the rescue ran on: it must outlive the views
+
+    def counts(self):
+        return self._counts("kmx_rescues_counts", "nr2", "n_jobs", "n_found", "n_concordant", "n_taken")
+
+    def host(self):
+        """(job_off[nr2+1] u64, read[n_jobs] u32, lo u32, hi u32, dist u8, start u32, end u32, status u8) as numpy copies."""
+        c = self.counts()
+        p = [C.c_void_p() for _ in range(8)]
+        _check(lib().kmx_rescues_view(self._h, *[C.byref(x) for x in p]))
+        dt = (np.uint32, np.uint32, np.uint32, np.uint8, np.uint32, np.uint32, np.uint8)
+        out = [_view(p[0].value, c["nr2"] + 1, np.uint64)] + [_view(x.value, c["n_jobs"], d) for x, d in zip(p[1:], dt)]
+        return tuple(x.copy() for x in out)
+
+    def device_ptrs(self):
+        """(d_job_off, d_read, d_lo, d_hi, d_dist, d_start, d_end, d_status): kmx_rescues_view_device."""
+        return self._device_ptrs("kmx_rescues_view_device", 8)
+
+    def scripts(self, index, reads, m=False, scratch_bytes=0, scripts=None):
+        """kmx_rescues_scripts: the CIGAR of every taken job (for a reverse placement that of the reverse complement against the
+        forward text, as SAM has it), on the stream of `reads`.  Returns a Scripts over the internal reads, sel = the job."""
+        s = scripts or Scripts()
+        o = Alignments._script_options(False, m, scratch_bytes)
+        _check(lib().kmx_rescues_scripts(index._h, reads._h, self._h, C.byref(o), C.byref(s._h)))
+        return s
+
+    def cigars(self, scripts):
+        """One CIGAR string per public read from the Scripts of scripts(): "" where the read was not rescued."""
+        job_off, read, _, _, _, _, _, status = self.host()
+        read_sel_off = scripts.host()[0]
+        strings = scripts.strings()
+        out = [""] * ((job_off.size - 1) // 2)
+        for r, st in zip(read, status):
+            if st == RESCUE_TAKEN and read_sel_off[int(r) + 1] > read_sel_off[int(r)]:
+                out[int(r) // 2] = strings[int(read_sel_off[int(r)])]
+        return out
+
     def close(self):
         super().close()
         self._reads = None
@@ -1061,10 +1144,12 @@ class Index:
             raise
 
     def map_pairs(self, ranks, roff, w, complement, min_insert, max_insert, orientation=PAIR_FR, unpaired_penalty=None, stride=1, band=0,
-                  min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False):
+                  min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False, rescue=False, rescue_edits=None, rescue_discordant=False):
         """map_reads_strands for paired reads: the reads are interleaved mates (read 2p is mate 1 of pair p, read 2p + 1 its mate 2, so
         their number is even), and kmx_alignments_fold_pairs stands in the fold's place.  Returns (StrandReads, Loci, Alignments,
-        Placements, Pairs); scripts=True appends kmx_placements_scripts (the CIGARs of the chosen loci)."""
+        Placements, Pairs); scripts=True appends kmx_placements_scripts (the CIGARs of the chosen loci).  rescue=True runs
+        kmx_pairs_rescue behind the fold (within rescue_edits edits, None: max_edits; rescue_discordant: DISCORDANT pairs too) and
+        appends its Rescues as the last element; the scripts then are those of the placements after the rescue."""
         roff = np.ascontiguousarray(roff, np.uint64)
         if (roff.size - 1) % 2:
             raise ValueError("map_pairs: an odd number of reads; the reads are interleaved mates")
@@ -1087,9 +1172,20 @@ class Index:
             opened += [pl, pairs]
             al.fold_pairs(loci, min_insert, max_insert, orientation, unpaired_penalty, stream=stream, placements=pl, pairs=pairs)
             pl._reads = pairs._reads = reads
-            if not scripts:
-                return reads, loci, al, pl, pairs
-            return reads, loci, al, pl, pairs, pl.scripts(self, reads, loci, al)
+            out = [reads, loci, al, pl, pairs]
+            res = None
+            if rescue:
+                res = Rescues()
+                opened.append(res)
+                pairs.rescue(self, reads, loci, al, pl, min_insert, max_insert, max_edits if rescue_edits is None else rescue_edits, orientation,
+                             rescue_discordant, unpaired_penalty, rescues=res)
+            if scripts:
+                sc = pl.scripts(self, reads, loci, al)
+                opened.append(sc)
+                out.append(sc)
+            if res is not None:
+                out.append(res)
+            return tuple(out)
         except Exception:
             for h in reversed(opened):
                 h.close()

@@ -1008,6 +1008,95 @@ kmx_status kmx_rescues_scripts(const kmx_index* index, const kmx_strand_reads* r
                                const kmx_script_options* options, kmx_scripts** inout);
 void kmx_rescues_free(kmx_rescues* r);
 
+/* ---- SAM tags: the MD string of every script and a MAPQ per read (an extension, no reference interface; a caller detects the
+ *      capability by the macro KMX_SAM_TAGS, KMX_VERSION is unchanged).  The chain gives FLAG, POS, CIGAR, TLEN and NM (= dist)
+ *      of a SAM record; these two calls give what was missing, from arrays that are on the device already.  Neither needs the
+ *      reads.
+ *
+ *      MD.  kmx_scripts_md serves the scripts of kmx_alignments_scripts[_device] (KMX_SCRIPT_ALL or not) and of
+ *      kmx_placements_scripts: `alignments` is the handle the scripts were made from, sel[e] indexes its start / end, bounded
+ *      by n_loci.  kmx_rescues_md serves the scripts of kmx_rescues_scripts: sel[e] indexes the job arrays of `rescues`, bounded
+ *      by n_jobs.  `index` is the index that was searched; its packed text (kmx_index_text) is derived on first use.
+ *      `letters` is a host table of sigma bytes, rank -> output byte (e.g. "ACGT"); duplicates are allowed.  `stream` NULL means
+ *      the stream the scripts handle was filled on, else it is that stream or one the caller has ordered behind it.
+ *
+ *      The contract of entry e, with l = sel[e], s = start[l], t = end[l], n the text length and the runs
+ *      cigar[cig_off[e] .. cig_off[e + 1]): a match counter c = 0 and a text cursor j = s; the runs in order:
+ *        '=' of length len: c += len, j += len;
+ *        'I': nothing;
+ *        'X' of length len: for each letter emit decimal(c), emit letters[text[j]], then c = 0, ++j;
+ *        'D' of length len: emit decimal(c), emit '^', emit letters[text[j .. j + len)], then c = 0, j += len;
+ *      at the end emit decimal(c).  This is the SAM specification's [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*: it gives 0 between
+ *      adjacent mismatches, after a deletion that a mismatch follows, and at either end.  md_off[n_sel + 1] is the exclusive
+ *      prefix sum of the byte counts, md the bytes; there are no terminators.  An entry without runs has an empty MD and is
+ *      not counted.  An entry gets an empty MD and counts in n_mismatched when l is out of bound, when not s <= t <= n, when
+ *      it has an op other than = X I D, or when its = X D lengths do not sum to t - s (or when its MD would take 2^32 bytes or
+ *      more).  With the right handles n_mismatched is 0.  Every access is bounded by n_sel, n_ops, the bound on sel and n:
+ *      foreign handles give meaningless but harmless results.  tests/md_naive.py is this contract in executable form.
+ *
+ *      The md handle.  The device arrays (kmx_md_view_device; md_off is NULL after a refusal or an error, md when n_bytes == 0)
+ *      are complete in stream order when the call returns; kmx_md_view copies to page-locked host memory on first use and
+ *      synchronises, on the stream of the call: 8 bytes per entry and the strings (md_off always holds at least the one
+ *      offset 0).  *inout == NULL allocates; a handle passed in is reused and its earlier views end.  The call only reads the
+ *      other handles.
+ *
+ *      KMX_ERR_INVALID_ARGUMENT before any handle is looked at and before any device is touched: a NULL argument, a
+ *      struct_size that is too small, flags != 0, a letters table with 0, '^' or a digit among its first sigma entries.  After
+ *      looking: a scripts handle made with KMX_SCRIPT_M ('=' and 'X' are no longer apart), handles that live on different
+ *      devices, a device without a replica of the index, an index that kmx_index_extend_query_size_range broke (KMX_ERR_HIP).
+ *      After such a refusal or an error the md handle, when there is one, holds an empty result.
+ *
+ *      MAPQ.  A MAPQ is a convention, not a measurement: this one is a GAP RULE, a heuristic that grows with the distance
+ *      between the chosen placement and its runner-up, and claims no calibration as a probability.  In int64, with E =
+ *      max_edits (the budget the alignments, and the rescue, were made with):
+ *        q(d, s, B) = min(cap, per_edit * max(0, s' - d)),   s' = B + 1 when s is "none", else s;
+ *        read i unplaced (strand == 255): 0;
+ *        otherwise q_se = q(dist[i], second[i], E), where 255 means none;
+ *        without `pairs`, or when cls[i / 2] != KMX_PAIR_CONCORDANT: mapq[i] = q_se;
+ *        for a concordant pair p = i / 2: q_pe = q(score[p], second_score[p], 2 E), where 0xFFFF means none, and
+ *        mapq[i] = min(cap, max(q_se, min(q_pe, q_se + pair_bonus))).
+ *      So a read equal to its reverse complement, or with an equal copy elsewhere, gets 0; a mate inside a repeat that followed
+ *      its unique partner gets min(cap, pair_bonus).  The limit: a rescued pair has second_score == 0xFFFF (no runner-up pair
+ *      is searched for), so it looks unique.  n_zero counts the PLACED reads with mapq 0, n_cap the reads with mapq == cap.
+ *      `pairs` NULL: single reads (kmx_alignments_fold_strands).  `stream` NULL means the stream that filled the placements;
+ *      a rescue rewrites them on the stream of the chain, so the order holds.  tests/mapq_naive.py is this contract in
+ *      executable form.  A placements handle with nr == 0 gives an empty result with all views NULL; kmx_mapq_view copies 1
+ *      byte per read.
+ *
+ *      KMX_ERR_INVALID_ARGUMENT before any handle is looked at: NULL placements, options or inout, a struct_size that is too
+ *      small, flags != 0, max_edits > KMX_ALIGN_MAX_EDITS, cap > 254.  After looking: pairs with 2 np != nr, or that live on
+ *      another device; the mapq handle, when there is one, then holds an empty result.  kmx_stats_get is not extended (see
+ *      kmx_loci_align). */
+#define KMX_SAM_TAGS 1
+typedef struct kmx_md_options {
+    uint32_t struct_size;  /* = sizeof(kmx_md_options): 8 */
+    uint32_t flags;        /* 0 */
+} kmx_md_options;
+typedef struct kmx_md kmx_md;
+kmx_status kmx_scripts_md(const kmx_index* index, const kmx_scripts* scripts, const kmx_alignments* alignments,
+                          const uint8_t* letters, const kmx_md_options* options, void* stream, kmx_md** inout);
+kmx_status kmx_rescues_md(const kmx_index* index, const kmx_scripts* scripts, const kmx_rescues* rescues, const uint8_t* letters,
+                          const kmx_md_options* options, void* stream, kmx_md** inout);
+kmx_status kmx_md_counts(const kmx_md* m, uint64_t* n_sel, uint64_t* n_bytes, uint64_t* n_mismatched);
+kmx_status kmx_md_view(kmx_md* m, const uint64_t** md_off /* n_sel + 1 */, const uint8_t** md /* n_bytes */);
+kmx_status kmx_md_view_device(const kmx_md* m, const uint64_t** d_md_off, const uint8_t** d_md);
+void kmx_md_free(kmx_md* m);
+typedef struct kmx_mapq_options {
+    uint32_t struct_size;  /* = sizeof(kmx_mapq_options): 24 */
+    uint32_t max_edits;    /* E <= KMX_ALIGN_MAX_EDITS: the budget the alignments (and the rescue) were made with */
+    uint32_t cap;          /* <= 254 (255 is SAM's "unavailable") */
+    uint32_t per_edit;
+    uint32_t pair_bonus;
+    uint32_t flags;        /* 0 */
+} kmx_mapq_options;
+typedef struct kmx_mapq kmx_mapq;
+kmx_status kmx_placements_mapq(const kmx_placements* placements, const kmx_pairs* pairs /* NULL: single reads */,
+                               const kmx_mapq_options* options, void* stream, kmx_mapq** inout);
+kmx_status kmx_mapq_counts(const kmx_mapq* m, uint64_t* nr, uint64_t* n_zero, uint64_t* n_cap);
+kmx_status kmx_mapq_view(kmx_mapq* m, const uint8_t** mapq /* nr */);
+kmx_status kmx_mapq_view_device(const kmx_mapq* m, const uint8_t** d_mapq);
+void kmx_mapq_free(kmx_mapq* m);
+
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.
  * Works on built, loaded and replicated indexes (this replica).  The first call derives a copy packed at 2, 4 or 8 bits per

@@ -392,6 +392,11 @@ struct kmx_rescues {
     void clear() { nr2 = n_jobs = n_found = n_concordant = n_taken = 0; filled = false; host_valid = false; }
 };
 
+kmx::JobsAccess kmx::rescues_access(const kmx_rescues* r)
+{
+    return JobsAccess{r->device, r->stream, r->n_jobs, r->start.as<uint32_t>(), r->end.as<uint32_t>()};
+}
+
 namespace {
 
 template <int NW>

@@ -349,6 +349,7 @@ struct kmx_scripts {
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t nr = 0, n_sel = 0, n_ops = 0, n_mismatched = 0;
     bool filled = false;                   // a call has succeeded since the last refusal or error
+    uint32_t flags = 0;                    // the options' flags of the call that filled the handle (kmx_scripts_md refuses KMX_SCRIPT_M)
     // results
     Buf read_sel_off, sel, cig_off, cigar;
     // scratch
@@ -386,6 +387,7 @@ kmx_status script_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const
     const uint64_t nr = L.nr, nl = L.n_loci;
     h->stream = s;
     h->clear();
+    h->flags = o.flags;
     (void)hipGetLastError();
     TRY_HIP(h->read_sel_off.ensure((nr + 1) * 8));
     if (nr == 0 || nl == 0) {                                  // no entry: no launch indexes an empty array
@@ -527,6 +529,11 @@ kmx_status script_call(const char* fn, const kmx_index* index, const kmx_loci* l
 }
 
 } // namespace
+
+kmx::ScriptsAccess kmx::scripts_access(const kmx_scripts* s)
+{
+    return ScriptsAccess{s->device, s->stream, s->n_sel, s->n_ops, s->flags, s->sel.as<uint32_t>(), s->cig_off.as<uint64_t>(), s->cigar.as<uint32_t>()};
+}
 
 kmx_status kmx::scripts_with_best(const char* fn, const kmx_index* index, const kmx_loci* loci, const kmx_alignments* alignments, const void* d_ranks,
                                   const void* d_roff, uint64_t nr, uint64_t ranks_len, const kmx_script_options* options, hipStream_t stream,

@@ -76,4 +76,29 @@ kmx_status scripts_on_arrays(const char* fn, const kmx_index* index, const LociA
                              const void* d_roff, uint64_t ranks_len, const uint32_t* best, const kmx_script_options* options,
                              hipStream_t stream, kmx_scripts** inout);
 
+// What the MD strings (kmx_tags.hip) need from a scripts handle (kmx_script.hip owns struct kmx_scripts): device pointers that belong
+// to the handle and stay as they are (the MD only reads them).  sel is only looked at when n_sel > 0, cigar when n_ops > 0; a handle
+// that no call has filled (or whose last call was refused) has n_sel = 0.  flags: the kmx_script_options::flags of the call that
+// filled it.
+struct ScriptsAccess {
+    int device;
+    hipStream_t stream;            // the stream of the call that filled the handle
+    uint64_t n_sel, n_ops;
+    uint32_t flags;
+    const uint32_t* sel;           // [n_sel]
+    const uint64_t* cig_off;       // [n_sel + 1]
+    const uint32_t* cigar;         // [n_ops]
+};
+ScriptsAccess scripts_access(const kmx_scripts* s);   // kmx_script.hip
+
+// ... and from the job arrays of a rescues handle (kmx_rescue.hip owns struct kmx_rescues), which the sel of kmx_rescues_scripts indexes
+struct JobsAccess {
+    int device;
+    hipStream_t stream;            // the stream of the rescue that filled the handle
+    uint64_t n_jobs;
+    const uint32_t* start;         // [n_jobs]
+    const uint32_t* end;
+};
+JobsAccess rescues_access(const kmx_rescues* r);   // kmx_rescue.hip
+
 } // namespace kmx

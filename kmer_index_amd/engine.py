@@ -3,6 +3,7 @@
 Every search goes through libkmx.so (hand-written gfx950 kernels).  There is no Python or
 CPU search path in this package: when the library or a device is missing, calls raise.
 """
+import collections
 import ctypes as C
 import os
 
@@ -53,6 +54,8 @@ EXPORTS = [
     "kmx_placements_scripts",
     "kmx_alignments_fold_pairs", "kmx_pairs_counts", "kmx_pairs_view", "kmx_pairs_view_device", "kmx_pairs_free",
     "kmx_pairs_rescue", "kmx_rescues_counts", "kmx_rescues_view", "kmx_rescues_view_device", "kmx_rescues_scripts", "kmx_rescues_free",
+    "kmx_scripts_md", "kmx_rescues_md", "kmx_md_counts", "kmx_md_view", "kmx_md_view_device", "kmx_md_free",
+    "kmx_placements_mapq", "kmx_mapq_counts", "kmx_mapq_view", "kmx_mapq_view_device", "kmx_mapq_free",
 ]
 
 
@@ -102,6 +105,15 @@ class PairOptions(C.Structure):
 class RescueOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_insert", C.c_uint32), ("max_insert", C.c_uint32), ("orientation", C.c_uint32),
                 ("max_edits", C.c_uint32), ("unpaired_penalty", C.c_uint32), ("segment", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MdOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MapqOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_edits", C.c_uint32), ("cap", C.c_uint32), ("per_edit", C.c_uint32),
+                ("pair_bonus", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class KernelStat(C.Structure):
@@ -285,6 +297,26 @@ def lib():
         L.kmx_rescues_scripts.restype = C.c_int
         L.kmx_rescues_scripts.argtypes = [vp, vp, vp, P(ScriptOptions), P(vp)]
         L.kmx_rescues_free.argtypes = [vp]
+        L.kmx_scripts_md.restype = C.c_int
+        L.kmx_scripts_md.argtypes = [vp, vp, vp, vp, P(MdOptions), vp, P(vp)]
+        L.kmx_rescues_md.restype = C.c_int
+        L.kmx_rescues_md.argtypes = [vp, vp, vp, vp, P(MdOptions), vp, P(vp)]
+        L.kmx_md_counts.restype = C.c_int
+        L.kmx_md_counts.argtypes = [vp] + [P(u64)] * 3
+        L.kmx_md_view.restype = C.c_int
+        L.kmx_md_view.argtypes = [vp] + [P(vp)] * 2
+        L.kmx_md_view_device.restype = C.c_int
+        L.kmx_md_view_device.argtypes = [vp] + [P(vp)] * 2
+        L.kmx_md_free.argtypes = [vp]
+        L.kmx_placements_mapq.restype = C.c_int
+        L.kmx_placements_mapq.argtypes = [vp, vp, P(MapqOptions), vp, P(vp)]
+        L.kmx_mapq_counts.restype = C.c_int
+        L.kmx_mapq_counts.argtypes = [vp] + [P(u64)] * 3
+        L.kmx_mapq_view.restype = C.c_int
+        L.kmx_mapq_view.argtypes = [vp, P(vp)]
+        L.kmx_mapq_view_device.restype = C.c_int
+        L.kmx_mapq_view_device.argtypes = [vp, P(vp)]
+        L.kmx_mapq_free.argtypes = [vp]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -649,6 +681,92 @@ class Scripts(_Handle):
         runs = [f"{int(v) >> 4}{CIGAR_OPS[int(v) & 15]}" for v in cigar]
         return ["".join(runs[int(a):int(b)]) for a, b in zip(cig_off[:-1], cig_off[1:])]
 
+    def md(self, index, source, letters, stream=0, md=None):
+        """kmx_scripts_md (source: the Alignments these scripts were made from) or kmx_rescues_md (source: the Rescues): the MD
+        string of every entry, from the runs and the index's text.  letters: sigma output bytes by rank (a str, bytes or uint8
+        array, e.g. "ACGT").  stream=0: the stream that filled this handle.  Returns an Md (`md` reuses one)."""
+        if isinstance(source, Rescues):
+            fn = lib().kmx_rescues_md
+        elif isinstance(source, Alignments):
+            fn = lib().kmx_scripts_md
+        else:
+            raise TypeError("Scripts.md: source is an Alignments or a Rescues")
+        table = None if letters is None else _letters_table(letters)
+        out = md or Md()
+        o = MdOptions(C.sizeof(MdOptions), 0)
+        _check(fn(index._h, self._h, source._h, table.ctypes.data if table is not None else None, C.byref(o), stream or None, C.byref(out._h)))
+        return out
+
+
+def _letters_table(letters):
+    """The rank -> output byte table as a contiguous uint8 array."""
+    if isinstance(letters, str):
+        letters = letters.encode("ascii")
+    if isinstance(letters, (bytes, bytearray)):
+        return np.frombuffer(bytes(letters), np.uint8).copy()
+    return np.ascontiguousarray(letters, np.uint8)
+
+
+class Md(_Handle):
+    """Owns a kmx_md handle (kmx_scripts_md, kmx_rescues_md): the MD string of every entry of a Scripts."""
+
+    _free = "kmx_md_free"
+
+    def __init__(self):
+        super().__init__()
+        self._reads = None          # the StrandReads whose stream the call ran on: it must outlive the views
+
+    def close(self):
+        super().close()
+        self._reads = None
+
+    def counts(self):
+        return self._counts("kmx_md_counts", "n_sel", "n_bytes", "n_mismatched")
+
+    def host(self):
+        """(md_off[n_sel+1] u64, md[n_bytes] u8) as numpy copies."""
+        c = self.counts()
+        p = [C.c_void_p() for _ in range(2)]
+        _check(lib().kmx_md_view(self._h, *[C.byref(x) for x in p]))
+        return _view(p[0].value, c["n_sel"] + 1, np.uint64).copy(), _view(p[1].value, c["n_bytes"], np.uint8).copy()
+
+    def device_ptrs(self):
+        """(d_md_off, d_md): kmx_md_view_device."""
+        return self._device_ptrs("kmx_md_view_device", 2)
+
+    def strings(self):
+        """One MD string per entry, e.g. "50A30^C69" ("" for an entry without a script)."""
+        md_off, md = self.host()
+        raw = md.tobytes()
+        return [raw[int(a):int(b)].decode("latin-1") for a, b in zip(md_off[:-1], md_off[1:])]
+
+
+class Mapq(_Handle):
+    """Owns a kmx_mapq handle (kmx_placements_mapq): one MAPQ per public read."""
+
+    _free = "kmx_mapq_free"
+
+    def __init__(self):
+        super().__init__()
+        self._reads = None          # the StrandReads whose stream the call ran on: it must outlive the views
+
+    def close(self):
+        super().close()
+        self._reads = None
+
+    def counts(self):
+        return self._counts("kmx_mapq_counts", "nr", "n_zero", "n_cap")
+
+    def host(self):
+        """mapq[nr] u8 as a numpy copy."""
+        p = C.c_void_p()
+        _check(lib().kmx_mapq_view(self._h, C.byref(p)))
+        return _view(p.value, self.counts()["nr"], np.uint8).copy()
+
+    def device_ptrs(self):
+        """(d_mapq,): kmx_mapq_view_device."""
+        return self._device_ptrs("kmx_mapq_view_device", 1)
+
 
 class StrandReads(_Handle):
     """Owns a kmx_strand_reads handle (kmx_reads_strands): every read and its reverse complement, on the device.  After
@@ -703,16 +821,33 @@ class Placements(_Handle):
         _check(lib().kmx_placements_scripts(index._h, reads._h, loci._h, alignments._h, self._h, C.byref(o), C.byref(s._h)))
         return s
 
-    def cigars(self, scripts):
-        """One CIGAR string per public read from the Scripts of scripts(): "" where the read is unplaced."""
+    def _per_read(self, scripts, strings):
+        """strings holds one string per entry of `scripts`: the string of every public read's winner, "" where it has none"""
         strand = self.host(best2=False)[1]
         read_sel_off = scripts.host()[0]
-        strings = scripts.strings()
         out = []
         for i, s in enumerate(strand):
             r = 2 * i + int(s)
             out.append(strings[int(read_sel_off[r])] if s != 255 and read_sel_off[r + 1] > read_sel_off[r] else "")
         return out
+
+    def cigars(self, scripts):
+        """One CIGAR string per public read from the Scripts of scripts(): "" where the read is unplaced."""
+        return self._per_read(scripts, scripts.strings())
+
+    def mds(self, md, scripts):
+        """One MD string per public read from the Md of scripts.md(): "" where cigars(scripts) has none."""
+        return self._per_read(scripts, md.strings())
+
+    def mapq(self, max_edits, pairs=None, cap=60, per_edit=10, pair_bonus=40, stream=0, mapq=None):
+        """kmx_placements_mapq: one MAPQ per read by the gap rule of include/kmx.h (a heuristic), from dist and second and, with
+        `pairs`, from the score and second_score of concordant pairs.  max_edits: the budget the alignments (and the rescue) were
+        made with.  stream=0: the stream that filled this handle.  Returns a Mapq (`mapq` reuses one)."""
+        q = mapq or Mapq()
+        o = MapqOptions(C.sizeof(MapqOptions), int(max_edits), int(cap), int(per_edit), int(pair_bonus), 0)
+        _check(lib().kmx_placements_mapq(self._h, pairs._h if pairs is not None else None, C.byref(o), stream or None, C.byref(q._h)))
+        q._reads = self._reads
+        return q
 
     def close(self):
         super().close()
@@ -795,16 +930,23 @@ class Rescues(_Handle):
         _check(lib().kmx_rescues_scripts(index._h, reads._h, self._h, C.byref(o), C.byref(s._h)))
         return s
 
-    def cigars(self, scripts):
-        """One CIGAR string per public read from the Scripts of scripts(): "" where the read was not rescued."""
+    def _per_read(self, scripts, strings):
+        """strings holds one string per entry of `scripts`: the string of every rescued public read, "" for every other"""
         job_off, read, _, _, _, _, _, status = self.host()
         read_sel_off = scripts.host()[0]
-        strings = scripts.strings()
         out = [""] * ((job_off.size - 1) // 2)
         for r, st in zip(read, status):
             if st == RESCUE_TAKEN and read_sel_off[int(r) + 1] > read_sel_off[int(r)]:
                 out[int(r) // 2] = strings[int(read_sel_off[int(r)])]
         return out
+
+    def cigars(self, scripts):
+        """One CIGAR string per public read from the Scripts of scripts(): "" where the read was not rescued."""
+        return self._per_read(scripts, scripts.strings())
+
+    def mds(self, md, scripts):
+        """One MD string per public read from the Md of scripts.md(): "" where cigars(scripts) has none."""
+        return self._per_read(scripts, md.strings())
 
     def close(self):
         super().close()
@@ -836,6 +978,60 @@ def sam_pair_fields(strand, start, cls, tlen):
     t = np.repeat(tlen, 2)
     t[1::2] = -t[1::2]
     return flag, pos, pos[mate], t.astype(np.int32)
+
+
+# what map_reads_strands / map_pairs append with tags=True: the Mapq, the Md of the scripts, and after a rescue the Scripts of the
+# rescued mates and their Md (else None)
+SamTags = collections.namedtuple("SamTags", "mapq md rescue_scripts rescue_md")
+
+
+def _first_given(strings):
+    """A list of strings, or several lists of equal length (the placements', then the rescue's): per read the first that is not empty."""
+    if strings and not isinstance(strings[0], str):
+        return [next((s for s in group if s), "") for group in zip(*strings)]
+    return list(strings)
+
+
+def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements_host, cigars, mds, mapq, pairs_host=None):
+    """One SAM line (no newline) per public read from host arrays: the reads (ranks, roff), the rank -> letter table, the rank
+    complement table, Placements.host(), the CIGAR and MD strings per read (Placements.cigars / .mds; a tuple of two lists, the
+    placements' and the rescue's, gives a rescued read those of the rescue), Mapq.host() and, for paired reads, Pairs.host().
+    FLAG / POS / PNEXT / TLEN come from sam_pair_fields when pairs_host is given; otherwise FLAG is 0 / 4 / 16, POS is start + 1 and
+    there is no mate.  CIGAR is * when the read is unplaced, RNEXT = or *, SEQ the reverse complement for a reverse placement,
+    QUAL *; placed reads carry NM:i: (the distance) and MD:Z:.  Pure Python / numpy: no device is needed."""
+    table = _letters_table(letters)
+    comp = np.ascontiguousarray(complement, np.uint8)
+    if table.size < sigma or comp.size < sigma:
+        raise ValueError("sam_lines: letters and complement need sigma entries")
+    ranks = np.asarray(ranks, np.uint8)
+    roff = np.asarray(roff, np.uint64)
+    strand, dist, start = (np.asarray(placements_host[k]) for k in (1, 2, 3))
+    nr = strand.size
+    cigars, mds = _first_given(cigars), _first_given(mds)
+    mapq = np.asarray(mapq, np.uint8)
+    if not (roff.size - 1 == len(qnames) == len(cigars) == len(mds) == mapq.size == nr):
+        raise ValueError("sam_lines: the arrays disagree in the number of reads")
+    placed = strand != 255
+    if pairs_host is not None:
+        flag, pos, pnext, tlen = sam_pair_fields(strand, start, pairs_host[0], pairs_host[1])
+    else:
+        flag = np.where(placed, np.where(strand == 1, 0x10, 0), 0x4)
+        pos = np.where(placed, start.astype(np.int64) + 1, 0)
+        pnext, tlen = np.zeros(nr, np.int64), np.zeros(nr, np.int32)
+    lines = []
+    for i in range(nr):
+        q = ranks[int(roff[i]):int(roff[i + 1])]
+        if (q >= sigma).any():
+            raise ValueError(f"sam_lines: read {i} holds a letter outside the alphabet")
+        if placed[i] and strand[i] == 1:
+            q = comp[q[::-1]]
+        seq = table[q].tobytes().decode("latin-1") or "*"
+        fields = [str(qnames[i]), str(int(flag[i])), rname if pos[i] else "*", str(int(pos[i])), str(int(mapq[i])),
+                  (cigars[i] or "*") if placed[i] else "*", "=" if pnext[i] else "*", str(int(pnext[i])), str(int(tlen[i])), seq, "*"]
+        if placed[i]:
+            fields += [f"NM:i:{int(dist[i])}", f"MD:Z:{mds[i]}"]
+        lines.append("\t".join(fields))
+    return lines
 
 
 class ApproxResult(_Handle):
@@ -1112,11 +1308,16 @@ class Index:
                                               stream or None, C.byref(s._h)))
         return s
 
-    def map_reads_strands(self, ranks, roff, w, complement, stride=1, band=0, min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False):
+    def map_reads_strands(self, ranks, roff, w, complement, stride=1, band=0, min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False,
+                          tags=False, letters=None):
         """map_reads on both strands: kmx_reads_strands, kmx_search_windows_device, kmx_windows_vote, kmx_loci_align_device and
         kmx_alignments_fold_strands in a row, all on the stream of the StrandReads.  Returns (StrandReads, Loci, Alignments,
         Placements): the loci and alignments are those of the doubled batch (internal read 2i is read i, 2i + 1 its reverse
-        complement), the placements one per read.  scripts=True appends kmx_placements_scripts (the CIGARs of the winners)."""
+        complement), the placements one per read.  scripts=True appends kmx_placements_scripts (the CIGARs of the winners).
+        tags=True (needs `letters`, the rank -> letter table; implies scripts) appends a SamTags(mapq, md, None, None) as the last
+        element: kmx_placements_mapq and kmx_scripts_md."""
+        if tags and letters is None:
+            raise ValueError("map_reads_strands: tags=True needs letters")
         if max_span is None:
             max_span = 0xFFFFFFFF
         opened = []
@@ -1135,21 +1336,35 @@ class Index:
             pl = al.fold_strands(loci, stream=stream)
             pl._reads = reads
             opened.append(pl)
-            if not scripts:
+            if not scripts and not tags:
                 return reads, loci, al, pl
-            return reads, loci, al, pl, pl.scripts(self, reads, loci, al)
+            sc = pl.scripts(self, reads, loci, al)
+            opened.append(sc)
+            if not tags:
+                return reads, loci, al, pl, sc
+            mq = pl.mapq(max_edits)
+            opened.append(mq)
+            md = sc.md(self, al, letters)
+            md._reads = reads
+            return reads, loci, al, pl, sc, SamTags(mq, md, None, None)
         except Exception:
             for h in reversed(opened):
                 h.close()
             raise
 
     def map_pairs(self, ranks, roff, w, complement, min_insert, max_insert, orientation=PAIR_FR, unpaired_penalty=None, stride=1, band=0,
-                  min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False, rescue=False, rescue_edits=None, rescue_discordant=False):
+                  min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False, rescue=False, rescue_edits=None, rescue_discordant=False,
+                  tags=False, letters=None):
         """map_reads_strands for paired reads: the reads are interleaved mates (read 2p is mate 1 of pair p, read 2p + 1 its mate 2, so
         their number is even), and kmx_alignments_fold_pairs stands in the fold's place.  Returns (StrandReads, Loci, Alignments,
         Placements, Pairs); scripts=True appends kmx_placements_scripts (the CIGARs of the chosen loci).  rescue=True runs
         kmx_pairs_rescue behind the fold (within rescue_edits edits, None: max_edits; rescue_discordant: DISCORDANT pairs too) and
-        appends its Rescues as the last element; the scripts then are those of the placements after the rescue."""
+        appends its Rescues as the last element; the scripts then are those of the placements after the rescue.  tags=True (needs
+        `letters`, the rank -> letter table; implies scripts) appends, behind everything else, a SamTags(mapq, md, rescue_scripts,
+        rescue_md): kmx_placements_mapq with the pairs (its budget the larger of max_edits and rescue_edits), kmx_scripts_md, and
+        after a rescue kmx_rescues_scripts and kmx_rescues_md (else None)."""
+        if tags and letters is None:
+            raise ValueError("map_pairs: tags=True needs letters")
         roff = np.ascontiguousarray(roff, np.uint64)
         if (roff.size - 1) % 2:
             raise ValueError("map_pairs: an odd number of reads; the reads are interleaved mates")
@@ -1179,12 +1394,26 @@ class Index:
                 opened.append(res)
                 pairs.rescue(self, reads, loci, al, pl, min_insert, max_insert, max_edits if rescue_edits is None else rescue_edits, orientation,
                              rescue_discordant, unpaired_penalty, rescues=res)
-            if scripts:
+            if scripts or tags:
                 sc = pl.scripts(self, reads, loci, al)
                 opened.append(sc)
                 out.append(sc)
             if res is not None:
                 out.append(res)
+            if tags:
+                budget = max_edits if not rescue or rescue_edits is None else max(max_edits, rescue_edits)
+                mq = pl.mapq(budget, pairs)
+                opened.append(mq)
+                md = sc.md(self, al, letters)
+                md._reads = reads
+                opened.append(md)
+                rsc = rmd = None
+                if res is not None:
+                    rsc = res.scripts(self, reads)
+                    opened.append(rsc)
+                    rmd = rsc.md(self, res, letters)
+                    rmd._reads = reads
+                out.append(SamTags(mq, md, rsc, rmd))
             return tuple(out)
         except Exception:
             for h in reversed(opened):

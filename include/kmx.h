@@ -1097,6 +1097,87 @@ kmx_status kmx_mapq_view(kmx_mapq* m, const uint8_t** mapq /* nr */);
 kmx_status kmx_mapq_view_device(const kmx_mapq* m, const uint8_t** d_mapq);
 void kmx_mapq_free(kmx_mapq* m);
 
+/* ---- Multi-sequence references: a contig table through the mapping chain (an extension, no reference interface; a caller
+ *      detects the capability by the macro KMX_MAP_CONTIGS, KMX_VERSION is unchanged).  A real reference has many sequences
+ *      (chromosomes, contigs, transcripts, amplicons); the index text is their concatenation.  With a table on the index the
+ *      device stages that choose (alignment window, pair fold, rescue window) keep every alignment, pair and rescue inside one
+ *      contig, and kmx_placements_locate turns a placement into (contig, position inside it).  AN INDEX WITHOUT A TABLE BEHAVES
+ *      EXACTLY AS BEFORE, IN EVERY CALL.
+ *
+ *      The table.  kmx_index_set_contigs(index, ctg_off, nc): contig c is text[ctg_off[c], ctg_off[c + 1]), ctg_off is a host
+ *      array of nc + 1 offsets that is copied (to every replica of the index).  nc == 0 removes the table (ctg_off is not looked
+ *      at).  KMX_ERR_INVALID_ARGUMENT, the table that was there staying in place: a NULL index, NULL ctg_off with nc > 0,
+ *      nc >= 0xFFFFFFFF, ctg_off[0] != 0, offsets that are not strictly ascending (an empty contig), ctg_off[nc] != n (the
+ *      text length); KMX_ERR_HIP for an index that kmx_index_extend_query_size_range broke.  Every successful call gives the
+ *      index a new table GENERATION (a private counter).  It must not be called while a chain call on this index is in flight
+ *      on another thread; it synchronises the devices of the index before it frees the previous table, so kernels that were
+ *      enqueued earlier have finished reading it.  kmx_index_contigs reads the table back: *nc (0: none) and, when ctg_off_out
+ *      is not NULL, the nc + 1 offsets (cap, the room in offsets, must be at least nc + 1).  THE TABLE IS NOT PART OF THE
+ *      SAVED IMAGE (kmx_index_save / kmx_index_load are unchanged): a caller sets it again after kmx_index_load.
+ *
+ *      Alignment.  kmx_loci_align[_device] on an index with a table: for every locus l that is not skipped, in int64 with
+ *      D = diag[l], S = span[l], m the read's length, E = max_edits and floor division,
+ *        mid  = clamp(D + (S + m) / 2, 0, n - 1),     c(l) = the contig that contains mid,
+ *        lo   = min(max(ctg_off[c], D - E), ctg_off[c + 1]),
+ *        hi   = max(lo, min(ctg_off[c + 1], D + S + m + E)),
+ *      and everything else by the contract of kmx_loci_align over T = text[lo, hi): a read that overhangs the contig's end
+ *      comes out with the overhang deleted, exactly as at the ends of the text without a table.  Equivalently: the contract
+ *      without a table, applied to the contig's letters alone with diagonal D - ctg_off[c], shifted back by ctg_off[c].  No
+ *      aligned [start, end) therefore contains a junction.  The handle keeps c(l) per locus: kmx_alignments_contigs_view and
+ *      kmx_alignments_contigs_view_device give ctg[n_loci] (u32; 0xFFFFFFFF for a skipped locus, c(l) for every other one,
+ *      KMX_ALIGN_NONE loci included) and *nc, the contigs of the table the call saw; ctg is NULL (and *nc 0) when the handle
+ *      was made without a table, and NULL when n_loci == 0.  The host view copies 4 bytes per locus on first use.  The handle
+ *      also records the generation of the table.
+ *
+ *      Pair fold.  kmx_alignments_fold_pairs on alignments that carry ctg: (x, y) is concordant only if ctg[x] == ctg[y] as
+ *      well, for the candidate and for second_score alike.  Nothing else changes; the call takes no index.
+ *      kmx_alignments_fold_strands is unchanged.
+ *
+ *      Rescue.  kmx_pairs_rescue: the anchor of a job is placed by a locus, its contig is ctg[locus[anchor]], and the job's
+ *      window [lo, hi) is clamped to that contig (ctg_off[c] in the place of 0, ctg_off[c + 1] in the place of n).  A rescued
+ *      mate therefore lies in its anchor's contig.  The call is refused after looking at the handles
+ *      (KMX_ERR_INVALID_ARGUMENT, the rescues handle then holds an empty result) when the alignments' nc or generation
+ *      differs from the index's: a handle made without a table, or under another one.
+ *
+ *      kmx_placements_locate(index, alignments, placements, options, stream, &located): per public read i of the placements
+ *      (of kmx_alignments_fold_strands, of kmx_alignments_fold_pairs, or after a rescue), ctg[i] and pos[i] (u32 each):
+ *        unplaced (strand == 255): 0xFFFFFFFF and 0;
+ *        placed by a locus: c = alignments.ctg[locus[i]];
+ *        rescued (placed, locus == 0xFFFFFFFF): with KMX_LOCATE_MATES in flags (the reads are interleaved mates, nr even)
+ *          c = alignments.ctg[locus[i ^ 1]], the mate's;
+ *        pos[i] = start[i] - ctg_off[c]   (0-based; SAM's POS is pos + 1).
+ *      No search is made, and the answer is exact even for an empty alignment that sits on a junction.  An entry is written
+ *      as unplaced and counted in n_mismatched when the locus is outside n_loci, when c >= nc, when start is outside
+ *      [ctg_off[c], ctg_off[c + 1]], or when a rescued read comes without the flag or without a mate placed by a locus;
+ *      n_located counts the other placed reads.  With the right handles n_mismatched is 0.  Every access is bounded by nr,
+ *      n_loci and nc: foreign handles give meaningless but harmless results.  `stream` NULL means the stream that filled the
+ *      placements.  The located handle follows the lifecycle of the other chain handles: *inout == NULL allocates, a handle
+ *      passed in is reused and its earlier views end; the device arrays (kmx_located_view_device, NULL when nr == 0) are
+ *      complete in stream order when the call returns; kmx_located_view copies 8 bytes per read to page-locked host memory
+ *      on first use and synchronises.  KMX_ERR_INVALID_ARGUMENT before any handle is looked at: a NULL argument, a
+ *      struct_size that is too small, an unknown flag.  After looking (the located handle, when there is one, then holds an
+ *      empty result): KMX_LOCATE_MATES with an odd nr, placements whose 2 nr differs from the alignments' nr, handles on
+ *      different devices, a device without a replica of the index, a broken index (KMX_ERR_HIP), alignments whose nc or
+ *      generation differs from the index's, an index without a table.  tests/contig_naive.py is all of this in executable
+ *      form.  Untested: an index with more than one replica.  kmx_stats_get is not extended (see kmx_loci_align). */
+#define KMX_MAP_CONTIGS 1
+#define KMX_LOCATE_MATES 1u   /* the reads are interleaved mates: a rescued read takes its mate's contig */
+kmx_status kmx_index_set_contigs(kmx_index* index, const uint64_t* ctg_off /* nc + 1 */, uint64_t nc);
+kmx_status kmx_index_contigs(const kmx_index* index, uint64_t* nc, uint64_t* ctg_off_out, uint64_t cap);
+kmx_status kmx_alignments_contigs_view(kmx_alignments* a, const uint32_t** ctg /* n_loci */, uint64_t* nc);
+kmx_status kmx_alignments_contigs_view_device(const kmx_alignments* a, const uint32_t** d_ctg, uint64_t* nc);
+typedef struct kmx_locate_options {
+    uint32_t struct_size;  /* = sizeof(kmx_locate_options): 8 */
+    uint32_t flags;        /* 0 or KMX_LOCATE_MATES */
+} kmx_locate_options;
+typedef struct kmx_located kmx_located;
+kmx_status kmx_placements_locate(const kmx_index* index, const kmx_alignments* alignments, const kmx_placements* placements,
+                                 const kmx_locate_options* options, void* stream, kmx_located** inout);
+kmx_status kmx_located_counts(const kmx_located* l, uint64_t* nr, uint64_t* n_located, uint64_t* n_mismatched);
+kmx_status kmx_located_view(kmx_located* l, const uint32_t** ctg /* nr */, const uint32_t** pos /* nr */);
+kmx_status kmx_located_view_device(const kmx_located* l, const uint32_t** d_ctg, const uint32_t** d_pos);
+void kmx_located_free(kmx_located* l);
+
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.
  * Works on built, loaded and replicated indexes (this replica).  The first call derives a copy packed at 2, 4 or 8 bits per

@@ -6,7 +6,8 @@
 //   k_align_peq        a thread per table word: bit i of Peq[read][letter][word] = (q[64 * word + i] == letter), and the same for the
 //                      reversed read; letters >= sigma set no bit
 //   k_align_classify   a thread per locus: its read (binary search of locus_off), skipped or not, its class NW in {1, 2, 4, 8, 16}
-//                      (the smallest that holds the read), counted per class
+//                      (the smallest that holds the read), counted per class; when the index has a contig table (KMX_MAP_CONTIGS), the
+//                      contig of the locus, found once by binary search and kept in ctg[] for the passes and the later stages
 //   k_align_place      the loci of every class listed together (a workgroup reserves its part of each class with one atomic)
 //   k_align_fwd<NW>    forward pass over T = text[lo, hi): carry-in 0 (the alignment may start anywhere), the score followed at bit
 //                      (m - 1) % 64 of word (m - 1) / 64, the minimum and the first column that reaches it kept; loci with d <= E are
@@ -36,20 +37,37 @@ using kmx::Buf;
 using Pinned = kmx::PinnedArr;
 using kmx::grid_for;
 
-// T = text[lo, hi) of a locus (kmx.h); lo <= hi <= n
-__device__ __forceinline__ void text_window(const AlignIn& A, int64_t D, uint32_t S, uint32_t m, uint64_t* lo, uint64_t* hi)
+// T = text[lo, hi) of a locus (kmx.h), inside contig c of the index's table or, when c names none, inside the text; lo <= hi <= n
+__device__ __forceinline__ void text_window(const AlignIn& A, uint32_t c, int64_t D, uint32_t S, uint32_t m, uint64_t* lo, uint64_t* hi)
 {
     const int64_t n = int64_t(A.n), E = int64_t(A.max_edits);
-    const int64_t l = min(max(int64_t(0), D - E), n);          // (diagonals of a vote lie below n: the second bound never binds)
-    const int64_t h = max(l, min(n, D + int64_t(S) + int64_t(m) + E));
+    int64_t b0 = 0, b1 = n;
+    if (A.ctg_off && c < A.nc) {                               // (uniform across the wave: a batch has a table or has none)
+        b1 = min(int64_t(A.ctg_off[c + 1]), n);
+        b0 = min(int64_t(A.ctg_off[c]), b1);
+    }
+    const int64_t l = min(max(b0, D - E), b1);                 // (diagonals of a vote lie below n: without a table the second bound never binds)
+    const int64_t h = max(l, min(b1, D + int64_t(S) + int64_t(m) + E));
     *lo = uint64_t(l);
     *hi = uint64_t(h);
+}
+
+// c(l) of kmx.h: the contig that holds the middle of the locus's band, by binary search of the table (nc >= 1, n >= 1)
+__device__ __forceinline__ uint32_t contig_of(const AlignIn& A, int64_t D, uint32_t S, uint32_t m)
+{
+    const int64_t mid = min(max(D + int64_t((uint64_t(S) + m) / 2), int64_t(0)), int64_t(A.n) - 1);
+    uint64_t lo = 0, hi = A.nc;                                // the last contig that starts at or before mid
+    while (hi - lo > 1) {
+        const uint64_t c = (lo + hi) >> 1;
+        if (int64_t(A.ctg_off[c]) <= mid) lo = c; else hi = c;
+    }
+    return uint32_t(lo);
 }
 
 // ---- classes -------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_align_classify(AlignIn A, uint32_t* __restrict__ lread, uint8_t* __restrict__ cls,
                                                            uint8_t* __restrict__ dist, uint32_t* __restrict__ start, uint32_t* __restrict__ end,
-                                                           unsigned long long* __restrict__ ctr)
+                                                           uint32_t* __restrict__ ctg, unsigned long long* __restrict__ ctr)
 {
     __shared__ uint32_t s_cnt[kClasses];
     if (threadIdx.x < kClasses) s_cnt[threadIdx.x] = 0;
@@ -66,11 +84,12 @@ __global__ __launch_bounds__(kBlock) void k_align_classify(AlignIn A, uint32_t* 
         const uint32_t m = read_letters(A, lo, &r0, &too_long);
         const uint32_t S = A.span[l];
         uint8_t c = CLS_OUT, d = KMX_ALIGN_SKIPPED;
-        uint32_t at = 0;
+        uint32_t at = 0, cg = kNoContig;
         if (S <= A.max_span && !too_long) {
+            if (ctg) cg = contig_of(A, A.diag[l], S, m);       // (with a table: found once, the passes read it back)
             if (m == 0) {                                      // the empty read aligns with the empty substring at lo
                 uint64_t tlo, thi;
-                text_window(A, A.diag[l], S, 0, &tlo, &thi);
+                text_window(A, cg, A.diag[l], S, 0, &tlo, &thi);
                 d = 0;
                 at = uint32_t(tlo);
             } else {
@@ -84,6 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_align_classify(AlignIn A, uint32_t* 
         dist[l] = d;                                           // (the forward pass overwrites the loci it aligns)
         start[l] = at;
         end[l] = at;
+        if (ctg) ctg[l] = cg;
     }
     __syncthreads();
     if (threadIdx.x < kClasses && s_cnt[threadIdx.x]) atomicAdd(&ctr[CTR_CLASS + threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
@@ -131,7 +151,7 @@ __global__ __launch_bounds__(kAlignBlock) void k_align_fwd(AlignIn A, PassIn P, 
     const uint32_t nw = (m + 63) / 64;
     if (m == 0 || nw > uint32_t(NW)) return;                    // (cannot happen: k_align_classify read the same offsets)
     uint64_t lo, hi;
-    text_window(A, A.diag[l], A.span[l], m, &lo, &hi);
+    text_window(A, A.ctg ? A.ctg[l] : kNoContig, A.diag[l], A.span[l], m, &lo, &hi);
     const uint64_t* pq = P.peq + P.peq_off[r];
     const uint32_t lastw = (m - 1) >> 6, lastbit = (m - 1) & 63;
     const uint32_t w = A.w, per = 64 / w, sigma = A.sigma;
@@ -173,7 +193,7 @@ __global__ __launch_bounds__(kAlignBlock) void k_align_rev(AlignIn A, PassIn P, 
     const uint32_t nw = (m + 63) / 64;
     if (m == 0 || nw > uint32_t(NW)) return;
     uint64_t lo, hi;
-    text_window(A, A.diag[l], A.span[l], m, &lo, &hi);
+    text_window(A, A.ctg ? A.ctg[l] : kNoContig, A.diag[l], A.span[l], m, &lo, &hi);
     const uint64_t e = min(uint64_t(end[l]), hi);               // (end lies in [lo, hi]: the forward pass wrote it)
     const uint32_t d = dist[l];
     const uint64_t* pq = P.peq + P.peq_off[r];
@@ -242,24 +262,25 @@ struct kmx_alignments {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t nr = 0, n_loci = 0, n_aligned = 0, n_skipped = 0;
-    // results
-    Buf dist, start, end, best, aligned;
+    uint64_t nc = 0, ctg_gen = 0;          // the contig table of the index the call saw: its contigs (0: none) and its generation
+    // results; ctg is only filled when nc > 0
+    Buf dist, start, end, best, aligned, ctg;
     // scratch
     Buf ranks, roff, pcnt, peq_off, bsum, peq, lread, cls, list, alist, ctr;
-    Pinned h_ctr, h_dist, h_start, h_end, h_best, h_aligned;
-    bool host_valid = false;
+    Pinned h_ctr, h_dist, h_start, h_end, h_best, h_aligned, h_ctg;
+    bool host_valid = false, host_ctg_valid = false;
     void release()
     {
-        for (Buf* b : {&dist, &start, &end, &best, &aligned, &ranks, &roff, &pcnt, &peq_off, &bsum, &peq, &lread, &cls, &list, &alist, &ctr}) b->release();
-        for (Pinned* b : {&h_ctr, &h_dist, &h_start, &h_end, &h_best, &h_aligned}) b->release();
+        for (Buf* b : {&dist, &start, &end, &best, &aligned, &ctg, &ranks, &roff, &pcnt, &peq_off, &bsum, &peq, &lread, &cls, &list, &alist, &ctr}) b->release();
+        for (Pinned* b : {&h_ctr, &h_dist, &h_start, &h_end, &h_best, &h_aligned, &h_ctg}) b->release();
     }
-    void clear() { nr = n_loci = n_aligned = n_skipped = 0; host_valid = false; }
+    void clear() { nr = n_loci = n_aligned = n_skipped = nc = ctg_gen = 0; host_valid = host_ctg_valid = false; }
 };
 
 kmx::AlignAccess kmx::alignments_access(const kmx_alignments* a)
 {
     return AlignAccess{a->device, a->stream, a->nr, a->n_loci, a->dist.as<uint8_t>(), a->start.as<uint32_t>(), a->end.as<uint32_t>(),
-                       a->best.as<uint32_t>()};
+                       a->best.as<uint32_t>(), a->nc && a->n_loci ? a->ctg.as<uint32_t>() : nullptr, a->nc, a->ctg_gen};
 }
 
 namespace {
@@ -281,6 +302,8 @@ kmx_status align_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const 
     const uint64_t nr = L.nr, nl = L.n_loci;
     a->stream = s;
     a->clear();
+    a->nc = X.ctg_off ? X.nc : 0;
+    a->ctg_gen = X.ctg_gen;
     (void)hipGetLastError();
     TRY_HIP(a->best.ensure(std::max<uint64_t>(nr, 1) * 4));
     TRY_HIP(a->aligned.ensure(std::max<uint64_t>(nr, 1) * 4));
@@ -298,6 +321,8 @@ kmx_status align_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const 
     TRY_HIP(a->end.ensure(nl * 4));
     TRY_HIP(a->lread.ensure(nl * 4));
     TRY_HIP(a->cls.ensure(nl));
+    if (a->nc) TRY_HIP(a->ctg.ensure(nl * 4));
+    uint32_t* ctg = a->nc ? a->ctg.as<uint32_t>() : nullptr;
     TRY_HIP(a->pcnt.ensure(nr * 4 + 16));
     TRY_HIP(a->peq_off.ensure((nr + 1) * 8));
     TRY_HIP(a->bsum.ensure(kmx::scan_blocks(nr) * 8 + 16));
@@ -305,11 +330,11 @@ kmx_status align_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const 
     unsigned long long* ctr = a->ctr.as<unsigned long long>();
     TRY_HIP(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
     const AlignIn A{static_cast<const uint8_t*>(d_ranks), static_cast<const uint64_t*>(d_roff), ranks_len, L.locus_off, L.diag, L.span, nr, nl, X.n,
-                    X.text->d_words, X.text->w, X.sigma, o.max_edits, o.max_span};
+                    X.text->d_words, X.text->w, X.sigma, o.max_edits, o.max_span, a->nc ? X.ctg_off : nullptr, ctg, a->nc};
     hipLaunchKernelGGL(k_align_count, dim3(grid_for(nr, kBlock)), dim3(kBlock), 0, s, A, a->pcnt.as<uint32_t>());
     kmx::launch_scan(s, a->pcnt.as<uint32_t>(), nr, a->bsum.as<uint64_t>(), a->peq_off.as<uint64_t>(), ctr + CTR_PEQ_WORDS);
     hipLaunchKernelGGL(k_align_classify, dim3(grid_for(nl, kBlock)), dim3(kBlock), 0, s, A, a->lread.as<uint32_t>(), a->cls.as<uint8_t>(),
-                       a->dist.as<uint8_t>(), a->start.as<uint32_t>(), a->end.as<uint32_t>(), ctr);
+                       a->dist.as<uint8_t>(), a->start.as<uint32_t>(), a->end.as<uint32_t>(), ctg, ctr);
     TRY_HIP(hipGetLastError());
     TRY_KMX(kmx::read_back("kmx_loci_align", s, ctr, a->h_ctr, CTR_COUNT * 8));
     uint64_t c[CTR_COUNT];
@@ -461,6 +486,31 @@ kmx_status kmx_alignments_view(kmx_alignments* a, const uint8_t** dist, const ui
     if (end) *end = a->h_end.as<uint32_t>();
     if (best) *best = a->h_best.as<uint32_t>();
     if (aligned) *aligned = a->h_aligned.as<uint32_t>();
+    return KMX_OK;
+}
+
+kmx_status kmx_alignments_contigs_view_device(const kmx_alignments* a, const uint32_t** d_ctg, uint64_t* nc)
+{
+    if (!a) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_alignments_contigs_view_device: alignments handle is NULL");
+    if (d_ctg) *d_ctg = a->nc && a->n_loci ? a->ctg.as<uint32_t>() : nullptr;
+    if (nc) *nc = a->nc;
+    return KMX_OK;
+}
+
+kmx_status kmx_alignments_contigs_view(kmx_alignments* a, const uint32_t** ctg, uint64_t* nc)
+{
+    if (!a) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_alignments_contigs_view: alignments handle is NULL");
+    if (nc) *nc = a->nc;
+    if (!a->nc) {                                              // made without a table: no array
+        if (ctg) *ctg = nullptr;
+        return KMX_OK;
+    }
+    if (!a->host_ctg_valid) {                                  // 4 bytes per locus
+        const kmx::HostCopy items[] = {{a->h_ctg, a->ctg, a->n_loci, 4}};
+        TRY_KMX(kmx::host_view("kmx_alignments_contigs_view", a->device, a->stream, items, 1));
+        a->host_ctg_valid = true;
+    }
+    if (ctg) *ctg = a->h_ctg.as<uint32_t>();
     return KMX_OK;
 }
 

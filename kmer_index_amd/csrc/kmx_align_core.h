@@ -26,7 +26,12 @@ struct AlignIn {
     uint64_t nr, n_loci, n;
     const uint64_t* text;          // packed at w bits per letter
     uint32_t w, sigma, max_edits, max_span;
+    const uint64_t* ctg_off;       // [nc + 1]: the index's contig table; nullptr without one (kmx_loci_align only)
+    const uint32_t* ctg;           // [n_loci]: the contig of every locus, as k_align_classify stored it; nullptr without a table
+    uint64_t nc;
 };
+
+constexpr uint32_t kNoContig = 0xFFFFFFFFu;
 
 // letters of read r, 0 when the read is not served: empty, longer than KMX_ALIGN_MAX_READ or outside the letters that may be read
 // (*too_long tells the last two from the first)

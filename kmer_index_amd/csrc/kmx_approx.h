@@ -22,6 +22,15 @@ struct PackedText {
 };
 #define KMX_TEXT_PAD_WORDS 4   // a window read of two words past any offset stays inside the allocation
 
+// The contig table of one replica (kmx_index_set_contigs): contig c is text[off[c], off[c + 1]).  d_off is NULL and nc 0 while the
+// index has no table.  gen counts the successful kmx_index_set_contigs calls on the index (the same in every replica): the
+// alignments record it, and the calls behind them refuse a handle that was made under another table.
+struct ContigTable {
+    uint64_t* d_off = nullptr;     // [nc + 1], on the replica's device
+    uint64_t nc = 0;
+    uint64_t gen = 0;
+};
+
 struct IndexAccess {
     int device;
     uint64_t n;
@@ -30,6 +39,8 @@ struct IndexAccess {
     bool broken;
     const KmxIndexDev* h;      // host copy of the replica's header (device pointers)
     PackedText* text;
+    const uint64_t* ctg_off;   // the replica's contig table (device, [nc + 1]); nullptr without one
+    uint64_t nc, ctg_gen;
 };
 IndexAccess index_access(const kmx_index* ix);                  // kmx_capi.hip
 // kmx_capi.hip: the replica of ix that lives on `device`; false when there is none

@@ -215,6 +215,8 @@ struct kmx_index {
     std::unique_ptr<HostDir[]> host_dirs;
     std::vector<kmx_index*> peers;      // replicas 1..N-1 of a multi-device index (owned by replica 0, which is this object)
     std::unique_ptr<kmx::PackedText> text = std::make_unique<kmx::PackedText>();   // kmx_index_text / kmx_search_approx (kmx_approx.hip)
+    kmx::ContigTable contigs;           // kmx_index_set_contigs: this replica's copy of the table
+    std::vector<uint64_t> h_contigs;    // ... and the host's (replica 0 only), for kmx_index_contigs
     size_t n_replicas() const { return 1 + peers.size(); }
     kmx_index* replica(size_t i) { return i ? peers[i - 1] : this; }
 };
@@ -1243,8 +1245,71 @@ void kmx_index_free(kmx_index* ix)
     (void)hipDeviceSynchronize();          // nothing of a completed search is still reading the image
     ix->stats.destroy();
     kmx::packed_text_release(ix->text.get());
+    if (ix->contigs.d_off) (void)hipFree(ix->contigs.d_off);
     for (void* p : ix->allocs) (void)hipFree(p);
     delete ix;
+}
+
+// ---- the contig table (KMX_MAP_CONTIGS) ----
+kmx_status kmx_index_set_contigs(kmx_index* ix, const uint64_t* ctg_off, uint64_t nc)
+{
+    const std::string who = "kmx_index_set_contigs: ";
+    if (!ix) return fail(KMX_ERR_INVALID_ARGUMENT, who + "index is NULL");
+    if (nc && !ctg_off) return fail(KMX_ERR_INVALID_ARGUMENT, who + "ctg_off is NULL");
+    if (nc >= 0xFFFFFFFFull) return fail(KMX_ERR_INVALID_ARGUMENT, who + "2^32 - 1 or more contigs");
+    if (nc) {
+        if (ctg_off[0] != 0) return fail(KMX_ERR_INVALID_ARGUMENT, who + "ctg_off[0] must be 0");
+        for (uint64_t c = 0; c < nc; ++c)
+            if (ctg_off[c + 1] <= ctg_off[c]) return fail(KMX_ERR_INVALID_ARGUMENT, who + "ctg_off must be strictly ascending (contig " + std::to_string(c) + " is empty)");
+        if (ctg_off[nc] != ix->n) return fail(KMX_ERR_INVALID_ARGUMENT, who + "ctg_off[nc] must be the text length");
+    }
+    if (ix->broken) return fail(KMX_ERR_HIP, who + "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    int cur = 0;
+    const bool have_cur = hipGetDevice(&cur) == hipSuccess;
+    if (!have_cur) (void)hipGetLastError();
+    auto back = [&] { if (have_cur) (void)hipSetDevice(cur); };
+    // every replica's new copy first: a failure leaves the table that was there
+    std::vector<uint64_t*> fresh(ix->n_replicas(), nullptr);
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; nc && i < ix->n_replicas() && e == hipSuccess; ++i) {
+        e = hipSetDevice(ix->replica(i)->device);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh[i]), (nc + 1) * 8);
+        if (e == hipSuccess) e = hipMemcpy(fresh[i], ctg_off, (nc + 1) * 8, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (size_t i = 0; i < ix->n_replicas(); ++i)
+            if (fresh[i]) { (void)hipSetDevice(ix->replica(i)->device); (void)hipFree(fresh[i]); }
+        back();
+        return fail(e == hipErrorOutOfMemory ? KMX_ERR_OUT_OF_MEMORY : KMX_ERR_HIP, who + hipGetErrorString(e));
+    }
+    const uint64_t gen = ix->contigs.gen + 1;
+    for (size_t i = 0; i < ix->n_replicas(); ++i) {
+        kmx_index* r = ix->replica(i);
+        (void)hipSetDevice(r->device);
+        if (r->contigs.d_off) {                                // no kernel of an earlier chain call still reads the table that goes
+            (void)hipDeviceSynchronize();
+            (void)hipFree(r->contigs.d_off);
+        }
+        r->contigs.d_off = fresh[i];
+        r->contigs.nc = nc;
+        r->contigs.gen = gen;
+    }
+    ix->h_contigs.assign(ctg_off, ctg_off + (nc ? nc + 1 : 0));
+    back();
+    return KMX_OK;
+}
+
+kmx_status kmx_index_contigs(const kmx_index* ix, uint64_t* nc, uint64_t* ctg_off_out, uint64_t cap)
+{
+    if (!ix) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_index_contigs: index is NULL");
+    const uint64_t n = ix->contigs.nc;
+    if (nc) *nc = n;
+    if (ctg_off_out && n) {
+        if (cap < n + 1) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_index_contigs: room for fewer than nc + 1 offsets");
+        std::memcpy(ctg_off_out, ix->h_contigs.data(), (n + 1) * 8);
+    }
+    return KMX_OK;
 }
 
 kmx_status kmx_index_info(const kmx_index* ix, uint64_t* n, uint32_t* sigma, uint32_t* n_ks, uint32_t* ks,
@@ -2952,7 +3017,8 @@ extern "C" kmx_status kmx_index_load(const char* path, const kmx_options* opts, 
 // ---- what kmx_approx.hip needs from an index (kmx_approx.h) ----
 kmx::IndexAccess kmx::index_access(const kmx_index* ix)
 {
-    return kmx::IndexAccess{ix->device, ix->n, ix->sigma, ix->range, ix->broken, &ix->h_header, ix->text.get()};
+    return kmx::IndexAccess{ix->device, ix->n, ix->sigma, ix->range, ix->broken, &ix->h_header, ix->text.get(), ix->contigs.d_off, ix->contigs.nc,
+                            ix->contigs.gen};
 }
 
 bool kmx::index_access_on(const kmx_index* cix, int device, kmx::IndexAccess* out)

@@ -34,6 +34,7 @@ struct PairIn {
     const uint32_t* start;
     const uint32_t* end;
     const uint32_t* best;          // [4 np]
+    const uint32_t* ctg;           // [n_loci]: the contig of every locus; nullptr when the alignments were made without a contig table
     uint64_t np, n_loci;
     int64_t min_insert, max_insert;
     uint64_t penalty;
@@ -72,7 +73,8 @@ __device__ __forceinline__ int64_t concordant_tlen(const PairIn& P, uint32_t sx,
 struct Locus { uint32_t l, s, start, end, d; };
 
 // Every concordant (x, y) of the pair whose offsets are o[0 .. 4] goes to visit(x, y) in some lane: the aligned loci of the mate with
-// fewer loci one after the other, the lanes over the loci of the other mate.
+// fewer loci one after the other, the lanes over the loci of the other mate.  With a contig table two loci of different contigs are
+// never concordant (the test on the pointer is uniform across the grid).
 template <typename Visit>
 __device__ __forceinline__ void walk_concordant(const PairIn& P, const uint64_t* o, uint32_t lane, Visit visit)
 {
@@ -83,10 +85,12 @@ __device__ __forceinline__ void walk_concordant(const PairIn& P, const uint64_t*
         const uint32_t dlo = P.dist[lo];
         if (dlo >= KMX_ALIGN_SKIPPED) continue;
         const Locus out{uint32_t(lo), lo < ob ? 0u : 1u, P.start[lo], P.end[lo], dlo};
+        const uint32_t co = P.ctg ? P.ctg[lo] : 0u;
         for (uint64_t li = ia + lane; li < ic; li += kWave) {
             const uint32_t dli = P.dist[li];
             if (dli >= KMX_ALIGN_SKIPPED) continue;
             const Locus in{uint32_t(li), li < ib ? 0u : 1u, P.start[li], P.end[li], dli};
+            if (P.ctg && P.ctg[li] != co) continue;
             const Locus& x = outer1 ? out : in;
             const Locus& y = outer1 ? in : out;
             bool first;
@@ -221,7 +225,7 @@ kmx_status pair_fold_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, co
     TRY_HIP(pr->ctr.ensure(CTR_COUNT * 8));
     unsigned long long* ctr = pr->ctr.as<unsigned long long>();
     TRY_HIP(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
-    const PairIn P{L.locus_off, A.dist, A.start, A.end, A.best, np, L.n_loci, int64_t(o.min_insert), int64_t(o.max_insert), o.unpaired_penalty, o.orientation};
+    const PairIn P{L.locus_off, A.dist, A.start, A.end, A.best, A.ctg, np, L.n_loci, int64_t(o.min_insert), int64_t(o.max_insert), o.unpaired_penalty, o.orientation};
     const PairOut O{pl->locus.as<uint32_t>(), pl->strand.as<uint8_t>(), pl->dist.as<uint8_t>(), pl->start.as<uint32_t>(), pl->end.as<uint32_t>(),
                     pl->second.as<uint8_t>(), pl->best2.as<uint32_t>(), pr->cls.as<uint8_t>(), pr->tlen.as<int32_t>(), pr->score.as<uint16_t>(),
                     pr->second_score.as<uint16_t>(), ctr};

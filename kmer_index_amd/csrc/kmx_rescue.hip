@@ -63,6 +63,9 @@ struct RescueIn {
     int64_t min_insert, max_insert;
     uint64_t penalty;
     uint32_t orientation, max_edits, flags;
+    const uint64_t* ctg_off;       // [nc + 1]: the index's contig table; nullptr without one
+    const uint32_t* ctg;           // [n_loci]: the contig of every locus (the alignments'); nullptr without a table
+    uint64_t nc, n_loci;
 };
 
 // the job arrays; job_off[nr2 + 1] delimits them per internal read
@@ -80,7 +83,8 @@ struct Jobs {
     uint64_t cap, n_jobs;          // room (2 np); the jobs there are (known after the plan)
 };
 
-// Internal read r is the looked-for strand of a mate with a job: its window [lo, hi) (kmx.h).
+// Internal read r is the looked-for strand of a mate with a job: its window [lo, hi) (kmx.h), clamped to the contig of the anchor's
+// locus when the index has a table.
 __device__ __forceinline__ bool job_window(const RescueIn& R, uint64_t r, uint32_t* lo, uint32_t* hi)
 {
     const uint64_t p = r >> 2;
@@ -93,13 +97,22 @@ __device__ __forceinline__ bool job_window(const RescueIn& R, uint64_t r, uint32
     if (s != (R.orientation == KMX_PAIR_FF ? sa : 1u - sa)) return false;
     const bool up = R.orientation == KMX_PAIR_FR ? sa == 0 : R.orientation == KMX_PAIR_RF ? sa == 1 : (a == 0) == (sa == 0);
     const int64_t n = int64_t(R.n);
+    int64_t b0 = 0, b1 = n;                                    // the bounds: the text, or the anchor's contig
+    if (R.ctg) {                                               // (uniform across the grid)
+        const uint32_t al = R.pl_locus[2 * p + a];             // (an anchor is always placed by a locus)
+        const uint32_t cg = al < R.n_loci ? R.ctg[al] : 0xFFFFFFFFu;
+        if (cg < R.nc) {
+            b1 = min(int64_t(R.ctg_off[cg + 1]), n);
+            b0 = min(int64_t(R.ctg_off[cg]), b1);
+        }
+    }
     int64_t l, h;
     if (up) {
-        l = min(int64_t(R.pl_start[2 * p + a]), n);
-        h = min(n, l + R.max_insert);
+        l = min(max(int64_t(R.pl_start[2 * p + a]), b0), b1);
+        h = min(b1, l + R.max_insert);
     } else {
-        h = min(int64_t(R.pl_end[2 * p + a]), n);
-        l = max(int64_t(0), h - R.max_insert);
+        h = max(min(int64_t(R.pl_end[2 * p + a]), b1), b0);
+        l = max(b0, h - R.max_insert);
     }
     *lo = uint32_t(l);
     *hi = uint32_t(h);
@@ -434,7 +447,7 @@ kmx_status rescue_run(const kmx::IndexAccess& X, const kmx_strand_reads* reads, 
     const RescueIn R{pl->locus.as<uint32_t>(), pl->strand.as<uint8_t>(), pl->dist.as<uint8_t>(), pl->start.as<uint32_t>(), pl->end.as<uint32_t>(),
                      pl->second.as<uint8_t>(), pl->best2.as<uint32_t>(), pr->cls.as<uint8_t>(), pr->tlen.as<int32_t>(), pr->score.as<uint16_t>(),
                      pr->second_score.as<uint16_t>(), np, X.n, int64_t(o.min_insert), int64_t(o.max_insert), o.unpaired_penalty, o.orientation,
-                     o.max_edits, o.flags};
+                     o.max_edits, o.flags, A.ctg ? X.ctg_off : nullptr, A.ctg, A.nc, A.n_loci};
     Jobs J{h->job_off.as<uint64_t>(), h->read.as<uint32_t>(), h->lo.as<uint32_t>(), h->hi.as<uint32_t>(), h->dist.as<uint8_t>(), h->start.as<uint32_t>(),
            h->end.as<uint32_t>(), h->status.as<uint8_t>(), h->cls.as<uint8_t>(), h->key.as<unsigned long long>(), cap, 0};
     // the job reads take the place of the reads with loci: job_off that of locus_off (diag and span are not looked at)
@@ -544,6 +557,8 @@ kmx_status kmx_pairs_rescue(const kmx_index* index, const kmx_strand_reads* read
     kmx::IndexAccess X{};
     if (!kmx::index_access_on(index, L.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the loci live on a device that holds no replica of this index");
     if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    if (A.nc != (X.ctg_off ? X.nc : 0) || A.ctg_gen != X.ctg_gen)
+        return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments were made under another contig table of the index (kmx_index_set_contigs was called since): align again");
     kmx::DeviceGuard dg;
     const kmx_status bound = kmx::bind_handle(inout, L.device);
     h = *inout;

@@ -51,6 +51,8 @@ struct AlignAccess {
     const uint32_t* start;
     const uint32_t* end;
     const uint32_t* best;          // [nr]
+    const uint32_t* ctg;           // [n_loci]: the contig of every locus; nullptr when the handle was made without a contig table
+    uint64_t nc, ctg_gen;          // the contigs and the generation of the table the call saw (kmx_approx.h: ContigTable)
 };
 AlignAccess alignments_access(const kmx_alignments* a);   // kmx_align.hip
 

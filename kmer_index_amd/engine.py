@@ -30,6 +30,7 @@ PAIR_UNPLACED, PAIR_CONCORDANT, PAIR_DISCORDANT, PAIR_MATE1_ONLY, PAIR_MATE2_ONL
 PAIR_NO_PENALTY, PAIR_NO_SCORE = 0xFFFFFFFF, 0xFFFF
 RESCUE_DISCORDANT, RESCUE_MAX_INSERT = 1, 65536
 RESCUE_NONE, RESCUE_FOUND, RESCUE_CONCORDANT, RESCUE_TAKEN = 0, 1, 2, 3
+LOCATE_MATES, NO_CONTIG = 1, 0xFFFFFFFF
 
 # every symbol include/kmx.h declares
 EXPORTS = [
@@ -56,6 +57,8 @@ EXPORTS = [
     "kmx_pairs_rescue", "kmx_rescues_counts", "kmx_rescues_view", "kmx_rescues_view_device", "kmx_rescues_scripts", "kmx_rescues_free",
     "kmx_scripts_md", "kmx_rescues_md", "kmx_md_counts", "kmx_md_view", "kmx_md_view_device", "kmx_md_free",
     "kmx_placements_mapq", "kmx_mapq_counts", "kmx_mapq_view", "kmx_mapq_view_device", "kmx_mapq_free",
+    "kmx_index_set_contigs", "kmx_index_contigs", "kmx_alignments_contigs_view", "kmx_alignments_contigs_view_device",
+    "kmx_placements_locate", "kmx_located_counts", "kmx_located_view", "kmx_located_view_device", "kmx_located_free",
 ]
 
 
@@ -114,6 +117,10 @@ class MdOptions(C.Structure):
 class MapqOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_edits", C.c_uint32), ("cap", C.c_uint32), ("per_edit", C.c_uint32),
                 ("pair_bonus", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LocateOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class KernelStat(C.Structure):
@@ -317,6 +324,23 @@ def lib():
         L.kmx_mapq_view_device.restype = C.c_int
         L.kmx_mapq_view_device.argtypes = [vp, P(vp)]
         L.kmx_mapq_free.argtypes = [vp]
+        L.kmx_index_set_contigs.restype = C.c_int
+        L.kmx_index_set_contigs.argtypes = [vp, vp, u64]
+        L.kmx_index_contigs.restype = C.c_int
+        L.kmx_index_contigs.argtypes = [vp, P(u64), vp, u64]
+        L.kmx_alignments_contigs_view.restype = C.c_int
+        L.kmx_alignments_contigs_view.argtypes = [vp, P(vp), P(u64)]
+        L.kmx_alignments_contigs_view_device.restype = C.c_int
+        L.kmx_alignments_contigs_view_device.argtypes = [vp, P(vp), P(u64)]
+        L.kmx_placements_locate.restype = C.c_int
+        L.kmx_placements_locate.argtypes = [vp, vp, vp, P(LocateOptions), vp, P(vp)]
+        L.kmx_located_counts.restype = C.c_int
+        L.kmx_located_counts.argtypes = [vp] + [P(u64)] * 3
+        L.kmx_located_view.restype = C.c_int
+        L.kmx_located_view.argtypes = [vp, P(vp), P(vp)]
+        L.kmx_located_view_device.restype = C.c_int
+        L.kmx_located_view_device.argtypes = [vp, P(vp), P(vp)]
+        L.kmx_located_free.argtypes = [vp]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -610,6 +634,21 @@ class Alignments(_Handle):
         """(d_dist, d_start, d_end, d_best, d_aligned): kmx_alignments_view_device."""
         return self._device_ptrs("kmx_alignments_view_device", 5)
 
+    def contigs_host(self):
+        """kmx_alignments_contigs_view: ctg[n_loci] u32 as a numpy copy, the contig of every locus (NO_CONTIG for a skipped one), or
+        None when the alignments were made on an index without a contig table."""
+        p, nc = C.c_void_p(), C.c_uint64()
+        _check(lib().kmx_alignments_contigs_view(self._h, C.byref(p), C.byref(nc)))
+        if nc.value == 0:
+            return None
+        return _view(p.value, self.counts()["n_loci"], np.uint32).copy()
+
+    def contigs_device_ptr(self):
+        """(d_ctg, nc): kmx_alignments_contigs_view_device; d_ctg is None without a table (nc == 0) or without a locus."""
+        p, nc = C.c_void_p(), C.c_uint64()
+        _check(lib().kmx_alignments_contigs_view_device(self._h, C.byref(p), C.byref(nc)))
+        return p.value, int(nc.value)
+
     @staticmethod
     def _script_options(all, m, scratch_bytes):
         return ScriptOptions(C.sizeof(ScriptOptions), (SCRIPT_ALL if all else 0) | (SCRIPT_M if m else 0), int(scratch_bytes))
@@ -849,9 +888,47 @@ class Placements(_Handle):
         q._reads = self._reads
         return q
 
+    def locate(self, index, alignments, mates=False, stream=0, located=None):
+        """kmx_placements_locate: the contig and the position inside it of every placement, from the contig table of `index` and
+        the contigs that `alignments` recorded per locus.  mates=True (LOCATE_MATES): the reads are interleaved mates, a rescued read
+        takes its mate's contig.  stream=0: the stream that filled this handle.  Returns a Located (`located` reuses one)."""
+        out = located or Located()
+        o = LocateOptions(C.sizeof(LocateOptions), LOCATE_MATES if mates else 0)
+        _check(lib().kmx_placements_locate(index._h, alignments._h, self._h, C.byref(o), stream or None, C.byref(out._h)))
+        out._reads = self._reads
+        return out
+
     def close(self):
         super().close()
         self._reads = None
+
+
+class Located(_Handle):
+    """Owns a kmx_located handle (kmx_placements_locate): the contig and the contig-local position of every public read."""
+
+    _free = "kmx_located_free"
+
+    def __init__(self):
+        super().__init__()
+        self._reads = None          # the StrandReads whose stream the call ran on: it must outlive the views
+
+    def close(self):
+        super().close()
+        self._reads = None
+
+    def counts(self):
+        return self._counts("kmx_located_counts", "nr", "n_located", "n_mismatched")
+
+    def host(self):
+        """(ctg[nr] u32, pos[nr] u32) as numpy copies: NO_CONTIG and 0 for an unplaced read."""
+        nr = self.counts()["nr"]
+        p = [C.c_void_p() for _ in range(2)]
+        _check(lib().kmx_located_view(self._h, *[C.byref(x) for x in p]))
+        return tuple(_view(x.value, nr, np.uint32).copy() for x in p)
+
+    def device_ptrs(self):
+        """(d_ctg, d_pos): kmx_located_view_device."""
+        return self._device_ptrs("kmx_located_view_device", 2)
 
 
 class Pairs(_Handle):
@@ -992,13 +1069,38 @@ def _first_given(strings):
     return list(strings)
 
 
-def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements_host, cigars, mds, mapq, pairs_host=None):
+def concat_sequences(seqs):
+    """The text of a multi-sequence reference: (ranks uint8, ctg_off uint64[len(seqs) + 1]) with sequence c at
+    ranks[ctg_off[c]:ctg_off[c + 1]], ready for Index(...) and Index.set_contigs.  An empty sequence is refused (a contig table
+    has none).  Pure numpy: no device is needed."""
+    seqs = [np.ascontiguousarray(q, np.uint8).ravel() for q in seqs]
+    if any(q.size == 0 for q in seqs):
+        raise ValueError("concat_sequences: an empty sequence")
+    ctg_off = np.zeros(len(seqs) + 1, np.uint64)
+    if seqs:
+        ctg_off[1:] = np.cumsum([q.size for q in seqs], dtype=np.uint64)
+    return (np.concatenate(seqs) if seqs else np.zeros(0, np.uint8)), ctg_off
+
+
+def sam_header(names, ctg_off):
+    """The header lines (no newlines) of a SAM file over a contig table: "@HD\tVN:1.6\tSO:unsorted" and one
+    "@SQ\tSN:<name>\tLN:<length>" per contig."""
+    ctg_off = np.asarray(ctg_off, np.uint64)
+    if ctg_off.size != len(names) + 1:
+        raise ValueError("sam_header: ctg_off needs one entry more than there are names")
+    return ["@HD\tVN:1.6\tSO:unsorted"] + [f"@SQ\tSN:{nm}\tLN:{int(b) - int(a)}" for nm, a, b in zip(names, ctg_off[:-1], ctg_off[1:])]
+
+
+def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements_host, cigars, mds, mapq, pairs_host=None, located_host=None):
     """One SAM line (no newline) per public read from host arrays: the reads (ranks, roff), the rank -> letter table, the rank
     complement table, Placements.host(), the CIGAR and MD strings per read (Placements.cigars / .mds; a tuple of two lists, the
     placements' and the rescue's, gives a rescued read those of the rescue), Mapq.host() and, for paired reads, Pairs.host().
     FLAG / POS / PNEXT / TLEN come from sam_pair_fields when pairs_host is given; otherwise FLAG is 0 / 4 / 16, POS is start + 1 and
     there is no mate.  CIGAR is * when the read is unplaced, RNEXT = or *, SEQ the reverse complement for a reverse placement,
-    QUAL *; placed reads carry NM:i: (the distance) and MD:Z:.  Pure Python / numpy: no device is needed."""
+    QUAL *; placed reads carry NM:i: (the distance) and MD:Z:.  located_host (Located.host(): ctg, pos) switches to contig
+    coordinates: rname then is a sequence of one name per contig, RNAME the read's contig (an unplaced read with a placed mate takes
+    the mate's), POS and PNEXT are contig-local, RNEXT is = for the same contig and the mate's contig name otherwise.  Pure Python /
+    numpy: no device is needed."""
     table = _letters_table(letters)
     comp = np.ascontiguousarray(complement, np.uint8)
     if table.size < sigma or comp.size < sigma:
@@ -1018,6 +1120,27 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
         flag = np.where(placed, np.where(strand == 1, 0x10, 0), 0x4)
         pos = np.where(placed, start.astype(np.int64) + 1, 0)
         pnext, tlen = np.zeros(nr, np.int64), np.zeros(nr, np.int32)
+    names = nextname = None
+    if located_host is not None:
+        ctg, lpos = (np.asarray(a, np.uint32) for a in located_host)
+        if ctg.size != nr or lpos.size != nr:
+            raise ValueError("sam_lines: the located arrays disagree in the number of reads")
+        if (placed & (ctg == NO_CONTIG)).any():
+            raise ValueError("sam_lines: a placed read has no contig (n_mismatched of the Located is not 0)")
+        if (ctg[placed] >= len(rname)).any():
+            raise ValueError("sam_lines: a contig without a name")
+        own = np.where(placed, lpos.astype(np.int64) + 1, 0)
+        if pairs_host is not None:
+            mate = np.arange(nr) ^ 1
+            rc = np.where(placed, ctg, ctg[mate])              # an unplaced read takes its mate's contig and POS
+            pos = np.where(placed, own, own[mate])
+            pnext = pos[mate]
+            names = [rname[int(c)] if c != NO_CONTIG else "*" for c in rc]
+            nextname = ["*" if rc[j] == NO_CONTIG else "=" if rc[j] == rc[i] else names[j] for i, j in enumerate(mate)]
+        else:
+            pos = own
+            names = [rname[int(c)] if c != NO_CONTIG else "*" for c in ctg]
+            nextname = ["*"] * nr
     lines = []
     for i in range(nr):
         q = ranks[int(roff[i]):int(roff[i + 1])]
@@ -1026,8 +1149,9 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
         if placed[i] and strand[i] == 1:
             q = comp[q[::-1]]
         seq = table[q].tobytes().decode("latin-1") or "*"
-        fields = [str(qnames[i]), str(int(flag[i])), rname if pos[i] else "*", str(int(pos[i])), str(int(mapq[i])),
-                  (cigars[i] or "*") if placed[i] else "*", "=" if pnext[i] else "*", str(int(pnext[i])), str(int(tlen[i])), seq, "*"]
+        fields = [str(qnames[i]), str(int(flag[i])), (rname if pos[i] else "*") if names is None else names[i], str(int(pos[i])), str(int(mapq[i])),
+                  (cigars[i] or "*") if placed[i] else "*", ("=" if pnext[i] else "*") if names is None else nextname[i], str(int(pnext[i])),
+                  str(int(tlen[i])), seq, "*"]
         if placed[i]:
             fields += [f"NM:i:{int(dist[i])}", f"MD:Z:{mds[i]}"]
         lines.append("\t".join(fields))
@@ -1120,6 +1244,24 @@ class Index:
 
     def save(self, path):
         _check(lib().kmx_index_save(self._h, os.fsencode(path)))
+
+    def set_contigs(self, ctg_off):
+        """kmx_index_set_contigs: contig c is text[ctg_off[c]:ctg_off[c + 1]); every chain call behind this one (map_reads,
+        map_reads_strands, map_pairs and their stages) keeps alignments, pairs and rescues inside one contig.  None or an empty
+        array removes the table.  The table is not part of a saved image: set it again after load()."""
+        ctg_off = np.zeros(0, np.uint64) if ctg_off is None else np.ascontiguousarray(ctg_off, np.uint64)
+        nc = max(int(ctg_off.size) - 1, 0)
+        _check(lib().kmx_index_set_contigs(self._h, ctg_off.ctypes.data if nc else None, nc))
+
+    def contigs(self):
+        """kmx_index_contigs: ctg_off[nc + 1] u64 of the table, or None when the index has none."""
+        nc = C.c_uint64()
+        _check(lib().kmx_index_contigs(self._h, C.byref(nc), None, 0))
+        if nc.value == 0:
+            return None
+        out = np.zeros(nc.value + 1, np.uint64)
+        _check(lib().kmx_index_contigs(self._h, C.byref(nc), out.ctypes.data, out.size))
+        return out
 
     def info(self):
         n, sigma, nks, dbytes = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint64()

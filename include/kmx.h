@@ -1178,6 +1178,92 @@ kmx_status kmx_located_view(kmx_located* l, const uint32_t** ctg /* nr */, const
 kmx_status kmx_located_view_device(const kmx_located* l, const uint32_t** d_ctg, const uint32_t** d_pos);
 void kmx_located_free(kmx_located* l);
 
+/* ---- Secondary placements: up to N further places per read (an extension, no reference interface; a caller detects the
+ *      capability by the macro KMX_MAP_SECONDARIES, KMX_VERSION is unchanged).  The folds report one placement per read and one
+ *      byte, second, about every other place it fits.  A read from a repeat family, an amplicon panel or a transcriptome fits
+ *      in many places, and a caller who writes XA:Z: or quantifies needs them.  Two loci of a read often describe the SAME
+ *      place (nothing upstream deduplicates them; a truncated window yields a worse shadow), so the N best loci are not the N
+ *      best places: this call applies the fold's ELSEWHERE rule transitively, on the device, and sends 13 bytes per reported
+ *      place to the host in the place of 9 per locus.
+ *
+ *      Input.  `loci` and `alignments` are those of a doubled batch (nr2 internal reads, nr = nr2 / 2 public ones);
+ *      `placements` is the handle of kmx_alignments_fold_strands or of kmx_alignments_fold_pairs, before or after
+ *      kmx_pairs_rescue: its locus / strand / dist / start / end are read.  The reads and the index are not needed.  `stream`
+ *      NULL means the stream that filled the placements; a rescue rewrites them on the stream of the chain, so the order
+ *      holds.  A caller who passes another stream orders it behind the stream that filled the placements, and orders the
+ *      stream of every later call that reads the secondaries (kmx_secondaries_scripts runs on the stream of `reads`,
+ *      kmx_secondaries_md on the scripts' or the one it is given) behind it: the last kernel of this call is left in flight
+ *      on `stream`, as with the other stream-taking calls of the chain.  N = max_secondary.
+ *
+ *      Candidates, in int64.  For public read i: a = locus_off[2i], b = locus_off[2i + 1], c = locus_off[2i + 2], each clamped
+ *      into [0, n_loci] and made ascending as the strand fold does; locus l has strand 0 if l < b, else 1.  The primary is
+ *      P = (strand[i], start[i], end[i]) of the placements, its distance dist[i].  An unplaced read (strand[i] == 255) has no
+ *      entries and more[i] = 0.  A locus l in [a, c) is a CANDIDATE when dist[l] < KMX_ALIGN_SKIPPED, l != locus[i], and
+ *      dist[l] <= dist[i] + max_delta (max_delta == 0xFFFFFFFF: always).  Two places (s, x0, x1) and (t, y0, y1) lie ELSEWHERE
+ *      from each other when s != t or max(x0, y0) >= min(x1, y1): the rule of kmx_alignments_fold_strands, on intervals.
+ *
+ *      The greedy selection.  T = {P}.  Repeat: among the candidates not yet taken that lie elsewhere from EVERY member of T,
+ *      find the one with the least (dist, l) (a forward locus has the lower index, so this is the fold's (dist, strand, l));
+ *      if there is none, stop with more[i] = 0; if N have been taken already, stop with more[i] = 1; otherwise take it and
+ *      add (its strand, start[l], end[l]) to T.  A locus that overlaps a taken place stays excluded for good, so a chain of
+ *      mutually overlapping loci gives one place.  A rescued read (placed, locus[i] == 0xFFFFFFFF) works the same way: its
+ *      primary is the interval in the placements, and no candidate is excluded by index.  With max_delta unbounded and the
+ *      placements of the strand fold, the least dist among the entries of a read equals second[i] (255: no entry).
+ *
+ *      Output.  The taken loci of read i in ASCENDING LOCUS INDEX, forward strand first.  sec_off[nr2 + 1] (u64) counts them
+ *      per INTERNAL read: the entries of public read i are [sec_off[2i], sec_off[2i + 2)), those on strand s
+ *      [sec_off[2i + s], sec_off[2i + s + 1)), which is the shape the script stage needs.  Per entry e: locus[e] (u32, an
+ *      index into the loci arrays), dist[e] (u8), start[e], end[e] (u32) and, when the alignments carry a contig table,
+ *      ctg[e] (u32) = the alignments' ctg[locus[e]] (the view is NULL otherwise).  Per public read: more[nr] (u8).  Counters:
+ *      n_sec = sec_off[nr2], n_multi = the reads with at least one entry, n_truncated = the reads with more == 1.  Every
+ *      index is bounded by n_loci, nr and the read's own range: foreign handles give meaningless but harmless results.
+ *      tests/secondary_naive.py is this contract in executable form.
+ *
+ *      The secondaries handle.  *inout == NULL allocates; a handle passed in is reused and its earlier views end.  The device
+ *      arrays (kmx_secondaries_view_device; sec_off is NULL after a refusal or an error, the entry arrays when n_sec == 0,
+ *      more when nr == 0) are complete in stream order when the call returns; kmx_secondaries_view copies to page-locked host
+ *      memory on first use and synchronises, on the stream of the call: 13 bytes per entry (17 with ctg), 8 per internal
+ *      read, 1 per public read (sec_off always holds at least the one offset 0).  Any output pointer may be NULL.  The call
+ *      only reads the other handles.
+ *
+ *      KMX_ERR_INVALID_ARGUMENT before any handle is looked at: a NULL argument, a struct_size that is too small, flags != 0,
+ *      max_secondary == 0 or > KMX_SECONDARY_MAX.  After looking (the secondaries handle, when there is one, then holds an
+ *      empty result): nr2 odd, placements whose 2 nr differs from the alignments' nr, loci and alignments that disagree in nr
+ *      or n_loci, handles on different devices; KMX_ERR_TOO_LARGE when nr * N >= 2^32.
+ *
+ *      CIGAR and MD of the entries.  kmx_secondaries_scripts is kmx_alignments_scripts_device over the doubled reads of
+ *      `reads` with the entry arrays in the place of the loci and their alignments and EVERY entry selected: an ordinary
+ *      kmx_scripts over the internal reads with sel[e] == e; for a reverse entry the script is that of the reverse complement
+ *      against text[start, end), the SAM convention.  It runs on the stream of `reads`.  KMX_SCRIPT_ALL in the options is
+ *      refused (there is nothing to add); KMX_SCRIPT_M and scratch_bytes work as before.  Refused after looking: secondaries
+ *      whose 2 nr differs from the reads' nr2, or that live on another device, and what kmx_rescues_scripts refuses about the
+ *      index.  kmx_secondaries_md is kmx_rescues_md over these scripts: sel[e] indexes start / end of the entries, bounded by
+ *      n_sec.  With it a caller can build secondary SAM lines; no call here writes them.  Untested: handles on different
+ *      devices.  kmx_stats_get is not extended (see kmx_loci_align). */
+#define KMX_MAP_SECONDARIES 1
+#define KMX_SECONDARY_MAX 32
+typedef struct kmx_secondary_options {
+    uint32_t struct_size;    /* = sizeof(kmx_secondary_options): 16 */
+    uint32_t max_secondary;  /* N, in 1 .. KMX_SECONDARY_MAX */
+    uint32_t max_delta;      /* a candidate has dist <= the primary's + max_delta; 0xFFFFFFFF: no bound */
+    uint32_t flags;          /* 0 */
+} kmx_secondary_options;
+typedef struct kmx_secondaries kmx_secondaries;
+kmx_status kmx_placements_secondaries(const kmx_loci* loci, const kmx_alignments* alignments, const kmx_placements* placements,
+                                      const kmx_secondary_options* options, void* stream, kmx_secondaries** inout);
+kmx_status kmx_secondaries_counts(const kmx_secondaries* s, uint64_t* nr, uint64_t* n_sec, uint64_t* n_multi, uint64_t* n_truncated);
+kmx_status kmx_secondaries_view(kmx_secondaries* s, const uint64_t** sec_off /* 2 nr + 1 */, const uint32_t** locus /* n_sec */,
+                                const uint8_t** dist, const uint32_t** start, const uint32_t** end, const uint32_t** ctg /* or NULL */,
+                                const uint8_t** more /* nr */);
+kmx_status kmx_secondaries_view_device(const kmx_secondaries* s, const uint64_t** d_sec_off, const uint32_t** d_locus,
+                                       const uint8_t** d_dist, const uint32_t** d_start, const uint32_t** d_end, const uint32_t** d_ctg,
+                                       const uint8_t** d_more);
+kmx_status kmx_secondaries_scripts(const kmx_index* index, const kmx_strand_reads* reads, const kmx_secondaries* secondaries,
+                                   const kmx_script_options* options, kmx_scripts** inout);
+kmx_status kmx_secondaries_md(const kmx_index* index, const kmx_scripts* scripts, const kmx_secondaries* secondaries,
+                              const uint8_t* letters, const kmx_md_options* options, void* stream, kmx_md** inout);
+void kmx_secondaries_free(kmx_secondaries* s);
+
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.
  * Works on built, loaded and replicated indexes (this replica).  The first call derives a copy packed at 2, 4 or 8 bits per

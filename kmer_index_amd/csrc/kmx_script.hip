@@ -544,7 +544,7 @@ kmx_status kmx::scripts_with_best(const char* fn, const kmx_index* index, const 
 
 kmx_status kmx::scripts_on_arrays(const char* fn, const kmx_index* index, const kmx::LociAccess& L, const kmx::AlignAccess& A, const void* d_ranks,
                                   const void* d_roff, uint64_t ranks_len, const uint32_t* best, const kmx_script_options* o, hipStream_t stream,
-                                  kmx_scripts** inout)
+                                  kmx_scripts** inout, bool every)
 {
     const std::string who = std::string(fn) + ": ";
     if (!index) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "index is NULL");
@@ -552,7 +552,12 @@ kmx_status kmx::scripts_on_arrays(const char* fn, const kmx_index* index, const 
     if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
     if (o->struct_size < sizeof(kmx_script_options)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
     if (o->flags & ~(KMX_SCRIPT_ALL | KMX_SCRIPT_M)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "unknown flags");
-    if (o->flags & KMX_SCRIPT_ALL) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "KMX_SCRIPT_ALL ignores best: not for the taken jobs of a rescue");
+    if (o->flags & KMX_SCRIPT_ALL)
+        return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + (every ? "KMX_SCRIPT_ALL is not the caller's to set: every entry has a script already"
+                                                                     : "KMX_SCRIPT_ALL ignores best: not for the taken jobs of a rescue"));
+    kmx_script_options run = *o;                               // (struct_size may be larger: only the known fields are read)
+    run.struct_size = sizeof run;
+    if (every) run.flags |= KMX_SCRIPT_ALL;
     kmx_scripts* h = *inout;
     auto refuse = [&](kmx_status st, const std::string& msg) {
         if (h) h->clear();
@@ -564,7 +569,7 @@ kmx_status kmx::scripts_on_arrays(const char* fn, const kmx_index* index, const 
     kmx::DeviceGuard dg;
     TRY_KMX(kmx::bind_handle(inout, L.device));
     h = *inout;
-    const kmx_status st = script_run(X, L, A, d_ranks, d_roff, ranks_len, best, *o, stream, h);
+    const kmx_status st = script_run(X, L, A, d_ranks, d_roff, ranks_len, best, run, stream, h);
     if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
         (void)hipStreamSynchronize(stream);
         h->clear();

@@ -1,6 +1,7 @@
 // The placements handle, which two folds fill: kmx_alignments_fold_strands (kmx_strands.hip, which owns the accessors and the scripts
 // of the winners) and kmx_alignments_fold_pairs (kmx_pairs.hip); the doubled reads (kmx_strands.hip) and the pairs (kmx_pairs.hip),
-// which the mate rescue (kmx_rescue.hip) reads and, with the placements, rewrites.  Private to the library.
+// which the mate rescue (kmx_rescue.hip) reads and, with the placements, rewrites; the secondary placements (kmx_secondary.hip) read
+// the placements through kmx::PlacementsAccess (kmx_vote.h).  Private to the library.
 #pragma once
 #include "kmx_handle.h"
 

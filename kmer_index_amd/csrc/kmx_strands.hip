@@ -146,7 +146,8 @@ __global__ __launch_bounds__(kBlock) void k_strand_fold(FoldIn F, FoldOut O)
 
 kmx::PlacementsAccess kmx::placements_access(const kmx_placements* p)
 {
-    return PlacementsAccess{p->device, p->stream, 2 * p->nr, p->best2.as<uint32_t>()};
+    return PlacementsAccess{p->device, p->stream, 2 * p->nr, p->best2.as<uint32_t>(), p->nr, p->locus.as<uint32_t>(), p->strand.as<uint8_t>(),
+                            p->dist.as<uint8_t>(), p->start.as<uint32_t>(), p->end.as<uint32_t>()};
 }
 
 namespace {

@@ -1,4 +1,4 @@
-// SAM tags of the read-mapping chain (kmx_scripts_md, kmx_rescues_md, kmx_placements_mapq; include/kmx.h, KMX_SAM_TAGS): the MD string
+// SAM tags of the read-mapping chain (kmx_scripts_md, kmx_rescues_md, kmx_secondaries_md, kmx_placements_mapq; include/kmx.h, KMX_SAM_TAGS): the MD string
 // of every entry of a scripts handle, from its runs and the packed text, and a MAPQ per public read from the placements and the pairs.
 //
 //   k_md_count         a thread per entry: validates the entry (sel inside its bound, s <= t <= n, only = X I D, the = X D lengths sum
@@ -375,6 +375,15 @@ kmx_status kmx_rescues_md(const kmx_index* index, const kmx_scripts* scripts, co
     TRY_KMX(md_front("kmx_rescues_md: ", index, scripts, rescues, "rescues", letters, options, inout));
     const kmx::JobsAccess J = kmx::rescues_access(rescues);
     return md_on_arrays("kmx_rescues_md", index, kmx::scripts_access(scripts), J.device, J.start, J.end, J.n_jobs, letters,
+                        static_cast<hipStream_t>(stream), inout);
+}
+
+kmx_status kmx_secondaries_md(const kmx_index* index, const kmx_scripts* scripts, const kmx_secondaries* secondaries, const uint8_t* letters,
+                              const kmx_md_options* options, void* stream, kmx_md** inout)
+{
+    TRY_KMX(md_front("kmx_secondaries_md: ", index, scripts, secondaries, "secondaries", letters, options, inout));
+    const kmx::JobsAccess J = kmx::secondaries_access(secondaries);
+    return md_on_arrays("kmx_secondaries_md", index, kmx::scripts_access(scripts), J.device, J.start, J.end, J.n_jobs, letters,
                         static_cast<hipStream_t>(stream), inout);
 }
 

@@ -58,12 +58,18 @@ AlignAccess alignments_access(const kmx_alignments* a);   // kmx_align.hip
 
 // What the scripts of the winners (kmx_placements_scripts) need from a placements handle (kmx_strands.hip owns struct
 // kmx_placements): best2 belongs to the handle and stays as it is (the scripts only read it).  A handle that no fold has filled yet
-// has nr2 = 0.
+// has nr2 = 0.  The secondary placements (kmx_secondary.hip) read the five placement arrays of the nr public reads as well.
 struct PlacementsAccess {
     int device;
     hipStream_t stream;            // the stream of the fold that filled the handle
     uint64_t nr2;                  // internal reads: twice the public ones
     const uint32_t* best2;         // [nr2]: best[] of the alignments with the losing strand's entry cleared
+    uint64_t nr;                   // public reads
+    const uint32_t* locus;         // [nr]
+    const uint8_t* strand;
+    const uint8_t* dist;
+    const uint32_t* start;
+    const uint32_t* end;
 };
 PlacementsAccess placements_access(const kmx_placements* p);   // kmx_strands.hip
 // kmx_script.hip: kmx_alignments_scripts_device on the reads d_ranks / d_roff (at most ranks_len letters) with P.best2 in the place
@@ -73,10 +79,12 @@ kmx_status scripts_with_best(const char* fn, const kmx_index* index, const kmx_l
                              const PlacementsAccess& P, kmx_scripts** inout);
 // kmx_script.hip: the scripts of the entries that best[L.nr] selects among arrays shaped like loci and alignments (L: nr, n_loci and
 // locus_off; A: dist / start / end) over the reads d_ranks / d_roff, on `stream`; the refusals of the options and of the index are
-// those of kmx_alignments_scripts_device, and KMX_SCRIPT_ALL is refused.  kmx_rescues_scripts (kmx_rescue.hip) is its caller.
+// those of kmx_alignments_scripts_device, and KMX_SCRIPT_ALL in the options is refused.  every == true: every entry with a distance
+// is selected and best is not looked at (the KMX_SCRIPT_ALL path, which only a caller inside the library may ask for).
+// kmx_rescues_scripts (kmx_rescue.hip) and kmx_secondaries_scripts (kmx_secondary.hip, every == true) are its callers.
 kmx_status scripts_on_arrays(const char* fn, const kmx_index* index, const LociAccess& L, const AlignAccess& A, const void* d_ranks,
                              const void* d_roff, uint64_t ranks_len, const uint32_t* best, const kmx_script_options* options,
-                             hipStream_t stream, kmx_scripts** inout);
+                             hipStream_t stream, kmx_scripts** inout, bool every = false);
 
 // What the MD strings (kmx_tags.hip) need from a scripts handle (kmx_script.hip owns struct kmx_scripts): device pointers that belong
 // to the handle and stay as they are (the MD only reads them).  sel is only looked at when n_sel > 0, cigar when n_ops > 0; a handle
@@ -102,5 +110,8 @@ struct JobsAccess {
     const uint32_t* end;
 };
 JobsAccess rescues_access(const kmx_rescues* r);   // kmx_rescue.hip
+// ... and from the entry arrays of a secondaries handle (kmx_secondary.hip owns struct kmx_secondaries; n_jobs = n_sec), which the
+// sel of kmx_secondaries_scripts indexes
+JobsAccess secondaries_access(const kmx_secondaries* s);   // kmx_secondary.hip
 
 } // namespace kmx

@@ -31,6 +31,7 @@ PAIR_NO_PENALTY, PAIR_NO_SCORE = 0xFFFFFFFF, 0xFFFF
 RESCUE_DISCORDANT, RESCUE_MAX_INSERT = 1, 65536
 RESCUE_NONE, RESCUE_FOUND, RESCUE_CONCORDANT, RESCUE_TAKEN = 0, 1, 2, 3
 LOCATE_MATES, NO_CONTIG = 1, 0xFFFFFFFF
+SECONDARY_MAX, SECONDARY_NO_DELTA = 32, 0xFFFFFFFF
 
 # every symbol include/kmx.h declares
 EXPORTS = [
@@ -59,6 +60,8 @@ EXPORTS = [
     "kmx_placements_mapq", "kmx_mapq_counts", "kmx_mapq_view", "kmx_mapq_view_device", "kmx_mapq_free",
     "kmx_index_set_contigs", "kmx_index_contigs", "kmx_alignments_contigs_view", "kmx_alignments_contigs_view_device",
     "kmx_placements_locate", "kmx_located_counts", "kmx_located_view", "kmx_located_view_device", "kmx_located_free",
+    "kmx_placements_secondaries", "kmx_secondaries_counts", "kmx_secondaries_view", "kmx_secondaries_view_device", "kmx_secondaries_scripts",
+    "kmx_secondaries_md", "kmx_secondaries_free",
 ]
 
 
@@ -121,6 +124,10 @@ class MapqOptions(C.Structure):
 
 class LocateOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SecondaryOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_secondary", C.c_uint32), ("max_delta", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class KernelStat(C.Structure):
@@ -341,6 +348,19 @@ def lib():
         L.kmx_located_view_device.restype = C.c_int
         L.kmx_located_view_device.argtypes = [vp, P(vp), P(vp)]
         L.kmx_located_free.argtypes = [vp]
+        L.kmx_placements_secondaries.restype = C.c_int
+        L.kmx_placements_secondaries.argtypes = [vp, vp, vp, P(SecondaryOptions), vp, P(vp)]
+        L.kmx_secondaries_counts.restype = C.c_int
+        L.kmx_secondaries_counts.argtypes = [vp] + [P(u64)] * 4
+        L.kmx_secondaries_view.restype = C.c_int
+        L.kmx_secondaries_view.argtypes = [vp] + [P(vp)] * 7
+        L.kmx_secondaries_view_device.restype = C.c_int
+        L.kmx_secondaries_view_device.argtypes = [vp] + [P(vp)] * 7
+        L.kmx_secondaries_scripts.restype = C.c_int
+        L.kmx_secondaries_scripts.argtypes = [vp, vp, vp, P(ScriptOptions), P(vp)]
+        L.kmx_secondaries_md.restype = C.c_int
+        L.kmx_secondaries_md.argtypes = [vp, vp, vp, vp, P(MdOptions), vp, P(vp)]
+        L.kmx_secondaries_free.argtypes = [vp]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -721,15 +741,18 @@ class Scripts(_Handle):
         return ["".join(runs[int(a):int(b)]) for a, b in zip(cig_off[:-1], cig_off[1:])]
 
     def md(self, index, source, letters, stream=0, md=None):
-        """kmx_scripts_md (source: the Alignments these scripts were made from) or kmx_rescues_md (source: the Rescues): the MD
-        string of every entry, from the runs and the index's text.  letters: sigma output bytes by rank (a str, bytes or uint8
-        array, e.g. "ACGT").  stream=0: the stream that filled this handle.  Returns an Md (`md` reuses one)."""
+        """kmx_scripts_md (source: the Alignments these scripts were made from), kmx_rescues_md (source: the Rescues) or
+        kmx_secondaries_md (source: the Secondaries): the MD string of every entry, from the runs and the index's text.  letters:
+        sigma output bytes by rank (a str, bytes or uint8 array, e.g. "ACGT").  stream=0: the stream that filled this handle.
+        Returns an Md (`md` reuses one)."""
         if isinstance(source, Rescues):
             fn = lib().kmx_rescues_md
+        elif isinstance(source, Secondaries):
+            fn = lib().kmx_secondaries_md
         elif isinstance(source, Alignments):
             fn = lib().kmx_scripts_md
         else:
-            raise TypeError("Scripts.md: source is an Alignments or a Rescues")
+            raise TypeError("Scripts.md: source is an Alignments, a Rescues or a Secondaries")
         table = None if letters is None else _letters_table(letters)
         out = md or Md()
         o = MdOptions(C.sizeof(MdOptions), 0)
@@ -897,6 +920,100 @@ class Placements(_Handle):
         _check(lib().kmx_placements_locate(index._h, alignments._h, self._h, C.byref(o), stream or None, C.byref(out._h)))
         out._reads = self._reads
         return out
+
+    def secondaries(self, loci, alignments, max_secondary, max_delta=None, stream=0, secondaries=None):
+        """kmx_placements_secondaries: up to max_secondary (<= SECONDARY_MAX) further places per read, chosen greedily by
+        (dist, locus) among the aligned loci of both strands that lie elsewhere from the primary and from every place taken before.
+        max_delta=None: no bound, else a candidate has dist <= the primary's + max_delta.  stream=0: the stream that filled this
+        handle.  Returns a Secondaries (`secondaries` reuses one)."""
+        out = secondaries or Secondaries()
+        o = SecondaryOptions(C.sizeof(SecondaryOptions), int(max_secondary), SECONDARY_NO_DELTA if max_delta is None else int(max_delta), 0)
+        _check(lib().kmx_placements_secondaries(loci._h, alignments._h, self._h, C.byref(o), stream or None, C.byref(out._h)))
+        out._reads = self._reads
+        return out
+
+    def close(self):
+        super().close()
+        self._reads = None
+
+
+def xa_strings(sec_off, dist, start, ctg, cigars, strand_names="+-", located=None, rname=None):
+    """The XA:Z: value of every public read from the host arrays of a Secondaries and one CIGAR per entry: "" or items
+    rname,<strand><pos>,CIGAR,NM; in bwa's form, pos 1-based.  located=(names, ctg_off) with ctg: the entry's contig name and a
+    contig-local pos; otherwise rname and the position in the text.  Pure Python: no device is needed."""
+    sec_off = np.asarray(sec_off, np.uint64)
+    if located is not None and ctg is None:
+        raise ValueError("xa: located needs the ctg of a Secondaries made under a contig table")
+    if located is None and rname is None:
+        raise ValueError("xa: give rname, or located=(names, ctg_off)")
+    out = []
+    for i in range((sec_off.size - 1) // 2):
+        items = []
+        for s in (0, 1):
+            for e in range(int(sec_off[2 * i + s]), int(sec_off[2 * i + s + 1])):
+                if located is not None:
+                    names, ctg_off = located
+                    name, pos = names[int(ctg[e])], int(start[e]) - int(ctg_off[int(ctg[e])]) + 1
+                else:
+                    name, pos = rname, int(start[e]) + 1
+                items.append(f"{name},{strand_names[s]}{pos},{cigars[e] or '*'},{int(dist[e])};")
+        out.append("".join(items))
+    return out
+
+
+class Secondaries(_Handle):
+    """Owns a kmx_secondaries handle (kmx_placements_secondaries): up to N further places per public read, the entries of internal
+    read 2i + s being those of read i on strand s."""
+
+    _free = "kmx_secondaries_free"
+
+    def __init__(self):
+        super().__init__()
+        self._reads = None          # the StrandReads whose stream the call ran on: it must outlive the views
+
+    def counts(self):
+        return self._counts("kmx_secondaries_counts", "nr", "n_sec", "n_multi", "n_truncated")
+
+    def host(self):
+        """(sec_off[2 nr + 1] u64, locus[n_sec] u32, dist u8, start u32, end u32, ctg u32 or None, more[nr] u8) as numpy copies;
+        ctg is None when the alignments carried no contig table."""
+        c = self.counts()
+        p = [C.c_void_p() for _ in range(7)]
+        _check(lib().kmx_secondaries_view(self._h, *[C.byref(x) for x in p]))
+        ns = c["n_sec"]
+        out = [_view(p[0].value, 2 * c["nr"] + 1, np.uint64)] + [_view(x.value, ns, d) for x, d in zip(p[1:5], (np.uint32, np.uint8, np.uint32, np.uint32))]
+        out.append(_view(p[5].value, ns, np.uint32) if p[5].value else None)
+        out.append(_view(p[6].value, c["nr"], np.uint8))
+        return tuple(None if x is None else x.copy() for x in out)
+
+    def device_ptrs(self):
+        """(d_sec_off, d_locus, d_dist, d_start, d_end, d_ctg, d_more): kmx_secondaries_view_device."""
+        return self._device_ptrs("kmx_secondaries_view_device", 7)
+
+    def scripts(self, index, reads, m=False, scratch_bytes=0, scripts=None):
+        """kmx_secondaries_scripts: the CIGAR of every entry (for a reverse entry that of the reverse complement against the forward
+        text, as SAM has it), on the stream of `reads`.  Returns a Scripts over the internal reads, sel[e] == e."""
+        s = scripts or Scripts()
+        o = Alignments._script_options(False, m, scratch_bytes)
+        _check(lib().kmx_secondaries_scripts(index._h, reads._h, self._h, C.byref(o), C.byref(s._h)))
+        return s
+
+    def cigars(self, scripts):
+        """One CIGAR string per entry from the Scripts of scripts()."""
+        return scripts.strings()
+
+    def md(self, index, scripts, letters, stream=0, md=None):
+        """kmx_secondaries_md: the MD string of every entry from the Scripts of scripts().  Returns an Md (`md` reuses one)."""
+        out = scripts.md(index, self, letters, stream, md)
+        out._reads = self._reads
+        return out
+
+    def xa(self, scripts, strand_names="+-", located=None, rname=None):
+        """One XA:Z: value per public read: "" or items rname,<strand><pos>,CIGAR,NM; in bwa's form (pos 1-based), in the order of
+        the entries.  located=(names, ctg_off): the name of the entry's contig and a contig-local pos (the handle must carry ctg);
+        otherwise `rname` names the one reference.  scripts: the Scripts of scripts()."""
+        sec_off, _, dist, start, _, ctg, _ = self.host()
+        return xa_strings(sec_off, dist, start, ctg, self.cigars(scripts), strand_names, located, rname)
 
     def close(self):
         super().close()
@@ -1091,7 +1208,8 @@ def sam_header(names, ctg_off):
     return ["@HD\tVN:1.6\tSO:unsorted"] + [f"@SQ\tSN:{nm}\tLN:{int(b) - int(a)}" for nm, a, b in zip(names, ctg_off[:-1], ctg_off[1:])]
 
 
-def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements_host, cigars, mds, mapq, pairs_host=None, located_host=None):
+def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements_host, cigars, mds, mapq, pairs_host=None, located_host=None,
+              xa=None):
     """One SAM line (no newline) per public read from host arrays: the reads (ranks, roff), the rank -> letter table, the rank
     complement table, Placements.host(), the CIGAR and MD strings per read (Placements.cigars / .mds; a tuple of two lists, the
     placements' and the rescue's, gives a rescued read those of the rescue), Mapq.host() and, for paired reads, Pairs.host().
@@ -1099,8 +1217,9 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
     there is no mate.  CIGAR is * when the read is unplaced, RNEXT = or *, SEQ the reverse complement for a reverse placement,
     QUAL *; placed reads carry NM:i: (the distance) and MD:Z:.  located_host (Located.host(): ctg, pos) switches to contig
     coordinates: rname then is a sequence of one name per contig, RNAME the read's contig (an unplaced read with a placed mate takes
-    the mate's), POS and PNEXT are contig-local, RNEXT is = for the same contig and the mate's contig name otherwise.  Pure Python /
-    numpy: no device is needed."""
+    the mate's), POS and PNEXT are contig-local, RNEXT is = for the same contig and the mate's contig name otherwise.  xa
+    (Secondaries.xa(): one string per read) appends XA:Z:<string> behind MD:Z: to every placed read whose string is not empty; None
+    leaves the lines as they were.  Pure Python / numpy: no device is needed."""
     table = _letters_table(letters)
     comp = np.ascontiguousarray(complement, np.uint8)
     if table.size < sigma or comp.size < sigma:
@@ -1113,6 +1232,8 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
     mapq = np.asarray(mapq, np.uint8)
     if not (roff.size - 1 == len(qnames) == len(cigars) == len(mds) == mapq.size == nr):
         raise ValueError("sam_lines: the arrays disagree in the number of reads")
+    if xa is not None and len(xa) != nr:
+        raise ValueError("sam_lines: xa disagrees in the number of reads")
     placed = strand != 255
     if pairs_host is not None:
         flag, pos, pnext, tlen = sam_pair_fields(strand, start, pairs_host[0], pairs_host[1])
@@ -1154,6 +1275,8 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
                   str(int(tlen[i])), seq, "*"]
         if placed[i]:
             fields += [f"NM:i:{int(dist[i])}", f"MD:Z:{mds[i]}"]
+            if xa is not None and xa[i]:
+                fields.append(f"XA:Z:{xa[i]}")
         lines.append("\t".join(fields))
     return lines
 
@@ -1451,17 +1574,21 @@ class Index:
         return s
 
     def map_reads_strands(self, ranks, roff, w, complement, stride=1, band=0, min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False,
-                          tags=False, letters=None):
+                          tags=False, letters=None, secondaries=0):
         """map_reads on both strands: kmx_reads_strands, kmx_search_windows_device, kmx_windows_vote, kmx_loci_align_device and
         kmx_alignments_fold_strands in a row, all on the stream of the StrandReads.  Returns (StrandReads, Loci, Alignments,
         Placements): the loci and alignments are those of the doubled batch (internal read 2i is read i, 2i + 1 its reverse
         complement), the placements one per read.  scripts=True appends kmx_placements_scripts (the CIGARs of the winners).
-        tags=True (needs `letters`, the rank -> letter table; implies scripts) appends a SamTags(mapq, md, None, None) as the last
-        element: kmx_placements_mapq and kmx_scripts_md."""
+        tags=True (needs `letters`, the rank -> letter table; implies scripts) appends a SamTags(mapq, md, None, None):
+        kmx_placements_mapq and kmx_scripts_md.  secondaries=N > 0 appends, behind everything else, the Secondaries of
+        kmx_placements_secondaries with max_secondary = N and no max_delta."""
         if tags and letters is None:
             raise ValueError("map_reads_strands: tags=True needs letters")
         if max_span is None:
             max_span = 0xFFFFFFFF
+        if secondaries:
+            out = self.map_reads_strands(ranks, roff, w, complement, stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags, letters)
+            return self._with_secondaries(out, secondaries)
         opened = []
         try:
             reads = self.strand_reads(ranks, roff, complement)
@@ -1494,9 +1621,22 @@ class Index:
                 h.close()
             raise
 
+    @staticmethod
+    def _with_secondaries(out, n):
+        """out: what a chain call returns, (StrandReads, Loci, Alignments, Placements, ...) with the placements final; the same with
+        the Secondaries of kmx_placements_secondaries (max_secondary = n, no max_delta) appended."""
+        try:
+            return out + (out[3].secondaries(out[1], out[2], n),)
+        except Exception:
+            for h in reversed(out):
+                for x in (h if isinstance(h, SamTags) else (h,)):
+                    if x is not None:
+                        x.close()
+            raise
+
     def map_pairs(self, ranks, roff, w, complement, min_insert, max_insert, orientation=PAIR_FR, unpaired_penalty=None, stride=1, band=0,
                   min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False, rescue=False, rescue_edits=None, rescue_discordant=False,
-                  tags=False, letters=None):
+                  tags=False, letters=None, secondaries=0):
         """map_reads_strands for paired reads: the reads are interleaved mates (read 2p is mate 1 of pair p, read 2p + 1 its mate 2, so
         their number is even), and kmx_alignments_fold_pairs stands in the fold's place.  Returns (StrandReads, Loci, Alignments,
         Placements, Pairs); scripts=True appends kmx_placements_scripts (the CIGARs of the chosen loci).  rescue=True runs
@@ -1504,9 +1644,15 @@ class Index:
         appends its Rescues as the last element; the scripts then are those of the placements after the rescue.  tags=True (needs
         `letters`, the rank -> letter table; implies scripts) appends, behind everything else, a SamTags(mapq, md, rescue_scripts,
         rescue_md): kmx_placements_mapq with the pairs (its budget the larger of max_edits and rescue_edits), kmx_scripts_md, and
-        after a rescue kmx_rescues_scripts and kmx_rescues_md (else None)."""
+        after a rescue kmx_rescues_scripts and kmx_rescues_md (else None).  secondaries=N > 0 appends, behind everything else, the
+        Secondaries of kmx_placements_secondaries (max_secondary = N, no max_delta) on the placements as they then are: after the
+        rescue, so that the primaries are final."""
         if tags and letters is None:
             raise ValueError("map_pairs: tags=True needs letters")
+        if secondaries:
+            out = self.map_pairs(ranks, roff, w, complement, min_insert, max_insert, orientation, unpaired_penalty, stride, band, min_votes, max_occ,
+                                 max_edits, max_span, scripts, rescue, rescue_edits, rescue_discordant, tags, letters)
+            return self._with_secondaries(out, secondaries)
         roff = np.ascontiguousarray(roff, np.uint64)
         if (roff.size - 1) % 2:
             raise ValueError("map_pairs: an odd number of reads; the reads are interleaved mates")

@@ -1264,6 +1264,94 @@ kmx_status kmx_secondaries_md(const kmx_index* index, const kmx_scripts* scripts
                               const uint8_t* letters, const kmx_md_options* options, void* stream, kmx_md** inout);
 void kmx_secondaries_free(kmx_secondaries* s);
 
+/* ---- Soft clipping: every script trimmed to its best-scoring part (an extension, no reference interface; a caller detects the
+ *      capability by the macro KMX_SOFT_CLIP, KMX_VERSION is unchanged).  The chain aligns every read END TO END at unit cost:
+ *      a read that overhangs the end of the text or of a contig comes out with the overhang as a terminal 'I' run, and a read
+ *      with an adapter tail or a chimeric end carries a dozen X / I / D at one end, which count in NM, in the MD string and in
+ *      XA.  SAM writes such ends as 'S'.  kmx_scripts_clip trims the runs of every entry of a scripts handle under an affine
+ *      scoring and gives the score (SAM's AS:i) with it.
+ *
+ *      THIS IS POST-ALIGNMENT TRIMMING OF THE EDIT-OPTIMAL SCRIPT, NOT A SMITH-WATERMAN REALIGNMENT.  The clipped alignment is
+ *      the best-scoring PART OF THE CANONICAL SCRIPT, not the best local alignment of the read: no cell of a dynamic programme
+ *      is computed again, and a better local alignment that the unit-cost script does not contain is not found.
+ *
+ *      Input.  The call takes ONLY a scripts handle: no index, no reads, no alignments.  It serves the scripts of
+ *      kmx_alignments_scripts[_device] (KMX_SCRIPT_ALL or not), kmx_placements_scripts, kmx_rescues_scripts and
+ *      kmx_secondaries_scripts alike.  Entry e of the clips is entry e of the scripts.  `stream` NULL means the stream that
+ *      filled the scripts, else it is that stream or one the caller has ordered behind it.
+ *
+ *      The contract of entry e, with the runs r_0 .. r_{R-1} = cigar[cig_off[e] .. cig_off[e + 1]) of the scripts and the
+ *      options a = match, b = mismatch, o = gap_open, x = gap_extend, p = clip_penalty, everything in int64:
+ *        w('=' of len) = len a,  w('X') = -len b,  w('I') = w('D') = -(o + len x);  W[0] = 0, W[k + 1] = W[k] + w(r_k);
+ *        a LEFT CUT i is 0, or any k with r_k an '=' run; a RIGHT CUT j is R, or any k with r_{k-1} an '=' run;
+ *        the candidates are all (i, j) with i < j, and (0, R) always, even for R = 0;
+ *        V(i, j) = W[j] - W[i] - p [i > 0] - p [j < R];
+ *        the candidate with the greatest V is taken; among equals the smallest i, then the largest j;
+ *        if that V < min_score the entry stays whole, (i, j) = (0, R), and the bit KMX_CLIP_LOW is set in cflags[e].
+ *      Per entry: score[e] (i32) = V of the (i, j) that is kept (for a LOW entry V(0, R) = W[R], the score of what is written),
+ *      saturated to the int32 range; sl[e] / sr[e] (u16) = the read letters ('=' 'X' 'I') of the runs in front of i / from j
+ *      on; tl[e] / tr[e] (u16) = the text letters ('=' 'X' 'D') of the same runs; nm[e] (u16) = the 'X' + 'I' + 'D' lengths of
+ *      the kept runs (the five saturate at 65535, which a script of the chain never reaches); cflags[e] (u8).  The new runs:
+ *      sl 'S' (only if sl > 0), r_i .. r_{j-1}, sr 'S' (only if sr > 0); 'S' is BAM op 4; cig_off[n_sel + 1] (u64) delimits
+ *      them, n_ops = cig_off[n_sel].  So: a clipped side always borders an '=' run, an 'I' or 'D' never touches an 'S', an
+ *      entry without an '=' run (a read of letters outside the alphabet: mI) is never clipped, sl + sr + the '=' 'X' 'I'
+ *      lengths of the kept runs equal the read's length, and the clipped text interval is [start + tl, end - tr).  An entry
+ *      gets at most R + 2 runs: the output is allocated at the scripts' n_ops + 2 n_sel and nothing is read back in front of
+ *      the write.  n_clipped counts the entries with sl + sr > 0, n_low those with the LOW bit.  An entry with an op other than
+ *      = X I D is copied unclipped with score 0, sl = sr = tl = tr = nm = 0 and the LOW bit; with the right handle there are
+ *      none.  Every access is bounded by n_sel and n_ops: a foreign handle gives meaningless but harmless results.
+ *      tests/clip_naive.py is this contract in executable form.
+ *
+ *      The clips handle follows the lifecycle of the other chain handles: *inout == NULL allocates, a handle passed in is
+ *      reused and its earlier views end; the device arrays (kmx_clips_view_device; cig_off is NULL after a refusal or an error,
+ *      the per-entry arrays when n_sel == 0, cigar when n_ops == 0) are complete in stream order when the call returns;
+ *      kmx_clips_view copies to page-locked host memory on first use and synchronises, on the stream of the call: 15 bytes per
+ *      entry, 8 per entry for cig_off and 4 per run (cig_off always holds at least the one offset 0).  Any output pointer may
+ *      be NULL.  The call only reads the scripts and leaves them as they are.
+ *
+ *      KMX_ERR_INVALID_ARGUMENT before the handle is looked at: a NULL argument, a struct_size that is too small, flags != 0,
+ *      match outside 1 .. 255, mismatch, gap_open or gap_extend above 255, clip_penalty above 65535.  After looking: a scripts
+ *      handle made with KMX_SCRIPT_M ('=' and 'X' are no longer apart).  After such a refusal or an error the clips handle,
+ *      when there is one, holds an empty result.
+ *
+ *      MD of the clipped entries.  kmx_clips_md (the scripts of kmx_alignments_scripts[_device] or kmx_placements_scripts and
+ *      their alignments) and kmx_clips_rescues_md (the scripts of kmx_rescues_scripts and the rescues) apply the rule of
+ *      kmx_scripts_md to the runs of the clips, with the text cursor starting at start[sel[e]] + tl[e], the end test against
+ *      end[sel[e]] - tr[e], and 'S' treated like 'I'; sel comes from the scripts handle.  An entry with tl + tr > end - start
+ *      counts in n_mismatched.  The refusals are those of kmx_scripts_md / kmx_rescues_md; in addition clips whose n_sel
+ *      differs from the scripts', or that live on another device, are refused after looking.  The secondaries need no MD here:
+ *      XA carries only CIGAR and NM.
+ *
+ *      Left out: supplementary lines, TLEN from the clipped ends, a clip-aware MAPQ and a clip-aware choice between loci.
+ *      Untested: an index with more than one replica, and the different-devices refusals.  kmx_stats_get is not extended (see
+ *      kmx_loci_align). */
+#define KMX_SOFT_CLIP 1
+#define KMX_CLIP_LOW 1u   /* cflags: the best value was below min_score (or the entry has a foreign op): left whole */
+typedef struct kmx_clip_options {
+    uint32_t struct_size;   /* = sizeof(kmx_clip_options): 32 */
+    uint32_t match;         /* a, 1 .. 255 */
+    uint32_t mismatch;      /* b, 0 .. 255 */
+    uint32_t gap_open;      /* o, 0 .. 255 */
+    uint32_t gap_extend;    /* x, 0 .. 255: a gap run of len letters costs o + len x */
+    uint32_t clip_penalty;  /* p, 0 .. 65535, charged once per clipped end */
+    int32_t min_score;
+    uint32_t flags;         /* 0 */
+} kmx_clip_options;
+typedef struct kmx_clips kmx_clips;
+kmx_status kmx_scripts_clip(const kmx_scripts* scripts, const kmx_clip_options* options, void* stream, kmx_clips** inout);
+kmx_status kmx_clips_counts(const kmx_clips* c, uint64_t* n_sel, uint64_t* n_ops, uint64_t* n_clipped, uint64_t* n_low);
+kmx_status kmx_clips_view(kmx_clips* c, const int32_t** score /* n_sel */, const uint16_t** sl, const uint16_t** sr, const uint16_t** tl,
+                          const uint16_t** tr, const uint16_t** nm, const uint8_t** cflags, const uint64_t** cig_off /* n_sel + 1 */,
+                          const uint32_t** cigar /* n_ops */);
+kmx_status kmx_clips_view_device(const kmx_clips* c, const int32_t** d_score, const uint16_t** d_sl, const uint16_t** d_sr,
+                                 const uint16_t** d_tl, const uint16_t** d_tr, const uint16_t** d_nm, const uint8_t** d_cflags,
+                                 const uint64_t** d_cig_off, const uint32_t** d_cigar);
+kmx_status kmx_clips_md(const kmx_index* index, const kmx_scripts* scripts, const kmx_clips* clips, const kmx_alignments* alignments,
+                        const uint8_t* letters, const kmx_md_options* options, void* stream, kmx_md** inout);
+kmx_status kmx_clips_rescues_md(const kmx_index* index, const kmx_scripts* scripts, const kmx_clips* clips, const kmx_rescues* rescues,
+                                const uint8_t* letters, const kmx_md_options* options, void* stream, kmx_md** inout);
+void kmx_clips_free(kmx_clips* c);
+
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.
  * Works on built, loaded and replicated indexes (this replica).  The first call derives a copy packed at 2, 4 or 8 bits per

@@ -1,5 +1,7 @@
 // SAM tags of the read-mapping chain (kmx_scripts_md, kmx_rescues_md, kmx_secondaries_md, kmx_placements_mapq; include/kmx.h, KMX_SAM_TAGS): the MD string
 // of every entry of a scripts handle, from its runs and the packed text, and a MAPQ per public read from the placements and the pairs.
+// kmx_clips_md and kmx_clips_rescues_md (KMX_SOFT_CLIP) run the same two MD kernels over the runs of a clips handle (kmx_clip.hip), with the
+// text letters clipped off either side as a per-entry offset pair; only that path accepts an S run.
 //
 //   k_md_count         a thread per entry: validates the entry (sel inside its bound, s <= t <= n, only = X I D, the = X D lengths sum
 //                      to t - s) and counts the bytes of its MD from the run lengths alone: the digits of every match counter, 2 bytes
@@ -25,7 +27,7 @@ namespace {
 
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kNoScore = 0xFFFFu;
-enum { OP_I = 1, OP_D = 2, OP_EQ = 7, OP_X = 8 };
+enum { OP_I = 1, OP_D = 2, OP_S = 4, OP_EQ = 7, OP_X = 8 };
 enum { MD_N_BYTES = 0, MD_N_MISMATCHED, MD_COUNT };
 enum { MQ_N_ZERO = 0, MQ_N_CAP, MQ_COUNT };
 
@@ -47,6 +49,8 @@ struct MdIn {
     uint64_t n_sel, n_ops, bound, n;
     const uint64_t* text;          // packed at w bits per letter
     uint32_t w;
+    const uint16_t* tl;            // [n_sel]: the text letters clipped off either side (kmx_clips_md: cig_off / cigar / n_ops then are the
+    const uint16_t* tr;            // clips', and an S run counts as an I); nullptr for the unclipped scripts
 };
 
 __device__ __forceinline__ uint32_t digits_of(uint64_t c)
@@ -82,6 +86,11 @@ __global__ __launch_bounds__(kBlock) void k_md_count(MdIn M, uint32_t* __restric
                 const uint32_t s = M.start[l], t = M.end[l];
                 bad = !(s <= t && t <= M.n);
                 want = uint64_t(t) - s;
+                if (M.tl && !bad) {                            // the clipped interval [s + tl, t - tr)
+                    const uint64_t off = uint64_t(M.tl[e]) + M.tr[e];
+                    bad = off > want;
+                    want -= off;
+                }
             }
             uint64_t c = 0, sum = 0;
             for (uint64_t k = a; k < b && !bad; ++k) {
@@ -92,7 +101,7 @@ __global__ __launch_bounds__(kBlock) void k_md_count(MdIn M, uint32_t* __restric
                     if (len) { bytes += digits_of(c) + 1 + 2 * (len - 1); c = 0; }
                     sum += len;
                 } else if (op == OP_D) { bytes += digits_of(c) + 1 + len; c = 0; sum += len; }
-                else if (op != OP_I) bad = true;
+                else if (op != OP_I && !(op == OP_S && M.tl)) bad = true;
             }
             bytes += digits_of(c);
             bad = bad || sum != want || bytes > 0xFFFFFFFFull;  // (2^32 bytes or more: the counts are 32-bit; needs t - s > 2^30)
@@ -136,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void k_md_write(MdIn M, const uint64_t* __r
         if (j >= M.n) return uint8_t('?');
         return table[uint32_t((M.text[j / per] >> ((j % per) * w)) & mask)];
     };
-    uint64_t c = 0, j = M.start[l];
+    uint64_t c = 0, j = uint64_t(M.start[l]) + (M.tl ? M.tl[e] : 0);
     for (uint64_t k = a; k < b; ++k) {
         const uint32_t v = M.cigar[k], op = v & 15u;
         const uint64_t len = v >> 4;
@@ -243,7 +252,7 @@ struct kmx_mapq {
 namespace {
 
 kmx_status md_run(const char* fn, const kmx::IndexAccess& X, const kmx::ScriptsAccess& S, const uint32_t* start, const uint32_t* end, uint64_t bound,
-                  const uint8_t* letters, hipStream_t s, kmx_md* h)
+                  const uint8_t* letters, hipStream_t s, kmx_md* h, const kmx::ClipsAccess* K)
 {
     const uint64_t ns = S.n_sel;
     h->stream = s;
@@ -261,7 +270,8 @@ kmx_status md_run(const char* fn, const kmx::IndexAccess& X, const kmx::ScriptsA
     TRY_HIP(h->ctr.ensure(MD_COUNT * 8));
     unsigned long long* ctr = h->ctr.as<unsigned long long>();
     TRY_HIP(hipMemsetAsync(ctr, 0, MD_COUNT * 8, s));
-    const MdIn M{S.sel, S.cig_off, S.cigar, start, end, ns, S.n_ops, bound, X.n, X.text->d_words, X.text->w};
+    const MdIn M{S.sel, K ? K->cig_off : S.cig_off, K ? K->cigar : S.cigar, start, end, ns, K ? K->n_ops : S.n_ops, bound, X.n, X.text->d_words,
+                 X.text->w, K ? K->tl : nullptr, K ? K->tr : nullptr};
     const dim3 grid(grid_for(ns, kBlock)), block(kBlock);
     hipLaunchKernelGGL(k_md_count, grid, block, 0, s, M, h->cnt.as<uint32_t>(), ctr);
     kmx::launch_scan(s, h->cnt.as<uint32_t>(), ns, h->bsum.as<uint64_t>(), h->md_off.as<uint64_t>(), ctr + MD_N_BYTES);
@@ -302,9 +312,10 @@ kmx_status md_front(const std::string& who, const kmx_index* index, const void* 
     return KMX_OK;
 }
 
-// the MD strings of the scripts S over the start / end arrays (of `bound` entries, on `device`) that their sel indexes
+// the MD strings of the scripts S over the start / end arrays (of `bound` entries, on `device`) that their sel indexes; K: the clips
+// of S, whose runs and offsets then stand in for the scripts' own
 kmx_status md_on_arrays(const char* fn, const kmx_index* index, const kmx::ScriptsAccess& S, int device, const uint32_t* start, const uint32_t* end,
-                        uint64_t bound, const uint8_t* letters, hipStream_t stream, kmx_md** inout)
+                        uint64_t bound, const uint8_t* letters, hipStream_t stream, kmx_md** inout, const kmx::ClipsAccess* K = nullptr)
 {
     const std::string who = std::string(fn) + ": ";
     kmx_md* h = *inout;
@@ -314,6 +325,8 @@ kmx_status md_on_arrays(const char* fn, const kmx_index* index, const kmx::Scrip
     };
     if (S.flags & KMX_SCRIPT_M) return refuse(KMX_ERR_INVALID_ARGUMENT, "the scripts were made with KMX_SCRIPT_M: an MD needs '=' and 'X' apart");
     if (S.n_sel && S.device != device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the handles live on different devices");
+    if (K && K->n_sel != S.n_sel) return refuse(KMX_ERR_INVALID_ARGUMENT, "the clips are not those of these scripts: n_sel differs");
+    if (K && K->n_sel && K->device != S.device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the clips and the scripts live on different devices");
     kmx::IndexAccess X{};
     if (!kmx::index_access_on(index, S.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the scripts live on a device that holds no replica of this index");
     if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
@@ -325,7 +338,7 @@ kmx_status md_on_arrays(const char* fn, const kmx_index* index, const kmx::Scrip
         return bound_st;
     }
     hipStream_t s = stream ? stream : S.stream;
-    const kmx_status st = md_run(fn, X, S, start, end, bound, letters, s, h);
+    const kmx_status st = md_run(fn, X, S, start, end, bound, letters, s, h, K);
     if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
         (void)hipStreamSynchronize(s);
         h->clear();
@@ -385,6 +398,28 @@ kmx_status kmx_secondaries_md(const kmx_index* index, const kmx_scripts* scripts
     const kmx::JobsAccess J = kmx::secondaries_access(secondaries);
     return md_on_arrays("kmx_secondaries_md", index, kmx::scripts_access(scripts), J.device, J.start, J.end, J.n_jobs, letters,
                         static_cast<hipStream_t>(stream), inout);
+}
+
+kmx_status kmx_clips_md(const kmx_index* index, const kmx_scripts* scripts, const kmx_clips* clips, const kmx_alignments* alignments,
+                        const uint8_t* letters, const kmx_md_options* options, void* stream, kmx_md** inout)
+{
+    if (!clips) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_clips_md: clips handle is NULL");
+    TRY_KMX(md_front("kmx_clips_md: ", index, scripts, alignments, "alignments", letters, options, inout));
+    const kmx::AlignAccess A = kmx::alignments_access(alignments);
+    const kmx::ClipsAccess K = kmx::clips_access(clips);
+    return md_on_arrays("kmx_clips_md", index, kmx::scripts_access(scripts), A.device, A.start, A.end, A.n_loci, letters,
+                        static_cast<hipStream_t>(stream), inout, &K);
+}
+
+kmx_status kmx_clips_rescues_md(const kmx_index* index, const kmx_scripts* scripts, const kmx_clips* clips, const kmx_rescues* rescues,
+                                const uint8_t* letters, const kmx_md_options* options, void* stream, kmx_md** inout)
+{
+    if (!clips) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_clips_rescues_md: clips handle is NULL");
+    TRY_KMX(md_front("kmx_clips_rescues_md: ", index, scripts, rescues, "rescues", letters, options, inout));
+    const kmx::JobsAccess J = kmx::rescues_access(rescues);
+    const kmx::ClipsAccess K = kmx::clips_access(clips);
+    return md_on_arrays("kmx_clips_rescues_md", index, kmx::scripts_access(scripts), J.device, J.start, J.end, J.n_jobs, letters,
+                        static_cast<hipStream_t>(stream), inout, &K);
 }
 
 kmx_status kmx_md_counts(const kmx_md* h, uint64_t* n_sel, uint64_t* n_bytes, uint64_t* n_mismatched)

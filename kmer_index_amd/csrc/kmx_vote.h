@@ -114,4 +114,17 @@ JobsAccess rescues_access(const kmx_rescues* r);   // kmx_rescue.hip
 // sel of kmx_secondaries_scripts indexes
 JobsAccess secondaries_access(const kmx_secondaries* s);   // kmx_secondary.hip
 
+// What the MD of clipped entries (kmx_clips_md, kmx_clips_rescues_md; kmx_tags.hip) needs from a clips handle (kmx_clip.hip owns
+// struct kmx_clips): the clipped runs and the text letters clipped off either side.  The per-entry arrays are only looked at when
+// n_sel > 0, cigar when n_ops > 0; a handle that no call has filled (or whose last call was refused) has n_sel = 0.
+struct ClipsAccess {
+    int device;
+    uint64_t n_sel, n_ops;
+    const uint16_t* tl;            // [n_sel]
+    const uint16_t* tr;
+    const uint64_t* cig_off;       // [n_sel + 1]
+    const uint32_t* cigar;         // [n_ops]
+};
+ClipsAccess clips_access(const kmx_clips* c);   // kmx_clip.hip
+
 } // namespace kmx

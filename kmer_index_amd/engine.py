@@ -32,6 +32,7 @@ RESCUE_DISCORDANT, RESCUE_MAX_INSERT = 1, 65536
 RESCUE_NONE, RESCUE_FOUND, RESCUE_CONCORDANT, RESCUE_TAKEN = 0, 1, 2, 3
 LOCATE_MATES, NO_CONTIG = 1, 0xFFFFFFFF
 SECONDARY_MAX, SECONDARY_NO_DELTA = 32, 0xFFFFFFFF
+CLIP_LOW = 1
 
 # every symbol include/kmx.h declares
 EXPORTS = [
@@ -62,6 +63,7 @@ EXPORTS = [
     "kmx_placements_locate", "kmx_located_counts", "kmx_located_view", "kmx_located_view_device", "kmx_located_free",
     "kmx_placements_secondaries", "kmx_secondaries_counts", "kmx_secondaries_view", "kmx_secondaries_view_device", "kmx_secondaries_scripts",
     "kmx_secondaries_md", "kmx_secondaries_free",
+    "kmx_scripts_clip", "kmx_clips_counts", "kmx_clips_view", "kmx_clips_view_device", "kmx_clips_md", "kmx_clips_rescues_md", "kmx_clips_free",
 ]
 
 
@@ -128,6 +130,11 @@ class LocateOptions(C.Structure):
 
 class SecondaryOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_secondary", C.c_uint32), ("max_delta", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ClipOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("match", C.c_uint32), ("mismatch", C.c_uint32), ("gap_open", C.c_uint32),
+                ("gap_extend", C.c_uint32), ("clip_penalty", C.c_uint32), ("min_score", C.c_int32), ("flags", C.c_uint32)]
 
 
 class KernelStat(C.Structure):
@@ -361,6 +368,19 @@ def lib():
         L.kmx_secondaries_md.restype = C.c_int
         L.kmx_secondaries_md.argtypes = [vp, vp, vp, vp, P(MdOptions), vp, P(vp)]
         L.kmx_secondaries_free.argtypes = [vp]
+        L.kmx_scripts_clip.restype = C.c_int
+        L.kmx_scripts_clip.argtypes = [vp, P(ClipOptions), vp, P(vp)]
+        L.kmx_clips_counts.restype = C.c_int
+        L.kmx_clips_counts.argtypes = [vp] + [P(u64)] * 4
+        L.kmx_clips_view.restype = C.c_int
+        L.kmx_clips_view.argtypes = [vp] + [P(vp)] * 9
+        L.kmx_clips_view_device.restype = C.c_int
+        L.kmx_clips_view_device.argtypes = [vp] + [P(vp)] * 9
+        L.kmx_clips_md.restype = C.c_int
+        L.kmx_clips_md.argtypes = [vp, vp, vp, vp, vp, P(MdOptions), vp, P(vp)]
+        L.kmx_clips_rescues_md.restype = C.c_int
+        L.kmx_clips_rescues_md.argtypes = [vp, vp, vp, vp, vp, P(MdOptions), vp, P(vp)]
+        L.kmx_clips_free.argtypes = [vp]
         L.kmx_index_text.restype = C.c_int
         L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
         L.kmx_stats_enable.restype = C.c_int
@@ -737,8 +757,18 @@ class Scripts(_Handle):
     def strings(self):
         """One CIGAR string per entry, e.g. "50=1X30=1D69=" ("" for an entry without a script)."""
         _, _, cig_off, cigar = self.host()
-        runs = [f"{int(v) >> 4}{CIGAR_OPS[int(v) & 15]}" for v in cigar]
-        return ["".join(runs[int(a):int(b)]) for a, b in zip(cig_off[:-1], cig_off[1:])]
+        return _runs_strings(cig_off, cigar)
+
+    def clip(self, match=1, mismatch=4, gap_open=6, gap_extend=1, clip_penalty=5, min_score=0, stream=0, clips=None):
+        """kmx_scripts_clip: every entry trimmed to the best-scoring part of its runs under the affine scoring (a gap run of len
+        letters costs gap_open + len gap_extend; clip_penalty once per clipped end); an entry whose best value is below min_score
+        stays whole and carries CLIP_LOW.  Post-alignment trimming of the edit-optimal script, not a realignment.  Serves the
+        Scripts of every source; stream=0: the stream that filled this handle.  Returns a Clips (`clips` reuses one)."""
+        out = clips or Clips()
+        o = ClipOptions(C.sizeof(ClipOptions), int(match), int(mismatch), int(gap_open), int(gap_extend), int(clip_penalty), int(min_score), 0)
+        _check(lib().kmx_scripts_clip(self._h, C.byref(o), stream or None, C.byref(out._h)))
+        out.scripts = self
+        return out
 
     def md(self, index, source, letters, stream=0, md=None):
         """kmx_scripts_md (source: the Alignments these scripts were made from), kmx_rescues_md (source: the Rescues) or
@@ -758,6 +788,81 @@ class Scripts(_Handle):
         o = MdOptions(C.sizeof(MdOptions), 0)
         _check(fn(index._h, self._h, source._h, table.ctypes.data if table is not None else None, C.byref(o), stream or None, C.byref(out._h)))
         return out
+
+
+def _runs_strings(cig_off, cigar):
+    """One CIGAR string per entry from the offsets and the runs (len << 4 | op)."""
+    runs = [f"{int(v) >> 4}{CIGAR_OPS[int(v) & 15]}" for v in cigar]
+    return ["".join(runs[int(a):int(b)]) for a, b in zip(cig_off[:-1], cig_off[1:])]
+
+
+class Clips(_Handle):
+    """Owns a kmx_clips handle (kmx_scripts_clip): every entry of a Scripts trimmed to the best-scoring part of its runs, with the
+    score and the letters clipped off either side.  Entry e is entry e of the Scripts."""
+
+    _free = "kmx_clips_free"
+
+    def __init__(self):
+        super().__init__()
+        self._reads = None          # the StrandReads whose stream the call ran on: it must outlive the views
+        self.scripts = None         # the Scripts the clips were made from (set by Scripts.clip)
+
+    def close(self):
+        super().close()
+        self._reads = self.scripts = None
+
+    def counts(self):
+        return self._counts("kmx_clips_counts", "n_sel", "n_ops", "n_clipped", "n_low")
+
+    def host(self):
+        """(score[n_sel] i32, sl u16, sr u16, tl u16, tr u16, nm u16, cflags u8, cig_off[n_sel+1] u64, cigar[n_ops] u32) as numpy
+        copies."""
+        c = self.counts()
+        p = [C.c_void_p() for _ in range(9)]
+        _check(lib().kmx_clips_view(self._h, *[C.byref(x) for x in p]))
+        dt = (np.int32, np.uint16, np.uint16, np.uint16, np.uint16, np.uint16, np.uint8)
+        out = [_view(x.value, c["n_sel"], d) for x, d in zip(p, dt)]
+        out += [_view(p[7].value, c["n_sel"] + 1, np.uint64), _view(p[8].value, c["n_ops"], np.uint32)]
+        return tuple(x.copy() for x in out)
+
+    def device_ptrs(self):
+        """(d_score, d_sl, d_sr, d_tl, d_tr, d_nm, d_cflags, d_cig_off, d_cigar): kmx_clips_view_device."""
+        return self._device_ptrs("kmx_clips_view_device", 9)
+
+    def strings(self):
+        """One CIGAR string per entry with S at the clipped ends, e.g. "1S149=" ("" for an entry without a script)."""
+        h = self.host()
+        return _runs_strings(h[7], h[8])
+
+    def md(self, index, scripts, source, letters, stream=0, md=None):
+        """kmx_clips_md (source: the Alignments the scripts were made from) or kmx_clips_rescues_md (source: the Rescues): the MD
+        string of every clipped entry, over the text interval [start + tl, end - tr).  scripts: the Scripts these clips were made
+        from.  stream=0: the stream that filled the scripts.  Returns an Md (`md` reuses one)."""
+        if isinstance(source, Rescues):
+            fn = lib().kmx_clips_rescues_md
+        elif isinstance(source, Alignments):
+            fn = lib().kmx_clips_md
+        else:
+            raise TypeError("Clips.md: source is an Alignments or a Rescues")
+        table = None if letters is None else _letters_table(letters)
+        out = md or Md()
+        o = MdOptions(C.sizeof(MdOptions), 0)
+        _check(fn(index._h, scripts._h, self._h, source._h, table.ctypes.data if table is not None else None, C.byref(o), stream or None,
+                  C.byref(out._h)))
+        out._reads = self._reads
+        return out
+
+
+def _clip_fields(entry, clips):
+    """entry[nr]: the entry of every public read among those of `clips`, -1 for none -> (tl i64, nm i64, score i64, has bool)"""
+    entry = np.asarray(entry, np.int64)
+    score, _, _, tl, _, nm, _, _, _ = clips.host()
+    has = entry >= 0
+    at = np.where(has, entry, 0)
+    if score.size == 0:
+        zero = np.zeros(entry.size, np.int64)
+        return zero, zero.copy(), zero.copy(), np.zeros(entry.size, bool)
+    return tuple(np.where(has, a.astype(np.int64)[at], 0) for a in (tl, nm, score)) + (has,)
 
 
 def _letters_table(letters):
@@ -883,19 +988,25 @@ class Placements(_Handle):
         _check(lib().kmx_placements_scripts(index._h, reads._h, loci._h, alignments._h, self._h, C.byref(o), C.byref(s._h)))
         return s
 
-    def _per_read(self, scripts, strings):
-        """strings holds one string per entry of `scripts`: the string of every public read's winner, "" where it has none"""
+    def _per_read(self, scripts, strings, none=""):
+        """strings holds one value per entry of `scripts`: the value of every public read's winner, `none` where it has none"""
         strand = self.host(best2=False)[1]
         read_sel_off = scripts.host()[0]
         out = []
         for i, s in enumerate(strand):
             r = 2 * i + int(s)
-            out.append(strings[int(read_sel_off[r])] if s != 255 and read_sel_off[r + 1] > read_sel_off[r] else "")
+            out.append(strings[int(read_sel_off[r])] if s != 255 and read_sel_off[r + 1] > read_sel_off[r] else none)
         return out
 
-    def cigars(self, scripts):
-        """One CIGAR string per public read from the Scripts of scripts(): "" where the read is unplaced."""
-        return self._per_read(scripts, scripts.strings())
+    def clip_fields(self, clips, scripts):
+        """(tl, nm, score, has) per public read from the Clips of scripts().clip(): the text letters clipped off the left, the
+        clipped NM and the score of the read's winner, has False (and zeros) where cigars(scripts) has none.  For sam_lines."""
+        return _clip_fields(self._per_read(scripts, range(scripts.counts()["n_sel"]), -1), clips)
+
+    def cigars(self, scripts, clips=None):
+        """One CIGAR string per public read from the Scripts of scripts(): "" where the read is unplaced.  clips (the Clips of
+        scripts.clip()): the clipped CIGARs, with S."""
+        return self._per_read(scripts, scripts.strings() if clips is None else clips.strings())
 
     def mds(self, md, scripts):
         """One MD string per public read from the Md of scripts.md(): "" where cigars(scripts) has none."""
@@ -937,11 +1048,15 @@ class Placements(_Handle):
         self._reads = None
 
 
-def xa_strings(sec_off, dist, start, ctg, cigars, strand_names="+-", located=None, rname=None):
+def xa_strings(sec_off, dist, start, ctg, cigars, strand_names="+-", located=None, rname=None, shift=None):
     """The XA:Z: value of every public read from the host arrays of a Secondaries and one CIGAR per entry: "" or items
     rname,<strand><pos>,CIGAR,NM; in bwa's form, pos 1-based.  located=(names, ctg_off) with ctg: the entry's contig name and a
-    contig-local pos; otherwise rname and the position in the text.  Pure Python: no device is needed."""
+    contig-local pos; otherwise rname and the position in the text.  shift: the text letters clipped off the left of every entry
+    (the tl of a Clips; dist and cigars then are the clipped nm and strings), added to its position.  Pure Python: no device is
+    needed."""
     sec_off = np.asarray(sec_off, np.uint64)
+    if shift is not None:
+        start = np.asarray(start, np.int64) + np.asarray(shift, np.int64)
     if located is not None and ctg is None:
         raise ValueError("xa: located needs the ctg of a Secondaries made under a contig table")
     if located is None and rname is None:
@@ -1008,12 +1123,18 @@ class Secondaries(_Handle):
         out._reads = self._reads
         return out
 
-    def xa(self, scripts, strand_names="+-", located=None, rname=None):
+    def xa(self, scripts, strand_names="+-", located=None, rname=None, clips=None):
         """One XA:Z: value per public read: "" or items rname,<strand><pos>,CIGAR,NM; in bwa's form (pos 1-based), in the order of
         the entries.  located=(names, ctg_off): the name of the entry's contig and a contig-local pos (the handle must carry ctg);
-        otherwise `rname` names the one reference.  scripts: the Scripts of scripts()."""
+        otherwise `rname` names the one reference.  scripts: the Scripts of scripts().  clips (the Clips of scripts.clip()): every
+        entry's position is shifted by its tl, and its CIGAR and NM are the clipped ones."""
         sec_off, _, dist, start, _, ctg, _ = self.host()
-        return xa_strings(sec_off, dist, start, ctg, self.cigars(scripts), strand_names, located, rname)
+        if clips is None:
+            return xa_strings(sec_off, dist, start, ctg, self.cigars(scripts), strand_names, located, rname)
+        if clips.counts()["n_sel"] != dist.size:
+            raise ValueError("xa: the clips are not those of these entries")
+        h = clips.host()
+        return xa_strings(sec_off, h[5], start, ctg, _runs_strings(h[7], h[8]), strand_names, located, rname, shift=h[3])
 
     def close(self):
         super().close()
@@ -1124,23 +1245,29 @@ class Rescues(_Handle):
         _check(lib().kmx_rescues_scripts(index._h, reads._h, self._h, C.byref(o), C.byref(s._h)))
         return s
 
-    def _per_read(self, scripts, strings):
-        """strings holds one string per entry of `scripts`: the string of every rescued public read, "" for every other"""
+    def _per_read(self, scripts, strings, none=""):
+        """strings holds one value per entry of `scripts`: the value of every rescued public read, `none` for every other"""
         job_off, read, _, _, _, _, _, status = self.host()
         read_sel_off = scripts.host()[0]
-        out = [""] * ((job_off.size - 1) // 2)
+        out = [none] * ((job_off.size - 1) // 2)
         for r, st in zip(read, status):
             if st == RESCUE_TAKEN and read_sel_off[int(r) + 1] > read_sel_off[int(r)]:
                 out[int(r) // 2] = strings[int(read_sel_off[int(r)])]
         return out
 
-    def cigars(self, scripts):
-        """One CIGAR string per public read from the Scripts of scripts(): "" where the read was not rescued."""
-        return self._per_read(scripts, scripts.strings())
+    def cigars(self, scripts, clips=None):
+        """One CIGAR string per public read from the Scripts of scripts(): "" where the read was not rescued.  clips (the Clips of
+        scripts.clip()): the clipped CIGARs, with S."""
+        return self._per_read(scripts, scripts.strings() if clips is None else clips.strings())
 
     def mds(self, md, scripts):
         """One MD string per public read from the Md of scripts.md(): "" where cigars(scripts) has none."""
         return self._per_read(scripts, md.strings())
+
+    def clip_fields(self, clips, scripts):
+        """(tl, nm, score, has) per public read from the Clips of scripts().clip(): has False (and zeros) where the read was not
+        rescued.  For sam_lines, as the second of a tuple."""
+        return _clip_fields(self._per_read(scripts, range(scripts.counts()["n_sel"]), -1), clips)
 
     def close(self):
         super().close()
@@ -1209,7 +1336,7 @@ def sam_header(names, ctg_off):
 
 
 def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements_host, cigars, mds, mapq, pairs_host=None, located_host=None,
-              xa=None):
+              xa=None, clip_fields=None):
     """One SAM line (no newline) per public read from host arrays: the reads (ranks, roff), the rank -> letter table, the rank
     complement table, Placements.host(), the CIGAR and MD strings per read (Placements.cigars / .mds; a tuple of two lists, the
     placements' and the rescue's, gives a rescued read those of the rescue), Mapq.host() and, for paired reads, Pairs.host().
@@ -1219,7 +1346,11 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
     coordinates: rname then is a sequence of one name per contig, RNAME the read's contig (an unplaced read with a placed mate takes
     the mate's), POS and PNEXT are contig-local, RNEXT is = for the same contig and the mate's contig name otherwise.  xa
     (Secondaries.xa(): one string per read) appends XA:Z:<string> behind MD:Z: to every placed read whose string is not empty; None
-    leaves the lines as they were.  Pure Python / numpy: no device is needed."""
+    leaves the lines as they were.  clip_fields (Placements.clip_fields(); a tuple of two, the placements' and the rescue's, like
+    cigars) writes soft-clipped records: cigars and mds then are the clipped ones (Clips.strings(), Clips.md()), a read's POS is
+    start + tl, and so are its contig-local POS and its mate's PNEXT, NM:i: is the clipped nm, and AS:i:<score> follows MD:Z:.  TLEN
+    stays the pair fold's, measured between the UNCLIPPED outer ends.  None leaves every line as it was.  Pure Python / numpy: no
+    device is needed."""
     table = _letters_table(letters)
     comp = np.ascontiguousarray(complement, np.uint8)
     if table.size < sigma or comp.size < sigma:
@@ -1235,6 +1366,19 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
     if xa is not None and len(xa) != nr:
         raise ValueError("sam_lines: xa disagrees in the number of reads")
     placed = strand != 255
+    shift = nm = score = has = None
+    if clip_fields is not None:
+        groups = clip_fields if len(clip_fields) == 2 else (clip_fields,)
+        if any(len(g) != 4 or any(np.asarray(a).size != nr for a in g) for g in groups):
+            raise ValueError("sam_lines: clip_fields is (tl, nm, score, has) per read, or a tuple of two of them")
+        shift, nm, score, has = (np.asarray(a) for a in groups[0])
+        for g in groups[1:]:                                   # a rescued read takes the rescue's
+            take = ~has & np.asarray(g[3], bool)
+            shift, nm, score = (np.where(take, np.asarray(b), a) for a, b in zip((shift, nm, score), g[:3]))
+            has = has | take
+        has = np.asarray(has, bool) & placed
+        shift = np.where(has, shift, 0).astype(np.int64)
+        start = (start.astype(np.int64) + shift).astype(np.uint32)
     if pairs_host is not None:
         flag, pos, pnext, tlen = sam_pair_fields(strand, start, pairs_host[0], pairs_host[1])
     else:
@@ -1250,7 +1394,7 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
             raise ValueError("sam_lines: a placed read has no contig (n_mismatched of the Located is not 0)")
         if (ctg[placed] >= len(rname)).any():
             raise ValueError("sam_lines: a contig without a name")
-        own = np.where(placed, lpos.astype(np.int64) + 1, 0)
+        own = np.where(placed, lpos.astype(np.int64) + 1 + (shift if shift is not None else 0), 0)
         if pairs_host is not None:
             mate = np.arange(nr) ^ 1
             rc = np.where(placed, ctg, ctg[mate])              # an unplaced read takes its mate's contig and POS
@@ -1274,7 +1418,9 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
                   (cigars[i] or "*") if placed[i] else "*", ("=" if pnext[i] else "*") if names is None else nextname[i], str(int(pnext[i])),
                   str(int(tlen[i])), seq, "*"]
         if placed[i]:
-            fields += [f"NM:i:{int(dist[i])}", f"MD:Z:{mds[i]}"]
+            fields += [f"NM:i:{int(nm[i]) if has is not None and has[i] else int(dist[i])}", f"MD:Z:{mds[i]}"]
+            if has is not None and has[i]:
+                fields.append(f"AS:i:{int(score[i])}")
             if xa is not None and xa[i]:
                 fields.append(f"XA:Z:{xa[i]}")
         lines.append("\t".join(fields))
@@ -1574,21 +1720,26 @@ class Index:
         return s
 
     def map_reads_strands(self, ranks, roff, w, complement, stride=1, band=0, min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False,
-                          tags=False, letters=None, secondaries=0):
+                          tags=False, letters=None, secondaries=0, clip=None):
         """map_reads on both strands: kmx_reads_strands, kmx_search_windows_device, kmx_windows_vote, kmx_loci_align_device and
         kmx_alignments_fold_strands in a row, all on the stream of the StrandReads.  Returns (StrandReads, Loci, Alignments,
         Placements): the loci and alignments are those of the doubled batch (internal read 2i is read i, 2i + 1 its reverse
         complement), the placements one per read.  scripts=True appends kmx_placements_scripts (the CIGARs of the winners).
         tags=True (needs `letters`, the rank -> letter table; implies scripts) appends a SamTags(mapq, md, None, None):
         kmx_placements_mapq and kmx_scripts_md.  secondaries=N > 0 appends, behind everything else, the Secondaries of
-        kmx_placements_secondaries with max_secondary = N and no max_delta."""
+        kmx_placements_secondaries with max_secondary = N and no max_delta.  clip (a dict of the scoring arguments of Scripts.clip,
+        {} for the defaults; needs scripts=True) appends, as the very last element, the Clips of kmx_scripts_clip over the scripts;
+        with tags=True the Md then is kmx_clips_md, that of the clipped entries."""
         if tags and letters is None:
             raise ValueError("map_reads_strands: tags=True needs letters")
+        if clip is not None and not scripts:
+            raise ValueError("map_reads_strands: clip needs scripts=True")
         if max_span is None:
             max_span = 0xFFFFFFFF
         if secondaries:
-            out = self.map_reads_strands(ranks, roff, w, complement, stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags, letters)
-            return self._with_secondaries(out, secondaries)
+            out = self.map_reads_strands(ranks, roff, w, complement, stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags, letters,
+                                         clip=clip)
+            return self._with_secondaries(out, secondaries, 0 if clip is None else 1)
         opened = []
         try:
             reads = self.strand_reads(ranks, roff, complement)
@@ -1609,24 +1760,32 @@ class Index:
                 return reads, loci, al, pl
             sc = pl.scripts(self, reads, loci, al)
             opened.append(sc)
+            last = ()
+            if clip is not None:
+                cl = sc.clip(**clip)
+                cl._reads = reads
+                opened.append(cl)
+                last = (cl,)
             if not tags:
-                return reads, loci, al, pl, sc
+                return (reads, loci, al, pl, sc) + last
             mq = pl.mapq(max_edits)
             opened.append(mq)
-            md = sc.md(self, al, letters)
+            md = sc.md(self, al, letters) if clip is None else cl.md(self, sc, al, letters)
             md._reads = reads
-            return reads, loci, al, pl, sc, SamTags(mq, md, None, None)
+            return (reads, loci, al, pl, sc, SamTags(mq, md, None, None)) + last
         except Exception:
             for h in reversed(opened):
                 h.close()
             raise
 
     @staticmethod
-    def _with_secondaries(out, n):
+    def _with_secondaries(out, n, n_clips=0):
         """out: what a chain call returns, (StrandReads, Loci, Alignments, Placements, ...) with the placements final; the same with
-        the Secondaries of kmx_placements_secondaries (max_secondary = n, no max_delta) appended."""
+        the Secondaries of kmx_placements_secondaries (max_secondary = n, no max_delta) appended, in front of the last n_clips
+        elements (the Clips, which stay last)."""
         try:
-            return out + (out[3].secondaries(out[1], out[2], n),)
+            cut = len(out) - n_clips
+            return out[:cut] + (out[3].secondaries(out[1], out[2], n),) + out[cut:]
         except Exception:
             for h in reversed(out):
                 for x in (h if isinstance(h, SamTags) else (h,)):
@@ -1636,7 +1795,7 @@ class Index:
 
     def map_pairs(self, ranks, roff, w, complement, min_insert, max_insert, orientation=PAIR_FR, unpaired_penalty=None, stride=1, band=0,
                   min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False, rescue=False, rescue_edits=None, rescue_discordant=False,
-                  tags=False, letters=None, secondaries=0):
+                  tags=False, letters=None, secondaries=0, clip=None):
         """map_reads_strands for paired reads: the reads are interleaved mates (read 2p is mate 1 of pair p, read 2p + 1 its mate 2, so
         their number is even), and kmx_alignments_fold_pairs stands in the fold's place.  Returns (StrandReads, Loci, Alignments,
         Placements, Pairs); scripts=True appends kmx_placements_scripts (the CIGARs of the chosen loci).  rescue=True runs
@@ -1646,13 +1805,19 @@ class Index:
         rescue_md): kmx_placements_mapq with the pairs (its budget the larger of max_edits and rescue_edits), kmx_scripts_md, and
         after a rescue kmx_rescues_scripts and kmx_rescues_md (else None).  secondaries=N > 0 appends, behind everything else, the
         Secondaries of kmx_placements_secondaries (max_secondary = N, no max_delta) on the placements as they then are: after the
-        rescue, so that the primaries are final."""
+        rescue, so that the primaries are final.  clip (a dict of the scoring arguments of Scripts.clip, {} for the defaults; needs
+        scripts=True) appends, as the very last elements, the Clips of kmx_scripts_clip over the scripts and, with rescue=True, the
+        Clips of the rescued mates' scripts.  Clips.scripts is the Scripts they were made from: SamTags.rescue_scripts with tags=True;
+        without tags that Scripts is returned nowhere else, Clips.close() does not close it, and the caller closes it;
+        with tags=True md and rescue_md then are kmx_clips_md and kmx_clips_rescues_md, those of the clipped entries."""
         if tags and letters is None:
             raise ValueError("map_pairs: tags=True needs letters")
+        if clip is not None and not scripts:
+            raise ValueError("map_pairs: clip needs scripts=True")
         if secondaries:
             out = self.map_pairs(ranks, roff, w, complement, min_insert, max_insert, orientation, unpaired_penalty, stride, band, min_votes, max_occ,
-                                 max_edits, max_span, scripts, rescue, rescue_edits, rescue_discordant, tags, letters)
-            return self._with_secondaries(out, secondaries)
+                                 max_edits, max_span, scripts, rescue, rescue_edits, rescue_discordant, tags, letters, clip=clip)
+            return self._with_secondaries(out, secondaries, 0 if clip is None else 2 if rescue else 1)
         roff = np.ascontiguousarray(roff, np.uint64)
         if (roff.size - 1) % 2:
             raise ValueError("map_pairs: an odd number of reads; the reads are interleaved mates")
@@ -1688,21 +1853,33 @@ class Index:
                 out.append(sc)
             if res is not None:
                 out.append(res)
+            cl = rcl = rsc = None
+            if clip is not None:
+                cl = sc.clip(**clip)
+                cl._reads = reads
+                opened.append(cl)
+                if res is not None:
+                    rsc = res.scripts(self, reads)
+                    opened.append(rsc)
+                    rcl = rsc.clip(**clip)
+                    rcl._reads = reads
+                    opened.append(rcl)
             if tags:
                 budget = max_edits if not rescue or rescue_edits is None else max(max_edits, rescue_edits)
                 mq = pl.mapq(budget, pairs)
                 opened.append(mq)
-                md = sc.md(self, al, letters)
+                md = sc.md(self, al, letters) if cl is None else cl.md(self, sc, al, letters)
                 md._reads = reads
                 opened.append(md)
-                rsc = rmd = None
+                rmd = None
                 if res is not None:
-                    rsc = res.scripts(self, reads)
-                    opened.append(rsc)
-                    rmd = rsc.md(self, res, letters)
+                    if rsc is None:
+                        rsc = res.scripts(self, reads)
+                        opened.append(rsc)
+                    rmd = rsc.md(self, res, letters) if rcl is None else rcl.md(self, rsc, res, letters)
                     rmd._reads = reads
                 out.append(SamTags(mq, md, rsc, rmd))
-            return tuple(out)
+            return tuple(out) + tuple(x for x in (cl, rcl) if x is not None)
         except Exception:
             for h in reversed(opened):
                 h.close()

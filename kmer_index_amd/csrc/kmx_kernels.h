@@ -75,6 +75,7 @@ hipError_t build_sparse_element(hipStream_t s, const uint8_t* d_text, uint64_t n
 // ping-pong with (keys_b, vals_b); *in_b: the sorted pairs are in the b arrays.  Synchronises the stream.
 hipError_t sort_pairs_u64(hipStream_t s, uint64_t* keys_a, uint32_t* vals_a, uint64_t* keys_b, uint32_t* vals_b, uint64_t n, uint32_t key_bits,
                           bool* in_b);
+// the exclusive prefix sum of in[0 .. n): `out` holds n + 1 entries, because out[n] receives the total (as *total_out does)
 void launch_scan(hipStream_t s, const uint32_t* in, uint64_t n, uint64_t* bsum, uint64_t* out,
                  unsigned long long* total_out);
 // k_fill build variants: e = output slots per thread (tile = 256 * e), nt = non-temporal stores

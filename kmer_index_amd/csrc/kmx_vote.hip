@@ -398,7 +398,7 @@ kmx_status vote_large(const kmx::WindowsAccess& W, const VoteIn& A, kmx_loci* L,
     hipStream_t s = W.stream;
     const uint64_t nr = A.nr;
     unsigned long long* d_total = L->ctr.as<unsigned long long>() + CTR_COUNT;
-    TRY_HIP(L->lvote_off.ensure(nr * 8));
+    TRY_HIP(L->lvote_off.ensure((nr + 1) * 8));
     TRY_HIP(L->ka.ensure((n_v + 1) * 8));
     TRY_HIP(L->kb.ensure((n_v + 1) * 8));
     TRY_HIP(L->va.ensure(n_v * 4 + 16));
@@ -465,7 +465,7 @@ kmx_status vote_run(const kmx::WindowsAccess& W, const kmx_vote_options& o, kmx_
     const uint32_t cap = small_cap(), cap_a = std::min(cap, kCapA);
     for (Buf* b : {&L->vcnt, &L->smax, &L->lcnt, &L->lcount}) TRY_HIP(b->ensure(nr * 4 + 16));
     TRY_HIP(L->cls.ensure(nr));
-    TRY_HIP(L->sc_off.ensure(nr * 8));
+    TRY_HIP(L->sc_off.ensure((nr + 1) * 8));
     TRY_HIP(L->bsum.ensure(kmx::scan_blocks(nr) * 8 + 16));
     TRY_HIP(L->ctr.ensure((CTR_COUNT + 1) * 8));
     unsigned long long* ctr = L->ctr.as<unsigned long long>();

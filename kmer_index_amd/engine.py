@@ -4,6 +4,7 @@ Every search goes through libkmx.so (hand-written gfx950 kernels).  There is no 
 CPU search path in this package: when the library or a device is missing, calls raise.
 """
 import collections
+import contextlib
 import ctypes as C
 import os
 
@@ -33,38 +34,6 @@ RESCUE_NONE, RESCUE_FOUND, RESCUE_CONCORDANT, RESCUE_TAKEN = 0, 1, 2, 3
 LOCATE_MATES, NO_CONTIG = 1, 0xFFFFFFFF
 SECONDARY_MAX, SECONDARY_NO_DELTA = 32, 0xFFFFFFFF
 CLIP_LOW = 1
-
-# every symbol include/kmx.h declares
-EXPORTS = [
-    "kmx_index_build", "kmx_index_free", "kmx_index_save", "kmx_index_load", "kmx_index_info", "kmx_index_memory", "kmx_index_arena_host", "kmx_index_extend_query_size_range", "kmx_choose_best_k", "kmx_plan", "kmx_plan_engine", "kmx_fast_pow",
-    "kmx_search_batch", "kmx_search_batch_device", "kmx_result_counts", "kmx_result_view_device",
-    "kmx_result_view", "kmx_result_masks", "kmx_result_free", "kmx_stats_enable", "kmx_stats_get",
-    "kmx_stats_reset", "kmx_debug_words", "kmx_last_error", "kmx_status_string", "kmx_version",
-    "kmx_index_devices", "kmx_result_parts", "kmx_result_part_view_device",
-    "kmx_index_bucket_host", "kmx_index_levels", "kmx_result_gather_device",
-    "kmx_search_approx", "kmx_approx_counts", "kmx_approx_view", "kmx_approx_free", "kmx_index_text",
-    "kmx_approx_lengths", "kmx_search_approx_strands", "kmx_approx_strands",
-    "kmx_search_approx_opts", "kmx_approx_found",
-    "kmx_index_paths", "kmx_result_paths",
-    "kmx_search_windows", "kmx_search_windows_device", "kmx_result_window_offsets",
-    "kmx_windows_vote", "kmx_loci_counts", "kmx_loci_view", "kmx_loci_view_device", "kmx_loci_free",
-    "kmx_loci_align", "kmx_loci_align_device", "kmx_alignments_counts", "kmx_alignments_view", "kmx_alignments_view_device",
-    "kmx_alignments_free",
-    "kmx_alignments_scripts", "kmx_alignments_scripts_device", "kmx_scripts_counts", "kmx_scripts_view", "kmx_scripts_view_device",
-    "kmx_scripts_free",
-    "kmx_reads_strands", "kmx_reads_strands_device", "kmx_strand_reads_view_device", "kmx_strand_reads_free",
-    "kmx_alignments_fold_strands", "kmx_placements_counts", "kmx_placements_view", "kmx_placements_view_device", "kmx_placements_free",
-    "kmx_placements_scripts",
-    "kmx_alignments_fold_pairs", "kmx_pairs_counts", "kmx_pairs_view", "kmx_pairs_view_device", "kmx_pairs_free",
-    "kmx_pairs_rescue", "kmx_rescues_counts", "kmx_rescues_view", "kmx_rescues_view_device", "kmx_rescues_scripts", "kmx_rescues_free",
-    "kmx_scripts_md", "kmx_rescues_md", "kmx_md_counts", "kmx_md_view", "kmx_md_view_device", "kmx_md_free",
-    "kmx_placements_mapq", "kmx_mapq_counts", "kmx_mapq_view", "kmx_mapq_view_device", "kmx_mapq_free",
-    "kmx_index_set_contigs", "kmx_index_contigs", "kmx_alignments_contigs_view", "kmx_alignments_contigs_view_device",
-    "kmx_placements_locate", "kmx_located_counts", "kmx_located_view", "kmx_located_view_device", "kmx_located_free",
-    "kmx_placements_secondaries", "kmx_secondaries_counts", "kmx_secondaries_view", "kmx_secondaries_view_device", "kmx_secondaries_scripts",
-    "kmx_secondaries_md", "kmx_secondaries_free",
-    "kmx_scripts_clip", "kmx_clips_counts", "kmx_clips_view", "kmx_clips_view_device", "kmx_clips_md", "kmx_clips_rescues_md", "kmx_clips_free",
-]
 
 
 class KmxError(RuntimeError):
@@ -155,6 +124,139 @@ class ResultPathInfo(C.Structure):
                 ("prefix_long", C.c_uint32), ("prefix_large_chunks", C.c_uint32), ("prefix_large_elems", C.c_uint64)]
 
 
+vp, u64, u32, i32, st, P = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32, C.c_int, C.POINTER
+
+# every symbol include/kmx.h declares: (restype, argtypes); st is a kmx_status.  lib() applies it, tests/test_capi_cpu.py holds the
+# number of argtypes against the header's prototypes.
+SIGNATURES = {
+    "kmx_index_build": (st, [vp, u64, u32, vp, u32, P(Options), P(vp)]),
+    "kmx_index_free": (None, [vp]),
+    "kmx_index_save": (st, [vp, C.c_char_p]),
+    "kmx_index_load": (st, [C.c_char_p, P(Options), P(vp)]),
+    "kmx_index_info": (st, [vp, P(u64), P(u32), P(u32), vp, vp, P(u64)]),
+    "kmx_index_memory": (st, [vp] + [P(u64)] * 5),
+    "kmx_index_arena_host": (st, [vp, P(vp), P(u64)]),
+    "kmx_index_extend_query_size_range": (st, [vp, u32]),
+    "kmx_index_devices": (st, [vp, P(u32), vp]),
+    "kmx_index_bucket_host": (st, [vp, u32, vp, P(vp), P(u32)]),
+    "kmx_index_levels": (st, [vp, vp]),
+    "kmx_index_paths": (st, [vp, P(IndexPathInfo)]),
+    "kmx_index_text": (st, [vp, vp, u64, P(u64)]),
+    "kmx_index_set_contigs": (st, [vp, vp, u64]),
+    "kmx_index_contigs": (st, [vp, P(u64), vp, u64]),
+    "kmx_choose_best_k": (st, [vp, u64, u32, vp]),
+    "kmx_plan": (st, [vp, u32, u32, vp, vp, vp, u64, P(u64)]),
+    "kmx_plan_engine": (st, [vp, u32, u32, u32, vp]),
+    "kmx_fast_pow": (u64, [u64, C.c_uint8]),
+    "kmx_stats_enable": (st, [vp, C.c_int]),
+    "kmx_stats_get": (st, [vp, P(KernelStat), P(u32)]),
+    "kmx_stats_reset": (st, [vp]),
+    "kmx_debug_words": (st, [vp, vp]),
+    "kmx_last_error": (C.c_char_p, []),
+    "kmx_status_string": (C.c_char_p, [C.c_int]),
+    "kmx_version": (u32, []),
+    # exact search
+    "kmx_search_batch": (st, [vp, vp, vp, u64, u32, P(vp)]),
+    "kmx_search_batch_device": (st, [vp, vp, vp, u64, u32, vp, P(vp)]),
+    "kmx_search_windows": (st, [vp, vp, vp, u64, P(WindowOptions), P(vp)]),
+    "kmx_search_windows_device": (st, [vp, vp, vp, u64, P(WindowOptions), vp, P(vp)]),
+    "kmx_result_counts": (st, [vp] + [P(u64)] * 6),
+    "kmx_result_view": (st, [vp] + [P(vp)] * 4),
+    "kmx_result_view_device": (st, [vp] + [P(vp)] * 3),
+    "kmx_result_masks": (st, [vp] + [P(vp)] * 4),
+    "kmx_result_parts": (st, [vp, P(u32)]),
+    "kmx_result_part_view_device": (st, [vp, u32, P(i32), P(u64), P(u64), P(vp), P(vp), P(vp)]),
+    "kmx_result_gather_device": (st, [vp, i32, P(vp), P(vp), P(vp)]),
+    "kmx_result_paths": (st, [vp, P(ResultPathInfo)]),
+    "kmx_result_window_offsets": (st, [vp, P(vp), P(vp), P(u64)]),
+    "kmx_result_free": (None, [vp]),
+    # approximate search
+    "kmx_search_approx": (st, [vp, vp, vp, u64, u32, u32, P(vp)]),
+    "kmx_search_approx_strands": (st, [vp, vp, vp, u64, u32, u32, vp, P(vp)]),
+    "kmx_search_approx_opts": (st, [vp, vp, vp, u64, P(ApproxOptions), P(vp)]),
+    "kmx_approx_counts": (st, [vp, P(u64), P(u64), P(u64), P(u32)]),
+    "kmx_approx_view": (st, [vp] + [P(vp)] * 4),
+    "kmx_approx_lengths": (st, [vp, P(vp)]),
+    "kmx_approx_strands": (st, [vp, P(vp)]),
+    "kmx_approx_found": (st, [vp, P(vp)]),
+    "kmx_approx_free": (None, [vp]),
+    # the read-mapping chain: vote, align, scripts
+    "kmx_windows_vote": (st, [vp, P(VoteOptions), P(vp)]),
+    "kmx_loci_counts": (st, [vp] + [P(u64)] * 5),
+    "kmx_loci_view": (st, [vp] + [P(vp)] * 5),
+    "kmx_loci_view_device": (st, [vp] + [P(vp)] * 5),
+    "kmx_loci_free": (None, [vp]),
+    "kmx_loci_align": (st, [vp, vp, vp, vp, u64, P(AlignOptions), P(vp)]),
+    "kmx_loci_align_device": (st, [vp, vp, vp, vp, u64, P(AlignOptions), vp, P(vp)]),
+    "kmx_alignments_counts": (st, [vp] + [P(u64)] * 4),
+    "kmx_alignments_view": (st, [vp] + [P(vp)] * 5),
+    "kmx_alignments_view_device": (st, [vp] + [P(vp)] * 5),
+    "kmx_alignments_contigs_view": (st, [vp, P(vp), P(u64)]),
+    "kmx_alignments_contigs_view_device": (st, [vp, P(vp), P(u64)]),
+    "kmx_alignments_free": (None, [vp]),
+    "kmx_alignments_scripts": (st, [vp, vp, vp, vp, vp, u64, P(ScriptOptions), P(vp)]),
+    "kmx_alignments_scripts_device": (st, [vp, vp, vp, vp, vp, u64, P(ScriptOptions), vp, P(vp)]),
+    "kmx_scripts_counts": (st, [vp] + [P(u64)] * 4),
+    "kmx_scripts_view": (st, [vp] + [P(vp)] * 4),
+    "kmx_scripts_view_device": (st, [vp] + [P(vp)] * 4),
+    "kmx_scripts_free": (None, [vp]),
+    # both strands, pairs, rescue
+    "kmx_reads_strands": (st, [vp, vp, vp, u64, vp, P(vp)]),
+    "kmx_reads_strands_device": (st, [vp, vp, vp, u64, vp, vp, P(vp)]),
+    "kmx_strand_reads_view_device": (st, [vp, P(vp), P(vp), P(u64), P(vp)]),
+    "kmx_strand_reads_free": (None, [vp]),
+    "kmx_alignments_fold_strands": (st, [vp, vp, P(FoldOptions), vp, P(vp)]),
+    "kmx_placements_counts": (st, [vp] + [P(u64)] * 4),
+    "kmx_placements_view": (st, [vp] + [P(vp)] * 7),
+    "kmx_placements_view_device": (st, [vp] + [P(vp)] * 7),
+    "kmx_placements_free": (None, [vp]),
+    "kmx_placements_scripts": (st, [vp, vp, vp, vp, vp, P(ScriptOptions), P(vp)]),
+    "kmx_alignments_fold_pairs": (st, [vp, vp, P(PairOptions), vp, P(vp), P(vp)]),
+    "kmx_pairs_counts": (st, [vp] + [P(u64)] * 6),
+    "kmx_pairs_view": (st, [vp] + [P(vp)] * 4),
+    "kmx_pairs_view_device": (st, [vp] + [P(vp)] * 4),
+    "kmx_pairs_free": (None, [vp]),
+    "kmx_pairs_rescue": (st, [vp, vp, vp, vp, P(RescueOptions), vp, vp, P(vp)]),
+    "kmx_rescues_counts": (st, [vp] + [P(u64)] * 5),
+    "kmx_rescues_view": (st, [vp] + [P(vp)] * 8),
+    "kmx_rescues_view_device": (st, [vp] + [P(vp)] * 8),
+    "kmx_rescues_scripts": (st, [vp, vp, vp, P(ScriptOptions), P(vp)]),
+    "kmx_rescues_free": (None, [vp]),
+    # SAM tags, contigs, secondaries, clips
+    "kmx_scripts_md": (st, [vp, vp, vp, vp, P(MdOptions), vp, P(vp)]),
+    "kmx_rescues_md": (st, [vp, vp, vp, vp, P(MdOptions), vp, P(vp)]),
+    "kmx_md_counts": (st, [vp] + [P(u64)] * 3),
+    "kmx_md_view": (st, [vp] + [P(vp)] * 2),
+    "kmx_md_view_device": (st, [vp] + [P(vp)] * 2),
+    "kmx_md_free": (None, [vp]),
+    "kmx_placements_mapq": (st, [vp, vp, P(MapqOptions), vp, P(vp)]),
+    "kmx_mapq_counts": (st, [vp] + [P(u64)] * 3),
+    "kmx_mapq_view": (st, [vp, P(vp)]),
+    "kmx_mapq_view_device": (st, [vp, P(vp)]),
+    "kmx_mapq_free": (None, [vp]),
+    "kmx_placements_locate": (st, [vp, vp, vp, P(LocateOptions), vp, P(vp)]),
+    "kmx_located_counts": (st, [vp] + [P(u64)] * 3),
+    "kmx_located_view": (st, [vp] + [P(vp)] * 2),
+    "kmx_located_view_device": (st, [vp] + [P(vp)] * 2),
+    "kmx_located_free": (None, [vp]),
+    "kmx_placements_secondaries": (st, [vp, vp, vp, P(SecondaryOptions), vp, P(vp)]),
+    "kmx_secondaries_counts": (st, [vp] + [P(u64)] * 4),
+    "kmx_secondaries_view": (st, [vp] + [P(vp)] * 7),
+    "kmx_secondaries_view_device": (st, [vp] + [P(vp)] * 7),
+    "kmx_secondaries_scripts": (st, [vp, vp, vp, P(ScriptOptions), P(vp)]),
+    "kmx_secondaries_md": (st, [vp, vp, vp, vp, P(MdOptions), vp, P(vp)]),
+    "kmx_secondaries_free": (None, [vp]),
+    "kmx_scripts_clip": (st, [vp, P(ClipOptions), vp, P(vp)]),
+    "kmx_clips_counts": (st, [vp] + [P(u64)] * 4),
+    "kmx_clips_view": (st, [vp] + [P(vp)] * 9),
+    "kmx_clips_view_device": (st, [vp] + [P(vp)] * 9),
+    "kmx_clips_md": (st, [vp, vp, vp, vp, vp, P(MdOptions), vp, P(vp)]),
+    "kmx_clips_rescues_md": (st, [vp, vp, vp, vp, vp, P(MdOptions), vp, P(vp)]),
+    "kmx_clips_free": (None, [vp]),
+}
+EXPORTS = list(SIGNATURES)
+
+
 _lib = None
 
 
@@ -172,229 +274,9 @@ def lib():
         if not os.path.exists(path):
             raise RuntimeError("libkmx.so is missing and could not be built; the engine has no fallback")
         L = C.CDLL(path)
-        vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
-        P = C.POINTER
-        L.kmx_index_build.restype = C.c_int
-        L.kmx_index_build.argtypes = [vp, u64, u32, vp, u32, P(Options), P(vp)]
-        L.kmx_index_free.argtypes = [vp]
-        L.kmx_index_save.restype = C.c_int
-        L.kmx_index_save.argtypes = [vp, C.c_char_p]
-        L.kmx_index_load.restype = C.c_int
-        L.kmx_index_load.argtypes = [C.c_char_p, P(Options), P(vp)]
-        L.kmx_index_info.restype = C.c_int
-        L.kmx_index_info.argtypes = [vp, P(u64), P(u32), P(u32), vp, vp, P(u64)]
-        L.kmx_index_memory.restype = C.c_int
-        L.kmx_index_memory.argtypes = [vp, P(u64), P(u64), P(u64), P(u64), P(u64)]
-        L.kmx_index_arena_host.restype = C.c_int
-        L.kmx_index_arena_host.argtypes = [vp, P(vp), P(u64)]
-        L.kmx_index_extend_query_size_range.restype = C.c_int
-        L.kmx_index_extend_query_size_range.argtypes = [vp, u32]
-        L.kmx_choose_best_k.restype = C.c_int
-        L.kmx_choose_best_k.argtypes = [vp, u64, u32, vp]
-        L.kmx_plan.restype = C.c_int
-        L.kmx_plan_engine.restype = C.c_int
-        L.kmx_plan_engine.argtypes = [vp, u32, u32, u32, vp]
-        L.kmx_plan.argtypes = [vp, u32, u32, vp, vp, vp, u64, P(u64)]
-        L.kmx_fast_pow.restype = u64
-        L.kmx_fast_pow.argtypes = [u64, C.c_uint8]
-        L.kmx_search_batch.restype = C.c_int
-        L.kmx_search_batch.argtypes = [vp, vp, vp, u64, u32, P(vp)]
-        L.kmx_search_batch_device.restype = C.c_int
-        L.kmx_search_batch_device.argtypes = [vp, vp, vp, u64, u32, vp, P(vp)]
-        L.kmx_result_counts.restype = C.c_int
-        L.kmx_result_counts.argtypes = [vp] + [P(u64)] * 6
-        L.kmx_result_view_device.restype = C.c_int
-        L.kmx_result_view_device.argtypes = [vp, P(vp), P(vp), P(vp)]
-        L.kmx_result_view.restype = C.c_int
-        L.kmx_result_view.argtypes = [vp, P(vp), P(vp), P(vp), P(vp)]
-        L.kmx_result_masks.restype = C.c_int
-        L.kmx_result_masks.argtypes = [vp, P(vp), P(vp), P(vp), P(vp)]
-        L.kmx_result_free.argtypes = [vp]
-        L.kmx_index_devices.restype = C.c_int
-        L.kmx_index_devices.argtypes = [vp, P(u32), vp]
-        L.kmx_result_parts.restype = C.c_int
-        L.kmx_result_parts.argtypes = [vp, P(u32)]
-        L.kmx_result_part_view_device.restype = C.c_int
-        L.kmx_result_part_view_device.argtypes = [vp, u32, P(C.c_int32), P(u64), P(u64), P(vp), P(vp), P(vp)]
-        L.kmx_index_bucket_host.restype = C.c_int
-        L.kmx_index_bucket_host.argtypes = [vp, u32, vp, P(vp), P(u32)]
-        L.kmx_index_levels.restype = C.c_int
-        L.kmx_index_levels.argtypes = [vp, vp]
-        L.kmx_result_gather_device.restype = C.c_int
-        L.kmx_result_gather_device.argtypes = [vp, C.c_int32, P(vp), P(vp), P(vp)]
-        L.kmx_search_approx.restype = C.c_int
-        L.kmx_search_approx.argtypes = [vp, vp, vp, u64, u32, u32, P(vp)]
-        L.kmx_approx_counts.restype = C.c_int
-        L.kmx_approx_counts.argtypes = [vp, P(u64), P(u64), P(u64), P(u32)]
-        L.kmx_approx_view.restype = C.c_int
-        L.kmx_approx_view.argtypes = [vp, P(vp), P(vp), P(vp), P(vp)]
-        L.kmx_approx_lengths.restype = C.c_int
-        L.kmx_approx_lengths.argtypes = [vp, P(vp)]
-        L.kmx_approx_free.argtypes = [vp]
-        L.kmx_search_approx_strands.restype = C.c_int
-        L.kmx_search_approx_strands.argtypes = [vp, vp, vp, u64, u32, u32, vp, P(vp)]
-        L.kmx_approx_strands.restype = C.c_int
-        L.kmx_approx_strands.argtypes = [vp, P(vp)]
-        L.kmx_search_approx_opts.restype = C.c_int
-        L.kmx_search_approx_opts.argtypes = [vp, vp, vp, u64, P(ApproxOptions), P(vp)]
-        L.kmx_approx_found.restype = C.c_int
-        L.kmx_approx_found.argtypes = [vp, P(vp)]
-        L.kmx_index_paths.restype = C.c_int
-        L.kmx_index_paths.argtypes = [vp, P(IndexPathInfo)]
-        L.kmx_result_paths.restype = C.c_int
-        L.kmx_result_paths.argtypes = [vp, P(ResultPathInfo)]
-        L.kmx_search_windows.restype = C.c_int
-        L.kmx_search_windows.argtypes = [vp, vp, vp, u64, P(WindowOptions), P(vp)]
-        L.kmx_search_windows_device.restype = C.c_int
-        L.kmx_search_windows_device.argtypes = [vp, vp, vp, u64, P(WindowOptions), vp, P(vp)]
-        L.kmx_result_window_offsets.restype = C.c_int
-        L.kmx_result_window_offsets.argtypes = [vp, P(vp), P(vp), P(u64)]
-        L.kmx_windows_vote.restype = C.c_int
-        L.kmx_windows_vote.argtypes = [vp, P(VoteOptions), P(vp)]
-        L.kmx_loci_counts.restype = C.c_int
-        L.kmx_loci_counts.argtypes = [vp, P(u64), P(u64), P(u64), P(u64), P(u64)]
-        L.kmx_loci_view.restype = C.c_int
-        L.kmx_loci_view.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]
-        L.kmx_loci_view_device.restype = C.c_int
-        L.kmx_loci_view_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]
-        L.kmx_loci_free.argtypes = [vp]
-        L.kmx_loci_align.restype = C.c_int
-        L.kmx_loci_align.argtypes = [vp, vp, vp, vp, u64, P(AlignOptions), P(vp)]
-        L.kmx_loci_align_device.restype = C.c_int
-        L.kmx_loci_align_device.argtypes = [vp, vp, vp, vp, u64, P(AlignOptions), vp, P(vp)]
-        L.kmx_alignments_counts.restype = C.c_int
-        L.kmx_alignments_counts.argtypes = [vp, P(u64), P(u64), P(u64), P(u64)]
-        L.kmx_alignments_view.restype = C.c_int
-        L.kmx_alignments_view.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]
-        L.kmx_alignments_view_device.restype = C.c_int
-        L.kmx_alignments_view_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]
-        L.kmx_alignments_free.argtypes = [vp]
-        L.kmx_alignments_scripts.restype = C.c_int
-        L.kmx_alignments_scripts.argtypes = [vp, vp, vp, vp, vp, u64, P(ScriptOptions), P(vp)]
-        L.kmx_alignments_scripts_device.restype = C.c_int
-        L.kmx_alignments_scripts_device.argtypes = [vp, vp, vp, vp, vp, u64, P(ScriptOptions), vp, P(vp)]
-        L.kmx_scripts_counts.restype = C.c_int
-        L.kmx_scripts_counts.argtypes = [vp, P(u64), P(u64), P(u64), P(u64)]
-        L.kmx_scripts_view.restype = C.c_int
-        L.kmx_scripts_view.argtypes = [vp, P(vp), P(vp), P(vp), P(vp)]
-        L.kmx_scripts_view_device.restype = C.c_int
-        L.kmx_scripts_view_device.argtypes = [vp, P(vp), P(vp), P(vp), P(vp)]
-        L.kmx_scripts_free.argtypes = [vp]
-        L.kmx_reads_strands.restype = C.c_int
-        L.kmx_reads_strands.argtypes = [vp, vp, vp, u64, vp, P(vp)]
-        L.kmx_reads_strands_device.restype = C.c_int
-        L.kmx_reads_strands_device.argtypes = [vp, vp, vp, u64, vp, vp, P(vp)]
-        L.kmx_strand_reads_view_device.restype = C.c_int
-        L.kmx_strand_reads_view_device.argtypes = [vp, P(vp), P(vp), P(u64), P(vp)]
-        L.kmx_strand_reads_free.argtypes = [vp]
-        L.kmx_alignments_fold_strands.restype = C.c_int
-        L.kmx_alignments_fold_strands.argtypes = [vp, vp, P(FoldOptions), vp, P(vp)]
-        L.kmx_placements_counts.restype = C.c_int
-        L.kmx_placements_counts.argtypes = [vp, P(u64), P(u64), P(u64), P(u64)]
-        L.kmx_placements_view.restype = C.c_int
-        L.kmx_placements_view.argtypes = [vp] + [P(vp)] * 7
-        L.kmx_placements_view_device.restype = C.c_int
-        L.kmx_placements_view_device.argtypes = [vp] + [P(vp)] * 7
-        L.kmx_placements_free.argtypes = [vp]
-        L.kmx_placements_scripts.restype = C.c_int
-        L.kmx_placements_scripts.argtypes = [vp, vp, vp, vp, vp, P(ScriptOptions), P(vp)]
-        L.kmx_alignments_fold_pairs.restype = C.c_int
-        L.kmx_alignments_fold_pairs.argtypes = [vp, vp, P(PairOptions), vp, P(vp), P(vp)]
-        L.kmx_pairs_counts.restype = C.c_int
-        L.kmx_pairs_counts.argtypes = [vp] + [P(u64)] * 6
-        L.kmx_pairs_view.restype = C.c_int
-        L.kmx_pairs_view.argtypes = [vp] + [P(vp)] * 4
-        L.kmx_pairs_view_device.restype = C.c_int
-        L.kmx_pairs_view_device.argtypes = [vp] + [P(vp)] * 4
-        L.kmx_pairs_free.argtypes = [vp]
-        L.kmx_pairs_rescue.restype = C.c_int
-        L.kmx_pairs_rescue.argtypes = [vp, vp, vp, vp, P(RescueOptions), vp, vp, P(vp)]
-        L.kmx_rescues_counts.restype = C.c_int
-        L.kmx_rescues_counts.argtypes = [vp] + [P(u64)] * 5
-        L.kmx_rescues_view.restype = C.c_int
-        L.kmx_rescues_view.argtypes = [vp] + [P(vp)] * 8
-        L.kmx_rescues_view_device.restype = C.c_int
-        L.kmx_rescues_view_device.argtypes = [vp] + [P(vp)] * 8
-        L.kmx_rescues_scripts.restype = C.c_int
-        L.kmx_rescues_scripts.argtypes = [vp, vp, vp, P(ScriptOptions), P(vp)]
-        L.kmx_rescues_free.argtypes = [vp]
-        L.kmx_scripts_md.restype = C.c_int
-        L.kmx_scripts_md.argtypes = [vp, vp, vp, vp, P(MdOptions), vp, P(vp)]
-        L.kmx_rescues_md.restype = C.c_int
-        L.kmx_rescues_md.argtypes = [vp, vp, vp, vp, P(MdOptions), vp, P(vp)]
-        L.kmx_md_counts.restype = C.c_int
-        L.kmx_md_counts.argtypes = [vp] + [P(u64)] * 3
-        L.kmx_md_view.restype = C.c_int
-        L.kmx_md_view.argtypes = [vp] + [P(vp)] * 2
-        L.kmx_md_view_device.restype = C.c_int
-        L.kmx_md_view_device.argtypes = [vp] + [P(vp)] * 2
-        L.kmx_md_free.argtypes = [vp]
-        L.kmx_placements_mapq.restype = C.c_int
-        L.kmx_placements_mapq.argtypes = [vp, vp, P(MapqOptions), vp, P(vp)]
-        L.kmx_mapq_counts.restype = C.c_int
-        L.kmx_mapq_counts.argtypes = [vp] + [P(u64)] * 3
-        L.kmx_mapq_view.restype = C.c_int
-        L.kmx_mapq_view.argtypes = [vp, P(vp)]
-        L.kmx_mapq_view_device.restype = C.c_int
-        L.kmx_mapq_view_device.argtypes = [vp, P(vp)]
-        L.kmx_mapq_free.argtypes = [vp]
-        L.kmx_index_set_contigs.restype = C.c_int
-        L.kmx_index_set_contigs.argtypes = [vp, vp, u64]
-        L.kmx_index_contigs.restype = C.c_int
-        L.kmx_index_contigs.argtypes = [vp, P(u64), vp, u64]
-        L.kmx_alignments_contigs_view.restype = C.c_int
-        L.kmx_alignments_contigs_view.argtypes = [vp, P(vp), P(u64)]
-        L.kmx_alignments_contigs_view_device.restype = C.c_int
-        L.kmx_alignments_contigs_view_device.argtypes = [vp, P(vp), P(u64)]
-        L.kmx_placements_locate.restype = C.c_int
-        L.kmx_placements_locate.argtypes = [vp, vp, vp, P(LocateOptions), vp, P(vp)]
-        L.kmx_located_counts.restype = C.c_int
-        L.kmx_located_counts.argtypes = [vp] + [P(u64)] * 3
-        L.kmx_located_view.restype = C.c_int
-        L.kmx_located_view.argtypes = [vp, P(vp), P(vp)]
-        L.kmx_located_view_device.restype = C.c_int
-        L.kmx_located_view_device.argtypes = [vp, P(vp), P(vp)]
-        L.kmx_located_free.argtypes = [vp]
-        L.kmx_placements_secondaries.restype = C.c_int
-        L.kmx_placements_secondaries.argtypes = [vp, vp, vp, P(SecondaryOptions), vp, P(vp)]
-        L.kmx_secondaries_counts.restype = C.c_int
-        L.kmx_secondaries_counts.argtypes = [vp] + [P(u64)] * 4
-        L.kmx_secondaries_view.restype = C.c_int
-        L.kmx_secondaries_view.argtypes = [vp] + [P(vp)] * 7
-        L.kmx_secondaries_view_device.restype = C.c_int
-        L.kmx_secondaries_view_device.argtypes = [vp] + [P(vp)] * 7
-        L.kmx_secondaries_scripts.restype = C.c_int
-        L.kmx_secondaries_scripts.argtypes = [vp, vp, vp, P(ScriptOptions), P(vp)]
-        L.kmx_secondaries_md.restype = C.c_int
-        L.kmx_secondaries_md.argtypes = [vp, vp, vp, vp, P(MdOptions), vp, P(vp)]
-        L.kmx_secondaries_free.argtypes = [vp]
-        L.kmx_scripts_clip.restype = C.c_int
-        L.kmx_scripts_clip.argtypes = [vp, P(ClipOptions), vp, P(vp)]
-        L.kmx_clips_counts.restype = C.c_int
-        L.kmx_clips_counts.argtypes = [vp] + [P(u64)] * 4
-        L.kmx_clips_view.restype = C.c_int
-        L.kmx_clips_view.argtypes = [vp] + [P(vp)] * 9
-        L.kmx_clips_view_device.restype = C.c_int
-        L.kmx_clips_view_device.argtypes = [vp] + [P(vp)] * 9
-        L.kmx_clips_md.restype = C.c_int
-        L.kmx_clips_md.argtypes = [vp, vp, vp, vp, vp, P(MdOptions), vp, P(vp)]
-        L.kmx_clips_rescues_md.restype = C.c_int
-        L.kmx_clips_rescues_md.argtypes = [vp, vp, vp, vp, vp, P(MdOptions), vp, P(vp)]
-        L.kmx_clips_free.argtypes = [vp]
-        L.kmx_index_text.restype = C.c_int
-        L.kmx_index_text.argtypes = [vp, vp, u64, P(u64)]
-        L.kmx_stats_enable.restype = C.c_int
-        L.kmx_stats_enable.argtypes = [vp, C.c_int]
-        L.kmx_stats_get.restype = C.c_int
-        L.kmx_stats_get.argtypes = [vp, P(KernelStat), P(u32)]
-        L.kmx_stats_reset.restype = C.c_int
-        L.kmx_stats_reset.argtypes = [vp]
-        L.kmx_debug_words.restype = C.c_int
-        L.kmx_debug_words.argtypes = [vp, vp]
-        L.kmx_last_error.restype = C.c_char_p
-        L.kmx_status_string.restype = C.c_char_p
-        L.kmx_status_string.argtypes = [C.c_int]
-        L.kmx_version.restype = u32
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -581,28 +463,54 @@ class Result:
 
 
 class _Handle:
-    """What the owners of a C handle share: the empty handle, close() through the class's free function, and the two calls that
-    fill a run of out-parameters of one type."""
+    """What the owners of a C handle share: the empty handle, close() through the class's free function, and counts(), host() and
+    device_ptrs() from what the class declares:
+
+    _counts_of = (the kmx_*_counts function, the names of its out-parameters in order): counts() is a dict under those names.
+    _view_of = (stem, fields): kmx_<stem>_view fills one host pointer per field and kmx_<stem>_view_device one device pointer;
+        a field is (name, dtype, length), the length a name of counts() or a function of that dict.  host() is the tuple of the
+        fields as numpy copies, device_ptrs() the tuple of the device pointers, both in the order of the fields."""
 
     _free = None                    # the name of the handle's kmx_*_free
+    _counts_of = None
+    _view_of = None
 
     def __init__(self):
         self._h = C.c_void_p()
+        self._reads = None          # the StrandReads whose stream the handle was filled on: it must outlive the views
 
-    def _counts(self, fn, *names):
-        v = [C.c_uint64() for _ in names]
+    def counts(self):
+        fn, names = self._counts_of
+        v = [p._type_() for p in SIGNATURES[fn][1][1:]]
         _check(getattr(lib(), fn)(self._h, *[C.byref(x) for x in v]))
         return dict(zip(names, [int(x.value) for x in v]))
 
-    def _device_ptrs(self, fn, n):
+    def _ptrs(self, fn, n, n_null=0):
+        """The first n out-parameters of a view function, which are pointers; NULL goes in for n_null further ones."""
         p = [C.c_void_p() for _ in range(n)]
-        _check(getattr(lib(), fn)(self._h, *[C.byref(x) for x in p]))
+        _check(getattr(lib(), fn)(self._h, *[C.byref(x) for x in p], *[None] * n_null))
         return tuple(x.value for x in p)
+
+    def _arrays(self, ptrs):
+        """Copies of the fields that the host pointers `ptrs` (those of the first len(ptrs) fields) point at."""
+        c = self.counts()
+        return tuple(_view(p, n(c) if callable(n) else c[n], dtype).copy() for p, (_, dtype, n) in zip(ptrs, self._view_of[1]))
+
+    def host(self):
+        """The fields of _view_of as numpy copies, in their order."""
+        stem, fields = self._view_of
+        return self._arrays(self._ptrs(f"kmx_{stem}_view", len(fields)))
+
+    def device_ptrs(self):
+        """The device pointer of every field of _view_of, in their order."""
+        stem, fields = self._view_of
+        return self._ptrs(f"kmx_{stem}_view_device", len(fields))
 
     def close(self):
         if self._h:
             getattr(lib(), self._free)(self._h)
             self._h = C.c_void_p()
+        self._reads = None
 
     def __del__(self):
         try:
@@ -611,27 +519,20 @@ class _Handle:
             pass
 
 
+def _made_from(new, *sources, reads=None):
+    """`new` was filled from the handles `sources`, on the stream of `reads` where the call takes the StrandReads itself: it keeps
+    alive the StrandReads that they keep alive (a reused handle takes the new owner too).  Returns new."""
+    new._reads = reads if reads is not None else next((s._reads for s in sources if s._reads is not None), None)
+    return new
+
+
 class Loci(_Handle):
     """Owns a kmx_loci handle (kmx_windows_vote)."""
 
     _free = "kmx_loci_free"
-
-    def counts(self):
-        return self._counts("kmx_loci_counts", "nr", "n_loci", "n_votes", "n_small", "n_large")
-
-    def host(self):
-        """(locus_off[nr+1] u64, diag i64, span u32, votes u32, skipped[nr] u32) as numpy copies."""
-        c = self.counts()
-        p = [C.c_void_p() for _ in range(5)]
-        _check(lib().kmx_loci_view(self._h, *[C.byref(x) for x in p]))
-        nr, nl = c["nr"], c["n_loci"]
-        out = (_view(p[0].value, nr + 1, np.uint64), _view(p[1].value, nl, np.int64), _view(p[2].value, nl, np.uint32),
-               _view(p[3].value, nl, np.uint32), _view(p[4].value, nr, np.uint32))
-        return tuple(x.copy() for x in out)
-
-    def device_ptrs(self):
-        """(d_locus_off, d_diag, d_span, d_votes, d_skipped): kmx_loci_view_device."""
-        return self._device_ptrs("kmx_loci_view_device", 5)
+    _counts_of = ("kmx_loci_counts", ("nr", "n_loci", "n_votes", "n_small", "n_large"))
+    _view_of = ("loci", (("locus_off", np.uint64, lambda c: c["nr"] + 1), ("diag", np.int64, "n_loci"), ("span", np.uint32, "n_loci"),
+                         ("votes", np.uint32, "n_loci"), ("skipped", np.uint32, "nr")))
 
     def align(self, index, ranks, roff, max_edits, max_span=0, alignments=None):
         """kmx_loci_align: every read (the reads of the windows search) against the text around each of its loci, within
@@ -642,37 +543,23 @@ class Loci(_Handle):
         o = AlignOptions(C.sizeof(AlignOptions), int(max_edits), int(max_span), 0)
         _check(lib().kmx_loci_align(index._h, self._h, ranks.ctypes.data if ranks.size else None, roff.ctypes.data, roff.size - 1,
                                     C.byref(o), C.byref(a._h)))
-        return a
+        return _made_from(a, self)
 
     def align_device(self, index, d_ranks_ptr, d_roff_ptr, nr, max_edits, max_span=0, stream=0, alignments=None):
         """kmx_loci_align_device on a caller-owned hipStream_t: the stream of the vote, or one ordered behind it."""
         a = alignments or Alignments()
         o = AlignOptions(C.sizeof(AlignOptions), int(max_edits), int(max_span), 0)
         _check(lib().kmx_loci_align_device(index._h, self._h, d_ranks_ptr, d_roff_ptr, nr, C.byref(o), stream or None, C.byref(a._h)))
-        return a
+        return _made_from(a, self)
 
 
 class Alignments(_Handle):
     """Owns a kmx_alignments handle (kmx_loci_align)."""
 
     _free = "kmx_alignments_free"
-
-    def counts(self):
-        return self._counts("kmx_alignments_counts", "nr", "n_loci", "n_aligned", "n_skipped")
-
-    def host(self):
-        """(dist[n_loci] u8, start u32, end u32, best[nr] u32, aligned[nr] u32) as numpy copies."""
-        c = self.counts()
-        p = [C.c_void_p() for _ in range(5)]
-        _check(lib().kmx_alignments_view(self._h, *[C.byref(x) for x in p]))
-        nr, nl = c["nr"], c["n_loci"]
-        out = (_view(p[0].value, nl, np.uint8), _view(p[1].value, nl, np.uint32), _view(p[2].value, nl, np.uint32),
-               _view(p[3].value, nr, np.uint32), _view(p[4].value, nr, np.uint32))
-        return tuple(x.copy() for x in out)
-
-    def device_ptrs(self):
-        """(d_dist, d_start, d_end, d_best, d_aligned): kmx_alignments_view_device."""
-        return self._device_ptrs("kmx_alignments_view_device", 5)
+    _counts_of = ("kmx_alignments_counts", ("nr", "n_loci", "n_aligned", "n_skipped"))
+    _view_of = ("alignments", (("dist", np.uint8, "n_loci"), ("start", np.uint32, "n_loci"), ("end", np.uint32, "n_loci"),
+                               ("best", np.uint32, "nr"), ("aligned", np.uint32, "nr")))
 
     def contigs_host(self):
         """kmx_alignments_contigs_view: ctg[n_loci] u32 as a numpy copy, the contig of every locus (NO_CONTIG for a skipped one), or
@@ -703,14 +590,14 @@ class Alignments(_Handle):
         o = self._script_options(all, m, scratch_bytes)
         _check(lib().kmx_alignments_scripts(index._h, loci._h, self._h, ranks.ctypes.data if ranks.size else None, roff.ctypes.data, roff.size - 1,
                                             C.byref(o), C.byref(s._h)))
-        return s
+        return _made_from(s, loci, self)
 
     def scripts_device(self, index, loci, d_ranks_ptr, d_roff_ptr, nr, all=False, m=False, scratch_bytes=0, stream=0, scripts=None):
         """kmx_alignments_scripts_device on a caller-owned hipStream_t: the stream of the alignment, or one ordered behind it."""
         s = scripts or Scripts()
         o = self._script_options(all, m, scratch_bytes)
         _check(lib().kmx_alignments_scripts_device(index._h, loci._h, self._h, d_ranks_ptr, d_roff_ptr, nr, C.byref(o), stream or None, C.byref(s._h)))
-        return s
+        return _made_from(s, loci, self)
 
     def fold_strands(self, loci, stream=0, placements=None):
         """kmx_alignments_fold_strands: these are the alignments of a doubled batch (StrandReads) and `loci` its loci; one placement
@@ -718,7 +605,7 @@ class Alignments(_Handle):
         p = placements or Placements()
         o = FoldOptions(C.sizeof(FoldOptions), 0)
         _check(lib().kmx_alignments_fold_strands(loci._h, self._h, C.byref(o), stream or None, C.byref(p._h)))
-        return p
+        return _made_from(p, loci, self)
 
     def fold_pairs(self, loci, min_insert, max_insert, orientation=PAIR_FR, unpaired_penalty=None, stream=0, placements=None, pairs=None):
         """kmx_alignments_fold_pairs: these are the alignments of a doubled batch of interleaved mates (public read 2p is mate 1 of
@@ -730,29 +617,17 @@ class Alignments(_Handle):
         o = PairOptions(C.sizeof(PairOptions), int(min_insert), int(max_insert), int(orientation),
                         PAIR_NO_PENALTY if unpaired_penalty is None else int(unpaired_penalty), 0)
         _check(lib().kmx_alignments_fold_pairs(loci._h, self._h, C.byref(o), stream or None, C.byref(pl._h), C.byref(pr._h)))
-        return pl, pr
+        return _made_from(pl, loci, self), _made_from(pr, loci, self)
 
 
 class Scripts(_Handle):
     """Owns a kmx_scripts handle (kmx_alignments_scripts)."""
 
     _free = "kmx_scripts_free"
-
-    def counts(self):
-        return self._counts("kmx_scripts_counts", "nr", "n_sel", "n_ops", "n_mismatched")
-
-    def host(self):
-        """(read_sel_off[nr+1] u64, sel[n_sel] u32, cig_off[n_sel+1] u64, cigar[n_ops] u32) as numpy copies."""
-        c = self.counts()
-        p = [C.c_void_p() for _ in range(4)]
-        _check(lib().kmx_scripts_view(self._h, *[C.byref(x) for x in p]))
-        out = (_view(p[0].value, c["nr"] + 1, np.uint64), _view(p[1].value, c["n_sel"], np.uint32),
-               _view(p[2].value, c["n_sel"] + 1, np.uint64), _view(p[3].value, c["n_ops"], np.uint32))
-        return tuple(x.copy() for x in out)
-
-    def device_ptrs(self):
-        """(d_read_sel_off, d_sel, d_cig_off, d_cigar): kmx_scripts_view_device."""
-        return self._device_ptrs("kmx_scripts_view_device", 4)
+    _counts_of = ("kmx_scripts_counts", ("nr", "n_sel", "n_ops", "n_mismatched"))
+    _view_of = ("scripts", (("read_sel_off", np.uint64, lambda c: c["nr"] + 1), ("sel", np.uint32, "n_sel"),
+                            ("cig_off", np.uint64, lambda c: c["n_sel"] + 1), ("cigar", np.uint32, "n_ops")))
+    _md_of = {"Alignments": "kmx_scripts_md", "Rescues": "kmx_rescues_md", "Secondaries": "kmx_secondaries_md"}     # by the source's type
 
     def strings(self):
         """One CIGAR string per entry, e.g. "50=1X30=1D69=" ("" for an entry without a script)."""
@@ -768,26 +643,27 @@ class Scripts(_Handle):
         o = ClipOptions(C.sizeof(ClipOptions), int(match), int(mismatch), int(gap_open), int(gap_extend), int(clip_penalty), int(min_score), 0)
         _check(lib().kmx_scripts_clip(self._h, C.byref(o), stream or None, C.byref(out._h)))
         out.scripts = self
-        return out
+        return _made_from(out, self)
 
     def md(self, index, source, letters, stream=0, md=None):
         """kmx_scripts_md (source: the Alignments these scripts were made from), kmx_rescues_md (source: the Rescues) or
         kmx_secondaries_md (source: the Secondaries): the MD string of every entry, from the runs and the index's text.  letters:
         sigma output bytes by rank (a str, bytes or uint8 array, e.g. "ACGT").  stream=0: the stream that filled this handle.
         Returns an Md (`md` reuses one)."""
-        if isinstance(source, Rescues):
-            fn = lib().kmx_rescues_md
-        elif isinstance(source, Secondaries):
-            fn = lib().kmx_secondaries_md
-        elif isinstance(source, Alignments):
-            fn = lib().kmx_scripts_md
-        else:
+        fn = self._md_of.get(type(source).__name__)
+        if fn is None:
             raise TypeError("Scripts.md: source is an Alignments, a Rescues or a Secondaries")
-        table = None if letters is None else _letters_table(letters)
-        out = md or Md()
-        o = MdOptions(C.sizeof(MdOptions), 0)
-        _check(fn(index._h, self._h, source._h, table.ctypes.data if table is not None else None, C.byref(o), stream or None, C.byref(out._h)))
-        return out
+        return _made_from(_md_call(fn, index, (self, source), letters, stream, md), self)
+
+
+def _md_call(fn, index, handles, letters, stream, md):
+    """One of the kmx_*_md functions, which differ in the handles they take behind the index.  Returns the Md (`md` reuses one)."""
+    table = None if letters is None else _letters_table(letters)
+    out = md or Md()
+    o = MdOptions(C.sizeof(MdOptions), 0)
+    _check(getattr(lib(), fn)(index._h, *[h._h for h in handles], table.ctypes.data if table is not None else None, C.byref(o), stream or None,
+                              C.byref(out._h)))
+    return out
 
 
 def _runs_strings(cig_off, cigar):
@@ -801,33 +677,19 @@ class Clips(_Handle):
     score and the letters clipped off either side.  Entry e is entry e of the Scripts."""
 
     _free = "kmx_clips_free"
+    _counts_of = ("kmx_clips_counts", ("n_sel", "n_ops", "n_clipped", "n_low"))
+    _view_of = ("clips", (("score", np.int32, "n_sel"), ("sl", np.uint16, "n_sel"), ("sr", np.uint16, "n_sel"), ("tl", np.uint16, "n_sel"),
+                          ("tr", np.uint16, "n_sel"), ("nm", np.uint16, "n_sel"), ("cflags", np.uint8, "n_sel"),
+                          ("cig_off", np.uint64, lambda c: c["n_sel"] + 1), ("cigar", np.uint32, "n_ops")))
+    _md_of = {"Alignments": "kmx_clips_md", "Rescues": "kmx_clips_rescues_md"}      # by the source's type
 
     def __init__(self):
         super().__init__()
-        self._reads = None          # the StrandReads whose stream the call ran on: it must outlive the views
         self.scripts = None         # the Scripts the clips were made from (set by Scripts.clip)
 
     def close(self):
         super().close()
-        self._reads = self.scripts = None
-
-    def counts(self):
-        return self._counts("kmx_clips_counts", "n_sel", "n_ops", "n_clipped", "n_low")
-
-    def host(self):
-        """(score[n_sel] i32, sl u16, sr u16, tl u16, tr u16, nm u16, cflags u8, cig_off[n_sel+1] u64, cigar[n_ops] u32) as numpy
-        copies."""
-        c = self.counts()
-        p = [C.c_void_p() for _ in range(9)]
-        _check(lib().kmx_clips_view(self._h, *[C.byref(x) for x in p]))
-        dt = (np.int32, np.uint16, np.uint16, np.uint16, np.uint16, np.uint16, np.uint8)
-        out = [_view(x.value, c["n_sel"], d) for x, d in zip(p, dt)]
-        out += [_view(p[7].value, c["n_sel"] + 1, np.uint64), _view(p[8].value, c["n_ops"], np.uint32)]
-        return tuple(x.copy() for x in out)
-
-    def device_ptrs(self):
-        """(d_score, d_sl, d_sr, d_tl, d_tr, d_nm, d_cflags, d_cig_off, d_cigar): kmx_clips_view_device."""
-        return self._device_ptrs("kmx_clips_view_device", 9)
+        self.scripts = None
 
     def strings(self):
         """One CIGAR string per entry with S at the clipped ends, e.g. "1S149=" ("" for an entry without a script)."""
@@ -838,19 +700,10 @@ class Clips(_Handle):
         """kmx_clips_md (source: the Alignments the scripts were made from) or kmx_clips_rescues_md (source: the Rescues): the MD
         string of every clipped entry, over the text interval [start + tl, end - tr).  scripts: the Scripts these clips were made
         from.  stream=0: the stream that filled the scripts.  Returns an Md (`md` reuses one)."""
-        if isinstance(source, Rescues):
-            fn = lib().kmx_clips_rescues_md
-        elif isinstance(source, Alignments):
-            fn = lib().kmx_clips_md
-        else:
+        fn = self._md_of.get(type(source).__name__)
+        if fn is None:
             raise TypeError("Clips.md: source is an Alignments or a Rescues")
-        table = None if letters is None else _letters_table(letters)
-        out = md or Md()
-        o = MdOptions(C.sizeof(MdOptions), 0)
-        _check(fn(index._h, scripts._h, self._h, source._h, table.ctypes.data if table is not None else None, C.byref(o), stream or None,
-                  C.byref(out._h)))
-        out._reads = self._reads
-        return out
+        return _made_from(_md_call(fn, index, (scripts, self, source), letters, stream, md), self)
 
 
 def _clip_fields(entry, clips):
@@ -878,28 +731,8 @@ class Md(_Handle):
     """Owns a kmx_md handle (kmx_scripts_md, kmx_rescues_md): the MD string of every entry of a Scripts."""
 
     _free = "kmx_md_free"
-
-    def __init__(self):
-        super().__init__()
-        self._reads = None          # the StrandReads whose stream the call ran on: it must outlive the views
-
-    def close(self):
-        super().close()
-        self._reads = None
-
-    def counts(self):
-        return self._counts("kmx_md_counts", "n_sel", "n_bytes", "n_mismatched")
-
-    def host(self):
-        """(md_off[n_sel+1] u64, md[n_bytes] u8) as numpy copies."""
-        c = self.counts()
-        p = [C.c_void_p() for _ in range(2)]
-        _check(lib().kmx_md_view(self._h, *[C.byref(x) for x in p]))
-        return _view(p[0].value, c["n_sel"] + 1, np.uint64).copy(), _view(p[1].value, c["n_bytes"], np.uint8).copy()
-
-    def device_ptrs(self):
-        """(d_md_off, d_md): kmx_md_view_device."""
-        return self._device_ptrs("kmx_md_view_device", 2)
+    _counts_of = ("kmx_md_counts", ("n_sel", "n_bytes", "n_mismatched"))
+    _view_of = ("md", (("md_off", np.uint64, lambda c: c["n_sel"] + 1), ("md", np.uint8, "n_bytes")))
 
     def strings(self):
         """One MD string per entry, e.g. "50A30^C69" ("" for an entry without a script)."""
@@ -912,27 +745,12 @@ class Mapq(_Handle):
     """Owns a kmx_mapq handle (kmx_placements_mapq): one MAPQ per public read."""
 
     _free = "kmx_mapq_free"
-
-    def __init__(self):
-        super().__init__()
-        self._reads = None          # the StrandReads whose stream the call ran on: it must outlive the views
-
-    def close(self):
-        super().close()
-        self._reads = None
-
-    def counts(self):
-        return self._counts("kmx_mapq_counts", "nr", "n_zero", "n_cap")
+    _counts_of = ("kmx_mapq_counts", ("nr", "n_zero", "n_cap"))
+    _view_of = ("mapq", (("mapq", np.uint8, "nr"),))
 
     def host(self):
-        """mapq[nr] u8 as a numpy copy."""
-        p = C.c_void_p()
-        _check(lib().kmx_mapq_view(self._h, C.byref(p)))
-        return _view(p.value, self.counts()["nr"], np.uint8).copy()
-
-    def device_ptrs(self):
-        """(d_mapq,): kmx_mapq_view_device."""
-        return self._device_ptrs("kmx_mapq_view_device", 1)
+        """The one field itself, not a tuple of one."""
+        return super().host()[0]
 
 
 class StrandReads(_Handle):
@@ -952,33 +770,41 @@ class StrandReads(_Handle):
         return a.value, b.value, int(n.value), s.value
 
 
-class Placements(_Handle):
+class _PerRead:
+    """The per-read lookups of a handle whose scripts() has at most one entry per public read.  The class supplies
+    _entries(scripts): that entry for every public read, -1 where the read has none."""
+
+    def _per_read(self, scripts, values, none=""):
+        """values holds one value per entry of `scripts`: the value of every public read's entry, `none` where it has none"""
+        return [values[e] if e >= 0 else none for e in self._entries(scripts)]
+
+    def cigars(self, scripts, clips=None):
+        """One CIGAR string per public read from the Scripts of scripts(): "" where the read has no entry (it is unplaced, or was
+        not rescued).  clips (the Clips of scripts.clip()): the clipped CIGARs, with S."""
+        return self._per_read(scripts, scripts.strings() if clips is None else clips.strings())
+
+    def mds(self, md, scripts):
+        """One MD string per public read from the Md of scripts.md(): "" where cigars(scripts) has none."""
+        return self._per_read(scripts, md.strings())
+
+    def clip_fields(self, clips, scripts):
+        """(tl, nm, score, has) per public read from the Clips of scripts().clip(): the text letters clipped off the left, the
+        clipped NM and the score of the read's entry, has False (and zeros) where cigars(scripts) has none.  For sam_lines (the
+        rescue's as the second of a tuple)."""
+        return _clip_fields(self._entries(scripts), clips)
+
+
+class Placements(_PerRead, _Handle):
     """Owns a kmx_placements handle (kmx_alignments_fold_strands): one placement per public read of a doubled batch."""
 
     _free = "kmx_placements_free"
-
-    def __init__(self):
-        super().__init__()
-        self._reads = None          # the StrandReads whose stream the fold ran on: it must outlive the views
-
-    def counts(self):
-        return self._counts("kmx_placements_counts", "nr", "n_placed", "n_reverse", "n_ambiguous")
+    _counts_of = ("kmx_placements_counts", ("nr", "n_placed", "n_reverse", "n_ambiguous"))
+    _view_of = ("placements", (("locus", np.uint32, "nr"), ("strand", np.uint8, "nr"), ("dist", np.uint8, "nr"), ("start", np.uint32, "nr"),
+                               ("end", np.uint32, "nr"), ("second", np.uint8, "nr"), ("best2", np.uint32, lambda c: 2 * c["nr"])))
 
     def host(self, best2=True):
-        """(locus[nr] u32, strand u8, dist u8, start u32, end u32, second u8, best2[2 nr] u32) as numpy copies; best2=False
-        leaves that array on the device (the tuple then has six entries)."""
-        nr = self.counts()["nr"]
-        p = [C.c_void_p() for _ in range(7)]
-        _check(lib().kmx_placements_view(self._h, *[C.byref(x) for x in p[:6]], C.byref(p[6]) if best2 else None))
-        dt = [np.uint32, np.uint8, np.uint8, np.uint32, np.uint32, np.uint8]
-        out = [_view(x.value, nr, d) for x, d in zip(p, dt)]
-        if best2:
-            out.append(_view(p[6].value, 2 * nr, np.uint32))
-        return tuple(x.copy() for x in out)
-
-    def device_ptrs(self):
-        """(d_locus, d_strand, d_dist, d_start, d_end, d_second, d_best2): kmx_placements_view_device."""
-        return self._device_ptrs("kmx_placements_view_device", 7)
+        """best2=False leaves the last field on the device (the tuple then has six entries)."""
+        return super().host() if best2 else self._arrays(self._ptrs("kmx_placements_view", 6, n_null=1))
 
     def scripts(self, index, reads, loci, alignments, m=False, scratch_bytes=0, scripts=None):
         """kmx_placements_scripts: the CIGAR of every placed read's winner (for a reverse placement that of the reverse complement
@@ -986,31 +812,17 @@ class Placements(_Handle):
         s = scripts or Scripts()
         o = Alignments._script_options(False, m, scratch_bytes)
         _check(lib().kmx_placements_scripts(index._h, reads._h, loci._h, alignments._h, self._h, C.byref(o), C.byref(s._h)))
-        return s
+        return _made_from(s, reads=reads)
 
-    def _per_read(self, scripts, strings, none=""):
-        """strings holds one value per entry of `scripts`: the value of every public read's winner, `none` where it has none"""
+    def _entries(self, scripts):
+        """the entry of every public read's winner, -1 for an unplaced read"""
         strand = self.host(best2=False)[1]
         read_sel_off = scripts.host()[0]
         out = []
         for i, s in enumerate(strand):
             r = 2 * i + int(s)
-            out.append(strings[int(read_sel_off[r])] if s != 255 and read_sel_off[r + 1] > read_sel_off[r] else none)
+            out.append(int(read_sel_off[r]) if s != 255 and read_sel_off[r + 1] > read_sel_off[r] else -1)
         return out
-
-    def clip_fields(self, clips, scripts):
-        """(tl, nm, score, has) per public read from the Clips of scripts().clip(): the text letters clipped off the left, the
-        clipped NM and the score of the read's winner, has False (and zeros) where cigars(scripts) has none.  For sam_lines."""
-        return _clip_fields(self._per_read(scripts, range(scripts.counts()["n_sel"]), -1), clips)
-
-    def cigars(self, scripts, clips=None):
-        """One CIGAR string per public read from the Scripts of scripts(): "" where the read is unplaced.  clips (the Clips of
-        scripts.clip()): the clipped CIGARs, with S."""
-        return self._per_read(scripts, scripts.strings() if clips is None else clips.strings())
-
-    def mds(self, md, scripts):
-        """One MD string per public read from the Md of scripts.md(): "" where cigars(scripts) has none."""
-        return self._per_read(scripts, md.strings())
 
     def mapq(self, max_edits, pairs=None, cap=60, per_edit=10, pair_bonus=40, stream=0, mapq=None):
         """kmx_placements_mapq: one MAPQ per read by the gap rule of include/kmx.h (a heuristic), from dist and second and, with
@@ -1019,8 +831,7 @@ class Placements(_Handle):
         q = mapq or Mapq()
         o = MapqOptions(C.sizeof(MapqOptions), int(max_edits), int(cap), int(per_edit), int(pair_bonus), 0)
         _check(lib().kmx_placements_mapq(self._h, pairs._h if pairs is not None else None, C.byref(o), stream or None, C.byref(q._h)))
-        q._reads = self._reads
-        return q
+        return _made_from(q, self)
 
     def locate(self, index, alignments, mates=False, stream=0, located=None):
         """kmx_placements_locate: the contig and the position inside it of every placement, from the contig table of `index` and
@@ -1029,8 +840,7 @@ class Placements(_Handle):
         out = located or Located()
         o = LocateOptions(C.sizeof(LocateOptions), LOCATE_MATES if mates else 0)
         _check(lib().kmx_placements_locate(index._h, alignments._h, self._h, C.byref(o), stream or None, C.byref(out._h)))
-        out._reads = self._reads
-        return out
+        return _made_from(out, self)
 
     def secondaries(self, loci, alignments, max_secondary, max_delta=None, stream=0, secondaries=None):
         """kmx_placements_secondaries: up to max_secondary (<= SECONDARY_MAX) further places per read, chosen greedily by
@@ -1040,12 +850,7 @@ class Placements(_Handle):
         out = secondaries or Secondaries()
         o = SecondaryOptions(C.sizeof(SecondaryOptions), int(max_secondary), SECONDARY_NO_DELTA if max_delta is None else int(max_delta), 0)
         _check(lib().kmx_placements_secondaries(loci._h, alignments._h, self._h, C.byref(o), stream or None, C.byref(out._h)))
-        out._reads = self._reads
-        return out
-
-    def close(self):
-        super().close()
-        self._reads = None
+        return _made_from(out, self)
 
 
 def xa_strings(sec_off, dist, start, ctg, cigars, strand_names="+-", located=None, rname=None, shift=None):
@@ -1081,29 +886,15 @@ class Secondaries(_Handle):
     read 2i + s being those of read i on strand s."""
 
     _free = "kmx_secondaries_free"
-
-    def __init__(self):
-        super().__init__()
-        self._reads = None          # the StrandReads whose stream the call ran on: it must outlive the views
-
-    def counts(self):
-        return self._counts("kmx_secondaries_counts", "nr", "n_sec", "n_multi", "n_truncated")
+    _counts_of = ("kmx_secondaries_counts", ("nr", "n_sec", "n_multi", "n_truncated"))
+    _view_of = ("secondaries", (("sec_off", np.uint64, lambda c: 2 * c["nr"] + 1), ("locus", np.uint32, "n_sec"), ("dist", np.uint8, "n_sec"),
+                                ("start", np.uint32, "n_sec"), ("end", np.uint32, "n_sec"), ("ctg", np.uint32, "n_sec"), ("more", np.uint8, "nr")))
 
     def host(self):
-        """(sec_off[2 nr + 1] u64, locus[n_sec] u32, dist u8, start u32, end u32, ctg u32 or None, more[nr] u8) as numpy copies;
-        ctg is None when the alignments carried no contig table."""
-        c = self.counts()
-        p = [C.c_void_p() for _ in range(7)]
-        _check(lib().kmx_secondaries_view(self._h, *[C.byref(x) for x in p]))
-        ns = c["n_sec"]
-        out = [_view(p[0].value, 2 * c["nr"] + 1, np.uint64)] + [_view(x.value, ns, d) for x, d in zip(p[1:5], (np.uint32, np.uint8, np.uint32, np.uint32))]
-        out.append(_view(p[5].value, ns, np.uint32) if p[5].value else None)
-        out.append(_view(p[6].value, c["nr"], np.uint8))
-        return tuple(None if x is None else x.copy() for x in out)
-
-    def device_ptrs(self):
-        """(d_sec_off, d_locus, d_dist, d_start, d_end, d_ctg, d_more): kmx_secondaries_view_device."""
-        return self._device_ptrs("kmx_secondaries_view_device", 7)
+        """ctg is None when the alignments carried no contig table."""
+        p = self._ptrs("kmx_secondaries_view", 7)
+        out = self._arrays(p)
+        return out[:5] + (out[5] if p[5] else None,) + out[6:]
 
     def scripts(self, index, reads, m=False, scratch_bytes=0, scripts=None):
         """kmx_secondaries_scripts: the CIGAR of every entry (for a reverse entry that of the reverse complement against the forward
@@ -1111,7 +902,7 @@ class Secondaries(_Handle):
         s = scripts or Scripts()
         o = Alignments._script_options(False, m, scratch_bytes)
         _check(lib().kmx_secondaries_scripts(index._h, reads._h, self._h, C.byref(o), C.byref(s._h)))
-        return s
+        return _made_from(s, reads=reads)
 
     def cigars(self, scripts):
         """One CIGAR string per entry from the Scripts of scripts()."""
@@ -1119,9 +910,7 @@ class Secondaries(_Handle):
 
     def md(self, index, scripts, letters, stream=0, md=None):
         """kmx_secondaries_md: the MD string of every entry from the Scripts of scripts().  Returns an Md (`md` reuses one)."""
-        out = scripts.md(index, self, letters, stream, md)
-        out._reads = self._reads
-        return out
+        return _made_from(scripts.md(index, self, letters, stream, md), self, scripts)
 
     def xa(self, scripts, strand_names="+-", located=None, rname=None, clips=None):
         """One XA:Z: value per public read: "" or items rname,<strand><pos>,CIGAR,NM; in bwa's form (pos 1-based), in the order of
@@ -1136,61 +925,22 @@ class Secondaries(_Handle):
         h = clips.host()
         return xa_strings(sec_off, h[5], start, ctg, _runs_strings(h[7], h[8]), strand_names, located, rname, shift=h[3])
 
-    def close(self):
-        super().close()
-        self._reads = None
-
 
 class Located(_Handle):
-    """Owns a kmx_located handle (kmx_placements_locate): the contig and the contig-local position of every public read."""
+    """Owns a kmx_located handle (kmx_placements_locate): the contig and the contig-local position of every public read, NO_CONTIG
+    and 0 for an unplaced one."""
 
     _free = "kmx_located_free"
-
-    def __init__(self):
-        super().__init__()
-        self._reads = None          # the StrandReads whose stream the call ran on: it must outlive the views
-
-    def close(self):
-        super().close()
-        self._reads = None
-
-    def counts(self):
-        return self._counts("kmx_located_counts", "nr", "n_located", "n_mismatched")
-
-    def host(self):
-        """(ctg[nr] u32, pos[nr] u32) as numpy copies: NO_CONTIG and 0 for an unplaced read."""
-        nr = self.counts()["nr"]
-        p = [C.c_void_p() for _ in range(2)]
-        _check(lib().kmx_located_view(self._h, *[C.byref(x) for x in p]))
-        return tuple(_view(x.value, nr, np.uint32).copy() for x in p)
-
-    def device_ptrs(self):
-        """(d_ctg, d_pos): kmx_located_view_device."""
-        return self._device_ptrs("kmx_located_view_device", 2)
+    _counts_of = ("kmx_located_counts", ("nr", "n_located", "n_mismatched"))
+    _view_of = ("located", (("ctg", np.uint32, "nr"), ("pos", np.uint32, "nr")))
 
 
 class Pairs(_Handle):
     """Owns a kmx_pairs handle (kmx_alignments_fold_pairs): one entry per pair of a doubled batch of interleaved mates."""
 
     _free = "kmx_pairs_free"
-
-    def __init__(self):
-        super().__init__()
-        self._reads = None          # the StrandReads whose stream the fold ran on: it must outlive the views
-
-    def counts(self):
-        return self._counts("kmx_pairs_counts", "np", "n_concordant", "n_discordant", "n_single", "n_unplaced", "n_ambiguous")
-
-    def host(self):
-        """(cls[np] u8, tlen i32, score u16, second_score u16) as numpy copies."""
-        n = self.counts()["np"]
-        p = [C.c_void_p() for _ in range(4)]
-        _check(lib().kmx_pairs_view(self._h, *[C.byref(x) for x in p]))
-        return tuple(_view(x.value, n, d).copy() for x, d in zip(p, (np.uint8, np.int32, np.uint16, np.uint16)))
-
-    def device_ptrs(self):
-        """(d_cls, d_tlen, d_score, d_second_score): kmx_pairs_view_device."""
-        return self._device_ptrs("kmx_pairs_view_device", 4)
+    _counts_of = ("kmx_pairs_counts", ("np", "n_concordant", "n_discordant", "n_single", "n_unplaced", "n_ambiguous"))
+    _view_of = ("pairs", (("cls", np.uint8, "np"), ("tlen", np.int32, "np"), ("score", np.uint16, "np"), ("second_score", np.uint16, "np")))
 
     def rescue(self, index, reads, loci, alignments, placements, min_insert, max_insert, max_edits, orientation=PAIR_FR, discordant=False,
                unpaired_penalty=None, segment=0, rescues=None):
@@ -1204,38 +954,17 @@ class Pairs(_Handle):
         o = RescueOptions(C.sizeof(RescueOptions), int(min_insert), int(max_insert), int(orientation), int(max_edits),
                           PAIR_NO_PENALTY if unpaired_penalty is None else int(unpaired_penalty), int(segment), RESCUE_DISCORDANT if discordant else 0)
         _check(lib().kmx_pairs_rescue(index._h, reads._h, loci._h, alignments._h, C.byref(o), placements._h, self._h, C.byref(r._h)))
-        r._reads = reads
-        return r
-
-    def close(self):
-        super().close()
-        self._reads = None
+        return _made_from(r, reads=reads)
 
 
-class Rescues(_Handle):
+class Rescues(_PerRead, _Handle):
     """Owns a kmx_rescues handle (kmx_pairs_rescue): one job per mate that was looked for in its partner's insert window."""
 
     _free = "kmx_rescues_free"
-
-    def __init__(self):
-        super().__init__()
-        self._reads = None          # the StrandReads whose stream the rescue ran on: it must outlive the views
-
-    def counts(self):
-        return self._counts("kmx_rescues_counts", "nr2", "n_jobs", "n_found", "n_concordant", "n_taken")
-
-    def host(self):
-        """(job_off[nr2+1] u64, read[n_jobs] u32, lo u32, hi u32, dist u8, start u32, end u32, status u8) as numpy copies."""
-        c = self.counts()
-        p = [C.c_void_p() for _ in range(8)]
-        _check(lib().kmx_rescues_view(self._h, *[C.byref(x) for x in p]))
-        dt = (np.uint32, np.uint32, np.uint32, np.uint8, np.uint32, np.uint32, np.uint8)
-        out = [_view(p[0].value, c["nr2"] + 1, np.uint64)] + [_view(x.value, c["n_jobs"], d) for x, d in zip(p[1:], dt)]
-        return tuple(x.copy() for x in out)
-
-    def device_ptrs(self):
-        """(d_job_off, d_read, d_lo, d_hi, d_dist, d_start, d_end, d_status): kmx_rescues_view_device."""
-        return self._device_ptrs("kmx_rescues_view_device", 8)
+    _counts_of = ("kmx_rescues_counts", ("nr2", "n_jobs", "n_found", "n_concordant", "n_taken"))
+    _view_of = ("rescues", (("job_off", np.uint64, lambda c: c["nr2"] + 1), ("read", np.uint32, "n_jobs"), ("lo", np.uint32, "n_jobs"),
+                            ("hi", np.uint32, "n_jobs"), ("dist", np.uint8, "n_jobs"), ("start", np.uint32, "n_jobs"), ("end", np.uint32, "n_jobs"),
+                            ("status", np.uint8, "n_jobs")))
 
     def scripts(self, index, reads, m=False, scratch_bytes=0, scripts=None):
         """kmx_rescues_scripts: the CIGAR of every taken job (for a reverse placement that of the reverse complement against the
@@ -1243,35 +972,17 @@ class Rescues(_Handle):
         s = scripts or Scripts()
         o = Alignments._script_options(False, m, scratch_bytes)
         _check(lib().kmx_rescues_scripts(index._h, reads._h, self._h, C.byref(o), C.byref(s._h)))
-        return s
+        return _made_from(s, reads=reads)
 
-    def _per_read(self, scripts, strings, none=""):
-        """strings holds one value per entry of `scripts`: the value of every rescued public read, `none` for every other"""
+    def _entries(self, scripts):
+        """the entry of every rescued public read, -1 for every other"""
         job_off, read, _, _, _, _, _, status = self.host()
         read_sel_off = scripts.host()[0]
-        out = [none] * ((job_off.size - 1) // 2)
-        for r, st in zip(read, status):
-            if st == RESCUE_TAKEN and read_sel_off[int(r) + 1] > read_sel_off[int(r)]:
-                out[int(r) // 2] = strings[int(read_sel_off[int(r)])]
+        out = [-1] * ((job_off.size - 1) // 2)
+        for r, taken in zip(read, status == RESCUE_TAKEN):
+            if taken and read_sel_off[int(r) + 1] > read_sel_off[int(r)]:
+                out[int(r) // 2] = int(read_sel_off[int(r)])
         return out
-
-    def cigars(self, scripts, clips=None):
-        """One CIGAR string per public read from the Scripts of scripts(): "" where the read was not rescued.  clips (the Clips of
-        scripts.clip()): the clipped CIGARs, with S."""
-        return self._per_read(scripts, scripts.strings() if clips is None else clips.strings())
-
-    def mds(self, md, scripts):
-        """One MD string per public read from the Md of scripts.md(): "" where cigars(scripts) has none."""
-        return self._per_read(scripts, md.strings())
-
-    def clip_fields(self, clips, scripts):
-        """(tl, nm, score, has) per public read from the Clips of scripts().clip(): has False (and zeros) where the read was not
-        rescued.  For sam_lines, as the second of a tuple."""
-        return _clip_fields(self._per_read(scripts, range(scripts.counts()["n_sel"]), -1), clips)
-
-    def close(self):
-        super().close()
-        self._reads = None
 
 
 def sam_pair_fields(strand, start, cls, tlen):
@@ -1431,40 +1142,26 @@ class ApproxResult(_Handle):
     """Owns a kmx_approx_result handle (kmx_search_approx)."""
 
     _free = "kmx_approx_free"
+    _counts_of = ("kmx_approx_counts", ("nq", "n_hits", "n_candidates", "n_chunks"))
+    _view_of = ("approx", (("hit_off", np.uint64, lambda c: c["nq"] + 1), ("positions", np.uint32, "n_hits"), ("mismatches", np.uint8, "n_hits"),
+                           ("status", np.uint8, "nq")))             # on the host only: the C-ABI has no kmx_approx_view_device
 
-    def counts(self):
-        nq, hits, cand, chunks = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
-        _check(lib().kmx_approx_counts(self._h, C.byref(nq), C.byref(hits), C.byref(cand), C.byref(chunks)))
-        return {"nq": int(nq.value), "n_hits": int(hits.value), "n_candidates": int(cand.value), "n_chunks": int(chunks.value)}
-
-    def host(self):
-        """(hit_off[nq+1] u64, positions u32, mismatches u8, status[nq] u8) as numpy copies."""
-        c = self.counts()
-        a, b, m, s = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _check(lib().kmx_approx_view(self._h, C.byref(a), C.byref(b), C.byref(m), C.byref(s)))
-        nq, nh = c["nq"], c["n_hits"]
-        out = (_view(a.value, nq + 1, np.uint64), _view(b.value, nh, np.uint32), _view(m.value, nh, np.uint8), _view(s.value, nq, np.uint8))
-        return tuple(x.copy() for x in out)
+    def _column(self, fn, dtype, count):
+        return _view(self._ptrs(fn, 1)[0], self.counts()[count], dtype).copy()
 
     def lengths(self):
         """kmx_approx_lengths: the window length of every hit (u32, parallel to positions) of a search with edit=True."""
-        p = C.c_void_p()
-        _check(lib().kmx_approx_lengths(self._h, C.byref(p)))
-        return _view(p.value, self.counts()["n_hits"], np.uint32).copy()
+        return self._column("kmx_approx_lengths", np.uint32, "n_hits")
 
     def strands(self):
         """kmx_approx_strands: the strand of every hit (u8, parallel to positions; 0 forward, 1 reverse) of a search with
         strands=True."""
-        p = C.c_void_p()
-        _check(lib().kmx_approx_strands(self._h, C.byref(p)))
-        return _view(p.value, self.counts()["n_hits"], np.uint8).copy()
+        return self._column("kmx_approx_strands", np.uint8, "n_hits")
 
     def found(self):
         """kmx_approx_found: per query the hits left after loci / best and before the max_hits cap (u64[nq]) of a search with
         any of the three reporting options; more than the query's list holds when the cap cut it."""
-        p = C.c_void_p()
-        _check(lib().kmx_approx_found(self._h, C.byref(p)))
-        return _view(p.value, self.counts()["nq"], np.uint64).copy()
+        return self._column("kmx_approx_found", np.uint64, "nq")
 
 
 class Index:
@@ -1681,24 +1378,15 @@ class Index:
         roff = np.ascontiguousarray(roff, np.uint64)
         if max_span is None:
             max_span = 0xFFFFFFFF
-        r = self.search_windows(ranks, roff, w, stride)
-        try:
-            loci = r.vote(band, min_votes, max_occ)
-        finally:
-            r.close()
-        try:
+        with contextlib.ExitStack() as opened:                         # closes what was made, the last first, when a later call raises
+            with contextlib.closing(self.search_windows(ranks, roff, w, stride)) as r:
+                loci = r.vote(band, min_votes, max_occ)
+            opened.callback(loci.close)
             al = loci.align(self, ranks, roff, max_edits, max_span)
-        except Exception:
-            loci.close()
-            raise
-        if not scripts:
-            return loci, al
-        try:
-            return loci, al, al.scripts(self, loci, ranks, roff)
-        except Exception:
-            loci.close()
-            al.close()
-            raise
+            opened.callback(al.close)
+            out = (loci, al, al.scripts(self, loci, ranks, roff)) if scripts else (loci, al)
+            opened.pop_all()
+        return out
 
     def strand_reads(self, ranks, roff, complement, reads=None):
         """kmx_reads_strands: the reads go up once and the doubled batch (read i, then its reverse complement under the rank table
@@ -1730,68 +1418,8 @@ class Index:
         kmx_placements_secondaries with max_secondary = N and no max_delta.  clip (a dict of the scoring arguments of Scripts.clip,
         {} for the defaults; needs scripts=True) appends, as the very last element, the Clips of kmx_scripts_clip over the scripts;
         with tags=True the Md then is kmx_clips_md, that of the clipped entries."""
-        if tags and letters is None:
-            raise ValueError("map_reads_strands: tags=True needs letters")
-        if clip is not None and not scripts:
-            raise ValueError("map_reads_strands: clip needs scripts=True")
-        if max_span is None:
-            max_span = 0xFFFFFFFF
-        if secondaries:
-            out = self.map_reads_strands(ranks, roff, w, complement, stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags, letters,
-                                         clip=clip)
-            return self._with_secondaries(out, secondaries, 0 if clip is None else 1)
-        opened = []
-        try:
-            reads = self.strand_reads(ranks, roff, complement)
-            opened.append(reads)
-            d_ranks2, d_roff2, nr2, stream = reads.device_ptrs()
-            r = self.search_windows_device(d_ranks2, d_roff2, nr2, w, stride, stream=stream)
-            try:
-                loci = r.vote(band, min_votes, max_occ)
-            finally:
-                r.close()
-            opened.append(loci)
-            al = loci.align_device(self, d_ranks2, d_roff2, nr2, max_edits, max_span, stream=stream)
-            opened.append(al)
-            pl = al.fold_strands(loci, stream=stream)
-            pl._reads = reads
-            opened.append(pl)
-            if not scripts and not tags:
-                return reads, loci, al, pl
-            sc = pl.scripts(self, reads, loci, al)
-            opened.append(sc)
-            last = ()
-            if clip is not None:
-                cl = sc.clip(**clip)
-                cl._reads = reads
-                opened.append(cl)
-                last = (cl,)
-            if not tags:
-                return (reads, loci, al, pl, sc) + last
-            mq = pl.mapq(max_edits)
-            opened.append(mq)
-            md = sc.md(self, al, letters) if clip is None else cl.md(self, sc, al, letters)
-            md._reads = reads
-            return (reads, loci, al, pl, sc, SamTags(mq, md, None, None)) + last
-        except Exception:
-            for h in reversed(opened):
-                h.close()
-            raise
-
-    @staticmethod
-    def _with_secondaries(out, n, n_clips=0):
-        """out: what a chain call returns, (StrandReads, Loci, Alignments, Placements, ...) with the placements final; the same with
-        the Secondaries of kmx_placements_secondaries (max_secondary = n, no max_delta) appended, in front of the last n_clips
-        elements (the Clips, which stay last)."""
-        try:
-            cut = len(out) - n_clips
-            return out[:cut] + (out[3].secondaries(out[1], out[2], n),) + out[cut:]
-        except Exception:
-            for h in reversed(out):
-                for x in (h if isinstance(h, SamTags) else (h,)):
-                    if x is not None:
-                        x.close()
-            raise
+        return self._map_chain("map_reads_strands", ranks, roff, w, complement, None, None, stride, band, min_votes, max_occ, max_edits, max_span,
+                               scripts, tags, letters, secondaries, clip)
 
     def map_pairs(self, ranks, roff, w, complement, min_insert, max_insert, orientation=PAIR_FR, unpaired_penalty=None, stride=1, band=0,
                   min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False, rescue=False, rescue_edits=None, rescue_discordant=False,
@@ -1810,80 +1438,67 @@ class Index:
         Clips of the rescued mates' scripts.  Clips.scripts is the Scripts they were made from: SamTags.rescue_scripts with tags=True;
         without tags that Scripts is returned nowhere else, Clips.close() does not close it, and the caller closes it;
         with tags=True md and rescue_md then are kmx_clips_md and kmx_clips_rescues_md, those of the clipped entries."""
+        return self._map_chain("map_pairs", ranks, roff, w, complement, (min_insert, max_insert, orientation, unpaired_penalty),
+                               (max_edits if rescue_edits is None else rescue_edits, rescue_discordant) if rescue else None,
+                               stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags, letters, secondaries, clip)
+
+    def _map_chain(self, who, ranks, roff, w, complement, insert, rescue, stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags,
+                   letters, secondaries, clip):
+        """What map_reads_strands (insert=None) and map_pairs (insert: min_insert, max_insert, orientation, unpaired_penalty; rescue:
+        None or the rescue's edits and whether it takes DISCORDANT pairs) return: the front and the fold, then the stages that were
+        asked for, every one on the stream of the StrandReads."""
         if tags and letters is None:
-            raise ValueError("map_pairs: tags=True needs letters")
+            raise ValueError(f"{who}: tags=True needs letters")
         if clip is not None and not scripts:
-            raise ValueError("map_pairs: clip needs scripts=True")
-        if secondaries:
-            out = self.map_pairs(ranks, roff, w, complement, min_insert, max_insert, orientation, unpaired_penalty, stride, band, min_votes, max_occ,
-                                 max_edits, max_span, scripts, rescue, rescue_edits, rescue_discordant, tags, letters, clip=clip)
-            return self._with_secondaries(out, secondaries, 0 if clip is None else 2 if rescue else 1)
-        roff = np.ascontiguousarray(roff, np.uint64)
-        if (roff.size - 1) % 2:
-            raise ValueError("map_pairs: an odd number of reads; the reads are interleaved mates")
+            raise ValueError(f"{who}: clip needs scripts=True")
+        if insert is not None:
+            roff = np.ascontiguousarray(roff, np.uint64)
+            if (roff.size - 1) % 2:
+                raise ValueError(f"{who}: an odd number of reads; the reads are interleaved mates")
         if max_span is None:
             max_span = 0xFFFFFFFF
-        opened = []
-        try:
-            reads = self.strand_reads(ranks, roff, complement)
-            opened.append(reads)
+        pairs = res = sc = cl = rsc = rcl = sam = sec = None
+        with contextlib.ExitStack() as opened:                         # closes what was made, the last first, when a later call raises
+
+            def keep(h):
+                opened.callback(h.close)
+                return h
+
+            reads = keep(self.strand_reads(ranks, roff, complement))
             d_ranks2, d_roff2, nr2, stream = reads.device_ptrs()
-            r = self.search_windows_device(d_ranks2, d_roff2, nr2, w, stride, stream=stream)
-            try:
-                loci = r.vote(band, min_votes, max_occ)
-            finally:
-                r.close()
-            opened.append(loci)
-            al = loci.align_device(self, d_ranks2, d_roff2, nr2, max_edits, max_span, stream=stream)
-            opened.append(al)
-            pl, pairs = Placements(), Pairs()
-            opened += [pl, pairs]
-            al.fold_pairs(loci, min_insert, max_insert, orientation, unpaired_penalty, stream=stream, placements=pl, pairs=pairs)
-            pl._reads = pairs._reads = reads
-            out = [reads, loci, al, pl, pairs]
-            res = None
-            if rescue:
-                res = Rescues()
-                opened.append(res)
-                pairs.rescue(self, reads, loci, al, pl, min_insert, max_insert, max_edits if rescue_edits is None else rescue_edits, orientation,
-                             rescue_discordant, unpaired_penalty, rescues=res)
+            with contextlib.closing(self.search_windows_device(d_ranks2, d_roff2, nr2, w, stride, stream=stream)) as r:
+                loci = keep(r.vote(band, min_votes, max_occ))
+            al = keep(loci.align_device(self, d_ranks2, d_roff2, nr2, max_edits, max_span, stream=stream))
+            loci._reads = al._reads = reads                            # every handle below is made from these two, or from `reads`
+            if insert is None:
+                pl = keep(al.fold_strands(loci, stream=stream))
+            else:
+                pl, pairs = keep(Placements()), keep(Pairs())
+                min_insert, max_insert, orientation, unpaired_penalty = insert
+                al.fold_pairs(loci, min_insert, max_insert, orientation, unpaired_penalty, stream=stream, placements=pl, pairs=pairs)
+                if rescue is not None:
+                    res = keep(Rescues())
+                    pairs.rescue(self, reads, loci, al, pl, min_insert, max_insert, rescue[0], orientation, rescue[1], unpaired_penalty, rescues=res)
             if scripts or tags:
-                sc = pl.scripts(self, reads, loci, al)
-                opened.append(sc)
-                out.append(sc)
-            if res is not None:
-                out.append(res)
-            cl = rcl = rsc = None
+                sc = keep(pl.scripts(self, reads, loci, al))
             if clip is not None:
-                cl = sc.clip(**clip)
-                cl._reads = reads
-                opened.append(cl)
+                cl = keep(sc.clip(**clip))
                 if res is not None:
-                    rsc = res.scripts(self, reads)
-                    opened.append(rsc)
-                    rcl = rsc.clip(**clip)
-                    rcl._reads = reads
-                    opened.append(rcl)
+                    rsc = keep(res.scripts(self, reads))
+                    rcl = keep(rsc.clip(**clip))
             if tags:
-                budget = max_edits if not rescue or rescue_edits is None else max(max_edits, rescue_edits)
-                mq = pl.mapq(budget, pairs)
-                opened.append(mq)
-                md = sc.md(self, al, letters) if cl is None else cl.md(self, sc, al, letters)
-                md._reads = reads
-                opened.append(md)
+                mq = keep(pl.mapq(max_edits if rescue is None else max(max_edits, rescue[0]), pairs))
+                md = keep(sc.md(self, al, letters) if cl is None else cl.md(self, sc, al, letters))
                 rmd = None
                 if res is not None:
-                    if rsc is None:
-                        rsc = res.scripts(self, reads)
-                        opened.append(rsc)
-                    rmd = rsc.md(self, res, letters) if rcl is None else rcl.md(self, rsc, res, letters)
-                    rmd._reads = reads
-                out.append(SamTags(mq, md, rsc, rmd))
-            return tuple(out) + tuple(x for x in (cl, rcl) if x is not None)
-        except Exception:
-            for h in reversed(opened):
-                h.close()
-            raise
+                    rsc = rsc or keep(res.scripts(self, reads))
+                    rmd = keep(rsc.md(self, res, letters) if rcl is None else rcl.md(self, rsc, res, letters))
+                sam = SamTags(mq, md, rsc, rmd)
+            if secondaries:
+                sec = keep(pl.secondaries(loci, al, secondaries))       # last, on the placements as the rescue left them
+            opened.pop_all()
+        # the four of every chain, then in this order whatever was asked for: a stage that did not run leaves no gap
+        return tuple(x for x in (reads, loci, al, pl, pairs, sc, res, sam, sec, cl, rcl) if x is not None)
 
     def debug_words(self):
         w = np.zeros(16, np.uint64)

@@ -29,6 +29,31 @@ def test_library_exports_every_declared_symbol(engine):
         assert f" T {s}" in out
 
 
+def test_signature_table_has_the_arity_of_every_prototype(engine):
+    """ctypes takes an argtypes list with one entry too few or too many without a word: every prototype of include/kmx.h has as many
+    parameters as its entry of engine.SIGNATURES has argtypes, and every entry has both fields."""
+    hdr = open(os.path.join(ROOT, "include", "kmx.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", "", hdr)
+    protos = re.findall(r"\b(kmx_[a-z_0-9]+)\s*\(([^;{]*?)\)\s*;", hdr)
+    covered = []
+    for name, args in protos:
+        depth, commas = 0, 0
+        for ch in args:
+            depth += (ch in "([") - (ch in ")]")
+            commas += ch == "," and depth == 0
+        n_params = 0 if args.strip() in ("", "void") else commas + 1
+        restype, argtypes = engine.SIGNATURES[name]
+        assert isinstance(argtypes, list) and len(argtypes) == n_params, (name, n_params, len(argtypes))
+        covered.append(name)
+    assert len(covered) == len(set(covered)) >= 119
+    assert sorted(covered) == _declared_symbols() == sorted(engine.SIGNATURES)
+    L = engine.lib()
+    for name, (restype, argtypes) in engine.SIGNATURES.items():
+        assert getattr(L, name).restype is restype and list(getattr(L, name).argtypes) == argtypes, name
+        assert restype is None if name.endswith("_free") else restype is not None, name
+
+
 def test_library_carries_gfx950_code_objects():
     """The .so embeds a gfx950 code object holding every kernel (no other arch, no fallback)."""
     lib = os.path.join(ROOT, "kmer_index_amd", "libkmx.so")

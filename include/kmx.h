@@ -1322,7 +1322,8 @@ void kmx_secondaries_free(kmx_secondaries* s);
  *      differs from the scripts', or that live on another device, are refused after looking.  The secondaries need no MD here:
  *      XA carries only CIGAR and NM.
  *
- *      Left out: supplementary lines, TLEN from the clipped ends, a clip-aware MAPQ and a clip-aware choice between loci.
+ *      Left out: TLEN from the clipped ends, a clip-aware MAPQ and a clip-aware choice between loci (supplementary lines from the
+ *      clipped-off part of a read: kmx_clips_supplementaries, below).
  *      Untested: an index with more than one replica, and the different-devices refusals.  kmx_stats_get is not extended (see
  *      kmx_loci_align). */
 #define KMX_SOFT_CLIP 1
@@ -1351,6 +1352,108 @@ kmx_status kmx_clips_md(const kmx_index* index, const kmx_scripts* scripts, cons
 kmx_status kmx_clips_rescues_md(const kmx_index* index, const kmx_scripts* scripts, const kmx_clips* clips, const kmx_rescues* rescues,
                                 const uint8_t* letters, const kmx_md_options* options, void* stream, kmx_md** inout);
 void kmx_clips_free(kmx_clips* c);
+
+/* ---- Supplementary alignments: the parts of a split read (an extension, no reference interface; a caller detects the
+ *      capability by the macro KMX_MAP_SUPPLEMENTARY, KMX_VERSION is unchanged).  Soft clipping marks the part of a read that
+ *      does not belong to its placement as 'S'.  A chimeric or split read (across a structural-variant breakpoint, a fusion, a
+ *      tandem duplication) is one whose parts belong to different places: the vote gives a locus to each part, kmx_loci_align
+ *      aligns the whole read at each, and kmx_scripts_clip trims each script to the part that fits there.  This call picks, on
+ *      the device, the clipped entries that cover read letters the primary does not cover: what SAM writes as supplementary
+ *      records (FLAG 0x800) and links with SA:Z:.
+ *
+ *      THE PARTS ARE THE BEST-SCORING PARTS OF THE EDIT-OPTIMAL SCRIPTS, NOT SMITH-WATERMAN REALIGNMENTS: the limit of
+ *      kmx_scripts_clip holds here too.  No cell of a dynamic programme is computed again; a part that the unit-cost script of
+ *      the whole read at its locus does not contain is not found.
+ *
+ *      Input.  `reads`, `loci` and `alignments` are those of a doubled batch (nr2 internal reads, nr = nr2 / 2 public ones);
+ *      `placements` is the handle of kmx_alignments_fold_strands or of kmx_alignments_fold_pairs, before or after
+ *      kmx_pairs_rescue: its locus / strand are read.  `scripts` is kmx_alignments_scripts_device over the doubled reads WITH
+ *      KMX_SCRIPT_ALL and without KMX_SCRIPT_M: sel ascends over every aligned locus, read_sel_off[nr2 + 1] runs over the
+ *      internal reads.  `clips` is kmx_scripts_clip of those scripts.  `stream` NULL means the stream that filled the clips.  A
+ *      caller who passes another stream orders it behind the streams that filled the six handles (a rescue rewrites the
+ *      placements on the stream of the chain), and orders the stream of every later call that reads the supplementaries
+ *      behind it: the last kernel of this call is left in flight on `stream`, as with the other stream-taking calls of the
+ *      chain.  N = max_supplementary.  The call only reads the six handles.
+ *
+ *      The contract, in int64.  For public read i: m = min(roff2[2i + 1] - roff2[2i], 65535) (the aligner takes no read above
+ *      KMX_ALIGN_MAX_READ letters, so a longer read has no entry); ea = read_sel_off[2i], eb = read_sel_off[2i + 1],
+ *      ec = read_sel_off[2i + 2], each clamped into [0, n_sel] and made ascending.  Its entries are E = [ea, ec); entry e has
+ *      strand s(e) = 0 if e < eb, else 1, and the locus l = sel[e].
+ *        The READ INTERVAL of e on the original read is [q0, q1) = [sl[e], m - sr[e]) on strand 0 and [sr[e], m - sl[e]) on
+ *        strand 1 (a reverse entry's clip is in the coordinates of the reverse complement).
+ *        The TEXT INTERVAL of e is [t0, t1) = [start[l] + tl[e], end[l] - tr[e]).
+ *        e HAS RUNS when the clips' cig_off[e + 1] > cig_off[e].
+ *        The PRIMARY is the least p in E with sel[p] == locus[i] of the placements.  Read i has no entries and more[i] = 0
+ *        when it is unplaced (strand[i] == 255), when it is rescued (locus[i] == 0xFFFFFFFF: the rescue's scripts are a
+ *        different handle; left out), when there is no such p, or when p has no runs.
+ *        An entry c != p is a CANDIDATE when it has runs, its KMX_CLIP_LOW bit is clear, sel[c] < n_loci,
+ *        score[c] >= min_score and q1 - q0 >= min_len.
+ *        ov(a, b) = max(0, min(q1_a, q1_b) - max(q0_a, q0_b)).
+ *      The greedy selection.  T = {p}.  Repeat: among the candidates not yet taken with ov(c, t) <= max_overlap for EVERY t in
+ *      T, find the one with the greatest score, among equals the least e; if there is none, stop with more[i] = 0; if N have
+ *      been taken already, stop with more[i] = 1; otherwise take it into T.  TEXT POSITIONS PLAY NO PART IN ADMISSION: a part
+ *      may lie on the primary's own text interval, which is what a tandem duplication looks like.  Two loci that describe one
+ *      place cover the same read letters, so the read-overlap rule, applied to every member of T, keeps the shadow of the
+ *      primary and of every taken part out, as the ELSEWHERE rule does for the secondaries.
+ *      The runner-up.  second_score[x] of a taken entry x is the greatest score[c] over the candidates c != x with
+ *      ov(c, x) > max_overlap that lie ELSEWHERE from x on the clipped text intervals (s(c) != s(x), or
+ *      max(t0_c, t0_x) >= min(t1_c, t1_x): the fold's rule); 0 when there is none (a candidate's score is at least
+ *      min_score >= 1, so 0 is unambiguous).
+ *
+ *      Output.  The taken entries of read i in ASCENDING e.  sup_off[nr + 1] (u64) counts them per PUBLIC read.  Per entry x:
+ *      ent[x] (u32, the index into the entries of `scripts` and `clips`: CIGAR, NM and, through kmx_clips_md, MD of the part
+ *      are those of that entry, no further kernel is needed), locus[x] (u32), strand[x] (u8), q0[x], q1[x] (u16), t0[x],
+ *      t1[x] (u32, the low 32 bits), score[x], second_score[x] (i32), nm[x] (u16) and, when the alignments carry a contig
+ *      table, ctg[x] (u32) = the alignments' ctg[locus[x]] (the view is NULL otherwise).  Per public read: more[nr] (u8).
+ *      Counters: n_sup = sup_off[nr], n_split = the reads with at least one entry, n_truncated = the reads with more == 1.
+ *      Every index is bounded by n_loci, n_sel, nr and the read's own range: foreign or mismatched handles give meaningless but
+ *      harmless results (scripts made without KMX_SCRIPT_ALL hold one entry per read, so there are no candidates).
+ *      tests/supp_naive.py is this contract in executable form.
+ *
+ *      The supplementaries handle follows the lifecycle of the other chain handles: *inout == NULL allocates, a handle passed
+ *      in is reused and its earlier views end; the device arrays (kmx_supplementaries_view_device; sup_off is NULL after a
+ *      refusal or an error, the entry arrays when n_sup == 0, more when nr == 0) are complete in stream order when the call
+ *      returns; kmx_supplementaries_view copies to page-locked host memory on first use and synchronises, on the stream of the
+ *      call: 31 bytes per entry (35 with ctg), 9 per public read (sup_off always holds at least the one offset 0).  Any output
+ *      pointer may be NULL.
+ *
+ *      KMX_ERR_INVALID_ARGUMENT before any handle is looked at: a NULL argument, a struct_size that is too small, flags != 0,
+ *      max_supplementary == 0 or > KMX_SUPPLEMENTARY_MAX, min_len == 0 or > 65535, min_score < 1.  After looking (the
+ *      supplementaries handle, when there is one, then holds an empty result): nr2 odd, placements whose 2 nr differs from the
+ *      reads' nr2, loci, alignments or scripts whose nr differs from it, loci and alignments that disagree in n_loci, clips
+ *      whose n_sel differs from the scripts', scripts made with KMX_SCRIPT_M, handles on different devices;
+ *      KMX_ERR_TOO_LARGE when nr * N >= 2^32.
+ *
+ *      Left out: parts of rescued reads, hard clips, pair-aware parts, a realignment of the part, and scripts only for the
+ *      reads whose primary is clipped (KMX_SCRIPT_ALL over every aligned locus is the cost of this call's input).  No call
+ *      here writes the SAM lines.  Untested: an index with more than one replica, and the different-devices refusals.
+ *      kmx_stats_get is not extended (see kmx_loci_align). */
+#define KMX_MAP_SUPPLEMENTARY 1
+#define KMX_SUPPLEMENTARY_MAX 8
+typedef struct kmx_supplementary_options {
+    uint32_t struct_size;        /* = sizeof(kmx_supplementary_options): 24 */
+    uint32_t max_supplementary;  /* N, in 1 .. KMX_SUPPLEMENTARY_MAX */
+    uint32_t min_len;            /* the read letters a part must keep, 1 .. 65535 */
+    uint32_t max_overlap;        /* the read letters a part may share with each part taken before it */
+    int32_t min_score;           /* >= 1: the clip score a part needs */
+    uint32_t flags;              /* 0 */
+} kmx_supplementary_options;
+typedef struct kmx_supplementaries kmx_supplementaries;
+kmx_status kmx_clips_supplementaries(const kmx_strand_reads* reads, const kmx_loci* loci, const kmx_alignments* alignments,
+                                     const kmx_placements* placements, const kmx_scripts* scripts, const kmx_clips* clips,
+                                     const kmx_supplementary_options* options, void* stream, kmx_supplementaries** inout);
+kmx_status kmx_supplementaries_counts(const kmx_supplementaries* s, uint64_t* nr, uint64_t* n_sup, uint64_t* n_split,
+                                      uint64_t* n_truncated);
+kmx_status kmx_supplementaries_view(kmx_supplementaries* s, const uint64_t** sup_off /* nr + 1 */, const uint32_t** ent /* n_sup */,
+                                    const uint32_t** locus, const uint8_t** strand, const uint16_t** q0, const uint16_t** q1,
+                                    const uint32_t** t0, const uint32_t** t1, const int32_t** score, const int32_t** second_score,
+                                    const uint16_t** nm, const uint32_t** ctg /* or NULL */, const uint8_t** more /* nr */);
+kmx_status kmx_supplementaries_view_device(const kmx_supplementaries* s, const uint64_t** d_sup_off, const uint32_t** d_ent,
+                                           const uint32_t** d_locus, const uint8_t** d_strand, const uint16_t** d_q0,
+                                           const uint16_t** d_q1, const uint32_t** d_t0, const uint32_t** d_t1, const int32_t** d_score,
+                                           const int32_t** d_second_score, const uint16_t** d_nm, const uint32_t** d_ctg,
+                                           const uint8_t** d_more);
+void kmx_supplementaries_free(kmx_supplementaries* s);
 
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.

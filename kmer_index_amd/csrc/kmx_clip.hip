@@ -210,7 +210,8 @@ kmx_status clip_run(const kmx::ScriptsAccess& S, const kmx_clip_options& o, hipS
 kmx::ClipsAccess kmx::clips_access(const kmx_clips* c)
 {
     return ClipsAccess{c->device, c->n_sel, c->n_ops, c->tl.as<uint16_t>(), c->tr.as<uint16_t>(), c->cig_off.as<uint64_t>(),
-                       c->cigar.as<uint32_t>()};
+                       c->cigar.as<uint32_t>(), c->stream, c->score.as<int32_t>(), c->sl.as<uint16_t>(), c->sr.as<uint16_t>(), c->nm.as<uint16_t>(),
+                       c->cflags.as<uint8_t>()};
 }
 
 extern "C" {

@@ -532,7 +532,8 @@ kmx_status script_call(const char* fn, const kmx_index* index, const kmx_loci* l
 
 kmx::ScriptsAccess kmx::scripts_access(const kmx_scripts* s)
 {
-    return ScriptsAccess{s->device, s->stream, s->n_sel, s->n_ops, s->flags, s->sel.as<uint32_t>(), s->cig_off.as<uint64_t>(), s->cigar.as<uint32_t>()};
+    return ScriptsAccess{s->device, s->stream, s->n_sel, s->n_ops, s->flags, s->sel.as<uint32_t>(), s->cig_off.as<uint64_t>(), s->cigar.as<uint32_t>(),
+                         s->nr, s->read_sel_off.as<uint64_t>()};
 }
 
 kmx_status kmx::scripts_with_best(const char* fn, const kmx_index* index, const kmx_loci* loci, const kmx_alignments* alignments, const void* d_ranks,

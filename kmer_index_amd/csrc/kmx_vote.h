@@ -98,6 +98,8 @@ struct ScriptsAccess {
     const uint32_t* sel;           // [n_sel]
     const uint64_t* cig_off;       // [n_sel + 1]
     const uint32_t* cigar;         // [n_ops]
+    uint64_t nr;                   // the reads the entries run over (kmx_supplementary.hip)
+    const uint64_t* read_sel_off;  // [nr + 1]
 };
 ScriptsAccess scripts_access(const kmx_scripts* s);   // kmx_script.hip
 
@@ -116,7 +118,8 @@ JobsAccess secondaries_access(const kmx_secondaries* s);   // kmx_secondary.hip
 
 // What the MD of clipped entries (kmx_clips_md, kmx_clips_rescues_md; kmx_tags.hip) needs from a clips handle (kmx_clip.hip owns
 // struct kmx_clips): the clipped runs and the text letters clipped off either side.  The per-entry arrays are only looked at when
-// n_sel > 0, cigar when n_ops > 0; a handle that no call has filled (or whose last call was refused) has n_sel = 0.
+// n_sel > 0, cigar when n_ops > 0; a handle that no call has filled (or whose last call was refused) has n_sel = 0.  The supplementary
+// alignments (kmx_supplementary.hip) read the other per-entry values as well.
 struct ClipsAccess {
     int device;
     uint64_t n_sel, n_ops;
@@ -124,6 +127,12 @@ struct ClipsAccess {
     const uint16_t* tr;
     const uint64_t* cig_off;       // [n_sel + 1]
     const uint32_t* cigar;         // [n_ops]
+    hipStream_t stream;            // the stream of the call that filled the handle
+    const int32_t* score;          // [n_sel]
+    const uint16_t* sl;
+    const uint16_t* sr;
+    const uint16_t* nm;
+    const uint8_t* cflags;
 };
 ClipsAccess clips_access(const kmx_clips* c);   // kmx_clip.hip
 

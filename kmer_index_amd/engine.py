@@ -34,6 +34,7 @@ RESCUE_NONE, RESCUE_FOUND, RESCUE_CONCORDANT, RESCUE_TAKEN = 0, 1, 2, 3
 LOCATE_MATES, NO_CONTIG = 1, 0xFFFFFFFF
 SECONDARY_MAX, SECONDARY_NO_DELTA = 32, 0xFFFFFFFF
 CLIP_LOW = 1
+SUPPLEMENTARY_MAX = 8
 
 
 class KmxError(RuntimeError):
@@ -104,6 +105,11 @@ class SecondaryOptions(C.Structure):
 class ClipOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("match", C.c_uint32), ("mismatch", C.c_uint32), ("gap_open", C.c_uint32),
                 ("gap_extend", C.c_uint32), ("clip_penalty", C.c_uint32), ("min_score", C.c_int32), ("flags", C.c_uint32)]
+
+
+class SupplementaryOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_supplementary", C.c_uint32), ("min_len", C.c_uint32), ("max_overlap", C.c_uint32),
+                ("min_score", C.c_int32), ("flags", C.c_uint32)]
 
 
 class KernelStat(C.Structure):
@@ -253,6 +259,12 @@ SIGNATURES = {
     "kmx_clips_md": (st, [vp, vp, vp, vp, vp, P(MdOptions), vp, P(vp)]),
     "kmx_clips_rescues_md": (st, [vp, vp, vp, vp, vp, P(MdOptions), vp, P(vp)]),
     "kmx_clips_free": (None, [vp]),
+    # supplementary alignments
+    "kmx_clips_supplementaries": (st, [vp, vp, vp, vp, vp, vp, P(SupplementaryOptions), vp, P(vp)]),
+    "kmx_supplementaries_counts": (st, [vp] + [P(u64)] * 4),
+    "kmx_supplementaries_view": (st, [vp] + [P(vp)] * 13),
+    "kmx_supplementaries_view_device": (st, [vp] + [P(vp)] * 13),
+    "kmx_supplementaries_free": (None, [vp]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -705,6 +717,23 @@ class Clips(_Handle):
             raise TypeError("Clips.md: source is an Alignments or a Rescues")
         return _made_from(_md_call(fn, index, (scripts, self, source), letters, stream, md), self)
 
+    def supplementaries(self, reads, loci, alignments, placements, scripts, max_supplementary=4, min_len=20, max_overlap=10, min_score=20,
+                        stream=0, supplementaries=None):
+        """kmx_clips_supplementaries: these are the clips of `scripts`, the all=True scripts of the doubled batch `reads` (no m=True);
+        up to max_supplementary (<= SUPPLEMENTARY_MAX) further parts per read, chosen greedily by (score, entry) among the clipped
+        entries of both strands that keep min_len read letters, score at least min_score and share at most max_overlap read letters
+        with the primary and with every part taken before.  The parts are the best-scoring parts of the edit-optimal scripts, not
+        realignments.  The four defaults are judgements (a part of 20 letters at k = 10 has seeds enough to be voted for; 10 letters
+        of overlap is what microhomology at a breakpoint may share): nothing measures them.  stream=0: the stream that filled this
+        handle.  Returns a Supplementaries (`supplementaries` reuses one)."""
+        out = supplementaries or Supplementaries()
+        o = SupplementaryOptions(C.sizeof(SupplementaryOptions), int(max_supplementary), int(min_len), int(max_overlap), int(min_score), 0)
+        _check(lib().kmx_clips_supplementaries(reads._h, loci._h, alignments._h, placements._h, scripts._h, self._h, C.byref(o), stream or None,
+                                               C.byref(out._h)))
+        if not out._owns:
+            out.all_scripts, out.all_clips = scripts, self
+        return _made_from(out, self, reads=reads)
+
 
 def _clip_fields(entry, clips):
     """entry[nr]: the entry of every public read among those of `clips`, -1 for none -> (tl i64, nm i64, score i64, has bool)"""
@@ -926,6 +955,156 @@ class Secondaries(_Handle):
         return xa_strings(sec_off, h[5], start, ctg, _runs_strings(h[7], h[8]), strand_names, located, rname, shift=h[3])
 
 
+def supplementary_mapq(score, second_score, cap=60):
+    """The MAPQ of every part from its score and its runner-up's: 0 where second_score >= score, else
+    min(cap, cap (score - second_score) // score).  A stated gap rule like kmx_placements_mapq's, not a calibrated one.  Pure numpy."""
+    score = np.asarray(score, np.int64)
+    second = np.asarray(second_score, np.int64)
+    q = np.minimum(cap, cap * (score - second) // np.maximum(score, 1))
+    return np.where(second >= score, 0, q).astype(np.uint8)
+
+
+def sa_strings(sup_off, primary, entries, located=None, rname=None, strand_names="+-"):
+    """The SA:Z: values of the records of every public read.  primary = (pos, strand, cigars, mapq, nm[, ctg]) with one value per
+    public read, entries = (pos, strand, cigars, mapq, nm[, ctg]) with one per entry of a Supplementaries (sup_off counts them per
+    read): pos the 0-based position of the clipped record in the text (start + tl; t0), cigars the clipped CIGARs.  The records of a
+    read are its primary and then its entries, each as rname,pos,strand,CIGAR,mapQ,NM; with pos 1-based; located=(names, ctg_off)
+    with ctg: the contig's name and a contig-local pos, otherwise `rname` and the position in the text.  Returns per read the list
+    [the primary's value, entry 0's, ...]: every record's value is the other records of its read, in that order ("" for the primary
+    of a read without entries).  Pure Python: no device is needed."""
+    sup_off = np.asarray(sup_off, np.uint64)
+    if located is None and rname is None:
+        raise ValueError("sa: give rname, or located=(names, ctg_off)")
+    if located is not None and (len(primary) < 6 or len(entries) < 6 or primary[5] is None or entries[5] is None):
+        raise ValueError("sa: located needs the ctg of the primaries and of the entries")
+
+    def record(src, k):
+        if located is not None:
+            names, ctg_off = located
+            c = int(src[5][k])
+            name, pos = names[c], int(src[0][k]) - int(ctg_off[c]) + 1
+        else:
+            name, pos = rname, int(src[0][k]) + 1
+        return f"{name},{pos},{strand_names[int(src[1][k])]},{src[2][k] or '*'},{int(src[3][k])},{int(src[4][k])};"
+
+    out = []
+    for i in range(sup_off.size - 1):
+        a, b = int(sup_off[i]), int(sup_off[i + 1])
+        if a == b:
+            out.append([""])
+            continue
+        recs = [record(primary, i)] + [record(entries, x) for x in range(a, b)]
+        out.append(["".join(r for k, r in enumerate(recs) if k != j) for j in range(len(recs))])
+    return out
+
+
+class Supplementaries(_Handle):
+    """Owns a kmx_supplementaries handle (kmx_clips_supplementaries): up to N further parts per public read, the entries of read i
+    being [sup_off[i], sup_off[i + 1]); ent[x] indexes the entries of the all-loci Scripts and Clips the handle was made from.
+    all_scripts / all_clips are those two when the chain keyword supplementary= made the handle, and close() then closes them too
+    (the chain registers every handle it makes as it makes it, so nothing leaks when a later stage raises); a handle of
+    Clips.supplementaries has all_clips (and all_clips.scripts) for reference only and closes neither."""
+
+    _free = "kmx_supplementaries_free"
+    _counts_of = ("kmx_supplementaries_counts", ("nr", "n_sup", "n_split", "n_truncated"))
+    _view_of = ("supplementaries", (("sup_off", np.uint64, lambda c: c["nr"] + 1), ("ent", np.uint32, "n_sup"), ("locus", np.uint32, "n_sup"),
+                                    ("strand", np.uint8, "n_sup"), ("q0", np.uint16, "n_sup"), ("q1", np.uint16, "n_sup"), ("t0", np.uint32, "n_sup"),
+                                    ("t1", np.uint32, "n_sup"), ("score", np.int32, "n_sup"), ("second_score", np.int32, "n_sup"),
+                                    ("nm", np.uint16, "n_sup"), ("ctg", np.uint32, "n_sup"), ("more", np.uint8, "nr")))
+
+    def __init__(self):
+        super().__init__()
+        self.all_scripts = self.all_clips = None
+        self._owns = False          # the chain made all_scripts / all_clips for this handle alone
+
+    def close(self):
+        super().close()
+        if self._owns:
+            for h in (self.all_clips, self.all_scripts):
+                if h is not None:
+                    h.close()
+        self.all_scripts = self.all_clips = None
+        self._owns = False
+
+    def host(self):
+        """ctg is None when the alignments carried no contig table."""
+        p = self._ptrs("kmx_supplementaries_view", 13)
+        out = self._arrays(p)
+        return out[:11] + (out[11] if p[11] else None,) + out[12:]
+
+    def mapq(self, cap=60):
+        """supplementary_mapq of every entry (u8[n_sup])."""
+        h = self.host()
+        return supplementary_mapq(h[8], h[9], cap)
+
+    def cigars(self, clips=None):
+        """One clipped CIGAR string per entry, from `clips` (default all_clips), the Clips the handle was made from."""
+        strings = (clips or self.all_clips).strings()
+        return [strings[int(e)] for e in self.host()[1]]
+
+    def mds(self, md):
+        """One MD string per entry from the Md of the all-loci clips (Clips.md over the all-loci scripts and the alignments)."""
+        strings = md.strings()
+        return [strings[int(e)] for e in self.host()[1]]
+
+    def sa(self, placements_host, cigars, clip_fields, mapq, cap=60, located=None, located_host=None, rname=None, clips=None, strand_names="+-"):
+        """sa_strings of this handle: per public read the SA:Z: values of its primary and of its entries.  placements_host:
+        Placements.host(); cigars, clip_fields: the primaries' clipped CIGARs and (tl, nm, score, has) per read (Placements.cigars(
+        scripts, clips) and .clip_fields(clips, scripts) over the placements' own scripts); mapq: Mapq.host().  The entries take
+        their CIGARs from `clips` (default all_clips) and their MAPQ from mapq(cap).  located=(names, ctg_off) with located_host
+        (Located.host()): contig names and contig-local positions; otherwise `rname` names the one reference."""
+        h = self.host()
+        strand, start = np.asarray(placements_host[1]), np.asarray(placements_host[3], np.int64)
+        pos = start + np.asarray(clip_fields[0], np.int64)
+        primary = (pos, np.where(strand == 1, 1, 0), cigars, mapq, clip_fields[1], None if located_host is None else located_host[0])
+        entries = (h[6], h[3], self.cigars(clips), self.mapq(cap), h[10], h[11])
+        return sa_strings(h[0], primary, entries, located, rname, strand_names)
+
+
+def sam_supplementary_lines(primary_lines, ranks, roff, letters, complement, sigma, sup_host, cigars, mds, mapq, sa, rname=None, located=None):
+    """The supplementary SAM lines (FLAG 0x800, no newline) of a batch, read after read in the order of the entries.
+    primary_lines: the lines of sam_lines for the same reads (QNAME, the pair bits of FLAG, RNEXT and PNEXT are taken from them);
+    sup_host: Supplementaries.host(); cigars, mds, mapq: one per entry (Supplementaries.cigars / .mds / .mapq); sa: what sa_strings
+    returned.  A line has FLAG 0x800, plus 0x10 on strand 1, plus the primary's pair bits (0x1, 0x8, 0x20, 0x40, 0x80: not 0x2);
+    RNAME and POS of the part (located=(names, ctg_off): its contig and a contig-local POS, else `rname` and t0 + 1); the entry's
+    MAPQ; the clipped CIGAR with its S runs (soft, not hard: SEQ is the whole read, reverse-complemented on strand 1); RNEXT and
+    PNEXT as on the primary line (= only where the mate lies on the part's own reference); TLEN 0; NM:i:, MD:Z:, AS:i: and SA:Z:.
+    Pure Python / numpy: no device is needed."""
+    table = _letters_table(letters)
+    comp = np.ascontiguousarray(complement, np.uint8)
+    ranks = np.asarray(ranks, np.uint8)
+    roff = np.asarray(roff, np.uint64)
+    sup_off, _, _, strand, _, _, t0, _, score, _, nm, ctg, _ = sup_host
+    if located is None and rname is None:
+        raise ValueError("sam_supplementary_lines: give rname, or located=(names, ctg_off)")
+    if located is not None and ctg is None:
+        raise ValueError("sam_supplementary_lines: located needs the ctg of a Supplementaries made under a contig table")
+    if not (roff.size - 1 == len(primary_lines) == len(sa) == sup_off.size - 1) or not (len(cigars) == len(mds) == len(mapq) == strand.size):
+        raise ValueError("sam_supplementary_lines: the arrays disagree in the number of reads or of entries")
+    lines = []
+    for i in range(sup_off.size - 1):
+        a, b = int(sup_off[i]), int(sup_off[i + 1])
+        if a == b:
+            continue
+        first = primary_lines[i].split("\t")
+        q = ranks[int(roff[i]):int(roff[i + 1])]
+        if (q >= sigma).any():
+            raise ValueError(f"sam_supplementary_lines: read {i} holds a letter outside the alphabet")
+        mate_name = first[2] if first[6] == "=" else first[6]
+        for j, x in enumerate(range(a, b)):
+            if located is not None:
+                names, ctg_off = located
+                name, pos = names[int(ctg[x])], int(t0[x]) - int(ctg_off[int(ctg[x])]) + 1
+            else:
+                name, pos = rname, int(t0[x]) + 1
+            flag = 0x800 | (0x10 if strand[x] == 1 else 0) | (int(first[1]) & (0x1 | 0x8 | 0x20 | 0x40 | 0x80))
+            seq = table[comp[q[::-1]] if strand[x] == 1 else q].tobytes().decode("latin-1") or "*"
+            rnext = "*" if mate_name == "*" else "=" if mate_name == name else mate_name
+            lines.append("\t".join([first[0], str(flag), name, str(pos), str(int(mapq[x])), cigars[x] or "*", rnext, first[7], "0", seq, "*",
+                                    f"NM:i:{int(nm[x])}", f"MD:Z:{mds[x]}", f"AS:i:{int(score[x])}", f"SA:Z:{sa[i][j + 1]}"]))
+    return lines
+
+
 class Located(_Handle):
     """Owns a kmx_located handle (kmx_placements_locate): the contig and the contig-local position of every public read, NO_CONTIG
     and 0 for an unplaced one."""
@@ -1047,7 +1226,7 @@ def sam_header(names, ctg_off):
 
 
 def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements_host, cigars, mds, mapq, pairs_host=None, located_host=None,
-              xa=None, clip_fields=None):
+              xa=None, clip_fields=None, sa=None):
     """One SAM line (no newline) per public read from host arrays: the reads (ranks, roff), the rank -> letter table, the rank
     complement table, Placements.host(), the CIGAR and MD strings per read (Placements.cigars / .mds; a tuple of two lists, the
     placements' and the rescue's, gives a rescued read those of the rescue), Mapq.host() and, for paired reads, Pairs.host().
@@ -1060,8 +1239,10 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
     leaves the lines as they were.  clip_fields (Placements.clip_fields(); a tuple of two, the placements' and the rescue's, like
     cigars) writes soft-clipped records: cigars and mds then are the clipped ones (Clips.strings(), Clips.md()), a read's POS is
     start + tl, and so are its contig-local POS and its mate's PNEXT, NM:i: is the clipped nm, and AS:i:<score> follows MD:Z:.  TLEN
-    stays the pair fold's, measured between the UNCLIPPED outer ends.  None leaves every line as it was.  Pure Python / numpy: no
-    device is needed."""
+    stays the pair fold's, measured between the UNCLIPPED outer ends.  None leaves every line as it was.  sa (what sa_strings or
+    Supplementaries.sa returned: per read a list whose first value is the primary's) appends SA:Z:<value> behind XA:Z: to every
+    placed read whose value is not empty; None leaves every line as it was (the FLAG 0x800 lines: sam_supplementary_lines).  Pure
+    Python / numpy: no device is needed."""
     table = _letters_table(letters)
     comp = np.ascontiguousarray(complement, np.uint8)
     if table.size < sigma or comp.size < sigma:
@@ -1076,6 +1257,8 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
         raise ValueError("sam_lines: the arrays disagree in the number of reads")
     if xa is not None and len(xa) != nr:
         raise ValueError("sam_lines: xa disagrees in the number of reads")
+    if sa is not None and len(sa) != nr:
+        raise ValueError("sam_lines: sa disagrees in the number of reads")
     placed = strand != 255
     shift = nm = score = has = None
     if clip_fields is not None:
@@ -1134,6 +1317,8 @@ def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements
                 fields.append(f"AS:i:{int(score[i])}")
             if xa is not None and xa[i]:
                 fields.append(f"XA:Z:{xa[i]}")
+            if sa is not None and sa[i][0]:
+                fields.append(f"SA:Z:{sa[i][0]}")
         lines.append("\t".join(fields))
     return lines
 
@@ -1408,7 +1593,7 @@ class Index:
         return s
 
     def map_reads_strands(self, ranks, roff, w, complement, stride=1, band=0, min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False,
-                          tags=False, letters=None, secondaries=0, clip=None):
+                          tags=False, letters=None, secondaries=0, clip=None, supplementary=None):
         """map_reads on both strands: kmx_reads_strands, kmx_search_windows_device, kmx_windows_vote, kmx_loci_align_device and
         kmx_alignments_fold_strands in a row, all on the stream of the StrandReads.  Returns (StrandReads, Loci, Alignments,
         Placements): the loci and alignments are those of the doubled batch (internal read 2i is read i, 2i + 1 its reverse
@@ -1417,13 +1602,16 @@ class Index:
         kmx_placements_mapq and kmx_scripts_md.  secondaries=N > 0 appends, behind everything else, the Secondaries of
         kmx_placements_secondaries with max_secondary = N and no max_delta.  clip (a dict of the scoring arguments of Scripts.clip,
         {} for the defaults; needs scripts=True) appends, as the very last element, the Clips of kmx_scripts_clip over the scripts;
-        with tags=True the Md then is kmx_clips_md, that of the clipped entries."""
+        with tags=True the Md then is kmx_clips_md, that of the clipped entries.  supplementary (a dict of the arguments of
+        Clips.supplementaries, {} for the defaults; needs scripts=True and clip) runs last: the KMX_SCRIPT_ALL scripts of the
+        doubled batch, their clips under the same `clip` scoring and kmx_clips_supplementaries on the placements, and appends, as
+        the very last element, the Supplementaries; its all_scripts / all_clips are those two handles and its close() closes them."""
         return self._map_chain("map_reads_strands", ranks, roff, w, complement, None, None, stride, band, min_votes, max_occ, max_edits, max_span,
-                               scripts, tags, letters, secondaries, clip)
+                               scripts, tags, letters, secondaries, clip, supplementary)
 
     def map_pairs(self, ranks, roff, w, complement, min_insert, max_insert, orientation=PAIR_FR, unpaired_penalty=None, stride=1, band=0,
                   min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False, rescue=False, rescue_edits=None, rescue_discordant=False,
-                  tags=False, letters=None, secondaries=0, clip=None):
+                  tags=False, letters=None, secondaries=0, clip=None, supplementary=None):
         """map_reads_strands for paired reads: the reads are interleaved mates (read 2p is mate 1 of pair p, read 2p + 1 its mate 2, so
         their number is even), and kmx_alignments_fold_pairs stands in the fold's place.  Returns (StrandReads, Loci, Alignments,
         Placements, Pairs); scripts=True appends kmx_placements_scripts (the CIGARs of the chosen loci).  rescue=True runs
@@ -1437,13 +1625,16 @@ class Index:
         scripts=True) appends, as the very last elements, the Clips of kmx_scripts_clip over the scripts and, with rescue=True, the
         Clips of the rescued mates' scripts.  Clips.scripts is the Scripts they were made from: SamTags.rescue_scripts with tags=True;
         without tags that Scripts is returned nowhere else, Clips.close() does not close it, and the caller closes it;
-        with tags=True md and rescue_md then are kmx_clips_md and kmx_clips_rescues_md, those of the clipped entries."""
+        with tags=True md and rescue_md then are kmx_clips_md and kmx_clips_rescues_md, those of the clipped entries.
+        supplementary (a dict of the arguments of Clips.supplementaries, {} for the defaults; needs scripts=True and clip) runs
+        last, on the placements as the rescue left them (a rescued mate has no parts), and appends the Supplementaries behind the
+        Clips, as in map_reads_strands."""
         return self._map_chain("map_pairs", ranks, roff, w, complement, (min_insert, max_insert, orientation, unpaired_penalty),
                                (max_edits if rescue_edits is None else rescue_edits, rescue_discordant) if rescue else None,
-                               stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags, letters, secondaries, clip)
+                               stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags, letters, secondaries, clip, supplementary)
 
     def _map_chain(self, who, ranks, roff, w, complement, insert, rescue, stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags,
-                   letters, secondaries, clip):
+                   letters, secondaries, clip, supplementary=None):
         """What map_reads_strands (insert=None) and map_pairs (insert: min_insert, max_insert, orientation, unpaired_penalty; rescue:
         None or the rescue's edits and whether it takes DISCORDANT pairs) return: the front and the fold, then the stages that were
         asked for, every one on the stream of the StrandReads."""
@@ -1451,13 +1642,15 @@ class Index:
             raise ValueError(f"{who}: tags=True needs letters")
         if clip is not None and not scripts:
             raise ValueError(f"{who}: clip needs scripts=True")
+        if supplementary is not None and (not scripts or clip is None):
+            raise ValueError(f"{who}: supplementary needs scripts=True and clip")
         if insert is not None:
             roff = np.ascontiguousarray(roff, np.uint64)
             if (roff.size - 1) % 2:
                 raise ValueError(f"{who}: an odd number of reads; the reads are interleaved mates")
         if max_span is None:
             max_span = 0xFFFFFFFF
-        pairs = res = sc = cl = rsc = rcl = sam = sec = None
+        pairs = res = sc = cl = rsc = rcl = sam = sec = sup = None
         with contextlib.ExitStack() as opened:                         # closes what was made, the last first, when a later call raises
 
             def keep(h):
@@ -1496,9 +1689,14 @@ class Index:
                 sam = SamTags(mq, md, rsc, rmd)
             if secondaries:
                 sec = keep(pl.secondaries(loci, al, secondaries))       # last, on the placements as the rescue left them
+            if supplementary is not None:                              # last too: every aligned locus of both strands, clipped as the winners are
+                asc = keep(al.scripts_device(self, loci, d_ranks2, d_roff2, nr2, all=True, stream=stream))
+                acl = keep(asc.clip(**clip, stream=stream))
+                sup = keep(acl.supplementaries(reads, loci, al, pl, asc, **supplementary, stream=stream))
+                sup.all_scripts, sup.all_clips, sup._owns = asc, acl, True
             opened.pop_all()
         # the four of every chain, then in this order whatever was asked for: a stage that did not run leaves no gap
-        return tuple(x for x in (reads, loci, al, pl, pairs, sc, res, sam, sec, cl, rcl) if x is not None)
+        return tuple(x for x in (reads, loci, al, pl, pairs, sc, res, sam, sec, cl, rcl, sup) if x is not None)
 
     def debug_words(self):
         w = np.zeros(16, np.uint64)

@@ -1274,6 +1274,7 @@ void kmx_secondaries_free(kmx_secondaries* s);
  *      THIS IS POST-ALIGNMENT TRIMMING OF THE EDIT-OPTIMAL SCRIPT, NOT A SMITH-WATERMAN REALIGNMENT.  The clipped alignment is
  *      the best-scoring PART OF THE CANONICAL SCRIPT, not the best local alignment of the read: no cell of a dynamic programme
  *      is computed again, and a better local alignment that the unit-cost script does not contain is not found.
+ *      kmx_scripts_realign (below, KMX_REALIGN) is the call that computes one, inside the band of the script.
  *
  *      Input.  The call takes ONLY a scripts handle: no index, no reads, no alignments.  It serves the scripts of
  *      kmx_alignments_scripts[_device] (KMX_SCRIPT_ALL or not), kmx_placements_scripts, kmx_rescues_scripts and
@@ -1352,6 +1353,90 @@ kmx_status kmx_clips_md(const kmx_index* index, const kmx_scripts* scripts, cons
 kmx_status kmx_clips_rescues_md(const kmx_index* index, const kmx_scripts* scripts, const kmx_clips* clips, const kmx_rescues* rescues,
                                 const uint8_t* letters, const kmx_md_options* options, void* stream, kmx_md** inout);
 void kmx_clips_free(kmx_clips* c);
+
+/* ---- Realignment: every script aligned again, locally and with affine gaps (an extension, no reference interface; a caller
+ *      detects the capability by the macro KMX_REALIGN, KMX_VERSION is unchanged).  Every script of the chain comes from one
+ *      unit-cost, end-to-end alignment, and kmx_scripts_clip only trims it: at unit cost a deletion of twelve letters costs what
+ *      twelve scattered edits cost, and the canonical walk prefers diagonals, so a long gap comes out in pieces
+ *      ('63=1D1=3D2=3D1=3D2=1D1=1D80=' where the read is '70=12D80='), and AS:i is the score of that path.
+ *      kmx_scripts_realign aligns every entry of a scripts handle again: a LOCAL, AFFINE-GAP alignment (Gotoh) of the read and
+ *      text[start, end), confined to the rectangle and to the band |j - i| <= dist of the script, and fills an ordinary clips
+ *      handle.  kmx_clips_md, kmx_clips_supplementaries and the views serve that handle as they serve one of
+ *      kmx_scripts_clip; the text interval of entry e still is [start + tl, end - tr).
+ *
+ *      Input.  The scripts of kmx_alignments_scripts[_device] (KMX_SCRIPT_ALL or not) or of kmx_placements_scripts, the
+ *      alignments handle their sel indexes, the index, and the reads that were aligned (for the scripts of the placements: the
+ *      doubled batch).  Entry e of the clips is entry e of the scripts.  The host form takes host arrays and runs on the
+ *      stream that filled the scripts; the device form takes device arrays and the caller's stream, that stream or one
+ *      ordered behind it.
+ *
+ *      The contract of entry e, with l = sel[e], r = the read with read_sel_off[r] <= e < read_sel_off[r + 1], q = its m
+ *      letters, t = text[start[l], end[l]) of L letters, d = dist[l], and the options a = match, b = mismatch, o = gap_open,
+ *      x = gap_extend, p = clip_penalty, everything in int64; a gap of len letters costs o + len x, as in kmx_scripts_clip; a
+ *      read letter >= sigma equals nothing:
+ *        cell (i, j) exists for 0 <= i <= m, 0 <= j <= L, |j - i| <= d; every other cell is -inf in every state;
+ *        Z(i) = 0 if i == 0, else -p (a path may begin at any cell, a left clip pays p);
+ *        s(i, j) = a if q[i-1] == t[j-1] and q[i-1] < sigma, else -b;
+ *        E(i, j) = max(E(i, j-1) - x, H(i, j-1) - o - x)            ends with 'D' (a text letter)
+ *        F(i, j) = max(F(i-1, j) - x, H(i-1, j) - o - x)            ends with 'I' (a read letter)
+ *        H(i, j) = max(Z(i), H(i-1, j-1) + s(i, j), E(i, j), F(i, j))
+ *        V(i, j) = H(i, j) - p [i < m];
+ *        the END CELL (i1, j1) has the greatest V; among equals the least i, then the least j;
+ *        the WALK starts at (i1, j1) in state H.  State H at (i, j), the first that applies: 1. H == Z(i): stop, (i0, j0) =
+ *        (i, j); 2. i, j > 0 and H == H(i-1, j-1) + s: '=' or 'X', to (i-1, j-1) in state H; 3. H == E(i, j): state E;
+ *        4. state F.  State E: 'D'; the next state is H if E(i, j) == H(i, j-1) - o - x, else E; to (i, j-1).  State F: the
+ *        same with 'I', F, H(i-1, j) and (i-1, j).
+ *      The entry is REALIGNED when the path is not empty and V(i1, j1) >= min_score: score[e] = V, sl = i0, sr = m - i1,
+ *      tl = j0, tr = L - j1, nm = the 'X' + 'I' + 'D' ops, the runs sl 'S' (only if sl > 0), the ops in forward order as BAM
+ *      runs, sr 'S' (only if sr > 0), cflags[e] = KMX_CLIP_REALIGNED.  EVERY OTHER ENTRY is what kmx_scripts_clip makes of a
+ *      LOW entry: the script's own runs, score = W[R], sl = sr = tl = tr = 0, nm = the 'X' + 'I' + 'D' lengths of the script,
+ *      cflags[e] = KMX_CLIP_LOW.  An entry whose script is empty (mismatched) is not looked at: zeros, no runs, KMX_CLIP_LOW.
+ *      n_clipped counts the entries with sl + sr > 0, n_low those with the LOW bit.  So: a clipped side borders an '=' op, the
+ *      first and the last kept op never are 'D', the '=' 'X' 'I' lengths sum to i1 - i0 and the '=' 'X' 'D' lengths to
+ *      j1 - j0, and with min_score >= 0 score[e] is at least the score[e] of kmx_scripts_clip at the same options: the
+ *      trimmed part of the script is one of the paths, and it lies inside the band.  tests/realign_naive.py is this contract
+ *      in executable form, cell by cell.
+ *
+ *      scratch_bytes caps the arena of the traceback codes (0: 256 MiB; an entry takes 32 m bytes per 64 diagonals); the
+ *      entries go through it in chunks and the result never depends on it.  Besides the arena the call holds a run
+ *      reservation of 4 (m + L + 2) bytes per entry, the bound of a path's runs, for the whole batch.  Every access is bounded
+ *      by n_sel, n_loci, roff, m <= KMX_ALIGN_MAX_READ and L <= m + dist: wrong reads or a foreign alignments handle give
+ *      meaningless but harmless results.  The call only reads its inputs.
+ *
+ *      Lifecycle, views and streams are those of the clips handle (above), the roff checks of the host form those of
+ *      kmx_alignments_scripts.  A handle may go through kmx_scripts_clip and kmx_scripts_realign in any order.
+ *
+ *      KMX_ERR_INVALID_ARGUMENT before any handle is looked at: a NULL argument, a struct_size that is too small, flags != 0,
+ *      match outside 1 .. 255, mismatch, gap_open or gap_extend above 255, clip_penalty above 65535.  After looking: scripts
+ *      made with KMX_SCRIPT_M, an nr that differs from the scripts', scripts with more entries than the alignments' n_loci,
+ *      handles on different devices, a device without a replica of the index, the host form's roff; KMX_ERR_HIP for an index
+ *      broken by kmx_index_extend_query_size_range.  After such a refusal or an error the clips handle, when there is one,
+ *      holds an empty result.
+ *
+ *      Left out: text outside [start, end) and any widening of the band (a better alignment that leaves either is not
+ *      found); the scripts of kmx_rescues_scripts and kmx_secondaries_scripts (their sel indexes job arrays, not
+ *      alignments); an alignment of the clipped-off letters alone (the tandem duplication of the supplementary alignments,
+ *      below); a choice between loci by score and a score-aware MAPQ; kmx_stats_get is not extended (see kmx_loci_align).
+ *      Untested: an index with more than one replica, the different-devices refusals, and any batch above the sizes of the
+ *      chain's tests (8192 internal reads): no rate at a user's size is claimed. */
+#define KMX_REALIGN 1
+#define KMX_CLIP_REALIGNED 2u   /* cflags: the entry holds the local affine-gap alignment of kmx_scripts_realign */
+typedef struct kmx_realign_options {
+    uint32_t struct_size;   /* = sizeof(kmx_realign_options): 40 */
+    uint32_t match;         /* a, 1 .. 255 */
+    uint32_t mismatch;      /* b, 0 .. 255 */
+    uint32_t gap_open;      /* o, 0 .. 255 */
+    uint32_t gap_extend;    /* x, 0 .. 255: a gap of len letters costs o + len x */
+    uint32_t clip_penalty;  /* p, 0 .. 65535, charged once per clipped end */
+    int32_t min_score;
+    uint32_t flags;         /* 0 */
+    uint64_t scratch_bytes; /* cap on the traceback arena, 0 = 256 MiB; the result never depends on it */
+} kmx_realign_options;
+kmx_status kmx_scripts_realign(const kmx_index* index, const kmx_alignments* alignments, const kmx_scripts* scripts, const uint8_t* ranks,
+                               const uint64_t* roff, uint64_t nr, const kmx_realign_options* options, kmx_clips** inout);
+kmx_status kmx_scripts_realign_device(const kmx_index* index, const kmx_alignments* alignments, const kmx_scripts* scripts,
+                                      const void* d_ranks, const void* d_roff, uint64_t nr, const kmx_realign_options* options, void* stream,
+                                      kmx_clips** inout);
 
 /* ---- Supplementary alignments: the parts of a split read (an extension, no reference interface; a caller detects the
  *      capability by the macro KMX_MAP_SUPPLEMENTARY, KMX_VERSION is unchanged).  Soft clipping marks the part of a read that

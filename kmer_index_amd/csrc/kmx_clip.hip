@@ -150,12 +150,15 @@ struct kmx_clips {
     Buf score, sl, sr, tl, tr, nm, cflags, cig_off, cigar;
     // scratch
     Buf cut_i, cut_j, cnt, bsum, ctr;
+    Buf extra[kmx::kClipsExtra];           // the scratch of kmx_scripts_realign (kmx_realign.hip)
+    Pinned h_extra;
     Pinned h_ctr, h_score, h_sl, h_sr, h_tl, h_tr, h_nm, h_cflags, h_cig_off, h_cigar;
     bool host_valid = false;
     void release()
     {
         for (Buf* b : {&score, &sl, &sr, &tl, &tr, &nm, &cflags, &cig_off, &cigar, &cut_i, &cut_j, &cnt, &bsum, &ctr}) b->release();
-        for (Pinned* b : {&h_ctr, &h_score, &h_sl, &h_sr, &h_tl, &h_tr, &h_nm, &h_cflags, &h_cig_off, &h_cigar}) b->release();
+        for (Buf& b : extra) b.release();
+        for (Pinned* b : {&h_extra, &h_ctr, &h_score, &h_sl, &h_sr, &h_tl, &h_tr, &h_nm, &h_cflags, &h_cig_off, &h_cigar}) b->release();
     }
     void clear() { n_sel = n_ops = n_clipped = n_low = 0; filled = false; host_valid = false; }
 };
@@ -213,6 +216,48 @@ kmx::ClipsAccess kmx::clips_access(const kmx_clips* c)
                        c->cigar.as<uint32_t>(), c->stream, c->score.as<int32_t>(), c->sl.as<uint16_t>(), c->sr.as<uint16_t>(), c->nm.as<uint16_t>(),
                        c->cflags.as<uint8_t>()};
 }
+
+kmx_status kmx::clips_bind(kmx_clips** inout, int device) { return kmx::bind_handle(inout, device); }
+
+kmx_status kmx::clips_begin(kmx_clips* h, hipStream_t s, uint64_t ns, ClipsFill* out)
+{
+    h->stream = s;
+    h->clear();
+    (void)hipGetLastError();
+    TRY_HIP(h->cig_off.ensure((ns + 1) * 8));
+    if (ns == 0) {                                             // no entry: no launch indexes an empty array
+        TRY_HIP(hipMemsetAsync(h->cig_off.p, 0, 8, s));
+        h->filled = true;
+    } else {
+        TRY_HIP(h->score.ensure(ns * 4));
+        for (Buf* b : {&h->sl, &h->sr, &h->tl, &h->tr, &h->nm}) TRY_HIP(b->ensure(ns * 2));
+        TRY_HIP(h->cflags.ensure(ns));
+        TRY_HIP(h->cnt.ensure(ns * 4 + 16));
+        TRY_HIP(h->bsum.ensure(kmx::scan_blocks(ns) * 8 + 16));
+    }
+    *out = ClipsFill{h->score.as<int32_t>(), h->sl.as<uint16_t>(), h->sr.as<uint16_t>(), h->tl.as<uint16_t>(), h->tr.as<uint16_t>(),
+                     h->nm.as<uint16_t>(), h->cflags.as<uint8_t>(), h->cig_off.as<uint64_t>(), h->cnt.as<uint32_t>(), h->bsum.as<uint64_t>(),
+                     h->extra, &h->h_extra};
+    return KMX_OK;
+}
+
+kmx_status kmx::clips_runs(kmx_clips* h, uint64_t n_ops, uint32_t** cigar)
+{
+    TRY_HIP(h->cigar.ensure(std::max<uint64_t>(n_ops, 1) * 4));
+    *cigar = h->cigar.as<uint32_t>();
+    return KMX_OK;
+}
+
+void kmx::clips_finish(kmx_clips* h, uint64_t n_sel, uint64_t n_ops, uint64_t n_clipped, uint64_t n_low)
+{
+    h->n_sel = n_sel;
+    h->n_ops = n_ops;
+    h->n_clipped = n_clipped;
+    h->n_low = n_low;
+    h->filled = true;
+}
+
+void kmx::clips_clear(kmx_clips* h) { h->clear(); }
 
 extern "C" {
 

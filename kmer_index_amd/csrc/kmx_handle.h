@@ -1,6 +1,6 @@
 // What the host code around the kernels shares: the buffers a handle owns, the error macros, and the steps of the lifecycle that
 // every handle of the read-mapping chain follows (kmx_vote.hip, kmx_align.hip, kmx_script.hip, kmx_strands.hip, kmx_pairs.hip, kmx_rescue.hip,
-// kmx_tags.hip, kmx_contigs.hip, kmx_secondary.hip, kmx_clip.hip, kmx_supplementary.hip).
+// kmx_tags.hip, kmx_contigs.hip, kmx_secondary.hip, kmx_clip.hip, kmx_supplementary.hip, kmx_realign.hip).
 // A chain handle has the members `device`, `release()` (its buffers go, on its device) and `clear()` (an empty result).
 #pragma once
 #include <hip/hip_runtime.h>

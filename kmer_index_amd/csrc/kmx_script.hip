@@ -5,7 +5,8 @@
 //   k_script_count     a thread per read: how many of its loci are selected (the best one, or every aligned one)
 //   k_script_select    a thread per read: sel[], the read of every entry and, per entry, whether it can be served, the bytes of its
 //                      traceback codes and its run reservation (2d + 1); the totals, the largest entry, the entries per class
-//   k_script_cut       one thread: where the chunk that starts at entry e0 ends (the last entry whose codes still fit the arena)
+//   k_script_cut       one thread: where the chunk that starts at entry e0 ends (the last entry whose codes still fit the arena);
+//                      it lives in kmx_script_core.h, with the entry's bounds and the LDS staging, which kmx_realign.hip shares
 //   k_script_dp<NPL>   a wave per entry of the chunk: the band by rows, NPL neighbouring diagonals per lane (NPL in {1, 2, 4, 8}, the
 //                      smallest with 64 * NPL >= 2d + 1; a wave of another class leaves at once).  The diagonal predecessor is the
 //                      lane's own value of the previous row, the upper one its right neighbour's, the chain along the row a min-plus
@@ -15,7 +16,8 @@
 //   k_script_walk      a thread per entry of the chunk: from (m, L) to (0, 0) along the codes, runs written backwards into the
 //                      entry's reservation, the run count left behind
 //   k_script_compact   a thread per entry: its runs moved to cigar[cig_off[e] ...]
-// Read and text letters of an entry are staged in LDS (the text from the packed copy, one 64-bit word per lane at a time).
+// Read and text letters of an entry are staged in LDS (the text from the packed copy, one 64-bit word per lane at a time:
+// stage_entry, kmx_script_core.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,40 +26,20 @@
 
 #include "kmx_approx.h"
 #include "kmx_kernels.h"
+#include "kmx_script_core.h"
 #include "kmx_vote.h"
 
 namespace {
 
 constexpr uint32_t kBlock = 256;
-constexpr uint32_t kWave = 64;
-constexpr int kClasses = 4;                                   // NPL = 1, 2, 4, 8
 constexpr int kInf = 1 << 20;                                 // beyond any distance; sums of a few of them stay inside int
-constexpr uint32_t kNoRead = 0x1FF, kNoText = 0x2FF;          // letters that equal nothing
-constexpr uint32_t kTextLds = KMX_ALIGN_MAX_READ + 256;       // L <= m + d <= 1024 + 250
 constexpr uint32_t kNoBest = 0xFFFFFFFFu;
-constexpr uint64_t kDefaultScratch = uint64_t(256) << 20;
-constexpr uint64_t kMaxChunk = uint64_t(1) << 30;             // entries of one chunk: the grid of k_script_dp
 enum { OP_M = 0, OP_I = 1, OP_D = 2, OP_EQ = 7, OP_X = 8, OP_NONE = 15 };
-enum { CTR_N_SEL = 0, CTR_CODE_BYTES, CTR_RES_RUNS, CTR_MAX_CODE, CTR_CUT, CTR_CLASS, CTR_N_OPS = CTR_CLASS + kClasses, CTR_N_MISMATCHED, CTR_COUNT };
+enum { CTR_N_OPS = CTR_SHARED, CTR_N_MISMATCHED, CTR_COUNT };
 
 using kmx::Buf;
 using Pinned = kmx::PinnedArr;
 using kmx::grid_for;
-
-// what every kernel reads
-struct ScriptIn {
-    const uint8_t* ranks;
-    const uint64_t* roff;          // [nr + 1]
-    uint64_t ranks_len;            // letters that may be read (host form: roff[nr]; device form: no bound of ours)
-    const uint64_t* locus_off;     // [nr + 1]
-    const uint8_t* dist;           // [n_loci]
-    const uint32_t* start;
-    const uint32_t* end;
-    const uint32_t* best;          // [nr]
-    uint64_t nr, n_loci, n;
-    const uint64_t* text;          // packed at w bits per letter
-    uint32_t w, sigma, flags;
-};
 
 // the per-entry arrays and the chunk [e0, e1) a pass works on
 struct Entries {
@@ -69,32 +51,6 @@ struct Entries {
     unsigned long long* ctr;
     uint64_t e0, e1;
 };
-
-// Read, text substring and distance of an entry; ok == false: the entry gets no script (kmx.h, "foreign reads").  With ok,
-// m <= KMX_ALIGN_MAX_READ, d <= KMX_ALIGN_MAX_EDITS, |m - L| <= d and text[start, start + L) lies inside the text.
-struct Entry {
-    uint64_t r0;
-    uint32_t m, L, d, start;
-    bool ok;
-};
-
-__device__ __forceinline__ Entry entry_of(const ScriptIn& S, uint32_t r, uint32_t l)
-{
-    Entry en{};
-    const uint64_t r0 = S.roff[r], r1 = S.roff[r + 1];
-    const uint32_t s = S.start[l], e = S.end[l], d = S.dist[l];
-    en.r0 = r0;
-    en.start = s;
-    en.d = d;
-    if (!(r1 >= r0 && r1 <= S.ranks_len && r1 - r0 <= KMX_ALIGN_MAX_READ && s <= e && e <= S.n && d <= KMX_ALIGN_MAX_EDITS)) return en;
-    en.m = uint32_t(r1 - r0);
-    en.L = e - s;
-    const uint32_t gap = en.m > en.L ? en.m - en.L : en.L - en.m;
-    en.ok = gap <= d && (en.m > 0 || en.L == d);               // (the empty read: H[0][L] = L)
-    return en;
-}
-
-__device__ __forceinline__ uint32_t class_of(uint32_t d) { return d < 32 ? 0u : d < 64 ? 1u : d < 128 ? 2u : 3u; }   // 64 << class >= 2d + 1
 
 // the loci of read r that are selected, in ascending order: f(l) for each
 template <typename F>
@@ -154,21 +110,6 @@ __global__ __launch_bounds__(kBlock) void k_script_select(ScriptIn S, const uint
     }
 }
 
-// ctr[CTR_CUT] = the end of the chunk that starts at e0: the most entries whose codes fit `cap` bytes (clamped up to the largest
-// entry of the batch, so a chunk never is empty)
-__global__ void k_script_cut(const uint64_t* __restrict__ code_off, uint64_t e0, uint64_t cap, unsigned long long* __restrict__ ctr)
-{
-    const uint64_t n_sel = ctr[CTR_N_SEL];
-    cap = max(cap, uint64_t(ctr[CTR_MAX_CODE]));
-    uint64_t lo = min(e0, n_sel), hi = min(n_sel, lo + kMaxChunk);   // the largest e in [lo, hi] with code_off[e] - code_off[e0] <= cap
-    const uint64_t base = code_off[lo];
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (code_off[mid] - base <= cap) lo = mid; else hi = mid - 1;
-    }
-    ctr[CTR_CUT] = lo;
-}
-
 // ---- the band ------------------------------------------------------------------------------------------------------------------------
 template <int NPL>
 __global__ __launch_bounds__(kWave) void k_script_dp(ScriptIn S, Entries C)
@@ -181,19 +122,7 @@ __global__ __launch_bounds__(kWave) void k_script_dp(ScriptIn S, Entries C)
     if (!en.ok || en.m == 0 || (1u << class_of(en.d)) != uint32_t(NPL)) return;      // (the whole wave: one entry)
     const uint32_t lane = threadIdx.x, m = en.m, L = en.L;
     const int d = int(en.d), W = 2 * d + 1;
-    for (uint32_t i = lane; i < m; i += kWave) s_q[i] = S.ranks[en.r0 + i];
-    if (L) {
-        const uint32_t w = S.w, per = 64 / w;
-        const uint64_t mask = (uint64_t(1) << w) - 1;          // (w <= 8)
-        const uint64_t lo = en.start, hi = lo + L;
-        for (uint64_t wi = lo / per + lane; wi <= (hi - 1) / per; wi += kWave) {
-            const uint64_t word = S.text[wi];
-            for (uint32_t k = 0; k < per; ++k) {
-                const uint64_t p = wi * per + k;
-                if (p >= lo && p < hi) s_t[p - lo] = uint8_t((word >> (k * w)) & mask);
-            }
-        }
-    }
+    stage_entry(S, en, lane, s_q, s_t);
     __syncthreads();
     uint64_t* codes = C.arena + (C.code_off[e] - C.code_off[C.e0]) / 8;
     // lane t holds the diagonals x = t * NPL + s, x = j - i + d in [0, W); cells off the band or off the text hold kInf
@@ -330,16 +259,6 @@ __global__ __launch_bounds__(kBlock) void k_script_compact(const unsigned long l
     const uint64_t a = cig_off[e], cnt = cig_off[e + 1] - a;
     const uint32_t* from = runs + run_off[e + 1] - cnt;
     for (uint64_t k = 0; k < cnt; ++k) cigar[a + k] = from[k];
-}
-
-hipError_t ensure_exact(Buf& b, size_t bytes)                  // (Buf::ensure leaves headroom; the arena keeps to its bound)
-{
-    if (bytes <= b.cap) return hipSuccess;
-    b.release();
-    hipError_t e = hipMalloc(&b.p, bytes);
-    if (e != hipSuccess) { b.p = nullptr; return e; }
-    b.cap = bytes;
-    return hipSuccess;
 }
 
 } // namespace

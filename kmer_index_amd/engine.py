@@ -33,7 +33,7 @@ RESCUE_DISCORDANT, RESCUE_MAX_INSERT = 1, 65536
 RESCUE_NONE, RESCUE_FOUND, RESCUE_CONCORDANT, RESCUE_TAKEN = 0, 1, 2, 3
 LOCATE_MATES, NO_CONTIG = 1, 0xFFFFFFFF
 SECONDARY_MAX, SECONDARY_NO_DELTA = 32, 0xFFFFFFFF
-CLIP_LOW = 1
+CLIP_LOW, CLIP_REALIGNED = 1, 2
 SUPPLEMENTARY_MAX = 8
 
 
@@ -105,6 +105,12 @@ class SecondaryOptions(C.Structure):
 class ClipOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("match", C.c_uint32), ("mismatch", C.c_uint32), ("gap_open", C.c_uint32),
                 ("gap_extend", C.c_uint32), ("clip_penalty", C.c_uint32), ("min_score", C.c_int32), ("flags", C.c_uint32)]
+
+
+class RealignOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("match", C.c_uint32), ("mismatch", C.c_uint32), ("gap_open", C.c_uint32),
+                ("gap_extend", C.c_uint32), ("clip_penalty", C.c_uint32), ("min_score", C.c_int32), ("flags", C.c_uint32),
+                ("scratch_bytes", C.c_uint64)]
 
 
 class SupplementaryOptions(C.Structure):
@@ -259,6 +265,8 @@ SIGNATURES = {
     "kmx_clips_md": (st, [vp, vp, vp, vp, vp, P(MdOptions), vp, P(vp)]),
     "kmx_clips_rescues_md": (st, [vp, vp, vp, vp, vp, P(MdOptions), vp, P(vp)]),
     "kmx_clips_free": (None, [vp]),
+    "kmx_scripts_realign": (st, [vp, vp, vp, vp, vp, u64, P(RealignOptions), P(vp)]),
+    "kmx_scripts_realign_device": (st, [vp, vp, vp, vp, vp, u64, P(RealignOptions), vp, P(vp)]),
     # supplementary alignments
     "kmx_clips_supplementaries": (st, [vp, vp, vp, vp, vp, vp, P(SupplementaryOptions), vp, P(vp)]),
     "kmx_supplementaries_counts": (st, [vp] + [P(u64)] * 4),
@@ -654,6 +662,38 @@ class Scripts(_Handle):
         out = clips or Clips()
         o = ClipOptions(C.sizeof(ClipOptions), int(match), int(mismatch), int(gap_open), int(gap_extend), int(clip_penalty), int(min_score), 0)
         _check(lib().kmx_scripts_clip(self._h, C.byref(o), stream or None, C.byref(out._h)))
+        out.scripts = self
+        return _made_from(out, self)
+
+    @staticmethod
+    def _realign_options(match, mismatch, gap_open, gap_extend, clip_penalty, min_score, scratch_bytes):
+        return RealignOptions(C.sizeof(RealignOptions), int(match), int(mismatch), int(gap_open), int(gap_extend), int(clip_penalty), int(min_score), 0,
+                              int(scratch_bytes))
+
+    def realign(self, index, alignments, ranks, roff, match=1, mismatch=4, gap_open=6, gap_extend=1, clip_penalty=5, min_score=0, scratch_bytes=0,
+                clips=None):
+        """kmx_scripts_realign: every entry aligned again, locally and with affine gaps, inside the rectangle read x text[start, end)
+        and the band |j - i| <= dist of its script, under the scoring of clip(); an entry without a path, or whose best value is
+        below min_score, keeps its script and carries CLIP_LOW, every other one carries CLIP_REALIGNED.  These are the Scripts of
+        Alignments.scripts[_device] or of Placements.scripts; alignments: the Alignments they were made from; ranks, roff: the
+        reads that were aligned (host arrays).  scratch_bytes bounds the device scratch of the traceback (0: the default).  Returns
+        a Clips (`clips` reuses one)."""
+        ranks = np.ascontiguousarray(ranks, np.uint8)
+        roff = np.ascontiguousarray(roff, np.uint64)
+        out = clips or Clips()
+        o = self._realign_options(match, mismatch, gap_open, gap_extend, clip_penalty, min_score, scratch_bytes)
+        _check(lib().kmx_scripts_realign(index._h, alignments._h, self._h, ranks.ctypes.data if ranks.size else None, roff.ctypes.data, roff.size - 1,
+                                         C.byref(o), C.byref(out._h)))
+        out.scripts = self
+        return _made_from(out, self)
+
+    def realign_device(self, index, alignments, d_ranks_ptr, d_roff_ptr, nr, match=1, mismatch=4, gap_open=6, gap_extend=1, clip_penalty=5,
+                       min_score=0, scratch_bytes=0, stream=0, clips=None):
+        """kmx_scripts_realign_device on a caller-owned hipStream_t: the stream that filled these scripts, or one ordered behind it."""
+        out = clips or Clips()
+        o = self._realign_options(match, mismatch, gap_open, gap_extend, clip_penalty, min_score, scratch_bytes)
+        _check(lib().kmx_scripts_realign_device(index._h, alignments._h, self._h, d_ranks_ptr, d_roff_ptr, nr, C.byref(o), stream or None,
+                                                C.byref(out._h)))
         out.scripts = self
         return _made_from(out, self)
 
@@ -1593,7 +1633,7 @@ class Index:
         return s
 
     def map_reads_strands(self, ranks, roff, w, complement, stride=1, band=0, min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False,
-                          tags=False, letters=None, secondaries=0, clip=None, supplementary=None):
+                          tags=False, letters=None, secondaries=0, clip=None, supplementary=None, realign=None):
         """map_reads on both strands: kmx_reads_strands, kmx_search_windows_device, kmx_windows_vote, kmx_loci_align_device and
         kmx_alignments_fold_strands in a row, all on the stream of the StrandReads.  Returns (StrandReads, Loci, Alignments,
         Placements): the loci and alignments are those of the doubled batch (internal read 2i is read i, 2i + 1 its reverse
@@ -1605,13 +1645,16 @@ class Index:
         with tags=True the Md then is kmx_clips_md, that of the clipped entries.  supplementary (a dict of the arguments of
         Clips.supplementaries, {} for the defaults; needs scripts=True and clip) runs last: the KMX_SCRIPT_ALL scripts of the
         doubled batch, their clips under the same `clip` scoring and kmx_clips_supplementaries on the placements, and appends, as
-        the very last element, the Supplementaries; its all_scripts / all_clips are those two handles and its close() closes them."""
+        the very last element, the Supplementaries; its all_scripts / all_clips are those two handles and its close() closes them.
+        realign (a dict that may hold scratch_bytes, {} for the default; needs scripts=True and clip): the Clips of the placements and
+        the all-loci Clips behind supplementary come from kmx_scripts_realign_device under the `clip` scoring in the place of
+        kmx_scripts_clip; the secondaries are untouched.  With realign=None every returned tuple is what it was without the keyword."""
         return self._map_chain("map_reads_strands", ranks, roff, w, complement, None, None, stride, band, min_votes, max_occ, max_edits, max_span,
-                               scripts, tags, letters, secondaries, clip, supplementary)
+                               scripts, tags, letters, secondaries, clip, supplementary, realign)
 
     def map_pairs(self, ranks, roff, w, complement, min_insert, max_insert, orientation=PAIR_FR, unpaired_penalty=None, stride=1, band=0,
                   min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False, rescue=False, rescue_edits=None, rescue_discordant=False,
-                  tags=False, letters=None, secondaries=0, clip=None, supplementary=None):
+                  tags=False, letters=None, secondaries=0, clip=None, supplementary=None, realign=None):
         """map_reads_strands for paired reads: the reads are interleaved mates (read 2p is mate 1 of pair p, read 2p + 1 its mate 2, so
         their number is even), and kmx_alignments_fold_pairs stands in the fold's place.  Returns (StrandReads, Loci, Alignments,
         Placements, Pairs); scripts=True appends kmx_placements_scripts (the CIGARs of the chosen loci).  rescue=True runs
@@ -1628,13 +1671,14 @@ class Index:
         with tags=True md and rescue_md then are kmx_clips_md and kmx_clips_rescues_md, those of the clipped entries.
         supplementary (a dict of the arguments of Clips.supplementaries, {} for the defaults; needs scripts=True and clip) runs
         last, on the placements as the rescue left them (a rescued mate has no parts), and appends the Supplementaries behind the
-        Clips, as in map_reads_strands."""
+        Clips, as in map_reads_strands.  realign: as in map_reads_strands; the clips of the rescued mates stay those of kmx_scripts_clip
+        (their scripts index the rescue's jobs, not alignments)."""
         return self._map_chain("map_pairs", ranks, roff, w, complement, (min_insert, max_insert, orientation, unpaired_penalty),
                                (max_edits if rescue_edits is None else rescue_edits, rescue_discordant) if rescue else None,
-                               stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags, letters, secondaries, clip, supplementary)
+                               stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags, letters, secondaries, clip, supplementary, realign)
 
     def _map_chain(self, who, ranks, roff, w, complement, insert, rescue, stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags,
-                   letters, secondaries, clip, supplementary=None):
+                   letters, secondaries, clip, supplementary=None, realign=None):
         """What map_reads_strands (insert=None) and map_pairs (insert: min_insert, max_insert, orientation, unpaired_penalty; rescue:
         None or the rescue's edits and whether it takes DISCORDANT pairs) return: the front and the fold, then the stages that were
         asked for, every one on the stream of the StrandReads."""
@@ -1644,6 +1688,8 @@ class Index:
             raise ValueError(f"{who}: clip needs scripts=True")
         if supplementary is not None and (not scripts or clip is None):
             raise ValueError(f"{who}: supplementary needs scripts=True and clip")
+        if realign is not None and (not scripts or clip is None):
+            raise ValueError(f"{who}: realign needs scripts=True and clip")
         if insert is not None:
             roff = np.ascontiguousarray(roff, np.uint64)
             if (roff.size - 1) % 2:
@@ -1674,8 +1720,14 @@ class Index:
                     pairs.rescue(self, reads, loci, al, pl, min_insert, max_insert, rescue[0], orientation, rescue[1], unpaired_penalty, rescues=res)
             if scripts or tags:
                 sc = keep(pl.scripts(self, reads, loci, al))
+
+            def clipped(s, **on):                                      # the Clips of the scripts s of the alignments, trimmed or realigned
+                if realign is None:
+                    return s.clip(**clip, **on)
+                return s.realign_device(self, al, d_ranks2, d_roff2, nr2, **clip, **realign, stream=stream)
+
             if clip is not None:
-                cl = keep(sc.clip(**clip))
+                cl = keep(clipped(sc))
                 if res is not None:
                     rsc = keep(res.scripts(self, reads))
                     rcl = keep(rsc.clip(**clip))
@@ -1691,7 +1743,7 @@ class Index:
                 sec = keep(pl.secondaries(loci, al, secondaries))       # last, on the placements as the rescue left them
             if supplementary is not None:                              # last too: every aligned locus of both strands, clipped as the winners are
                 asc = keep(al.scripts_device(self, loci, d_ranks2, d_roff2, nr2, all=True, stream=stream))
-                acl = keep(asc.clip(**clip, stream=stream))
+                acl = keep(clipped(asc, stream=stream))
                 sup = keep(acl.supplementaries(reads, loci, al, pl, asc, **supplementary, stream=stream))
                 sup.all_scripts, sup.all_clips, sup._owns = asc, acl, True
             opened.pop_all()

@@ -407,8 +407,9 @@ kmx_status align_call(const char* fn, const kmx_index* index, const kmx_loci* lo
     };
     if (nr != L.nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "nr differs from the loci handle's");
     kmx::IndexAccess X{};
-    if (!kmx::index_access_on(index, L.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the loci live on a device that holds no replica of this index");
-    if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    kmx_status no_st;
+    std::string no_index;
+    if (!kmx::index_for(index, L.device, "the loci", &X, &no_st, &no_index)) return refuse(no_st, no_index);
     uint64_t n_letters = ~uint64_t(0);
     if (host) {
         const char* why = kmx::check_host_reads(ranks, static_cast<const uint64_t*>(roff), nr, &n_letters);

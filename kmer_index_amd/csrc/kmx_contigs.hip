@@ -120,9 +120,7 @@ kmx_status kmx_placements_locate(const kmx_index* index, const kmx_alignments* a
     if (!index) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "index is NULL");
     if (!alignments) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "alignments handle is NULL");
     if (!placements) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "placements handle is NULL");
-    if (!o) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options is NULL");
-    if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
-    if (o->struct_size < sizeof(kmx_locate_options)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
+    TRY_KMX(kmx::check_call(who, o, inout));
     if (o->flags & ~KMX_LOCATE_MATES) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "unknown flags");
     const kmx::AlignAccess A = kmx::alignments_access(alignments);
     kmx_located* h = *inout;
@@ -134,18 +132,15 @@ kmx_status kmx_placements_locate(const kmx_index* index, const kmx_alignments* a
     if (2 * placements->nr != A.nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "the placements are not those of these alignments: 2 nr differs from the alignments' nr");
     if (placements->nr && placements->device != A.device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments and the placements live on different devices");
     kmx::IndexAccess X{};
-    if (!kmx::index_access_on(index, A.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments live on a device that holds no replica of this index");
-    if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    kmx_status no_st;
+    std::string no_index;
+    if (!kmx::index_for(index, A.device, "the alignments", &X, &no_st, &no_index)) return refuse(no_st, no_index);
     if (A.nc != (X.ctg_off ? X.nc : 0) || A.ctg_gen != X.ctg_gen)
         return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments were made under another contig table of the index (kmx_index_set_contigs was called since): align again");
     if (!X.ctg_off || X.nc == 0) return refuse(KMX_ERR_INVALID_ARGUMENT, "the index has no contig table (kmx_index_set_contigs)");
     kmx::DeviceGuard dg;
-    const kmx_status bound = kmx::bind_handle(inout, A.device);
+    TRY_KMX(kmx::bind_handle(inout, A.device));
     h = *inout;
-    if (bound != KMX_OK) {
-        if (h) h->clear();
-        return bound;
-    }
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : placements->stream;
     const kmx_status st = locate_run(X, A, placements, o->flags, s, h);
     if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one

@@ -1,6 +1,9 @@
-// What the host code around the kernels shares: the buffers a handle owns, the error macros, and the steps of the lifecycle that
-// every handle of the read-mapping chain follows (kmx_vote.hip, kmx_align.hip, kmx_script.hip, kmx_strands.hip, kmx_pairs.hip, kmx_rescue.hip,
-// kmx_tags.hip, kmx_contigs.hip, kmx_secondary.hip, kmx_clip.hip, kmx_supplementary.hip, kmx_realign.hip).
+// What the host code around the kernels shares: the buffers a handle owns, the error macros, the refusals every entry point starts
+// with, and the steps of the lifecycle that every handle of the read-mapping chain follows (kmx_vote.hip, kmx_align.hip,
+// kmx_script.hip, kmx_strands.hip, kmx_pairs.hip, kmx_rescue.hip, kmx_tags.hip, kmx_contigs.hip, kmx_secondary.hip, kmx_clip.hip,
+// kmx_supplementary.hip, kmx_realign.hip).  The other private headers of the chain: kmx_vote.h (what a stage reads of
+// the handle before it), kmx_strands.h and kmx_clips.h (the handle structs that two sources fill), kmx_align_core.h,
+// kmx_script_core.h, kmx_runs.h and kmx_fold_core.h (device code that several sources compile).
 // A chain handle has the members `device`, `release()` (its buffers go, on its device) and `clear()` (an empty result).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +13,7 @@
 #include <cstring>
 #include <string>
 
+#include "kmx_approx.h"
 #include "kmx_types.h"
 
 namespace kmx {
@@ -28,6 +32,33 @@ kmx_status set_error(kmx_status st, const std::string& msg);    // kmx_capi.hip:
     } while (0)
 // ... and so does a step of ours that failed (it has set the error text)
 #define TRY_KMX(expr) do { const kmx_status st__ = (expr); if (st__ != KMX_OK) return st__; } while (0)
+
+// the first refusals of an entry point `who` ("kmx_...: ") with options o and a handle to fill at *inout
+template <typename O>
+kmx_status check_call(const std::string& who, const O* o, const void* inout)
+{
+    if (!o) return set_error(KMX_ERR_INVALID_ARGUMENT, who + "options is NULL");
+    if (!inout) return set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
+    if (o->struct_size < sizeof(O)) return set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
+    return KMX_OK;
+}
+
+// *X = the replica of `index` on `device`, where `whose` ("the scripts", "the loci", ...) live; false: there is none, or the index is
+// broken, and (*st, *why) is the refusal
+inline bool index_for(const kmx_index* index, int device, const char* whose, IndexAccess* X, kmx_status* st, std::string* why)
+{
+    if (!index_access_on(index, device, X)) {
+        *st = KMX_ERR_INVALID_ARGUMENT;
+        *why = std::string(whose) + " live on a device that holds no replica of this index";
+        return false;
+    }
+    if (X->broken) {
+        *st = KMX_ERR_HIP;
+        *why = "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent";
+        return false;
+    }
+    return true;
+}
 
 // grow-only device buffer, released with its owner
 struct Buf {
@@ -114,7 +145,8 @@ inline kmx_status upload_reads(const void* ranks, const void* roff, uint64_t nr,
     return KMX_OK;
 }
 
-// *inout becomes a handle on `device` (created when NULL), and `device` the current one: the caller holds a DeviceGuard.
+// *inout becomes a handle on `device` (created when NULL), and `device` the current one: the caller holds a DeviceGuard.  When the
+// device cannot be made current, a handle there is holds an empty result, as after every refusal that has looked at it.
 template <typename H>
 kmx_status bind_handle(H** inout, int device)
 {
@@ -124,7 +156,11 @@ kmx_status bind_handle(H** inout, int device)
         h->release();
         h->clear();
     }
-    TRY_HIP(hipSetDevice(device));
+    if (hipError_t e = hipSetDevice(device); e != hipSuccess) {
+        (void)hipGetLastError();
+        if (h) h->clear();
+        return set_error(KMX_ERR_HIP, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
+    }
     if (!h) h = new H();
     *inout = h;
     h->device = device;

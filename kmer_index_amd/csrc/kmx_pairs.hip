@@ -12,6 +12,7 @@
 
 #include <string>
 
+#include "kmx_fold_core.h"
 #include "kmx_strands.h"
 #include "kmx_vote.h"
 
@@ -21,8 +22,7 @@ constexpr uint32_t kBlock = 256;
 constexpr uint32_t kWave = 64;
 constexpr uint32_t kNoBest = 0xFFFFFFFFu;
 constexpr uint32_t kNoScore = 0xFFFFu;
-// the pair counters follow the placements' in one array
-enum { CTR_N_CONCORDANT = kmx::PL_COUNT, CTR_N_DISCORDANT, CTR_N_SINGLE, CTR_N_UNPLACED, CTR_N_PAIRS_AMBIGUOUS, CTR_COUNT };
+constexpr int CTR_COUNT = kmx::PR_COUNT;                       // the placements' counters, then the pairs'
 
 using kmx::Buf;
 using Pinned = kmx::PinnedArr;
@@ -36,9 +36,8 @@ struct PairIn {
     const uint32_t* best;          // [4 np]
     const uint32_t* ctg;           // [n_loci]: the contig of every locus; nullptr when the alignments were made without a contig table
     uint64_t np, n_loci;
-    int64_t min_insert, max_insert;
     uint64_t penalty;
-    uint32_t orientation;
+    Insert ins;
 };
 
 struct PairOut {
@@ -55,19 +54,6 @@ struct PairOut {
     uint16_t* second_score;
     unsigned long long* ctr;       // [CTR_COUNT]
 };
-
-// (x on strand sx at [xs, xe), y on strand sy at [ys, ye)): the template length when the two are concordant, else -1; *first: the
-// upstream locus is mate 1's
-__device__ __forceinline__ int64_t concordant_tlen(const PairIn& P, uint32_t sx, uint32_t xs, uint32_t xe, uint32_t sy, uint32_t ys, uint32_t ye,
-                                                   bool* first)
-{
-    if ((sx == sy) != (P.orientation == KMX_PAIR_FF)) return -1;
-    const bool f = sx == (P.orientation == KMX_PAIR_RF ? 1u : 0u);
-    const int64_t us = f ? xs : ys, ue = f ? xe : ye, vs = f ? ys : xs, ve = f ? ye : xe;
-    const int64_t t = ve - us;
-    *first = f;
-    return us <= vs && ue <= ve && t >= P.min_insert && t <= P.max_insert ? t : -1;
-}
 
 // A locus as the walk hands it on: its index, strand, interval and distance
 struct Locus { uint32_t l, s, start, end, d; };
@@ -94,7 +80,7 @@ __device__ __forceinline__ void walk_concordant(const PairIn& P, const uint64_t*
             const Locus& x = outer1 ? out : in;
             const Locus& y = outer1 ? in : out;
             bool first;
-            if (concordant_tlen(P, x.s, x.start, x.end, y.s, y.start, y.end, &first) >= 0) visit(x, y);
+            if (concordant_tlen(P.ins, x.s, x.start, x.end, y.s, y.start, y.end, &first) >= 0) visit(x, y);
         }
     }
 }
@@ -109,25 +95,18 @@ __global__ __launch_bounds__(kBlock) void k_pair_fold(PairIn P, PairOut O)
     if (p < P.np) {
         // the loci of the four internal reads: o[0] <= ... <= o[4], inside the arrays whatever the offsets hold
         uint64_t o[5];
-        o[0] = min(P.locus_off[4 * p], P.n_loci);
-#pragma unroll
-        for (int j = 1; j < 5; ++j) o[j] = min(max(P.locus_off[4 * p + j], o[j - 1]), P.n_loci);
-        // step 1: the single winner of each mate, as in k_strand_fold
+        strand_ranges(P.locus_off, P.n_loci, 4 * p, &o[0], &o[1], &o[2]);
+        strand_ranges(P.locus_off, P.n_loci, 4 * p + 2, &o[2], &o[3], &o[4], o[1]);
+        // step 1: the single winner of each mate
         bool placed[2];
         uint64_t w[2];                                         // the chosen locus of each mate
         uint32_t wd[2];
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-            const uint64_t a = o[2 * m], b = o[2 * m + 1], c = o[2 * m + 2];
-            const uint32_t bf = P.best[4 * p + 2 * m], br = P.best[4 * p + 2 * m + 1];
-            uint32_t df = KMX_ALIGN_NONE, dr = KMX_ALIGN_NONE;
-            if (bf != kNoBest && bf < b - a) df = P.dist[a + bf];
-            if (br != kNoBest && br < c - b) dr = P.dist[b + br];
-            const bool okf = df < KMX_ALIGN_SKIPPED, okr = dr < KMX_ALIGN_SKIPPED;
-            const bool fwd = okf && (!okr || df <= dr);
-            placed[m] = okf || okr;
-            w[m] = fwd ? a + bf : b + br;
-            wd[m] = placed[m] ? (fwd ? df : dr) : uint32_t(KMX_ALIGN_NONE);
+            const Winner W = strand_winner(P.dist, P.best, 4 * p + 2 * m, o[2 * m], o[2 * m + 1], o[2 * m + 2]);
+            placed[m] = W.placed;
+            w[m] = W.locus;
+            wd[m] = W.dist;
         }
         // step 2: the concordant (x, y) with the least (score, x, y)
         uint32_t cs = kNoBest, cx = kNoBest, cy = kNoBest;
@@ -150,13 +129,13 @@ __global__ __launch_bounds__(kBlock) void k_pair_fold(PairIn P, PairOut O)
             const uint32_t sx = cx < o[1] ? 0u : 1u, xs = P.start[cx], xe = P.end[cx];
             const uint32_t sy = cy < o[3] ? 0u : 1u, ys = P.start[cy], ye = P.end[cy];
             walk_concordant(P, o, lane, [&](const Locus& x, const Locus& y) {
-                const bool x_else = x.l != cx && (x.s != sx || max(x.start, xs) >= min(x.end, xe));
-                const bool y_else = y.l != cy && (y.s != sy || max(y.start, ys) >= min(y.end, ye));
+                const bool x_else = x.l != cx && elsewhere(x.s, x.start, x.end, sx, xs, xe);
+                const bool y_else = y.l != cy && elsewhere(y.s, y.start, y.end, sy, ys, ye);
                 if (x_else || y_else) second_score = min(second_score, x.d + y.d);
             });
             for (int off = kWave / 2; off > 0; off >>= 1) second_score = min(second_score, uint32_t(__shfl_xor(second_score, off)));
             bool first;
-            const int64_t t = concordant_tlen(P, sx, xs, xe, sy, ys, ye, &first);
+            const int64_t t = concordant_tlen(P.ins, sx, xs, xe, sy, ys, ye, &first);
             tlen = first ? int32_t(t) : -int32_t(t);
             cls = KMX_PAIR_CONCORDANT;
             score = cs;
@@ -171,14 +150,8 @@ __global__ __launch_bounds__(kBlock) void k_pair_fold(PairIn P, PairOut O)
             uint32_t ws = 0, we = 0, second = KMX_ALIGN_NONE;
             if (placed[m]) {
                 ws = P.start[w[m]]; we = P.end[w[m]];
-                for (uint64_t l = a + lane; l < c; l += kWave) {
-                    const uint32_t d = P.dist[l];
-                    if (d >= KMX_ALIGN_SKIPPED || l == w[m]) continue;
-                    const uint32_t s = l < b ? 0u : 1u;
-                    if (s != sw || max(P.start[l], ws) >= min(P.end[l], we)) second = min(second, d);
-                }
+                second = second_elsewhere(P.dist, P.start, P.end, a, b, c, lane, w[m], sw, ws, we);
             }
-            for (int off = kWave / 2; off > 0; off >>= 1) second = min(second, uint32_t(__shfl_xor(second, off)));
             if (lane == 0) {
                 O.locus[i] = placed[m] ? uint32_t(w[m]) : kNoBest;
                 O.strand[i] = placed[m] ? uint8_t(sw) : uint8_t(255);
@@ -188,11 +161,7 @@ __global__ __launch_bounds__(kBlock) void k_pair_fold(PairIn P, PairOut O)
                 O.second[i] = uint8_t(second);
                 O.best2[2 * i] = placed[m] && sw == 0 ? uint32_t(w[m] - a) : kNoBest;
                 O.best2[2 * i + 1] = placed[m] && sw == 1 ? uint32_t(w[m] - b) : kNoBest;
-                if (placed[m]) {
-                    atomicAdd(&s_ctr[kmx::PL_N_PLACED], 1u);
-                    if (sw) atomicAdd(&s_ctr[kmx::PL_N_REVERSE], 1u);
-                    if (second == wd[m]) atomicAdd(&s_ctr[kmx::PL_N_AMBIGUOUS], 1u);
-                }
+                count_placement(s_ctr, placed[m], sw, second, wd[m]);
             }
         }
         if (lane == 0) {
@@ -200,9 +169,7 @@ __global__ __launch_bounds__(kBlock) void k_pair_fold(PairIn P, PairOut O)
             O.tlen[p] = tlen;
             O.score[p] = uint16_t(score);
             O.second_score[p] = uint16_t(second_score);
-            atomicAdd(&s_ctr[cls == KMX_PAIR_CONCORDANT ? CTR_N_CONCORDANT : cls == KMX_PAIR_DISCORDANT ? CTR_N_DISCORDANT
-                             : cls == KMX_PAIR_UNPLACED ? CTR_N_UNPLACED : CTR_N_SINGLE], 1u);
-            if (cls == KMX_PAIR_CONCORDANT && second_score == score) atomicAdd(&s_ctr[CTR_N_PAIRS_AMBIGUOUS], 1u);
+            count_pair(s_ctr, cls, score, second_score);
         }
     }
     __syncthreads();
@@ -225,7 +192,8 @@ kmx_status pair_fold_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, co
     TRY_HIP(pr->ctr.ensure(CTR_COUNT * 8));
     unsigned long long* ctr = pr->ctr.as<unsigned long long>();
     TRY_HIP(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
-    const PairIn P{L.locus_off, A.dist, A.start, A.end, A.best, A.ctg, np, L.n_loci, int64_t(o.min_insert), int64_t(o.max_insert), o.unpaired_penalty, o.orientation};
+    const PairIn P{L.locus_off, A.dist, A.start, A.end, A.best, A.ctg, np, L.n_loci, o.unpaired_penalty,
+                   Insert{int64_t(o.min_insert), int64_t(o.max_insert), o.orientation}};
     const PairOut O{pl->locus.as<uint32_t>(), pl->strand.as<uint8_t>(), pl->dist.as<uint8_t>(), pl->start.as<uint32_t>(), pl->end.as<uint32_t>(),
                     pl->second.as<uint8_t>(), pl->best2.as<uint32_t>(), pr->cls.as<uint8_t>(), pr->tlen.as<int32_t>(), pr->score.as<uint16_t>(),
                     pr->second_score.as<uint16_t>(), ctr};
@@ -234,15 +202,9 @@ kmx_status pair_fold_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, co
     TRY_KMX(kmx::read_back("kmx_alignments_fold_pairs", s, ctr, pr->h_ctr, CTR_COUNT * 8));
     const uint64_t* h = pr->h_ctr.as<uint64_t>();
     pl->nr = 2 * np;
-    pl->n_placed = h[kmx::PL_N_PLACED];
-    pl->n_reverse = h[kmx::PL_N_REVERSE];
-    pl->n_ambiguous = h[kmx::PL_N_AMBIGUOUS];
+    pl->counts_from(h);
     pr->np = np;
-    pr->n_concordant = h[CTR_N_CONCORDANT];
-    pr->n_discordant = h[CTR_N_DISCORDANT];
-    pr->n_single = h[CTR_N_SINGLE];
-    pr->n_unplaced = h[CTR_N_UNPLACED];
-    pr->n_ambiguous = h[CTR_N_PAIRS_AMBIGUOUS];
+    pr->counts_from(h);
     return KMX_OK;
 }
 

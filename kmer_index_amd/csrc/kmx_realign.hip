@@ -35,7 +35,9 @@
 #include <string>
 
 #include "kmx_approx.h"
+#include "kmx_clips.h"
 #include "kmx_kernels.h"
+#include "kmx_runs.h"
 #include "kmx_script_core.h"
 #include "kmx_vote.h"
 
@@ -43,19 +45,11 @@ namespace {
 
 constexpr uint32_t kBlock = 256;
 constexpr int kNeg = -(1 << 28);
-constexpr uint64_t kMaxRuns = 0x7FFFFFFFull;                   // the runs of one script that are looked at
 constexpr int kKeyBias = 1 << 20;                              // V + kKeyBias > 0: V >= -2 * 65535
-enum { OP_I = 1, OP_D = 2, OP_S = 4, OP_EQ = 7, OP_X = 8, OP_NONE = 15 };
-enum { CTR_N_OPS = CTR_SHARED, CTR_N_CLIPPED, CTR_N_LOW, CTR_COUNT };
-enum { X_RANKS = 0, X_ROFF, X_EREAD, X_ESTAT, X_ECODE, X_ERES, X_CODE_OFF, X_RES_OFF, X_END_I, X_END_J, X_END_V, X_ARENA, X_RUNS, X_CTR, X_COUNT };
-static_assert(X_COUNT <= kmx::kClipsExtra, "the clips handle keeps too few buffers");
+enum { CTR_CLIPS = CTR_SHARED, CTR_COUNT = CTR_CLIPS + kmx::CL_COUNT };          // the clips' counters follow the band's
 
 using kmx::Buf;
 using kmx::grid_for;
-
-struct Scoring {
-    int a, b, o, x, p, min_score;
-};
 
 // the scripts that are realigned
 struct ScriptsIn {
@@ -79,13 +73,6 @@ struct Chunk {
     uint64_t e0, e1;
 };
 
-// the runs of the script of entry e, inside cigar[n_ops] whatever the offsets hold
-__device__ __forceinline__ void runs_of(const ScriptsIn& P, uint64_t e, uint64_t* a, uint64_t* b)
-{
-    *a = min(P.cig_off[e], P.n_ops);
-    *b = min(min(max(P.cig_off[e + 1], *a), P.n_ops), *a + kMaxRuns);
-}
-
 __device__ __forceinline__ uint64_t key_of(int v, uint32_t i, uint32_t j)     // greater: a greater V, then a smaller i, then a smaller j
 {
     return (uint64_t(uint32_t(v + kKeyBias)) << 32) | (uint64_t(0xFFFFu - i) << 16) | uint64_t(0xFFFFu - j);
@@ -108,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void k_realign_prepare(ScriptIn S, ScriptsI
             if (P.read_sel_off[mid + 1] <= e) lo = mid + 1; else hi = mid;
         }
         uint64_t a, b;
-        runs_of(P, e, &a, &b);
+        runs_of(P.cig_off, P.n_ops, e, &a, &b);
         const uint64_t R = b - a;
         const uint32_t l = P.sel[e];
         Entry en{};
@@ -234,17 +221,6 @@ __global__ __launch_bounds__(kWave) void k_realign_dp(ScriptIn S, ScriptsIn P, S
 }
 
 // ---- the walk ------------------------------------------------------------------------------------------------------------------------
-struct ClipOut {
-    int32_t* score;                // [n_sel]
-    uint16_t* sl;
-    uint16_t* sr;
-    uint16_t* tl;
-    uint16_t* tr;
-    uint16_t* nm;
-    uint8_t* cflags;
-    uint32_t* cnt;                 // the runs of the entry
-};
-
 __global__ __launch_bounds__(kBlock) void k_realign_walk(ScriptIn S, ScriptsIn P, Scoring G, Chunk C, uint32_t* __restrict__ runs, ClipOut O)
 {
     const uint64_t e = C.e0 + uint64_t(blockIdx.x) * kBlock + threadIdx.x;
@@ -257,14 +233,12 @@ __global__ __launch_bounds__(kBlock) void k_realign_walk(ScriptIn S, ScriptsIn P
         const uint64_t res = C.res_off[e + 1] - C.res_off[e];
         uint32_t* out = runs + C.res_off[e + 1];               // one past the reservation: the runs go in from its end
         const uint64_t* codes = C.arena + (C.code_off[e] - C.code_off[C.e0]) / 8;
-        const uint32_t w = S.w, per = 64 / w;
-        const uint64_t mask = (uint64_t(1) << w) - 1;
         const uint32_t i1 = C.end_i[e], j1 = C.end_j[e];
         const int v = C.end_v[e];
         uint32_t i = i1, j = j1, cur = OP_NONE, len = 0, cnt = 0, nm = 0, state = 0;      // state: 0 H, 1 E, 2 F
         bool bad = !en.ok || en.m == 0 || i1 > en.m || j1 > en.L || v < G.min_score;
         if (!bad && i1 < en.m) {                               // sr S: the last run
-            if (res) { out[-1] = ((en.m - i1) << 4) | OP_S; cnt = 1; } else bad = true;
+            if (res) { out[-1] = make_run(en.m - i1, OP_S); cnt = 1; } else bad = true;
         }
         for (uint32_t step = 0; !bad; ++step) {
             if (state == 0 && i == 0) break;                   // H(0, j) = 0 = Z(0)
@@ -279,8 +253,7 @@ __global__ __launch_bounds__(kBlock) void k_realign_walk(ScriptIn S, ScriptsIn P
                 if (c != 1) { state = c - 1; continue; }
                 if (j == 0) { bad = true; break; }
                 const uint32_t qc = S.ranks[en.r0 + i - 1];
-                const uint64_t at = uint64_t(en.start) + j - 1;
-                const uint32_t tc = uint32_t((S.text[at / per] >> ((at % per) * w)) & mask);
+                const uint32_t tc = text_letter(S.text, S.w, uint64_t(en.start) + j - 1);
                 op = qc == tc && qc < S.sigma ? OP_EQ : OP_X;
                 --i;
                 --j;
@@ -298,7 +271,7 @@ __global__ __launch_bounds__(kBlock) void k_realign_walk(ScriptIn S, ScriptsIn P
             if (op == cur) { ++len; continue; }
             if (len) {
                 if (cnt >= res) { bad = true; break; }
-                out[-1 - int64_t(cnt)] = (len << 4) | cur;
+                out[-1 - int64_t(cnt)] = make_run(len, cur);
                 ++cnt;
             }
             cur = op;
@@ -308,9 +281,9 @@ __global__ __launch_bounds__(kBlock) void k_realign_walk(ScriptIn S, ScriptsIn P
             const uint32_t need = 1 + (i > 0 ? 1u : 0u);
             if (cnt + need > res) bad = true;
             else {
-                out[-1 - int64_t(cnt)] = (len << 4) | cur;
+                out[-1 - int64_t(cnt)] = make_run(len, cur);
                 ++cnt;
-                if (i > 0) { out[-1 - int64_t(cnt)] = (i << 4) | OP_S; ++cnt; }        // sl S: the first run
+                if (i > 0) { out[-1 - int64_t(cnt)] = make_run(i, OP_S); ++cnt; }        // sl S: the first run
                 O.score[e] = v;
                 O.sl[e] = uint16_t(i);
                 O.sr[e] = uint16_t(en.m - i1);
@@ -326,8 +299,6 @@ __global__ __launch_bounds__(kBlock) void k_realign_walk(ScriptIn S, ScriptsIn P
     if (!done) O.cflags[e] = uint8_t(KMX_CLIP_LOW);            // k_realign_whole writes the rest
 }
 
-__device__ __forceinline__ uint16_t sat16(uint64_t v) { return uint16_t(min(v, uint64_t(0xFFFF))); }
-
 __global__ __launch_bounds__(kBlock) void k_realign_whole(ScriptsIn P, Scoring G, const uint64_t* __restrict__ res_off, uint32_t* __restrict__ runs,
                                                           ClipOut O, unsigned long long* __restrict__ ctr)
 {
@@ -340,33 +311,15 @@ __global__ __launch_bounds__(kBlock) void k_realign_whole(ScriptsIn P, Scoring G
             if (O.sl[e] || O.sr[e]) atomicAdd(&s_ctr[0], 1u);
         } else {
             uint64_t a, b;
-            runs_of(P, e, &a, &b);
+            runs_of(P.cig_off, P.n_ops, e, &a, &b);
             uint64_t R = b - a;
             if (R > res_off[e + 1] - res_off[e]) R = 0;        // (never: the reservation holds the script)
-            uint32_t* out = runs + res_off[e + 1] - R;
-            int64_t W = 0;
-            uint64_t nm = 0;
-            bool bad = false;
-            for (uint64_t k = 0; k < R; ++k) {
-                const uint32_t v = P.cigar[a + k], op = v & 15u;
-                const int64_t len = int64_t(v >> 4);
-                if (op == OP_EQ) W += len * G.a;
-                else if (op == OP_X) W -= len * G.b;
-                else if (op == OP_I || op == OP_D) W -= G.o + len * G.x;
-                else bad = true;
-                if (op != OP_EQ) nm += uint64_t(len);
-                out[k] = v;
-            }
-            O.score[e] = bad ? 0 : int32_t(max(int64_t(INT32_MIN), min(int64_t(INT32_MAX), W)));
-            O.sl[e] = O.sr[e] = O.tl[e] = O.tr[e] = 0;
-            O.nm[e] = bad ? uint16_t(0) : sat16(nm);
-            O.cflags[e] = uint8_t(KMX_CLIP_LOW);
-            O.cnt[e] = uint32_t(R);
+            whole_entry(G, P.cigar + a, R, runs + res_off[e + 1] - R, O, e);
             atomicAdd(&s_ctr[1], 1u);
         }
     }
     __syncthreads();
-    if (threadIdx.x < 2 && s_ctr[threadIdx.x]) atomicAdd(&ctr[CTR_N_CLIPPED + threadIdx.x], (unsigned long long)s_ctr[threadIdx.x]);
+    if (threadIdx.x < 2 && s_ctr[threadIdx.x]) atomicAdd(&ctr[CTR_CLIPS + kmx::CL_N_CLIPPED + threadIdx.x], (unsigned long long)s_ctr[threadIdx.x]);
 }
 
 __global__ __launch_bounds__(kBlock) void k_realign_compact(uint64_t n_sel, const uint64_t* __restrict__ res_off, const uint32_t* __restrict__ runs,
@@ -392,42 +345,45 @@ void launch_dp(hipStream_t s, int cls, const ScriptIn& S, const ScriptsIn& P, co
 
 // d_ranks / d_roff: the reads on the device of the handles; ranks_len: the letters that may be read
 kmx_status realign_run(const char* fn, const kmx::IndexAccess& X, const kmx::AlignAccess& A, const kmx::ScriptsAccess& Sc, const void* d_ranks,
-                       const void* d_roff, uint64_t ranks_len, const kmx_realign_options& o, hipStream_t s, kmx_clips* h, const kmx::ClipsFill& F)
+                       const void* d_roff, uint64_t ranks_len, const kmx_realign_options& o, hipStream_t s, kmx_clips* h)
 {
     const uint64_t ns = Sc.n_sel;
     TRY_KMX(kmx::ensure_text(X, s));
-    Buf* x = F.extra;
-    TRY_HIP(x[X_EREAD].ensure(ns * 4));
-    TRY_HIP(x[X_ESTAT].ensure(ns));
-    for (int k : {X_ECODE, X_ERES}) TRY_HIP(x[k].ensure(ns * 4 + 16));
-    for (int k : {X_CODE_OFF, X_RES_OFF}) TRY_HIP(x[k].ensure((ns + 1) * 8));
-    for (int k : {X_END_I, X_END_J, X_END_V}) TRY_HIP(x[k].ensure(ns * 4));
-    TRY_HIP(x[X_CTR].ensure(CTR_COUNT * 8));
-    unsigned long long* ctr = x[X_CTR].as<unsigned long long>();
+    kmx_clips::Realign& x = h->re;
+    TRY_HIP(x.eread.ensure(ns * 4));
+    TRY_HIP(x.estat.ensure(ns));
+    for (Buf* b : {&x.ecode, &x.eres}) TRY_HIP(b->ensure(ns * 4 + 16));
+    for (Buf* b : {&x.code_off, &x.res_off}) TRY_HIP(b->ensure((ns + 1) * 8));
+    for (Buf* b : {&x.end_i, &x.end_j, &x.end_v}) TRY_HIP(b->ensure(ns * 4));
+    TRY_HIP(h->ctr.ensure(CTR_COUNT * 8));
+    unsigned long long* ctr = h->ctr.as<unsigned long long>();
     TRY_HIP(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
     const ScriptIn S{static_cast<const uint8_t*>(d_ranks), static_cast<const uint64_t*>(d_roff), ranks_len, nullptr, A.dist, A.start, A.end, nullptr,
                      Sc.nr, A.n_loci, X.n, X.text->d_words, X.text->w, X.sigma, 0};
     const ScriptsIn P{Sc.read_sel_off, Sc.sel, Sc.cig_off, Sc.cigar, Sc.nr, ns, Sc.n_ops};
     const Scoring G{int(o.match), int(o.mismatch), int(o.gap_open), int(o.gap_extend), int(o.clip_penalty), o.min_score};
-    Chunk C{x[X_EREAD].as<uint32_t>(), x[X_ESTAT].as<uint8_t>(), x[X_CODE_OFF].as<uint64_t>(), x[X_RES_OFF].as<uint64_t>(), nullptr,
-            x[X_END_I].as<uint32_t>(), x[X_END_J].as<uint32_t>(), x[X_END_V].as<int32_t>(), 0, 0};
-    const ClipOut O{F.score, F.sl, F.sr, F.tl, F.tr, F.nm, F.cflags, F.cnt};
+    Chunk C{x.eread.as<uint32_t>(), x.estat.as<uint8_t>(), x.code_off.as<uint64_t>(), x.res_off.as<uint64_t>(), nullptr,
+            x.end_i.as<uint32_t>(), x.end_j.as<uint32_t>(), x.end_v.as<int32_t>(), 0, 0};
+    const ClipOut O{h->score.as<int32_t>(), h->sl.as<uint16_t>(), h->sr.as<uint16_t>(), h->tl.as<uint16_t>(), h->tr.as<uint16_t>(),
+                    h->nm.as<uint16_t>(), h->cflags.as<uint8_t>(), h->cnt.as<uint32_t>()};
+    uint64_t* bsum = h->bsum.as<uint64_t>();
+    uint64_t* cig_off = h->cig_off.as<uint64_t>();
     const dim3 grid(grid_for(ns, kBlock)), block(kBlock);
-    hipLaunchKernelGGL(k_realign_prepare, grid, block, 0, s, S, P, C, x[X_ECODE].as<uint32_t>(), x[X_ERES].as<uint32_t>(), ctr);
-    kmx::launch_scan(s, x[X_ECODE].as<uint32_t>(), ns, F.bsum, x[X_CODE_OFF].as<uint64_t>(), ctr + CTR_CODE_BYTES);
-    kmx::launch_scan(s, x[X_ERES].as<uint32_t>(), ns, F.bsum, x[X_RES_OFF].as<uint64_t>(), ctr + CTR_RES_RUNS);
+    hipLaunchKernelGGL(k_realign_prepare, grid, block, 0, s, S, P, C, x.ecode.as<uint32_t>(), x.eres.as<uint32_t>(), ctr);
+    kmx::launch_scan(s, x.ecode.as<uint32_t>(), ns, bsum, x.code_off.as<uint64_t>(), ctr + CTR_CODE_BYTES);
+    kmx::launch_scan(s, x.eres.as<uint32_t>(), ns, bsum, x.res_off.as<uint64_t>(), ctr + CTR_RES_RUNS);
     const uint64_t want = o.scratch_bytes ? o.scratch_bytes : kDefaultScratch;
-    hipLaunchKernelGGL(k_script_cut, dim3(1), dim3(1), 0, s, x[X_CODE_OFF].as<uint64_t>(), uint64_t(0), want, ctr);
+    hipLaunchKernelGGL(k_script_cut, dim3(1), dim3(1), 0, s, x.code_off.as<uint64_t>(), uint64_t(0), want, ctr);
     TRY_HIP(hipGetLastError());
-    TRY_KMX(kmx::read_back(fn, s, ctr, *F.h_extra, CTR_COUNT * 8));
+    TRY_KMX(kmx::read_back(fn, s, ctr, h->h_ctr, CTR_COUNT * 8));
     uint64_t c[CTR_COUNT];
-    std::memcpy(c, F.h_extra->p, sizeof c);
+    std::memcpy(c, h->h_ctr.p, sizeof c);
     const uint64_t cap = std::max(want, c[CTR_MAX_CODE]);
-    TRY_HIP(ensure_exact(x[X_ARENA], std::max<uint64_t>(std::min(cap, c[CTR_CODE_BYTES]), 32)));
-    TRY_HIP(x[X_RUNS].ensure(std::max<uint64_t>(c[CTR_RES_RUNS], 1) * 4));
-    C.arena = x[X_ARENA].as<uint64_t>();
+    TRY_HIP(ensure_exact(x.arena, std::max<uint64_t>(std::min(cap, c[CTR_CODE_BYTES]), 32)));
+    TRY_HIP(x.runs.ensure(std::max<uint64_t>(c[CTR_RES_RUNS], 1) * 4));
+    C.arena = x.arena.as<uint64_t>();
     C.e1 = c[CTR_CUT];
-    uint32_t* runs = x[X_RUNS].as<uint32_t>();
+    uint32_t* runs = x.runs.as<uint32_t>();
     while (C.e0 < ns) {
         if (C.e1 <= C.e0 || C.e1 > ns) return kmx::set_error(KMX_ERR_HIP, std::string(fn) + ": an empty chunk");   // (never: the bound is clamped)
         for (int k = 0; k < kClasses; ++k)
@@ -435,23 +391,23 @@ kmx_status realign_run(const char* fn, const kmx::IndexAccess& X, const kmx::Ali
         hipLaunchKernelGGL(k_realign_walk, dim3(grid_for(C.e1 - C.e0, kBlock)), block, 0, s, S, P, G, C, runs, O);
         C.e0 = C.e1;
         if (C.e0 < ns) {                                       // one more read-back per further chunk: where it ends
-            hipLaunchKernelGGL(k_script_cut, dim3(1), dim3(1), 0, s, x[X_CODE_OFF].as<uint64_t>(), C.e0, want, ctr);
+            hipLaunchKernelGGL(k_script_cut, dim3(1), dim3(1), 0, s, x.code_off.as<uint64_t>(), C.e0, want, ctr);
             TRY_HIP(hipGetLastError());
-            TRY_KMX(kmx::read_back(fn, s, ctr, *F.h_extra, CTR_COUNT * 8));
-            C.e1 = F.h_extra->as<uint64_t>()[CTR_CUT];
+            TRY_KMX(kmx::read_back(fn, s, ctr, h->h_ctr, CTR_COUNT * 8));
+            C.e1 = h->h_ctr.as<uint64_t>()[CTR_CUT];
         }
     }
-    hipLaunchKernelGGL(k_realign_whole, grid, block, 0, s, P, G, x[X_RES_OFF].as<uint64_t>(), runs, O, ctr);
-    kmx::launch_scan(s, F.cnt, ns, F.bsum, F.cig_off, ctr + CTR_N_OPS);
+    hipLaunchKernelGGL(k_realign_whole, grid, block, 0, s, P, G, x.res_off.as<uint64_t>(), runs, O, ctr);
+    kmx::launch_scan(s, O.cnt, ns, bsum, cig_off, ctr + CTR_CLIPS + kmx::CL_N_OPS);
     TRY_HIP(hipGetLastError());
-    TRY_KMX(kmx::read_back(fn, s, ctr, *F.h_extra, CTR_COUNT * 8));      // the counts, and the runs the output holds
-    std::memcpy(c, F.h_extra->p, sizeof c);
-    if (c[CTR_N_OPS] > c[CTR_RES_RUNS]) return kmx::set_error(KMX_ERR_HIP, std::string(fn) + ": more runs than were reserved");   // (never: a guard for the views)
-    uint32_t* cigar = nullptr;
-    TRY_KMX(kmx::clips_runs(h, c[CTR_N_OPS], &cigar));
-    hipLaunchKernelGGL(k_realign_compact, grid, block, 0, s, ns, x[X_RES_OFF].as<uint64_t>(), runs, F.cig_off, c[CTR_N_OPS], cigar);
+    TRY_KMX(kmx::read_back(fn, s, ctr, h->h_ctr, CTR_COUNT * 8));      // the counts, and the runs the output holds
+    std::memcpy(c, h->h_ctr.p, sizeof c);
+    const uint64_t n_ops = c[CTR_CLIPS + kmx::CL_N_OPS];
+    if (n_ops > c[CTR_RES_RUNS]) return kmx::set_error(KMX_ERR_HIP, std::string(fn) + ": more runs than were reserved");   // (never: a guard for the views)
+    TRY_KMX(h->runs(n_ops));
+    hipLaunchKernelGGL(k_realign_compact, grid, block, 0, s, ns, x.res_off.as<uint64_t>(), runs, cig_off, n_ops, h->cigar.as<uint32_t>());
     TRY_HIP(hipGetLastError());
-    kmx::clips_finish(h, ns, c[CTR_N_OPS], c[CTR_N_CLIPPED], c[CTR_N_LOW]);
+    h->finish(ns, c + CTR_CLIPS);
     return KMX_OK;
 }
 
@@ -461,15 +417,8 @@ kmx_status realign_call(const char* fn, const kmx_index* index, const kmx_alignm
                         const void* roff, uint64_t nr, const kmx_realign_options* o, bool host, hipStream_t stream, kmx_clips** inout)
 {
     const std::string who = std::string(fn) + ": ";
-    if (!o) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options is NULL");
-    if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
-    if (o->struct_size < sizeof(kmx_realign_options)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
-    if (o->flags != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "flags must be 0");
-    if (o->match < 1 || o->match > 255) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "match outside 1 .. 255");
-    if (o->mismatch > 255) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "mismatch > 255");
-    if (o->gap_open > 255) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "gap_open > 255");
-    if (o->gap_extend > 255) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "gap_extend > 255");
-    if (o->clip_penalty > 65535) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "clip_penalty > 65535");
+    TRY_KMX(kmx::check_call(who, o, inout));
+    TRY_KMX(kmx::check_scoring(who, *o));
     if (!index) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "index is NULL");
     if (!al) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "alignments handle is NULL");
     if (!scripts) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "scripts handle is NULL");
@@ -478,7 +427,7 @@ kmx_status realign_call(const char* fn, const kmx_index* index, const kmx_alignm
     const kmx::ScriptsAccess Sc = kmx::scripts_access(scripts);
     kmx_clips* h = *inout;
     auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (h) kmx::clips_clear(h);
+        if (h) h->clear();
         return kmx::set_error(st, who + msg);
     };
     if (Sc.flags & KMX_SCRIPT_M) return refuse(KMX_ERR_INVALID_ARGUMENT, "the scripts were made with KMX_SCRIPT_M: a score needs '=' and 'X' apart");
@@ -486,35 +435,31 @@ kmx_status realign_call(const char* fn, const kmx_index* index, const kmx_alignm
     if (Sc.n_sel > A.n_loci) return refuse(KMX_ERR_INVALID_ARGUMENT, "the scripts hold more loci than the alignments handle's n_loci");
     if (Sc.device != A.device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the scripts and the alignments live on different devices");
     kmx::IndexAccess X{};
-    if (!kmx::index_access_on(index, Sc.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the scripts live on a device that holds no replica of this index");
-    if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    kmx_status no_st;
+    std::string no_index;
+    if (!kmx::index_for(index, Sc.device, "the scripts", &X, &no_st, &no_index)) return refuse(no_st, no_index);
     uint64_t n_letters = ~uint64_t(0);
     if (host) {
         const char* why = kmx::check_host_reads(ranks, static_cast<const uint64_t*>(roff), nr, &n_letters);
         if (why) return refuse(KMX_ERR_INVALID_ARGUMENT, why);
     }
     kmx::DeviceGuard dg;
-    const kmx_status bound = kmx::clips_bind(inout, Sc.device);
+    TRY_KMX(kmx::bind_handle(inout, Sc.device));
     h = *inout;
-    if (bound != KMX_OK) {
-        if (h) kmx::clips_clear(h);
-        return bound;
-    }
     hipStream_t s = host ? Sc.stream : stream;
-    kmx::ClipsFill F{};
-    kmx_status st = kmx::clips_begin(h, s, Sc.n_sel, &F);
+    kmx_status st = h->begin(s, Sc.n_sel);
     if (st == KMX_OK && Sc.n_sel) {
         const void* d_ranks = ranks;
         const void* d_roff = roff;
         if (host) {
-            st = kmx::upload_reads(ranks, roff, nr, n_letters, F.extra[X_RANKS], F.extra[X_ROFF], s);
-            d_ranks = F.extra[X_RANKS].p;
-            d_roff = F.extra[X_ROFF].p;
+            st = kmx::upload_reads(ranks, roff, nr, n_letters, h->re.ranks, h->re.roff, s);
+            d_ranks = h->re.ranks.p;
+            d_roff = h->re.roff.p;
         }
-        if (st == KMX_OK) st = realign_run(fn, X, A, Sc, d_ranks, d_roff, n_letters, *o, s, h, F);
+        if (st == KMX_OK) st = realign_run(fn, X, A, Sc, d_ranks, d_roff, n_letters, *o, s, h);
     }
     if (host || st != KMX_OK) (void)hipStreamSynchronize(s);   // the caller's arrays are free again; a failed call leaves nothing in flight
-    if (st != KMX_OK) kmx::clips_clear(h);                     // the handle holds an empty result, not half of this one
+    if (st != KMX_OK) h->clear();                     // the handle holds an empty result, not half of this one
     return st;
 }
 

@@ -28,6 +28,7 @@
 
 #include "kmx_approx.h"
 #include "kmx_align_core.h"
+#include "kmx_fold_core.h"
 #include "kmx_kernels.h"
 #include "kmx_strands.h"
 #include "kmx_vote.h"
@@ -38,9 +39,9 @@ constexpr uint32_t kNoBest = 0xFFFFFFFFu;
 constexpr uint32_t kNoScore = 0xFFFFu;
 constexpr uint64_t kNoKey = ~uint64_t(0);
 constexpr uint64_t kDefaultSegment = 512;
-// the counters of the plan, then what the fold recounts: the rescue's own, the placements' (in the order of kmx::PL_*), the pairs'
-enum { CTR_N_JOBS = 0, CTR_PEQ_WORDS, CTR_CLASS, CTR_N_FOUND = CTR_CLASS + kClasses, CTR_N_JOB_CONCORDANT, CTR_N_TAKEN, CTR_PL,
-       CTR_N_CONCORDANT = CTR_PL + kmx::PL_COUNT, CTR_N_DISCORDANT, CTR_N_SINGLE, CTR_N_UNPLACED, CTR_N_PAIRS_AMBIGUOUS, CTR_COUNT };
+// the counters of the plan, then what the fold recounts: the rescue's own, then the placements' and the pairs' (kmx::PL_*, kmx::PR_*)
+enum { CTR_N_JOBS = 0, CTR_PEQ_WORDS, CTR_CLASS, CTR_N_FOUND = CTR_CLASS + kClasses, CTR_N_JOB_CONCORDANT, CTR_N_TAKEN, CTR_FOLD,
+       CTR_COUNT = CTR_FOLD + kmx::PR_COUNT };
 
 using kmx::Buf;
 using Pinned = kmx::PinnedArr;
@@ -60,9 +61,9 @@ struct RescueIn {
     uint16_t* score;
     uint16_t* second_score;
     uint64_t np, n;
-    int64_t min_insert, max_insert;
     uint64_t penalty;
-    uint32_t orientation, max_edits, flags;
+    Insert ins;
+    uint32_t max_edits, flags;
     const uint64_t* ctg_off;       // [nc + 1]: the index's contig table; nullptr without one
     const uint32_t* ctg;           // [n_loci]: the contig of every locus (the alignments'); nullptr without a table
     uint64_t nc, n_loci;
@@ -94,8 +95,8 @@ __device__ __forceinline__ bool job_window(const RescueIn& R, uint64_t r, uint32
     if (!only && !(c == KMX_PAIR_DISCORDANT && (R.flags & KMX_RESCUE_DISCORDANT))) return false;
     const uint32_t sa = R.pl_strand[2 * p + a];
     if (sa > 1) return false;                                  // (cannot happen: the anchor is placed)
-    if (s != (R.orientation == KMX_PAIR_FF ? sa : 1u - sa)) return false;
-    const bool up = R.orientation == KMX_PAIR_FR ? sa == 0 : R.orientation == KMX_PAIR_RF ? sa == 1 : (a == 0) == (sa == 0);
+    if (s != (R.ins.orientation == KMX_PAIR_FF ? sa : 1u - sa)) return false;
+    const bool up = R.ins.orientation == KMX_PAIR_FR ? sa == 0 : R.ins.orientation == KMX_PAIR_RF ? sa == 1 : (a == 0) == (sa == 0);
     const int64_t n = int64_t(R.n);
     int64_t b0 = 0, b1 = n;                                    // the bounds: the text, or the anchor's contig
     if (R.ctg) {                                               // (uniform across the grid)
@@ -109,10 +110,10 @@ __device__ __forceinline__ bool job_window(const RescueIn& R, uint64_t r, uint32
     int64_t l, h;
     if (up) {
         l = min(max(int64_t(R.pl_start[2 * p + a]), b0), b1);
-        h = min(b1, l + R.max_insert);
+        h = min(b1, l + R.ins.max_insert);
     } else {
         h = max(min(int64_t(R.pl_end[2 * p + a]), b1), b0);
-        l = max(b0, h - R.max_insert);
+        l = max(b0, h - R.ins.max_insert);
     }
     *lo = uint32_t(l);
     *hi = uint32_t(h);
@@ -257,20 +258,6 @@ struct LociIn {
     uint64_t n_loci;
 };
 
-// mate 1 on strand sx at [xs, xe), mate 2 on strand sy at [ys, ye): the template length when the two are concordant by the rule of
-// kmx_alignments_fold_pairs, else -1; *first: the upstream one is mate 1
-__device__ __forceinline__ int64_t concordant_tlen(const RescueIn& R, uint32_t sx, uint32_t xs, uint32_t xe, uint32_t sy, uint32_t ys, uint32_t ye,
-                                                   bool* first)
-{
-    *first = false;
-    if ((sx == sy) != (R.orientation == KMX_PAIR_FF)) return -1;
-    const bool f = sx == (R.orientation == KMX_PAIR_RF ? 1u : 0u);
-    const int64_t us = f ? xs : ys, ue = f ? xe : ye, vs = f ? ys : xs, ve = f ? ye : xe;
-    const int64_t t = ve - us;
-    *first = f;
-    return us <= vs && ue <= ve && t >= R.min_insert && t <= R.max_insert ? t : -1;
-}
-
 __global__ __launch_bounds__(kBlock) void k_rescue_fold(RescueIn R, LociIn L, Jobs J, uint32_t* __restrict__ best, unsigned long long* __restrict__ ctr)
 {
     __shared__ unsigned int s_ctr[CTR_COUNT];
@@ -311,8 +298,8 @@ __global__ __launch_bounds__(kBlock) void k_rescue_fold(RescueIn R, LociIn L, Jo
             jstrand[b] = J.read[j0] & 1u;
             const int a = 1 - b;
             bool first;
-            const int64_t t = b == 0 ? concordant_tlen(R, jstrand[b], js[b], je[b], st[a], ss[a], se[a], &first)
-                                     : concordant_tlen(R, st[a], ss[a], se[a], jstrand[b], js[b], je[b], &first);
+            const int64_t t = b == 0 ? concordant_tlen(R.ins, jstrand[b], js[b], je[b], st[a], ss[a], se[a], &first)
+                                     : concordant_tlen(R.ins, st[a], ss[a], se[a], jstrand[b], js[b], je[b], &first);
             if (t < 0) continue;
             status[b] = 2;
             jt[b] = first ? t : -t;
@@ -322,18 +309,10 @@ __global__ __launch_bounds__(kBlock) void k_rescue_fold(RescueIn R, LociIn L, Jo
         if (take >= 0 && cls == KMX_PAIR_DISCORDANT && uint64_t(jscore[take]) > uint64_t(sd[0]) + sd[1] + R.penalty) take = -1;
         if (take >= 0) {                                       // (the same in every lane)
             // the least distance of an aligned locus of the rescued read elsewhere from the new placement
-            const uint64_t a = min(L.locus_off[4 * p + 2 * take], L.n_loci);
-            const uint64_t b = min(max(L.locus_off[4 * p + 2 * take + 1], a), L.n_loci);
-            const uint64_t c = min(max(L.locus_off[4 * p + 2 * take + 2], b), L.n_loci);
+            uint64_t a, b, c;
+            strand_ranges(L.locus_off, L.n_loci, 4 * p + 2 * take, &a, &b, &c);
             const uint32_t sw = jstrand[take], ws = js[take], we = je[take];
-            uint32_t second = KMX_ALIGN_NONE;
-            for (uint64_t l = a + lane; l < c; l += kWave) {
-                const uint32_t d = L.dist[l];
-                if (d >= KMX_ALIGN_SKIPPED) continue;
-                const uint32_t s = l < b ? 0u : 1u;
-                if (s != sw || max(L.start[l], ws) >= min(L.end[l], we)) second = min(second, d);
-            }
-            for (int off = kWave / 2; off > 0; off >>= 1) second = min(second, uint32_t(__shfl_xor(second, off)));
+            const uint32_t second = second_elsewhere(L.dist, L.start, L.end, a, b, c, lane, kNoLocus, sw, ws, we);   // (the placement is no locus)
             status[take] = 3;
             st[take] = sw;
             sd[take] = jd[take];
@@ -369,15 +348,8 @@ __global__ __launch_bounds__(kBlock) void k_rescue_fold(RescueIn R, LociIn L, Jo
             }
             // the counters of the two handles, from the final values
 #pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                if (st[m] == 255u) continue;
-                atomicAdd(&s_ctr[CTR_PL + kmx::PL_N_PLACED], 1u);
-                if (st[m] == 1u) atomicAdd(&s_ctr[CTR_PL + kmx::PL_N_REVERSE], 1u);
-                if (sec[m] == sd[m]) atomicAdd(&s_ctr[CTR_PL + kmx::PL_N_AMBIGUOUS], 1u);
-            }
-            atomicAdd(&s_ctr[cls == KMX_PAIR_CONCORDANT ? CTR_N_CONCORDANT : cls == KMX_PAIR_DISCORDANT ? CTR_N_DISCORDANT
-                             : cls == KMX_PAIR_UNPLACED ? CTR_N_UNPLACED : CTR_N_SINGLE], 1u);
-            if (cls == KMX_PAIR_CONCORDANT && second_score == score) atomicAdd(&s_ctr[CTR_N_PAIRS_AMBIGUOUS], 1u);
+            for (int m = 0; m < 2; ++m) count_placement(s_ctr + CTR_FOLD, st[m] != 255u, st[m], sec[m], sd[m]);
+            count_pair(s_ctr + CTR_FOLD, cls, score, second_score);
         }
     }
     __syncthreads();
@@ -446,7 +418,7 @@ kmx_status rescue_run(const kmx::IndexAccess& X, const kmx_strand_reads* reads, 
     TRY_HIP(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
     const RescueIn R{pl->locus.as<uint32_t>(), pl->strand.as<uint8_t>(), pl->dist.as<uint8_t>(), pl->start.as<uint32_t>(), pl->end.as<uint32_t>(),
                      pl->second.as<uint8_t>(), pl->best2.as<uint32_t>(), pr->cls.as<uint8_t>(), pr->tlen.as<int32_t>(), pr->score.as<uint16_t>(),
-                     pr->second_score.as<uint16_t>(), np, X.n, int64_t(o.min_insert), int64_t(o.max_insert), o.unpaired_penalty, o.orientation,
+                     pr->second_score.as<uint16_t>(), np, X.n, o.unpaired_penalty, Insert{int64_t(o.min_insert), int64_t(o.max_insert), o.orientation},
                      o.max_edits, o.flags, A.ctg ? X.ctg_off : nullptr, A.ctg, A.nc, A.n_loci};
     Jobs J{h->job_off.as<uint64_t>(), h->read.as<uint32_t>(), h->lo.as<uint32_t>(), h->hi.as<uint32_t>(), h->dist.as<uint8_t>(), h->start.as<uint32_t>(),
            h->end.as<uint32_t>(), h->status.as<uint8_t>(), h->cls.as<uint8_t>(), h->key.as<unsigned long long>(), cap, 0};
@@ -498,14 +470,8 @@ kmx_status rescue_run(const kmx::IndexAccess& X, const kmx_strand_reads* reads, 
         TRY_HIP(hipGetLastError());
         TRY_KMX(kmx::read_back("kmx_pairs_rescue", s, ctr, h->h_ctr, CTR_COUNT * 8));
         const uint64_t* f = h->h_ctr.as<uint64_t>();
-        pl->n_placed = f[CTR_PL + kmx::PL_N_PLACED];
-        pl->n_reverse = f[CTR_PL + kmx::PL_N_REVERSE];
-        pl->n_ambiguous = f[CTR_PL + kmx::PL_N_AMBIGUOUS];
-        pr->n_concordant = f[CTR_N_CONCORDANT];
-        pr->n_discordant = f[CTR_N_DISCORDANT];
-        pr->n_single = f[CTR_N_SINGLE];
-        pr->n_unplaced = f[CTR_N_UNPLACED];
-        pr->n_ambiguous = f[CTR_N_PAIRS_AMBIGUOUS];
+        pl->counts_from(f + CTR_FOLD);
+        pr->counts_from(f + CTR_FOLD);
         h->n_found = f[CTR_N_FOUND];
         h->n_concordant = f[CTR_N_JOB_CONCORDANT];
         h->n_taken = f[CTR_N_TAKEN];
@@ -555,17 +521,14 @@ kmx_status kmx_pairs_rescue(const kmx_index* index, const kmx_strand_reads* read
         return refuse(KMX_ERR_INVALID_ARGUMENT, "the handles live on different devices");
     if (nr2 & 3) return refuse(KMX_ERR_INVALID_ARGUMENT, "the number of reads is no multiple of 4: not the loci of a doubled batch of pairs");
     kmx::IndexAccess X{};
-    if (!kmx::index_access_on(index, L.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the loci live on a device that holds no replica of this index");
-    if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    kmx_status no_st;
+    std::string no_index;
+    if (!kmx::index_for(index, L.device, "the loci", &X, &no_st, &no_index)) return refuse(no_st, no_index);
     if (A.nc != (X.ctg_off ? X.nc : 0) || A.ctg_gen != X.ctg_gen)
         return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments were made under another contig table of the index (kmx_index_set_contigs was called since): align again");
     kmx::DeviceGuard dg;
-    const kmx_status bound = kmx::bind_handle(inout, L.device);
+    TRY_KMX(kmx::bind_handle(inout, L.device));
     h = *inout;
-    if (bound != KMX_OK) {
-        if (h) h->clear();
-        return bound;
-    }
     hipStream_t s = reads->stream;
     bool folded = false;
     const kmx_status st = rescue_run(X, reads, L, A, *o, s, placements, pairs, h, &folded);

@@ -26,6 +26,7 @@
 
 #include "kmx_approx.h"
 #include "kmx_kernels.h"
+#include "kmx_runs.h"
 #include "kmx_script_core.h"
 #include "kmx_vote.h"
 
@@ -34,7 +35,6 @@ namespace {
 constexpr uint32_t kBlock = 256;
 constexpr int kInf = 1 << 20;                                 // beyond any distance; sums of a few of them stay inside int
 constexpr uint32_t kNoBest = 0xFFFFFFFFu;
-enum { OP_M = 0, OP_I = 1, OP_D = 2, OP_EQ = 7, OP_X = 8, OP_NONE = 15 };
 enum { CTR_N_OPS = CTR_SHARED, CTR_N_MISMATCHED, CTR_COUNT };
 
 using kmx::Buf;
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(kBlock) void k_script_walk(ScriptIn S, Entries C, c
             if (op == cur) { ++len; continue; }
             if (len) {
                 if (cnt >= res) { bad = true; break; }
-                out[-1 - int64_t(cnt)] = (len << 4) | cur;
+                out[-1 - int64_t(cnt)] = make_run(len, cur);
                 ++cnt;
             }
             cur = op;
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(kBlock) void k_script_walk(ScriptIn S, Entries C, c
         }
         if (!bad && len) {
             if (cnt >= res) bad = true;
-            else { out[-1 - int64_t(cnt)] = (len << 4) | cur; ++cnt; }
+            else { out[-1 - int64_t(cnt)] = make_run(len, cur); ++cnt; }
         }
         if (bad) {                                             // (only with foreign reads, and then the band has caught it already)
             cnt = 0;
@@ -422,8 +422,9 @@ kmx_status script_call(const char* fn, const kmx_index* index, const kmx_loci* l
     if (P && P->nr2 != nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "the placements are not those of these reads: nr differs");
     if (P && nr && P->device != L.device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the placements and the loci live on different devices");
     kmx::IndexAccess X{};
-    if (!kmx::index_access_on(index, L.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the loci live on a device that holds no replica of this index");
-    if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    kmx_status no_st;
+    std::string no_index;
+    if (!kmx::index_for(index, L.device, "the loci", &X, &no_st, &no_index)) return refuse(no_st, no_index);
     uint64_t n_letters = ranks_len;
     if (host) {
         const char* why = kmx::check_host_reads(ranks, static_cast<const uint64_t*>(roff), nr, &n_letters);
@@ -468,9 +469,7 @@ kmx_status kmx::scripts_on_arrays(const char* fn, const kmx_index* index, const 
 {
     const std::string who = std::string(fn) + ": ";
     if (!index) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "index is NULL");
-    if (!o) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options is NULL");
-    if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
-    if (o->struct_size < sizeof(kmx_script_options)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
+    TRY_KMX(kmx::check_call(who, o, inout));
     if (o->flags & ~(KMX_SCRIPT_ALL | KMX_SCRIPT_M)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "unknown flags");
     if (o->flags & KMX_SCRIPT_ALL)
         return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + (every ? "KMX_SCRIPT_ALL is not the caller's to set: every entry has a script already"
@@ -484,8 +483,9 @@ kmx_status kmx::scripts_on_arrays(const char* fn, const kmx_index* index, const 
         return kmx::set_error(st, who + msg);
     };
     kmx::IndexAccess X{};
-    if (!kmx::index_access_on(index, L.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the arrays live on a device that holds no replica of this index");
-    if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    kmx_status no_st;
+    std::string no_index;
+    if (!kmx::index_for(index, L.device, "the arrays", &X, &no_st, &no_index)) return refuse(no_st, no_index);
     kmx::DeviceGuard dg;
     TRY_KMX(kmx::bind_handle(inout, L.device));
     h = *inout;

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <string>
 
+#include "kmx_fold_core.h"
 #include "kmx_kernels.h"
 #include "kmx_strands.h"
 #include "kmx_vote.h"
@@ -61,10 +62,8 @@ __global__ __launch_bounds__(kBlock) void k_sec_pick(SecIn F, uint32_t* __restri
     const uint32_t lane = threadIdx.x % kWave, wv = threadIdx.x / kWave;
     const uint64_t i = uint64_t(blockIdx.x) * kWaves + wv;
     if (i < F.nr) {
-        // the loci of the two strands: [a, b) forward, [b, c) reverse, inside the arrays whatever the offsets hold
-        const uint64_t a = min(F.locus_off[2 * i], F.n_loci);
-        const uint64_t b = min(max(F.locus_off[2 * i + 1], a), F.n_loci);
-        const uint64_t c = min(max(F.locus_off[2 * i + 2], b), F.n_loci);
+        uint64_t a, b, c;
+        strand_ranges(F.locus_off, F.n_loci, 2 * i, &a, &b, &c);
         const uint32_t ps = F.pl_strand[i];
         const bool placed = ps != 255;                         // (a foreign strand of 2 .. 254 is a place that no locus overlaps)
         const int64_t limit = int64_t(F.pl_dist[i]) + int64_t(F.max_delta);
@@ -85,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void k_sec_pick(SecIn F, uint32_t* __restri
                 const uint32_t s = l < b ? 0u : 1u, x0 = F.start[l], x1 = F.end[l];
                 bool live = true;                              // not taken, and elsewhere from every member of T
                 for (uint32_t t = 0; t <= taken && live; ++t)
-                    live = tl[t] != uint32_t(l) && (ts[t] != s || max(x0, t0[t]) >= min(x1, t1[t]));
+                    live = tl[t] != uint32_t(l) && elsewhere(s, x0, x1, ts[t], t0[t], t1[t]);
                 if (live) key = min(key, (uint64_t(d) << 32) | l);
             }
             for (int off = kWave / 2; off > 0; off >>= 1) key = min(key, uint64_t(__shfl_xor((unsigned long long)key, off)));
@@ -237,9 +236,7 @@ kmx_status kmx_placements_secondaries(const kmx_loci* loci, const kmx_alignments
     if (!loci) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "loci handle is NULL");
     if (!alignments) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "alignments handle is NULL");
     if (!placements) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "placements handle is NULL");
-    if (!o) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options is NULL");
-    if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
-    if (o->struct_size < sizeof(kmx_secondary_options)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
+    TRY_KMX(kmx::check_call(who, o, inout));
     if (o->flags != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "flags must be 0");
     if (o->max_secondary == 0 || o->max_secondary > KMX_SECONDARY_MAX)
         return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "max_secondary is not in 1 .. KMX_SECONDARY_MAX");
@@ -258,12 +255,8 @@ kmx_status kmx_placements_secondaries(const kmx_loci* loci, const kmx_alignments
     if (A.device != L.device || (L.nr && P.device != L.device)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the handles live on different devices");
     if ((L.nr / 2) * uint64_t(o->max_secondary) >= (uint64_t(1) << 32)) return refuse(KMX_ERR_TOO_LARGE, "nr * max_secondary is 2^32 or more: split the batch");
     kmx::DeviceGuard dg;
-    const kmx_status bound = kmx::bind_handle(inout, L.device);
+    TRY_KMX(kmx::bind_handle(inout, L.device));
     h = *inout;
-    if (bound != KMX_OK) {
-        if (h) h->clear();
-        return bound;
-    }
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : P.stream;
     const kmx_status st = secondaries_run(L, A, P, *o, s, h);
     if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one

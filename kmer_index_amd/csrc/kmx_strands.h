@@ -8,6 +8,9 @@
 namespace kmx {
 // the batch counters a fold kernel adds up, in the order of kmx_placements_counts
 enum { PL_N_PLACED = 0, PL_N_REVERSE, PL_N_AMBIGUOUS, PL_COUNT };
+// ... and, behind them in the same array where a kernel counts both (k_pair_fold, k_rescue_fold), the pairs', in the order of
+// kmx_pairs_counts
+enum { PR_N_CONCORDANT = PL_COUNT, PR_N_DISCORDANT, PR_N_SINGLE, PR_N_UNPLACED, PR_N_AMBIGUOUS, PR_COUNT };
 } // namespace kmx
 
 struct kmx_placements {
@@ -23,6 +26,8 @@ struct kmx_placements {
         for (kmx::PinnedArr* b : {&h_ctr, &h_locus, &h_strand, &h_dist, &h_start, &h_end, &h_second, &h_best2}) b->release();
     }
     void clear() { nr = n_placed = n_reverse = n_ambiguous = 0; host_valid = false; host_best2_valid = false; }
+    // c: the counters of a fold as they were read back, c[kmx::PL_*] the placements'
+    void counts_from(const uint64_t* c) { n_placed = c[kmx::PL_N_PLACED]; n_reverse = c[kmx::PL_N_REVERSE]; n_ambiguous = c[kmx::PL_N_AMBIGUOUS]; }
     // the seven arrays of n public reads
     hipError_t room(uint64_t n)
     {
@@ -69,4 +74,13 @@ struct kmx_pairs {
         for (kmx::PinnedArr* b : {&h_ctr, &h_cls, &h_tlen, &h_score, &h_second_score}) b->release();
     }
     void clear() { np = n_concordant = n_discordant = n_single = n_unplaced = n_ambiguous = 0; host_valid = false; }
+    // c: the counters of a fold as they were read back, c[kmx::PR_*] the pairs'
+    void counts_from(const uint64_t* c)
+    {
+        n_concordant = c[kmx::PR_N_CONCORDANT];
+        n_discordant = c[kmx::PR_N_DISCORDANT];
+        n_single = c[kmx::PR_N_SINGLE];
+        n_unplaced = c[kmx::PR_N_UNPLACED];
+        n_ambiguous = c[kmx::PR_N_AMBIGUOUS];
+    }
 };

@@ -15,6 +15,7 @@
 #include <string>
 
 #include "kmx_approx.h"
+#include "kmx_fold_core.h"
 #include "kmx_kernels.h"
 #include "kmx_strands.h"
 #include "kmx_vote.h"
@@ -26,7 +27,7 @@ constexpr uint32_t kWave = 64;
 constexpr uint32_t kNoBest = 0xFFFFFFFFu;
 constexpr uint64_t kMaxReads = uint64_t(1) << 30;
 constexpr uint64_t kMaxLetters = uint64_t(1) << 62;
-enum { CTR_N_PLACED = kmx::PL_N_PLACED, CTR_N_REVERSE = kmx::PL_N_REVERSE, CTR_N_AMBIGUOUS = kmx::PL_N_AMBIGUOUS, CTR_COUNT = kmx::PL_COUNT };
+constexpr int CTR_COUNT = kmx::PL_COUNT;
 
 using kmx::Buf;
 using Pinned = kmx::PinnedArr;
@@ -87,59 +88,36 @@ struct FoldOut {
 
 __global__ __launch_bounds__(kBlock) void k_strand_fold(FoldIn F, FoldOut O)
 {
-    __shared__ unsigned int s_placed, s_rev, s_amb;
-    if (threadIdx.x == 0) { s_placed = 0; s_rev = 0; s_amb = 0; }
+    __shared__ unsigned int s_ctr[CTR_COUNT];
+    if (threadIdx.x < CTR_COUNT) s_ctr[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t lane = threadIdx.x % kWave;
     const uint64_t i = uint64_t(blockIdx.x) * (kBlock / kWave) + threadIdx.x / kWave;
     if (i < F.nr) {
-        // the loci of the two strands: [a, b) forward, [b, c) reverse, inside the arrays whatever the offsets hold
-        const uint64_t a = min(F.locus_off[2 * i], F.n_loci);
-        const uint64_t b = min(max(F.locus_off[2 * i + 1], a), F.n_loci);
-        const uint64_t c = min(max(F.locus_off[2 * i + 2], b), F.n_loci);
-        const uint32_t bf = F.best[2 * i], br = F.best[2 * i + 1];
-        // step 1: the winner, the better of the two bests; the forward strand wins a tie
-        uint32_t df = KMX_ALIGN_NONE, dr = KMX_ALIGN_NONE;
-        if (bf != kNoBest && bf < b - a) df = F.dist[a + bf];
-        if (br != kNoBest && br < c - b) dr = F.dist[b + br];
-        const bool okf = df < KMX_ALIGN_SKIPPED, okr = dr < KMX_ALIGN_SKIPPED;
-        const bool placed = okf || okr;
-        const uint32_t sw = okf && (!okr || df <= dr) ? 0u : 1u;
-        const uint64_t w = sw == 0 ? a + bf : b + br;
-        uint32_t wd = KMX_ALIGN_NONE, ws = 0, we = 0;
-        if (placed) { wd = sw == 0 ? df : dr; ws = F.start[w]; we = F.end[w]; }
-        // step 2: the least distance of an aligned locus elsewhere
-        uint32_t second = KMX_ALIGN_NONE;
-        if (placed)
-            for (uint64_t l = a + lane; l < c; l += kWave) {
-                const uint32_t d = F.dist[l];
-                if (d >= KMX_ALIGN_SKIPPED || l == w) continue;
-                const uint32_t s = l < b ? 0u : 1u;
-                if (s != sw || max(F.start[l], ws) >= min(F.end[l], we)) second = min(second, d);
-            }
-        for (int off = kWave / 2; off > 0; off >>= 1) second = min(second, uint32_t(__shfl_xor(second, off)));
+        uint64_t a, b, c;
+        strand_ranges(F.locus_off, F.n_loci, 2 * i, &a, &b, &c);
+        // step 1: the winner; step 2: the least distance of an aligned locus elsewhere
+        const Winner W = strand_winner(F.dist, F.best, 2 * i, a, b, c);
+        uint32_t ws = 0, we = 0, second = KMX_ALIGN_NONE;
+        if (W.placed) {
+            ws = F.start[W.locus];
+            we = F.end[W.locus];
+            second = second_elsewhere(F.dist, F.start, F.end, a, b, c, lane, W.locus, W.strand, ws, we);
+        }
         if (lane == 0) {
-            O.locus[i] = placed ? uint32_t(w) : kNoBest;
-            O.strand[i] = placed ? uint8_t(sw) : uint8_t(255);
-            O.dist[i] = uint8_t(wd);
+            O.locus[i] = W.placed ? uint32_t(W.locus) : kNoBest;
+            O.strand[i] = W.placed ? uint8_t(W.strand) : uint8_t(255);
+            O.dist[i] = uint8_t(W.dist);
             O.start[i] = ws;
             O.end[i] = we;
             O.second[i] = uint8_t(second);
-            O.best2[2 * i] = placed && sw == 0 ? bf : kNoBest;
-            O.best2[2 * i + 1] = placed && sw == 1 ? br : kNoBest;
-            if (placed) {
-                atomicAdd(&s_placed, 1u);
-                if (sw) atomicAdd(&s_rev, 1u);
-                if (second == wd) atomicAdd(&s_amb, 1u);
-            }
+            O.best2[2 * i] = W.placed && W.strand == 0 ? uint32_t(W.locus - a) : kNoBest;
+            O.best2[2 * i + 1] = W.placed && W.strand == 1 ? uint32_t(W.locus - b) : kNoBest;
+            count_placement(s_ctr, W.placed, W.strand, second, W.dist);
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        if (s_placed) atomicAdd(&O.ctr[CTR_N_PLACED], (unsigned long long)s_placed);
-        if (s_rev) atomicAdd(&O.ctr[CTR_N_REVERSE], (unsigned long long)s_rev);
-        if (s_amb) atomicAdd(&O.ctr[CTR_N_AMBIGUOUS], (unsigned long long)s_amb);
-    }
+    if (threadIdx.x < CTR_COUNT && s_ctr[threadIdx.x]) atomicAdd(&O.ctr[threadIdx.x], (unsigned long long)s_ctr[threadIdx.x]);
 }
 
 } // namespace
@@ -243,9 +221,7 @@ kmx_status fold_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, hipStre
     TRY_HIP(hipGetLastError());
     TRY_KMX(kmx::read_back("kmx_alignments_fold_strands", s, ctr, p->h_ctr, CTR_COUNT * 8));
     p->nr = nr;
-    p->n_placed = p->h_ctr.as<uint64_t>()[CTR_N_PLACED];
-    p->n_reverse = p->h_ctr.as<uint64_t>()[CTR_N_REVERSE];
-    p->n_ambiguous = p->h_ctr.as<uint64_t>()[CTR_N_AMBIGUOUS];
+    p->counts_from(p->h_ctr.as<uint64_t>());
     return KMX_OK;
 }
 
@@ -283,9 +259,7 @@ kmx_status kmx_alignments_fold_strands(const kmx_loci* loci, const kmx_alignment
     const std::string who = "kmx_alignments_fold_strands: ";
     if (!loci) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "loci handle is NULL");
     if (!alignments) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "alignments handle is NULL");
-    if (!o) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options is NULL");
-    if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
-    if (o->struct_size < sizeof(kmx_fold_options)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
+    TRY_KMX(kmx::check_call(who, o, inout));
     if (o->flags != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "flags must be 0");
     const kmx::LociAccess L = kmx::loci_access(loci);
     const kmx::AlignAccess A = kmx::alignments_access(alignments);

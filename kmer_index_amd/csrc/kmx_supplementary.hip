@@ -331,9 +331,7 @@ kmx_status kmx_clips_supplementaries(const kmx_strand_reads* reads, const kmx_lo
                                      const kmx_supplementary_options* o, void* stream, kmx_supplementaries** inout)
 {
     const std::string who = "kmx_clips_supplementaries: ";
-    if (!o) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options is NULL");
-    if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
-    if (o->struct_size < sizeof(kmx_supplementary_options)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
+    TRY_KMX(kmx::check_call(who, o, inout));
     if (o->flags != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "flags must be 0");
     if (o->max_supplementary == 0 || o->max_supplementary > KMX_SUPPLEMENTARY_MAX)
         return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "max_supplementary is not in 1 .. KMX_SUPPLEMENTARY_MAX");
@@ -370,12 +368,8 @@ kmx_status kmx_clips_supplementaries(const kmx_strand_reads* reads, const kmx_lo
     if ((nr2 / 2) * uint64_t(o->max_supplementary) >= (uint64_t(1) << 32))
         return refuse(KMX_ERR_TOO_LARGE, "nr * max_supplementary is 2^32 or more: split the batch");
     kmx::DeviceGuard dg;
-    const kmx_status bound = kmx::bind_handle(inout, reads->device);
+    TRY_KMX(kmx::bind_handle(inout, reads->device));
     h = *inout;
-    if (bound != KMX_OK) {
-        if (h) h->clear();
-        return bound;
-    }
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : C.stream;
     const kmx_status st = supplementaries_run(reads, A, P, S, C, *o, s, h);
     if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one

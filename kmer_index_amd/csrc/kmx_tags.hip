@@ -20,6 +20,7 @@
 
 #include "kmx_approx.h"
 #include "kmx_kernels.h"
+#include "kmx_runs.h"
 #include "kmx_strands.h"
 #include "kmx_vote.h"
 
@@ -27,7 +28,6 @@ namespace {
 
 constexpr uint32_t kBlock = 256;
 constexpr uint32_t kNoScore = 0xFFFFu;
-enum { OP_I = 1, OP_D = 2, OP_S = 4, OP_EQ = 7, OP_X = 8 };
 enum { MD_N_BYTES = 0, MD_N_MISMATCHED, MD_COUNT };
 enum { MQ_N_ZERO = 0, MQ_N_CAP, MQ_COUNT };
 
@@ -60,13 +60,6 @@ __device__ __forceinline__ uint32_t digits_of(uint64_t c)
     return nd;
 }
 
-// the runs of entry e, inside cigar[n_ops] whatever the offsets hold
-__device__ __forceinline__ void runs_of(const MdIn& M, uint64_t e, uint64_t* a, uint64_t* b)
-{
-    *a = min(M.cig_off[e], M.n_ops);
-    *b = min(max(M.cig_off[e + 1], *a), M.n_ops);
-}
-
 // ---- MD --------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_md_count(MdIn M, uint32_t* __restrict__ cnt, unsigned long long* __restrict__ ctr)
 {
@@ -76,7 +69,7 @@ __global__ __launch_bounds__(kBlock) void k_md_count(MdIn M, uint32_t* __restric
     const uint64_t e = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
     if (e < M.n_sel) {
         uint64_t a, b;
-        runs_of(M, e, &a, &b);
+        runs_of(M.cig_off, M.n_ops, e, &a, &b);
         uint64_t bytes = 0;
         if (b > a) {                                           // (an entry without runs: an empty MD, not counted)
             const uint32_t l = M.sel[e];
@@ -94,8 +87,8 @@ __global__ __launch_bounds__(kBlock) void k_md_count(MdIn M, uint32_t* __restric
             }
             uint64_t c = 0, sum = 0;
             for (uint64_t k = a; k < b && !bad; ++k) {
-                const uint32_t v = M.cigar[k], op = v & 15u;
-                const uint64_t len = v >> 4;
+                const uint32_t v = M.cigar[k], op = run_op(v);
+                const uint64_t len = run_len(v);
                 if (op == OP_EQ) { c += len; sum += len; }
                 else if (op == OP_X) {
                     if (len) { bytes += digits_of(c) + 1 + 2 * (len - 1); c = 0; }
@@ -138,17 +131,14 @@ __global__ __launch_bounds__(kBlock) void k_md_write(MdIn M, const uint64_t* __r
     const uint32_t l = M.sel[e];
     if (l >= M.bound) return;                                  // (cannot happen: k_md_count saw the same arrays)
     uint64_t a, b;
-    runs_of(M, e, &a, &b);
-    const uint32_t w = M.w, per = 64 / w;
-    const uint64_t mask = (uint64_t(1) << w) - 1;              // (w <= 8)
+    runs_of(M.cig_off, M.n_ops, e, &a, &b);
     auto letter_at = [&](uint64_t j) -> uint8_t {              // the text letter j through the table; past the text: a '?' nobody sees
-        if (j >= M.n) return uint8_t('?');
-        return table[uint32_t((M.text[j / per] >> ((j % per) * w)) & mask)];
+        return j < M.n ? table[text_letter(M.text, M.w, j)] : uint8_t('?');
     };
     uint64_t c = 0, j = uint64_t(M.start[l]) + (M.tl ? M.tl[e] : 0);
     for (uint64_t k = a; k < b; ++k) {
-        const uint32_t v = M.cigar[k], op = v & 15u;
-        const uint64_t len = v >> 4;
+        const uint32_t v = M.cigar[k], op = run_op(v);
+        const uint64_t len = run_len(v);
         if (op == OP_EQ) { c += len; j += len; }
         else if (op == OP_X) {
             for (uint64_t x = 0; x < len; ++x) {
@@ -297,9 +287,7 @@ kmx_status md_run(const char* fn, const kmx::IndexAccess& X, const kmx::ScriptsA
 kmx_status md_front(const std::string& who, const kmx_index* index, const void* scripts, const void* source, const char* source_name,
                     const uint8_t* letters, const kmx_md_options* o, kmx_md** inout)
 {
-    if (!o) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options is NULL");
-    if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
-    if (o->struct_size < sizeof(kmx_md_options)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
+    TRY_KMX(kmx::check_call(who, o, inout));
     if (o->flags != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "flags must be 0");
     if (!letters) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "NULL letters table");
     if (!index) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "index is NULL");
@@ -328,15 +316,12 @@ kmx_status md_on_arrays(const char* fn, const kmx_index* index, const kmx::Scrip
     if (K && K->n_sel != S.n_sel) return refuse(KMX_ERR_INVALID_ARGUMENT, "the clips are not those of these scripts: n_sel differs");
     if (K && K->n_sel && K->device != S.device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the clips and the scripts live on different devices");
     kmx::IndexAccess X{};
-    if (!kmx::index_access_on(index, S.device, &X)) return refuse(KMX_ERR_INVALID_ARGUMENT, "the scripts live on a device that holds no replica of this index");
-    if (X.broken) return refuse(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    kmx_status no_st;
+    std::string no_index;
+    if (!kmx::index_for(index, S.device, "the scripts", &X, &no_st, &no_index)) return refuse(no_st, no_index);
     kmx::DeviceGuard dg;
-    const kmx_status bound_st = kmx::bind_handle(inout, S.device);
+    TRY_KMX(kmx::bind_handle(inout, S.device));
     h = *inout;
-    if (bound_st != KMX_OK) {
-        if (h) h->clear();
-        return bound_st;
-    }
     hipStream_t s = stream ? stream : S.stream;
     const kmx_status st = md_run(fn, X, S, start, end, bound, letters, s, h, K);
     if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
@@ -459,9 +444,7 @@ void kmx_md_free(kmx_md* h) { kmx::free_handle(h); }
 kmx_status kmx_placements_mapq(const kmx_placements* placements, const kmx_pairs* pairs, const kmx_mapq_options* o, void* stream, kmx_mapq** inout)
 {
     const std::string who = "kmx_placements_mapq: ";
-    if (!o) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options is NULL");
-    if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
-    if (o->struct_size < sizeof(kmx_mapq_options)) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "options->struct_size is too small");
+    TRY_KMX(kmx::check_call(who, o, inout));
     if (o->flags != 0) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "flags must be 0");
     if (o->max_edits > KMX_ALIGN_MAX_EDITS) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "max_edits > KMX_ALIGN_MAX_EDITS");
     if (o->cap > 254) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "cap > 254 (255 is SAM's \"unavailable\")");
@@ -474,12 +457,8 @@ kmx_status kmx_placements_mapq(const kmx_placements* placements, const kmx_pairs
     if (pairs && 2 * pairs->np != placements->nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "the pairs are not those of these placements: 2 np differs from nr");
     if (pairs && placements->nr && pairs->device != placements->device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the placements and the pairs live on different devices");
     kmx::DeviceGuard dg;
-    const kmx_status bound = kmx::bind_handle(inout, placements->device);
+    TRY_KMX(kmx::bind_handle(inout, placements->device));
     h = *inout;
-    if (bound != KMX_OK) {
-        if (h) h->clear();
-        return bound;
-    }
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : placements->stream;
     const kmx_status st = mapq_run(placements, pairs, *o, s, h);
     if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one

@@ -116,7 +116,7 @@ JobsAccess rescues_access(const kmx_rescues* r);   // kmx_rescue.hip
 // sel of kmx_secondaries_scripts indexes
 JobsAccess secondaries_access(const kmx_secondaries* s);   // kmx_secondary.hip
 
-// What the MD of clipped entries (kmx_clips_md, kmx_clips_rescues_md; kmx_tags.hip) needs from a clips handle (kmx_clip.hip owns
+// What the MD of clipped entries (kmx_clips_md, kmx_clips_rescues_md; kmx_tags.hip) needs from a clips handle (kmx_clips.h holds
 // struct kmx_clips): the clipped runs and the text letters clipped off either side.  The per-entry arrays are only looked at when
 // n_sel > 0, cigar when n_ops > 0; a handle that no call has filled (or whose last call was refused) has n_sel = 0.  The supplementary
 // alignments (kmx_supplementary.hip) read the other per-entry values as well.
@@ -135,31 +135,5 @@ struct ClipsAccess {
     const uint8_t* cflags;
 };
 ClipsAccess clips_access(const kmx_clips* c);   // kmx_clip.hip
-
-// How the realignment (kmx_scripts_realign, kmx_realign.hip) fills a clips handle, which kmx_clip.hip owns.  The order of a call:
-// clips_bind (the handle lives on `device`, allocated when *inout == NULL), clips_begin (an empty result on stream s, then the
-// per-entry arrays for n_sel entries: `out` points into the handle; with n_sel == 0 the one offset 0 is written and the handle is
-// filled), clips_runs (room for n_ops runs), clips_finish (the counts; the handle is filled).  clips_clear: the empty result of a
-// refusal or an error.  extra / h_extra: buffers for the caller's own scratch, released with the handle.
-constexpr int kClipsExtra = 16;
-struct ClipsFill {
-    int32_t* score;                // [n_sel]
-    uint16_t* sl;
-    uint16_t* sr;
-    uint16_t* tl;
-    uint16_t* tr;
-    uint16_t* nm;
-    uint8_t* cflags;
-    uint64_t* cig_off;             // [n_sel + 1]
-    uint32_t* cnt;                 // [n_sel], and 16 bytes more: the runs of every entry, for the scan that gives cig_off
-    uint64_t* bsum;                // the block sums of kmx::launch_scan over n_sel values
-    Buf* extra;                    // [kClipsExtra]
-    PinnedArr* h_extra;
-};
-kmx_status clips_bind(kmx_clips** inout, int device);
-kmx_status clips_begin(kmx_clips* c, hipStream_t s, uint64_t n_sel, ClipsFill* out);
-kmx_status clips_runs(kmx_clips* c, uint64_t n_ops, uint32_t** cigar);
-void clips_finish(kmx_clips* c, uint64_t n_sel, uint64_t n_ops, uint64_t n_clipped, uint64_t n_low);
-void clips_clear(kmx_clips* c);
 
 } // namespace kmx

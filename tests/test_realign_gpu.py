@@ -393,3 +393,52 @@ def test_the_chain_keyword_puts_the_realignment_in_the_trimmer_s_place(engine, i
         tclip.check_clips(base[9].all_clips, base[9].all_scripts, clip_penalty=0)
     finally:
         close_all(held)
+
+
+# ---- 7. an entry that stays whole is the same entry in the trimmer and in the realignment ------------------------------------------------
+def short_reads():
+    """(64 reads of 40 .. 80 letters from random places with 0 .. 3 edits and one with a letter outside the alphabet, the first read
+    without an edit)"""
+    t = text()
+    z = tclip.synth.u64_stream(913, 16 * 64).astype(np.int64) & 0x7FFFFFFF
+    reads, edits = [], []
+    for p in range(64):
+        zz = z[16 * p:16 * p + 16]
+        s = 1000 + int(zz[0] % 17_000)
+        edits.append(int(zz[1] % 4))
+        reads.append(tclip.edited(zz[2:], t[s:s + 40 + p % 41], edits[-1]))
+    foreign = t[3000:3060].copy()
+    foreign[30] = 4
+    return reads + [foreign], edits.index(0)
+
+
+def test_a_floor_nothing_meets_leaves_the_same_whole_entries_in_both_calls(engine, index):
+    reads, x = short_reads()
+    ranks, roff = pack(reads)
+    floor = 2 ** 31 - 1
+    held = list(index.map_reads(ranks, roff, K, **CHAIN))
+    try:
+        loci, al = held
+        # the scripts of other letters in read x than were aligned: its entries are mismatched and have no runs
+        swapped = ranks.copy()
+        swapped[int(roff[x]):int(roff[x + 1])] = other(swapped[int(roff[x]):int(roff[x + 1])])
+        sc = al.scripts(index, loci, swapped, roff, all=True)
+        held.append(sc)
+        read_sel_off, sel, cig_off, cigar = sc.host()
+        runs = np.diff(cig_off.astype(np.int64))
+        of_read = lambda r: slice(int(read_sel_off[r]), int(read_sel_off[r + 1]))
+        assert sel.size >= 50 and runs[of_read(x)].size >= 1 and not runs[of_read(x)].any() and sc.counts()["n_mismatched"] >= 1
+        assert runs[of_read(64)].size >= 1 and runs[of_read(64)].min() >= 3                    # '=', an X at the foreign letter, '='
+        trimmed = sc.clip(min_score=floor)
+        held.append(trimmed)
+        again = sc.realign(index, al, swapped, roff, min_score=floor)
+        held.append(again)
+        got, want = again.host(), trimmed.host()
+        for name, g, w in zip(CLIPS, got, want):
+            assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), name
+        assert again.counts() == trimmed.counts() == dict(n_sel=sel.size, n_ops=cigar.size, n_clipped=0, n_low=sel.size)
+        # ... and what the oracle says (tests/realign_naive.py takes a whole entry from tests/clip_naive.py): the script, whole
+        tclip.check_clips(trimmed, sc, min_score=floor)
+        assert np.array_equal(got[7], cig_off) and np.array_equal(got[8], cigar) and (got[6] == engine.CLIP_LOW).all()
+    finally:
+        close_all(held)

@@ -1540,6 +1540,130 @@ kmx_status kmx_supplementaries_view_device(const kmx_supplementaries* s, const u
                                            const uint8_t** d_more);
 void kmx_supplementaries_free(kmx_supplementaries* s);
 
+/* ---- Pileup: the chain's alignments counted per text position, and the candidate sites (an extension, no reference
+ *      interface; a caller detects the capability by the macro KMX_PILEUP, KMX_VERSION is unchanged).  Every other stage
+ *      turns per-locus data into a per-read answer; kmx_clips_pileup_device / kmx_clips_rescues_pileup turn the per-read
+ *      answers (the runs of a scripts or clips handle, the clipped text interval, KMX_CLIP_LOW, the score, a MAPQ array)
+ *      into a per-text-position answer on the device, and kmx_pileup_sites into the few positions worth looking at.
+ *
+ *      The pileup handle holds, for a text region [lo, hi) of len = hi - lo positions, C = sigma + 3 planes of uint32
+ *      counters, CHANNEL-MAJOR: counts[c len + (pos - lo)].  Channel c < sigma: a read letter of rank c aligned ('=' or 'X')
+ *      to the position; c = sigma (OTHER): an aligned read letter >= sigma; c = sigma + 1 (DEL): the position lies inside a
+ *      'D' run; c = sigma + 2 (INS): an 'I' run lies between the position and the next, counted once per run at the text
+ *      letter in front of it (the VCF anchor).  The layout is ABI.  Counters wrap modulo 2^32; nothing guards that.
+ *
+ *      Input.  kmx_clips_pileup_device serves the scripts of kmx_alignments_scripts[_device] and kmx_placements_scripts: sel
+ *      indexes the alignments' start / end, and d_ranks / d_roff / nr are the reads that were aligned, on the device (for
+ *      the scripts of the placements: the doubled batch).  kmx_clips_rescues_pileup serves the scripts of
+ *      kmx_rescues_scripts: sel indexes the rescue's jobs, and the reads are the doubled batch of `reads`.  `clips` is the
+ *      clips handle of those scripts (kmx_scripts_clip or kmx_scripts_realign), or NULL: the scripts' own runs then, with
+ *      tl = tr = 0, no score and no cflags.  d_mapq is a raw device array (kmx_mapq_view_device) that is read at r >> 1 for
+ *      internal read r, so it means something only over a doubled batch; NULL: no MAPQ filter.  `stream` NULL means the
+ *      stream that filled the scripts.  The calls only read their inputs.
+ *
+ *      The contract of entry e, in int64 (tests/pileup_naive.py is this text in executable form).  The runs are the
+ *      clips' when given, else the scripts'; l = sel[e]; r = the internal read with read_sel_off[r] <= e <
+ *      read_sel_off[r + 1], m its length, q its letters; s = start[l], t = end[l]; tl, tr, score, cflags are the clips', or 0.
+ *      In this order:
+ *        1. No runs: nothing happens, no counter moves.
+ *        2. FILTERED (n_filtered) when KMX_PILEUP_SKIP_LOW is set, clips are given and cflags & KMX_CLIP_LOW; or clips are
+ *           given and score < min_score; or d_mapq is given, there is such an r, and d_mapq[r >> 1] < min_mapq.
+ *        3. MISMATCHED (n_mismatched, nothing added) when l >= the bound of start / end; there is no such r (or its roff
+ *           range is not one); not s <= t <= n; tl + tr > t - s; an op other than = X I D S; an S run that is neither the
+ *           first nor the last run; the = X D lengths differ from t - s - tl - tr; the = X I S lengths differ from m.  One
+ *           pass over the runs decides this in front of any add.
+ *        4. Otherwise ADDED (n_added).  t0 = s + tl, t1 = t - tr, cursors i = 0, j = t0.  'S': i += len.  '=' / 'X': for
+ *           each letter x, add(q[i + x] < sigma ? q[i + x] : sigma, j + x); both cursors advance.  'D': add(DEL, j + x) for
+ *           each x; j advances.  'I': if t0 < j < t1, add(INS, j - 1) once; i advances (a terminal 'I' run is an overhang,
+ *           which SAM would clip: not counted).  add(c, pos) does something only for lo <= pos < hi: the counter goes up
+ *           by one, and so does n_cells.
+ *      Internal read 2i + 1 of a doubled batch already is the reverse complement: its letters are in text orientation,
+ *      nothing is strand-specific.  Every access is bounded by n_sel, n_ops, the bound, nr, the read's own range and the
+ *      region: foreign handles give meaningless but harmless counts.
+ *
+ *      Lifecycle.  *inout == NULL allocates the handle and zeroes the planes of the call's region (hi == 0: the text length
+ *      n).  A handle passed in without KMX_PILEUP_ADD is re-made for the call's region and zeroed; with KMX_PILEUP_ADD the
+ *      call adds to what is there (to zeroed planes when the handle holds nothing), and is refused, the handle untouched,
+ *      when lo, hi or sigma differ from the handle's.  The counters of kmx_pileup_counts are cumulative since the planes
+ *      were last zeroed.  THE CALL DOES NOT SYNCHRONISE: it leaves its kernels in flight on `stream` and reads nothing
+ *      back.  kmx_pileup_counts and kmx_pileup_view synchronise on the stream of the
+ *      last call; kmx_pileup_view fills page-locked host memory (4 C len bytes), kmx_pileup_view_device returns the device
+ *      pointer (NULL for a handle that holds nothing).  Streams between calls, and the scratch of the handle that two calls
+ *      share, are the caller's to order, as elsewhere in the chain.
+ *
+ *      mode and tile are knobs like scratch_bytes: THE RESULT NEVER DEPENDS ON THEM.  KMX_PILEUP_ATOMIC: a wave per entry,
+ *      the lanes on consecutive positions of a plane, global atomic adds.  KMX_PILEUP_TILED (the region in tiles of `tile`
+ *      positions, a workgroup per tile that counts in LDS and adds its planes with plain loads and stores) was built and
+ *      measured, lost to the atomic path at every shape that was probed, and is not in the library:
+ *      KMX_PILEUP_TILED AND KMX_PILEUP_AUTO RUN THE ATOMIC PATH, and `tile` is checked and otherwise ignored.  Both fields
+ *      stay so that a path for batches the probe could not reach can come back without a change of the ABI.
+ *
+ *      kmx_pileup_sites: for every pos in [lo, hi), ref = text[pos]; depth = the sum of the channels 0 .. sigma + 1 in
+ *      uint64; the position is skipped when depth < max(min_depth, 1), else it counts in n_covered.  The candidates, in
+ *      ascending channel order, are the letters c < sigma with c != ref, then DEL, then INS (OTHER never is one); a
+ *      candidate passes when cnt >= max(min_alt, 1) and cnt frac_den >= frac_num depth, in integers.  One record per
+ *      passing (pos, channel), ordered by (pos, channel): pos (u32), ref, alt (u8; alt is a channel), depth, count,
+ *      ref_count (u32; depth saturated) and, when the index has a contig table, ctg (u32; the view is NULL otherwise).  A
+ *      deletion is reported per deleted position.  The sites handle follows the lifecycle of the other chain handles (the
+ *      call synchronises: one read-back sizes the records; `stream` NULL means the stream of the pileup's last call).
+ *
+ *      KMX_ERR_INVALID_ARGUMENT before any handle is looked at: a NULL argument (clips and d_mapq may be NULL), a
+ *      struct_size that is too small, unknown flag bits, mode > 2, a tile that is neither 0 nor a power of two >= 64; for
+ *      the sites frac_den == 0 or frac_num > frac_den.  After looking: lo >= hi or hi > n, scripts made with KMX_SCRIPT_M,
+ *      clips whose n_sel differs from the scripts', an nr that differs from the scripts', an odd nr with d_mapq, handles on
+ *      different devices, a device without a replica of the index, the KMX_PILEUP_ADD mismatch; KMX_ERR_HIP for an index
+ *      broken by kmx_index_extend_query_size_range; for the sites a pileup that holds nothing, or whose channels are not
+ *      sigma + 3 or whose hi > n.  After such a refusal a pileup handle that was passed in holds nothing, unless
+ *      KMX_PILEUP_ADD was set: then it is untouched.  After an error of the device it holds nothing.
+ *
+ *      Left out: merging deleted positions into one indel record, the inserted letters, base qualities, a VCF writer, the
+ *      scripts of kmx_secondaries_scripts.  Untested: an index with more than one replica, the different-devices refusals,
+ *      and any batch above the sizes of the chain's tests (8192 internal reads).  kmx_stats_get is not extended. */
+#define KMX_PILEUP 1
+#define KMX_PILEUP_ADD      1u   /* flags: add to the planes the handle holds */
+#define KMX_PILEUP_SKIP_LOW 2u   /* flags: entries whose clips carry KMX_CLIP_LOW are FILTERED */
+#define KMX_PILEUP_AUTO   0u
+#define KMX_PILEUP_ATOMIC 1u
+#define KMX_PILEUP_TILED  2u
+typedef struct kmx_pileup_options {
+    uint32_t struct_size;   /* = sizeof(kmx_pileup_options): 40 */
+    uint32_t flags;         /* KMX_PILEUP_ADD | KMX_PILEUP_SKIP_LOW */
+    uint64_t lo, hi;        /* the region; hi == 0: the text length n */
+    int32_t min_score;      /* entries whose clips score less are FILTERED */
+    uint32_t min_mapq;      /* entries whose read's MAPQ is less are FILTERED (with d_mapq) */
+    uint32_t mode;          /* KMX_PILEUP_AUTO, _ATOMIC or _TILED; the result never depends on it (all three run the atomic path) */
+    uint32_t tile;          /* 0, or a power of two >= 64; checked, otherwise ignored (see above) */
+} kmx_pileup_options;
+typedef struct kmx_sites_options {
+    uint32_t struct_size;   /* = sizeof(kmx_sites_options): 20 */
+    uint32_t min_depth;
+    uint32_t min_alt;
+    uint32_t frac_num;      /* a candidate needs cnt frac_den >= frac_num depth */
+    uint32_t frac_den;
+} kmx_sites_options;
+typedef struct kmx_pileup kmx_pileup;
+typedef struct kmx_sites kmx_sites;
+kmx_status kmx_clips_pileup_device(const kmx_index* index, const kmx_alignments* alignments, const kmx_scripts* scripts,
+                                   const kmx_clips* clips /* or NULL */, const void* d_ranks, const void* d_roff, uint64_t nr,
+                                   const uint8_t* d_mapq /* nr / 2, or NULL */, const kmx_pileup_options* options, void* stream,
+                                   kmx_pileup** inout);
+kmx_status kmx_clips_rescues_pileup(const kmx_index* index, const kmx_strand_reads* reads, const kmx_rescues* rescues,
+                                    const kmx_scripts* scripts, const kmx_clips* clips /* or NULL */, const uint8_t* d_mapq /* or NULL */,
+                                    const kmx_pileup_options* options, void* stream, kmx_pileup** inout);
+kmx_status kmx_pileup_counts(kmx_pileup* p, uint64_t* lo, uint64_t* hi, uint32_t* n_channels, uint64_t* n_added, uint64_t* n_filtered,
+                             uint64_t* n_mismatched, uint64_t* n_cells);
+kmx_status kmx_pileup_view(kmx_pileup* p, const uint32_t** counts /* n_channels * (hi - lo) */);
+kmx_status kmx_pileup_view_device(const kmx_pileup* p, const uint32_t** d_counts);
+void kmx_pileup_free(kmx_pileup* p);
+kmx_status kmx_pileup_sites(const kmx_index* index, const kmx_pileup* pileup, const kmx_sites_options* options, void* stream,
+                            kmx_sites** inout);
+kmx_status kmx_sites_counts(const kmx_sites* s, uint64_t* n_sites, uint64_t* n_covered);
+kmx_status kmx_sites_view(kmx_sites* s, const uint32_t** pos /* n_sites */, const uint8_t** ref, const uint8_t** alt, const uint32_t** depth,
+                          const uint32_t** count, const uint32_t** ref_count, const uint32_t** ctg /* or NULL */);
+kmx_status kmx_sites_view_device(const kmx_sites* s, const uint32_t** d_pos, const uint8_t** d_ref, const uint8_t** d_alt,
+                                 const uint32_t** d_depth, const uint32_t** d_count, const uint32_t** d_ref_count, const uint32_t** d_ctg);
+void kmx_sites_free(kmx_sites* s);
+
 /* The text, reconstructed on the device from the index (an extension, no reference interface): every offset 0 .. n-k of one
  * element's contiguous copy of the buckets names the first letter of its k-mer, the index's tail gives the last k-1 letters.
  * Works on built, loaded and replicated indexes (this replica).  The first call derives a copy packed at 2, 4 or 8 bits per

@@ -6,7 +6,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libkmx.so")
-SOURCES = ["kmx_kernels.hip", "kmx_capi.hip", "kmx_build_sort.hip", "kmx_approx.hip", "kmx_vote.hip", "kmx_align.hip", "kmx_script.hip", "kmx_strands.hip", "kmx_pairs.hip", "kmx_rescue.hip", "kmx_tags.hip", "kmx_contigs.hip", "kmx_secondary.hip", "kmx_clip.hip", "kmx_supplementary.hip", "kmx_realign.hip", "kmx_host.cpp"]
+SOURCES = ["kmx_kernels.hip", "kmx_capi.hip", "kmx_build_sort.hip", "kmx_approx.hip", "kmx_vote.hip", "kmx_align.hip", "kmx_script.hip", "kmx_strands.hip", "kmx_pairs.hip", "kmx_rescue.hip", "kmx_tags.hip", "kmx_contigs.hip", "kmx_secondary.hip", "kmx_clip.hip", "kmx_supplementary.hip", "kmx_realign.hip", "kmx_pileup.hip", "kmx_host.cpp"]
 HEADERS = ["kmx_types.h", "kmx_host.h", "kmx_kernels.h", "kmx_approx.h", "kmx_handle.h", "kmx_vote.h", "kmx_strands.h", "kmx_clips.h", "kmx_align_core.h", "kmx_script_core.h", "kmx_runs.h", "kmx_fold_core.h", os.path.join("..", "..", "include", "kmx.h")]
 
 

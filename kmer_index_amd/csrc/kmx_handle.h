@@ -1,7 +1,7 @@
 // What the host code around the kernels shares: the buffers a handle owns, the error macros, the refusals every entry point starts
 // with, and the steps of the lifecycle that every handle of the read-mapping chain follows (kmx_vote.hip, kmx_align.hip,
 // kmx_script.hip, kmx_strands.hip, kmx_pairs.hip, kmx_rescue.hip, kmx_tags.hip, kmx_contigs.hip, kmx_secondary.hip, kmx_clip.hip,
-// kmx_supplementary.hip, kmx_realign.hip).  The other private headers of the chain: kmx_vote.h (what a stage reads of
+// kmx_supplementary.hip, kmx_realign.hip, kmx_pileup.hip).  The other private headers of the chain: kmx_vote.h (what a stage reads of
 // the handle before it), kmx_strands.h and kmx_clips.h (the handle structs that two sources fill), kmx_align_core.h,
 // kmx_script_core.h, kmx_runs.h and kmx_fold_core.h (device code that several sources compile).
 // A chain handle has the members `device`, `release()` (its buffers go, on its device) and `clear()` (an empty result).

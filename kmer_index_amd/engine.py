@@ -35,6 +35,8 @@ LOCATE_MATES, NO_CONTIG = 1, 0xFFFFFFFF
 SECONDARY_MAX, SECONDARY_NO_DELTA = 32, 0xFFFFFFFF
 CLIP_LOW, CLIP_REALIGNED = 1, 2
 SUPPLEMENTARY_MAX = 8
+PILEUP_ADD, PILEUP_SKIP_LOW = 1, 2
+PILEUP_AUTO, PILEUP_ATOMIC, PILEUP_TILED = 0, 1, 2
 
 
 class KmxError(RuntimeError):
@@ -116,6 +118,15 @@ class RealignOptions(C.Structure):
 class SupplementaryOptions(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_supplementary", C.c_uint32), ("min_len", C.c_uint32), ("max_overlap", C.c_uint32),
                 ("min_score", C.c_int32), ("flags", C.c_uint32)]
+
+
+class PileupOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("lo", C.c_uint64), ("hi", C.c_uint64), ("min_score", C.c_int32),
+                ("min_mapq", C.c_uint32), ("mode", C.c_uint32), ("tile", C.c_uint32)]
+
+
+class SitesOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("frac_num", C.c_uint32), ("frac_den", C.c_uint32)]
 
 
 class KernelStat(C.Structure):
@@ -273,6 +284,18 @@ SIGNATURES = {
     "kmx_supplementaries_view": (st, [vp] + [P(vp)] * 13),
     "kmx_supplementaries_view_device": (st, [vp] + [P(vp)] * 13),
     "kmx_supplementaries_free": (None, [vp]),
+    # pileup and sites
+    "kmx_clips_pileup_device": (st, [vp, vp, vp, vp, vp, vp, u64, vp, P(PileupOptions), vp, P(vp)]),
+    "kmx_clips_rescues_pileup": (st, [vp, vp, vp, vp, vp, vp, P(PileupOptions), vp, P(vp)]),
+    "kmx_pileup_counts": (st, [vp, P(u64), P(u64), P(u32)] + [P(u64)] * 4),
+    "kmx_pileup_view": (st, [vp, P(vp)]),
+    "kmx_pileup_view_device": (st, [vp, P(vp)]),
+    "kmx_pileup_free": (None, [vp]),
+    "kmx_pileup_sites": (st, [vp, vp, P(SitesOptions), vp, P(vp)]),
+    "kmx_sites_counts": (st, [vp] + [P(u64)] * 2),
+    "kmx_sites_view": (st, [vp] + [P(vp)] * 7),
+    "kmx_sites_view_device": (st, [vp] + [P(vp)] * 7),
+    "kmx_sites_free": (None, [vp]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -707,6 +730,55 @@ class Scripts(_Handle):
             raise TypeError("Scripts.md: source is an Alignments, a Rescues or a Secondaries")
         return _made_from(_md_call(fn, index, (self, source), letters, stream, md), self)
 
+    def pileup(self, index, source, reads, lo=0, hi=None, min_score=-2**31, mapq=None, min_mapq=0, skip_low=False, add=False, mode=PILEUP_AUTO, tile=0,
+               stream=0, pileup=None):
+        """kmx_clips_pileup_device (source: the Alignments these scripts were made from) or kmx_clips_rescues_pileup (source: the
+        Rescues) with clips = NULL: the scripts' own runs counted per text position of [lo, hi) (hi=None: the text's end) into the
+        sigma + 3 planes of a Pileup.  reads: the StrandReads the scripts run over.  mapq (a Mapq or a device pointer) with min_mapq
+        filters by read; min_score and skip_low need clips (Clips.pileup).  add=True adds to `pileup`; mode (PILEUP_AUTO, _ATOMIC,
+        _TILED) and tile never change the result.  stream=0: the stream that filled this handle.  The call leaves its kernels in
+        flight; Pileup.counts / planes wait for them.  Returns a Pileup (`pileup` reuses one)."""
+        return _pileup_call("Scripts.pileup", index, self, None, source, reads, mapq, stream, pileup,
+                            _pileup_options(lo, hi, min_score, min_mapq, skip_low, add, mode, tile))
+
+    def pileup_device(self, index, alignments, d_ranks_ptr, d_roff_ptr, nr, lo=0, hi=None, min_score=-2**31, mapq=None, min_mapq=0, skip_low=False,
+                      add=False, mode=PILEUP_AUTO, tile=0, stream=0, pileup=None, clips=None):
+        """kmx_clips_pileup_device on reads that are on the device (d_ranks_ptr, d_roff_ptr, nr: those the scripts were made over, e.g.
+        the single-strand reads of map_reads) and a caller-owned hipStream_t; clips: the Clips of these scripts, or None."""
+        out = pileup or Pileup()
+        o = _pileup_options(lo, hi, min_score, min_mapq, skip_low, add, mode, tile)
+        _check(lib().kmx_clips_pileup_device(index._h, alignments._h, self._h, clips._h if clips is not None else None, d_ranks_ptr, d_roff_ptr, nr,
+                                             _mapq_ptr(mapq), C.byref(o), stream or None, C.byref(out._h)))
+        return _made_from(out, self)
+
+
+def _pileup_options(lo, hi, min_score, min_mapq, skip_low, add, mode, tile):
+    return PileupOptions(C.sizeof(PileupOptions), (PILEUP_ADD if add else 0) | (PILEUP_SKIP_LOW if skip_low else 0), int(lo), int(hi or 0),
+                         int(min_score), int(min_mapq), int(mode), int(tile))
+
+
+def _mapq_ptr(mapq):
+    """The device array of a Mapq, or a raw device pointer, or None."""
+    return mapq.device_ptrs()[0] if isinstance(mapq, Mapq) else (mapq or None)
+
+
+def _pileup_call(who, index, scripts, clips, source, reads, mapq, stream, pileup, options):
+    """kmx_clips_pileup_device (source: the Alignments the scripts were made from) or kmx_clips_rescues_pileup (source: the Rescues)
+    over the doubled batch `reads` (a StrandReads).  Returns the Pileup (`pileup` reuses one)."""
+    out = pileup or Pileup()
+    kind = type(source).__name__
+    ch = clips._h if clips is not None else None
+    if kind == "Alignments":
+        d_ranks2, d_roff2, nr2, _ = reads.device_ptrs()
+        _check(lib().kmx_clips_pileup_device(index._h, source._h, scripts._h, ch, d_ranks2, d_roff2, nr2, _mapq_ptr(mapq), C.byref(options),
+                                             stream or None, C.byref(out._h)))
+    elif kind == "Rescues":
+        _check(lib().kmx_clips_rescues_pileup(index._h, reads._h, source._h, scripts._h, ch, _mapq_ptr(mapq), C.byref(options), stream or None,
+                                              C.byref(out._h)))
+    else:
+        raise TypeError(f"{who}: source is an Alignments or a Rescues")
+    return _made_from(out, scripts, reads=reads)
+
 
 def _md_call(fn, index, handles, letters, stream, md):
     """One of the kmx_*_md functions, which differ in the handles they take behind the index.  Returns the Md (`md` reuses one)."""
@@ -756,6 +828,18 @@ class Clips(_Handle):
         if fn is None:
             raise TypeError("Clips.md: source is an Alignments or a Rescues")
         return _made_from(_md_call(fn, index, (scripts, self, source), letters, stream, md), self)
+
+    def pileup(self, index, scripts, source, reads, lo=0, hi=None, min_score=-2**31, mapq=None, min_mapq=0, skip_low=False, add=False,
+               mode=PILEUP_AUTO, tile=0, stream=0, pileup=None):
+        """Scripts.pileup over the runs of these clips (trimmed or realigned): the text interval of every entry is [start + tl,
+        end - tr), entries that score below min_score are filtered, and with skip_low those that carry CLIP_LOW.  scripts: the Scripts
+        these clips were made from; source: the Alignments or the Rescues behind them.  Returns a Pileup (`pileup` reuses one)."""
+        return _pileup_call("Clips.pileup", index, scripts, self, source, reads, mapq, stream, pileup,
+                            _pileup_options(lo, hi, min_score, min_mapq, skip_low, add, mode, tile))
+
+    def pileup_device(self, index, scripts, alignments, d_ranks_ptr, d_roff_ptr, nr, **kw):
+        """Scripts.pileup_device over the runs of these clips."""
+        return scripts.pileup_device(index, alignments, d_ranks_ptr, d_roff_ptr, nr, clips=self, **kw)
 
     def supplementaries(self, reads, loci, alignments, placements, scripts, max_supplementary=4, min_len=20, max_overlap=10, min_score=20,
                         stream=0, supplementaries=None):
@@ -820,6 +904,44 @@ class Mapq(_Handle):
     def host(self):
         """The one field itself, not a tuple of one."""
         return super().host()[0]
+
+
+class Pileup(_Handle):
+    """Owns a kmx_pileup handle (kmx_clips_pileup_device, kmx_clips_rescues_pileup): sigma + 3 planes of u32 counters over the text
+    region [lo, hi), channel-major: the letters by rank, OTHER, DEL, INS."""
+
+    _free = "kmx_pileup_free"
+    _counts_of = ("kmx_pileup_counts", ("lo", "hi", "n_channels", "n_added", "n_filtered", "n_mismatched", "n_cells"))
+    _view_of = ("pileup", (("counts", np.uint32, lambda c: c["n_channels"] * (c["hi"] - c["lo"])),))
+
+    def planes(self):
+        """The counters as a (n_channels, hi - lo) uint32 array (a copy); waits for the kernels of the last call."""
+        c = self.counts()
+        return self.host()[0].reshape(c["n_channels"], c["hi"] - c["lo"])
+
+    def sites(self, index, min_depth=1, min_alt=1, frac=(1, 5), stream=0, sites=None):
+        """kmx_pileup_sites: one record per position and channel other than the reference letter (a letter, DEL or INS; never OTHER)
+        whose count is at least min_alt and at least frac[0] / frac[1] of the depth, at positions of depth >= min_depth.  stream=0:
+        the stream of the last call into this handle.  Returns a Sites (`sites` reuses one)."""
+        out = sites or Sites()
+        o = SitesOptions(C.sizeof(SitesOptions), int(min_depth), int(min_alt), int(frac[0]), int(frac[1]))
+        _check(lib().kmx_pileup_sites(index._h, self._h, C.byref(o), stream or None, C.byref(out._h)))
+        return _made_from(out, self)
+
+
+class Sites(_Handle):
+    """Owns a kmx_sites handle (kmx_pileup_sites): the records (pos, ref, alt, depth, count, ref_count[, ctg]) ordered by (pos, alt)."""
+
+    _free = "kmx_sites_free"
+    _counts_of = ("kmx_sites_counts", ("n_sites", "n_covered"))
+    _view_of = ("sites", (("pos", np.uint32, "n_sites"), ("ref", np.uint8, "n_sites"), ("alt", np.uint8, "n_sites"), ("depth", np.uint32, "n_sites"),
+                          ("count", np.uint32, "n_sites"), ("ref_count", np.uint32, "n_sites"), ("ctg", np.uint32, "n_sites")))
+
+    def host(self):
+        """ctg is None when the index has no contig table."""
+        p = self._ptrs("kmx_sites_view", 7)
+        out = self._arrays(p)
+        return out[:6] + (out[6] if p[6] else None,)
 
 
 class StrandReads(_Handle):
@@ -1633,7 +1755,7 @@ class Index:
         return s
 
     def map_reads_strands(self, ranks, roff, w, complement, stride=1, band=0, min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False,
-                          tags=False, letters=None, secondaries=0, clip=None, supplementary=None, realign=None):
+                          tags=False, letters=None, secondaries=0, clip=None, supplementary=None, realign=None, pileup=None):
         """map_reads on both strands: kmx_reads_strands, kmx_search_windows_device, kmx_windows_vote, kmx_loci_align_device and
         kmx_alignments_fold_strands in a row, all on the stream of the StrandReads.  Returns (StrandReads, Loci, Alignments,
         Placements): the loci and alignments are those of the doubled batch (internal read 2i is read i, 2i + 1 its reverse
@@ -1648,13 +1770,18 @@ class Index:
         the very last element, the Supplementaries; its all_scripts / all_clips are those two handles and its close() closes them.
         realign (a dict that may hold scratch_bytes, {} for the default; needs scripts=True and clip): the Clips of the placements and
         the all-loci Clips behind supplementary come from kmx_scripts_realign_device under the `clip` scoring in the place of
-        kmx_scripts_clip; the secondaries are untouched.  With realign=None every returned tuple is what it was without the keyword."""
+        kmx_scripts_clip; the secondaries are untouched.  With realign=None every returned tuple is what it was without the keyword.
+        pileup (a dict that may hold into, lo, hi, min_score, min_mapq, skip_low, mode, tile; {} for the defaults; needs scripts=True,
+        and tags=True when min_mapq > 0) runs last of all: Clips.pileup on the placements' Clips when clip is given (trimmed or
+        realigned), else Scripts.pileup on the scripts, with the Mapq of the tags when min_mapq > 0, and appends the Pileup as the very
+        last element.  into: a Pileup the call adds to (add=True); it is the caller's, and stays open when a later step raises.  With
+        pileup=None every call and every returned tuple is what it was without the keyword."""
         return self._map_chain("map_reads_strands", ranks, roff, w, complement, None, None, stride, band, min_votes, max_occ, max_edits, max_span,
-                               scripts, tags, letters, secondaries, clip, supplementary, realign)
+                               scripts, tags, letters, secondaries, clip, supplementary, realign, pileup)
 
     def map_pairs(self, ranks, roff, w, complement, min_insert, max_insert, orientation=PAIR_FR, unpaired_penalty=None, stride=1, band=0,
                   min_votes=1, max_occ=0, max_edits=0, max_span=None, scripts=False, rescue=False, rescue_edits=None, rescue_discordant=False,
-                  tags=False, letters=None, secondaries=0, clip=None, supplementary=None, realign=None):
+                  tags=False, letters=None, secondaries=0, clip=None, supplementary=None, realign=None, pileup=None):
         """map_reads_strands for paired reads: the reads are interleaved mates (read 2p is mate 1 of pair p, read 2p + 1 its mate 2, so
         their number is even), and kmx_alignments_fold_pairs stands in the fold's place.  Returns (StrandReads, Loci, Alignments,
         Placements, Pairs); scripts=True appends kmx_placements_scripts (the CIGARs of the chosen loci).  rescue=True runs
@@ -1672,13 +1799,15 @@ class Index:
         supplementary (a dict of the arguments of Clips.supplementaries, {} for the defaults; needs scripts=True and clip) runs
         last, on the placements as the rescue left them (a rescued mate has no parts), and appends the Supplementaries behind the
         Clips, as in map_reads_strands.  realign: as in map_reads_strands; the clips of the rescued mates stay those of kmx_scripts_clip
-        (their scripts index the rescue's jobs, not alignments)."""
+        (their scripts index the rescue's jobs, not alignments).  pileup: as in map_reads_strands; after a rescue the rescued mates'
+        Clips (or Scripts) go into the same Pileup; a Scripts of the rescued mates that is made for this alone is closed by the chain."""
         return self._map_chain("map_pairs", ranks, roff, w, complement, (min_insert, max_insert, orientation, unpaired_penalty),
                                (max_edits if rescue_edits is None else rescue_edits, rescue_discordant) if rescue else None,
-                               stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags, letters, secondaries, clip, supplementary, realign)
+                               stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags, letters, secondaries, clip, supplementary, realign,
+                               pileup)
 
     def _map_chain(self, who, ranks, roff, w, complement, insert, rescue, stride, band, min_votes, max_occ, max_edits, max_span, scripts, tags,
-                   letters, secondaries, clip, supplementary=None, realign=None):
+                   letters, secondaries, clip, supplementary=None, realign=None, pileup=None):
         """What map_reads_strands (insert=None) and map_pairs (insert: min_insert, max_insert, orientation, unpaired_penalty; rescue:
         None or the rescue's edits and whether it takes DISCORDANT pairs) return: the front and the fold, then the stages that were
         asked for, every one on the stream of the StrandReads."""
@@ -1690,13 +1819,21 @@ class Index:
             raise ValueError(f"{who}: supplementary needs scripts=True and clip")
         if realign is not None and (not scripts or clip is None):
             raise ValueError(f"{who}: realign needs scripts=True and clip")
+        if pileup is not None:
+            unknown = set(pileup) - {"into", "lo", "hi", "min_score", "min_mapq", "skip_low", "mode", "tile"}
+            if unknown:
+                raise ValueError(f"{who}: pileup holds unknown keys {sorted(unknown)}")
+            if not scripts:
+                raise ValueError(f"{who}: pileup needs scripts=True")
+            if pileup.get("min_mapq", 0) > 0 and not tags:
+                raise ValueError(f"{who}: pileup with min_mapq > 0 needs tags=True")
         if insert is not None:
             roff = np.ascontiguousarray(roff, np.uint64)
             if (roff.size - 1) % 2:
                 raise ValueError(f"{who}: an odd number of reads; the reads are interleaved mates")
         if max_span is None:
             max_span = 0xFFFFFFFF
-        pairs = res = sc = cl = rsc = rcl = sam = sec = sup = None
+        pairs = res = sc = cl = rsc = rcl = sam = sec = sup = pu = None
         with contextlib.ExitStack() as opened:                         # closes what was made, the last first, when a later call raises
 
             def keep(h):
@@ -1746,9 +1883,31 @@ class Index:
                 acl = keep(clipped(asc, stream=stream))
                 sup = keep(acl.supplementaries(reads, loci, al, pl, asc, **supplementary, stream=stream))
                 sup.all_scripts, sup.all_clips, sup._owns = asc, acl, True
+            if pileup is not None:                                     # last of all: the per-read answers into a per-position one
+                opt = {k: v for k, v in pileup.items() if k != "into"}
+                into = pileup.get("into")
+                mapq = sam.mapq if opt.get("min_mapq", 0) > 0 else None
+                pu = into if into is not None else keep(Pileup())     # (an `into` handle is the caller's: not closed when a step raises)
+                if cl is not None:
+                    cl.pileup(self, sc, al, reads, mapq=mapq, add=into is not None, stream=stream, pileup=pu, **opt)
+                else:
+                    sc.pileup(self, al, reads, mapq=mapq, add=into is not None, stream=stream, pileup=pu, **opt)
+                if res is not None:
+                    own = rsc is None                                  # made for this alone: closed here
+                    rs = rsc if rsc is not None else res.scripts(self, reads)
+                    try:
+                        if rcl is not None:
+                            rcl.pileup(self, rs, res, reads, mapq=mapq, add=True, stream=stream, pileup=pu, **opt)
+                        else:
+                            rs.pileup(self, res, reads, mapq=mapq, add=True, stream=stream, pileup=pu, **opt)
+                    finally:
+                        if own:
+                            if pu._h:
+                                pu.counts()                            # (waits: the kernels that read rs have finished)
+                            rs.close()
             opened.pop_all()
         # the four of every chain, then in this order whatever was asked for: a stage that did not run leaves no gap
-        return tuple(x for x in (reads, loci, al, pl, pairs, sc, res, sam, sec, cl, rcl, sup) if x is not None)
+        return tuple(x for x in (reads, loci, al, pl, pairs, sc, res, sam, sec, cl, rcl, sup, pu) if x is not None)
 
     def debug_words(self):
         w = np.zeros(16, np.uint64)

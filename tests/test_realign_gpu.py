@@ -2,7 +2,9 @@
 always tests/realign_naive.py on the host views of the engine's own handles (the scripts, the alignments, the reads as the device
 holds them, the text); every array, its dtype and every counter must be identical, and the device views must equal the host views.
 tests/test_realign_cpu.py shows on the CPU alone what the planted reads must give.  No batch is larger than those of the chain tests
-this file imports from.  Untested: an index with several replicas, and the different-devices refusals."""
+this file imports from.  Gaps in the classes of more than one diagonal per lane, the tie rules on texts of low complexity, the
+scorings at the bounds of the header and seeded batches: tests/test_realign_bands_gpu.py.  Untested: an index with several replicas,
+and the different-devices refusals."""
 import ctypes as C
 
 import numpy as np

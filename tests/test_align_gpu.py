@@ -7,69 +7,18 @@ import pytest
 
 from kmer_index_amd import synth
 from tests.align_naive import MAX_READ, NO_BEST, NONE, SKIPPED, align
+from tests import chain_data
+from tests.chain_checks import dev_array
+from tests.chain_data import N_READS, READ_WORKLOADS, text_of
 from tests.helpers import pack
 
 pytestmark = pytest.mark.gpu
 
 NAMES = ("dist", "start", "end", "best", "aligned")
-# name: (sigma, k, text length, reads of the generator); the tests take the first N_READS of them
-WORKLOADS = {"dna4_k10": (4, 10, 50_000, 3000), "aa20_k5": (20, 5, 50_000, 3000)}
-N_READS = 600
+WORKLOADS = {name: READ_WORKLOADS[name] for name in ("dna4_k10", "aa20_k5")}      # (sigma, k, text length, reads of the generator)
+reads_of = functools.partial(chain_data.reads_of, n_reads=N_READS, meta="bad")      # the first N_READS, with (kind, s, m, plain, bad) per read
 VOTE = (8, 2, 0)                  # (band, min_votes, max_occ)
 MAX_SPAN = 64
-
-
-@functools.lru_cache(maxsize=None)
-def text_of(sigma, n):
-    t = synth.ranks(7 + sigma, n, sigma)
-    t.setflags(write=False)
-    return t
-
-
-@functools.lru_cache(maxsize=None)
-def reads_of(name):
-    """The first N_READS reads of the workload of that name in test_vote_gpu.py (restated, not imported) and, per read,
-    (kind, s, m, plain): plain = cut from the text at s and left as it was.  Read i has m = z % 301 letters and kind i % 4: 3 is
-    random letters, the others are cut from the text (at 0 when i % 40 == 0, flush with its end when i % 40 == 4, else anywhere);
-    kind 1 with m > 40 gets a substitution at letters 12, 37, 62, ...; kind 2 with m > 60 loses the letter at m / 3 and has the one
-    at 2m / 3 twice.  i % 40 == 8 / 12 with m >= 40: 20 random letters in front of text[:m - 20] / behind text[n - (m - 20):].
-    Every 50th read carries one letter >= sigma, at its first, last and middle letter in turn."""
-    sigma, _, n, n_reads = WORKLOADS[name]
-    text = text_of(sigma, n)
-    z = synth.u64_stream(4241 + sigma + n_reads, 2 * n_reads).astype(np.int64) & 0x7FFFFFFF
-    reads, meta = [], []
-    n_bad = 0
-    for i in range(N_READS):
-        m, kind = int(z[2 * i] % 301), i % 4
-        s, plain = -1, False
-        if kind == 3:
-            q = synth.ranks(900_001 + i, m, sigma)
-        elif i % 40 == 8 and m >= 40:
-            q = np.concatenate([synth.ranks(700_001 + i, 20, sigma), text[:m - 20]])
-        elif i % 40 == 12 and m >= 40:
-            q = np.concatenate([text[n - (m - 20):], synth.ranks(800_001 + i, 20, sigma)])
-        else:
-            s = 0 if i % 40 == 0 else n - m if i % 40 == 4 else int(z[2 * i + 1] % (n - m - 1 + 1))
-            if kind == 2 and m > 60:
-                q = text[s:s + m + 1].copy()
-                q = np.delete(q, m // 3)[:m]
-                q = np.insert(q, 2 * m // 3, q[2 * m // 3])[:m]
-            else:
-                q = text[s:s + m].copy()
-                if kind == 1 and m > 40:
-                    q[12::25] = (q[12::25] + 1) % sigma
-            plain = kind == 0
-        bad = i % 50 == 7 and m > 0
-        if bad:
-            q[(0, m - 1, m // 2)[n_bad % 3]] = (sigma, 255)[(n_bad // 3) % 2]
-            n_bad += 1
-            plain = False
-        reads.append(np.asarray(q, np.uint8))
-        meta.append((kind, s, m, plain, bad))
-    ranks, roff = pack(reads)
-    ranks.setflags(write=False)
-    roff.setflags(write=False)
-    return ranks, roff, meta
 
 
 class Work:
@@ -393,18 +342,6 @@ def test_one_handle_for_batches_of_different_sizes(work):
     al.close()
 
 
-def device_array(torch, ptr, n, dtype):
-    if n == 0:
-        return np.zeros(0, dtype)
-
-    class _Arr:
-        def __init__(self):
-            self.__cuda_array_interface__ = {"shape": (int(n) * np.dtype(dtype).itemsize,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
-    out = torch.as_tensor(_Arr(), device="cuda").clone()
-    torch.cuda.synchronize()
-    return out.cpu().numpy().view(dtype)
-
-
 def test_device_form_on_a_callers_stream_and_device_view(work):
     import torch
     idx = work.index("dna4_k10")
@@ -422,7 +359,7 @@ def test_device_form_on_a_callers_stream_and_device_view(work):
     c = al.counts()
     sizes = (c["n_loci"], c["n_loci"], c["n_loci"], c["nr"], c["nr"])
     for name, ptr, n, x in zip(NAMES, al.device_ptrs(), sizes, want):
-        assert np.array_equal(device_array(torch, ptr, n, x.dtype), x), name
+        assert np.array_equal(dev_array(ptr, n, x.dtype), x), name
     assert_same(al.host(), c, want, before[1].size)
     for g, x in zip(loci.host(), before):                                  # the call only reads the loci handle
         assert np.array_equal(g, x)

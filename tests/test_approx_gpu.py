@@ -9,8 +9,7 @@ import pytest
 
 from kmer_index_amd import synth
 from tests.approx_naive import compare_batch
-from tests.helpers import pack
-from tests.test_search_gpu import CASES
+from tests.helpers import CASES, pack
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

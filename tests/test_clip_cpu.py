@@ -14,7 +14,7 @@ from kmer_index_amd import synth
 from tests import clip_naive as cn
 from tests import md_naive as mn
 from tests import script_naive as sn
-from tests.test_tags_cpu import edited
+from tests.chain_data import edited
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LETTERS = "ACGT"

@@ -3,104 +3,18 @@ the chain calls.  The oracle is always tests/clip_naive.py on the host views of 
 every counter must be identical.  The planted reads say what the batch must hold.  Nothing is larger than the shapes of the other
 chain tests.  Untested: an index with several replicas, and the different-devices refusals."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
-from kmer_index_amd import synth
 from tests import clip_naive as cn
-from tests import md_naive as mn
-from tests import test_pairs_gpu as tp
-from tests import test_rescue_gpu as tr
-from tests import test_secondaries_gpu as tsec
-from tests import test_tags_gpu as tt
+from tests.chain_checks import check_clip_md, check_clips, close_all, entry_of, refused, same
+from tests.chain_data import (CHAIN as PAIR_CHAIN, CLIP_CHAIN as CHAIN, CLIP_PLANTED as PLANTED, CLIP_SIZES as SIZES, CLIPS, COMP4, INSERT, K,
+                              LETTERS4 as LETTERS, M, MD, PAIR_WORKLOADS, REPEAT_CHAIN, SCRIPTS, clip_planted_reads as planted_reads, clip_text as text,
+                              other, rc4, repeat_text, rescue_pairs_of, text_of)
 from tests.helpers import pack
-from tests.test_tags_cpu import edited
 
 pytestmark = pytest.mark.gpu
-
-CLIPS = ("score", "sl", "sr", "tl", "tr", "nm", "cflags", "cig_off", "cigar")
-SCRIPTS = ("read_sel_off", "sel", "cig_off", "cigar")
-LETTERS = "ACGT"
-COMP4 = np.asarray([3, 2, 1, 0], np.uint8)
-N, K, E, M = 20_000, 10, 24, 150
-CHAIN = dict(band=8, min_votes=2, max_edits=E, max_span=64)
-SIZES = (7000, 5000, 8000)                                     # the contigs of the junction test: junctions at 7000 and 12 000
-same, dev_array, close_all, rc4 = tp.same, tp.dev_array, tsec.close_all, tsec.rc4
-
-
-@functools.lru_cache(maxsize=None)
-def text():
-    t = synth.ranks(911, N, 4)
-    t.setflags(write=False)
-    return t
-
-
-def other(q):
-    """every letter replaced by another one"""
-    return (np.asarray(q, np.uint8) + 2) % 4
-
-
-# the planted reads by name, then fillers: 150 letters from random places with 0 .. 3 edits
-PLANTED = ("unedited", "three_subs", "tail", "tail_reverse", "over_end", "over_start", "outside")
-
-
-@functools.lru_cache(maxsize=None)
-def planted_reads():
-    t = text()
-    subs = t[2000:2000 + M].copy()
-    subs[[0, 2, 4]] = other(subs[[0, 2, 4]])
-    reads = [t[1000:1000 + M].copy(), subs, np.concatenate([t[3000:3138], other(t[3138:3150])]),
-             rc4(np.concatenate([t[4000:4138], other(t[4138:4150])])), np.concatenate([t[N - 140:], np.full(10, (int(t[N - 1]) + 2) % 4, np.uint8)]),
-             np.concatenate([other(t[N - 10:]), t[:140]]), np.full(M, 4, np.uint8)]
-    z = synth.u64_stream(912, 16 * 40).astype(np.int64) & 0x7FFFFFFF
-    for p in range(40):
-        zz = z[16 * p:16 * p + 16]
-        s = 5000 + int(zz[0] % 10_000)
-        q = edited(zz[2:], t[s:s + M], int(zz[1] % 4))
-        reads.append(rc4(q) if p % 2 else q)
-    return reads
-
-
-def check_clips(cl, sc, **opt):
-    """The clips handle against clip_naive on the host views of the scripts; the device views against the host views.  Returns the
-    oracle's arrays by name, with its strings and counters."""
-    _, sel, cig_off, cigar = sc.host()
-    want = cn.clip(cig_off, cigar, **dict(cn.DEFAULTS, **opt))
-    got = cl.host()
-    same(CLIPS, got, want[:9])
-    assert cl.counts() == dict(n_sel=sel.size, n_ops=want[8].size, n_clipped=want[9], n_low=want[10])
-    dv = cl.device_ptrs()
-    sizes = (sel.size,) * 7 + (sel.size + 1, want[8].size)
-    for name, p, n, g in zip(CLIPS, dv, sizes, got):
-        assert (p is None) == (n == 0), name
-        assert np.array_equal(dev_array(p, n, g.dtype), g), name
-    assert cl.strings() == cn.strings(want[7], want[8])
-    assert want[8].size <= cigar.size + 2 * sel.size           # the bound the output is allocated at
-    out = dict(zip(CLIPS, want[:9]))
-    out.update(strings=cl.strings(), n_clipped=want[9], n_low=want[10], sel=sel)
-    return out
-
-
-def check_clip_md(md, want, start, end, txt, bound=None):
-    """The md handle of clipped entries against clip_naive.md; returns the strings."""
-    w = cn.md(want["sel"], want["cig_off"], want["cigar"], want["tl"], want["tr"], start, end, txt, LETTERS, bound)
-    got = md.host()
-    same(tt.MD, got, w[:2])
-    assert md.counts() == dict(n_sel=want["sel"].size, n_bytes=w[1].size, n_mismatched=w[2])
-    d_off, d_md = md.device_ptrs()
-    same(tt.MD, (dev_array(d_off, want["sel"].size + 1, np.uint64), dev_array(d_md, w[1].size, np.uint8)), got)
-    return mn.strings(*w[:2])
-
-
-def entry_of(pl, sc, i):
-    """the entry of public read i among the scripts of the placements"""
-    strand = pl.host(best2=False)[1]
-    read_sel_off = sc.host()[0]
-    r = 2 * i + int(strand[i])
-    assert strand[i] != 255 and read_sel_off[r + 1] > read_sel_off[r], i
-    return int(read_sel_off[r])
 
 
 @pytest.fixture(scope="module")
@@ -260,13 +174,6 @@ def test_reads_of_nothing_but_insertions_stay_whole_and_low(engine, index):
 
 
 # ---- 3. every aligned locus, the refusals after looking, no entries, one handle through sizes --------------------------------------------
-def refused(engine, call, fn="kmx_scripts_clip"):
-    with pytest.raises(engine.KmxError) as e:
-        call()
-    assert e.value.status == 1 and fn + ": " in str(e.value)
-    return str(e.value)
-
-
 def test_all_scripts_the_m_refusal_no_entries_and_one_handle_through_sizes(engine, index):
     t = text()
     pool = [x for x in planted_reads() if x.max() < 4]
@@ -288,7 +195,7 @@ def test_all_scripts_the_m_refusal_no_entries_and_one_handle_through_sizes(engin
         # '=' and 'X' joined: refused after looking, and the handle then holds an empty result
         joined = al.scripts(index, loci, ranks, roff, m=True)
         held.append(joined)
-        assert "KMX_SCRIPT_M" in refused(engine, lambda: joined.clip(clips=cl))
+        assert "KMX_SCRIPT_M" in refused(engine, lambda: joined.clip(clips=cl), "kmx_scripts_clip")
         assert cl.counts() == dict(n_sel=0, n_ops=0, n_clipped=0, n_low=0) and cl.device_ptrs() == (None,) * 9
         h = cl.host()
         assert h[7].tolist() == [0] and all(x.size == 0 for x in h[:7] + h[8:]) and cl.strings() == []
@@ -321,14 +228,14 @@ def test_all_scripts_the_m_refusal_no_entries_and_one_handle_through_sizes(engin
 # ---- 4. the scripts of a rescue and of secondaries ------------------------------------------------------------------------------------------
 def test_clips_and_md_of_rescued_mates(engine):
     name = "dna4_k10"
-    sigma, k, n = tp.WORKLOADS[name]
-    txt = tp.text_of(sigma, n)
+    sigma, k, n = PAIR_WORKLOADS[name]
+    txt = text_of(sigma, n)
     idx = engine.Index(txt, sigma, [k], table=2)
     held = []
     try:
-        ranks, roff = tr.rescue_pairs_of(name)
+        ranks, roff = rescue_pairs_of(name)
         ranks, roff = ranks[:int(roff[80])], roff[:81]          # 40 pairs, 10 of them to rescue
-        held += list(idx.map_pairs(ranks, roff, k, COMP4, **tp.CHAIN, **tp.INSERT, rescue=True))
+        held += list(idx.map_pairs(ranks, roff, k, COMP4, **PAIR_CHAIN, **INSERT, rescue=True))
         reads, res = held[0], held[5]
         rsc = res.scripts(idx, reads)
         held.append(rsc)
@@ -354,13 +261,13 @@ def test_clips_and_md_of_rescued_mates(engine):
 
 
 def test_clips_of_secondaries_and_their_xa(engine):
-    txt, _ = tsec.repeat_text()
+    txt, _ = repeat_text()
     idx = engine.Index(txt, 4, [10], table=2)
     held = []
     try:
         unit3 = np.concatenate([txt[2000:2150].copy()])
         reads = [np.concatenate([other(unit3[:4]), unit3[4:100]]), txt[300:380].copy()]
-        out = idx.map_reads_strands(*pack(reads), 10, COMP4, **tsec.REPEAT_CHAIN, secondaries=4)
+        out = idx.map_reads_strands(*pack(reads), 10, COMP4, **REPEAT_CHAIN, secondaries=4)
         held += list(out)
         reads_h, loci, al, pl, sec = out
         ssc = sec.scripts(idx, reads_h)
@@ -405,7 +312,7 @@ def test_the_chain_keyword_appends_the_separate_calls(engine, index, mapped):
         check_clip_md(out[5].md, want, start, end, text())     # with tags the MD is the clipped one
         amd = apart.md(index, plain[4], plain[2], LETTERS)
         held.append(amd)
-        same(tt.MD, out[5].md.host(), amd.host())
+        same(MD, out[5].md.host(), amd.host())
         assert out[5].md.strings() != plain[5].md.strings()
         # SAM lines from the clipped fields: POS moves by tl, AS follows MD
         pl, sc, cl = out[3], out[4], out[-1]
@@ -417,12 +324,12 @@ def test_the_chain_keyword_appends_the_separate_calls(engine, index, mapped):
         assert f[3] == str(2000 + 5 + 1) and f[5] == "5S145=" and f[11:] == ["NM:i:0", "MD:Z:145", "AS:i:143"]
         # pairs with a rescue and tags: the clips of both scripts come last, and the MDs are the clipped ones
         name = "dna4_k10"
-        sigma, k, n = tp.WORKLOADS[name]
-        idx2 = engine.Index(tp.text_of(sigma, n), sigma, [k], table=2)
+        sigma, k, n = PAIR_WORKLOADS[name]
+        idx2 = engine.Index(text_of(sigma, n), sigma, [k], table=2)
         held.append(idx2)
-        ranks, roff = tr.rescue_pairs_of(name)
+        ranks, roff = rescue_pairs_of(name)
         mates = (ranks[:int(roff[32])], roff[:33])
-        kw = dict(tp.CHAIN, **tp.INSERT)
+        kw = dict(PAIR_CHAIN, **INSERT)
         with pytest.raises(ValueError):
             idx2.map_pairs(*mates, k, COMP4, **kw, clip={})
         base = idx2.map_pairs(*mates, k, COMP4, **kw, scripts=True, rescue=True, tags=True, letters=LETTERS)
@@ -440,9 +347,9 @@ def test_the_chain_keyword_appends_the_separate_calls(engine, index, mapped):
         w2 = check_clips(rcl, tags.rescue_scripts, clip_penalty=0)
         assert w2["n_clipped"] == rcl.counts()["n_sel"] == got[6].counts()["n_taken"] == 4
         _, start, end = got[2].host()[:3]
-        check_clip_md(tags.md, w1, start, end, tp.text_of(sigma, n))
+        check_clip_md(tags.md, w1, start, end, text_of(sigma, n))
         jobs = got[6].host()
-        check_clip_md(tags.rescue_md, w2, jobs[5], jobs[6], tp.text_of(sigma, n))
+        check_clip_md(tags.rescue_md, w2, jobs[5], jobs[6], text_of(sigma, n))
         assert tags.rescue_md.strings() != base[-1].rescue_md.strings()
         fields = (got[3].clip_fields(cl, got[5]), got[6].clip_fields(rcl, tags.rescue_scripts))
         assert int(fields[1][3].sum()) == 4 and not (fields[0][3] & fields[1][3]).any()   # a rescued read has no script of its own

@@ -1,7 +1,7 @@
 """The contig table on the GPU (KMX_MAP_CONTIGS): kmx_index_set_contigs, the clamped windows of kmx_loci_align, the contig rule of
 kmx_alignments_fold_pairs, the clamped jobs of kmx_pairs_rescue, kmx_placements_locate and engine.sam_lines over contigs.  The oracle
 is always tests/contig_naive.py applied to the engine's own host views of the loci and alignments (the pattern of
-tests/test_pairs_gpu.py); every array and every counter must be bit-identical.  Texts have at most 50 000 letters and batches at most
+tests/chain_checks.check_pairs); every array and every counter must be bit-identical.  Texts have at most 50 000 letters and batches at most
 300 pairs.  Untested: an index with more than one replica (more than one device)."""
 import functools
 import re
@@ -16,18 +16,14 @@ from tests import fold_naive as fn
 from tests import md_naive as mn
 from tests import pair_naive as pn
 from tests import rescue_naive as rn
-from tests import test_pairs_gpu as tp
-from tests import test_rescue_gpu as tr
-from tests import test_tags_gpu as tt
+from tests.chain_checks import close_all, counters_of, dev_array, same, spell
+from tests.chain_data import (ALIGN as ALIGN5, CHAIN, COMPLEMENT, INSERT, JOBS, LETTERS, PAIRS, PAIR_SIZES, PAIR_WORKLOADS as WORKLOADS, PLACEMENTS, kill,
+                              pair_text, rc, rescue_pairs_of, table_of, text_of)
 from tests.helpers import pack
 
 pytestmark = pytest.mark.gpu
 
-PLACEMENTS, PAIRS, JOBS = pn.PLACEMENTS, pn.PAIRS, rn.JOBS
-ALIGN = tp.ALIGN + ("ctg",)
-WORKLOADS, COMPLEMENT, CHAIN, INSERT = tp.WORKLOADS, tp.COMPLEMENT, tp.CHAIN, tp.INSERT
-LETTERS = tt.LETTERS
-text_of, rc, same, dev_array, close_all, spell = tp.text_of, tp.rc, tp.same, tp.dev_array, tt.close_all, tt.spell
+ALIGN = ALIGN5 + ("ctg",)
 E = CHAIN["max_edits"]
 NO, NC = pn.NO_BEST, cn.NO_CONTIG
 PER = {4: 32, 20: 8}                                           # letters per word of the packed text
@@ -35,14 +31,6 @@ PER = {4: 32, 20: 8}                                           # letters per wor
 
 def comp_of(sigma):
     return np.asarray(COMPLEMENT[sigma], np.uint8)
-
-
-def table_of(sizes):
-    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
-
-
-def counters_of(pl, pr):
-    return tr.counters_of(pl, pr)
 
 
 def check_align(al, h_loci, text, ctg_off, ranks, roff, sigma, max_edits, max_span):
@@ -134,7 +122,7 @@ def everything(out):
 def test_one_contig_changes_nothing_and_removing_the_table_restores_the_handles(engine):
     name = "dna4_k10"
     sigma, k, n = WORKLOADS[name]
-    ranks, roff = tr.rescue_pairs_of(name)
+    ranks, roff = rescue_pairs_of(name)
     idx = engine.Index(text_of(sigma, n), sigma, [k], table=2)
     held = []
     try:
@@ -267,18 +255,6 @@ def test_windows_are_clamped_to_the_contig(engine, name):
 
 
 # ---- 3. pairs ---------------------------------------------------------------------------------------------------------------------------
-PAIR_SIZES = (1500,) * 12 + (300, 300) + (1500,) * 12          # contigs 12 and 13 hold the same 300 letters
-
-
-@functools.lru_cache(maxsize=None)
-def pair_text():
-    t = synth.ranks(91, sum(PAIR_SIZES), 4).copy()
-    off = table_of(PAIR_SIZES).astype(np.int64)
-    t[off[13]:off[14]] = t[off[12]:off[13]]
-    t.setflags(write=False)
-    return t
-
-
 def oriented(frag, m, orientation):
     """the mates of a fragment, m letters each, concordant under the orientation"""
     if orientation == pn.FR:
@@ -357,7 +333,7 @@ def rescue_reads():
     for c in range(len(RESCUE_SIZES) - 1):
         j = int(off[c + 1])
         for i, s in enumerate((j - 200, j + 50, j - 77)):
-            reads += [text[j - 400:j - 300].copy(), tr.kill(rc(text[s:s + 80]), 10)]
+            reads += [text[j - 400:j - 300].copy(), kill(rc(text[s:s + 80]), 10)]
             kind.append(i)
     return pack([np.asarray(q, np.uint8) for q in reads]), np.asarray(kind)
 
@@ -461,7 +437,7 @@ def test_locate_and_sam_lines_over_contigs(engine):
         frag = rc(text[s:s + f]) if p % 2 else text[s:s + f]
         m1, m2 = frag[:90].copy(), rc(frag[-90:])
         if p % 5 == 0:
-            m2 = tr.kill(m2[:80], 10)                          # a mate for the rescue
+            m2 = kill(m2[:80], 10)                          # a mate for the rescue
         if p % 7 == 0:
             m1 = synth.ranks(9000 + p, 90, sigma)
         if p % 11 == 0:
@@ -536,7 +512,7 @@ def test_random_tables_over_the_pairs_workload(engine, seed):
         mates = [frag[:int(rng.integers(80, 151))].copy(), rc(frag[f - int(rng.integers(80, 151)):], sigma)]
         lost = (p // 4) % 2
         if p % 4 == 0:
-            mates[lost] = tr.kill(mates[lost][:8 * k], k)
+            mates[lost] = kill(mates[lost][:8 * k], k)
         elif p % 4 == 1:
             mates[lost] = rng.integers(0, sigma, 90).astype(np.uint8)
         reads += mates

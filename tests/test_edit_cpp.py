@@ -5,29 +5,16 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "tests", "cpp", "test_edit_api.bin")
-
-
-def _compile():
-    from kmer_index_amd import build
-    build.build()
-    libdir = os.path.join(ROOT, "kmer_index_amd")
-    cmd = ["g++", "-std=c++20", "-O2", "-Wall", "-Wextra", "-Werror", f"-I{os.path.join(ROOT, 'include')}",
-           os.path.join(ROOT, "tests", "cpp", "test_edit_api.cpp"), "-o", BIN, f"-L{libdir}", "-lkmx", f"-Wl,-rpath,{libdir}",
-           "-Wl,-rpath,/opt/rocm/lib"]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    return BIN
+from tests.cpp_build import compile_cpp
 
 
 def test_edit_mirror_compiles():
-    assert os.path.exists(_compile())
+    assert os.path.exists(compile_cpp("test_edit_api"))
 
 
 @pytest.mark.gpu
 def test_edit_mirror_runs_on_gpu():
-    exe = _compile()
+    exe = compile_cpp("test_edit_api")
     res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stdout + res.stderr
     assert "edit api ok" in res.stdout

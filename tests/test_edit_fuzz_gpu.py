@@ -6,8 +6,7 @@ import pytest
 
 from kmer_index_amd import synth
 from tests.edit_naive import compare_batch
-from tests.helpers import pack
-from tests.test_edit_gpu import mutate
+from tests.helpers import mutate, pack
 
 pytestmark = pytest.mark.gpu
 

@@ -10,8 +10,7 @@ import pytest
 
 from kmer_index_amd import synth
 from tests.edit_naive import compare_batch, edit_naive
-from tests.helpers import pack
-from tests.test_search_gpu import CASES
+from tests.helpers import CASES, mutate, pack
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,25 +21,6 @@ def _edit_search(idx, qranks, qoff, e):
     r = idx.search_approx(qranks, qoff, e, edit=True)
     ho, pos, dist, st = r.host()
     return ho, pos, dist, r.lengths(), st, r
-
-
-def mutate(src, m, d, sigma, rng):
-    """A read of m letters: d edits of seeded kinds (substitution, deletion, insertion) at seeded columns below m of src,
-    then the first m letters, filled up with seeded letters where deletions left fewer."""
-    q = [int(x) for x in src]
-    for _ in range(d):
-        c = int(rng.integers(0, max(1, min(m, len(q)))))
-        kind = int(rng.integers(3))
-        if kind == 0 and q:
-            q[c] = (q[c] + 1 + int(rng.integers(sigma - 1))) % sigma
-        elif kind == 1 and q:
-            del q[c]
-        else:
-            q.insert(c, int(rng.integers(sigma)))
-    q = q[:m]
-    while len(q) < m:
-        q.append(int(rng.integers(sigma)))
-    return np.array(q, np.uint8)
 
 
 def _queries(text, sigma, ks, e, seed):

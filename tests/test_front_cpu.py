@@ -6,19 +6,13 @@ import pytest
 
 from kmer_index_amd import synth
 from tests import chain_naive as chn
+from tests import front_data as fd
 from tests import front_naive as frn
-from tests import test_front_gpu as tg
 from tests import vote_naive as vn
 from tests import windows_naive as wn
+from tests.chain_checks import same
+from tests.chain_data import COMPLEMENT, HITS, LOCI
 from tests.helpers import pack
-
-HITS = tg.HITS
-
-
-def same(names, got, want):
-    for name, g, w in zip(names, got, want):
-        assert g.dtype == w.dtype, name
-        assert np.array_equal(g, w), name
 
 
 # ---- 1. front_naive.hits against the definition -----------------------------------------------------------------------------------------
@@ -70,8 +64,8 @@ def test_hits_on_a_text_with_a_letter_outside_the_alphabet_and_on_no_reads():
 
 
 def test_window_offsets_equal_windows_naive_on_the_inputs_of_the_gpu_tests():
-    for name, batch, w in (("dna4_k6_s3", "a", 6), ("dna5_k5_s4", "a", 5), (tg.C_LAYOUT, ("c", 4097), 6)):
-        ranks, roff = tg.BATCHES[batch](name)
+    for name, batch, w in (("dna4_k6_s3", "a", 6), ("dna5_k5_s4", "a", 5), (fd.C_LAYOUT, ("c", 4097), 6)):
+        ranks, roff = fd.BATCHES[batch](name)
         for stride in (1, 3):
             win_off = frn.window_starts(roff, w, stride)[0]
             assert np.array_equal(win_off, wn.expand_loop(ranks, roff, w, stride)[2].astype(np.int64))
@@ -95,21 +89,21 @@ def check_tiled(base, tiled):
 
 @pytest.fixture(scope="module")
 def forty_pairs():
-    ranks, roff = tg.pairs_d()
+    ranks, roff = fd.pairs_d()
     return ranks[:int(roff[80])], roff[:81]
 
 
 def test_tile_of_the_chain_equals_the_chain_of_the_tiled_batch(forty_pairs):
-    text, comp = tg.text_of(tg.D_LAYOUT), tg.COMPLEMENT[4]
+    text, comp = fd.layout_text(fd.D_LAYOUT), COMPLEMENT[4]
     twice = chn.tile_reads(*forty_pairs, 2)
     assert twice[1].size == 161 and np.array_equal(twice[0][:twice[0].size // 2], twice[0][twice[0].size // 2:])
-    kw = dict(tg.D_CHAIN, secondaries=2, clip={})
-    base = chn.strands(text, 4, *forty_pairs, 6, comp, tg.LETTERS, **kw)
-    check_tiled(chn.tile(base, 2), chn.strands(text, 4, *twice, 6, comp, tg.LETTERS, **kw))
+    kw = dict(fd.D_CHAIN, secondaries=2, clip={})
+    base = chn.strands(text, 4, *forty_pairs, 6, comp, fd.LETTERS, **kw)
+    check_tiled(chn.tile(base, 2), chn.strands(text, 4, *twice, 6, comp, fd.LETTERS, **kw))
     assert base[3].totals["n_placed"] >= 50 and base[6].kind == "secondaries" and base[7].totals["n_sel"] >= 50
-    kw = dict(tg.D_INSERT, stride=tg.D_PAIR_STRIDE, **tg.D_CHAIN)
-    base = chn.pairs(text, 4, *forty_pairs, 6, comp, tg.LETTERS, **kw)
-    check_tiled(chn.tile(base, 2), chn.pairs(text, 4, *twice, 6, comp, tg.LETTERS, **kw))
+    kw = dict(fd.D_INSERT, stride=fd.D_PAIR_STRIDE, **fd.D_CHAIN)
+    base = chn.pairs(text, 4, *forty_pairs, 6, comp, fd.LETTERS, **kw)
+    check_tiled(chn.tile(base, 2), chn.pairs(text, 4, *twice, 6, comp, fd.LETTERS, **kw))
     # the tiling moved something in every kind of index: loci, internal reads and jobs
     assert base[6].totals["n_taken"] >= 2 and base[7].rescue_scripts.arrays[1].size >= 2 and base[5].arrays[1].size >= 50
     # and one copy is the base itself
@@ -117,21 +111,21 @@ def test_tile_of_the_chain_equals_the_chain_of_the_tiled_batch(forty_pairs):
 
 
 def test_the_front_of_the_chain_is_front_naive_and_vote_naive(forty_pairs):
-    text = tg.text_of(tg.D_LAYOUT)
-    reads, loci, al = chn._front(text, 4, *forty_pairs, 6, tg.COMPLEMENT[4], 1, 4, 10, 0, 6, 64)
+    text = fd.layout_text(fd.D_LAYOUT)
+    reads, loci, al = chn._front(text, 4, *forty_pairs, 6, COMPLEMENT[4], 1, 4, 10, 0, 6, 64)
     win_off, hit_off, positions, _ = frn.hits(text, 4, *reads.arrays, 6, 1)
-    same(tg.LOCI, loci.arrays, vn.vote(hit_off, positions, win_off, 1, 4, 10, 0)[:5])
+    same(LOCI, loci.arrays, vn.vote(hit_off, positions, win_off, 1, 4, 10, 0)[:5])
     assert loci.totals["n_loci"] >= 50 and al.totals["n_aligned"] >= 50      # 80 reads, about nine in ten cut from the text
 
 
 # ---- 3. the floors of the GPU tests' inputs -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("stride", [1, 3])
-@pytest.mark.parametrize("name", list(tg.LAYOUTS))
+@pytest.mark.parametrize("name", list(fd.LAYOUTS))
 def test_floors_of_the_layout_reads(name, stride):
-    tg.floors_a(name, stride)
-    sigma, k, n, shift, atab = tg.LAYOUTS[name]
+    fd.floors_a(name, stride)
+    sigma, k, n, shift, atab = fd.LAYOUTS[name]
     # the layout rules of the index, restated on the text's histogram (the GPU tests assert the layout the index reports)
-    code, _ = frn._codes(tg.text_of(name), sigma, k)
+    code, _ = frn._codes(fd.layout_text(name), sigma, k)
     npos, n_keys, present = code.size, sigma ** k, np.unique(code).size
     c = npos / n_keys
     assert n_keys <= 4 * npos                                  # the automatic table is the dense one
@@ -139,21 +133,21 @@ def test_floors_of_the_layout_reads(name, stride):
     assert shift == (0 if atab else 3 if c <= 3.5 else 4 if c <= 10.5 else 5 if c <= 24 else 0)
     assert not shift or (n_keys << shift) <= 8 * npos
     # every vote option set leaves loci to compare, and the max_occ of the third skips windows on the layouts with long buckets
-    for opts in tg.OPTION_SETS:
-        want = tg.naive_vote(name, "a", stride, opts)
+    for opts in fd.OPTION_SETS:
+        want = fd.naive_vote(name, "a", stride, opts)
         assert want[1].size >= 100
 
 
 @pytest.mark.parametrize("name", ["dna4_k6_s4", "dna4_k6_s5"])
 def test_floors_of_the_vote_shape_reads(name):
-    tg.floors_b(name)
+    fd.floors_b(name)
 
 
-@pytest.mark.parametrize("nr2", sorted(tg.C_DIRECT + tuple(2 * x for x in tg.C_PUBLIC)))
+@pytest.mark.parametrize("nr2", sorted(fd.C_DIRECT + tuple(2 * x for x in fd.C_PUBLIC)))
 def test_floors_of_the_scan_tile_batches(nr2):
-    tg.floors_c(nr2)
-    assert sorted(tg.C_DIRECT + tuple(2 * x for x in tg.C_PUBLIC)) == [4095, 4096, 4097, 4098, 8193]
+    fd.floors_c(nr2)
+    assert sorted(fd.C_DIRECT + tuple(2 * x for x in fd.C_PUBLIC)) == [4095, 4096, 4097, 4098, 8193]
 
 
 def test_floors_of_the_chain_batch():
-    tg.floors_d()
+    fd.floors_d()

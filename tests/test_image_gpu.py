@@ -8,7 +8,7 @@ import pytest
 
 from kmer_index_amd import synth
 from tests import image_writer as iw
-from tests.test_image_cpu import _mutants
+from tests.helpers import image_mutants
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +33,7 @@ def test_accepted_mutants_are_searchable(engine, tmp_path):
     qr, qoff = _queries(rng, text, 3000)
     p = tmp_path / "m.kmx"
     accepted = refused = 0
-    for raw in _mutants(rng, text, elems, 600):
+    for raw in image_mutants(rng, text, elems, 600):
         p.write_bytes(raw)
         try:
             idx = engine.Index.load(str(p))

@@ -6,6 +6,7 @@ import pytest
 
 from tests import fold_naive as fn
 from tests import pair_naive as pn
+from tests.chain_checks import same
 
 NAMES = pn.PLACEMENTS + pn.PAIRS
 NO = pn.NO_BEST
@@ -34,16 +35,14 @@ def case(per_strand):
     return off, dist, start, end, best_of(off, dist)
 
 
-def same(got, want):
-    for name, g, w in zip(NAMES, got, want):
-        assert g.dtype == w.dtype, name
-        assert np.array_equal(g, w), name
+def same_result(got, want):
+    same(NAMES, got, want)
     assert got[11] == want[11]
 
 
 def both(args, lo, hi, orientation=pn.FR, penalty=pn.NO_PENALTY):
     got = pn.fold_pairs(*args, lo, hi, orientation, penalty)
-    same(got, pn.fold_pairs_loop(*args, lo, hi, orientation, penalty))
+    same_result(got, pn.fold_pairs_loop(*args, lo, hi, orientation, penalty))
     r = dict(zip(NAMES, got))
     r.update(got[11])
     return r

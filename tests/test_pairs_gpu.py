@@ -1,8 +1,7 @@
 """Paired-end reads on the GPU: kmx_alignments_fold_pairs, Index.map_pairs and kmx_placements_scripts on its placements.  The oracle
-is tests/pair_naive.py applied to the host arrays of the engine's own loci and alignments (the pattern of check_fold in
-tests/test_strands_map_gpu.py); the texts and the repeat text of that file are restated here."""
+is tests/pair_naive.py applied to the host arrays of the engine's own loci and alignments (chain_checks.check_pairs); the texts, the
+pairs and their floors are those of tests/chain_data.py."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -11,118 +10,14 @@ from kmer_index_amd import synth
 from tests import fold_naive as fn
 from tests import pair_naive as pn
 from tests import script_naive as sn
+from tests.chain_checks import MappedPairs, check_pairs, dev_array, refused, same
+from tests.chain_data import (ALIGN, CHAIN, COMPLEMENT, INSERT, LOCI, N_PAIRS, PAIRS, PAIR_FLOORS as FLOORS, PAIR_WORKLOADS as WORKLOADS, PLACEMENTS,
+                              REPEAT_CHAIN, SCRIPTS, pairs_of, rc, repeat_pair, repeat_text, text_of)
 from tests.helpers import pack
 
 pytestmark = pytest.mark.gpu
 
-PLACEMENTS, PAIRS = pn.PLACEMENTS, pn.PAIRS
-LOCI = ("locus_off", "diag", "span", "votes", "skipped")
-ALIGN = ("dist", "start", "end", "best", "aligned")
 NO, NONE16 = pn.NO_BEST, pn.NO_SCORE
-# (sigma, k, text length)
-WORKLOADS = {"dna4_k10": (4, 10, 50_000), "aa20_k5": (20, 5, 50_000)}
-COMPLEMENT = {4: (3, 2, 1, 0), 20: tuple(range(20))}          # dna4, the plain reversal
-N_PAIRS = 300
-CHAIN = dict(band=8, min_votes=2, max_edits=8, max_span=64)
-INSERT = dict(min_insert=100, max_insert=600)
-# Floors on (n_concordant, n_discordant, n_single) of the workload below, from the naive chain on the CPU (a dictionary of the text's
-# k-mers, vote_naive.vote, align_naive.align on fold_naive.double_reads of the mates, pair_naive.fold_pairs; never from the engine).
-# Of the 300 pairs the 30 with p % 10 == 0 (mates 5000 apart) and the 30 with p % 10 == 3 (both mates on one strand) are discordant,
-# the 30 with p % 10 == 5 keep one mate, the 30 with p % 10 == 7 none, and the other 180 are concordant.
-FLOORS = {"dna4_k10": (180, 60, 30), "aa20_k5": (180, 60, 30)}
-
-
-@functools.lru_cache(maxsize=None)
-def text_of(sigma, n):
-    t = synth.ranks(7 + sigma, n, sigma)
-    t.setflags(write=False)
-    return t
-
-
-def rc(q, sigma=4):
-    return fn.revcomp(q, COMPLEMENT[sigma], sigma)
-
-
-@functools.lru_cache(maxsize=None)
-def pairs_of(name):
-    """N_PAIRS pairs as interleaved mates.  Pair p comes from a fragment of 200 .. 500 letters, taken from the reverse strand when p is
-    odd (then mate 2 is the upstream one); mate 1 is its first 80 .. 150 letters, mate 2 the reverse complement of its last 80 .. 150.
-    p % 4 == 0: mate 1 carries a substitution at letters 10, 40, 70, ... and mate 2 loses its middle letter.  p % 10 == 0: mate 2 is
-    cut 5000 letters downstream instead; == 3: mate 2 is not reverse-complemented (both on one strand); == 5: one mate is random
-    letters (mate 1 and mate 2 in turn); == 7: both are."""
-    sigma, _, n = WORKLOADS[name]
-    text = text_of(sigma, n)
-    z = synth.u64_stream(977 + sigma, 4 * N_PAIRS).astype(np.int64) & 0x7FFFFFFF
-    reads = []
-    for p in range(N_PAIRS):
-        f, m1, m2 = 200 + int(z[4 * p] % 301), 80 + int(z[4 * p + 1] % 71), 80 + int(z[4 * p + 2] % 71)
-        s = int(z[4 * p + 3] % (n - 6000))
-        frag = rc(text[s:s + f], sigma) if p % 2 else text[s:s + f]      # odd: the fragment as the reverse strand has it
-        mate1 = frag[:m1].copy()
-        mate2 = rc(text[s + 5000:s + 5000 + m2] if p % 10 == 0 else frag[f - m2:], sigma)
-        if p % 10 == 3:
-            mate2 = rc(mate2, sigma)
-        if p % 4 == 0:
-            mate1[10::30] = (mate1[10::30] + 1) % sigma
-            mate2 = np.delete(mate2, m2 // 2)
-        if p % 10 == 7 or p % 20 == 5:
-            mate1 = synth.ranks(600_001 + p, m1, sigma)
-        if p % 10 == 7 or p % 20 == 15:
-            mate2 = synth.ranks(610_001 + p, m2, sigma)
-        reads += [np.asarray(mate1, np.uint8), np.asarray(mate2, np.uint8)]
-    ranks, roff = pack(reads)
-    ranks.setflags(write=False)
-    roff.setflags(write=False)
-    return ranks, roff
-
-
-def dev_array(ptr, n, dtype):
-    """n elements at a device pointer as a numpy copy"""
-    import torch
-
-    if n == 0 or not ptr:
-        return np.zeros(0, dtype)
-
-    class _Arr:
-        def __init__(self):
-            self.__cuda_array_interface__ = {"shape": (int(n) * np.dtype(dtype).itemsize,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
-
-    out = torch.as_tensor(_Arr(), device="cuda").clone()
-    torch.cuda.synchronize()
-    return out.cpu().numpy().view(dtype)
-
-
-def same(names, got, want):
-    for name, g, w in zip(names, got, want):
-        assert g.dtype == w.dtype, name
-        assert np.array_equal(g, w), name
-
-
-def check_pairs(pl, pr, h_loci, h_al, min_insert, max_insert, orientation=pn.FR, unpaired_penalty=pn.NO_PENALTY):
-    """The placements and the pairs against the oracle on these host loci and alignments; returns the oracle's result by name."""
-    dist, start, end, best, _ = h_al
-    want = pn.fold_pairs(h_loci[0], dist, start, end, best, min_insert, max_insert, orientation, unpaired_penalty)
-    same(PLACEMENTS, pl.host(), want[:7])
-    same(PAIRS, pr.host(), want[7:11])
-    c, k = dict(pl.counts(), **{"n_pairs_ambiguous": pr.counts()["n_ambiguous"]}), pr.counts()
-    c.update({x: k[x] for x in ("np", "n_concordant", "n_discordant", "n_single", "n_unplaced")})
-    assert c == want[11]
-    out = dict(zip(PLACEMENTS + PAIRS, want))
-    out.update(want[11])
-    return out
-
-
-class MappedPairs:
-    """map_pairs of a batch with the host arrays of its loci and alignments"""
-
-    def __init__(self, idx, sigma, ranks, roff, k, **kw):
-        self.idx, self.sigma, self.ranks, self.roff = idx, sigma, ranks, roff
-        self.reads, self.loci, self.al, self.pl, self.pairs = idx.map_pairs(ranks, roff, k, np.asarray(COMPLEMENT[sigma], np.uint8), **kw)
-        self.h_loci, self.h_al = self.loci.host(), self.al.host()
-
-    def close(self):
-        for h in (self.pairs, self.pl, self.al, self.loci, self.reads):
-            h.close()
 
 
 class Work:
@@ -171,29 +66,11 @@ def test_pairs_of_the_workload_equal_the_oracle(work, name):
 
 
 # ---- 2. the case that needs the feature ------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def repeat_text():
-    """2000 random letters, a 50-letter unit 140 times, 2000 random letters, a reverse palindrome x + rc(x) of 40 letters"""
-    unit = synth.ranks(501, 50, 4)
-    x = synth.ranks(502, 20, 4)
-    t = np.concatenate([synth.ranks(503, 2000, 4), np.tile(unit, 140), synth.ranks(504, 2000, 4), x, rc(x)])
-    t.setflags(write=False)
-    return t, unit
-
-
 @pytest.fixture(scope="module")
 def repeat_index(engine):
     idx = engine.Index(repeat_text()[0], 4, [10], table=2)
     yield idx
     idx.close()
-
-
-REPEAT_CHAIN = dict(band=0, min_votes=2, max_edits=8)
-
-
-def repeat_pair():
-    text, _ = repeat_text()
-    return pack([text[8800:8900].copy(), rc(text[9200:9300])])
 
 
 def test_unique_mate_pulls_its_partner_out_of_the_repeat(repeat_index):
@@ -337,7 +214,7 @@ def check_scripts(mp, text, sigma):
     try:
         want = sn.scripts(text, ranks2, roff2, mp.h_loci[0], dist, start, end, best2, sigma, False, False)
         got = scr.host()
-        same(("read_sel_off", "sel", "cig_off", "cigar"), got, want[:4])
+        same(SCRIPTS, got, want[:4])
         c = scr.counts()
         assert (c["nr"], c["n_sel"], c["n_mismatched"]) == (2 * strand.size, int(placed.sum()), 0) and want[4] == 0
         assert np.array_equal(got[1], locus[placed])
@@ -369,13 +246,6 @@ def test_scripts_of_the_chosen_loci(work, repeat_index):
 
 
 # ---- 5. plumbing -----------------------------------------------------------------------------------------------------------------------
-def refused(engine, call):
-    with pytest.raises(engine.KmxError) as e:
-        call()
-    assert e.value.status == 1
-    return str(e.value)
-
-
 def test_refusals_and_the_state_of_both_handles(engine, repeat_index):
     text, _ = repeat_text()
     idx, L = repeat_index, engine.lib()

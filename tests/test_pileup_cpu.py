@@ -10,6 +10,7 @@ import numpy as np
 
 from kmer_index_amd import synth
 from tests import pileup_naive as pn
+from tests.chain_data import clip_text as text, other
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, SIGMA = 20_000, 4
@@ -17,14 +18,6 @@ OTHER, DEL, INS = SIGMA, SIGMA + 1, SIGMA + 2
 OPS = {"=": pn.OP_EQ, "X": pn.OP_X, "I": pn.OP_I, "D": pn.OP_D, "S": pn.OP_S, "M": 0, "N": 3}
 NEW = ("kmx_clips_pileup_device", "kmx_clips_rescues_pileup", "kmx_pileup_counts", "kmx_pileup_view", "kmx_pileup_view_device", "kmx_pileup_free",
        "kmx_pileup_sites", "kmx_sites_counts", "kmx_sites_view", "kmx_sites_view_device", "kmx_sites_free")
-
-
-def text():
-    return synth.ranks(911, N, 4)                              # the text of tests/test_clip_gpu.py
-
-
-def other(q):
-    return (np.asarray(q, np.uint8) + 2) % 4
 
 
 def parse(cigar):

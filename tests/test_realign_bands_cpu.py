@@ -1,5 +1,5 @@
 """tests/realign_band.py on the CPU alone: its best value against the contract (tests/realign_naive.py) on every input of
-tests/test_realign_bands_gpu.py and against the enumeration of paths of tests/test_realign_cpu.py, the replay of the oracle's own
+tests/test_realign_bands_gpu.py and against the enumeration of paths (chain_checks.best_path_value), the replay of the oracle's own
 runs, the conditions that the generated inputs are made for (asserted, not tuned: a generator that misses one is changed, never the
 condition), and the -inf and key arithmetic of kmx_realign.hip as plain integer inequalities over the constants of the sources."""
 import functools
@@ -12,7 +12,8 @@ import pytest
 from tests import align_naive as an
 from tests import realign_band as rb
 from tests import realign_naive as rn
-from tests.test_realign_cpu import SCORINGS as SMALL_SCORINGS, best_path_value
+from tests.chain_checks import best_path_value
+from tests.chain_data import SMALL_SCORINGS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WIDE = (rb.DEFAULT, rb.ZERO, rb.ALL_255)                       # the scorings of the entries of the widest class: a second each in the oracle

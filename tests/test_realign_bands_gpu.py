@@ -13,15 +13,13 @@ import pytest
 
 from tests import realign_band as rb
 from tests import realign_naive as rn
-from tests import test_clip_gpu as tclip
-from tests import test_pileup_gpu as tpile
-from tests import test_realign_gpu as tre
+from tests.chain_checks import check_clip_md, check_clips, check_pileup, check_realign, close_all, doubled, pileup_want, refused, same
+from tests.chain_data import CLIPS, COMP4, LETTERS4 as LETTERS
 from tests.helpers import pack
 
 pytestmark = pytest.mark.gpu
 
-CLIPS, LETTERS, COMP4, K = tclip.CLIPS, tclip.LETTERS, tclip.COMP4, rb.K
-same, close_all, check_realign, doubled = tclip.same, tclip.close_all, tre.check_realign, tre.doubled
+K = rb.K
 R, LOW = rn.REALIGNED, rn.LOW
 DEL, INS = 5, 6                                                # the planes of a pileup over four letters
 
@@ -67,7 +65,7 @@ def second_opinion(cl, sc, al, ranks, roff, txt, sigma, opt):
 
 
 def checked(cl, sc, al, ranks, roff, txt, sigma, want=None, **opt):
-    """check_realign of tests/test_realign_gpu.py against the oracle (`want`: its tuple, where it is known already), with the report
+    """chain_checks.check_realign against the oracle (`want`: its tuple, where it is known already), with the report
     of a mismatch, and the second opinion"""
     want = oracle(sc, al, ranks, roff, txt, sigma, **opt) if want is None else want
     try:
@@ -124,7 +122,7 @@ def test_gaps_in_every_class(engine, index, s):
         assert cl.counts() == per_entry.counts()
         trimmed = sc.clip(**s)
         held.append(trimmed)
-        tclip.check_clips(trimmed, sc, **s)
+        check_clips(trimmed, sc, **s)
         assert (out["score"] >= trimmed.host()[0]).all()       # (min_score = 0: the trimmed part is one of the paths of the band)
         if s != rb.DEFAULT:
             return
@@ -136,10 +134,10 @@ def test_gaps_in_every_class(engine, index, s):
         d_ranks, d_roff = torch.from_numpy(ranks).cuda(), torch.from_numpy(roff.view(np.int64)).cuda()
         torch.cuda.synchronize()
         n = txt.size
-        counts, ctr = tpile.want_of(sc, cl, al, ranks, roff, hi=n, n=n)
+        counts, ctr = pileup_want(sc, cl, al, ranks, roff, hi=n, n=n)
         pu = cl.pileup_device(index, sc, al, d_ranks.data_ptr(), d_roff.data_ptr(), roff.size - 1)
         held.append(pu)
-        tpile.check(pu, counts, ctr, hi=n)
+        check_pileup(pu, counts, ctr, hi=n)
         assert ctr["n_added"] == len(b.aligned) and ctr["n_mismatched"] == 0
         planes = pu.planes()
         deleted, inserted = b.at[9], b.at[10]                  # the reads of the widest class with one gap
@@ -150,7 +148,7 @@ def test_gaps_in_every_class(engine, index, s):
         md = cl.md(index, sc, al, LETTERS)
         held.append(md)
         _, start, end = al.host()[:3]
-        strings = tclip.check_clip_md(md, out, start, end, txt)
+        strings = check_clip_md(md, out, start, end, txt)
         assert md.counts()["n_mismatched"] == 0 and strings[9].count("^") == 1 and len(strings[9]) > 72
     finally:
         close_all(held)
@@ -237,7 +235,7 @@ def test_scoring_bounds(engine, index, bounds, s):
             assert not (got[1][1] or got[2][1] or got[1][3] or got[2][3])                     # the two reads without an edit
         trimmed = sc.clip(**s)
         held.append(trimmed)
-        cut = tclip.check_clips(trimmed, sc, **s)
+        cut = check_clips(trimmed, sc, **s)
         assert (int(cut["score"][1]), cut["strings"][1], cut["strings"][4]) == (1024 * a, "1024=", "40I")
         assert (out["score"] >= cut["score"]).all()
     finally:
@@ -257,7 +255,7 @@ def test_min_score_at_either_end_of_int32_and_the_refusals(engine, index, bounds
             assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), name
         n_sel = sc.counts()["n_sel"]
         assert cl.counts() == trimmed.counts() == dict(n_sel=n_sel, n_ops=sc.counts()["n_ops"], n_clipped=0, n_low=n_sel)
-        tclip.check_clips(trimmed, sc, min_score=rb.INT_MAX)
+        check_clips(trimmed, sc, min_score=rb.INT_MAX)
         assert cl.strings() == sc.strings() and (cl.host()[6] == LOW).all()
         # -2^31: every entry is realigned, under a scoring that makes the best path of an edited read worth less than nothing
         s = rb.SCORINGS[8]
@@ -265,7 +263,7 @@ def test_min_score_at_either_end_of_int32_and_the_refusals(engine, index, bounds
         for floor in (rb.INT_MIN, rb.INT_MAX):
             sc.realign(index, al, ranks, roff, **s, min_score=floor, clips=cl)
             sc.clip(**s, min_score=floor, clips=trimmed)
-            tclip.check_clips(trimmed, sc, **s, min_score=floor)
+            check_clips(trimmed, sc, **s, min_score=floor)
             out = checked(cl, sc, al, ranks, roff, txt, 4, **opts(s, min_score=floor))
             assert (out["cflags"] == LOW).tolist() == [floor == rb.INT_MAX] * 5
             # (40 insertions cost 255 + 40 * 255, less than the clip of a read that keeps nothing: even 40I is a path here)
@@ -281,7 +279,7 @@ def test_min_score_at_either_end_of_int32_and_the_refusals(engine, index, bounds
         for kw in (dict(match=0), dict(match=256), dict(gap_extend=256), dict(clip_penalty=65536)):
             for call, fn in ((lambda c: sc.realign(index, al, ranks, roff, **kw, clips=c), "kmx_scripts_realign"), (lambda c: sc.clip(**kw, clips=c), "kmx_scripts_clip")):
                 fresh = engine.Clips()
-                tre.refused(engine, lambda: call(fresh), fn)
+                refused(engine, lambda: call(fresh), fn)
                 assert not fresh._h, kw
     finally:
         close_all(held)
@@ -321,15 +319,15 @@ def test_seeded_batches(engine, fuzz, seed):
         _, start, end = al.host()[:3]
         md = cl.md(idx, sc, al, LETTERS)
         held.append(md)
-        tclip.check_clip_md(md, out, start, end, txt)
+        check_clip_md(md, out, start, end, txt)
         assert md.counts()["n_mismatched"] == 0
-        counts, ctr = tpile.want_of(sc, cl, al, ranks2, roff2, hi=n, n=n)
+        counts, ctr = pileup_want(sc, cl, al, ranks2, roff2, hi=n, n=n)
         assert cl.pileup(idx, sc, al, reads, pileup=pu) is pu
-        tpile.check(pu, counts, ctr, hi=n)
+        check_pileup(pu, counts, ctr, hi=n)
         assert ctr["n_mismatched"] == 0 and ctr["n_added"] == sc.counts()["n_sel"]
         # the trimmer under the same scoring and floor, through the same clips handle
         assert sc.clip(**s, min_score=b.min_score, stream=stream, clips=cl) is cl
-        cut = tclip.check_clips(cl, sc, **s, min_score=b.min_score)
+        cut = check_clips(cl, sc, **s, min_score=b.min_score)
         if b.min_score >= 0:
             assert (out["score"] >= cut["score"]).all()
     finally:

@@ -11,48 +11,11 @@ from tests import align_naive as an
 from tests import clip_naive as cn
 from tests import realign_naive as rn
 from tests import script_naive as sn
-from tests.test_tags_cpu import edited
+from tests.chain_checks import best_path_value
+from tests.chain_data import SMALL_SCORINGS as SCORINGS, clip_text as text, edited, other
 
 N, E = 20_000, 24
-SCORINGS = {
-    "default": dict(),
-    "free_clips": dict(clip_penalty=0),
-    "all_zero": dict(mismatch=0, gap_open=0, gap_extend=0, clip_penalty=0),
-    "zeros_p3": dict(mismatch=0, gap_open=0, gap_extend=0, clip_penalty=3),
-    "a2_b1_o0_x1_p1": dict(match=2, mismatch=1, gap_open=0, gap_extend=1, clip_penalty=1),
-}
-
-
-def text():
-    return synth.ranks(911, N, 4)                              # the text of tests/test_clip_gpu.py
-
-
-def other(q):
-    return (np.asarray(q, np.uint8) + 2) % 4
-
-
 # ---- 1. the best value against every path -----------------------------------------------------------------------------------------------
-def best_path_value(q, t, d, sigma, match, mismatch, gap_open, gap_extend, clip_penalty, **_):
-    """The greatest value of any path inside the band, by walking every path: a recursion over the paths, no table.  A path starts at
-    any cell that exists (a start at i > 0 pays p), takes '=' / 'X', I and D steps through cells that exist (a gap run of len letters
-    costs o + len x, so a step that goes on in the direction of the last one pays x alone) and ends anywhere (an end at i < m pays p)."""
-    m, L = len(q), len(t)
-    exists = lambda i, j: 0 <= i <= m and 0 <= j <= L and abs(j - i) <= d
-
-    def onwards(i, j, last):
-        best = -clip_penalty if i < m else 0                   # ending here
-        if exists(i + 1, j + 1):
-            s = match if q[i] == t[j] and q[i] < sigma else -mismatch
-            best = max(best, s + onwards(i + 1, j + 1, "M"))
-        if exists(i + 1, j):
-            best = max(best, -gap_extend - (0 if last == "I" else gap_open) + onwards(i + 1, j, "I"))
-        if exists(i, j + 1):
-            best = max(best, -gap_extend - (0 if last == "D" else gap_open) + onwards(i, j + 1, "D"))
-        return best
-
-    return max((0 if i == 0 else -clip_penalty) + onwards(i, j, None) for i in range(m + 1) for j in range(L + 1) if exists(i, j))
-
-
 @pytest.mark.parametrize("name", list(SCORINGS))
 def test_the_best_value_equals_an_enumeration_of_every_path_in_the_band(name):
     opt = dict(rn.DEFAULTS, **SCORINGS[name])

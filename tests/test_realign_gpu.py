@@ -2,7 +2,7 @@
 always tests/realign_naive.py on the host views of the engine's own handles (the scripts, the alignments, the reads as the device
 holds them, the text); every array, its dtype and every counter must be identical, and the device views must equal the host views.
 tests/test_realign_cpu.py shows on the CPU alone what the planted reads must give.  No batch is larger than those of the chain tests
-this file imports from.  Gaps in the classes of more than one diagonal per lane, the tie rules on texts of low complexity, the
+(tests/chain_data.py).  Gaps in the classes of more than one diagonal per lane, the tie rules on texts of low complexity, the
 scorings at the bounds of the header and seeded batches: tests/test_realign_bands_gpu.py.  Untested: an index with several replicas,
 and the different-devices refusals."""
 import ctypes as C
@@ -10,34 +10,19 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from kmer_index_amd import synth
 from tests import clip_naive as cn
 from tests import realign_naive as rn
-from tests import test_clip_gpu as tclip
-from tests import test_pairs_gpu as tp
-from tests import test_rescue_gpu as tr
-from tests import test_supplementary_gpu as tsup
+from tests.chain_checks import check_clip_md, check_clips, check_realign, check_supp, close_all, doubled, entry_of, refused, same
+from tests.chain_data import (CHAIN as PAIR_CHAIN, CLIP_CHAIN as CHAIN, CLIP_PLANTED, CLIPS, COMP4, INSERT, K, LETTERS4 as LETTERS, M, PAIR_WORKLOADS, SCRIPTS,
+                              boundary_reads, clip_planted_reads, clip_text as text, edited, other, realign_batch as batch, rescue_pairs_of, table_reads,
+                              text_of)
 from tests.helpers import pack
 
 pytestmark = pytest.mark.gpu
 
-CLIPS, SCRIPTS, LETTERS, COMP4, K, M, CHAIN = tclip.CLIPS, tclip.SCRIPTS, tclip.LETTERS, tclip.COMP4, tclip.K, tclip.M, tclip.CHAIN
-same, dev_array, close_all, rc4, text, other, entry_of = tclip.same, tclip.dev_array, tclip.close_all, tclip.rc4, tclip.text, tclip.other, tclip.entry_of
 ZERO = dict(mismatch=0, gap_open=0, gap_extend=0, clip_penalty=0)
 EMPTY = dict(n_sel=0, n_ops=0, n_clipped=0, n_low=0)
-
-
-def table_reads():
-    """the two reads of the issue's table and a chimera: a deletion of 12 letters, an insertion of 4, and 120 + 30 letters of two places"""
-    t = text()
-    return [np.concatenate([t[8000:8070], t[8082:8162]]), np.concatenate([t[6000:6070], other(t[6070:6074]), t[6070:6146]]),
-            np.concatenate([t[7000:7120], t[12_000:12_030]])]
-
-
-def doubled(reads):
-    """(ranks2, roff2) of a StrandReads as the device holds them: the reads that the chain aligned"""
-    d_ranks2, d_roff2, nr2, _ = reads.device_ptrs()
-    roff2 = dev_array(d_roff2, nr2 + 1, np.uint64)
-    return dev_array(d_ranks2, int(roff2[-1]), np.uint8), roff2
 
 
 def oracle(sc, al, ranks, roff, txt=None, **opt):
@@ -45,32 +30,11 @@ def oracle(sc, al, ranks, roff, txt=None, **opt):
     return rn.realign(*sc.host(), dist, start, end, ranks, roff, text() if txt is None else txt, 4, **dict(rn.DEFAULTS, **opt))
 
 
-def check_realign(cl, sc, want):
-    """The clips handle against the oracle's tuple `want`; the device views against the host views.  Returns the oracle's arrays by
-    name, with its strings and counters."""
-    n_sel = sc.counts()["n_sel"]
-    got = cl.host()
-    same(CLIPS, got, want[:9])
-    assert cl.counts() == dict(n_sel=n_sel, n_ops=want[8].size, n_clipped=want[9], n_low=want[10])
-    sizes = (n_sel,) * 7 + (n_sel + 1, want[8].size)
-    for name, p, n, g in zip(CLIPS, cl.device_ptrs(), sizes, got):
-        assert (p is None) == (n == 0), name
-        assert np.array_equal(dev_array(p, n, g.dtype), g), name
-    assert cl.strings() == rn.strings(want[7], want[8])
-    out = dict(zip(CLIPS, want[:9]))
-    out.update(strings=cl.strings(), n_clipped=want[9], n_low=want[10], sel=sc.host()[1])
-    return out
-
-
 @pytest.fixture(scope="module")
 def index(engine):
     idx = engine.Index(text(), 4, [K], table=2)
     yield idx
     idx.close()
-
-
-def batch():
-    return tclip.planted_reads() + table_reads()
 
 
 @pytest.fixture(scope="module")
@@ -86,7 +50,7 @@ def test_planted_reads_equal_the_oracle_at_four_settings_and_leave_the_scripts_a
     ranks2, roff2 = doubled(reads)
     d_ranks2, d_roff2, nr2, stream = reads.device_ptrs()
     before = (sc.host(), sc.device_ptrs(), sc.counts())
-    at = {name: i for i, name in enumerate(tclip.PLANTED + ("deletion", "insertion", "chimera"))}
+    at = {name: i for i, name in enumerate(CLIP_PLANTED + ("deletion", "insertion", "chimera"))}
     at = {name: (i if i < 7 else i + 40) for name, i in at.items()}                            # (the 40 fillers lie between)
     ent = {name: entry_of(pl, sc, i) for name, i in at.items() if name != "outside"}
     field = lambda out, name: (out["strings"][ent[name]], int(out["score"][ent[name]]), int(out["sl"][ent[name]]), int(out["sr"][ent[name]]),
@@ -120,7 +84,7 @@ def test_planted_reads_equal_the_oracle_at_four_settings_and_leave_the_scripts_a
         md = cl.md(index, sc, al, LETTERS)
         held.append(md)
         _, start, end = al.host()[:3]
-        strings = tclip.check_clip_md(md, five, start, end, text())
+        strings = check_clip_md(md, five, start, end, text())
         assert md.counts()["n_mismatched"] == 0 and strings[ent["three_subs"]] == "145" and "^" in strings[ent["deletion"]]
         tl, nm, score, has = pl.clip_fields(cl, sc)
         assert (tl[at["three_subs"]], nm[at["three_subs"]], score[at["three_subs"]]) == (2, 0, 140) and not has[at["outside"]]
@@ -154,25 +118,6 @@ def oracle_one(sc, al, ranks, roff, e):
 
 
 # ---- 2. every class of the band and every boundary of the 64-row store, one entry per chunk ---------------------------------------------
-def boundary_reads():
-    """(the reads that vote, the reads that are aligned at their loci): substitutions at every other letter of both ends, so that the
-    distance falls into each class of the band (< 32, 32 .. 63, 64 .. 127, >= 128), the read of 1024 letters of tests/test_clip_gpu.py
-    among them, and reads of 1, 63, 64, 65, 128 and 129 letters"""
-    t = text()
-    voters, aligned = [], []
-    for s, m, w in ((9000, 200, 16), (9500, 300, 50), (10_000, 400, 100), (10_500, 600, 170), (6000, 1024, 250), (11_200, 1, 0), (11_400, 63, 6),
-                    (11_600, 64, 6), (11_800, 65, 6), (12_000, 128, 6), (12_200, 129, 6)):
-        q = t[s:s + m].copy()
-        if w:
-            q[0:w:2] = other(q[0:w:2])
-            q[m - w::2] = other(q[m - w::2])
-        if m == 1024:
-            q[300:701:100] = other(q[300:701:100])
-        voters.append(t[s:s + M].copy())
-        aligned.append(q)
-    return voters, aligned
-
-
 def test_every_class_and_row_boundary_with_one_entry_per_chunk(engine, index):
     voters, aligned = boundary_reads()
     ranks, roff = pack(aligned)
@@ -206,7 +151,7 @@ def test_every_class_and_row_boundary_with_one_entry_per_chunk(engine, index):
 
 # ---- 3. reads of letters outside the alphabet --------------------------------------------------------------------------------------------
 def test_reads_of_nothing_but_insertions_stay_whole_and_low(engine, index):
-    ranks, roff = pack(tclip.planted_reads()[:6] + [text()[9000:9120].copy()])
+    ranks, roff = pack(clip_planted_reads()[:6] + [text()[9000:9120].copy()])
     blank = np.full(ranks.size, 255, np.uint8)
     held = [index.vote_windows(ranks, roff, K, 1, 8, 2, 0)]
     try:
@@ -254,20 +199,13 @@ def test_all_loci_of_thirty_reads_and_their_supplementaries(engine, index):
         assert (want["score"] >= trimmed.host()[0]).all() and (want["score"] > trimmed.host()[0]).any()
         sup = acl.supplementaries(reads, loci, al, pl, asc, stream=stream)
         held.append(sup)
-        got = tsup.check_supp(sup, reads, al, pl, asc, acl)
+        got = check_supp(sup, reads, al, pl, asc, acl)
         assert got["n_sup"] >= 1 and "100S50=" in sup.cigars()  # the second part of the last read
     finally:
         close_all(held)
 
 
 # ---- 5. refusals and lifecycle ---------------------------------------------------------------------------------------------------------------
-def refused(engine, call, fn="kmx_scripts_realign"):
-    with pytest.raises(engine.KmxError) as e:
-        call()
-    assert e.value.status == 1 and fn + ": " in str(e.value)
-    return str(e.value)
-
-
 def test_refusals_no_entries_and_one_handle_through_sizes_and_both_calls(engine, index):
     pool = [x for x in batch() if x.max() < 4]
     ranks, roff = pack(pool[:30])
@@ -282,13 +220,13 @@ def test_refusals_no_entries_and_one_handle_through_sizes_and_both_calls(engine,
         # '=' and 'X' joined: refused after looking, and the handle then holds an empty result
         joined = al.scripts(index, loci, ranks, roff, m=True)
         held.append(joined)
-        assert "KMX_SCRIPT_M" in refused(engine, lambda: joined.realign(index, al, ranks, roff, clips=cl))
+        assert "KMX_SCRIPT_M" in refused(engine, lambda: joined.realign(index, al, ranks, roff, clips=cl), "kmx_scripts_realign")
         assert cl.counts() == EMPTY and cl.device_ptrs() == (None,) * 9
         h = cl.host()
         assert h[7].tolist() == [0] and all(x.size == 0 for x in h[:7] + h[8:]) and cl.strings() == []
         # other reads than the scripts': refused after looking
         sc.realign(index, al, ranks, roff, clips=cl)
-        assert "nr differs" in refused(engine, lambda: sc.realign(index, al, ranks[:int(roff[29])], roff[:30], clips=cl))
+        assert "nr differs" in refused(engine, lambda: sc.realign(index, al, ranks[:int(roff[29])], roff[:30], clips=cl), "kmx_scripts_realign")
         assert cl.counts() == EMPTY
         # a refusal before looking leaves the result
         sc.realign(index, al, ranks, roff, clips=cl)
@@ -317,7 +255,7 @@ def test_refusals_no_entries_and_one_handle_through_sizes_and_both_calls(engine,
             sc2.realign(index, al2, rk, ro, clip_penalty=0, clips=cl)
             check_realign(cl, sc2, oracle(sc2, al2, rk, ro, clip_penalty=0))
             sc2.clip(clip_penalty=0, clips=cl)
-            tclip.check_clips(cl, sc2, clip_penalty=0)
+            check_clips(cl, sc2, clip_penalty=0)
             sc2.realign(index, al2, rk, ro, clips=cl)
             check_realign(cl, sc2, oracle(sc2, al2, rk, ro))
     finally:
@@ -326,7 +264,7 @@ def test_refusals_no_entries_and_one_handle_through_sizes_and_both_calls(engine,
 
 # ---- 6. the chain keyword -------------------------------------------------------------------------------------------------------------------
 def test_the_chain_keyword_puts_the_realignment_in_the_trimmer_s_place(engine, index):
-    picked = tclip.planted_reads()[:6] + tclip.planted_reads()[7:11] + table_reads()[:2]        # (sam_lines refuses a letter outside the alphabet)
+    picked = clip_planted_reads()[:6] + clip_planted_reads()[7:11] + table_reads()[:2]        # (sam_lines refuses a letter outside the alphabet)
     reads = pack(picked)
     held = []
     try:
@@ -337,7 +275,7 @@ def test_the_chain_keyword_puts_the_realignment_in_the_trimmer_s_place(engine, i
         plain = index.map_reads_strands(*reads, K, COMP4, **CHAIN, scripts=True, clip=dict(clip_penalty=2), realign=None)
         held += list(plain)
         assert [type(h).__name__ for h in plain] == ["StrandReads", "Loci", "Alignments", "Placements", "Scripts", "Clips"]
-        tclip.check_clips(plain[5], plain[4], clip_penalty=2)
+        check_clips(plain[5], plain[4], clip_penalty=2)
         out = index.map_reads_strands(*reads, K, COMP4, **CHAIN, scripts=True, tags=True, letters=LETTERS, clip=dict(clip_penalty=2),
                                       realign=dict(scratch_bytes=1 << 20))
         held += list(out)
@@ -353,7 +291,7 @@ def test_the_chain_keyword_puts_the_realignment_in_the_trimmer_s_place(engine, i
         same(CLIPS, cl.host(), apart.host())
         assert cl.counts() == apart.counts() and (want["cflags"] == engine.CLIP_REALIGNED).all()
         _, start, end = al.host()[:3]
-        tclip.check_clip_md(tags.md, want, start, end, text())  # with tags the MD is that of the realigned entries
+        check_clip_md(tags.md, want, start, end, text())  # with tags the MD is that of the realigned entries
         # SAM lines from the fields of the realigned clips: the CIGAR, POS moved by tl, AS behind MD
         fields = pl.clip_fields(cl, sc)
         lines = engine.sam_lines([f"q{i}" for i in range(len(picked))], *reads, LETTERS, COMP4, 4, "chr", pl.host(best2=False), pl.cigars(sc, cl),
@@ -366,13 +304,13 @@ def test_the_chain_keyword_puts_the_realignment_in_the_trimmer_s_place(engine, i
         assert f[5] != plain[5].strings()[entry_of(plain[3], plain[4], 10)] and int(want["score"][e]) > int(plain[5].host()[0][e])
         # pairs with a rescue and supplementaries: the placements' clips and the all-loci clips are realigned, the rescue's stay trimmed
         name = "dna4_k10"
-        sigma, k, n = tp.WORKLOADS[name]
-        txt = tp.text_of(sigma, n)
+        sigma, k, n = PAIR_WORKLOADS[name]
+        txt = text_of(sigma, n)
         idx2 = engine.Index(txt, sigma, [k], table=2)
         held.append(idx2)
-        ranks, roff = tr.rescue_pairs_of(name)
+        ranks, roff = rescue_pairs_of(name)
         mates = (ranks[:int(roff[32])], roff[:33])
-        kw = dict(tp.CHAIN, **tp.INSERT)
+        kw = dict(PAIR_CHAIN, **INSERT)
         with pytest.raises(ValueError):
             idx2.map_pairs(*mates, k, COMP4, **kw, scripts=True, realign={})
         base = idx2.map_pairs(*mates, k, COMP4, **kw, scripts=True, rescue=True, clip=dict(clip_penalty=0), supplementary={})
@@ -387,12 +325,12 @@ def test_the_chain_keyword_puts_the_realignment_in_the_trimmer_s_place(engine, i
         same(SCRIPTS, sc.host(), base[5].host())
         ranks2, roff2 = doubled(rd)
         check_realign(cl, sc, oracle(sc, al, ranks2, roff2, txt, clip_penalty=0))
-        tclip.check_clips(rcl, rcl.scripts, clip_penalty=0)
+        check_clips(rcl, rcl.scripts, clip_penalty=0)
         same(CLIPS, rcl.host(), base[8].host())
         assert rcl.counts()["n_sel"] == res.counts()["n_taken"] == 4
         check_realign(sup.all_clips, sup.all_scripts, oracle(sup.all_scripts, al, ranks2, roff2, txt, clip_penalty=0))
-        tsup.check_supp(sup, rd, al, pl, sup.all_scripts, sup.all_clips)
-        tclip.check_clips(base[9].all_clips, base[9].all_scripts, clip_penalty=0)
+        check_supp(sup, rd, al, pl, sup.all_scripts, sup.all_clips)
+        check_clips(base[9].all_clips, base[9].all_scripts, clip_penalty=0)
     finally:
         close_all(held)
 
@@ -402,13 +340,13 @@ def short_reads():
     """(64 reads of 40 .. 80 letters from random places with 0 .. 3 edits and one with a letter outside the alphabet, the first read
     without an edit)"""
     t = text()
-    z = tclip.synth.u64_stream(913, 16 * 64).astype(np.int64) & 0x7FFFFFFF
+    z = synth.u64_stream(913, 16 * 64).astype(np.int64) & 0x7FFFFFFF
     reads, edits = [], []
     for p in range(64):
         zz = z[16 * p:16 * p + 16]
         s = 1000 + int(zz[0] % 17_000)
         edits.append(int(zz[1] % 4))
-        reads.append(tclip.edited(zz[2:], t[s:s + 40 + p % 41], edits[-1]))
+        reads.append(edited(zz[2:], t[s:s + 40 + p % 41], edits[-1]))
     foreign = t[3000:3060].copy()
     foreign[30] = 4
     return reads + [foreign], edits.index(0)
@@ -440,7 +378,7 @@ def test_a_floor_nothing_meets_leaves_the_same_whole_entries_in_both_calls(engin
             assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), name
         assert again.counts() == trimmed.counts() == dict(n_sel=sel.size, n_ops=cigar.size, n_clipped=0, n_low=sel.size)
         # ... and what the oracle says (tests/realign_naive.py takes a whole entry from tests/clip_naive.py): the script, whole
-        tclip.check_clips(trimmed, sc, min_score=floor)
+        check_clips(trimmed, sc, min_score=floor)
         assert np.array_equal(got[7], cig_off) and np.array_equal(got[8], cigar) and (got[6] == engine.CLIP_LOW).all()
     finally:
         close_all(held)

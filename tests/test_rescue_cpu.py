@@ -7,16 +7,13 @@ import pytest
 from tests import fold_naive as fn
 from tests import pair_naive as pn
 from tests import rescue_naive as rn
+from tests.chain_data import rc
 from tests.helpers import pack
 
 SIGMA = 4
 COMP = (3, 2, 1, 0)
 NO = rn.NO_BEST
 FR, RF, FF = pn.FR, pn.RF, pn.FF
-
-
-def rc(q):
-    return fn.revcomp(q, COMP, SIGMA)
 
 
 def best_of(locus_off, dist):

@@ -1,7 +1,7 @@
 """Mate rescue on the GPU: kmx_pairs_rescue, kmx_rescues_scripts, Pairs.rescue and Index.map_pairs(rescue=True).  The oracle is always
 tests/rescue_naive.rescue applied to the engine's own host views from before the call (the loci, the alignments, the placements and
 the pairs); every array and every counter must be bit-identical.  The texts, the repeat text, the chain settings and the helpers are
-those of tests/test_pairs_gpu.py."""
+those of tests/chain_data.py and tests/chain_checks.py."""
 import ctypes as C
 import functools
 
@@ -14,63 +14,18 @@ from tests import fold_naive as fn
 from tests import pair_naive as pn
 from tests import rescue_naive as rn
 from tests import script_naive as sn
-from tests import test_pairs_gpu as tp
 from tests import vote_naive as vn
 from tests import windows_naive as wn
+from tests.chain_checks import MappedPairs, counters_of, dev_array, same
+from tests.chain_data import (ALIGN, CHAIN, COMPLEMENT, INSERT, JOBS, LOCI, N_PAIRS, PAIRS, PAIR_WORKLOADS as WORKLOADS, PLACEMENTS, REPEAT_CHAIN,
+                              RESCUE_FLOORS as FLOORS, SCRIPTS, copies_text, kill, rc, repeat_text, rescue_pairs_of, text_of)
 from tests.helpers import pack
 
 pytestmark = pytest.mark.gpu
 
-PLACEMENTS, PAIRS, JOBS = pn.PLACEMENTS, pn.PAIRS, rn.JOBS
-WORKLOADS, COMPLEMENT, CHAIN, INSERT = tp.WORKLOADS, tp.COMPLEMENT, tp.CHAIN, tp.INSERT
-text_of, rc, same, dev_array = tp.text_of, tp.rc, tp.same, tp.dev_array
 NO, NONE16 = pn.NO_BEST, pn.NO_SCORE
 ONLY = (pn.MATE1_ONLY, pn.MATE2_ONLY)
-N_PAIRS = 300
 E = CHAIN["max_edits"]
-# Pairs of the workload below that are MATE1_ONLY / MATE2_ONLY after the pair fold and CONCORDANT after the rescue, from the naive
-# chain on the CPU (naive_floor below: a dictionary of the text's k-mers, vote_naive.vote, align_naive.align, pair_naive.fold_pairs,
-# rescue_naive.rescue; never from the engine).  75 pairs are planted, and every one of them comes out ONLY and is rescued.
-FLOORS = {"dna4_k10": 75, "aa20_k5": 75}
-
-
-def kill(q, k):
-    """a substitution at every k-th letter from letter k - 2 on: no window of k letters survives, the first and the last letter do"""
-    q = np.array(q, np.uint8)
-    q[k - 2::k] = (q[k - 2::k] + 1) % (4 if k == 10 else 20)
-    return q
-
-
-@functools.lru_cache(maxsize=None)
-def rescue_pairs_of(name):
-    """N_PAIRS pairs as interleaved mates, cut as tests/test_pairs_gpu.pairs_of cuts them: from a fragment of 200 .. 500 letters, taken
-    from the reverse strand when (p // 8) is odd.  By p % 4, with `lost` = (p // 4) % 2 the mate it is done to, of 8 k letters:
-    0: the lost mate has a substitution at every k-th letter (8 edits, no intact window); 1: it is random letters; 2: it is cut 5000
-    letters downstream and broken as in 0; 3: an ordinary pair."""
-    sigma, k, n = WORKLOADS[name]
-    text = text_of(sigma, n)
-    z = synth.u64_stream(1977 + sigma, 4 * N_PAIRS).astype(np.int64) & 0x7FFFFFFF
-    reads = []
-    for p in range(N_PAIRS):
-        kind, lost, rev = p % 4, (p // 4) % 2, (p // 8) % 2
-        f, m = 200 + int(z[4 * p] % 301), [80 + int(z[4 * p + 1] % 71), 80 + int(z[4 * p + 2] % 71)]
-        s = int(z[4 * p + 3] % (n - 6000))
-        if kind != 3:
-            m[lost] = 8 * k
-        g = rc(text[s:s + f], sigma) if rev else text[s:s + f]
-        mates = [g[:m[0]].copy(), rc(g[f - m[1]:], sigma)]
-        if kind == 0:
-            mates[lost] = kill(mates[lost], k)
-        elif kind == 1:
-            mates[lost] = synth.ranks(700_001 + p, m[lost], sigma)
-        elif kind == 2:
-            far = text[s + 5000:s + 5000 + m[lost]]
-            mates[lost] = kill(far if (lost == 0) != bool(rev) else rc(far, sigma), k)
-        reads += [np.asarray(x, np.uint8) for x in mates]
-    ranks, roff = pack(reads)
-    ranks.setflags(write=False)
-    roff.setflags(write=False)
-    return ranks, roff
 
 
 def naive_floor(name):
@@ -94,7 +49,7 @@ def naive_floor(name):
     return int((np.isin(folded[7], ONLY) & (got[1][0] == pn.CONCORDANT)).sum())
 
 
-class Mapped(tp.MappedPairs):
+class Mapped(MappedPairs):
     """map_pairs of a batch, its host loci and alignments, the doubled reads and the text"""
 
     def __init__(self, idx, text, sigma, ranks, roff, k, **kw):
@@ -110,12 +65,6 @@ class Mapped(tp.MappedPairs):
 
     def refold(self, min_insert, max_insert, orientation=pn.FR, unpaired_penalty=None):
         self.al.fold_pairs(self.loci, min_insert, max_insert, orientation, unpaired_penalty, placements=self.pl, pairs=self.pairs)
-
-
-def counters_of(pl, pr):
-    c, k = dict(pl.counts(), n_pairs_ambiguous=pr.counts()["n_ambiguous"]), pr.counts()
-    c.update({x: k[x] for x in ("np", "n_concordant", "n_discordant", "n_single", "n_unplaced")})
-    return c
 
 
 def check_against(mp, res, want):
@@ -201,19 +150,6 @@ def test_lost_mates_of_the_workload_are_rescued(work, name):
 
 
 # ---- 2. discordant pairs ---------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def copies_text():
-    """The dna4 text with, for pair 0, an exact second copy of mate 2's source at 30000 and the true copy near the anchor broken; for
-    pair 1, region 15000 with mate 1's source and a broken copy of mate 2's, region 35000 the other way round."""
-    t = text_of(4, 50_000).copy()
-    t[30_000:30_080] = t[10_320:10_400]
-    t[10_320:10_400] = kill(t[10_320:10_400], 10)
-    t[35_000:35_080] = kill(t[15_000:15_080], 10)
-    t[15_320:15_400] = kill(t[35_320:35_400], 10)
-    t.setflags(write=False)
-    return t
-
-
 def test_discordant_pairs_are_rescued_only_when_asked(engine):
     t = copies_text()
     idx = engine.Index(t, 4, [10], table=2)
@@ -338,8 +274,8 @@ def test_mates_of_every_class_and_the_two_that_are_not_served(work):
 # ---- 6. the repeat ---------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def repeat_text_with_a_broken_copy():
-    """the repeat text of tests/test_pairs_gpu.py, 300 random letters, 80 letters of the repeat broken at every 10th, 300 random letters"""
-    t0, unit = tp.repeat_text()
+    """the repeat text of tests/chain_data.py, 300 random letters, 80 letters of the repeat broken at every 10th, 300 random letters"""
+    t0, unit = repeat_text()
     two = np.concatenate([unit, unit])
     t = np.concatenate([t0, synth.ranks(505, 300, 4), kill(two[:80], 10), synth.ranks(506, 300, 4)])
     t.setflags(write=False)
@@ -352,7 +288,7 @@ def test_a_rescued_read_with_many_loci_and_equal_copies_in_one_window(engine):
     # pair 0: mate 2 is 80 letters of the repeat, exact at 139 places far from its anchor and broken 200 letters behind it
     # pair 1: mate 2 is the same 80 letters broken: no locus, and every copy in the window of its anchor [1800, 1900) is as good
     reads = [t[n0 + 100:n0 + 200].copy(), rc(two[:80]), t[1800:1900].copy(), kill(rc(two[:80]), 10)]
-    mp = Mapped(idx, t, 4, *pack(reads), 10, **tp.REPEAT_CHAIN, **INSERT)
+    mp = Mapped(idx, t, 4, *pack(reads), 10, **REPEAT_CHAIN, **INSERT)
     res = None
     try:
         n_loci = np.diff(mp.h_loci[0].astype(np.int64))
@@ -427,7 +363,7 @@ def test_scripts_of_the_rescued_mates(work):
             held.append(scr)
             want = sn.scripts(mp.text, mp.ranks2, mp.roff2, job_off, dist, start, end, best, sigma, False, m)
             got = scr.host()
-            same(("read_sel_off", "sel", "cig_off", "cigar"), got, want[:4])
+            same(SCRIPTS, got, want[:4])
             c = scr.counts()
             assert (c["nr"], c["n_sel"], c["n_mismatched"]) == (best.size, int((status == 3).sum()), 0) and want[4] == 0
             assert np.array_equal(got[1], np.flatnonzero(status == 3))             # sel = the job
@@ -528,8 +464,8 @@ def test_views_agree_inputs_stay_and_map_pairs_is_the_calls_it_is_made_of(work):
         same(PAIRS, [dev_array(p, N_PAIRS, d) for p, d in zip(mp.pairs.device_ptrs(), (np.uint8, np.int32, np.uint16, np.uint16))], mp.pairs.host())
         # the loci, the alignments and the reads are untouched
         assert ptrs == (mp.loci.device_ptrs(), mp.al.device_ptrs(), mp.reads.device_ptrs())
-        same(tp.LOCI, mp.loci.host(), mp.h_loci)
-        same(tp.ALIGN, mp.al.host(), mp.h_al)
+        same(LOCI, mp.loci.host(), mp.h_loci)
+        same(ALIGN, mp.al.host(), mp.h_al)
         assert np.array_equal(dev_array(d_ranks2, mp.ranks2.size, np.uint8), mp.ranks2)
         # map_pairs(rescue=True) is the calls it is made of, and map_pairs() is what it was
         ranks, roff = rescue_pairs_of(name)

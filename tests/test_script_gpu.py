@@ -7,67 +7,22 @@ import pytest
 
 from kmer_index_amd import synth
 from tests import script_naive as sn
+from tests import chain_data
+from tests.chain_checks import dev_array
+from tests.chain_data import N_READS, READ_WORKLOADS, text_of
 from tests.helpers import pack
 
 pytestmark = pytest.mark.gpu
 
 NAMES = ("read_sel_off", "sel", "cig_off", "cigar")
-# the two workloads of tests/test_align_gpu.py (restated, not imported): (sigma, k, text length, reads of the generator)
-WORKLOADS = {"dna4_k10": (4, 10, 50_000, 3000), "aa20_k5": (20, 5, 50_000, 3000)}
-N_READS = 600
+WORKLOADS = {name: READ_WORKLOADS[name] for name in ("dna4_k10", "aa20_k5")}      # (sigma, k, text length, reads of the generator)
+reads_of = functools.partial(chain_data.reads_of, n_reads=N_READS)      # the first N_READS
 VOTE = (8, 2, 0)                  # (band, min_votes, max_occ)
 MAX_SPAN = 64
 # at E = 8, best only: entries (exact), then floors: scripts with I, with D, with both, with X, all '='
 FLOORS_E8 = {"dna4_k10": (369, 123, 117, 117, 93, 158), "aa20_k5": (374, 126, 123, 123, 89, 162)}
 # at E = 24, best only: entries (exact), scripts that begin with I, that end with I (the reads that overhang the text)
 FLOORS_E24 = {"dna4_k10": (440, 14, 17), "aa20_k5": (440, 13, 15)}
-
-
-@functools.lru_cache(maxsize=None)
-def text_of(sigma, n):
-    t = synth.ranks(7 + sigma, n, sigma)
-    t.setflags(write=False)
-    return t
-
-
-@functools.lru_cache(maxsize=None)
-def reads_of(name):
-    """The first N_READS reads of the workload of that name.  Read i has m = z % 301 letters and kind i % 4: 3 is random letters, the
-    others are cut from the text (at 0 when i % 40 == 0, flush with its end when i % 40 == 4, else anywhere); kind 1 with m > 40 gets
-    a substitution at letters 12, 37, 62, ...; kind 2 with m > 60 loses the letter at m / 3 and has the one at 2m / 3 twice.
-    i % 40 == 8 / 12 with m >= 40: 20 random letters in front of text[:m - 20] / behind text[n - (m - 20):].  Every 50th read
-    carries one letter >= sigma, at its first, last and middle letter in turn."""
-    sigma, _, n, n_reads = WORKLOADS[name]
-    text = text_of(sigma, n)
-    z = synth.u64_stream(4241 + sigma + n_reads, 2 * n_reads).astype(np.int64) & 0x7FFFFFFF
-    reads = []
-    n_bad = 0
-    for i in range(N_READS):
-        m, kind = int(z[2 * i] % 301), i % 4
-        if kind == 3:
-            q = synth.ranks(900_001 + i, m, sigma)
-        elif i % 40 == 8 and m >= 40:
-            q = np.concatenate([synth.ranks(700_001 + i, 20, sigma), text[:m - 20]])
-        elif i % 40 == 12 and m >= 40:
-            q = np.concatenate([text[n - (m - 20):], synth.ranks(800_001 + i, 20, sigma)])
-        else:
-            s = 0 if i % 40 == 0 else n - m if i % 40 == 4 else int(z[2 * i + 1] % (n - m - 1 + 1))
-            if kind == 2 and m > 60:
-                q = text[s:s + m + 1].copy()
-                q = np.delete(q, m // 3)[:m]
-                q = np.insert(q, 2 * m // 3, q[2 * m // 3])[:m]
-            else:
-                q = text[s:s + m].copy()
-                if kind == 1 and m > 40:
-                    q[12::25] = (q[12::25] + 1) % sigma
-        if i % 50 == 7 and m > 0:
-            q[(0, m - 1, m // 2)[n_bad % 3]] = (sigma, 255)[(n_bad // 3) % 2]
-            n_bad += 1
-        reads.append(np.asarray(q, np.uint8))
-    ranks, roff = pack(reads)
-    ranks.setflags(write=False)
-    roff.setflags(write=False)
-    return ranks, roff
 
 
 class Mapped:
@@ -500,18 +455,6 @@ def test_one_handle_for_batches_of_different_sizes(work):
     scr.close()
 
 
-def device_array(torch, ptr, n, dtype):
-    if n == 0:
-        return np.zeros(0, dtype)
-
-    class _Arr:
-        def __init__(self):
-            self.__cuda_array_interface__ = {"shape": (int(n) * np.dtype(dtype).itemsize,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
-    out = torch.as_tensor(_Arr(), device="cuda").clone()
-    torch.cuda.synchronize()
-    return out.cpu().numpy().view(dtype)
-
-
 def test_device_form_on_a_callers_stream_and_device_view(work):
     import torch
     idx = work.index("dna4_k10")
@@ -530,7 +473,7 @@ def test_device_form_on_a_callers_stream_and_device_view(work):
     c = scr.counts()
     sizes = (c["nr"] + 1, c["n_sel"], c["n_sel"] + 1, c["n_ops"])
     for name, ptr, n, x in zip(NAMES, scr.device_ptrs(), sizes, want):
-        assert np.array_equal(device_array(torch, ptr, n, x.dtype), x), name
+        assert np.array_equal(dev_array(ptr, n, x.dtype), x), name
     assert_same(scr, want, N_READS)
     # the call only reads the two handles
     assert (loci.device_ptrs(), al.device_ptrs()) == before[2:]

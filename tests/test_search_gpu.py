@@ -3,19 +3,9 @@ import numpy as np
 import pytest
 
 from kmer_index_amd import synth
-from tests.helpers import inside_envelope, make_queries, pack
+from tests.helpers import CASES, inside_envelope, make_queries, pack
 
 pytestmark = pytest.mark.gpu
-
-CASES = [
-    # (name, sigma, n, ks, lengths)  — lengths stay inside the reference's correct envelope
-    ("dna4_k5", 4, 100_000, [5], list(range(1, 16)) + [20]),
-    ("dna4_k10", 4, 400_000, [10], list(range(4, 31)) + [40]),
-    ("dna5_k10", 5, 400_000, [10], list(range(5, 31))),
-    ("aa20_k5", 20, 300_000, [5], list(range(1, 16))),
-    ("dna4_multi", 4, 400_000, [8, 10, 12], list(range(2, 30)) + [33, 35]),
-    ("dna15_k3_multi", 15, 200_000, [3, 4, 5], list(range(1, 10))),
-]
 
 
 def _compare(engine, orc, text, sigma, ks, qranks, qoff, table):

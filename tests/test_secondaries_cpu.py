@@ -10,6 +10,7 @@ import pytest
 
 from tests import fold_naive as fn
 from tests import secondary_naive as sn
+from tests.chain_checks import same_mixed
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NO = sn.NO_BEST
@@ -55,15 +56,6 @@ def random_case(seed):
     return case(per)
 
 
-def same(got, want):
-    for name, g, w in zip(sn.NAMES, got, want):
-        if isinstance(w, np.ndarray):
-            assert g.dtype == w.dtype, name
-            assert np.array_equal(g, w), name
-        else:
-            assert g == w, name
-
-
 def elsewhere(p, q):
     return p[0] != q[0] or max(p[1], q[1]) >= min(p[2], q[2])
 
@@ -74,7 +66,7 @@ def test_secondaries_equals_secondaries_loop_and_keeps_its_promises(seed):
     (off, dist, start, end), pl = random_case(seed)
     for N, delta in ((1, None), (3, None), (32, None), (4, 0), (32, 1), (2, sn.NO_DELTA)):
         got = sn.secondaries(off, dist, start, end, pl, N, delta)
-        same(got, sn.secondaries_loop(off, dist, start, end, pl, N, delta))
+        same_mixed(sn.NAMES, got, sn.secondaries_loop(off, dist, start, end, pl, N, delta))
         sec_off, locus, sd, ss, se, more, n_sec, n_multi, n_truncated = got
         nr = (off.size - 1) // 2
         assert sec_off.size == off.size and more.size == nr and n_sec == int(sec_off[-1]) == locus.size and n_truncated == int(more.sum())
@@ -108,7 +100,7 @@ def entries(per_strand, N, delta=None, placements=None):
     if placements is not None:
         pl = placements
     out = sn.secondaries(*arrays, pl, N, delta)
-    same(out, sn.secondaries_loop(*arrays, pl, N, delta))
+    same_mixed(sn.NAMES, out, sn.secondaries_loop(*arrays, pl, N, delta))
     return [int(x) for x in out[1]], [int(x) for x in out[5]], out
 
 

@@ -1,9 +1,8 @@
 """Secondary placements on the GPU: kmx_placements_secondaries, kmx_secondaries_scripts, kmx_secondaries_md, Secondaries.xa and the
 `secondaries=` keyword of the chain calls.  The oracle is always tests/secondary_naive.py on the host views of the engine's own loci,
 alignments and placements; the scripts and MD strings of the entries go against tests/script_naive.py and tests/md_naive.py.  No
-shape is larger than those of tests/test_strands_map_gpu.py and tests/test_pairs_gpu.py, whose workloads are reused."""
+shape is larger than those of tests/test_strands_map_gpu.py and tests/test_pairs_gpu.py, whose workloads (tests/chain_data.py) are reused."""
 import ctypes as C
-import functools
 import re
 
 import numpy as np
@@ -14,27 +13,18 @@ from tests import align_naive as an
 from tests import fold_naive as fn
 from tests import script_naive as scn
 from tests import secondary_naive as sn
-from tests import test_contigs_gpu as tc
-from tests import test_pairs_gpu as tp
-from tests import test_rescue_gpu as tr
-from tests import test_strands_map_gpu as ts
-from tests import test_tags_gpu as tt
 from tests import vote_naive as vn
 from tests import windows_naive as wn
+from tests.chain_checks import MappedStrands, StrandWork, check_md, check_rebuild, close_all, dev_array, read_of_entries, refused, same
+from tests.chain_data import (ALIGN, CHAIN, COMP4, COMPLEMENT, FOLD, INSERT, LOCI, N_READS, PAIR_SIZES, PAIR_WORKLOADS, PLANT_AT, REPEAT_CHAIN,
+                              RESCUE_FLOORS, SCRIPTS, STRAND_FLOORS, kill, pair_text, pairs_of, planted_text, rc4, repeat_text, rescue_pairs_of,
+                              table_of, text_of)
 from tests.helpers import pack
 
 pytestmark = pytest.mark.gpu
 
 SEC = ("sec_off", "locus", "dist", "start", "end", "more")
-SCRIPTS = ("read_sel_off", "sel", "cig_off", "cigar")
 NO = sn.NO_BEST
-COMP4 = np.asarray([3, 2, 1, 0], np.uint8)
-REPEAT_CHAIN = dict(band=0, min_votes=2, max_edits=8)
-same, dev_array = tp.same, tp.dev_array
-
-
-def rc4(q):
-    return fn.revcomp(q, COMP4, 4)
 
 
 def naive_chain(text, ranks, roff, sigma, complement, k, band, min_votes, max_edits, max_span=0xFFFFFFFF):
@@ -85,22 +75,7 @@ def entries_of(out, i):
     return [(0 if e < b else 1, int(out["start"][e]), int(out["dist"][e])) for e in range(a, c)]
 
 
-def close_all(held):
-    tt.close_all([h for h in held if h is not None])
-
-
 # ---- 1. the tandem repeat ---------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def repeat_text():
-    """2000 random letters, a 50-letter unit 140 times, 2000 random letters, a reverse palindrome x + rc(x) of 40 letters (the text of
-    tests/test_strands_map_gpu.repeat_text, restated)"""
-    unit = synth.ranks(501, 50, 4)
-    x = synth.ranks(502, 20, 4)
-    t = np.concatenate([synth.ranks(503, 2000, 4), np.tile(unit, 140), synth.ranks(504, 2000, 4), x, rc4(x)])
-    t.setflags(write=False)
-    return t, unit
-
-
 def repeat_reads():
     text, unit = repeat_text()
     two, three = np.concatenate([unit, unit]), np.concatenate([unit, unit, unit])
@@ -129,7 +104,7 @@ def repeat_index(engine):
 
 @pytest.fixture(scope="module")
 def repeat_mapped(repeat_index):
-    mp = ts.Mapped(repeat_index, 4, *pack(repeat_reads()), 10, **REPEAT_CHAIN)
+    mp = MappedStrands(repeat_index, 4, *pack(repeat_reads()), 10, **REPEAT_CHAIN)
     yield mp
     mp.close()
 
@@ -154,22 +129,6 @@ def test_tandem_repeat_palindrome_and_one_sided_reads(repeat_mapped):
 
 
 # ---- 2. planted copies ------------------------------------------------------------------------------------------------------------------
-PLANT_AT = (500, 1500, 2600, 3700, 4900)      # exact, exact, 1 substitution, 3 substitutions, exact but reverse-complemented
-
-
-@functools.lru_cache(maxsize=None)
-def planted_text():
-    t = synth.ranks(811, 6000, 4).copy()
-    seg = synth.ranks(812, 120, 4)
-    one, three = seg.copy(), seg.copy()
-    one[60] = (one[60] + 1) % 4
-    three[[25, 60, 95]] = (three[[25, 60, 95]] + 2) % 4
-    for at, copy in zip(PLANT_AT, (seg, seg, one, three, rc4(seg))):
-        t[at:at + 120] = copy
-    t.setflags(write=False)
-    return t, seg
-
-
 def planted_reads():
     text, seg = planted_text()
     return [seg.copy(), rc4(seg), text[PLANT_AT[1] - 40:PLANT_AT[1] + 60].copy()]
@@ -178,7 +137,7 @@ def planted_reads():
 @pytest.fixture(scope="module")
 def planted(engine):
     idx = engine.Index(planted_text()[0], 4, [10], table=2)
-    mp = ts.Mapped(idx, 4, *pack(planted_reads()), 10, **REPEAT_CHAIN)
+    mp = MappedStrands(idx, 4, *pack(planted_reads()), 10, **REPEAT_CHAIN)
     yield mp
     mp.close()
     idx.close()
@@ -216,7 +175,7 @@ MULTI_FLOORS = {("dna4_k10", 8): 2, ("aa20_k5", 8): 0, ("dna4_k10", 0): 2}
 
 @pytest.fixture(scope="module")
 def work(engine):
-    w = ts.Work(engine)
+    w = StrandWork(engine)
     yield w
     w.close()
 
@@ -233,14 +192,14 @@ def test_workloads_equal_the_oracle_and_leave_the_inputs_alone(work, name, band)
         has = np.diff(out["sec_off"].astype(np.int64)[::2]) > 0
         assert np.array_equal(has, (strand != 255) & (second != 255))             # an entry exactly where the fold saw a runner-up
         assert out["n_multi"] == int(has.sum()) >= MULTI_FLOORS[(name, band)]
-        aligned2 = np.add.reduceat(np.append(mp.h_al[4], 0).astype(np.int64), np.arange(0, 2 * ts.N_READS, 2))
+        aligned2 = np.add.reduceat(np.append(mp.h_al[4], 0).astype(np.int64), np.arange(0, 2 * N_READS, 2))
         shadows = (strand != 255) & (aligned2 >= 2) & (second == 255)             # two or more loci, one place
-        assert int(shadows.sum()) >= ts.FLOORS[(name, band)][3] and not has[shadows].any()
+        assert int(shadows.sum()) >= STRAND_FLOORS[(name, band)][3] and not has[shadows].any()
         # the inputs are what they were
         assert before == (mp.loci.device_ptrs(), mp.al.device_ptrs(), mp.pl.device_ptrs(), mp.loci.counts(), mp.al.counts(), mp.pl.counts())
-        same(ts.LOCI, mp.loci.host(), mp.h_loci)
-        same(ts.ALIGN, mp.al.host(), mp.h_al)
-        same(ts.FOLD, mp.pl.host(), pl_before)
+        same(LOCI, mp.loci.host(), mp.h_loci)
+        same(ALIGN, mp.al.host(), mp.h_al)
+        same(FOLD, mp.pl.host(), pl_before)
     finally:
         sec.close()
 
@@ -248,19 +207,19 @@ def test_workloads_equal_the_oracle_and_leave_the_inputs_alone(work, name, band)
 # ---- 4. paired reads --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,rescue", [("dna4_k10", False), ("aa20_k5", False), ("dna4_k10", True)])
 def test_paired_reads_before_and_after_a_rescue(engine, name, rescue):
-    sigma, k, n = tp.WORKLOADS[name]
-    ranks, roff = tr.rescue_pairs_of(name) if rescue else tp.pairs_of(name)
-    idx = engine.Index(tp.text_of(sigma, n), sigma, [k], table=2)
+    sigma, k, n = PAIR_WORKLOADS[name]
+    ranks, roff = rescue_pairs_of(name) if rescue else pairs_of(name)
+    idx = engine.Index(text_of(sigma, n), sigma, [k], table=2)
     held = []
     try:
-        held += list(idx.map_pairs(ranks, roff, k, np.asarray(tp.COMPLEMENT[sigma], np.uint8), **tp.CHAIN, **tp.INSERT, rescue=rescue))
+        held += list(idx.map_pairs(ranks, roff, k, np.asarray(COMPLEMENT[sigma], np.uint8), **CHAIN, **INSERT, rescue=rescue))
         loci, al, pl = held[1:4]
         sec = pl.secondaries(loci, al, 4)
         held.append(sec)
         out = check(sec, loci.host(), al.host(), pl, 4)        # the oracle runs on the final placements
         p_locus, p_strand, _, p_start, p_end = pl.host(best2=False)[:5]
         rescued = np.flatnonzero((p_strand != 255) & (p_locus == NO))
-        assert rescued.size == (tr.FLOORS[name] if rescue else 0) == (held[5].counts()["n_taken"] if rescue else 0)
+        assert rescued.size == (RESCUE_FLOORS[name] if rescue else 0) == (held[5].counts()["n_taken"] if rescue else 0)
         for i in rescued:                                      # never its own interval
             s = int(p_strand[i])
             for e in range(int(out["sec_off"][2 * i + s]), int(out["sec_off"][2 * i + s + 1])):
@@ -291,9 +250,9 @@ def test_a_repeat_mate_that_followed_its_partner_lists_the_leftmost_copy(repeat_
 
 # ---- 5. contigs -------------------------------------------------------------------------------------------------------------------------
 def test_entries_carry_their_contig_and_xa_is_contig_local(engine):
-    text, ctg_off = tc.pair_text(), tc.table_of(tc.PAIR_SIZES)
+    text, ctg_off = pair_text(), table_of(PAIR_SIZES)
     off = ctg_off.astype(np.int64)
-    names = [f"ctg{c}" for c in range(len(tc.PAIR_SIZES))]
+    names = [f"ctg{c}" for c in range(len(PAIR_SIZES))]
     assert len(names) <= 40 and np.array_equal(text[off[12]:off[13]], text[off[13]:off[14]])
     reads = [text[int(off[12]) + 5 + 30 * i:int(off[12]) + 95 + 30 * i].copy() for i in range(6)]           # from the contig that stands twice
     reads += [rc4(reads[1]), text[int(off[3]) + 100:int(off[3]) + 200].copy(), rc4(text[int(off[20]) + 7:int(off[20]) + 99])]
@@ -302,7 +261,7 @@ def test_entries_carry_their_contig_and_xa_is_contig_local(engine):
     held = []
     try:
         idx.set_contigs(ctg_off)
-        held += list(idx.map_reads_strands(ranks, roff, 10, COMP4, **tp.CHAIN))
+        held += list(idx.map_reads_strands(ranks, roff, 10, COMP4, **CHAIN))
         rd, loci, al, pl = held
         ctg = al.contigs_host()
         sec = pl.secondaries(loci, al, 4)
@@ -331,7 +290,7 @@ def test_entries_carry_their_contig_and_xa_is_contig_local(engine):
             sec.xa(sc)                                         # neither rname nor located
         # without a table the handle has no ctg, and located is refused
         idx.set_contigs(None)
-        held += list(idx.map_reads_strands(ranks, roff, 10, COMP4, **tp.CHAIN, secondaries=4))
+        held += list(idx.map_reads_strands(ranks, roff, 10, COMP4, **CHAIN, secondaries=4))
         sec2 = held[-1]
         check(sec2, held[-4].host(), held[-3].host(), held[-2], 4)
         with pytest.raises(ValueError):
@@ -346,7 +305,7 @@ def test_entries_carry_their_contig_and_xa_is_contig_local(engine):
 def check_scripts_and_md(engine, idx, mp, text, sigma, sec, letters):
     """the scripts and MD strings of every entry of sec against the naive modules; returns (Scripts, Md, strings) for the caller to close"""
     sec_off, locus, dist, start, end, _, _ = sec.host()
-    ranks2, roff2 = fn.double_reads(mp.ranks, mp.roff, ts.COMPLEMENT[sigma], sigma)
+    ranks2, roff2 = fn.double_reads(mp.ranks, mp.roff, COMPLEMENT[sigma], sigma)
     sc = sec.scripts(idx, mp.reads)
     md = None
     try:
@@ -356,16 +315,16 @@ def check_scripts_and_md(engine, idx, mp, text, sigma, sec, letters):
         c = sc.counts()
         assert (c["nr"], c["n_sel"], c["n_mismatched"]) == (sec_off.size - 1, locus.size, 0) and want[4] == 0
         assert np.array_equal(got[1], np.arange(locus.size, dtype=np.uint32)) and np.array_equal(got[0], sec_off)      # sel[e] == e
-        for e, r in enumerate(tt.read_of_entries(got[0])):     # every script replays: the read, or its reverse complement, against the text
+        for e, r in enumerate(read_of_entries(got[0])):     # every script replays: the read, or its reverse complement, against the text
             runs = got[3][int(got[2][e]):int(got[2][e + 1])]
             q = ranks2[int(roff2[r]):int(roff2[r + 1])]
             assert scn.replay(q, text[int(start[e]):int(end[e])], runs, sigma) == (int(dist[e]), True), e
             assert sum(int(v) >> 4 for v in runs if engine.CIGAR_OPS[int(v) & 15] in "XID") == int(dist[e]), e
         assert sec.cigars(sc) == scn.strings(want[2], want[3])
         md = sec.md(idx, sc, letters)
-        strings = tt.check_md(md, sc, start, end, text, sigma, bound=locus.size)
+        strings = check_md(md, sc, start, end, text, sigma, bound=locus.size)
         assert md.counts()["n_mismatched"] == 0 and len(strings) == locus.size
-        tt.check_rebuild(strings, sc, ranks2, roff2, start, end, text, sigma)
+        check_rebuild(strings, sc, ranks2, roff2, start, end, text, sigma)
         return sc, md, strings
     except Exception:
         close_all([md, sc])
@@ -385,7 +344,7 @@ def test_scripts_and_md_of_the_planted_copies_and_the_script_flags(engine, plant
         assert sorted(strings[:4], key=len)[:2] == ["120", "120"] and sum(len(re.findall("[ACGT]", s)) for s in strings[:4]) == 4
         # scratch_bytes changes nothing; KMX_SCRIPT_M joins '=' and 'X'; KMX_SCRIPT_ALL is refused and leaves the result in place
         sec_off, _, dist, start, end, _, _ = sec.host()
-        ranks2, roff2 = fn.double_reads(mp.ranks, mp.roff, ts.COMPLEMENT[4], 4)
+        ranks2, roff2 = fn.double_reads(mp.ranks, mp.roff, COMPLEMENT[4], 4)
         want = scn.scripts(text, ranks2, roff2, sec_off, dist, start, end, None, 4, True, False)
         same(SCRIPTS, sec.scripts(idx, mp.reads, scratch_bytes=1, scripts=sc).host(), want[:4])
         o = engine.ScriptOptions(C.sizeof(engine.ScriptOptions), engine.SCRIPT_ALL, 0)
@@ -418,7 +377,7 @@ def test_scripts_and_md_of_copies_with_a_deletion_and_an_insertion(engine):
     t[2300:2421] = extra                                       # the read has a letter less and a substitution
     t[3300:3419] = rc4(np.delete(seg, 90))
     idx = engine.Index(t, 4, [10], table=2)
-    mp = ts.Mapped(idx, 4, *pack([seg.copy(), rc4(seg)]), 10, **REPEAT_CHAIN)
+    mp = MappedStrands(idx, 4, *pack([seg.copy(), rc4(seg)]), 10, **REPEAT_CHAIN)
     held = []
     try:
         sec = mp.pl.secondaries(mp.loci, mp.al, 32)
@@ -479,7 +438,7 @@ def test_scripts_md_and_xa_lines_of_the_tandem_repeat_and_a_workload(engine, rep
         wmp = work.workload("dna4_k10")
         wsec = wmp.pl.secondaries(wmp.loci, wmp.al, 4)
         held.append(wsec)
-        held += list(check_scripts_and_md(engine, work.index("dna4_k10"), wmp, ts.text_of(4, 50_000), 4, wsec, "ACGT")[:2])
+        held += list(check_scripts_and_md(engine, work.index("dna4_k10"), wmp, text_of(4, 50_000), 4, wsec, "ACGT")[:2])
     finally:
         close_all(held)
 
@@ -525,7 +484,7 @@ def test_the_chain_keyword_appends_the_separate_call(engine, repeat_index):
         check(out[5], out[1].host(), out[2].host(), out[3], 3)
         # pairs, and pairs with a rescue: the secondaries come last, behind the Rescues, and are those of the final placements
         text, _ = repeat_text()
-        mates = pack([text[8800:8900].copy(), rc4(text[9200:9300]), text[300:400].copy(), tr.kill(rc4(text[600:680]), 10)])
+        mates = pack([text[8800:8900].copy(), rc4(text[9200:9300]), text[300:400].copy(), kill(rc4(text[600:680]), 10)])
         kw = dict(REPEAT_CHAIN, min_insert=100, max_insert=600)
         for rescue in (False, True):
             plain = repeat_index.map_pairs(*mates, 10, COMP4, **kw, rescue=rescue, secondaries=0)
@@ -548,13 +507,6 @@ def test_the_chain_keyword_appends_the_separate_call(engine, repeat_index):
         close_all(held)
 
 
-def refused(engine, call):
-    with pytest.raises(engine.KmxError) as e:
-        call()
-    assert e.value.status == 1 and "kmx_placements_secondaries" in str(e.value)
-    return str(e.value)
-
-
 def test_refusals_after_looking_leave_an_empty_result(engine, repeat_index):
     """Untested: handles on different devices (one device)."""
     text, _ = repeat_text()
@@ -563,7 +515,7 @@ def test_refusals_after_looking_leave_an_empty_result(engine, repeat_index):
     two = pack([text[100:170].copy(), text[2000:2100].copy()])
     two_b = pack([text[100:170].copy(), text[300:390].copy()])
     kw = dict(band=0, min_votes=8, max_edits=4)
-    mp = ts.Mapped(idx, 4, *two, 10, **kw)                     # 4 internal reads
+    mp = MappedStrands(idx, 4, *two, 10, **kw)                     # 4 internal reads
     held = []
     try:
         loci3, al3 = idx.map_reads(*pack([text[100:170].copy()] * 3), 10, **kw)
@@ -583,7 +535,8 @@ def test_refusals_after_looking_leave_an_empty_result(engine, repeat_index):
                            (lambda: pl2.secondaries(loci4, al4, 4, secondaries=sec), "the placements are not those of these reads")):
             pl4.secondaries(loci4, al4, 4, secondaries=sec)
             assert sec.counts()["nr"] == 2 and sec.device_ptrs()[0] is not None
-            assert word in refused(engine, call)
+            said = refused(engine, call)
+            assert "kmx_placements_secondaries" in said and word in said
             assert sec.counts() == {"nr": 0, "n_sec": 0, "n_multi": 0, "n_truncated": 0}
             h = sec.host()
             assert h[0].tolist() == [0] and all(x.size == 0 for x in h[1:5]) and h[5] is None and h[6].size == 0

@@ -5,10 +5,8 @@ import numpy as np
 import pytest
 
 from kmer_index_amd import synth
-from tests.helpers import pack
+from tests.helpers import mutate, pack, random_involution
 from tests.strand_naive import compare_batch, revcomp
-from tests.test_edit_gpu import mutate
-from tests.test_strands_gpu import random_involution
 
 pytestmark = pytest.mark.gpu
 

@@ -9,24 +9,13 @@ import numpy as np
 import pytest
 
 from kmer_index_amd import synth
-from tests.helpers import pack
+from tests.helpers import CASES, pack, random_involution
 from tests.strand_naive import compare_batch, revcomp, strand_naive
-from tests.test_search_gpu import CASES
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_PARITY = 60_000          # letters of text per parity case (the checker is O(n m) per query and strand)
 DNA4 = np.array([3, 2, 1, 0], np.uint8)
-
-
-def random_involution(sigma, seed):
-    """A seeded involution of [0, sigma) that is not the identity: a shuffled alphabet paired off two by two (an odd one
-    left maps to itself)."""
-    perm = np.random.default_rng(seed).permutation(sigma)
-    t = np.arange(sigma, dtype=np.uint8)
-    for a, b in zip(perm[0:sigma - 1:2], perm[1:sigma:2]):
-        t[a], t[b] = b, a
-    return t
 
 
 def table_for(engine, sigma, seed):

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from tests import fold_naive as fn
+from tests.chain_checks import same_mixed
 from tests.helpers import pack
 
 NAMES = ("locus", "strand", "dist", "start", "end", "second", "best2", "n_placed", "n_reverse", "n_ambiguous")
@@ -32,15 +33,6 @@ def case(per_strand):
     return off, dist, start, end, best_of(off, dist)
 
 
-def same(got, want):
-    for name, g, w in zip(NAMES, got, want):
-        if isinstance(w, np.ndarray):
-            assert g.dtype == w.dtype, name
-            assert np.array_equal(g, w), name
-        else:
-            assert g == w, name
-
-
 def random_case(seed):
     rng = np.random.default_rng(seed)
     per = []
@@ -58,7 +50,7 @@ def random_case(seed):
 @pytest.mark.parametrize("seed", range(40))
 def test_fold_equals_fold_loop(seed):
     args = random_case(seed)
-    same(fn.fold(*args), fn.fold_loop(*args))
+    same_mixed(NAMES, fn.fold(*args), fn.fold_loop(*args))
 
 
 @pytest.mark.parametrize("sigma,complement", [(4, [3, 2, 1, 0]), (5, [4, 2, 1, 3, 0]), (20, list(range(20)))])
@@ -83,7 +75,7 @@ def test_double_reads_of_rc_reads_gives_the_reads_back(sigma, complement):
 
 def both(args):
     got = fn.fold(*args)
-    same(got, fn.fold_loop(*args))
+    same_mixed(NAMES, got, fn.fold_loop(*args))
     return dict(zip(NAMES, got))
 
 

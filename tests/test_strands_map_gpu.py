@@ -11,149 +11,16 @@ import pytest
 from kmer_index_amd import synth
 from tests import fold_naive as fn
 from tests import script_naive as sn
+from tests import chain_data
+from tests.chain_checks import MappedStrands as Mapped, StrandWork as Work, check_fold, dev_array, refused, same
+from tests.chain_data import ALIGN, CHAIN, COMPLEMENT, FOLD, LOCI, N_READS, READ_WORKLOADS, STRAND_FLOORS as FLOORS, rc4, repeat_text, text_of
 from tests.helpers import pack
 
 pytestmark = pytest.mark.gpu
 
-FOLD = ("locus", "strand", "dist", "start", "end", "second", "best2")
-LOCI = ("locus_off", "diag", "span", "votes", "skipped")
-ALIGN = ("dist", "start", "end", "best", "aligned")
 NO = fn.NO_BEST
-# (sigma, k, text length, reads of the generator): the two workloads of tests/test_script_gpu.py, restated
-WORKLOADS = {"dna4_k10": (4, 10, 50_000, 3000), "aa20_k5": (20, 5, 50_000, 3000)}
-COMPLEMENT = {4: (3, 2, 1, 0), 5: (4, 2, 1, 3, 0), 20: tuple(range(20))}      # dna4, dna5 (N is its own complement), the plain reversal
-N_READS = 600
-CHAIN = dict(band=8, min_votes=2, max_edits=8, max_span=64)
-# Floors on what the fold is given, from tests/align_naive.py and tests/fold_naive.py on the CPU (a dictionary of the text's k-mers,
-# vote_naive.vote, align_naive.align, fold_naive.fold; never from the engine): (workload, band) -> (n_placed exactly, placed on the
-# forward strand at least, placed on the reverse strand at least, placed reads with two or more aligned loci and second == 255 at
-# least).  The even reads (kinds 0 and 2) are cut from the forward strand, the odd reads of kind 1 from the reverse one.  Kind 1
-# carries a substitution every 25 letters, so only its reads of up to about 212 letters stay within 8 edits, which is why the
-# reverse strand holds somewhat under a third of the placed reads and not half.  At band 8 a read's split diagonals join into one
-# locus, so the last figure is the business of the band 0 case.
-FLOORS = {
-    ("dna4_k10", 8): (370, 268, 102, 1),
-    ("aa20_k5", 8): (374, 268, 106, 0),
-    ("dna4_k10", 0): (370, 268, 102, 118),
-}
-
-
-@functools.lru_cache(maxsize=None)
-def text_of(sigma, n):
-    t = synth.ranks(7 + sigma, n, sigma)
-    t.setflags(write=False)
-    return t
-
-
-@functools.lru_cache(maxsize=None)
-def reads_of(name):
-    """N_READS reads built like those of tests/test_script_gpu.py, every odd-numbered one reverse-complemented afterwards.  Read i has
-    m = z % 301 letters and kind i % 4: 3 is random letters, the others are cut from the text (at 0 when i % 40 == 0, flush with its
-    end when i % 40 == 4, else anywhere); kind 1 with m > 40 gets a substitution at letters 12, 37, 62, ...; kind 2 with m > 60
-    loses the letter at m / 3 and has the one at 2m / 3 twice.  i % 40 == 8 / 12 with m >= 40: 20 random letters in front of
-    text[:m - 20] / behind text[n - (m - 20):].  Every 50th read carries one letter >= sigma, at its first, last and middle letter in
-    turn."""
-    sigma, _, n, n_reads = WORKLOADS[name]
-    text = text_of(sigma, n)
-    z = synth.u64_stream(4241 + sigma + n_reads, 2 * n_reads).astype(np.int64) & 0x7FFFFFFF
-    reads = []
-    n_bad = 0
-    for i in range(N_READS):
-        m, kind = int(z[2 * i] % 301), i % 4
-        if kind == 3:
-            q = synth.ranks(900_001 + i, m, sigma)
-        elif i % 40 == 8 and m >= 40:
-            q = np.concatenate([synth.ranks(700_001 + i, 20, sigma), text[:m - 20]])
-        elif i % 40 == 12 and m >= 40:
-            q = np.concatenate([text[n - (m - 20):], synth.ranks(800_001 + i, 20, sigma)])
-        else:
-            s = 0 if i % 40 == 0 else n - m if i % 40 == 4 else int(z[2 * i + 1] % (n - m - 1 + 1))
-            if kind == 2 and m > 60:
-                q = text[s:s + m + 1].copy()
-                q = np.delete(q, m // 3)[:m]
-                q = np.insert(q, 2 * m // 3, q[2 * m // 3])[:m]
-            else:
-                q = text[s:s + m].copy()
-                if kind == 1 and m > 40:
-                    q[12::25] = (q[12::25] + 1) % sigma
-        if i % 50 == 7 and m > 0:
-            q[(0, m - 1, m // 2)[n_bad % 3]] = (sigma, 255)[(n_bad // 3) % 2]
-            n_bad += 1
-        q = np.asarray(q, np.uint8)
-        reads.append(fn.revcomp(q, COMPLEMENT[sigma], sigma) if i % 2 else q)
-    ranks, roff = pack(reads)
-    ranks.setflags(write=False)
-    roff.setflags(write=False)
-    return ranks, roff
-
-
-def dev_array(ptr, n, dtype):
-    """n elements at a device pointer as a numpy copy"""
-    import torch
-
-    if n == 0 or not ptr:
-        return np.zeros(0, dtype)
-
-    class _Arr:
-        def __init__(self):
-            self.__cuda_array_interface__ = {"shape": (int(n) * np.dtype(dtype).itemsize,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
-
-    out = torch.as_tensor(_Arr(), device="cuda").clone()
-    torch.cuda.synchronize()
-    return out.cpu().numpy().view(dtype)
-
-
-def same(names, got, want):
-    for name, g, w in zip(names, got, want):
-        assert g.dtype == w.dtype, name
-        assert np.array_equal(g, w), name
-
-
-def check_fold(pl, h_loci, h_al):
-    """The placements against the oracle on these host loci and alignments; returns the oracle's result by name."""
-    dist, start, end, best, _ = h_al
-    want = fn.fold(h_loci[0], dist, start, end, best)
-    same(FOLD, pl.host(), want[:7])
-    c = pl.counts()
-    assert (c["nr"], c["n_placed"], c["n_reverse"], c["n_ambiguous"]) == ((h_loci[0].size - 1) // 2,) + want[7:]
-    return dict(zip(FOLD + ("n_placed", "n_reverse", "n_ambiguous"), want))
-
-
-class Mapped:
-    """map_reads_strands of a batch with the host arrays of its loci and alignments"""
-
-    def __init__(self, idx, sigma, ranks, roff, k, **kw):
-        self.idx, self.sigma, self.ranks, self.roff = idx, sigma, ranks, roff
-        self.reads, self.loci, self.al, self.pl = idx.map_reads_strands(ranks, roff, k, np.asarray(COMPLEMENT[sigma], np.uint8), **kw)
-        self.h_loci, self.h_al = self.loci.host(), self.al.host()
-
-    def close(self):
-        for h in (self.pl, self.al, self.loci, self.reads):
-            h.close()
-
-
-class Work:
-    def __init__(self, engine):
-        self.engine = engine
-        self.indexes, self.mapped = {}, {}
-
-    def index(self, name):
-        if name not in self.indexes:
-            sigma, k, n, _ = WORKLOADS[name]
-            self.indexes[name] = self.engine.Index(text_of(sigma, n), sigma, [k], table=2)
-        return self.indexes[name]
-
-    def workload(self, name, band=8):
-        if (name, band) not in self.mapped:
-            sigma, k, _, _ = WORKLOADS[name]
-            self.mapped[(name, band)] = Mapped(self.index(name), sigma, *reads_of(name), k, **dict(CHAIN, band=band))
-        return self.mapped[(name, band)]
-
-    def close(self):
-        for m in self.mapped.values():
-            m.close()
-        for idx in self.indexes.values():
-            idx.close()
+WORKLOADS = {name: READ_WORKLOADS[name] for name in ("dna4_k10", "aa20_k5")}      # (sigma, k, text length, reads of the generator)
+reads_of = functools.partial(chain_data.reads_of, n_reads=N_READS, reverse_odd=True)      # every odd-numbered read reverse-complemented
 
 
 @pytest.fixture(scope="module")
@@ -258,20 +125,6 @@ def test_fold_equals_the_oracle(work, name, band):
 
 
 # ---- 4. shapes where the fold can go wrong ---------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def repeat_text():
-    """2000 random letters, a 50-letter unit 140 times, 2000 random letters, a reverse palindrome x + rc(x) of 40 letters"""
-    unit = synth.ranks(501, 50, 4)
-    x = synth.ranks(502, 20, 4)
-    t = np.concatenate([synth.ranks(503, 2000, 4), np.tile(unit, 140), synth.ranks(504, 2000, 4), x, fn.revcomp(x, COMPLEMENT[4], 4)])
-    t.setflags(write=False)
-    return t, unit
-
-
-def rc4(q):
-    return fn.revcomp(q, COMPLEMENT[4], 4)
-
-
 @pytest.fixture(scope="module")
 def repeat_index(engine):
     idx = engine.Index(repeat_text()[0], 4, [10], table=2)
@@ -381,13 +234,6 @@ def test_scripts_of_the_winners(engine, work, name):
 
 
 # ---- 6. plumbing -----------------------------------------------------------------------------------------------------------------------
-def refused(engine, call):
-    with pytest.raises(engine.KmxError) as e:
-        call()
-    assert e.value.status == 1
-    return str(e.value)
-
-
 def test_bad_complement_tables_are_refused_and_leave_an_empty_batch(engine, small_indexes):
     import torch
 

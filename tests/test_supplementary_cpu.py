@@ -1,105 +1,15 @@
 """Supplementary alignments without a device: tests/supp_naive.py on hand-made arrays with the expected output written out, the
-planted reads of tests/test_supplementary_gpu.py through the CPU oracles alone (so that the GPU test's claims about its inputs are
+planted reads of tests/chain_data.py through the CPU oracles alone (so that the GPU test's claims about its inputs are
 shown before any device runs), the pure-Python SAM side of the engine on literal arrays, and the refusals of
 kmx_clips_supplementaries that look at no handle."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
-from kmer_index_amd import synth
-from tests import chain_naive as ch
-from tests import clip_naive as cn
-from tests import fold_naive as fn
-from tests import script_naive as sn
 from tests import supp_naive as sp
-from tests.helpers import pack
-from tests.test_tags_cpu import edited
-
-COMP4 = np.asarray([3, 2, 1, 0], np.uint8)
-LETTERS = "ACGT"
-# the shapes of tests/test_clip_gpu.py.  E: a planted part of L >= 40 letters leaves at most M - L <= 110 letters of the read to be
-# edits, so every such part is aligned at its locus whatever the rest of the read does there
-N, K, E, M = 20_000, 10, 110, 150
-CHAIN = dict(band=8, min_votes=2, max_edits=E, max_span=64)
-COPIES = 66                                                    # of either unit: 132 entries for the read made of the two
-
-
-def rc4(q):
-    return fn.revcomp(q, COMP4, 4)
-
-
-@functools.lru_cache(maxsize=None)
-def units():
-    return synth.ranks(932, 40, 4), synth.ranks(933, 40, 4)
-
-
-@functools.lru_cache(maxsize=None)
-def text():
-    """20 000 random letters; text[9000:9050] occurs again at 11 000; either unit of 40 letters occurs 66 times, 50 letters apart"""
-    t = synth.ranks(931, N, 4).copy()
-    t[11_000:11_050] = t[9000:9050]
-    for c in range(COPIES):
-        t[12_000 + 50 * c:12_040 + 50 * c] = units()[0]
-        t[16_000 + 50 * c:16_040 + 50 * c] = units()[1]
-    t.setflags(write=False)
-    return t
-
-
-# the planted reads by name, then 40 fillers: 150 letters from random places with 0 .. 3 edits, every other one reverse-complemented
-PLANTED = ("plain", "split", "split_rc", "split_rc_whole", "three", "dup", "adapter", "short", "tandem", "inverted", "many", "outside")
-
-
-@functools.lru_cache(maxsize=None)
-def planted_reads():
-    t, cat = text(), np.concatenate
-    split_rc = cat([t[2500:2600], rc4(t[5500:5550])])
-    reads = [t[1000:1150].copy(),                              # plain
-             cat([t[2000:2100], t[5000:5050]]),                # split: 100 + 50 on one strand
-             split_rc,                                         # the second part reverse-complemented
-             rc4(split_rc),                                    # the whole of it reverse-complemented: the primary lies on strand 1
-             cat([t[3000:3060], t[6000:6050], t[7500:7540]]),  # three parts
-             cat([t[3500:3600], t[9000:9050]]),                # the second part is the segment that occurs twice
-             cat([t[4000:4120], synth.ranks(934, 30, 4)]),     # an adapter tail
-             cat([t[4500:4635], t[8000:8015]]),                # a second part below min_len
-             cat([t[6500:6600], t[6530:6580]]),                # a tandem duplication on one strand
-             cat([t[7000:7100], rc4(t[7030:7080])]),           # the same with the second part inverted
-             cat(units()),                                     # 66 loci for either half
-             np.full(M, 4, np.uint8)]                          # no letter of the alphabet
-    z = synth.u64_stream(935, 16 * 40).astype(np.int64) & 0x7FFFFFFF
-    for p in range(40):
-        zz = z[16 * p:16 * p + 16]
-        s = 200 + int(zz[0] % 10_000)
-        q = edited(zz[2:], t[s:s + M], int(zz[1] % 4))
-        reads.append(rc4(q) if p % 2 else q)
-    return reads
-
-
-@functools.lru_cache(maxsize=None)
-def cpu_chain():
-    """The planted batch through front, vote, align, fold, the scripts of every aligned locus and their clips: the host arrays that
-    supp_naive takes, by name."""
-    t = text()
-    ranks, roff = pack(planted_reads())
-    reads, loci, al = ch._front(t, 4, ranks, roff, K, COMP4, 1, CHAIN["band"], CHAIN["min_votes"], 0, E, CHAIN["max_span"])
-    dist, start, end, best, _ = al.arrays
-    f = fn.fold(loci.arrays[0], dist, start, end, best)
-    read_sel_off, sel, cig_off, cigar, bad = sn.scripts(t, *reads.arrays, loci.arrays[0], dist, start, end, best, 4, True, False)
-    assert bad == 0
-    clips = cn.clip(cig_off, cigar, **cn.DEFAULTS)
-    return dict(roff2=reads.arrays[1], locus_off=loci.arrays[0], dist=dist, start=start, end=end, placements=f[:7], read_sel_off=read_sel_off, sel=sel,
-                clips=clips[:9], strings=cn.strings(clips[7], clips[8]))
-
-
-def oracle(c, ctg=None, **opt):
-    return sp.supplementaries(c["roff2"], c["start"], c["end"], ctg, c["placements"], c["read_sel_off"], c["sel"], c["clips"], **opt)
-
-
-def rows(out, i=0):
-    """(ent, strand, q0, q1, t0, t1, score, second_score) of the entries of read i"""
-    a, b = int(out["sup_off"][i]), int(out["sup_off"][i + 1])
-    return [tuple(int(out[k][x]) for k in ("ent", "strand", "q0", "q1", "t0", "t1", "score", "second_score")) for x in range(a, b)]
+from tests.chain_checks import supp_cpu_chain as cpu_chain, supp_oracle as oracle, supp_rows as rows
+from tests.chain_data import COMP4, COPIES, LETTERS4 as LETTERS, SUPP_PLANTED as PLANTED, supp_planted_reads as planted_reads
 
 
 # ---- 1. the contract on hand-made arrays ------------------------------------------------------------------------------------------------

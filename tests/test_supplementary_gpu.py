@@ -10,61 +10,20 @@ import pytest
 from tests import chain_naive as ch
 from tests import clip_naive as cn
 from tests import supp_naive as sp
-from tests import test_clip_gpu as tclip
-from tests import test_pairs_gpu as tp
-from tests import test_rescue_gpu as tr
-from tests import test_secondaries_gpu as tsec
-from tests import test_supplementary_cpu as tc
+from tests.chain_checks import (check_clip_md, check_clips, check_supp, close_all, entry_of, refused, same, supp_cpu_chain, supp_oracle,
+                                supp_rows as rows)
+from tests.chain_data import (CLIPS, COMP4, COPIES, K, LETTERS4 as LETTERS, M, SUPP_CHAIN as CHAIN, SUPP_PLANTED, kill, rc4,
+                              supp_planted_reads, supp_text)
 from tests.helpers import pack
 
 pytestmark = pytest.mark.gpu
 
-LETTERS, COMP4, K, E, M, CHAIN = tc.LETTERS, tc.COMP4, tc.K, tc.E, tc.M, tc.CHAIN
-SIZES = {"ent": "n_sup", "locus": "n_sup", "strand": "n_sup", "q0": "n_sup", "q1": "n_sup", "t0": "n_sup", "t1": "n_sup", "score": "n_sup",
-         "second_score": "n_sup", "nm": "n_sup", "ctg": "n_sup", "more": "nr"}
-same, dev_array, close_all, rc4 = tp.same, tp.dev_array, tsec.close_all, tc.rc4
 EMPTY = dict(nr=0, n_sup=0, n_split=0, n_truncated=0)
-
-
-def roff2_of(reads):
-    _, d_roff2, nr2, _ = reads.device_ptrs()
-    return dev_array(d_roff2, nr2 + 1, np.uint64) if nr2 else np.zeros(1, np.uint64)
-
-
-def check_supp(sup, reads, al, pl, asc, acl, **opt):
-    """The handle against supp_naive on the host views of the handles it was made from; the device views against the host views.
-    Returns the oracle's dict."""
-    _, start, end = al.host()[:3]
-    read_sel_off, sel = asc.host()[:2]
-    want = sp.supplementaries(roff2_of(reads), start, end, al.contigs_host(), pl.host(best2=False), read_sel_off, sel, acl.host(),
-                              **dict(sp.DEFAULTS, **opt))
-    got = sup.host()
-    nr = (roff2_of(reads).size - 1) // 2
-    assert len(got) == len(sp.ARRAYS) == 13
-    for name, g in zip(sp.ARRAYS, got):
-        if want[name] is None:
-            assert g is None, name
-        else:
-            same((name,), (g,), (want[name],))
-    assert sup.counts() == dict(nr=nr, n_sup=want["n_sup"], n_split=want["n_split"], n_truncated=want["n_truncated"])
-    c = sup.counts()
-    for name, p, g in zip(sp.ARRAYS, sup.device_ptrs(), got):
-        n = c["nr"] + 1 if name == "sup_off" else c[SIZES[name]]
-        if name == "ctg" and g is None:
-            assert p is None
-            continue
-        assert (p is None) == (n == 0), name
-        assert np.array_equal(dev_array(p, n, g.dtype), g), name
-    return want
-
-
-def rows(want, i):
-    return tc.rows(want, i)
 
 
 @pytest.fixture(scope="module")
 def index(engine):
-    idx = engine.Index(tc.text(), 4, [K], table=2)
+    idx = engine.Index(supp_text(), 4, [K], table=2)
     yield idx
     idx.close()
 
@@ -72,7 +31,7 @@ def index(engine):
 @pytest.fixture(scope="module")
 def mapped(index):
     """the planted batch through the chain with the keyword: (reads, loci, al, pl, sc, tags, cl, sup)"""
-    out = index.map_reads_strands(*pack(tc.planted_reads()), K, COMP4, **CHAIN, scripts=True, tags=True, letters=LETTERS, clip={}, supplementary={})
+    out = index.map_reads_strands(*pack(supp_planted_reads()), K, COMP4, **CHAIN, scripts=True, tags=True, letters=LETTERS, clip={}, supplementary={})
     yield out
     close_all(list(out))
 
@@ -82,17 +41,17 @@ def test_planted_reads_equal_the_oracle_and_the_cpu_chain(engine, mapped):
     reads, loci, al, pl, sc, tags, cl, sup = mapped
     assert isinstance(sup, engine.Supplementaries) and isinstance(sup.all_scripts, engine.Scripts) and isinstance(sup.all_clips, engine.Clips)
     asc, acl = sup.all_scripts, sup.all_clips
-    assert asc.counts()["n_sel"] == al.counts()["n_aligned"] == acl.counts()["n_sel"] and asc.counts()["nr"] == 2 * len(tc.planted_reads())
-    tclip.check_clips(acl, asc)
+    assert asc.counts()["n_sel"] == al.counts()["n_aligned"] == acl.counts()["n_sel"] and asc.counts()["nr"] == 2 * len(supp_planted_reads())
+    check_clips(acl, asc)
     want = check_supp(sup, reads, al, pl, asc, acl)
     # what the CPU chain alone gave for these reads (tests/test_supplementary_cpu.py asserts the per-read figures on it)
-    cpu = tc.oracle(tc.cpu_chain())
+    cpu = supp_oracle(supp_cpu_chain())
     for name in sp.ARRAYS[:11] + ("more",) + sp.COUNTERS:
         assert np.array_equal(want[name], cpu[name]), name
-    at = {name: i for i, name in enumerate(tc.PLANTED)}
+    at = {name: i for i, name in enumerate(SUPP_PLANTED)}
     assert rows(want, at["split"]) and rows(want, at["split_rc"])[0][1] == 1 and rows(want, at["split_rc_whole"])[0][1] == 0
     assert len(rows(want, at["three"])) == 2 and rows(want, at["many"])[0][6] == rows(want, at["many"])[0][7] and want["n_sup"] == 8
-    assert asc.host()[0][2 * at["many"] + 2] - asc.host()[0][2 * at["many"]] == 2 * tc.COPIES > 64
+    assert asc.host()[0][2 * at["many"] + 2] - asc.host()[0][2 * at["many"]] == 2 * COPIES > 64
     x = int(want["sup_off"][at["dup"]])
     assert sup.mapq()[x] == 0 and sup.mapq().tolist() == sp.mapq(want["score"], want["second_score"]) and sup.mapq().dtype == np.uint8
     assert sup.cigars() == [cn.strings(acl.host()[7], acl.host()[8])[int(e)] for e in want["ent"]]
@@ -111,22 +70,22 @@ def test_the_primary_has_the_same_clip_among_all_loci_as_among_the_winners(mappe
         if s == 255 or l == 0xFFFFFFFF:
             continue
         p = [e for e in range(int(read_sel_off[2 * i]), int(read_sel_off[2 * i + 2])) if sel[e] == l]
-        e = tclip.entry_of(pl, sc, i)
+        e = entry_of(pl, sc, i)
         assert len(p) == 1 and all_strings[p[0]] == own_strings[e] != ""
         assert all_h[3][p[0]] == own_h[3][e] and all_h[0][p[0]] == own_h[0][e]                 # tl, score
         n += 1
-    assert n == len(tc.planted_reads()) - 1                    # every read but the one without a letter of the alphabet
+    assert n == len(supp_planted_reads()) - 1                    # every read but the one without a letter of the alphabet
 
 
 # ---- 2. the batch four times over ------------------------------------------------------------------------------------------------------------
 def test_four_copies_of_the_batch_give_four_copies_of_the_result(index, mapped):
     base = mapped[-1]
     R = 4
-    ranks, roff = pack(tc.planted_reads())
+    ranks, roff = pack(supp_planted_reads())
     out = index.map_reads_strands(*ch.tile_reads(ranks, roff, R), K, COMP4, **CHAIN, scripts=True, clip={}, supplementary={})
     try:
         reads, loci, al, pl, sc, cl, sup = out
-        nr = len(tc.planted_reads())
+        nr = len(supp_planted_reads())
         assert sup.counts()["nr"] == R * nr > 64 and 2 * R * nr < 8193
         check_supp(sup, reads, al, pl, sup.all_scripts, sup.all_clips)
         b, g = base.host(), sup.host()
@@ -171,7 +130,7 @@ def test_an_empty_batch_and_a_batch_without_a_locus(engine, index):
 def test_one_handle_through_other_options_ends_the_earlier_views(engine, mapped):
     reads, loci, al, pl, sc, tags, cl, base = mapped
     asc, acl = base.all_scripts, base.all_clips
-    at = {name: i for i, name in enumerate(tc.PLANTED)}
+    at = {name: i for i, name in enumerate(SUPP_PLANTED)}
     sup = engine.Supplementaries()
     try:
         assert acl.supplementaries(reads, loci, al, pl, asc, supplementaries=sup) is sup and sup.all_clips is acl
@@ -195,9 +154,9 @@ def test_one_handle_through_other_options_ends_the_earlier_views(engine, mapped)
 
 # ---- 4. pairs with a rescue: the SAM lines -----------------------------------------------------------------------------------------------------
 def test_pairs_with_a_rescue_and_their_sam_lines(engine, index):
-    t, cat = tc.text(), np.concatenate
+    t, cat = supp_text(), np.concatenate
     mates = [cat([t[2000:2100], t[5000:5050]]), rc4(t[2300:2450]),               # a split mate 1, its mate 2 concordant with the primary
-             t[1000:1150].copy(), tr.kill(rc4(t[1300:1450]), K),                  # mate 2 has no intact window: rescued
+             t[1000:1150].copy(), kill(rc4(t[1300:1450]), K),                  # mate 2 has no intact window: rescued
              t[6700:6850].copy(), rc4(cat([t[7000:7100], rc4(t[7030:7080])])),    # mate 2 split, its primary on the reverse strand
              t[8200:8350].copy(), rc4(t[8500:8650])]                              # an ordinary pair
     ranks, roff = pack(mates)
@@ -243,7 +202,7 @@ def test_pairs_with_a_rescue_and_their_sam_lines(engine, index):
         amd = acl.md(index, asc, al, LETTERS)
         held.append(amd)
         _, start, end = al.host()[:3]
-        md_strings = tclip.check_clip_md(amd, tclip.check_clips(acl, asc), start, end, t)
+        md_strings = check_clip_md(amd, check_clips(acl, asc), start, end, t)
         got = engine.sam_supplementary_lines(lines, ranks, roff, LETTERS, COMP4, 4, sup.host(), sup.cigars(), sup.mds(amd), sup.mapq(), sa, rname="chr")
         expect = []
         for i in (0, 5):
@@ -269,10 +228,10 @@ def test_pairs_with_a_rescue_and_their_sam_lines(engine, index):
 
 # ---- 5. a contig table ---------------------------------------------------------------------------------------------------------------------------
 def test_under_a_contig_table_the_entries_carry_their_contig(engine):
-    t = tc.text()
-    at = {name: i for i, name in enumerate(tc.PLANTED)}
+    t = supp_text()
+    at = {name: i for i, name in enumerate(SUPP_PLANTED)}
     pick = ("plain", "split", "split_rc", "dup")
-    reads_in = [tc.planted_reads()[at[n]] for n in pick]
+    reads_in = [supp_planted_reads()[at[n]] for n in pick]
     ctg_off = np.asarray([0, 4000, 12_000, 20_000], np.uint64)
     names = ("c0", "c1", "c2")
     idx = engine.Index(t, 4, [K], table=2)
@@ -299,24 +258,17 @@ def test_under_a_contig_table_the_entries_carry_their_contig(engine):
 
 
 # ---- 6. the refusals after looking, the chain keyword -----------------------------------------------------------------------------------------
-def refused(engine, call, status=1):
-    with pytest.raises(engine.KmxError) as e:
-        call()
-    assert e.value.status == status and "kmx_clips_supplementaries: " in str(e.value)
-    return str(e.value)
-
-
 def test_refusals_after_looking_leave_an_empty_result(engine, index, mapped):
     reads, loci, al, pl, sc, tags, cl, base = mapped
     asc, acl = base.all_scripts, base.all_clips
     d_ranks2, d_roff2, nr2, stream = reads.device_ptrs()
     held = []
     try:
-        other = index.map_reads_strands(*pack(tc.planted_reads()[:3]), K, COMP4, **CHAIN, scripts=True, clip={}, supplementary={})
+        other = index.map_reads_strands(*pack(supp_planted_reads()[:3]), K, COMP4, **CHAIN, scripts=True, clip={}, supplementary={})
         held += list(other)
         o_reads, o_loci, o_al, o_pl, o_sc, o_cl, o_sup = other
         # the same reads under another vote: as many reads, other loci
-        again = index.map_reads_strands(*pack(tc.planted_reads()), K, COMP4, **dict(CHAIN, min_votes=8))
+        again = index.map_reads_strands(*pack(supp_planted_reads()), K, COMP4, **dict(CHAIN, min_votes=8))
         held += list(again)
         assert again[1].counts()["n_loci"] != loci.counts()["n_loci"] and again[1].counts()["nr"] == loci.counts()["nr"]
         joined = al.scripts_device(index, loci, d_ranks2, d_roff2, nr2, all=True, m=True, stream=stream)
@@ -335,7 +287,7 @@ def test_refusals_after_looking_leave_an_empty_result(engine, index, mapped):
         for call, word in cases:
             acl.supplementaries(reads, loci, al, pl, asc, supplementaries=sup)
             assert sup.counts()["n_sup"] == 8 and sup.device_ptrs()[0] is not None
-            assert word in refused(engine, call)
+            assert word in refused(engine, call, "kmx_clips_supplementaries")
             assert sup.counts() == EMPTY and sup.device_ptrs() == (None,) * 13
             h = sup.host()
             assert h[0].tolist() == [0] and h[11] is None and all(x.size == 0 for x in h[1:11] + h[12:])
@@ -353,7 +305,7 @@ def test_refusals_after_looking_leave_an_empty_result(engine, index, mapped):
 
 def test_the_chain_keyword_appends_the_separate_calls(engine, index, mapped):
     reads, loci, al, pl, sc, tags, cl, sup = mapped
-    ranks, roff = pack(tc.planted_reads())
+    ranks, roff = pack(supp_planted_reads())
     held = []
     try:
         for kw in (dict(supplementary={}), dict(scripts=True, supplementary={}), dict(clip={}, supplementary={})):
@@ -376,13 +328,13 @@ def test_the_chain_keyword_appends_the_separate_calls(engine, index, mapped):
         for name, g, w in zip(sp.ARRAYS, sup.host(), apart.host()):
             assert (g is None and w is None) or (g.dtype == w.dtype and np.array_equal(g, w)), name
         assert sup.counts() == apart.counts() and apart.counts()["n_sup"] == 8
-        same(tclip.CLIPS, sup.all_clips.host(), acl.host())
+        same(CLIPS, sup.all_clips.host(), acl.host())
         # other arguments, and other clip scoring, through the keyword
         opt = dict(max_supplementary=1, min_len=30)
         out = index.map_reads_strands(ranks, roff, K, COMP4, **CHAIN, scripts=True, clip=dict(clip_penalty=2), supplementary=opt)
         held += list(out)
         assert len(out) == 7
-        tclip.check_clips(out[-1].all_clips, out[-1].all_scripts, clip_penalty=2)
+        check_clips(out[-1].all_clips, out[-1].all_scripts, clip_penalty=2)
         check_supp(out[-1], out[0], out[2], out[3], out[-1].all_scripts, out[-1].all_clips, **opt)
         # the handle of the chain closes the two it was made from
         a, b = out[-1].all_scripts, out[-1].all_clips

@@ -11,6 +11,7 @@ from kmer_index_amd import synth
 from tests import mapq_naive as qn
 from tests import md_naive as mn
 from tests import script_naive as sn
+from tests.chain_data import edited
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LETTERS = "ACGT"
@@ -70,20 +71,6 @@ def by_columns(runs, q, t):
             c = 0
             in_del = False
     return out + str(c)
-
-
-def edited(z, q, n_edits):
-    """q with n_edits random edits (substitutions, insertions, deletions) at random places, from the numbers z"""
-    q = list(int(x) for x in q)
-    for k in range(n_edits):
-        kind, at, letter = int(z[3 * k] % 3), int(z[3 * k + 1] % max(len(q), 1)), int(z[3 * k + 2] % 4)
-        if kind == 0 and q:
-            q[at] = (q[at] + 1 + letter % 3) % 4
-        elif kind == 1:
-            q.insert(at, letter)
-        elif q:
-            del q[at]
-    return np.asarray(q, np.uint8)
 
 
 def test_md_naive_equals_the_column_formatter_and_rebuilds_the_text():

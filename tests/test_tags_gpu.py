@@ -1,7 +1,7 @@
 """SAM tags on the GPU: kmx_scripts_md, kmx_rescues_md, kmx_placements_mapq, the tags of Index.map_pairs / map_reads_strands and
 engine.sam_lines on their results.  The oracle is always tests/md_naive.py or tests/mapq_naive.py applied to the engine's own host
 views; every array and every counter must be bit-identical.  The texts, the reads, the chain settings and the helpers are those of
-tests/test_pairs_gpu.py and tests/test_rescue_gpu.py; nothing larger runs on the device."""
+tests/chain_data.py and tests/chain_checks.py; nothing larger runs on the device."""
 import ctypes as C
 import re
 
@@ -12,49 +12,14 @@ from tests import fold_naive as fn
 from tests import mapq_naive as qn
 from tests import md_naive as mn
 from tests import pair_naive as pn
-from tests import test_pairs_gpu as tp
-from tests import test_rescue_gpu as tr
+from tests.chain_checks import check_md, check_rebuild, close_all, dev_array, read_of_entries, same, spell
+from tests.chain_data import (ALIGN, CHAIN, COMPLEMENT, INSERT, JOBS, LETTERS, N_PAIRS, PAIRS, PAIR_WORKLOADS as WORKLOADS, PLACEMENTS, REPEAT_CHAIN,
+                              RESCUE_FLOORS, SCRIPTS, pairs_of, repeat_pair, repeat_text, rescue_pairs_of, text_of)
 from tests.helpers import pack
 
 pytestmark = pytest.mark.gpu
 
-WORKLOADS, COMPLEMENT, CHAIN, INSERT = tp.WORKLOADS, tp.COMPLEMENT, tp.CHAIN, tp.INSERT
-text_of, rc, same, dev_array = tp.text_of, tp.rc, tp.same, tp.dev_array
-LETTERS = {4: "ACGT", 20: "ACDEFGHIKLMNPQRSTVWY"}
 E = CHAIN["max_edits"]
-N_PAIRS = tp.N_PAIRS
-MD = ("md_off", "md")
-
-
-def spell(ranks, sigma):
-    return "".join(LETTERS[sigma][int(x)] for x in ranks)
-
-
-def read_of_entries(read_sel_off):
-    return np.repeat(np.arange(read_sel_off.size - 1), np.diff(read_sel_off.astype(np.int64)))
-
-
-def check_md(md, sc, start, end, text, sigma, bound=None):
-    """The md handle against md_naive on the host views of the scripts and these start / end arrays; returns the oracle's strings."""
-    _, sel, cig_off, cigar = sc.host()
-    want = mn.md(sel, cig_off, cigar, start, end, text, LETTERS[sigma], bound)
-    got = md.host()
-    same(MD, got, want[:2])
-    assert md.counts() == dict(n_sel=sel.size, n_bytes=want[1].size, n_mismatched=want[2])
-    d_off, d_md = md.device_ptrs()
-    same(MD, (dev_array(d_off, sel.size + 1, np.uint64), dev_array(d_md, want[1].size, np.uint8)), got)
-    assert md.strings() == mn.strings(*want[:2])
-    return md.strings()
-
-
-def check_rebuild(strings, sc, ranks2, roff2, start, end, text, sigma):
-    """every string matches the grammar, and SEQ + CIGAR + MD give back text[start:end]"""
-    read_sel_off, sel, cig_off, cigar = sc.host()
-    for e, (r, l) in enumerate(zip(read_of_entries(read_sel_off), sel)):
-        runs = cigar[int(cig_off[e]):int(cig_off[e + 1])]
-        assert mn.GRAMMAR.match(strings[e]), strings[e]
-        seq = spell(ranks2[int(roff2[r]):int(roff2[r + 1])], sigma)
-        assert mn.rebuild(seq, runs, strings[e]) == spell(text[int(start[l]):int(end[l])], sigma), e
 
 
 def check_mapq(mq, pl, max_edits, pairs=None, **opts):
@@ -68,7 +33,7 @@ def check_mapq(mq, pl, max_edits, pairs=None, **opts):
 
 
 class Work:
-    """the indexes and, per workload, map_pairs(scripts=True) of tests/test_pairs_gpu.pairs_of"""
+    """the indexes and, per workload, map_pairs(scripts=True) of tests/chain_data.pairs_of"""
 
     def __init__(self, engine):
         self.engine = engine
@@ -83,7 +48,7 @@ class Work:
     def workload(self, name):
         if name not in self.mapped:
             sigma, k, _ = WORKLOADS[name]
-            self.mapped[name] = self.index(name).map_pairs(*tp.pairs_of(name), k, np.asarray(COMPLEMENT[sigma], np.uint8), **CHAIN, **INSERT, scripts=True)
+            self.mapped[name] = self.index(name).map_pairs(*pairs_of(name), k, np.asarray(COMPLEMENT[sigma], np.uint8), **CHAIN, **INSERT, scripts=True)
         return self.mapped[name]
 
     def close(self):
@@ -101,14 +66,6 @@ def work(engine):
     w.close()
 
 
-def close_all(held):
-    for h in reversed(held):
-        if isinstance(h, tuple):                               # a SamTags
-            close_all([x for x in h if x is not None])
-        elif h is not None:
-            h.close()
-
-
 # ---- 1. MD of the placements' scripts -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", sorted(WORKLOADS))
 def test_md_of_the_workload_equals_the_oracle_and_rebuilds_the_text(work, name):
@@ -121,7 +78,7 @@ def test_md_of_the_workload_equals_the_oracle_and_rebuilds_the_text(work, name):
         _, start, end = al.host()[:3]
         strings = check_md(md, sc, start, end, text, sigma)
         assert md.counts()["n_mismatched"] == 0 and md.counts()["n_sel"] == pl.counts()["n_placed"] >= 400
-        ranks2, roff2 = fn.double_reads(*tp.pairs_of(name), COMPLEMENT[sigma], sigma)
+        ranks2, roff2 = fn.double_reads(*pairs_of(name), COMPLEMENT[sigma], sigma)
         check_rebuild(strings, sc, ranks2, roff2, start, end, text, sigma)
         # what the batch must contain, counted on the oracle's strings (check_md has compared them)
         reverse = read_of_entries(sc.host()[0]) % 2 == 1
@@ -132,8 +89,8 @@ def test_md_of_the_workload_equals_the_oracle_and_rebuilds_the_text(work, name):
         # the scripts and the alignments are untouched
         after = (sc.host(), al.host(), sc.device_ptrs(), al.device_ptrs(), sc.counts(), al.counts())
         assert before[2:] == after[2:]
-        same(("read_sel_off", "sel", "cig_off", "cigar"), after[0], before[0])
-        same(tp.ALIGN, after[1], before[1])
+        same(SCRIPTS, after[0], before[0])
+        same(ALIGN, after[1], before[1])
         # one string per public read, where the CIGARs are
         per_read, cigars = pl.mds(md, sc), pl.cigars(sc)
         assert len(per_read) == 2 * N_PAIRS and [bool(s) for s in per_read] == [bool(s) for s in cigars]
@@ -143,11 +100,11 @@ def test_md_of_the_workload_equals_the_oracle_and_rebuilds_the_text(work, name):
 
 
 # ---- 2. MD of the rescued mates --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", sorted(tr.FLOORS))
+@pytest.mark.parametrize("name", sorted(RESCUE_FLOORS))
 def test_md_of_the_rescued_mates(work, name):
     sigma, k, n = WORKLOADS[name]
     text, idx = text_of(sigma, n), work.index(name)
-    ranks, roff = tr.rescue_pairs_of(name)
+    ranks, roff = rescue_pairs_of(name)
     held = list(idx.map_pairs(ranks, roff, k, np.asarray(COMPLEMENT[sigma], np.uint8), **CHAIN, **INSERT, rescue=True))
     try:
         reads, res = held[0], held[5]
@@ -158,7 +115,7 @@ def test_md_of_the_rescued_mates(work, name):
         jobs = res.host()
         start, end, status = jobs[5], jobs[6], jobs[7]
         strings = check_md(rmd, rsc, start, end, text, sigma)
-        assert rmd.counts()["n_mismatched"] == 0 and len(strings) == tr.FLOORS[name] == 75 == int((status == 3).sum())
+        assert rmd.counts()["n_mismatched"] == 0 and len(strings) == RESCUE_FLOORS[name] == 75 == int((status == 3).sum())
         assert np.array_equal(rsc.host()[1], np.flatnonzero(status == 3))
         # The 8 planted substitutions of every rescued mate: 8 mismatch letters, except where the substitution next to an end of the
         # read meets a neighbour of the text that equals the letter beside it.  Then the alignment's own rule (the largest start, the
@@ -174,7 +131,7 @@ def test_md_of_the_rescued_mates(work, name):
         ranks2, roff2 = fn.double_reads(ranks, roff, COMPLEMENT[sigma], sigma)
         check_rebuild(strings, rsc, ranks2, roff2, start, end, text, sigma)
         per_read, cigars = res.mds(rmd, rsc), res.cigars(rsc)
-        assert len(per_read) == 2 * tr.N_PAIRS and [bool(s) for s in per_read] == [bool(s) for s in cigars] and sum(bool(s) for s in per_read) == 75
+        assert len(per_read) == 2 * N_PAIRS and [bool(s) for s in per_read] == [bool(s) for s in cigars] and sum(bool(s) for s in per_read) == 75
     finally:
         close_all(held)
 
@@ -184,7 +141,7 @@ def test_md_of_all_scripts_of_map_reads_and_the_refusal_of_m_scripts(work):
     name = "dna4_k10"
     sigma, k, n = WORKLOADS[name]
     engine, idx, text = work.engine, work.index(name), text_of(sigma, n)
-    ranks, roff = tp.pairs_of(name)
+    ranks, roff = pairs_of(name)
     ranks, roff = ranks[:int(roff[200])], roff[:201]
     held = list(idx.map_reads(ranks, roff, k, **CHAIN))
     try:
@@ -261,7 +218,7 @@ def test_scripts_with_the_alignments_of_another_batch(work):
     sigma, k, n = WORKLOADS[name]
     idx, text = work.index(name), text_of(sigma, n)
     reads, loci, al, pl, pairs, sc = work.workload(name)
-    ranks, roff = tp.pairs_of(name)
+    ranks, roff = pairs_of(name)
     other = list(idx.map_pairs(ranks[int(roff[300]):int(roff[500])], roff[300:501] - roff[300], k, np.asarray(COMPLEMENT[sigma], np.uint8), **CHAIN, **INSERT))
     md = None
     try:
@@ -335,14 +292,14 @@ def test_batches_of_every_size_through_one_md_handle_and_the_letters_refusals(wo
 def test_mapq_of_single_reads_pairs_and_rescued_pairs(work, name):
     sigma, k, _ = WORKLOADS[name]
     idx, comp = work.index(name), np.asarray(COMPLEMENT[sigma], np.uint8)
-    ranks, roff = tr.rescue_pairs_of(name)
+    ranks, roff = rescue_pairs_of(name)
     held = list(idx.map_pairs(ranks, roff, k, comp, **CHAIN, **INSERT))
     try:
         reads, loci, al, pl, pairs = held
         mq = pl.mapq(E, pairs)
         held.append(mq)
         before = check_mapq(mq, pl, E, pairs)
-        assert mq.counts()["n_cap"] >= 250 and mq.counts()["nr"] == 2 * tr.N_PAIRS
+        assert mq.counts()["n_cap"] >= 250 and mq.counts()["nr"] == 2 * N_PAIRS
         check_mapq(pl.mapq(E, mapq=mq), pl, E)                                   # the same placements as single reads
         res = pairs.rescue(idx, reads, loci, al, pl, **INSERT, max_edits=E)
         held.append(res)
@@ -364,11 +321,11 @@ def test_mapq_of_single_reads_pairs_and_rescued_pairs(work, name):
 
 
 def test_mapq_of_the_repeat_mate_and_of_the_reverse_palindrome(engine):
-    text, _ = tp.repeat_text()
+    text, _ = repeat_text()
     idx = engine.Index(text, 4, [10], table=2)
     held = []
     try:
-        held += list(idx.map_pairs(*tp.repeat_pair(), 10, np.asarray(COMPLEMENT[4], np.uint8), **tp.REPEAT_CHAIN, min_insert=450, max_insert=520))
+        held += list(idx.map_pairs(*repeat_pair(), 10, np.asarray(COMPLEMENT[4], np.uint8), **REPEAT_CHAIN, min_insert=450, max_insert=520))
         pl, pairs = held[3], held[4]
         assert pl.host()[5].tolist() == [0, 255] and pairs.host()[0].tolist() == [pn.CONCORDANT]
         mq = pl.mapq(E, pairs)
@@ -379,7 +336,7 @@ def test_mapq_of_the_repeat_mate_and_of_the_reverse_palindrome(engine):
         assert check_mapq(pl.mapq(E, mapq=mq), pl, E).tolist() == [0, 60]                  # alone it stays a repeat read
         # x + rc(x) equals its reverse complement: the other strand is a copy elsewhere
         n = text.size
-        out = idx.map_reads_strands(*pack([text[n - 40:].copy(), text[500:560].copy()]), 10, np.asarray(COMPLEMENT[4], np.uint8), **tp.REPEAT_CHAIN)
+        out = idx.map_reads_strands(*pack([text[n - 40:].copy(), text[500:560].copy()]), 10, np.asarray(COMPLEMENT[4], np.uint8), **REPEAT_CHAIN)
         held += list(out)
         assert out[3].host()[2].tolist() == [0, 0] and out[3].host()[5].tolist() == [0, 255]
         assert check_mapq(out[3].mapq(E, mapq=mq), out[3], E).tolist() == [0, 60] and mq.counts() == dict(nr=2, n_zero=1, n_cap=1)
@@ -392,7 +349,7 @@ def test_mapq_batches_of_every_size_and_every_refusal(work):
     name = "dna4_k10"
     sigma, k, _ = WORKLOADS[name]
     engine, idx, comp = work.engine, work.index(name), np.asarray(COMPLEMENT[sigma], np.uint8)
-    ranks, roff = tp.pairs_of(name)
+    ranks, roff = pairs_of(name)
     L = engine.lib()
     mq = engine.Mapq()
     held = [mq]
@@ -438,7 +395,7 @@ def test_map_pairs_and_map_reads_strands_with_tags_are_the_calls_they_are_made_o
     name = "dna4_k10"
     sigma, k, n = WORKLOADS[name]
     engine, idx, comp, text = work.engine, work.index(name), np.asarray(COMPLEMENT[sigma], np.uint8), text_of(sigma, n)
-    ranks, roff = tr.rescue_pairs_of(name)
+    ranks, roff = rescue_pairs_of(name)
     held = []
     try:
         out = idx.map_pairs(ranks, roff, k, comp, **CHAIN, **INSERT, rescue=True, tags=True, letters=LETTERS[sigma])
@@ -457,10 +414,10 @@ def test_map_pairs_and_map_reads_strands_with_tags_are_the_calls_they_are_made_o
         plain = idx.map_pairs(ranks, roff, k, comp, **CHAIN, **INSERT, rescue=True, scripts=True)
         held += list(plain)
         assert len(plain) == 7
-        same(tp.PLACEMENTS, plain[3].host(), pl.host())
-        same(tp.PAIRS, plain[4].host(), pairs.host())
-        same(("read_sel_off", "sel", "cig_off", "cigar"), plain[5].host(), sc.host())
-        same(tr.JOBS, plain[6].host(), res.host())
+        same(PLACEMENTS, plain[3].host(), pl.host())
+        same(PAIRS, plain[4].host(), pairs.host())
+        same(SCRIPTS, plain[5].host(), sc.host())
+        same(JOBS, plain[6].host(), res.host())
         bare = idx.map_pairs(ranks, roff, k, comp, **CHAIN, **INSERT)
         held += list(bare)
         assert len(bare) == 5
@@ -468,7 +425,7 @@ def test_map_pairs_and_map_reads_strands_with_tags_are_the_calls_they_are_made_o
         held += list(no_rescue)
         assert len(no_rescue) == 7 and no_rescue[6].rescue_scripts is None and no_rescue[6].rescue_md is None
         check_mapq(no_rescue[6].mapq, no_rescue[3], E, no_rescue[4])
-        same(tp.PLACEMENTS, bare[3].host(), no_rescue[3].host())
+        same(PLACEMENTS, bare[3].host(), no_rescue[3].host())
         # both strands of single reads
         single = idx.map_reads_strands(ranks, roff, k, comp, **CHAIN, tags=True, letters=LETTERS[sigma])
         held += list(single)
@@ -478,8 +435,8 @@ def test_map_pairs_and_map_reads_strands_with_tags_are_the_calls_they_are_made_o
         old = idx.map_reads_strands(ranks, roff, k, comp, **CHAIN, scripts=True)
         held += list(old)
         assert len(old) == 5
-        same(tp.PLACEMENTS, old[3].host(), single[3].host())
-        same(("read_sel_off", "sel", "cig_off", "cigar"), old[4].host(), single[4].host())
+        same(PLACEMENTS, old[3].host(), single[3].host())
+        same(SCRIPTS, old[4].host(), single[4].host())
         older = idx.map_reads_strands(ranks, roff, k, comp, **CHAIN)
         held += list(older)
         assert len(older) == 4
@@ -497,7 +454,7 @@ def test_sam_lines_of_the_device_results_rebuild_the_text(work, paired):
     name = "dna4_k10"
     sigma, k, n = WORKLOADS[name]
     engine, idx, comp, text = work.engine, work.index(name), np.asarray(COMPLEMENT[sigma], np.uint8), text_of(sigma, n)
-    ranks, roff = tr.rescue_pairs_of(name)
+    ranks, roff = rescue_pairs_of(name)
     if paired:
         out = idx.map_pairs(ranks, roff, k, comp, **CHAIN, **INSERT, rescue=True, tags=True, letters=LETTERS[sigma])
         reads, loci, al, pl, pairs, sc, res, tags = out

@@ -18,32 +18,12 @@ import sys
 import numpy as np
 import pytest
 
-from kmer_index_amd import synth
 from tests import variant_layouts as vl
+from tests.variant_runs import K, cells_case, dev_search, lookup_text_and_batch, same_answers, small_batches
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-K = 6
 FILL_VARIANTS = [("4", False), ("4n", False), ("8", False), ("8n", False), ("12", False), ("12n", False), ("16", False), ("16n", False),
                  ("8", True), ("8n", True)]
-
-
-def dev_search(idx, qranks, qoff, res, flags=0):
-    """kmx_search_batch_device on queries uploaded with torch: ((hit_off, positions, status, kinds), paths)."""
-    import torch
-    d_q = torch.from_numpy(np.ascontiguousarray(qranks, np.uint8)).cuda()
-    d_o = torch.from_numpy(np.ascontiguousarray(qoff, np.uint64).view(np.int64)).cuda()
-    torch.cuda.synchronize()
-    idx.search_device(d_q.data_ptr(), d_o.data_ptr(), qoff.size - 1, flags=flags, result=res)
-    out = res.host()
-    return out, res.paths()
-
-
-def same(got, want, what):
-    ho, pos, st, _ = got
-    o_off, o_pos, o_st = want
-    assert np.array_equal(st, o_st.astype(np.uint8)), ("status", what)
-    assert np.array_equal(ho, o_off), ("hit_off", what)
-    assert np.array_equal(pos, o_pos), ("positions", what)
 
 
 class Case:
@@ -60,7 +40,7 @@ class Case:
         self.planted = {ev["q"]: orc.naive_scan(text, batch.qs[ev["q"]]) for ev in batch.events if "q" in ev}
 
     def check(self, got, what):
-        same(got, self.want, what)
+        same_answers(got, self.want, what)
         ho, pos = got[0], got[1]
         for q, naive in self.planted.items():
             assert np.array_equal(pos[int(ho[q]):int(ho[q + 1])], naive), ("naive scan", what, q)
@@ -218,21 +198,13 @@ def test_fill_variants_agree_with_one_another(engine, world, monkeypatch):
 # ---------------------------------------------------------------------------------------------------------------------------
 # k_lookup variants
 
-def lookup_text_and_batch(nq):
-    """50 000 letters of DNA4, k = 7: as a dense table the index has cells of 8 and at most four positions per key (tiny_cells).
-    Queries: exact (planted and random: some absent), sub-k (4, 5 letters), two-part (14, and 10 = 7 + a rest)."""
-    text = synth.ranks(77, 50_000, 4)
-    q, off = synth.mixed_queries(78, text, nq, [7, 7, 7, 7, 5, 14, 10, 4, 7, 7], 4, planted_frac=0.6)
-    return text, q, off
-
-
 LOOKUP_CHILD = r"""
 import json, sys
 sys.path.insert(0, %(root)r)
 import numpy as np
 from kmer_index_amd import engine
 from oracle import orc
-from tests.test_variants_gpu import dev_search, same, lookup_text_and_batch
+from tests.variant_runs import dev_search, same_answers, lookup_text_and_batch
 
 text = q = None
 for table in (engine.TABLE_DENSE, engine.TABLE_OPEN):
@@ -248,7 +220,7 @@ for table in (engine.TABLE_DENSE, engine.TABLE_OPEN):
         nl, nh = int(off[nq]), int(o_off[nq])
         for rep in range(2):
             got, p = dev_search(idx, q[:nl], off[:nq + 1], res)
-            same(got, (o_off[:nq + 1], o_pos[:nh], o_st[:nq]), (table, nq, rep))
+            same_answers(got, (o_off[:nq + 1], o_pos[:nh], o_st[:nq]), (table, nq, rep))
             print("paths", json.dumps({"table": table, "nq": nq, "cell_shift": ip["cell_shift"], "tiny": ip["tiny_cells"], "items": p["lookup_items"],
                                        "pairs": p["lookup_pairs"], "small": p["small"]}))
     kinds = np.bincount(got[3], minlength=4)
@@ -308,7 +280,7 @@ def test_lookup_variants_by_history(engine, orc):
         seq = [("pairs", with_pairs), ("after pairs", without), ("plain", without), ("long", with_long), ("after long", without), ("plain again", without)]
         for name, (qq, o, want) in seq:
             got, p = dev_search(idx, qq, o, res)
-            same(got, want, (table, name))
+            same_answers(got, want, (table, name))
             reached[(tiny, name)] = (p["lookup_items"], p["lookup_pairs"], p["deferred_long"])
         res.close()
         idx.close()
@@ -325,18 +297,6 @@ def test_lookup_variants_by_history(engine, orc):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # cells
-
-def cells_case(n):
-    """DNA4, k = 6 (4096 keys, dense): n letters give c = n / 4096 positions per key.  Every key once as an exact query (the
-    histogram names the ones whose buckets hold 2^shift - 1, 2^shift and 2^shift + 1 positions), then sub-k queries and the tail."""
-    text = synth.ranks(500 + n, n, 4)
-    hist = np.bincount(vl.kmer_codes(text, K), minlength=4 ** K)
-    qs = [vl.decode(c, K) for c in range(4 ** K)]
-    qs += [text[s:s + m].copy() for m in (5, 4, 3) for s in (0, 777, n // 2)] + [text[n - m:].copy() for m in (5, 4, 3)]
-    off = np.zeros(len(qs) + 1, np.uint64)
-    off[1:] = np.cumsum([len(x) for x in qs])
-    return text, hist, np.concatenate(qs).astype(np.uint8), off
-
 
 # c = npos / n_keys just ABOVE the thresholds of the default choice — 3.5 (cells of 8 up to there), 10.5 (of 16), 24 (of 32, none
 # beyond) — so that the default is the next answer and only a knob that took effect gives the shift asked for:
@@ -366,7 +326,7 @@ def test_cell_sizes(engine, orc, monkeypatch, var, value, shift, n, default):
     res = engine.Result()
     for rep in range(2):
         got, p = dev_search(idx, q, off, res)
-        same(got, want, (var, value, rep))
+        same_answers(got, want, (var, value, rep))
         assert not p["small"]
     for c in np.nonzero((hist >= edge - 1) & (hist <= edge + 1))[0][:12]:
         assert np.array_equal(got[1][int(got[0][c]):int(got[0][c + 1])], orc.naive_scan(text, vl.decode(int(c), K)))
@@ -377,37 +337,9 @@ def test_cell_sizes(engine, orc, monkeypatch, var, value, shift, n, default):
 SMALL_CHILD = r"""
 import sys
 sys.path.insert(0, %(root)r)
-from tests.test_variants_gpu import small_batches
+from tests.variant_runs import small_batches
 print("small child ok", *small_batches())
 """
-
-
-def small_batches():
-    """Host-buffer searches of 1 .. 40 queries on the index of cells of 16: ('small' | 'general', digest of every answer)."""
-    from kmer_index_amd import engine
-    import hashlib
-    from oracle import orc
-    from tests.helpers import digest
-    text, hist, q, off = cells_case(42_900)
-    idx = engine.Index(text, 4, [K], table=engine.TABLE_DENSE)
-    assert idx.paths()["cell_shift"] == [4]
-    oidx = orc.Index(text, 4, [K])
-    edge = np.nonzero((hist >= 15) & (hist <= 17))[0]
-    digests, small = [], set()
-    res = engine.Result()
-    for nq in range(1, 41):
-        ids = [int(edge[(7 * nq + j) % edge.size]) if j % 2 else 4 ** K + (nq + j) % 12 for j in range(nq)]     # edge buckets and sub-k queries
-        qs = [q[int(off[i]):int(off[i + 1])] for i in ids]
-        o = np.zeros(nq + 1, np.uint64)
-        o[1:] = np.cumsum([len(x) for x in qs])
-        r = idx.search(np.concatenate(qs), o, result=res)
-        ho, pos, st, kd = r.host()
-        same((ho, pos, st, kd), oidx.search_batch(np.concatenate(qs), o, mode=orc.MODE_INTENDED)[:3], nq)
-        small.add(r.paths()["small"])
-        digests.append(digest(ho, pos) ^ int(st.sum()))
-    res.close()
-    idx.close()
-    return ("small" if True in small else "general"), hashlib.sha1(np.array(digests, np.uint64).tobytes()).hexdigest()
 
 
 @pytest.mark.gpu

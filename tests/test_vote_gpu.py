@@ -6,67 +6,18 @@ import numpy as np
 import pytest
 
 from kmer_index_amd import synth
+from tests import chain_data
+from tests.chain_checks import dev_array
+from tests.chain_data import READ_WORKLOADS, text_of
 from tests.helpers import pack
 from tests.vote_naive import vote
 
 pytestmark = pytest.mark.gpu
 
 NAMES = ("locus_off", "diag", "span", "votes", "skipped")
-# name: (sigma, k, text length, reads)
-WORKLOADS = {"dna4_k10": (4, 10, 50_000, 3000), "aa20_k5": (20, 5, 50_000, 3000), "dna4_k5": (4, 5, 100_000, 300)}
+WORKLOADS = READ_WORKLOADS              # name: (sigma, k, text length, reads)
+reads_of = functools.partial(chain_data.reads_of, meta="plain")      # with (kind, s, m, plain) per read
 OPTION_SETS = [(0, 1, 0), (0, 10, 0), (3, 8, 100), (0, 2, 1), (65_535, 1, 0)]      # (band, min_votes, max_occ)
-
-
-@functools.lru_cache(maxsize=None)
-def text_of(sigma, n):
-    t = synth.ranks(7 + sigma, n, sigma)
-    t.setflags(write=False)
-    return t
-
-
-@functools.lru_cache(maxsize=None)
-def reads_of(name):
-    """The reads of a workload and, per read, (kind, s, m, plain): plain = cut from the text at s and left as it was.
-    Read i has m = z % 301 letters and kind i % 4: 3 is random letters, the others are cut from the text (at 0 when i % 40 == 0,
-    flush with its end when i % 40 == 4, else anywhere); kind 1 with m > 40 gets a substitution at letters 12, 37, 62, ...; kind 2
-    with m > 60 loses the letter at m / 3 and has the one at 2m / 3 twice.  i % 40 == 8 / 12 with m >= 40: 20 random letters in
-    front of text[:m - 20] / behind text[n - (m - 20):], reads that overhang the text.  Every 50th read carries one letter >= sigma,
-    at its first, last and middle letter in turn."""
-    sigma, _, n, n_reads = WORKLOADS[name]
-    text = text_of(sigma, n)
-    z = synth.u64_stream(4241 + sigma + n_reads, 2 * n_reads).astype(np.int64) & 0x7FFFFFFF
-    reads, meta = [], []
-    n_bad = 0
-    for i in range(n_reads):
-        m, kind = int(z[2 * i] % 301), i % 4
-        s, plain = -1, False
-        if kind == 3:
-            q = synth.ranks(900_001 + i, m, sigma)
-        elif i % 40 == 8 and m >= 40:
-            q = np.concatenate([synth.ranks(700_001 + i, 20, sigma), text[:m - 20]])
-        elif i % 40 == 12 and m >= 40:
-            q = np.concatenate([text[n - (m - 20):], synth.ranks(800_001 + i, 20, sigma)])
-        else:
-            s = 0 if i % 40 == 0 else n - m if i % 40 == 4 else int(z[2 * i + 1] % (n - m - 1 + 1))
-            if kind == 2 and m > 60:
-                q = text[s:s + m + 1].copy()
-                q = np.delete(q, m // 3)[:m]                               # one letter gone ...
-                q = np.insert(q, 2 * m // 3, q[2 * m // 3])[:m]            # ... and one twice
-            else:
-                q = text[s:s + m].copy()
-                if kind == 1 and m > 40:
-                    q[12::25] = (q[12::25] + 1) % sigma
-            plain = kind == 0
-        if i % 50 == 7 and m > 0:
-            q[(0, m - 1, m // 2)[n_bad % 3]] = (sigma, 255)[(n_bad // 3) % 2]
-            n_bad += 1
-            plain = False
-        reads.append(np.asarray(q, np.uint8))
-        meta.append((kind, s, m, plain))
-    ranks, roff = pack(reads)
-    ranks.setflags(write=False)
-    roff.setflags(write=False)
-    return ranks, roff, meta
 
 
 @pytest.fixture(scope="module")
@@ -306,7 +257,7 @@ def test_vote_on_a_device_form_result_and_device_view(engine, indexes):
     ptrs = loci.device_ptrs()
     sizes = (c["nr"] + 1, c["n_loci"], c["n_loci"], c["n_loci"], c["nr"])
     for name, ptr, n, x in zip(NAMES, ptrs, sizes, want[:5]):
-        got = device_array(torch, ptr, n, x.dtype)
+        got = dev_array(ptr, n, x.dtype)
         assert np.array_equal(got, x), name
     # search into the result again while the loci handle from it is alive, then read that handle
     few = pack([ranks[int(roff[i]):int(roff[i + 1])] for i in range(40)])
@@ -318,18 +269,6 @@ def test_vote_on_a_device_form_result_and_device_view(engine, indexes):
     other.close()
     loci.close()
     r.close()
-
-
-def device_array(torch, ptr, n, dtype):
-    if n == 0:
-        return np.zeros(0, dtype)
-
-    class _Arr:
-        def __init__(self):
-            self.__cuda_array_interface__ = {"shape": (int(n) * np.dtype(dtype).itemsize,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
-    out = torch.as_tensor(_Arr(), device="cuda").clone()
-    torch.cuda.synchronize()
-    return out.cpu().numpy().view(dtype)
 
 
 # ---- 6. refusals after looking at the handle -----------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from kmer_index_amd import synth
+from tests.chain_data import text_of
 from tests.helpers import make_queries, pack
 from tests.windows_naive import expand
 
@@ -17,14 +18,7 @@ N_READS = 3_000
 
 
 @functools.lru_cache(maxsize=None)
-def text_of(sigma, n=N_TEXT):
-    t = synth.ranks(7 + sigma, n, sigma)
-    t.setflags(write=False)
-    return t
-
-
-@functools.lru_cache(maxsize=None)
-def reads_of(sigma, n=N_TEXT, n_reads=N_READS, seed=1):
+def window_reads(sigma, n=N_TEXT, n_reads=N_READS, seed=1):
     """About n_reads reads of 0 .. 300 letters: every second one cut from the text (every 25th of those ends with the text's
     last letter), the others random; every 50th read (2 %) carries a letter >= sigma — sigma or 255 in turn — at its first
     letter, its last letter or in its middle in turn, so that it enters and leaves rolling windows."""
@@ -104,7 +98,7 @@ def test_every_table_layout(engine, name):
     assert info["tables"] == [engine.TABLE_OPEN if layout == "open" else engine.TABLE_DENSE]
     assert (paths["cell_shift"][0] != 0) == (layout == "cells") and (mem["cells"] != 0) == (layout == "cells")
     assert (mem["aligned_copy"] != 0) == (layout == "atab")
-    ranks, roff = reads_of(sigma, n)
+    ranks, roff = window_reads(sigma, n)
     for stride in (1, 3):
         want, _ = check(engine, idx, ranks, roff, k, stride)
         # DNA4 k = 5 has 1 024 keys for 100 000 letters: every key occurs, no valid window is without a hit
@@ -117,7 +111,7 @@ def test_every_table_layout(engine, name):
 def test_wide_hashes(engine, sigma, k):
     idx = engine.Index(text_of(sigma), sigma, [k])
     assert idx.info()["tables"] == [engine.TABLE_OPEN]
-    ranks, roff = reads_of(sigma)
+    ranks, roff = window_reads(sigma)
     for stride in (1, 3):
         want, _ = check(engine, idx, ranks, roff, k, stride)
         assert_not_vacuous(engine, want)
@@ -127,7 +121,7 @@ def test_wide_hashes(engine, sigma, k):
 # ---- 3. multi-k ------------------------------------------------------------------------------------------------------------
 def test_multi_k_index(engine):
     idx = engine.Index(text_of(4), 4, [8, 10, 12])
-    ranks, roff = reads_of(4)
+    ranks, roff = window_reads(4)
     for w in (8, 10, 12):
         want, _ = check(engine, idx, ranks, roff, w, 1)
         assert_not_vacuous(engine, want)
@@ -147,7 +141,7 @@ def dna10(engine):
 
 @pytest.mark.parametrize("stride", [1, 2, 9, 10, 13, 301])
 def test_strides(engine, dna10, stride):
-    ranks, roff = reads_of(4)
+    ranks, roff = window_reads(4)
     want, r = check(engine, dna10, ranks, roff, 10, stride)
     if stride == 301:                                        # larger than every read: one window per read of 10 letters or more
         lens = np.diff(roff.astype(np.int64))
@@ -165,7 +159,7 @@ def test_no_windows_at_all(engine, dna10):
     r = dna10.search_windows(np.zeros(0, np.uint8), np.zeros(1, np.uint64), 10, result=r)      # nr == 0
     assert r.counts()["nq"] == 0 and r.host()[0].tolist() == [0] and r.window_offsets().tolist() == [0]
     # ... and the handle serves a real batch afterwards
-    check(engine, dna10, *reads_of(4), 10, 1, result=r)
+    check(engine, dna10, *window_reads(4), 10, 1, result=r)
 
 
 # ---- 5. tile edges ---------------------------------------------------------------------------------------------------------
@@ -201,7 +195,7 @@ def test_tile_edges(engine, dna10):
 
 # ---- 6. count only ---------------------------------------------------------------------------------------------------------
 def test_count_only(engine, dna10):
-    ranks, roff = reads_of(4)
+    ranks, roff = window_reads(4)
     want, win = reference(dna10, ranks, roff, 10, 1, flags=engine.SEARCH_COUNT_ONLY)
     r = dna10.search_windows(ranks, roff, 10, 1, flags=engine.SEARCH_COUNT_ONLY)
     got = r.host()
@@ -238,7 +232,7 @@ def test_device_form_and_handle_reuse(engine):
         assert np.array_equal(dev.cpu().numpy().view(np.uint64), win)
         return r
 
-    ranks, roff = reads_of(4)
+    ranks, roff = window_reads(4)
     some = pack([ranks[int(roff[i]):int(roff[i + 1])] for i in range(0, 1200)])
     few = pack([ranks[int(roff[i]):int(roff[i + 1])] for i in range(1200, 1500)])
     r = windows(some, 10, 1, None)
@@ -270,7 +264,7 @@ def engine_copy(torch, dst, src_ptr, nbytes):
 
 # ---- 8. stats --------------------------------------------------------------------------------------------------------------
 def test_stats_name(engine, dna10):
-    ranks, roff = reads_of(4)
+    ranks, roff = window_reads(4)
     dna10.stats_enable(True)
     dna10.stats_reset()
     dna10.search(*expand(ranks, roff, 10, 7)[:2])

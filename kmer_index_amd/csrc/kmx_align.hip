@@ -263,24 +263,23 @@ struct kmx_alignments {
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t nr = 0, n_loci = 0, n_aligned = 0, n_skipped = 0;
     uint64_t nc = 0, ctg_gen = 0;          // the contig table of the index the call saw: its contigs (0: none) and its generation
-    // results; ctg is only filled when nc > 0
-    Buf dist, start, end, best, aligned, ctg;
+    // results; best and aligned are handed out whatever the handle holds; ctg is only filled when nc > 0 and has a pair of views of its own
+    kmx::ArrOf<uint8_t> dist;
+    kmx::ArrOf<uint32_t> start, end, best, aligned, ctg{kmx::ARR_OWN_VIEW};
     // scratch
     Buf ranks, roff, pcnt, peq_off, bsum, peq, lread, cls, list, alist, ctr;
-    Pinned h_ctr, h_dist, h_start, h_end, h_best, h_aligned, h_ctg;
+    Pinned h_ctr;
     bool host_valid = false, host_ctg_valid = false;
-    void release()
-    {
-        for (Buf* b : {&dist, &start, &end, &best, &aligned, &ctg, &ranks, &roff, &pcnt, &peq_off, &bsum, &peq, &lread, &cls, &list, &alist, &ctr}) b->release();
-        for (Pinned* b : {&h_ctr, &h_dist, &h_start, &h_end, &h_best, &h_aligned, &h_ctg}) b->release();
-    }
-    void clear() { nr = n_loci = n_aligned = n_skipped = nc = ctg_gen = 0; host_valid = host_ctg_valid = false; }
+    std::vector<kmx::Arr*> results() { return {&dist, &start, &end, &best, &aligned, &ctg}; }
+    std::vector<Buf*> scratch() { return {&ranks, &roff, &pcnt, &peq_off, &bsum, &peq, &lread, &cls, &list, &alist, &ctr}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { nr = n_loci = n_aligned = n_skipped = nc = ctg_gen = 0; kmx::clear_arrays(*this); host_ctg_valid = false; }
 };
 
 kmx::AlignAccess kmx::alignments_access(const kmx_alignments* a)
 {
     return AlignAccess{a->device, a->stream, a->nr, a->n_loci, a->dist.as<uint8_t>(), a->start.as<uint32_t>(), a->end.as<uint32_t>(),
-                       a->best.as<uint32_t>(), a->nc && a->n_loci ? a->ctg.as<uint32_t>() : nullptr, a->nc, a->ctg_gen};
+                       a->best.as<uint32_t>(), a->ctg.dev(), a->nc, a->ctg_gen};
 }
 
 namespace {
@@ -300,14 +299,11 @@ kmx_status align_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const 
                      const kmx_align_options& o, hipStream_t s, kmx_alignments* a)
 {
     const uint64_t nr = L.nr, nl = L.n_loci;
-    a->stream = s;
-    a->clear();
     a->nc = X.ctg_off ? X.nc : 0;
     a->ctg_gen = X.ctg_gen;
-    (void)hipGetLastError();
     TRY_HIP(a->best.ensure(std::max<uint64_t>(nr, 1) * 4));
     TRY_HIP(a->aligned.ensure(std::max<uint64_t>(nr, 1) * 4));
-    a->nr = nr;
+    a->nr = a->best.n = a->aligned.n = nr;
     if (nr == 0) return KMX_OK;
     if (nl == 0) {                                             // no locus: no launch indexes an empty array
         TRY_HIP(hipMemsetAsync(a->best.p, 0xFF, nr * 4, s));
@@ -373,6 +369,8 @@ kmx_status align_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const 
     TRY_HIP(hipGetLastError());
     TRY_KMX(kmx::read_back("kmx_loci_align", s, ctr, a->h_ctr, CTR_COUNT * 8));
     a->n_loci = nl;
+    kmx::expose({&a->dist, &a->start, &a->end}, nl);
+    if (a->nc) a->ctg.n = nl;
     a->n_aligned = a->h_ctr.as<uint64_t>()[CTR_N_ALIGNED];
     a->n_skipped = a->h_ctr.as<uint64_t>()[CTR_N_SKIPPED];
     return KMX_OK;
@@ -401,10 +399,7 @@ kmx_status align_call(const char* fn, const kmx_index* index, const kmx_loci* lo
     const std::string who = std::string(fn) + ": ";
     const kmx::LociAccess L = kmx::loci_access(loci);
     kmx_alignments* a = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (a) a->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, a);
     if (nr != L.nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "nr differs from the loci handle's");
     kmx::IndexAccess X{};
     kmx_status no_st;
@@ -419,17 +414,17 @@ kmx_status align_call(const char* fn, const kmx_index* index, const kmx_loci* lo
     TRY_KMX(kmx::bind_handle(inout, L.device));
     a = *inout;
     hipStream_t s = host ? L.stream : stream;
-    kmx_status st = KMX_OK;
-    const void* d_ranks = ranks;
-    const void* d_roff = roff;
-    if (host && nr && L.n_loci) {
-        st = kmx::upload_reads(ranks, roff, nr, n_letters, a->ranks, a->roff, s);
-        d_ranks = a->ranks.p;
-        d_roff = a->roff.p;
-    }
-    if (st == KMX_OK) st = align_run(X, L, d_ranks, d_roff, n_letters, *o, s, a);
-    if (host || st != KMX_OK) (void)hipStreamSynchronize(s);   // the caller's arrays are free again; a failed call leaves nothing in flight
-    if (st != KMX_OK) a->clear();                              // the handle holds an empty result, not half of this one
+    const kmx_status st = kmx::run_into(a, s, [&] {
+        const void* d_ranks = ranks;
+        const void* d_roff = roff;
+        if (host && nr && L.n_loci) {
+            TRY_KMX(kmx::upload_reads(ranks, roff, nr, n_letters, a->ranks, a->roff, s));
+            d_ranks = a->ranks.p;
+            d_roff = a->roff.p;
+        }
+        return align_run(X, L, d_ranks, d_roff, n_letters, *o, s, a);
+    });
+    if (host && st == KMX_OK) (void)hipStreamSynchronize(s);   // the caller's arrays are free again
     return st;
 }
 
@@ -463,9 +458,9 @@ kmx_status kmx_alignments_view_device(const kmx_alignments* a, const uint8_t** d
                                       const uint32_t** d_best, const uint32_t** d_aligned)
 {
     if (!a) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_alignments_view_device: alignments handle is NULL");
-    if (d_dist) *d_dist = a->n_loci ? a->dist.as<uint8_t>() : nullptr;
-    if (d_start) *d_start = a->n_loci ? a->start.as<uint32_t>() : nullptr;
-    if (d_end) *d_end = a->n_loci ? a->end.as<uint32_t>() : nullptr;
+    if (d_dist) *d_dist = a->dist.dev();
+    if (d_start) *d_start = a->start.dev();
+    if (d_end) *d_end = a->end.dev();
     if (d_best) *d_best = a->best.as<uint32_t>();
     if (d_aligned) *d_aligned = a->aligned.as<uint32_t>();
     return KMX_OK;
@@ -475,25 +470,19 @@ kmx_status kmx_alignments_view(kmx_alignments* a, const uint8_t** dist, const ui
                                const uint32_t** aligned)
 {
     if (!a) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_alignments_view: alignments handle is NULL");
-    if (!a->host_valid) {
-        const uint64_t nr = a->nr, nl = a->n_loci;
-        const kmx::HostCopy items[] = {{a->h_dist, a->dist, nl, 1}, {a->h_start, a->start, nl, 4}, {a->h_end, a->end, nl, 4},
-                                       {a->h_best, a->best, nr, 4}, {a->h_aligned, a->aligned, nr, 4}};
-        TRY_KMX(kmx::host_view("kmx_alignments_view", a->device, a->stream, items, std::size(items)));
-        a->host_valid = true;
-    }
-    if (dist) *dist = a->h_dist.as<uint8_t>();
-    if (start) *start = a->h_start.as<uint32_t>();
-    if (end) *end = a->h_end.as<uint32_t>();
-    if (best) *best = a->h_best.as<uint32_t>();
-    if (aligned) *aligned = a->h_aligned.as<uint32_t>();
+    TRY_KMX(kmx::host_view("kmx_alignments_view", *a));
+    if (dist) *dist = a->dist.host();
+    if (start) *start = a->start.host();
+    if (end) *end = a->end.host();
+    if (best) *best = a->best.host();
+    if (aligned) *aligned = a->aligned.host();
     return KMX_OK;
 }
 
 kmx_status kmx_alignments_contigs_view_device(const kmx_alignments* a, const uint32_t** d_ctg, uint64_t* nc)
 {
     if (!a) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_alignments_contigs_view_device: alignments handle is NULL");
-    if (d_ctg) *d_ctg = a->nc && a->n_loci ? a->ctg.as<uint32_t>() : nullptr;
+    if (d_ctg) *d_ctg = a->ctg.dev();
     if (nc) *nc = a->nc;
     return KMX_OK;
 }
@@ -507,11 +496,10 @@ kmx_status kmx_alignments_contigs_view(kmx_alignments* a, const uint32_t** ctg, 
         return KMX_OK;
     }
     if (!a->host_ctg_valid) {                                  // 4 bytes per locus
-        const kmx::HostCopy items[] = {{a->h_ctg, a->ctg, a->n_loci, 4}};
-        TRY_KMX(kmx::host_view("kmx_alignments_contigs_view", a->device, a->stream, items, 1));
+        TRY_KMX(kmx::copy_to_host("kmx_alignments_contigs_view", a->device, a->stream, {&a->ctg}));
         a->host_ctg_valid = true;
     }
-    if (ctg) *ctg = a->h_ctg.as<uint32_t>();
+    if (ctg) *ctg = a->ctg.host();
     return KMX_OK;
 }
 

@@ -1264,7 +1264,7 @@ static kmx_status approx_search(const char* fn, const kmx_index* index, const ui
     TRY_KMX(check_queries(who, qranks, qoff, nq));
     *out = nullptr;
     const kmx::IndexAccess A = kmx::index_access(index);
-    if (A.broken) return kmx::set_error(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    if (A.broken) return kmx::set_error(KMX_ERR_HIP, kmx::kIndexUnusable);
     const uint32_t e = max_subst, E1 = e + 1;
     const uint32_t S = complement ? 2u : 1u;             // internal queries per query (both strands: q and rc(q))
     uint8_t comp[256];

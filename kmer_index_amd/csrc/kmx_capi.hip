@@ -1263,7 +1263,7 @@ kmx_status kmx_index_set_contigs(kmx_index* ix, const uint64_t* ctg_off, uint64_
             if (ctg_off[c + 1] <= ctg_off[c]) return fail(KMX_ERR_INVALID_ARGUMENT, who + "ctg_off must be strictly ascending (contig " + std::to_string(c) + " is empty)");
         if (ctg_off[nc] != ix->n) return fail(KMX_ERR_INVALID_ARGUMENT, who + "ctg_off[nc] must be the text length");
     }
-    if (ix->broken) return fail(KMX_ERR_HIP, who + "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    if (ix->broken) return fail(KMX_ERR_HIP, who + kmx::kIndexUnusable);
     int cur = 0;
     const bool have_cur = hipGetDevice(&cur) == hipSuccess;
     if (!have_cur) (void)hipGetLastError();
@@ -1573,7 +1573,7 @@ static kmx_status search_device_begin(const kmx_index* cix, const void* d_first,
 {
     const std::string f = std::string(fn) + ": ";
     kmx_index* ix = const_cast<kmx_index*>(cix);
-    if (ix->broken) return fail(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    if (ix->broken) return fail(KMX_ERR_HIP, kmx::kIndexUnusable);
     if (!ix->peers.empty() && nonempty) {
         // several replicas: the one that lives where the queries are
         hipPointerAttribute_t attr{};
@@ -2471,7 +2471,7 @@ kmx_status kmx_search_batch(const kmx_index* cix, const uint8_t* qranks, const u
         if (qoff[i + 1] < qoff[i]) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: qoff must be non-decreasing");
     if (nq && !qranks && qoff[nq] != 0) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: NULL query letters");   // (a batch of empty queries has none)
     kmx_index* ix = const_cast<kmx_index*>(cix);
-    if (ix->broken) return fail(KMX_ERR_HIP, "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent");
+    if (ix->broken) return fail(KMX_ERR_HIP, kmx::kIndexUnusable);
     if (ix->n_replicas() > 1) return search_host_replicas(ix, qranks, qoff, nq, flags, out);
     if (*out && !(*out)->parts.empty() && !(*out)->chunked) return fail(KMX_ERR_INVALID_ARGUMENT, "kmx_search_batch: the result handle belongs to a multi-device search");
     uint64_t chunk_q = uint64_t(1) << 25;                   // queries per pass; KMX_HOST_CHUNK overrides (tests)

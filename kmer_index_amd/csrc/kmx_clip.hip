@@ -197,16 +197,15 @@ kmx_status kmx_clips_view_device(const kmx_clips* h, const int32_t** d_score, co
                                  const uint32_t** d_cigar)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_clips_view_device: clips handle is NULL");
-    const bool any = h->n_sel != 0;
-    if (d_score) *d_score = any ? h->score.as<int32_t>() : nullptr;
-    if (d_sl) *d_sl = any ? h->sl.as<uint16_t>() : nullptr;
-    if (d_sr) *d_sr = any ? h->sr.as<uint16_t>() : nullptr;
-    if (d_tl) *d_tl = any ? h->tl.as<uint16_t>() : nullptr;
-    if (d_tr) *d_tr = any ? h->tr.as<uint16_t>() : nullptr;
-    if (d_nm) *d_nm = any ? h->nm.as<uint16_t>() : nullptr;
-    if (d_cflags) *d_cflags = any ? h->cflags.as<uint8_t>() : nullptr;
-    if (d_cig_off) *d_cig_off = h->filled ? h->cig_off.as<uint64_t>() : nullptr;
-    if (d_cigar) *d_cigar = h->n_ops ? h->cigar.as<uint32_t>() : nullptr;
+    if (d_score) *d_score = h->score.dev();
+    if (d_sl) *d_sl = h->sl.dev();
+    if (d_sr) *d_sr = h->sr.dev();
+    if (d_tl) *d_tl = h->tl.dev();
+    if (d_tr) *d_tr = h->tr.dev();
+    if (d_nm) *d_nm = h->nm.dev();
+    if (d_cflags) *d_cflags = h->cflags.dev();
+    if (d_cig_off) *d_cig_off = h->cig_off.dev();
+    if (d_cigar) *d_cigar = h->cigar.dev();
     return KMX_OK;
 }
 
@@ -214,25 +213,16 @@ kmx_status kmx_clips_view(kmx_clips* h, const int32_t** score, const uint16_t** 
                           const uint16_t** nm, const uint8_t** cflags, const uint64_t** cig_off, const uint32_t** cigar)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_clips_view: clips handle is NULL");
-    if (!h->host_valid) {                                      // 15 bytes per entry, 8 per entry for cig_off, 4 per run
-        const uint64_t ns = h->n_sel;
-        const bool f = h->filled;                              // else the empty result: one offset, 0
-        const kmx::HostCopy items[] = {{h->h_score, h->score, ns, 4}, {h->h_sl, h->sl, ns, 2}, {h->h_sr, h->sr, ns, 2}, {h->h_tl, h->tl, ns, 2},
-                                       {h->h_tr, h->tr, ns, 2}, {h->h_nm, h->nm, ns, 2}, {h->h_cflags, h->cflags, ns, 1},
-                                       {h->h_cig_off, h->cig_off, f ? ns + 1 : 0, 8}, {h->h_cigar, h->cigar, h->n_ops, 4}};
-        TRY_KMX(kmx::host_view("kmx_clips_view", h->device, h->stream, items, std::size(items)));
-        if (!f) h->h_cig_off.as<uint64_t>()[0] = 0;
-        h->host_valid = true;
-    }
-    if (score) *score = h->h_score.as<int32_t>();
-    if (sl) *sl = h->h_sl.as<uint16_t>();
-    if (sr) *sr = h->h_sr.as<uint16_t>();
-    if (tl) *tl = h->h_tl.as<uint16_t>();
-    if (tr) *tr = h->h_tr.as<uint16_t>();
-    if (nm) *nm = h->h_nm.as<uint16_t>();
-    if (cflags) *cflags = h->h_cflags.as<uint8_t>();
-    if (cig_off) *cig_off = h->h_cig_off.as<uint64_t>();
-    if (cigar) *cigar = h->h_cigar.as<uint32_t>();
+    TRY_KMX(kmx::host_view("kmx_clips_view", *h));             // 15 bytes per entry, 8 per entry for cig_off, 4 per run
+    if (score) *score = h->score.host();
+    if (sl) *sl = h->sl.host();
+    if (sr) *sr = h->sr.host();
+    if (tl) *tl = h->tl.host();
+    if (tr) *tr = h->tr.host();
+    if (nm) *nm = h->nm.host();
+    if (cflags) *cflags = h->cflags.host();
+    if (cig_off) *cig_off = h->cig_off.host();
+    if (cigar) *cigar = h->cigar.host();
     return KMX_OK;
 }
 

@@ -27,9 +27,12 @@ struct kmx_clips {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t n_sel = 0, n_ops = 0, n_clipped = 0, n_low = 0;
-    bool filled = false;                   // a call has succeeded since the last refusal or error: cig_off holds n_sel + 1 offsets
-    // results
-    kmx::Buf score, sl, sr, tl, tr, nm, cflags, cig_off, cigar;
+    // results: one entry per entry of the scripts, the offsets of their runs and the runs
+    kmx::ArrOf<int32_t> score;
+    kmx::ArrOf<uint16_t> sl, sr, tl, tr, nm;
+    kmx::ArrOf<uint8_t> cflags;
+    kmx::ArrOf<uint64_t> cig_off{kmx::ARR_OFFSETS};
+    kmx::ArrOf<uint32_t> cigar;
     // scratch of both fillers: the runs of every entry and the block sums of the scan that gives cig_off, the counters
     kmx::Buf cnt, bsum, ctr;
     // scratch of kmx_scripts_clip: the cuts
@@ -38,20 +41,24 @@ struct kmx_clips {
     // traceback codes of a chunk and the run reservations
     struct Realign {
         kmx::Buf ranks, roff, eread, estat, ecode, eres, code_off, res_off, end_i, end_j, end_v, arena, runs;
-        void release()
-        {
-            for (kmx::Buf* b : {&ranks, &roff, &eread, &estat, &ecode, &eres, &code_off, &res_off, &end_i, &end_j, &end_v, &arena, &runs}) b->release();
-        }
     } re;
-    kmx::PinnedArr h_ctr, h_score, h_sl, h_sr, h_tl, h_tr, h_nm, h_cflags, h_cig_off, h_cigar;
+    kmx::PinnedArr h_ctr;
     bool host_valid = false;
-    void release()
+    std::vector<kmx::Arr*> results() { return {&score, &sl, &sr, &tl, &tr, &nm, &cflags, &cig_off, &cigar}; }
+    std::vector<kmx::Buf*> scratch()
     {
-        for (kmx::Buf* b : {&score, &sl, &sr, &tl, &tr, &nm, &cflags, &cig_off, &cigar, &cnt, &bsum, &ctr, &cut_i, &cut_j}) b->release();
-        re.release();
-        for (kmx::PinnedArr* b : {&h_ctr, &h_score, &h_sl, &h_sr, &h_tl, &h_tr, &h_nm, &h_cflags, &h_cig_off, &h_cigar}) b->release();
+        return {&cnt, &bsum, &ctr, &cut_i, &cut_j, &re.ranks, &re.roff, &re.eread, &re.estat, &re.ecode, &re.eres, &re.code_off, &re.res_off, &re.end_i,
+                &re.end_j, &re.end_v, &re.arena, &re.runs};
     }
-    void clear() { n_sel = n_ops = n_clipped = n_low = 0; filled = false; host_valid = false; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { n_sel = n_ops = n_clipped = n_low = 0; kmx::clear_arrays(*this); }
+    // a filler has succeeded: the arrays expose what the counters say
+    void expose()
+    {
+        kmx::expose(results(), n_sel);
+        cig_off.n = n_sel + 1;
+        cigar.n = n_ops;
+    }
 
     // The steps of a filler, in this order.  begin: an empty result on stream s, then room for the per-entry arrays of ns entries, cnt
     // and bsum; with ns == 0 the one offset 0 is written and the handle is filled, and the filler is done.
@@ -63,11 +70,11 @@ struct kmx_clips {
         TRY_HIP(cig_off.ensure((ns + 1) * 8));
         if (ns == 0) {                                         // no entry: no launch indexes an empty array
             TRY_HIP(hipMemsetAsync(cig_off.p, 0, 8, s));
-            filled = true;
+            expose();
             return KMX_OK;
         }
         TRY_HIP(score.ensure(ns * 4));
-        for (kmx::Buf* b : {&sl, &sr, &tl, &tr, &nm}) TRY_HIP(b->ensure(ns * 2));
+        for (kmx::Arr* a : {&sl, &sr, &tl, &tr, &nm}) TRY_HIP(a->ensure(ns * 2));
         TRY_HIP(cflags.ensure(ns));
         TRY_HIP(cnt.ensure(ns * 4 + 16));
         TRY_HIP(bsum.ensure(kmx::scan_blocks(ns) * 8 + 16));
@@ -86,6 +93,6 @@ struct kmx_clips {
         n_ops = counts[kmx::CL_N_OPS];
         n_clipped = counts[kmx::CL_N_CLIPPED];
         n_low = counts[kmx::CL_N_LOW];
-        filled = true;
+        expose();
     }
 };

@@ -74,15 +74,14 @@ struct kmx_located {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t nr = 0, n_located = 0, n_mismatched = 0;
-    Buf ctg, pos, ctr;
-    Pinned h_ctr, h_ctg, h_pos;
+    kmx::ArrOf<uint32_t> ctg, pos;         // the results: one entry per public read
+    Buf ctr;
+    Pinned h_ctr;
     bool host_valid = false;
-    void release()
-    {
-        for (Buf* b : {&ctg, &pos, &ctr}) b->release();
-        for (Pinned* b : {&h_ctr, &h_ctg, &h_pos}) b->release();
-    }
-    void clear() { nr = n_located = n_mismatched = 0; host_valid = false; }
+    std::vector<kmx::Arr*> results() { return {&ctg, &pos}; }
+    std::vector<Buf*> scratch() { return {&ctr}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { nr = n_located = n_mismatched = 0; kmx::clear_arrays(*this); }
 };
 
 namespace {
@@ -90,9 +89,6 @@ namespace {
 kmx_status locate_run(const kmx::IndexAccess& X, const kmx::AlignAccess& A, const kmx_placements* pl, uint32_t flags, hipStream_t s, kmx_located* h)
 {
     const uint64_t nr = pl->nr;
-    h->stream = s;
-    h->clear();
-    (void)hipGetLastError();
     if (nr == 0) return KMX_OK;
     for (Buf* b : {&h->ctg, &h->pos}) TRY_HIP(b->ensure(nr * 4));
     TRY_HIP(h->ctr.ensure(LC_COUNT * 8));
@@ -103,7 +99,7 @@ kmx_status locate_run(const kmx::IndexAccess& X, const kmx::AlignAccess& A, cons
     hipLaunchKernelGGL(k_locate, dim3(grid_for(nr, kBlock)), dim3(kBlock), 0, s, Q, h->ctg.as<uint32_t>(), h->pos.as<uint32_t>(), ctr);
     TRY_HIP(hipGetLastError());
     TRY_KMX(kmx::read_back("kmx_placements_locate", s, ctr, h->h_ctr, LC_COUNT * 8));
-    h->nr = nr;
+    h->nr = h->ctg.n = h->pos.n = nr;
     h->n_located = h->h_ctr.as<uint64_t>()[LC_N_LOCATED];
     h->n_mismatched = h->h_ctr.as<uint64_t>()[LC_N_MISMATCHED];
     return KMX_OK;
@@ -124,10 +120,7 @@ kmx_status kmx_placements_locate(const kmx_index* index, const kmx_alignments* a
     if (o->flags & ~KMX_LOCATE_MATES) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "unknown flags");
     const kmx::AlignAccess A = kmx::alignments_access(alignments);
     kmx_located* h = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (h) h->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, h);
     if ((o->flags & KMX_LOCATE_MATES) && (placements->nr & 1)) return refuse(KMX_ERR_INVALID_ARGUMENT, "KMX_LOCATE_MATES with an odd number of reads: not interleaved mates");
     if (2 * placements->nr != A.nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "the placements are not those of these alignments: 2 nr differs from the alignments' nr");
     if (placements->nr && placements->device != A.device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments and the placements live on different devices");
@@ -142,12 +135,7 @@ kmx_status kmx_placements_locate(const kmx_index* index, const kmx_alignments* a
     TRY_KMX(kmx::bind_handle(inout, A.device));
     h = *inout;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : placements->stream;
-    const kmx_status st = locate_run(X, A, placements, o->flags, s, h);
-    if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
-        (void)hipStreamSynchronize(s);
-        h->clear();
-    }
-    return st;
+    return kmx::run_into(h, s, [&] { return locate_run(X, A, placements, o->flags, s, h); });
 }
 
 kmx_status kmx_located_counts(const kmx_located* h, uint64_t* nr, uint64_t* n_located, uint64_t* n_mismatched)
@@ -162,8 +150,8 @@ kmx_status kmx_located_counts(const kmx_located* h, uint64_t* nr, uint64_t* n_lo
 kmx_status kmx_located_view_device(const kmx_located* h, const uint32_t** d_ctg, const uint32_t** d_pos)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_located_view_device: located handle is NULL");
-    if (d_ctg) *d_ctg = h->nr ? h->ctg.as<uint32_t>() : nullptr;
-    if (d_pos) *d_pos = h->nr ? h->pos.as<uint32_t>() : nullptr;
+    if (d_ctg) *d_ctg = h->ctg.dev();
+    if (d_pos) *d_pos = h->pos.dev();
     return KMX_OK;
 }
 
@@ -175,13 +163,9 @@ kmx_status kmx_located_view(kmx_located* h, const uint32_t** ctg, const uint32_t
         if (pos) *pos = nullptr;
         return KMX_OK;
     }
-    if (!h->host_valid) {                                      // 8 bytes per read
-        const kmx::HostCopy items[] = {{h->h_ctg, h->ctg, h->nr, 4}, {h->h_pos, h->pos, h->nr, 4}};
-        TRY_KMX(kmx::host_view("kmx_located_view", h->device, h->stream, items, 2));
-        h->host_valid = true;
-    }
-    if (ctg) *ctg = h->h_ctg.as<uint32_t>();
-    if (pos) *pos = h->h_pos.as<uint32_t>();
+    TRY_KMX(kmx::host_view("kmx_located_view", *h));           // 8 bytes per read
+    if (ctg) *ctg = h->ctg.host();
+    if (pos) *pos = h->pos.host();
     return KMX_OK;
 }
 

@@ -4,7 +4,10 @@
 // kmx_supplementary.hip, kmx_realign.hip, kmx_pileup.hip).  The other private headers of the chain: kmx_vote.h (what a stage reads of
 // the handle before it), kmx_strands.h and kmx_clips.h (the handle structs that two sources fill), kmx_align_core.h,
 // kmx_script_core.h, kmx_runs.h and kmx_fold_core.h (device code that several sources compile).
-// A chain handle has the members `device`, `release()` (its buffers go, on its device) and `clear()` (an empty result).
+// A chain handle has the members `device`, `stream`, `host_valid` and `h_ctr`, declares its result arrays once, as Arr members and the list
+// `results()`, and its scratch buffers as the list `scratch()`; release_arrays, clear_arrays, the device view of an array (ArrOf::dev) and
+// host_view are derived from those lists here.  `release()` (its buffers go, on its device) and `clear()` (an empty result) stay the
+// handle's own: the scalar counters are per handle.  DESIGN.md 7l has one row per handle and array.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,6 +15,7 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "kmx_approx.h"
 #include "kmx_types.h"
@@ -43,6 +47,9 @@ kmx_status check_call(const std::string& who, const O* o, const void* inout)
     return KMX_OK;
 }
 
+// the refusal of an index whose replicas a failed extension has left apart (kmx_capi.hip and kmx_approx.hip word theirs differently)
+inline constexpr const char* kIndexUnusable = "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent";
+
 // *X = the replica of `index` on `device`, where `whose` ("the scripts", "the loci", ...) live; false: there is none, or the index is
 // broken, and (*st, *why) is the refusal
 inline bool index_for(const kmx_index* index, int device, const char* whose, IndexAccess* X, kmx_status* st, std::string* why)
@@ -54,7 +61,7 @@ inline bool index_for(const kmx_index* index, int device, const char* whose, Ind
     }
     if (X->broken) {
         *st = KMX_ERR_HIP;
-        *why = "the index is unusable: a failed kmx_index_extend_query_size_range left its replicas inconsistent";
+        *why = kIndexUnusable;
         return false;
     }
     return true;
@@ -177,30 +184,107 @@ void free_handle(H* h)
     delete h;
 }
 
-// One array of a host view: room for max(count, 1) elements of `elem` bytes in h, and the first `count` of d copied there.
-struct HostCopy {
-    PinnedArr& h;
-    const Buf& d;
-    uint64_t count;
-    uint32_t elem;
+// One result array of a chain handle.  It is its grow-only device buffer (ensure(), p and as<T>() as for any Buf: what the kernels of a run
+// take), and holds the page-locked host copy and the live count n, the elements the handle exposes now: 0 after clear().  Room and live
+// count are apart: ensure() only grows the device buffer, n is set when the fill has succeeded.
+enum : uint32_t {
+    ARR_OFFSETS = 1,       // an offset array (u64): while it exposes nothing its host view holds the one offset 0
+    ARR_OWN_VIEW = 2,      // copied to the host by a view of its own, not with the handle's other arrays
+};
+struct Arr : Buf {
+    PinnedArr h;
+    const uint32_t elem;   // bytes per element
+    const uint32_t flags;  // ARR_*
+    uint64_t n = 0;
+    Arr(uint32_t elem, uint32_t flags) : elem(elem), flags(flags) {}
+    void release() { Buf::release(); h.release(); n = 0; }
+};
+// ... of elements T: the typed views
+template <typename T>
+struct ArrOf : Arr {
+    explicit ArrOf(uint32_t flags = 0) : Arr(sizeof(T), flags) {}
+    const T* dev() const { return n ? as<T>() : nullptr; }     // the device view: NULL while the array exposes nothing
+    const T* host() const { return h.as<T>(); }                // the host view behind host_view(): never NULL
 };
 
-// Grows every array (a failure refuses before any copy), then copies on stream s of `device` and synchronises once.
-inline kmx_status host_view(const char* fn, int device, hipStream_t s, const HostCopy* items, size_t n)
+inline void expose(const std::vector<Arr*>& arrs, uint64_t n) { for (Arr* a : arrs) a->n = n; }
+
+// what release() and clear() of a handle H do about its arrays
+template <typename H>
+void release_arrays(H& h)
+{
+    for (Arr* a : h.results()) a->release();
+    for (Buf* b : h.scratch()) b->release();
+    h.h_ctr.release();
+}
+template <typename H>
+void clear_arrays(H& h)
+{
+    for (Arr* a : h.results()) a->n = 0;
+    h.host_valid = false;
+}
+
+// The live elements of every array to its host copy: room for max(n, 1) elements each first (a failure refuses before any copy; the
+// host pointers are never NULL), then the copies on stream s of `device` and one synchronisation.  fn: the entry point, for the text.
+inline kmx_status copy_to_host(const char* fn, int device, hipStream_t s, const std::vector<Arr*>& arrs)
 {
     bool any = false;
-    for (const HostCopy* c = items; c != items + n; ++c) {
-        if (!c->h.grow(std::max<uint64_t>(c->count, 1) * c->elem))
+    for (Arr* a : arrs) {
+        if (!a->h.grow(std::max<uint64_t>(a->n, 1) * a->elem))
             return set_error(KMX_ERR_OUT_OF_MEMORY, std::string(fn) + ": page-locked host allocation failed");
-        any = any || c->count;
+        if ((a->flags & ARR_OFFSETS) && !a->n) a->h.as<uint64_t>()[0] = 0;
+        any = any || a->n;
     }
     if (!any) return KMX_OK;
     DeviceGuard dg;
     TRY_HIP(hipSetDevice(device));
-    for (const HostCopy* c = items; c != items + n; ++c)
-        if (c->count) TRY_HIP(hipMemcpyAsync(c->h.p, c->d.p, c->count * c->elem, hipMemcpyDeviceToHost, s));
+    for (Arr* a : arrs)
+        if (a->n) TRY_HIP(hipMemcpyAsync(a->h.p, a->p, a->n * a->elem, hipMemcpyDeviceToHost, s));
     TRY_HIP(hipStreamSynchronize(s));
     return KMX_OK;
+}
+
+// The host view of a handle: unless it is valid, every result array without a view of its own; `also`: one more array, whatever the
+// handle's view holds (the caller keeps that array's validity)
+template <typename H>
+kmx_status host_view(const char* fn, H& h, Arr* also = nullptr)
+{
+    std::vector<Arr*> arrs;
+    if (!h.host_valid)
+        for (Arr* a : h.results())
+            if (!(a->flags & ARR_OWN_VIEW)) arrs.push_back(a);
+    if (also) arrs.push_back(also);
+    if (arrs.empty()) return KMX_OK;
+    TRY_KMX(copy_to_host(fn, h.device, h.stream, arrs));
+    h.host_valid = true;
+    return KMX_OK;
+}
+
+// The refusals of the entry point `who` behind its first ones, once it has looked at the handle h (nullptr: there is none yet): the handle
+// holds an empty result.  who and h are the caller's variables, read when the refusal is made.
+template <typename H>
+auto refuser(const std::string& who, H*& h)
+{
+    return [&who, &h](kmx_status st, const std::string& msg) {
+        if (h) h->clear();
+        return set_error(st, who + msg);
+    };
+}
+
+// The step an entry point ends in: the handle takes stream s and holds an empty result, the sticky HIP error goes, the stage runs; when
+// it fails nothing is left in flight and the handle holds an empty result again, not half of this one.
+template <typename H, typename F>
+kmx_status run_into(H* h, hipStream_t s, F&& stage)
+{
+    h->stream = s;
+    h->clear();
+    (void)hipGetLastError();
+    const kmx_status st = stage();
+    if (st != KMX_OK) {
+        (void)hipStreamSynchronize(s);
+        h->clear();
+    }
+    return st;
 }
 
 } // namespace kmx

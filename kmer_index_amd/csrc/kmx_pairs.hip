@@ -188,7 +188,7 @@ kmx_status pair_fold_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, co
     TRY_HIP(pl->room(2 * np));
     TRY_HIP(pr->cls.ensure(np));
     TRY_HIP(pr->tlen.ensure(np * 4));
-    for (Buf* b : {&pr->score, &pr->second_score}) TRY_HIP(b->ensure(np * 2));
+    for (kmx::Arr* a : {&pr->score, &pr->second_score}) TRY_HIP(a->ensure(np * 2));
     TRY_HIP(pr->ctr.ensure(CTR_COUNT * 8));
     unsigned long long* ctr = pr->ctr.as<unsigned long long>();
     TRY_HIP(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
@@ -201,9 +201,9 @@ kmx_status pair_fold_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, co
     TRY_HIP(hipGetLastError());
     TRY_KMX(kmx::read_back("kmx_alignments_fold_pairs", s, ctr, pr->h_ctr, CTR_COUNT * 8));
     const uint64_t* h = pr->h_ctr.as<uint64_t>();
-    pl->nr = 2 * np;
+    pl->expose(2 * np);
     pl->counts_from(h);
-    pr->np = np;
+    pr->expose(np);
     pr->counts_from(h);
     return KMX_OK;
 }
@@ -276,27 +276,21 @@ kmx_status kmx_pairs_view_device(const kmx_pairs* p, const uint8_t** d_cls, cons
                                  const uint16_t** d_second_score)
 {
     if (!p) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_pairs_view_device: pairs handle is NULL");
-    const bool any = p->np != 0;
-    if (d_cls) *d_cls = any ? p->cls.as<uint8_t>() : nullptr;
-    if (d_tlen) *d_tlen = any ? p->tlen.as<int32_t>() : nullptr;
-    if (d_score) *d_score = any ? p->score.as<uint16_t>() : nullptr;
-    if (d_second_score) *d_second_score = any ? p->second_score.as<uint16_t>() : nullptr;
+    if (d_cls) *d_cls = p->cls.dev();
+    if (d_tlen) *d_tlen = p->tlen.dev();
+    if (d_score) *d_score = p->score.dev();
+    if (d_second_score) *d_second_score = p->second_score.dev();
     return KMX_OK;
 }
 
 kmx_status kmx_pairs_view(kmx_pairs* p, const uint8_t** cls, const int32_t** tlen, const uint16_t** score, const uint16_t** second_score)
 {
     if (!p) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_pairs_view: pairs handle is NULL");
-    if (!p->host_valid) {                                      // 9 bytes per pair
-        const kmx::HostCopy items[] = {{p->h_tlen, p->tlen, p->np, 4}, {p->h_score, p->score, p->np, 2}, {p->h_second_score, p->second_score, p->np, 2},
-                                       {p->h_cls, p->cls, p->np, 1}};
-        TRY_KMX(kmx::host_view("kmx_pairs_view", p->device, p->stream, items, 4));
-        p->host_valid = true;
-    }
-    if (cls) *cls = p->h_cls.as<uint8_t>();
-    if (tlen) *tlen = p->h_tlen.as<int32_t>();
-    if (score) *score = p->h_score.as<uint16_t>();
-    if (second_score) *second_score = p->h_second_score.as<uint16_t>();
+    TRY_KMX(kmx::host_view("kmx_pairs_view", *p));             // 9 bytes per pair
+    if (cls) *cls = p->cls.host();
+    if (tlen) *tlen = p->tlen.host();
+    if (score) *score = p->score.host();
+    if (second_score) *second_score = p->second_score.host();
     return KMX_OK;
 }
 

@@ -298,17 +298,15 @@ struct kmx_pileup {
     hipStream_t stream = nullptr;          // the stream of the last call (the views and the counts synchronise on it)
     uint64_t lo = 0, hi = 0;
     uint32_t n_channels = 0, sigma = 0;    // n_channels == 0: the handle holds nothing
-    Buf counts, ctr;
-    // scratch of a call: the verdicts
-    Buf verdict, read, c0, c1;
-    Pinned h_ctr, h_counts;
+    kmx::ArrOf<uint32_t> counts;           // the result: cells() counters, kept across a KMX_PILEUP_ADD call and its refusals
+    // the counters (read back on demand: kmx_pileup_counts), and the scratch of a call: the verdicts
+    Buf ctr, verdict, read, c0, c1;
+    Pinned h_ctr;
     bool host_valid = false;
-    void release()
-    {
-        for (Buf* b : {&counts, &ctr, &verdict, &read, &c0, &c1}) b->release();
-        for (Pinned* b : {&h_ctr, &h_counts}) b->release();
-    }
-    void clear() { lo = hi = 0; n_channels = sigma = 0; host_valid = false; }
+    std::vector<kmx::Arr*> results() { return {&counts}; }
+    std::vector<Buf*> scratch() { return {&ctr, &verdict, &read, &c0, &c1}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { lo = hi = 0; n_channels = sigma = 0; kmx::clear_arrays(*this); }
     uint64_t cells() const { return uint64_t(n_channels) * (hi - lo); }
 };
 
@@ -317,15 +315,16 @@ struct kmx_sites {
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t n_sites = 0, n_covered = 0;
     bool with_ctg = false;
-    Buf pos, ref, alt, depth, count, ref_count, ctg, cnt, off, bsum, ctr;
-    Pinned h_ctr, h_pos, h_ref, h_alt, h_depth, h_count, h_ref_count, h_ctg;
+    // results: one entry per record; ctg only when the index has a contig table
+    kmx::ArrOf<uint32_t> pos, depth, count, ref_count, ctg;
+    kmx::ArrOf<uint8_t> ref, alt;
+    Buf cnt, off, bsum, ctr;
+    Pinned h_ctr;
     bool host_valid = false;
-    void release()
-    {
-        for (Buf* b : {&pos, &ref, &alt, &depth, &count, &ref_count, &ctg, &cnt, &off, &bsum, &ctr}) b->release();
-        for (Pinned* b : {&h_ctr, &h_pos, &h_ref, &h_alt, &h_depth, &h_count, &h_ref_count, &h_ctg}) b->release();
-    }
-    void clear() { n_sites = n_covered = 0; with_ctg = false; host_valid = false; }
+    std::vector<kmx::Arr*> results() { return {&pos, &ref, &alt, &depth, &count, &ref_count, &ctg}; }
+    std::vector<Buf*> scratch() { return {&cnt, &off, &bsum, &ctr}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { n_sites = n_covered = 0; with_ctg = false; kmx::clear_arrays(*this); }
 };
 
 namespace {
@@ -417,6 +416,7 @@ kmx_status pileup_on_arrays(const char* fn, const kmx_index* index, const kmx::S
             h->hi = hi;
             h->sigma = X.sigma;
             h->n_channels = n_channels;
+            h->counts.n = h->cells();
         }
         const PileIn P{S.sel, K ? K->cig_off : S.cig_off, K ? K->cigar : S.cigar, start, end, S.read_sel_off, static_cast<const uint8_t*>(R.ranks),
                        static_cast<const uint64_t*>(R.roff), K ? K->tl : nullptr, K ? K->tr : nullptr, K ? K->score : nullptr, K ? K->cflags : nullptr,
@@ -433,9 +433,6 @@ kmx_status pileup_on_arrays(const char* fn, const kmx_index* index, const kmx::S
 
 kmx_status sites_run(const kmx::IndexAccess& X, const kmx_pileup* p, const kmx_sites_options& o, hipStream_t s, kmx_sites* h)
 {
-    h->stream = s;
-    h->clear();
-    (void)hipGetLastError();
     TRY_KMX(kmx::ensure_text(X, s));
     const uint64_t len = p->hi - p->lo;
     TRY_HIP(h->cnt.ensure(len * 4 + 16));
@@ -463,6 +460,8 @@ kmx_status sites_run(const kmx::IndexAccess& X, const kmx_pileup* p, const kmx_s
         TRY_HIP(hipGetLastError());
     }
     h->n_sites = n_sites;
+    kmx::expose(h->results(), n_sites);
+    if (!with_ctg) h->ctg.n = 0;
     h->n_covered = h->h_ctr.as<uint64_t>()[SI_N_COVERED];
     h->with_ctg = with_ctg;
     return KMX_OK;
@@ -528,7 +527,7 @@ kmx_status kmx_pileup_counts(kmx_pileup* p, uint64_t* lo, uint64_t* hi, uint32_t
 kmx_status kmx_pileup_view_device(const kmx_pileup* p, const uint32_t** d_counts)
 {
     if (!p) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_pileup_view_device: pileup handle is NULL");
-    if (d_counts) *d_counts = p->n_channels ? p->counts.as<uint32_t>() : nullptr;
+    if (d_counts) *d_counts = p->counts.dev();
     return KMX_OK;
 }
 
@@ -539,12 +538,8 @@ kmx_status kmx_pileup_view(kmx_pileup* p, const uint32_t** counts)
         if (counts) *counts = nullptr;
         return KMX_OK;
     }
-    if (!p->host_valid) {                                      // 4 bytes per channel and position
-        const kmx::HostCopy items[] = {{p->h_counts, p->counts, p->cells(), 4}};
-        TRY_KMX(kmx::host_view("kmx_pileup_view", p->device, p->stream, items, 1));
-        p->host_valid = true;
-    }
-    if (counts) *counts = p->h_counts.as<uint32_t>();
+    TRY_KMX(kmx::host_view("kmx_pileup_view", *p));            // 4 bytes per channel and position
+    if (counts) *counts = p->counts.host();
     return KMX_OK;
 }
 
@@ -559,10 +554,7 @@ kmx_status kmx_pileup_sites(const kmx_index* index, const kmx_pileup* pileup, co
     if (!index) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "index is NULL");
     if (!pileup) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "pileup handle is NULL");
     kmx_sites* h = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (h) h->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, h);
     if (pileup->n_channels == 0) return refuse(KMX_ERR_INVALID_ARGUMENT, "the pileup holds nothing");
     kmx::IndexAccess X{};
     kmx_status no_st;
@@ -573,12 +565,7 @@ kmx_status kmx_pileup_sites(const kmx_index* index, const kmx_pileup* pileup, co
     TRY_KMX(kmx::bind_handle(inout, pileup->device));
     h = *inout;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : pileup->stream;
-    const kmx_status st = sites_run(X, pileup, *o, s, h);
-    if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
-        (void)hipStreamSynchronize(s);
-        h->clear();
-    }
-    return st;
+    return kmx::run_into(h, s, [&] { return sites_run(X, pileup, *o, s, h); });
 }
 
 kmx_status kmx_sites_counts(const kmx_sites* h, uint64_t* n_sites, uint64_t* n_covered)
@@ -593,14 +580,13 @@ kmx_status kmx_sites_view_device(const kmx_sites* h, const uint32_t** d_pos, con
                                  const uint32_t** d_count, const uint32_t** d_ref_count, const uint32_t** d_ctg)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_sites_view_device: sites handle is NULL");
-    const bool any = h->n_sites != 0;
-    if (d_pos) *d_pos = any ? h->pos.as<uint32_t>() : nullptr;
-    if (d_ref) *d_ref = any ? h->ref.as<uint8_t>() : nullptr;
-    if (d_alt) *d_alt = any ? h->alt.as<uint8_t>() : nullptr;
-    if (d_depth) *d_depth = any ? h->depth.as<uint32_t>() : nullptr;
-    if (d_count) *d_count = any ? h->count.as<uint32_t>() : nullptr;
-    if (d_ref_count) *d_ref_count = any ? h->ref_count.as<uint32_t>() : nullptr;
-    if (d_ctg) *d_ctg = any && h->with_ctg ? h->ctg.as<uint32_t>() : nullptr;
+    if (d_pos) *d_pos = h->pos.dev();
+    if (d_ref) *d_ref = h->ref.dev();
+    if (d_alt) *d_alt = h->alt.dev();
+    if (d_depth) *d_depth = h->depth.dev();
+    if (d_count) *d_count = h->count.dev();
+    if (d_ref_count) *d_ref_count = h->ref_count.dev();
+    if (d_ctg) *d_ctg = h->ctg.dev();
     return KMX_OK;
 }
 
@@ -608,21 +594,14 @@ kmx_status kmx_sites_view(kmx_sites* h, const uint32_t** pos, const uint8_t** re
                           const uint32_t** count, const uint32_t** ref_count, const uint32_t** ctg)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_sites_view: sites handle is NULL");
-    if (!h->host_valid) {                                      // 18 bytes per record, 22 with ctg
-        const uint64_t n = h->n_sites;
-        const kmx::HostCopy items[] = {{h->h_pos, h->pos, n, 4},     {h->h_ref, h->ref, n, 1},     {h->h_alt, h->alt, n, 1},
-                                       {h->h_depth, h->depth, n, 4}, {h->h_count, h->count, n, 4}, {h->h_ref_count, h->ref_count, n, 4},
-                                       {h->h_ctg, h->ctg, h->with_ctg ? n : 0, 4}};
-        TRY_KMX(kmx::host_view("kmx_sites_view", h->device, h->stream, items, std::size(items)));
-        h->host_valid = true;
-    }
-    if (pos) *pos = h->h_pos.as<uint32_t>();
-    if (ref) *ref = h->h_ref.as<uint8_t>();
-    if (alt) *alt = h->h_alt.as<uint8_t>();
-    if (depth) *depth = h->h_depth.as<uint32_t>();
-    if (count) *count = h->h_count.as<uint32_t>();
-    if (ref_count) *ref_count = h->h_ref_count.as<uint32_t>();
-    if (ctg) *ctg = h->with_ctg ? h->h_ctg.as<uint32_t>() : nullptr;
+    TRY_KMX(kmx::host_view("kmx_sites_view", *h));             // 18 bytes per record, 22 with ctg
+    if (pos) *pos = h->pos.host();
+    if (ref) *ref = h->ref.host();
+    if (alt) *alt = h->alt.host();
+    if (depth) *depth = h->depth.host();
+    if (count) *count = h->count.host();
+    if (ref_count) *ref_count = h->ref_count.host();
+    if (ctg) *ctg = h->with_ctg ? h->ctg.host() : nullptr;
     return KMX_OK;
 }
 

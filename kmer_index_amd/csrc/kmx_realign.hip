@@ -426,10 +426,7 @@ kmx_status realign_call(const char* fn, const kmx_index* index, const kmx_alignm
     const kmx::AlignAccess A = kmx::alignments_access(al);
     const kmx::ScriptsAccess Sc = kmx::scripts_access(scripts);
     kmx_clips* h = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (h) h->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, h);
     if (Sc.flags & KMX_SCRIPT_M) return refuse(KMX_ERR_INVALID_ARGUMENT, "the scripts were made with KMX_SCRIPT_M: a score needs '=' and 'X' apart");
     if (nr != Sc.nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "nr differs from the scripts handle's");
     if (Sc.n_sel > A.n_loci) return refuse(KMX_ERR_INVALID_ARGUMENT, "the scripts hold more loci than the alignments handle's n_loci");

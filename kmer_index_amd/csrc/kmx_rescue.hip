@@ -362,19 +362,24 @@ struct kmx_rescues {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t nr2 = 0, n_jobs = 0, n_found = 0, n_concordant = 0, n_taken = 0;
-    bool filled = false;                   // a call has succeeded since the last refusal or error: job_off holds nr2 + 1 offsets
-    // results
-    Buf job_off, read, lo, hi, dist, start, end, status;
+    // results: the offsets per internal read, then one entry per job
+    kmx::ArrOf<uint64_t> job_off{kmx::ARR_OFFSETS};
+    kmx::ArrOf<uint32_t> read, lo, hi, start, end;
+    kmx::ArrOf<uint8_t> dist, status;
     // scratch; best[nr2] selects the taken jobs for kmx_rescues_scripts
     Buf flag, bsum, pcnt, peq_off, peq, cls, key, best, ctr;
-    Pinned h_ctr, h_job_off, h_read, h_lo, h_hi, h_dist, h_start, h_end, h_status;
+    Pinned h_ctr;
     bool host_valid = false;
-    void release()
+    std::vector<kmx::Arr*> results() { return {&job_off, &read, &lo, &hi, &dist, &start, &end, &status}; }
+    std::vector<Buf*> scratch() { return {&flag, &bsum, &pcnt, &peq_off, &peq, &cls, &key, &best, &ctr}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { nr2 = n_jobs = n_found = n_concordant = n_taken = 0; kmx::clear_arrays(*this); }
+    // a call has succeeded: the arrays expose what the counters say
+    void expose()
     {
-        for (Buf* b : {&job_off, &read, &lo, &hi, &dist, &start, &end, &status, &flag, &bsum, &pcnt, &peq_off, &peq, &cls, &key, &best, &ctr}) b->release();
-        for (Pinned* b : {&h_ctr, &h_job_off, &h_read, &h_lo, &h_hi, &h_dist, &h_start, &h_end, &h_status}) b->release();
+        kmx::expose(results(), n_jobs);
+        job_off.n = nr2 + 1;
     }
-    void clear() { nr2 = n_jobs = n_found = n_concordant = n_taken = 0; filled = false; host_valid = false; }
 };
 
 kmx::JobsAccess kmx::rescues_access(const kmx_rescues* r)
@@ -396,13 +401,10 @@ kmx_status rescue_run(const kmx::IndexAccess& X, const kmx_strand_reads* reads, 
                       const kmx_rescue_options& o, hipStream_t s, kmx_placements* pl, kmx_pairs* pr, kmx_rescues* h, bool* folded)
 {
     const uint64_t nr2 = L.nr, np = nr2 / 4, cap = 2 * np;
-    h->stream = s;
-    h->clear();
-    (void)hipGetLastError();
     TRY_HIP(h->job_off.ensure((nr2 + 1) * 8));
     if (np == 0) {                                             // no pair: no launch indexes an empty array
         TRY_HIP(hipMemsetAsync(h->job_off.p, 0, 8, s));
-        h->filled = true;
+        h->expose();
         return KMX_OK;
     }
     TRY_KMX(kmx::ensure_text(X, s));
@@ -410,7 +412,7 @@ kmx_status rescue_run(const kmx::IndexAccess& X, const kmx_strand_reads* reads, 
     TRY_HIP(h->bsum.ensure(kmx::scan_blocks(nr2) * 8 + 16));
     TRY_HIP(h->peq_off.ensure((nr2 + 1) * 8));
     for (Buf* b : {&h->read, &h->lo, &h->hi, &h->start, &h->end}) TRY_HIP(b->ensure(cap * 4));
-    for (Buf* b : {&h->dist, &h->status, &h->cls}) TRY_HIP(b->ensure(cap));
+    for (Buf* b : std::initializer_list<Buf*>{&h->dist, &h->status, &h->cls}) TRY_HIP(b->ensure(cap));
     TRY_HIP(h->key.ensure(cap * 8));
     TRY_HIP(h->best.ensure(nr2 * 4));
     TRY_HIP(h->ctr.ensure(CTR_COUNT * 8));
@@ -478,7 +480,7 @@ kmx_status rescue_run(const kmx::IndexAccess& X, const kmx_strand_reads* reads, 
     }
     h->nr2 = nr2;
     h->n_jobs = n_jobs;
-    h->filled = true;
+    h->expose();
     return KMX_OK;
 }
 
@@ -507,10 +509,7 @@ kmx_status kmx_pairs_rescue(const kmx_index* index, const kmx_strand_reads* read
     const kmx::LociAccess L = kmx::loci_access(loci);
     const kmx::AlignAccess A = kmx::alignments_access(alignments);
     kmx_rescues* h = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {  // the placements and the pairs stay as they are
-        if (h) h->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, h);                        // (the placements and the pairs stay as they are)
     const uint64_t nr2 = L.nr;
     if (A.nr != nr2) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments handle's nr differs from the loci handle's");
     if (reads->nr2 != nr2) return refuse(KMX_ERR_INVALID_ARGUMENT, "the reads are not those of the loci: nr2 differs");
@@ -531,14 +530,10 @@ kmx_status kmx_pairs_rescue(const kmx_index* index, const kmx_strand_reads* read
     h = *inout;
     hipStream_t s = reads->stream;
     bool folded = false;
-    const kmx_status st = rescue_run(X, reads, L, A, *o, s, placements, pairs, h, &folded);
-    if (st != KMX_OK) {                                        // nothing in flight; no handle holds half a result
-        (void)hipStreamSynchronize(s);
-        h->clear();
-        if (folded) {
-            placements->clear();
-            pairs->clear();
-        }
+    const kmx_status st = kmx::run_into(h, s, [&] { return rescue_run(X, reads, L, A, *o, s, placements, pairs, h, &folded); });
+    if (st != KMX_OK && folded) {                              // no handle holds half a result
+        placements->clear();
+        pairs->clear();
     }
     return st;
 }
@@ -558,15 +553,14 @@ kmx_status kmx_rescues_view_device(const kmx_rescues* h, const uint64_t** d_job_
                                    const uint8_t** d_dist, const uint32_t** d_start, const uint32_t** d_end, const uint8_t** d_status)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_rescues_view_device: rescues handle is NULL");
-    const bool any = h->n_jobs != 0;
-    if (d_job_off) *d_job_off = h->filled ? h->job_off.as<uint64_t>() : nullptr;
-    if (d_read) *d_read = any ? h->read.as<uint32_t>() : nullptr;
-    if (d_lo) *d_lo = any ? h->lo.as<uint32_t>() : nullptr;
-    if (d_hi) *d_hi = any ? h->hi.as<uint32_t>() : nullptr;
-    if (d_dist) *d_dist = any ? h->dist.as<uint8_t>() : nullptr;
-    if (d_start) *d_start = any ? h->start.as<uint32_t>() : nullptr;
-    if (d_end) *d_end = any ? h->end.as<uint32_t>() : nullptr;
-    if (d_status) *d_status = any ? h->status.as<uint8_t>() : nullptr;
+    if (d_job_off) *d_job_off = h->job_off.dev();
+    if (d_read) *d_read = h->read.dev();
+    if (d_lo) *d_lo = h->lo.dev();
+    if (d_hi) *d_hi = h->hi.dev();
+    if (d_dist) *d_dist = h->dist.dev();
+    if (d_start) *d_start = h->start.dev();
+    if (d_end) *d_end = h->end.dev();
+    if (d_status) *d_status = h->status.dev();
     return KMX_OK;
 }
 
@@ -574,24 +568,15 @@ kmx_status kmx_rescues_view(kmx_rescues* h, const uint64_t** job_off, const uint
                             const uint8_t** dist, const uint32_t** start, const uint32_t** end, const uint8_t** status)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_rescues_view: rescues handle is NULL");
-    if (!h->host_valid) {                                      // 8 bytes per internal read, 22 per job
-        const uint64_t nj = h->n_jobs;
-        const bool f = h->filled;                              // else the empty result: one offset, 0
-        const kmx::HostCopy items[] = {{h->h_job_off, h->job_off, f ? h->nr2 + 1 : 0, 8}, {h->h_read, h->read, nj, 4}, {h->h_lo, h->lo, nj, 4},
-                                       {h->h_hi, h->hi, nj, 4},   {h->h_start, h->start, nj, 4}, {h->h_end, h->end, nj, 4},
-                                       {h->h_dist, h->dist, nj, 1}, {h->h_status, h->status, nj, 1}};
-        TRY_KMX(kmx::host_view("kmx_rescues_view", h->device, h->stream, items, std::size(items)));
-        if (!f) h->h_job_off.as<uint64_t>()[0] = 0;
-        h->host_valid = true;
-    }
-    if (job_off) *job_off = h->h_job_off.as<uint64_t>();
-    if (read) *read = h->h_read.as<uint32_t>();
-    if (lo) *lo = h->h_lo.as<uint32_t>();
-    if (hi) *hi = h->h_hi.as<uint32_t>();
-    if (dist) *dist = h->h_dist.as<uint8_t>();
-    if (start) *start = h->h_start.as<uint32_t>();
-    if (end) *end = h->h_end.as<uint32_t>();
-    if (status) *status = h->h_status.as<uint8_t>();
+    TRY_KMX(kmx::host_view("kmx_rescues_view", *h));           // 8 bytes per internal read, 22 per job
+    if (job_off) *job_off = h->job_off.host();
+    if (read) *read = h->read.host();
+    if (lo) *lo = h->lo.host();
+    if (hi) *hi = h->hi.host();
+    if (dist) *dist = h->dist.host();
+    if (start) *start = h->start.host();
+    if (end) *end = h->end.host();
+    if (status) *status = h->status.host();
     return KMX_OK;
 }
 

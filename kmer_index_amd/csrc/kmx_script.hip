@@ -267,22 +267,26 @@ struct kmx_scripts {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t nr = 0, n_sel = 0, n_ops = 0, n_mismatched = 0;
-    bool filled = false;                   // a call has succeeded since the last refusal or error
     uint32_t flags = 0;                    // the options' flags of the call that filled the handle (kmx_scripts_md refuses KMX_SCRIPT_M)
     // results
-    Buf read_sel_off, sel, cig_off, cigar;
+    kmx::ArrOf<uint64_t> read_sel_off{kmx::ARR_OFFSETS}, cig_off{kmx::ARR_OFFSETS};
+    kmx::ArrOf<uint32_t> sel, cigar;
     // scratch
     Buf ranks, roff, cnt, bsum, eread, estat, ecode, eres, eruns, code_off, run_off, arena, runs, ctr;
-    Pinned h_ctr, h_read_sel_off, h_sel, h_cig_off, h_cigar;
+    Pinned h_ctr;
     bool host_valid = false;
-    void release()
+    std::vector<kmx::Arr*> results() { return {&read_sel_off, &sel, &cig_off, &cigar}; }
+    std::vector<Buf*> scratch() { return {&ranks, &roff, &cnt, &bsum, &eread, &estat, &ecode, &eres, &eruns, &code_off, &run_off, &arena, &runs, &ctr}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { nr = n_sel = n_ops = n_mismatched = 0; kmx::clear_arrays(*this); }
+    // a call has succeeded: the arrays expose what the counters say
+    void expose()
     {
-        for (Buf* b : {&read_sel_off, &sel, &cig_off, &cigar, &ranks, &roff, &cnt, &bsum, &eread, &estat, &ecode, &eres, &eruns, &code_off, &run_off,
-                       &arena, &runs, &ctr})
-            b->release();
-        for (Pinned* b : {&h_ctr, &h_read_sel_off, &h_sel, &h_cig_off, &h_cigar}) b->release();
+        read_sel_off.n = nr + 1;
+        sel.n = n_sel;
+        cig_off.n = n_sel + 1;
+        cigar.n = n_ops;
     }
-    void clear() { nr = n_sel = n_ops = n_mismatched = 0; filled = false; host_valid = false; }
 };
 
 namespace {
@@ -304,17 +308,14 @@ kmx_status script_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const
                       uint64_t ranks_len, const uint32_t* best, const kmx_script_options& o, hipStream_t s, kmx_scripts* h)
 {
     const uint64_t nr = L.nr, nl = L.n_loci;
-    h->stream = s;
-    h->clear();
     h->flags = o.flags;
-    (void)hipGetLastError();
     TRY_HIP(h->read_sel_off.ensure((nr + 1) * 8));
     if (nr == 0 || nl == 0) {                                  // no entry: no launch indexes an empty array
         TRY_HIP(h->cig_off.ensure(8));
         TRY_HIP(hipMemsetAsync(h->read_sel_off.p, 0, (nr + 1) * 8, s));
         TRY_HIP(hipMemsetAsync(h->cig_off.p, 0, 8, s));
         h->nr = nr;
-        h->filled = true;
+        h->expose();
         return KMX_OK;
     }
     TRY_KMX(kmx::ensure_text(X, s));
@@ -326,7 +327,7 @@ kmx_status script_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const
     TRY_HIP(h->eread.ensure(cap_e * 4));
     TRY_HIP(h->estat.ensure(cap_e));
     for (Buf* b : {&h->ecode, &h->eres, &h->eruns}) TRY_HIP(b->ensure(cap_e * 4 + 16));
-    for (Buf* b : {&h->code_off, &h->run_off, &h->cig_off}) TRY_HIP(b->ensure((cap_e + 1) * 8));
+    for (Buf* b : std::initializer_list<Buf*>{&h->code_off, &h->run_off, &h->cig_off}) TRY_HIP(b->ensure((cap_e + 1) * 8));
     TRY_HIP(h->ctr.ensure(CTR_COUNT * 8));
     unsigned long long* ctr = h->ctr.as<unsigned long long>();
     TRY_HIP(hipMemsetAsync(ctr, 0, CTR_COUNT * 8, s));
@@ -379,7 +380,7 @@ kmx_status script_run(const kmx::IndexAccess& X, const kmx::LociAccess& L, const
     h->n_sel = n_sel;
     h->n_ops = h->h_ctr.as<uint64_t>()[CTR_N_OPS];
     h->n_mismatched = h->h_ctr.as<uint64_t>()[CTR_N_MISMATCHED];
-    h->filled = true;
+    h->expose();
     return KMX_OK;
 }
 
@@ -411,10 +412,7 @@ kmx_status script_call(const char* fn, const kmx_index* index, const kmx_loci* l
     const kmx::LociAccess L = kmx::loci_access(loci);
     const kmx::AlignAccess A = kmx::alignments_access(al);
     kmx_scripts* h = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (h) h->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, h);
     if (nr != L.nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "nr differs from the loci handle's");
     if (nr != A.nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "nr differs from the alignments handle's");
     if (A.n_loci != L.n_loci) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments handle's n_loci differs from the loci handle's");
@@ -434,17 +432,17 @@ kmx_status script_call(const char* fn, const kmx_index* index, const kmx_loci* l
     TRY_KMX(kmx::bind_handle(inout, L.device));
     h = *inout;
     hipStream_t s = host ? A.stream : stream;
-    kmx_status st = KMX_OK;
-    const void* d_ranks = ranks;
-    const void* d_roff = roff;
-    if (host && nr && L.n_loci) {
-        st = kmx::upload_reads(ranks, roff, nr, n_letters, h->ranks, h->roff, s);
-        d_ranks = h->ranks.p;
-        d_roff = h->roff.p;
-    }
-    if (st == KMX_OK) st = script_run(X, L, A, d_ranks, d_roff, n_letters, P ? P->best2 : A.best, *o, s, h);
-    if (host || st != KMX_OK) (void)hipStreamSynchronize(s);   // the caller's arrays are free again; a failed call leaves nothing in flight
-    if (st != KMX_OK) h->clear();                              // the handle holds an empty result, not half of this one
+    const kmx_status st = kmx::run_into(h, s, [&] {
+        const void* d_ranks = ranks;
+        const void* d_roff = roff;
+        if (host && nr && L.n_loci) {
+            TRY_KMX(kmx::upload_reads(ranks, roff, nr, n_letters, h->ranks, h->roff, s));
+            d_ranks = h->ranks.p;
+            d_roff = h->roff.p;
+        }
+        return script_run(X, L, A, d_ranks, d_roff, n_letters, P ? P->best2 : A.best, *o, s, h);
+    });
+    if (host && st == KMX_OK) (void)hipStreamSynchronize(s);   // the caller's arrays are free again
     return st;
 }
 
@@ -478,10 +476,7 @@ kmx_status kmx::scripts_on_arrays(const char* fn, const kmx_index* index, const 
     run.struct_size = sizeof run;
     if (every) run.flags |= KMX_SCRIPT_ALL;
     kmx_scripts* h = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (h) h->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, h);
     kmx::IndexAccess X{};
     kmx_status no_st;
     std::string no_index;
@@ -489,12 +484,7 @@ kmx_status kmx::scripts_on_arrays(const char* fn, const kmx_index* index, const 
     kmx::DeviceGuard dg;
     TRY_KMX(kmx::bind_handle(inout, L.device));
     h = *inout;
-    const kmx_status st = script_run(X, L, A, d_ranks, d_roff, ranks_len, best, run, stream, h);
-    if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
-        (void)hipStreamSynchronize(stream);
-        h->clear();
-    }
-    return st;
+    return kmx::run_into(h, stream, [&] { return script_run(X, L, A, d_ranks, d_roff, ranks_len, best, run, stream, h); });
 }
 
 extern "C" {
@@ -526,29 +516,21 @@ kmx_status kmx_scripts_view_device(const kmx_scripts* h, const uint64_t** d_read
                                    const uint32_t** d_cigar)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_scripts_view_device: scripts handle is NULL");
-    if (d_read_sel_off) *d_read_sel_off = h->filled ? h->read_sel_off.as<uint64_t>() : nullptr;
-    if (d_sel) *d_sel = h->n_sel ? h->sel.as<uint32_t>() : nullptr;
-    if (d_cig_off) *d_cig_off = h->filled ? h->cig_off.as<uint64_t>() : nullptr;
-    if (d_cigar) *d_cigar = h->n_ops ? h->cigar.as<uint32_t>() : nullptr;
+    if (d_read_sel_off) *d_read_sel_off = h->read_sel_off.dev();
+    if (d_sel) *d_sel = h->sel.dev();
+    if (d_cig_off) *d_cig_off = h->cig_off.dev();
+    if (d_cigar) *d_cigar = h->cigar.dev();
     return KMX_OK;
 }
 
 kmx_status kmx_scripts_view(kmx_scripts* h, const uint64_t** read_sel_off, const uint32_t** sel, const uint64_t** cig_off, const uint32_t** cigar)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_scripts_view: scripts handle is NULL");
-    if (!h->host_valid) {
-        const uint64_t nr = h->nr, ns = h->n_sel, no = h->n_ops;
-        const bool f = h->filled;                              // else the empty result: one offset each, 0
-        const kmx::HostCopy items[] = {{h->h_read_sel_off, h->read_sel_off, f ? nr + 1 : 0, 8}, {h->h_sel, h->sel, ns, 4},
-                                       {h->h_cig_off, h->cig_off, f ? ns + 1 : 0, 8}, {h->h_cigar, h->cigar, no, 4}};
-        TRY_KMX(kmx::host_view("kmx_scripts_view", h->device, h->stream, items, std::size(items)));
-        if (!f) h->h_read_sel_off.as<uint64_t>()[0] = h->h_cig_off.as<uint64_t>()[0] = 0;
-        h->host_valid = true;
-    }
-    if (read_sel_off) *read_sel_off = h->h_read_sel_off.as<uint64_t>();
-    if (sel) *sel = h->h_sel.as<uint32_t>();
-    if (cig_off) *cig_off = h->h_cig_off.as<uint64_t>();
-    if (cigar) *cigar = h->h_cigar.as<uint32_t>();
+    TRY_KMX(kmx::host_view("kmx_scripts_view", *h));
+    if (read_sel_off) *read_sel_off = h->read_sel_off.host();
+    if (sel) *sel = h->sel.host();
+    if (cig_off) *cig_off = h->cig_off.host();
+    if (cigar) *cigar = h->cigar.host();
     return KMX_OK;
 }
 

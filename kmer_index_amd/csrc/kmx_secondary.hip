@@ -154,20 +154,27 @@ struct kmx_secondaries {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t nr = 0, n_sec = 0, n_multi = 0, n_truncated = 0;
-    bool filled = false;                   // a call has succeeded since the last refusal or error: sec_off holds 2 nr + 1 offsets
     bool has_ctg = false;                  // the alignments carried a contig table: ctg holds n_sec entries
-    // results
-    Buf sec_off, locus, dist, start, end, ctg, more;
+    // results: the offsets per internal read, one entry per place, more per public read
+    kmx::ArrOf<uint64_t> sec_off{kmx::ARR_OFFSETS};
+    kmx::ArrOf<uint32_t> locus, start, end, ctg;
+    kmx::ArrOf<uint8_t> dist, more;
     // scratch
     Buf picks, cnt, bsum, ctr;
-    Pinned h_ctr, h_sec_off, h_locus, h_dist, h_start, h_end, h_ctg, h_more;
+    Pinned h_ctr;
     bool host_valid = false;
-    void release()
+    std::vector<kmx::Arr*> results() { return {&sec_off, &locus, &dist, &start, &end, &ctg, &more}; }
+    std::vector<Buf*> scratch() { return {&picks, &cnt, &bsum, &ctr}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { nr = n_sec = n_multi = n_truncated = 0; has_ctg = false; kmx::clear_arrays(*this); }
+    // a call has succeeded: the arrays expose what the counters say
+    void expose()
     {
-        for (Buf* b : {&sec_off, &locus, &dist, &start, &end, &ctg, &more, &picks, &cnt, &bsum, &ctr}) b->release();
-        for (Pinned* b : {&h_ctr, &h_sec_off, &h_locus, &h_dist, &h_start, &h_end, &h_ctg, &h_more}) b->release();
+        kmx::expose(results(), n_sec);
+        sec_off.n = 2 * nr + 1;
+        more.n = nr;
+        if (!has_ctg) ctg.n = 0;
     }
-    void clear() { nr = n_sec = n_multi = n_truncated = 0; filled = false; has_ctg = false; host_valid = false; }
 };
 
 kmx::JobsAccess kmx::secondaries_access(const kmx_secondaries* h)
@@ -181,13 +188,10 @@ kmx_status secondaries_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, 
                            hipStream_t s, kmx_secondaries* h)
 {
     const uint64_t nr2 = L.nr, nr = nr2 / 2;
-    h->stream = s;
-    h->clear();
-    (void)hipGetLastError();
     TRY_HIP(h->sec_off.ensure((nr2 + 1) * 8));
     if (nr == 0) {                                             // no read: no launch indexes an empty array
         TRY_HIP(hipMemsetAsync(h->sec_off.p, 0, 8, s));
-        h->filled = true;
+        h->expose();
         return KMX_OK;
     }
     const uint32_t N = o.max_secondary;
@@ -221,7 +225,7 @@ kmx_status secondaries_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, 
     h->n_multi = h->h_ctr.as<uint64_t>()[CTR_N_MULTI];
     h->n_truncated = h->h_ctr.as<uint64_t>()[CTR_N_TRUNCATED];
     h->has_ctg = A.ctg != nullptr;
-    h->filled = true;
+    h->expose();
     return KMX_OK;
 }
 
@@ -244,10 +248,7 @@ kmx_status kmx_placements_secondaries(const kmx_loci* loci, const kmx_alignments
     const kmx::AlignAccess A = kmx::alignments_access(alignments);
     const kmx::PlacementsAccess P = kmx::placements_access(placements);
     kmx_secondaries* h = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (h) h->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, h);
     if (L.nr != A.nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments handle's nr differs from the loci handle's");
     if (L.nr & 1) return refuse(KMX_ERR_INVALID_ARGUMENT, "an odd number of reads: not the loci of a doubled batch");
     if (A.n_loci != L.n_loci) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments handle's n_loci differs from the loci handle's");
@@ -258,12 +259,7 @@ kmx_status kmx_placements_secondaries(const kmx_loci* loci, const kmx_alignments
     TRY_KMX(kmx::bind_handle(inout, L.device));
     h = *inout;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : P.stream;
-    const kmx_status st = secondaries_run(L, A, P, *o, s, h);
-    if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
-        (void)hipStreamSynchronize(s);
-        h->clear();
-    }
-    return st;
+    return kmx::run_into(h, s, [&] { return secondaries_run(L, A, P, *o, s, h); });
 }
 
 kmx_status kmx_secondaries_counts(const kmx_secondaries* h, uint64_t* nr, uint64_t* n_sec, uint64_t* n_multi, uint64_t* n_truncated)
@@ -280,14 +276,13 @@ kmx_status kmx_secondaries_view_device(const kmx_secondaries* h, const uint64_t*
                                        const uint32_t** d_start, const uint32_t** d_end, const uint32_t** d_ctg, const uint8_t** d_more)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_secondaries_view_device: secondaries handle is NULL");
-    const bool any = h->n_sec != 0;
-    if (d_sec_off) *d_sec_off = h->filled ? h->sec_off.as<uint64_t>() : nullptr;
-    if (d_locus) *d_locus = any ? h->locus.as<uint32_t>() : nullptr;
-    if (d_dist) *d_dist = any ? h->dist.as<uint8_t>() : nullptr;
-    if (d_start) *d_start = any ? h->start.as<uint32_t>() : nullptr;
-    if (d_end) *d_end = any ? h->end.as<uint32_t>() : nullptr;
-    if (d_ctg) *d_ctg = any && h->has_ctg ? h->ctg.as<uint32_t>() : nullptr;
-    if (d_more) *d_more = h->nr ? h->more.as<uint8_t>() : nullptr;
+    if (d_sec_off) *d_sec_off = h->sec_off.dev();
+    if (d_locus) *d_locus = h->locus.dev();
+    if (d_dist) *d_dist = h->dist.dev();
+    if (d_start) *d_start = h->start.dev();
+    if (d_end) *d_end = h->end.dev();
+    if (d_ctg) *d_ctg = h->ctg.dev();
+    if (d_more) *d_more = h->more.dev();
     return KMX_OK;
 }
 
@@ -295,23 +290,14 @@ kmx_status kmx_secondaries_view(kmx_secondaries* h, const uint64_t** sec_off, co
                                 const uint32_t** end, const uint32_t** ctg, const uint8_t** more)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_secondaries_view: secondaries handle is NULL");
-    if (!h->host_valid) {                                      // 8 bytes per internal read, 1 per public read, 13 per entry (17 with ctg)
-        const uint64_t ns = h->n_sec;
-        const bool f = h->filled;                              // else the empty result: one offset, 0
-        const kmx::HostCopy items[] = {{h->h_sec_off, h->sec_off, f ? 2 * h->nr + 1 : 0, 8}, {h->h_locus, h->locus, ns, 4}, {h->h_start, h->start, ns, 4},
-                                       {h->h_end, h->end, ns, 4}, {h->h_dist, h->dist, ns, 1}, {h->h_more, h->more, h->nr, 1},
-                                       {h->h_ctg, h->ctg, h->has_ctg ? ns : 0, 4}};
-        TRY_KMX(kmx::host_view("kmx_secondaries_view", h->device, h->stream, items, std::size(items)));
-        if (!f) h->h_sec_off.as<uint64_t>()[0] = 0;
-        h->host_valid = true;
-    }
-    if (sec_off) *sec_off = h->h_sec_off.as<uint64_t>();
-    if (locus) *locus = h->h_locus.as<uint32_t>();
-    if (dist) *dist = h->h_dist.as<uint8_t>();
-    if (start) *start = h->h_start.as<uint32_t>();
-    if (end) *end = h->h_end.as<uint32_t>();
-    if (ctg) *ctg = h->has_ctg ? h->h_ctg.as<uint32_t>() : nullptr;
-    if (more) *more = h->h_more.as<uint8_t>();
+    TRY_KMX(kmx::host_view("kmx_secondaries_view", *h));       // 8 bytes per internal read, 1 per public read, 13 per entry (17 with ctg)
+    if (sec_off) *sec_off = h->sec_off.host();
+    if (locus) *locus = h->locus.host();
+    if (dist) *dist = h->dist.host();
+    if (start) *start = h->start.host();
+    if (end) *end = h->end.host();
+    if (ctg) *ctg = h->has_ctg ? h->ctg.host() : nullptr;
+    if (more) *more = h->more.host();
     return KMX_OK;
 }
 

@@ -17,25 +17,26 @@ struct kmx_placements {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t nr = 0, n_placed = 0, n_reverse = 0, n_ambiguous = 0;
-    kmx::Buf locus, strand, dist, start, end, second, best2, ctr;
-    kmx::PinnedArr h_ctr, h_locus, h_strand, h_dist, h_start, h_end, h_second, h_best2;
+    // results, one entry per public read; best2, a pair per read, goes to the host only when a caller asks for it
+    kmx::ArrOf<uint32_t> locus, start, end, best2{kmx::ARR_OWN_VIEW};
+    kmx::ArrOf<uint8_t> strand, dist, second;
+    kmx::Buf ctr;
+    kmx::PinnedArr h_ctr;
     bool host_valid = false, host_best2_valid = false;
-    void release()
-    {
-        for (kmx::Buf* b : {&locus, &strand, &dist, &start, &end, &second, &best2, &ctr}) b->release();
-        for (kmx::PinnedArr* b : {&h_ctr, &h_locus, &h_strand, &h_dist, &h_start, &h_end, &h_second, &h_best2}) b->release();
-    }
-    void clear() { nr = n_placed = n_reverse = n_ambiguous = 0; host_valid = false; host_best2_valid = false; }
+    std::vector<kmx::Arr*> results() { return {&locus, &strand, &dist, &start, &end, &second, &best2}; }
+    std::vector<kmx::Buf*> scratch() { return {&ctr}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { nr = n_placed = n_reverse = n_ambiguous = 0; kmx::clear_arrays(*this); host_best2_valid = false; }
+    // the fold has filled the arrays of n public reads
+    void expose(uint64_t n) { nr = n; kmx::expose(results(), n); best2.n = 2 * n; }
     // c: the counters of a fold as they were read back, c[kmx::PL_*] the placements'
     void counts_from(const uint64_t* c) { n_placed = c[kmx::PL_N_PLACED]; n_reverse = c[kmx::PL_N_REVERSE]; n_ambiguous = c[kmx::PL_N_AMBIGUOUS]; }
     // the seven arrays of n public reads
     hipError_t room(uint64_t n)
     {
-        for (kmx::Buf* b : {&locus, &start, &end})
-            if (hipError_t e = b->ensure(n * 4); e != hipSuccess) return e;
-        for (kmx::Buf* b : {&strand, &dist, &second})
-            if (hipError_t e = b->ensure(n); e != hipSuccess) return e;
-        return best2.ensure(2 * n * 4);
+        for (kmx::Arr* a : results())
+            if (hipError_t e = a->ensure((a == &best2 ? 2 : 1) * n * a->elem); e != hipSuccess) return e;
+        return hipSuccess;
     }
 };
 
@@ -65,15 +66,19 @@ struct kmx_pairs {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the fold that filled the handle (the host view copies on it)
     uint64_t np = 0, n_concordant = 0, n_discordant = 0, n_single = 0, n_unplaced = 0, n_ambiguous = 0;
-    kmx::Buf cls, tlen, score, second_score, ctr;
-    kmx::PinnedArr h_ctr, h_cls, h_tlen, h_score, h_second_score;
+    // results, one entry per pair
+    kmx::ArrOf<uint8_t> cls;
+    kmx::ArrOf<int32_t> tlen;
+    kmx::ArrOf<uint16_t> score, second_score;
+    kmx::Buf ctr;
+    kmx::PinnedArr h_ctr;
     bool host_valid = false;
-    void release()
-    {
-        for (kmx::Buf* b : {&cls, &tlen, &score, &second_score, &ctr}) b->release();
-        for (kmx::PinnedArr* b : {&h_ctr, &h_cls, &h_tlen, &h_score, &h_second_score}) b->release();
-    }
-    void clear() { np = n_concordant = n_discordant = n_single = n_unplaced = n_ambiguous = 0; host_valid = false; }
+    std::vector<kmx::Arr*> results() { return {&cls, &tlen, &score, &second_score}; }
+    std::vector<kmx::Buf*> scratch() { return {&ctr}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { np = n_concordant = n_discordant = n_single = n_unplaced = n_ambiguous = 0; kmx::clear_arrays(*this); }
+    // the fold has filled the arrays of n pairs
+    void expose(uint64_t n) { np = n; kmx::expose(results(), n); }
     // c: the counters of a fold as they were read back, c[kmx::PR_*] the pairs'
     void counts_from(const uint64_t* c)
     {

@@ -138,10 +138,7 @@ kmx_status strands_call(const char* fn, const kmx_index* index, const void* rank
     if (!index) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "index is NULL");
     if (!inout) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "inout is NULL");
     kmx_strand_reads* h = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (h) h->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, h);
     if (!complement) return refuse(KMX_ERR_INVALID_ARGUMENT, "NULL complement table");
     kmx::IndexAccess X = kmx::index_access(index);
     uint8_t comp[256];
@@ -206,9 +203,6 @@ kmx_status strands_call(const char* fn, const kmx_index* index, const void* rank
 kmx_status fold_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, hipStream_t s, kmx_placements* p)
 {
     const uint64_t nr = L.nr / 2;
-    p->stream = s;
-    p->clear();
-    (void)hipGetLastError();
     if (nr == 0) return KMX_OK;
     TRY_HIP(p->room(nr));
     TRY_HIP(p->ctr.ensure(CTR_COUNT * 8));
@@ -220,7 +214,7 @@ kmx_status fold_run(const kmx::LociAccess& L, const kmx::AlignAccess& A, hipStre
     hipLaunchKernelGGL(k_strand_fold, dim3(grid_for(nr, kBlock / kWave)), dim3(kBlock), 0, s, F, O);
     TRY_HIP(hipGetLastError());
     TRY_KMX(kmx::read_back("kmx_alignments_fold_strands", s, ctr, p->h_ctr, CTR_COUNT * 8));
-    p->nr = nr;
+    p->expose(nr);
     p->counts_from(p->h_ctr.as<uint64_t>());
     return KMX_OK;
 }
@@ -264,10 +258,7 @@ kmx_status kmx_alignments_fold_strands(const kmx_loci* loci, const kmx_alignment
     const kmx::LociAccess L = kmx::loci_access(loci);
     const kmx::AlignAccess A = kmx::alignments_access(alignments);
     kmx_placements* p = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (p) p->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, p);
     if (L.nr != A.nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments handle's nr differs from the loci handle's");
     if (L.nr & 1) return refuse(KMX_ERR_INVALID_ARGUMENT, "an odd number of reads: not the loci of a doubled batch");
     if (A.n_loci != L.n_loci) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments handle's n_loci differs from the loci handle's");
@@ -276,12 +267,7 @@ kmx_status kmx_alignments_fold_strands(const kmx_loci* loci, const kmx_alignment
     TRY_KMX(kmx::bind_handle(inout, L.device));
     p = *inout;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : A.stream;
-    const kmx_status st = fold_run(L, A, s, p);
-    if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
-        (void)hipStreamSynchronize(s);
-        p->clear();
-    }
-    return st;
+    return kmx::run_into(p, s, [&] { return fold_run(L, A, s, p); });
 }
 
 kmx_status kmx_placements_counts(const kmx_placements* p, uint64_t* nr, uint64_t* n_placed, uint64_t* n_reverse, uint64_t* n_ambiguous)
@@ -298,14 +284,13 @@ kmx_status kmx_placements_view_device(const kmx_placements* p, const uint32_t** 
                                       const uint32_t** d_start, const uint32_t** d_end, const uint8_t** d_second, const uint32_t** d_best2)
 {
     if (!p) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_placements_view_device: placements handle is NULL");
-    const bool any = p->nr != 0;
-    if (d_locus) *d_locus = any ? p->locus.as<uint32_t>() : nullptr;
-    if (d_strand) *d_strand = any ? p->strand.as<uint8_t>() : nullptr;
-    if (d_dist) *d_dist = any ? p->dist.as<uint8_t>() : nullptr;
-    if (d_start) *d_start = any ? p->start.as<uint32_t>() : nullptr;
-    if (d_end) *d_end = any ? p->end.as<uint32_t>() : nullptr;
-    if (d_second) *d_second = any ? p->second.as<uint8_t>() : nullptr;
-    if (d_best2) *d_best2 = any ? p->best2.as<uint32_t>() : nullptr;
+    if (d_locus) *d_locus = p->locus.dev();
+    if (d_strand) *d_strand = p->strand.dev();
+    if (d_dist) *d_dist = p->dist.dev();
+    if (d_start) *d_start = p->start.dev();
+    if (d_end) *d_end = p->end.dev();
+    if (d_second) *d_second = p->second.dev();
+    if (d_best2) *d_best2 = p->best2.dev();
     return KMX_OK;
 }
 
@@ -313,23 +298,16 @@ kmx_status kmx_placements_view(kmx_placements* p, const uint32_t** locus, const 
                                const uint32_t** end, const uint8_t** second, const uint32_t** best2)
 {
     if (!p) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_placements_view: placements handle is NULL");
-    const bool want_best2 = best2 && !p->host_best2_valid;
-    if (!p->host_valid || want_best2) {
-        const uint64_t nr = p->host_valid ? 0 : p->nr;         // 15 bytes per read; best2 (a pair per read) only when asked for
-        const kmx::HostCopy items[] = {{p->h_locus, p->locus, nr, 4},   {p->h_start, p->start, nr, 4}, {p->h_end, p->end, nr, 4},
-                                       {p->h_strand, p->strand, nr, 1}, {p->h_dist, p->dist, nr, 1},   {p->h_second, p->second, nr, 1},
-                                       {p->h_best2, p->best2, p->nr, 8}};
-        TRY_KMX(kmx::host_view("kmx_placements_view", p->device, p->stream, items, best2 ? 7 : 6));
-        p->host_valid = true;
-        if (best2) p->host_best2_valid = true;
-    }
-    if (locus) *locus = p->h_locus.as<uint32_t>();
-    if (strand) *strand = p->h_strand.as<uint8_t>();
-    if (dist) *dist = p->h_dist.as<uint8_t>();
-    if (start) *start = p->h_start.as<uint32_t>();
-    if (end) *end = p->h_end.as<uint32_t>();
-    if (second) *second = p->h_second.as<uint8_t>();
-    if (best2) *best2 = p->h_best2.as<uint32_t>();
+    const bool want_best2 = best2 && !p->host_best2_valid;     // 15 bytes per read; best2 (a pair per read) only when asked for
+    TRY_KMX(kmx::host_view("kmx_placements_view", *p, want_best2 ? &p->best2 : nullptr));
+    if (best2) p->host_best2_valid = true;
+    if (locus) *locus = p->locus.host();
+    if (strand) *strand = p->strand.host();
+    if (dist) *dist = p->dist.host();
+    if (start) *start = p->start.host();
+    if (end) *end = p->end.host();
+    if (second) *second = p->second.host();
+    if (best2) *best2 = p->best2.host();
     return KMX_OK;
 }
 

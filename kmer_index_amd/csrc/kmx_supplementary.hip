@@ -251,21 +251,29 @@ struct kmx_supplementaries {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t nr = 0, n_sup = 0, n_split = 0, n_truncated = 0;
-    bool filled = false;                   // a call has succeeded since the last refusal or error: sup_off holds nr + 1 offsets
     bool has_ctg = false;                  // the alignments carried a contig table: ctg holds n_sup entries
-    // results
-    Buf sup_off, ent, locus, strand, q0, q1, t0, t1, score, second, nm, ctg, more;
+    // results: the offsets and more per public read, one entry per part
+    kmx::ArrOf<uint64_t> sup_off{kmx::ARR_OFFSETS};
+    kmx::ArrOf<uint32_t> ent, locus, t0, t1, ctg;
+    kmx::ArrOf<int32_t> score, second;
+    kmx::ArrOf<uint16_t> q0, q1, nm;
+    kmx::ArrOf<uint8_t> strand, more;
     // scratch
     Buf picks, cnt, prim, bsum, ctr;
-    Pinned h_ctr, h_sup_off, h_ent, h_locus, h_strand, h_q0, h_q1, h_t0, h_t1, h_score, h_second, h_nm, h_ctg, h_more;
+    Pinned h_ctr;
     bool host_valid = false;
-    void release()
+    std::vector<kmx::Arr*> results() { return {&sup_off, &ent, &locus, &strand, &q0, &q1, &t0, &t1, &score, &second, &nm, &ctg, &more}; }
+    std::vector<Buf*> scratch() { return {&picks, &cnt, &prim, &bsum, &ctr}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { nr = n_sup = n_split = n_truncated = 0; has_ctg = false; kmx::clear_arrays(*this); }
+    // a call has succeeded: the arrays expose what the counters say
+    void expose()
     {
-        for (Buf* b : {&sup_off, &ent, &locus, &strand, &q0, &q1, &t0, &t1, &score, &second, &nm, &ctg, &more, &picks, &cnt, &prim, &bsum, &ctr}) b->release();
-        for (Pinned* b : {&h_ctr, &h_sup_off, &h_ent, &h_locus, &h_strand, &h_q0, &h_q1, &h_t0, &h_t1, &h_score, &h_second, &h_nm, &h_ctg, &h_more})
-            b->release();
+        kmx::expose(results(), n_sup);
+        sup_off.n = nr + 1;
+        more.n = nr;
+        if (!has_ctg) ctg.n = 0;
     }
-    void clear() { nr = n_sup = n_split = n_truncated = 0; filled = false; has_ctg = false; host_valid = false; }
 };
 
 namespace {
@@ -274,13 +282,10 @@ kmx_status supplementaries_run(const kmx_strand_reads* reads, const kmx::AlignAc
                                const kmx::ClipsAccess& C, const kmx_supplementary_options& o, hipStream_t s, kmx_supplementaries* h)
 {
     const uint64_t nr = reads->nr2 / 2;
-    h->stream = s;
-    h->clear();
-    (void)hipGetLastError();
     TRY_HIP(h->sup_off.ensure((nr + 1) * 8));
     if (nr == 0) {                                             // no read: no launch indexes an empty array
         TRY_HIP(hipMemsetAsync(h->sup_off.p, 0, 8, s));
-        h->filled = true;
+        h->expose();
         return KMX_OK;
     }
     const uint32_t N = o.max_supplementary;
@@ -303,7 +308,7 @@ kmx_status supplementaries_run(const kmx_strand_reads* reads, const kmx::AlignAc
     const uint64_t n_sup = h->h_ctr.as<uint64_t>()[CTR_N_SUP];
     if (n_sup > nr * N) return kmx::set_error(KMX_ERR_HIP, "kmx_clips_supplementaries: more entries than N per read");   // (never: a guard for the arrays)
     if (n_sup) {
-        for (Buf* b : {&h->ent, &h->locus, &h->t0, &h->t1, &h->score, &h->second}) TRY_HIP(b->ensure(n_sup * 4));
+        for (Buf* b : std::initializer_list<Buf*>{&h->ent, &h->locus, &h->t0, &h->t1, &h->score, &h->second}) TRY_HIP(b->ensure(n_sup * 4));
         for (Buf* b : {&h->q0, &h->q1, &h->nm}) TRY_HIP(b->ensure(n_sup * 2));
         TRY_HIP(h->strand.ensure(n_sup));
         if (A.ctg) TRY_HIP(h->ctg.ensure(n_sup * 4));
@@ -318,7 +323,7 @@ kmx_status supplementaries_run(const kmx_strand_reads* reads, const kmx::AlignAc
     h->n_split = h->h_ctr.as<uint64_t>()[CTR_N_SPLIT];
     h->n_truncated = h->h_ctr.as<uint64_t>()[CTR_N_TRUNCATED];
     h->has_ctg = A.ctg != nullptr;
-    h->filled = true;
+    h->expose();
     return KMX_OK;
 }
 
@@ -350,10 +355,7 @@ kmx_status kmx_clips_supplementaries(const kmx_strand_reads* reads, const kmx_lo
     const kmx::ClipsAccess C = kmx::clips_access(clips);
     const uint64_t nr2 = reads->nr2;
     kmx_supplementaries* h = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (h) h->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, h);
     if (nr2 & 1) return refuse(KMX_ERR_INVALID_ARGUMENT, "an odd number of reads: not a doubled batch");
     if (L.nr != nr2) return refuse(KMX_ERR_INVALID_ARGUMENT, "the loci handle's nr differs from the reads' nr2");
     if (A.nr != nr2) return refuse(KMX_ERR_INVALID_ARGUMENT, "the alignments handle's nr differs from the reads' nr2");
@@ -371,12 +373,7 @@ kmx_status kmx_clips_supplementaries(const kmx_strand_reads* reads, const kmx_lo
     TRY_KMX(kmx::bind_handle(inout, reads->device));
     h = *inout;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : C.stream;
-    const kmx_status st = supplementaries_run(reads, A, P, S, C, *o, s, h);
-    if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
-        (void)hipStreamSynchronize(s);
-        h->clear();
-    }
-    return st;
+    return kmx::run_into(h, s, [&] { return supplementaries_run(reads, A, P, S, C, *o, s, h); });
 }
 
 kmx_status kmx_supplementaries_counts(const kmx_supplementaries* h, uint64_t* nr, uint64_t* n_sup, uint64_t* n_split, uint64_t* n_truncated)
@@ -395,20 +392,19 @@ kmx_status kmx_supplementaries_view_device(const kmx_supplementaries* h, const u
                                            const uint32_t** d_ctg, const uint8_t** d_more)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_supplementaries_view_device: supplementaries handle is NULL");
-    const bool any = h->n_sup != 0;
-    if (d_sup_off) *d_sup_off = h->filled ? h->sup_off.as<uint64_t>() : nullptr;
-    if (d_ent) *d_ent = any ? h->ent.as<uint32_t>() : nullptr;
-    if (d_locus) *d_locus = any ? h->locus.as<uint32_t>() : nullptr;
-    if (d_strand) *d_strand = any ? h->strand.as<uint8_t>() : nullptr;
-    if (d_q0) *d_q0 = any ? h->q0.as<uint16_t>() : nullptr;
-    if (d_q1) *d_q1 = any ? h->q1.as<uint16_t>() : nullptr;
-    if (d_t0) *d_t0 = any ? h->t0.as<uint32_t>() : nullptr;
-    if (d_t1) *d_t1 = any ? h->t1.as<uint32_t>() : nullptr;
-    if (d_score) *d_score = any ? h->score.as<int32_t>() : nullptr;
-    if (d_second_score) *d_second_score = any ? h->second.as<int32_t>() : nullptr;
-    if (d_nm) *d_nm = any ? h->nm.as<uint16_t>() : nullptr;
-    if (d_ctg) *d_ctg = any && h->has_ctg ? h->ctg.as<uint32_t>() : nullptr;
-    if (d_more) *d_more = h->nr ? h->more.as<uint8_t>() : nullptr;
+    if (d_sup_off) *d_sup_off = h->sup_off.dev();
+    if (d_ent) *d_ent = h->ent.dev();
+    if (d_locus) *d_locus = h->locus.dev();
+    if (d_strand) *d_strand = h->strand.dev();
+    if (d_q0) *d_q0 = h->q0.dev();
+    if (d_q1) *d_q1 = h->q1.dev();
+    if (d_t0) *d_t0 = h->t0.dev();
+    if (d_t1) *d_t1 = h->t1.dev();
+    if (d_score) *d_score = h->score.dev();
+    if (d_second_score) *d_second_score = h->second.dev();
+    if (d_nm) *d_nm = h->nm.dev();
+    if (d_ctg) *d_ctg = h->ctg.dev();
+    if (d_more) *d_more = h->more.dev();
     return KMX_OK;
 }
 
@@ -417,30 +413,20 @@ kmx_status kmx_supplementaries_view(kmx_supplementaries* h, const uint64_t** sup
                                     const int32_t** second_score, const uint16_t** nm, const uint32_t** ctg, const uint8_t** more)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_supplementaries_view: supplementaries handle is NULL");
-    if (!h->host_valid) {                                      // 8 + 1 bytes per public read, 31 per entry (35 with ctg)
-        const uint64_t ns = h->n_sup;
-        const bool f = h->filled;                              // else the empty result: one offset, 0
-        const kmx::HostCopy items[] = {{h->h_sup_off, h->sup_off, f ? h->nr + 1 : 0, 8}, {h->h_ent, h->ent, ns, 4}, {h->h_locus, h->locus, ns, 4},
-                                       {h->h_strand, h->strand, ns, 1}, {h->h_q0, h->q0, ns, 2}, {h->h_q1, h->q1, ns, 2}, {h->h_t0, h->t0, ns, 4},
-                                       {h->h_t1, h->t1, ns, 4}, {h->h_score, h->score, ns, 4}, {h->h_second, h->second, ns, 4}, {h->h_nm, h->nm, ns, 2},
-                                       {h->h_more, h->more, h->nr, 1}, {h->h_ctg, h->ctg, h->has_ctg ? ns : 0, 4}};
-        TRY_KMX(kmx::host_view("kmx_supplementaries_view", h->device, h->stream, items, std::size(items)));
-        if (!f) h->h_sup_off.as<uint64_t>()[0] = 0;
-        h->host_valid = true;
-    }
-    if (sup_off) *sup_off = h->h_sup_off.as<uint64_t>();
-    if (ent) *ent = h->h_ent.as<uint32_t>();
-    if (locus) *locus = h->h_locus.as<uint32_t>();
-    if (strand) *strand = h->h_strand.as<uint8_t>();
-    if (q0) *q0 = h->h_q0.as<uint16_t>();
-    if (q1) *q1 = h->h_q1.as<uint16_t>();
-    if (t0) *t0 = h->h_t0.as<uint32_t>();
-    if (t1) *t1 = h->h_t1.as<uint32_t>();
-    if (score) *score = h->h_score.as<int32_t>();
-    if (second_score) *second_score = h->h_second.as<int32_t>();
-    if (nm) *nm = h->h_nm.as<uint16_t>();
-    if (ctg) *ctg = h->has_ctg ? h->h_ctg.as<uint32_t>() : nullptr;
-    if (more) *more = h->h_more.as<uint8_t>();
+    TRY_KMX(kmx::host_view("kmx_supplementaries_view", *h));   // 8 + 1 bytes per public read, 31 per entry (35 with ctg)
+    if (sup_off) *sup_off = h->sup_off.host();
+    if (ent) *ent = h->ent.host();
+    if (locus) *locus = h->locus.host();
+    if (strand) *strand = h->strand.host();
+    if (q0) *q0 = h->q0.host();
+    if (q1) *q1 = h->q1.host();
+    if (t0) *t0 = h->t0.host();
+    if (t1) *t1 = h->t1.host();
+    if (score) *score = h->score.host();
+    if (second_score) *second_score = h->second.host();
+    if (nm) *nm = h->nm.host();
+    if (ctg) *ctg = h->has_ctg ? h->ctg.host() : nullptr;
+    if (more) *more = h->more.host();
     return KMX_OK;
 }
 

@@ -212,31 +212,36 @@ struct kmx_md {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t n_sel = 0, n_bytes = 0, n_mismatched = 0;
-    bool filled = false;                   // a call has succeeded since the last refusal or error: md_off holds n_sel + 1 offsets
-    Buf md_off, md, cnt, bsum, ctr;
-    Pinned h_ctr, h_md_off, h_md;
+    // results: the offsets per entry and the bytes of the strings
+    kmx::ArrOf<uint64_t> md_off{kmx::ARR_OFFSETS};
+    kmx::ArrOf<uint8_t> md;
+    Buf cnt, bsum, ctr;
+    Pinned h_ctr;
     bool host_valid = false;
-    void release()
+    std::vector<kmx::Arr*> results() { return {&md_off, &md}; }
+    std::vector<Buf*> scratch() { return {&cnt, &bsum, &ctr}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { n_sel = n_bytes = n_mismatched = 0; kmx::clear_arrays(*this); }
+    // a call has succeeded: the arrays expose what the counters say
+    void expose()
     {
-        for (Buf* b : {&md_off, &md, &cnt, &bsum, &ctr}) b->release();
-        for (Pinned* b : {&h_ctr, &h_md_off, &h_md}) b->release();
+        md_off.n = n_sel + 1;
+        md.n = n_bytes;
     }
-    void clear() { n_sel = n_bytes = n_mismatched = 0; filled = false; host_valid = false; }
 };
 
 struct kmx_mapq {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the call that filled the handle (the host view copies on it)
     uint64_t nr = 0, n_zero = 0, n_cap = 0;
-    Buf mapq, ctr;
-    Pinned h_ctr, h_mapq;
+    kmx::ArrOf<uint8_t> mapq;              // the result: one value per public read
+    Buf ctr;
+    Pinned h_ctr;
     bool host_valid = false;
-    void release()
-    {
-        for (Buf* b : {&mapq, &ctr}) b->release();
-        for (Pinned* b : {&h_ctr, &h_mapq}) b->release();
-    }
-    void clear() { nr = n_zero = n_cap = 0; host_valid = false; }
+    std::vector<kmx::Arr*> results() { return {&mapq}; }
+    std::vector<Buf*> scratch() { return {&ctr}; }
+    void release() { kmx::release_arrays(*this); }
+    void clear() { nr = n_zero = n_cap = 0; kmx::clear_arrays(*this); }
 };
 
 namespace {
@@ -245,13 +250,10 @@ kmx_status md_run(const char* fn, const kmx::IndexAccess& X, const kmx::ScriptsA
                   const uint8_t* letters, hipStream_t s, kmx_md* h, const kmx::ClipsAccess* K)
 {
     const uint64_t ns = S.n_sel;
-    h->stream = s;
-    h->clear();
-    (void)hipGetLastError();
     TRY_HIP(h->md_off.ensure((ns + 1) * 8));
     if (ns == 0) {                                             // no entry: no launch indexes an empty array
         TRY_HIP(hipMemsetAsync(h->md_off.p, 0, 8, s));
-        h->filled = true;
+        h->expose();
         return KMX_OK;
     }
     TRY_KMX(kmx::ensure_text(X, s));
@@ -279,7 +281,7 @@ kmx_status md_run(const char* fn, const kmx::IndexAccess& X, const kmx::ScriptsA
     h->n_sel = ns;
     h->n_bytes = n_bytes;
     h->n_mismatched = h->h_ctr.as<uint64_t>()[MD_N_MISMATCHED];
-    h->filled = true;
+    h->expose();
     return KMX_OK;
 }
 
@@ -307,10 +309,7 @@ kmx_status md_on_arrays(const char* fn, const kmx_index* index, const kmx::Scrip
 {
     const std::string who = std::string(fn) + ": ";
     kmx_md* h = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (h) h->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, h);
     if (S.flags & KMX_SCRIPT_M) return refuse(KMX_ERR_INVALID_ARGUMENT, "the scripts were made with KMX_SCRIPT_M: an MD needs '=' and 'X' apart");
     if (S.n_sel && S.device != device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the handles live on different devices");
     if (K && K->n_sel != S.n_sel) return refuse(KMX_ERR_INVALID_ARGUMENT, "the clips are not those of these scripts: n_sel differs");
@@ -323,20 +322,12 @@ kmx_status md_on_arrays(const char* fn, const kmx_index* index, const kmx::Scrip
     TRY_KMX(kmx::bind_handle(inout, S.device));
     h = *inout;
     hipStream_t s = stream ? stream : S.stream;
-    const kmx_status st = md_run(fn, X, S, start, end, bound, letters, s, h, K);
-    if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
-        (void)hipStreamSynchronize(s);
-        h->clear();
-    }
-    return st;
+    return kmx::run_into(h, s, [&] { return md_run(fn, X, S, start, end, bound, letters, s, h, K); });
 }
 
 kmx_status mapq_run(const kmx_placements* pl, const kmx_pairs* pr, const kmx_mapq_options& o, hipStream_t s, kmx_mapq* h)
 {
     const uint64_t nr = pl->nr;
-    h->stream = s;
-    h->clear();
-    (void)hipGetLastError();
     if (nr == 0) return KMX_OK;
     TRY_HIP(h->mapq.ensure(nr));
     TRY_HIP(h->ctr.ensure(MQ_COUNT * 8));
@@ -348,7 +339,7 @@ kmx_status mapq_run(const kmx_placements* pl, const kmx_pairs* pr, const kmx_map
     hipLaunchKernelGGL(k_mapq, dim3(grid_for(nr, kBlock)), dim3(kBlock), 0, s, Q, h->mapq.as<uint8_t>(), ctr);
     TRY_HIP(hipGetLastError());
     TRY_KMX(kmx::read_back("kmx_placements_mapq", s, ctr, h->h_ctr, MQ_COUNT * 8));
-    h->nr = nr;
+    h->nr = h->mapq.n = nr;
     h->n_zero = h->h_ctr.as<uint64_t>()[MQ_N_ZERO];
     h->n_cap = h->h_ctr.as<uint64_t>()[MQ_N_CAP];
     return KMX_OK;
@@ -419,23 +410,17 @@ kmx_status kmx_md_counts(const kmx_md* h, uint64_t* n_sel, uint64_t* n_bytes, ui
 kmx_status kmx_md_view_device(const kmx_md* h, const uint64_t** d_md_off, const uint8_t** d_md)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_md_view_device: md handle is NULL");
-    if (d_md_off) *d_md_off = h->filled ? h->md_off.as<uint64_t>() : nullptr;
-    if (d_md) *d_md = h->n_bytes ? h->md.as<uint8_t>() : nullptr;
+    if (d_md_off) *d_md_off = h->md_off.dev();
+    if (d_md) *d_md = h->md.dev();
     return KMX_OK;
 }
 
 kmx_status kmx_md_view(kmx_md* h, const uint64_t** md_off, const uint8_t** md)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_md_view: md handle is NULL");
-    if (!h->host_valid) {                                      // 8 bytes per entry and its string
-        const bool f = h->filled;                              // else the empty result: one offset, 0
-        const kmx::HostCopy items[] = {{h->h_md_off, h->md_off, f ? h->n_sel + 1 : 0, 8}, {h->h_md, h->md, h->n_bytes, 1}};
-        TRY_KMX(kmx::host_view("kmx_md_view", h->device, h->stream, items, std::size(items)));
-        if (!f) h->h_md_off.as<uint64_t>()[0] = 0;
-        h->host_valid = true;
-    }
-    if (md_off) *md_off = h->h_md_off.as<uint64_t>();
-    if (md) *md = h->h_md.as<uint8_t>();
+    TRY_KMX(kmx::host_view("kmx_md_view", *h));                // 8 bytes per entry and its string
+    if (md_off) *md_off = h->md_off.host();
+    if (md) *md = h->md.host();
     return KMX_OK;
 }
 
@@ -450,22 +435,14 @@ kmx_status kmx_placements_mapq(const kmx_placements* placements, const kmx_pairs
     if (o->cap > 254) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "cap > 254 (255 is SAM's \"unavailable\")");
     if (!placements) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, who + "placements handle is NULL");
     kmx_mapq* h = *inout;
-    auto refuse = [&](kmx_status st, const std::string& msg) {
-        if (h) h->clear();
-        return kmx::set_error(st, who + msg);
-    };
+    auto refuse = kmx::refuser(who, h);
     if (pairs && 2 * pairs->np != placements->nr) return refuse(KMX_ERR_INVALID_ARGUMENT, "the pairs are not those of these placements: 2 np differs from nr");
     if (pairs && placements->nr && pairs->device != placements->device) return refuse(KMX_ERR_INVALID_ARGUMENT, "the placements and the pairs live on different devices");
     kmx::DeviceGuard dg;
     TRY_KMX(kmx::bind_handle(inout, placements->device));
     h = *inout;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : placements->stream;
-    const kmx_status st = mapq_run(placements, pairs, *o, s, h);
-    if (st != KMX_OK) {                                        // the handle holds an empty result, not half of this one
-        (void)hipStreamSynchronize(s);
-        h->clear();
-    }
-    return st;
+    return kmx::run_into(h, s, [&] { return mapq_run(placements, pairs, *o, s, h); });
 }
 
 kmx_status kmx_mapq_counts(const kmx_mapq* h, uint64_t* nr, uint64_t* n_zero, uint64_t* n_cap)
@@ -480,7 +457,7 @@ kmx_status kmx_mapq_counts(const kmx_mapq* h, uint64_t* nr, uint64_t* n_zero, ui
 kmx_status kmx_mapq_view_device(const kmx_mapq* h, const uint8_t** d_mapq)
 {
     if (!h) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_mapq_view_device: mapq handle is NULL");
-    if (d_mapq) *d_mapq = h->nr ? h->mapq.as<uint8_t>() : nullptr;
+    if (d_mapq) *d_mapq = h->mapq.dev();
     return KMX_OK;
 }
 
@@ -491,12 +468,8 @@ kmx_status kmx_mapq_view(kmx_mapq* h, const uint8_t** mapq)
         if (mapq) *mapq = nullptr;
         return KMX_OK;
     }
-    if (!h->host_valid) {                                      // 1 byte per read
-        const kmx::HostCopy items[] = {{h->h_mapq, h->mapq, h->nr, 1}};
-        TRY_KMX(kmx::host_view("kmx_mapq_view", h->device, h->stream, items, 1));
-        h->host_valid = true;
-    }
-    if (mapq) *mapq = h->h_mapq.as<uint8_t>();
+    TRY_KMX(kmx::host_view("kmx_mapq_view", *h));              // 1 byte per read
+    if (mapq) *mapq = h->mapq.host();
     return KMX_OK;
 }
 

@@ -362,21 +362,29 @@ struct kmx_loci {
     int device = 0;
     hipStream_t stream = nullptr;          // the stream of the vote that filled the handle (the host view copies on it)
     uint64_t nr = 0, n_loci = 0, n_votes = 0, n_small = 0, n_large = 0;
-    // results
-    Buf locus_off, diag, span, votes, skipped;
+    // results; locus_off and skipped are handed out whatever the handle holds, and a handle that a vote has ever filled keeps the one
+    // offset 0 (kmx_windows_vote writes it on the device after an error)
+    kmx::ArrOf<uint64_t> locus_off{kmx::ARR_OFFSETS};
+    kmx::ArrOf<int64_t> diag;
+    kmx::ArrOf<uint32_t> span, votes, skipped;
     // scratch
     Buf vcnt, cls, smax, lcnt, lcount, sc_off, lvote_off, bsum, ctr, sc_diag, sc_span, sc_votes, ka, kb, va, vb, hstart, keep, krank, ufirst;
     const uint64_t* sorted_keys = nullptr; // the large reads' keys behind the sort: ka or kb
-    Pinned h_ctr, h_locus_off, h_diag, h_span, h_votes, h_skipped;
+    Pinned h_ctr;
     bool host_valid = false;
-    void release()
+    std::vector<kmx::Arr*> results() { return {&locus_off, &diag, &span, &votes, &skipped}; }
+    std::vector<Buf*> scratch()
     {
-        for (Buf* b : {&locus_off, &diag, &span, &votes, &skipped, &vcnt, &cls, &smax, &lcnt, &lcount, &sc_off, &lvote_off, &bsum, &ctr, &sc_diag,
-                       &sc_span, &sc_votes, &ka, &kb, &va, &vb, &hstart, &keep, &krank, &ufirst})
-            b->release();
-        for (Pinned* b : {&h_ctr, &h_locus_off, &h_diag, &h_span, &h_votes, &h_skipped}) b->release();
+        return {&vcnt, &cls, &smax, &lcnt, &lcount, &sc_off, &lvote_off, &bsum, &ctr, &sc_diag, &sc_span, &sc_votes, &ka, &kb, &va, &vb, &hstart, &keep,
+                &krank, &ufirst};
     }
-    void clear() { nr = n_loci = n_votes = n_small = n_large = 0; host_valid = false; }
+    void release() { kmx::release_arrays(*this); }
+    void clear()
+    {
+        nr = n_loci = n_votes = n_small = n_large = 0;
+        kmx::clear_arrays(*this);
+        locus_off.n = locus_off.p ? 1 : 0;
+    }
 };
 
 namespace {
@@ -453,6 +461,8 @@ kmx_status vote_run(const kmx::WindowsAccess& W, const kmx_vote_options& o, kmx_
     (void)hipGetLastError();
     TRY_HIP(L->locus_off.ensure((nr + 1) * 8));
     TRY_HIP(L->skipped.ensure(std::max<uint64_t>(nr, 1) * 4));
+    L->locus_off.n = nr + 1;
+    L->skipped.n = nr;
     TRY_HIP(hipMemsetAsync(L->locus_off.p, 0, (nr + 1) * 8, s));
     if (nr == 0) return KMX_OK;
     if (nr >= (uint64_t(1) << 31))
@@ -533,6 +543,7 @@ kmx_status vote_run(const kmx::WindowsAccess& W, const kmx_vote_options& o, kmx_
                                L->locus_off.as<uint64_t>(), L->diag.as<int64_t>(), L->span.as<uint32_t>(), L->votes.as<uint32_t>());
     });
     TRY_HIP(hipGetLastError());
+    kmx::expose({&L->diag, &L->span, &L->votes}, L->n_loci);
     return KMX_OK;
 }
 
@@ -583,9 +594,9 @@ kmx_status kmx_loci_view_device(const kmx_loci* l, const uint64_t** d_locus_off,
 {
     if (!l) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_loci_view_device: loci handle is NULL");
     if (d_locus_off) *d_locus_off = l->locus_off.as<uint64_t>();
-    if (d_diag) *d_diag = l->n_loci ? l->diag.as<int64_t>() : nullptr;
-    if (d_span) *d_span = l->n_loci ? l->span.as<uint32_t>() : nullptr;
-    if (d_votes) *d_votes = l->n_loci ? l->votes.as<uint32_t>() : nullptr;
+    if (d_diag) *d_diag = l->diag.dev();
+    if (d_span) *d_span = l->span.dev();
+    if (d_votes) *d_votes = l->votes.dev();
     if (d_skipped) *d_skipped = l->skipped.as<uint32_t>();
     return KMX_OK;
 }
@@ -594,20 +605,12 @@ kmx_status kmx_loci_view(kmx_loci* l, const uint64_t** locus_off, const int64_t*
                          const uint32_t** skipped)
 {
     if (!l) return kmx::set_error(KMX_ERR_INVALID_ARGUMENT, "kmx_loci_view: loci handle is NULL");
-    if (!l->host_valid) {
-        const uint64_t nr = l->nr, nl = l->n_loci;
-        const bool filled = l->locus_off.p != nullptr;         // else no vote has filled the handle yet: one offset, 0
-        const kmx::HostCopy items[] = {{l->h_locus_off, l->locus_off, filled ? nr + 1 : 0, 8}, {l->h_skipped, l->skipped, nr, 4},
-                                       {l->h_diag, l->diag, nl, 8}, {l->h_span, l->span, nl, 4}, {l->h_votes, l->votes, nl, 4}};
-        TRY_KMX(kmx::host_view("kmx_loci_view", l->device, l->stream, items, std::size(items)));
-        if (!filled) l->h_locus_off.as<uint64_t>()[0] = 0;
-        l->host_valid = true;
-    }
-    if (locus_off) *locus_off = l->h_locus_off.as<uint64_t>();
-    if (diag) *diag = l->h_diag.as<int64_t>();
-    if (span) *span = l->h_span.as<uint32_t>();
-    if (votes) *votes = l->h_votes.as<uint32_t>();
-    if (skipped) *skipped = l->h_skipped.as<uint32_t>();
+    TRY_KMX(kmx::host_view("kmx_loci_view", *l));
+    if (locus_off) *locus_off = l->locus_off.host();
+    if (diag) *diag = l->diag.host();
+    if (span) *span = l->span.host();
+    if (votes) *votes = l->votes.host();
+    if (skipped) *skipped = l->skipped.host();
     return KMX_OK;
 }
 

@@ -412,3 +412,38 @@ SMALL_SCORINGS = {
     "zeros_p3": dict(mismatch=0, gap_open=0, gap_extend=0, clip_penalty=3),
     "a2_b1_o0_x1_p1": dict(match=2, mismatch=1, gap_open=0, gap_extend=1, clip_penalty=1),
 }
+
+
+# ---- the tiny chain of tests/test_handle_views_gpu.py -------------------------------------------------------------------------------------------
+TINY_N = 6000
+TINY_E = 110                                                   # as SUPP_E: any locus with three votes is aligned, whatever the rest of the read does there
+TINY_CHAIN = dict(band=8, min_votes=3, max_edits=TINY_E, max_span=64)
+TINY_INSERT = dict(min_insert=100, max_insert=600)
+TINY_CONTIGS = (2500, 3500)
+
+
+@functools.lru_cache(maxsize=None)
+def tiny_text():
+    """6000 random letters; text[3000:3050] occurs again at 4400"""
+    t = synth.ranks(951, TINY_N, 4).copy()
+    t[4400:4450] = t[3000:3050]
+    t.setflags(write=False)
+    return t
+
+
+def tiny_pairs():
+    """Eight pairs as interleaved mates of about M letters, one entry at least for every handle of the chain: a split mate (a
+    supplementary part), a mate without an intact window (rescued), a mate over the segment that occurs twice (a secondary place), a
+    mate with a broken tail (clipped), one with a substitution and a deletion (MD, a site), a pair of random letters (unplaced) and
+    two ordinary pairs, one of them from the reverse strand.  The first two pairs are the quarter batch."""
+    t, cat = tiny_text(), np.concatenate
+    edits = t[3600:3751].copy()
+    edits[40] = (edits[40] + 1) % 4
+    return [cat([t[500:600], t[2000:2050]]), rc4(t[800:950]),
+            t[1000:1150].copy(), kill(rc4(t[1300:1450]), K),
+            t[2950:3100].copy(), rc4(t[3250:3400]),
+            cat([t[5000:5138], other(t[5138:5150])]), rc4(t[5300:5450]),
+            np.delete(edits, 90), rc4(t[3900:4050]),
+            synth.ranks(952, M, 4), synth.ranks(953, M, 4),
+            t[1600:1750].copy(), rc4(t[1900:2050]),
+            rc4(t[5700:5850]), t[5450:5600].copy()]

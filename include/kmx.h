@@ -1390,7 +1390,10 @@ void kmx_clips_free(kmx_clips* c);
  *      tl = j0, tr = L - j1, nm = the 'X' + 'I' + 'D' ops, the runs sl 'S' (only if sl > 0), the ops in forward order as BAM
  *      runs, sr 'S' (only if sr > 0), cflags[e] = KMX_CLIP_REALIGNED.  EVERY OTHER ENTRY is what kmx_scripts_clip makes of a
  *      LOW entry: the script's own runs, score = W[R], sl = sr = tl = tr = 0, nm = the 'X' + 'I' + 'D' lengths of the script,
- *      cflags[e] = KMX_CLIP_LOW.  An entry whose script is empty (mismatched) is not looked at: zeros, no runs, KMX_CLIP_LOW.
+ *      cflags[e] = KMX_CLIP_LOW.  An entry with runs whose handles do not belong together is such an entry, and neither its read
+ *      nor its text is looked at: no such r, a read range that is not one (roff[r] <= roff[r + 1] <= the letters that may be
+ *      read), m > KMX_ALIGN_MAX_READ, sel[e] >= n_loci, not start[l] <= end[l] <= n, dist[l] > KMX_ALIGN_MAX_EDITS, or
+ *      |m - L| > dist[l].  An entry whose script is empty (mismatched) is not looked at: zeros, no runs, KMX_CLIP_LOW.
  *      n_clipped counts the entries with sl + sr > 0, n_low those with the LOW bit.  So: a clipped side borders an '=' op, the
  *      first and the last kept op never are 'D', the '=' 'X' 'I' lengths sum to i1 - i0 and the '=' 'X' 'D' lengths to
  *      j1 - j0, and with min_score >= 0 score[e] is at least the score[e] of kmx_scripts_clip at the same options: the

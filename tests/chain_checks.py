@@ -92,6 +92,18 @@ def close_all(held):
             h.close()
 
 
+def snapshot(*handles):
+    """what untouched() compares after a call that must only read these handles"""
+    return [(h.host(), h.device_ptrs(), h.counts()) for h in handles]
+
+
+def untouched(before, *handles):
+    for (host, ptrs, counts), h in zip(before, handles):
+        assert h.device_ptrs() == ptrs and h.counts() == counts, f"{type(h).__name__}: pointers or counts changed"
+        for g, w in zip(h.host(), host):
+            assert g.dtype == w.dtype and np.array_equal(g, w), differ(type(h).__name__, g, w)
+
+
 def counters_of(pl, pr):
     c, k = dict(pl.counts(), n_pairs_ambiguous=pr.counts()["n_ambiguous"]), pr.counts()
     c.update({x: k[x] for x in ("np", "n_concordant", "n_discordant", "n_single", "n_unplaced")})

@@ -24,12 +24,54 @@ def runs_of(cig_off, n_ops, e):
     return a, min(max(int(cig_off[e + 1]), a), n_ops)
 
 
+CAUSES = ("bound", "no_read", "roff", "interval", "clip", "op", "inner_s", "text_len", "read_len")
+
+
+def mismatch_causes(l, bound, r, roff, n_letters, start, end, n, tl, tr, runs):
+    """Rule 3 of the contract for one entry with runs: the names of the causes that hold, [] for none.  A cause is looked at only where
+    the arrays it needs can be read: the interval's behind the bound's, the lengths' behind those of the read and of the interval.
+      bound      l >= the bound of start / end
+      no_read    there is no read r with read_sel_off[r] <= e < read_sel_off[r + 1]
+      roff       its roff range is not one: roff[r] <= roff[r + 1] <= the letters handed over does not hold
+      interval   not s <= t <= n
+      clip       tl + tr > t - s
+      op         an op other than = X I D S
+      inner_s    an S run that is neither the first nor the last
+      text_len   the = X D lengths differ from t - s - tl - tr
+      read_len   the = X I S lengths differ from m"""
+    out = []
+    if l >= bound:
+        out.append("bound")
+    if r is None:
+        out.append("no_read")
+    elif not int(roff[r]) <= int(roff[r + 1]) <= n_letters:
+        out.append("roff")
+    if l < bound:
+        s, t = int(start[l]), int(end[l])
+        if not s <= t <= n:
+            out.append("interval")
+        elif tl + tr > t - s:
+            out.append("clip")
+    if any(op not in (OP_EQ, OP_X, OP_I, OP_D, OP_S) for op, _ in runs):
+        out.append("op")
+    if any(op == OP_S and k not in (0, len(runs) - 1) for k, (op, _) in enumerate(runs)):
+        out.append("inner_s")
+    if out:
+        return out
+    if sum(ln for op, ln in runs if op in (OP_EQ, OP_X, OP_D)) != t - s - tl - tr:
+        out.append("text_len")
+    if sum(ln for op, ln in runs if op in (OP_EQ, OP_X, OP_I, OP_S)) != int(roff[r + 1]) - int(roff[r]):
+        out.append("read_len")
+    return out
+
+
 def add(counts, lo, hi, sigma, scripts, clips, start, end, ranks, roff, mapq=None, *, n, bound=None, min_score=NO_FLOOR, min_mapq=0,
-        skip_low=False):
+        skip_low=False, why=None):
     """counts[(sigma + 3, hi - lo)] += the pileup of the entries, in place.  scripts = (read_sel_off, sel, cig_off, cigar), the host view
     of a Scripts; clips = the host view of its Clips (score, sl, sr, tl, tr, nm, cflags, cig_off, cigar) or None; start / end: the
     arrays that sel indexes (`bound` of them: all by default); ranks / roff: the reads the entries run over; mapq: one value per pair of
-    internal reads, or None; n: the text length.  Returns dict(n_added, n_filtered, n_mismatched, n_cells) of this call."""
+    internal reads, or None; n: the text length; why: a dict that receives, for every entry that reaches rule 3, the causes that make it
+    MISMATCHED ([] for an ADDED one).  Returns dict(n_added, n_filtered, n_mismatched, n_cells) of this call."""
     read_sel_off, sel, cig_off, cigar = scripts
     if clips is not None:
         score, _, _, ctl, ctr, _, cflags, cig_off, cigar = clips
@@ -64,19 +106,14 @@ def add(counts, lo, hi, sigma, scripts, clips, start, end, ranks, roff, mapq=Non
             continue
         # 3. the pass over the runs in front of any add
         l = int(sel[e])
-        bad = l >= bound or r is None
-        if not bad:
-            s, t = int(start[l]), int(end[l])
-            q = ranks[int(roff[r]):int(roff[r + 1])]
-            bad = not (s <= t <= n) or tl + tr > t - s
-        if not bad:
-            bad = any(op not in (OP_EQ, OP_X, OP_I, OP_D, OP_S) for op, _ in runs)
-            bad = bad or any(op == OP_S and k not in (0, len(runs) - 1) for k, (op, _) in enumerate(runs))
-            bad = bad or sum(ln for op, ln in runs if op in (OP_EQ, OP_X, OP_D)) != t - s - tl - tr
-            bad = bad or sum(ln for op, ln in runs if op in (OP_EQ, OP_X, OP_I, OP_S)) != len(q)
-        if bad:
+        causes = mismatch_causes(l, bound, r, roff, len(ranks), start, end, n, tl, tr, runs)
+        if why is not None:
+            why[e] = causes
+        if causes:
             out["n_mismatched"] += 1
             continue
+        s, t = int(start[l]), int(end[l])
+        q = ranks[int(roff[r]):int(roff[r + 1])]
         # 4. the replay
         out["n_added"] += 1
         t0, t1 = s + tl, t - tr

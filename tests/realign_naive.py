@@ -26,10 +26,16 @@ Every other entry is what kmx_scripts_clip makes of a LOW entry (tests/clip_naiv
 sl = sr = tl = tr = 0, nm = its X + I + D lengths, cflags = LOW (1).  An entry whose script is empty is not looked at: zeros, no
 runs, LOW.
 
+Handles that do not belong together (guards()).  An entry with runs is such an "other entry", whole and LOW, and neither its read
+nor its text is looked at, when there is no read r for it; when its read range is not one (roff[r] <= roff[r + 1] <= the letters
+handed over); when m > MAX_READ; when sel[e] is not below the number of loci; when start[l] <= end[l] <= n does not hold; when
+dist[l] > MAX_EDITS; or when |m - L| > dist[l].  Every entry of handles that do belong together passes all of them.
+
 realign() returns (score i32, sl u16, sr u16, tl u16, tr u16, nm u16, cflags u8, cig_off u64[n_sel + 1], cigar u32, n_clipped, n_low)."""
 import numpy as np
 
 from tests import clip_naive as cn
+from tests.align_naive import MAX_EDITS, MAX_READ
 
 OP_I, OP_D, OP_S, OP_EQ, OP_X = cn.OP_I, cn.OP_D, cn.OP_S, cn.OP_EQ, cn.OP_X
 LOW, REALIGNED = 1, 2
@@ -153,20 +159,66 @@ def realign_one(q, t, d, sigma, script_runs, **options):
     return runs, v, sl, sr, j0, len(t) - j1, sum(op != OP_EQ for op in ops), REALIGNED
 
 
-def realign(read_sel_off, sel, cig_off, cigar, dist, start, end, ranks, roff, text, sigma, **options):
+GUARDS = ("no_read", "roff", "long_read", "interval", "dist", "gap", "locus")
+
+
+def guards(l, n_loci, r, roff, n_letters, dist, start, end, n):
+    """The names of the guards that keep entry (l, r) from the band, [] for none: the rule for handles that do not belong together.
+      no_read    there is no read r with read_sel_off[r] <= e < read_sel_off[r + 1]
+      roff       its read range is not one: roff[r] <= roff[r + 1] <= the letters handed over does not hold
+      long_read  m > MAX_READ
+      locus      sel[e] is not below the number of loci
+      interval   start <= end <= n does not hold
+      dist       dist > MAX_EDITS (a locus that was skipped or not aligned among them)
+      gap        |m - L| > dist
+    A guard is looked at only where the arrays it needs can be read."""
+    out = []
+    m = None
+    if r is None:
+        out.append("no_read")
+    elif not int(roff[r]) <= int(roff[r + 1]) <= n_letters:
+        out.append("roff")
+    else:
+        m = int(roff[r + 1]) - int(roff[r])
+        if m > MAX_READ:
+            out.append("long_read")
+    if l >= n_loci:
+        return out + ["locus"]
+    s, t, d = int(start[l]), int(end[l]), int(dist[l])
+    if not s <= t <= n:
+        out.append("interval")
+    if d > MAX_EDITS:
+        out.append("dist")
+    if not out and abs(m - (t - s)) > d:
+        out.append("gap")
+    return out
+
+
+def realign(read_sel_off, sel, cig_off, cigar, dist, start, end, ranks, roff, text, sigma, n_loci=None, why=None, **options):
     """The nine clips arrays and the two counters of a scripts handle (read_sel_off, sel, cig_off, cigar), its alignments (dist, start,
-    end), the internal reads (ranks, roff) and the text."""
+    end; n_loci of them: all by default), the internal reads (ranks, roff) and the text.  why: a dict that receives guards() of every
+    entry with runs."""
     n = len(sel)
-    read_of = np.repeat(np.arange(len(read_sel_off) - 1), np.diff(np.asarray(read_sel_off, np.int64)))
+    n_loci = len(dist) if n_loci is None else n_loci
+    nr = len(roff) - 1
     score, cflags = np.zeros(n, np.int32), np.zeros(n, np.uint8)
     sl, sr, tl, tr, nm = (np.zeros(n, np.uint16) for _ in range(5))
     off, out = [0], []
     for e in range(n):
-        l, r = int(sel[e]), int(read_of[e])
-        q = ranks[int(roff[r]):int(roff[r + 1])]
-        t = text[int(start[l]):int(end[l])]
-        runs, score[e], sl[e], sr[e], tl[e], tr[e], nm[e], cflags[e] = realign_one(q, t, int(dist[l]), sigma, cigar[int(cig_off[e]):int(cig_off[e + 1])],
-                                                                                   **options)
+        script = [int(v) for v in cigar[int(cig_off[e]):int(cig_off[e + 1])]]
+        l = int(sel[e])
+        r = int(np.searchsorted(read_sel_off, e, side="right")) - 1         # the read with read_sel_off[r] <= e < read_sel_off[r + 1]
+        if not (0 <= r < nr and int(read_sel_off[r]) <= e < int(read_sel_off[r + 1])):
+            r = None
+        held = guards(l, n_loci, r, roff, len(ranks), dist, start, end, len(text)) if script else []
+        if why is not None and script:
+            why[e] = held
+        if held:                                               # handles that do not belong together: whole and LOW, nothing else is read
+            runs, score[e], sl[e], sr[e], tl[e], tr[e], nm[e], cflags[e] = whole(script, **options)
+        else:
+            q = ranks[int(roff[r]):int(roff[r + 1])] if script else ranks[:0]
+            t = text[int(start[l]):int(end[l])] if script else text[:0]
+            runs, score[e], sl[e], sr[e], tl[e], tr[e], nm[e], cflags[e] = realign_one(q, t, int(dist[l]) if script else 0, sigma, script, **options)
         out += runs
         off.append(len(out))
     n_clipped = int(((sl.astype(np.int64) + sr) > 0).sum())

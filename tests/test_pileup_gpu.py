@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tests import pileup_naive as pn
-from tests.chain_checks import check_pileup, close_all, dev_array, doubled, pileup_want, refused, same
+from tests.chain_checks import check_pileup, close_all, dev_array, doubled, pileup_want, refused, same, snapshot, untouched
 from tests.chain_data import (CHAIN as PAIR_CHAIN, CLIP_CHAIN as CHAIN, CLIP_SIZES as SIZES, CLIPS, COMP4, COMPLEMENT, INSERT, K, M, N, PAIR_WORKLOADS, SCRIPTS,
                               boundary_reads, clip_planted_reads, clip_text as text, other, pairs_of, rc4, realign_batch, rescue_pairs_of, table_reads,
                               text_of)
@@ -38,17 +38,6 @@ def check_sites(st, counts, lo, txt, sigma, ctg_off=None, **opt):
         if p:
             assert np.array_equal(dev_array(p, g.size, g.dtype), g), name
     return dict(zip(SITES, got))
-
-
-def snapshot(*handles):
-    return [(h.host(), h.device_ptrs(), h.counts()) for h in handles]
-
-
-def untouched(before, *handles):
-    for (host, ptrs, counts), h in zip(before, handles):
-        assert h.device_ptrs() == ptrs and h.counts() == counts
-        for g, w in zip(h.host(), host):
-            assert g.dtype == w.dtype and np.array_equal(g, w)
 
 
 @pytest.fixture(scope="module")

@@ -2,9 +2,10 @@
 
 Only what the hot path needs lives here:
   csrc/      hand-written gfx950 kernels + the C-ABI (include/kmx.h)
-  engine.py  ctypes binding of the C-ABI (plumbing for tests / bench / smoke)
+  engine.py  ctypes binding of the C-ABI, the handle classes of the mapping chain, Index (plumbing for tests / bench / smoke)
+  sam.py     the SAM text written from the handles' host views: pure numpy, no library, no device
   synth.py   portable synthetic inputs
   build.py   hipcc build of libkmx.so
 The C++ host mirror of the reference's template surface is in include/kmer_index_amd/.
 """
-from . import build, engine, synth  # noqa: F401
+from . import build, engine, sam, synth  # noqa: F401

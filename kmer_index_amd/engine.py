@@ -1,4 +1,7 @@
-"""ctypes binding of the C-ABI (include/kmx.h) — plumbing for tests, bench.py and smoke().
+"""ctypes binding of the C-ABI (include/kmx.h) — plumbing for tests, bench.py and smoke().  Three parts, in this order: the binding
+itself (the structures, SIGNATURES, lib()); Result and the handle classes of the mapping chain (_Handle and its subclasses, whose
+host() views are named tuples of the fields each class declares); Index with the chain builders.  The SAM text written from those
+views is sam.py, pure numpy; its names are re-exported here, and the handles' string methods pass their host views to it.
 
 Every search goes through libkmx.so (hand-written gfx950 kernels).  There is no Python or
 CPU search path in this package: when the library or a device is missing, calls raise.
@@ -11,6 +14,8 @@ import os
 import numpy as np
 
 from . import build as _build
+from .sam import (CIGAR_OPS, NO_CONTIG, PAIR_CONCORDANT, _clip_fields, _first_given, _letters_table, _runs_strings,  # noqa: F401
+                  concat_sequences, sa_strings, sam_header, sam_lines, sam_pair_fields, sam_supplementary_lines, supplementary_mapq, xa_strings)
 
 KMX_MAX_KS = 32
 KMX_MAX_DEVICES = 16
@@ -25,13 +30,12 @@ APPROX_LOCI, APPROX_BEST = 2, 4
 TILE_Q_NONE, TILE_Q_PARTITION, TILE_Q_SCAN = 0, 1, 2
 ALIGN_MAX_EDITS, ALIGN_MAX_READ, ALIGN_SKIPPED, ALIGN_NONE = 250, 1024, 254, 255
 SCRIPT_ALL, SCRIPT_M = 1, 2
-CIGAR_OPS = "MIDNSHP=X"
 PAIR_FR, PAIR_RF, PAIR_FF = 0, 1, 2
-PAIR_UNPLACED, PAIR_CONCORDANT, PAIR_DISCORDANT, PAIR_MATE1_ONLY, PAIR_MATE2_ONLY = 0, 1, 2, 3, 4
+PAIR_UNPLACED, PAIR_DISCORDANT, PAIR_MATE1_ONLY, PAIR_MATE2_ONLY = 0, 2, 3, 4         # (PAIR_CONCORDANT = 1, CIGAR_OPS, NO_CONTIG: from sam.py)
 PAIR_NO_PENALTY, PAIR_NO_SCORE = 0xFFFFFFFF, 0xFFFF
 RESCUE_DISCORDANT, RESCUE_MAX_INSERT = 1, 65536
 RESCUE_NONE, RESCUE_FOUND, RESCUE_CONCORDANT, RESCUE_TAKEN = 0, 1, 2, 3
-LOCATE_MATES, NO_CONTIG = 1, 0xFFFFFFFF
+LOCATE_MATES = 1
 SECONDARY_MAX, SECONDARY_NO_DELTA = 32, 0xFFFFFFFF
 CLIP_LOW, CLIP_REALIGNED = 1, 2
 SUPPLEMENTARY_MAX = 8
@@ -511,12 +515,15 @@ class _Handle:
 
     _counts_of = (the kmx_*_counts function, the names of its out-parameters in order): counts() is a dict under those names.
     _view_of = (stem, fields): kmx_<stem>_view fills one host pointer per field and kmx_<stem>_view_device one device pointer;
-        a field is (name, dtype, length), the length a name of counts() or a function of that dict.  host() is the tuple of the
-        fields as numpy copies, device_ptrs() the tuple of the device pointers, both in the order of the fields."""
+        a field is (name, dtype, length), the length a name of counts() or a function of that dict.  host() is the named tuple of
+        the fields as numpy copies, device_ptrs() the tuple of the device pointers, both in the order of the fields.
+    _optional = the names of the fields that the C view may hand out as NULL for "not there": host() has None for such a field."""
 
     _free = None                    # the name of the handle's kmx_*_free
     _counts_of = None
     _view_of = None
+    _optional = ()
+    _view_types = {}                # (class, number of fields): the named tuple of that prefix of the class's fields
 
     def __init__(self):
         self._h = C.c_void_p()
@@ -535,12 +542,17 @@ class _Handle:
         return tuple(x.value for x in p)
 
     def _arrays(self, ptrs):
-        """Copies of the fields that the host pointers `ptrs` (those of the first len(ptrs) fields) point at."""
+        """Copies of the fields that the host pointers `ptrs` (those of the first len(ptrs) fields) point at, under their names."""
         c = self.counts()
-        return tuple(_view(p, n(c) if callable(n) else c[n], dtype).copy() for p, (_, dtype, n) in zip(ptrs, self._view_of[1]))
+        fields = self._view_of[1][:len(ptrs)]
+        key = (type(self), len(fields))
+        if key not in self._view_types:
+            self._view_types[key] = collections.namedtuple(f"{type(self).__name__}View", [name for name, _, _ in fields])
+        return self._view_types[key](*(None if name in self._optional and not p else _view(p, n(c) if callable(n) else c[n], dtype).copy()
+                                       for p, (name, dtype, n) in zip(ptrs, fields)))
 
     def host(self):
-        """The fields of _view_of as numpy copies, in their order."""
+        """The fields of _view_of as numpy copies under their names, in their order."""
         stem, fields = self._view_of
         return self._arrays(self._ptrs(f"kmx_{stem}_view", len(fields)))
 
@@ -674,8 +686,8 @@ class Scripts(_Handle):
 
     def strings(self):
         """One CIGAR string per entry, e.g. "50=1X30=1D69=" ("" for an entry without a script)."""
-        _, _, cig_off, cigar = self.host()
-        return _runs_strings(cig_off, cigar)
+        h = self.host()
+        return _runs_strings(h.cig_off, h.cigar)
 
     def clip(self, match=1, mismatch=4, gap_open=6, gap_extend=1, clip_penalty=5, min_score=0, stream=0, clips=None):
         """kmx_scripts_clip: every entry trimmed to the best-scoring part of its runs under the affine scoring (a gap run of len
@@ -790,12 +802,6 @@ def _md_call(fn, index, handles, letters, stream, md):
     return out
 
 
-def _runs_strings(cig_off, cigar):
-    """One CIGAR string per entry from the offsets and the runs (len << 4 | op)."""
-    runs = [f"{int(v) >> 4}{CIGAR_OPS[int(v) & 15]}" for v in cigar]
-    return ["".join(runs[int(a):int(b)]) for a, b in zip(cig_off[:-1], cig_off[1:])]
-
-
 class Clips(_Handle):
     """Owns a kmx_clips handle (kmx_scripts_clip): every entry of a Scripts trimmed to the best-scoring part of its runs, with the
     score and the letters clipped off either side.  Entry e is entry e of the Scripts."""
@@ -818,7 +824,7 @@ class Clips(_Handle):
     def strings(self):
         """One CIGAR string per entry with S at the clipped ends, e.g. "1S149=" ("" for an entry without a script)."""
         h = self.host()
-        return _runs_strings(h[7], h[8])
+        return _runs_strings(h.cig_off, h.cigar)
 
     def md(self, index, scripts, source, letters, stream=0, md=None):
         """kmx_clips_md (source: the Alignments the scripts were made from) or kmx_clips_rescues_md (source: the Rescues): the MD
@@ -859,27 +865,6 @@ class Clips(_Handle):
         return _made_from(out, self, reads=reads)
 
 
-def _clip_fields(entry, clips):
-    """entry[nr]: the entry of every public read among those of `clips`, -1 for none -> (tl i64, nm i64, score i64, has bool)"""
-    entry = np.asarray(entry, np.int64)
-    score, _, _, tl, _, nm, _, _, _ = clips.host()
-    has = entry >= 0
-    at = np.where(has, entry, 0)
-    if score.size == 0:
-        zero = np.zeros(entry.size, np.int64)
-        return zero, zero.copy(), zero.copy(), np.zeros(entry.size, bool)
-    return tuple(np.where(has, a.astype(np.int64)[at], 0) for a in (tl, nm, score)) + (has,)
-
-
-def _letters_table(letters):
-    """The rank -> output byte table as a contiguous uint8 array."""
-    if isinstance(letters, str):
-        letters = letters.encode("ascii")
-    if isinstance(letters, (bytes, bytearray)):
-        return np.frombuffer(bytes(letters), np.uint8).copy()
-    return np.ascontiguousarray(letters, np.uint8)
-
-
 class Md(_Handle):
     """Owns a kmx_md handle (kmx_scripts_md, kmx_rescues_md): the MD string of every entry of a Scripts."""
 
@@ -903,7 +888,7 @@ class Mapq(_Handle):
 
     def host(self):
         """The one field itself, not a tuple of one."""
-        return super().host()[0]
+        return super().host().mapq
 
 
 class Pileup(_Handle):
@@ -917,7 +902,7 @@ class Pileup(_Handle):
     def planes(self):
         """The counters as a (n_channels, hi - lo) uint32 array (a copy); waits for the kernels of the last call."""
         c = self.counts()
-        return self.host()[0].reshape(c["n_channels"], c["hi"] - c["lo"])
+        return self.host().counts.reshape(c["n_channels"], c["hi"] - c["lo"])
 
     def sites(self, index, min_depth=1, min_alt=1, frac=(1, 5), stream=0, sites=None):
         """kmx_pileup_sites: one record per position and channel other than the reference letter (a letter, DEL or INS; never OTHER)
@@ -936,12 +921,7 @@ class Sites(_Handle):
     _counts_of = ("kmx_sites_counts", ("n_sites", "n_covered"))
     _view_of = ("sites", (("pos", np.uint32, "n_sites"), ("ref", np.uint8, "n_sites"), ("alt", np.uint8, "n_sites"), ("depth", np.uint32, "n_sites"),
                           ("count", np.uint32, "n_sites"), ("ref_count", np.uint32, "n_sites"), ("ctg", np.uint32, "n_sites")))
-
-    def host(self):
-        """ctg is None when the index has no contig table."""
-        p = self._ptrs("kmx_sites_view", 7)
-        out = self._arrays(p)
-        return out[:6] + (out[6] if p[6] else None,)
+    _optional = ("ctg",)            # None when the index has no contig table
 
 
 class StrandReads(_Handle):
@@ -982,7 +962,7 @@ class _PerRead:
         """(tl, nm, score, has) per public read from the Clips of scripts().clip(): the text letters clipped off the left, the
         clipped NM and the score of the read's entry, has False (and zeros) where cigars(scripts) has none.  For sam_lines (the
         rescue's as the second of a tuple)."""
-        return _clip_fields(self._entries(scripts), clips)
+        return _clip_fields(self._entries(scripts), clips.host())
 
 
 class Placements(_PerRead, _Handle):
@@ -1007,8 +987,8 @@ class Placements(_PerRead, _Handle):
 
     def _entries(self, scripts):
         """the entry of every public read's winner, -1 for an unplaced read"""
-        strand = self.host(best2=False)[1]
-        read_sel_off = scripts.host()[0]
+        strand = self.host(best2=False).strand
+        read_sel_off = scripts.host().read_sel_off
         out = []
         for i, s in enumerate(strand):
             r = 2 * i + int(s)
@@ -1044,34 +1024,6 @@ class Placements(_PerRead, _Handle):
         return _made_from(out, self)
 
 
-def xa_strings(sec_off, dist, start, ctg, cigars, strand_names="+-", located=None, rname=None, shift=None):
-    """The XA:Z: value of every public read from the host arrays of a Secondaries and one CIGAR per entry: "" or items
-    rname,<strand><pos>,CIGAR,NM; in bwa's form, pos 1-based.  located=(names, ctg_off) with ctg: the entry's contig name and a
-    contig-local pos; otherwise rname and the position in the text.  shift: the text letters clipped off the left of every entry
-    (the tl of a Clips; dist and cigars then are the clipped nm and strings), added to its position.  Pure Python: no device is
-    needed."""
-    sec_off = np.asarray(sec_off, np.uint64)
-    if shift is not None:
-        start = np.asarray(start, np.int64) + np.asarray(shift, np.int64)
-    if located is not None and ctg is None:
-        raise ValueError("xa: located needs the ctg of a Secondaries made under a contig table")
-    if located is None and rname is None:
-        raise ValueError("xa: give rname, or located=(names, ctg_off)")
-    out = []
-    for i in range((sec_off.size - 1) // 2):
-        items = []
-        for s in (0, 1):
-            for e in range(int(sec_off[2 * i + s]), int(sec_off[2 * i + s + 1])):
-                if located is not None:
-                    names, ctg_off = located
-                    name, pos = names[int(ctg[e])], int(start[e]) - int(ctg_off[int(ctg[e])]) + 1
-                else:
-                    name, pos = rname, int(start[e]) + 1
-                items.append(f"{name},{strand_names[s]}{pos},{cigars[e] or '*'},{int(dist[e])};")
-        out.append("".join(items))
-    return out
-
-
 class Secondaries(_Handle):
     """Owns a kmx_secondaries handle (kmx_placements_secondaries): up to N further places per public read, the entries of internal
     read 2i + s being those of read i on strand s."""
@@ -1080,12 +1032,7 @@ class Secondaries(_Handle):
     _counts_of = ("kmx_secondaries_counts", ("nr", "n_sec", "n_multi", "n_truncated"))
     _view_of = ("secondaries", (("sec_off", np.uint64, lambda c: 2 * c["nr"] + 1), ("locus", np.uint32, "n_sec"), ("dist", np.uint8, "n_sec"),
                                 ("start", np.uint32, "n_sec"), ("end", np.uint32, "n_sec"), ("ctg", np.uint32, "n_sec"), ("more", np.uint8, "nr")))
-
-    def host(self):
-        """ctg is None when the alignments carried no contig table."""
-        p = self._ptrs("kmx_secondaries_view", 7)
-        out = self._arrays(p)
-        return out[:5] + (out[5] if p[5] else None,) + out[6:]
+    _optional = ("ctg",)            # None when the alignments carried no contig table
 
     def scripts(self, index, reads, m=False, scratch_bytes=0, scripts=None):
         """kmx_secondaries_scripts: the CIGAR of every entry (for a reverse entry that of the reverse complement against the forward
@@ -1108,56 +1055,13 @@ class Secondaries(_Handle):
         the entries.  located=(names, ctg_off): the name of the entry's contig and a contig-local pos (the handle must carry ctg);
         otherwise `rname` names the one reference.  scripts: the Scripts of scripts().  clips (the Clips of scripts.clip()): every
         entry's position is shifted by its tl, and its CIGAR and NM are the clipped ones."""
-        sec_off, _, dist, start, _, ctg, _ = self.host()
+        h = self.host()
         if clips is None:
-            return xa_strings(sec_off, dist, start, ctg, self.cigars(scripts), strand_names, located, rname)
-        if clips.counts()["n_sel"] != dist.size:
+            return xa_strings(h.sec_off, h.dist, h.start, h.ctg, self.cigars(scripts), strand_names, located, rname)
+        if clips.counts()["n_sel"] != h.dist.size:
             raise ValueError("xa: the clips are not those of these entries")
-        h = clips.host()
-        return xa_strings(sec_off, h[5], start, ctg, _runs_strings(h[7], h[8]), strand_names, located, rname, shift=h[3])
-
-
-def supplementary_mapq(score, second_score, cap=60):
-    """The MAPQ of every part from its score and its runner-up's: 0 where second_score >= score, else
-    min(cap, cap (score - second_score) // score).  A stated gap rule like kmx_placements_mapq's, not a calibrated one.  Pure numpy."""
-    score = np.asarray(score, np.int64)
-    second = np.asarray(second_score, np.int64)
-    q = np.minimum(cap, cap * (score - second) // np.maximum(score, 1))
-    return np.where(second >= score, 0, q).astype(np.uint8)
-
-
-def sa_strings(sup_off, primary, entries, located=None, rname=None, strand_names="+-"):
-    """The SA:Z: values of the records of every public read.  primary = (pos, strand, cigars, mapq, nm[, ctg]) with one value per
-    public read, entries = (pos, strand, cigars, mapq, nm[, ctg]) with one per entry of a Supplementaries (sup_off counts them per
-    read): pos the 0-based position of the clipped record in the text (start + tl; t0), cigars the clipped CIGARs.  The records of a
-    read are its primary and then its entries, each as rname,pos,strand,CIGAR,mapQ,NM; with pos 1-based; located=(names, ctg_off)
-    with ctg: the contig's name and a contig-local pos, otherwise `rname` and the position in the text.  Returns per read the list
-    [the primary's value, entry 0's, ...]: every record's value is the other records of its read, in that order ("" for the primary
-    of a read without entries).  Pure Python: no device is needed."""
-    sup_off = np.asarray(sup_off, np.uint64)
-    if located is None and rname is None:
-        raise ValueError("sa: give rname, or located=(names, ctg_off)")
-    if located is not None and (len(primary) < 6 or len(entries) < 6 or primary[5] is None or entries[5] is None):
-        raise ValueError("sa: located needs the ctg of the primaries and of the entries")
-
-    def record(src, k):
-        if located is not None:
-            names, ctg_off = located
-            c = int(src[5][k])
-            name, pos = names[c], int(src[0][k]) - int(ctg_off[c]) + 1
-        else:
-            name, pos = rname, int(src[0][k]) + 1
-        return f"{name},{pos},{strand_names[int(src[1][k])]},{src[2][k] or '*'},{int(src[3][k])},{int(src[4][k])};"
-
-    out = []
-    for i in range(sup_off.size - 1):
-        a, b = int(sup_off[i]), int(sup_off[i + 1])
-        if a == b:
-            out.append([""])
-            continue
-        recs = [record(primary, i)] + [record(entries, x) for x in range(a, b)]
-        out.append(["".join(r for k, r in enumerate(recs) if k != j) for j in range(len(recs))])
-    return out
+        c = clips.host()
+        return xa_strings(h.sec_off, c.nm, h.start, h.ctg, _runs_strings(c.cig_off, c.cigar), strand_names, located, rname, shift=c.tl)
 
 
 class Supplementaries(_Handle):
@@ -1173,6 +1077,7 @@ class Supplementaries(_Handle):
                                     ("strand", np.uint8, "n_sup"), ("q0", np.uint16, "n_sup"), ("q1", np.uint16, "n_sup"), ("t0", np.uint32, "n_sup"),
                                     ("t1", np.uint32, "n_sup"), ("score", np.int32, "n_sup"), ("second_score", np.int32, "n_sup"),
                                     ("nm", np.uint16, "n_sup"), ("ctg", np.uint32, "n_sup"), ("more", np.uint8, "nr")))
+    _optional = ("ctg",)            # None when the alignments carried no contig table
 
     def __init__(self):
         super().__init__()
@@ -1188,26 +1093,20 @@ class Supplementaries(_Handle):
         self.all_scripts = self.all_clips = None
         self._owns = False
 
-    def host(self):
-        """ctg is None when the alignments carried no contig table."""
-        p = self._ptrs("kmx_supplementaries_view", 13)
-        out = self._arrays(p)
-        return out[:11] + (out[11] if p[11] else None,) + out[12:]
-
     def mapq(self, cap=60):
         """supplementary_mapq of every entry (u8[n_sup])."""
         h = self.host()
-        return supplementary_mapq(h[8], h[9], cap)
+        return supplementary_mapq(h.score, h.second_score, cap)
 
     def cigars(self, clips=None):
         """One clipped CIGAR string per entry, from `clips` (default all_clips), the Clips the handle was made from."""
         strings = (clips or self.all_clips).strings()
-        return [strings[int(e)] for e in self.host()[1]]
+        return [strings[int(e)] for e in self.host().ent]
 
     def mds(self, md):
         """One MD string per entry from the Md of the all-loci clips (Clips.md over the all-loci scripts and the alignments)."""
         strings = md.strings()
-        return [strings[int(e)] for e in self.host()[1]]
+        return [strings[int(e)] for e in self.host().ent]
 
     def sa(self, placements_host, cigars, clip_fields, mapq, cap=60, located=None, located_host=None, rname=None, clips=None, strand_names="+-"):
         """sa_strings of this handle: per public read the SA:Z: values of its primary and of its entries.  placements_host:
@@ -1216,55 +1115,13 @@ class Supplementaries(_Handle):
         their CIGARs from `clips` (default all_clips) and their MAPQ from mapq(cap).  located=(names, ctg_off) with located_host
         (Located.host()): contig names and contig-local positions; otherwise `rname` names the one reference."""
         h = self.host()
-        strand, start = np.asarray(placements_host[1]), np.asarray(placements_host[3], np.int64)
-        pos = start + np.asarray(clip_fields[0], np.int64)
-        primary = (pos, np.where(strand == 1, 1, 0), cigars, mapq, clip_fields[1], None if located_host is None else located_host[0])
-        entries = (h[6], h[3], self.cigars(clips), self.mapq(cap), h[10], h[11])
-        return sa_strings(h[0], primary, entries, located, rname, strand_names)
-
-
-def sam_supplementary_lines(primary_lines, ranks, roff, letters, complement, sigma, sup_host, cigars, mds, mapq, sa, rname=None, located=None):
-    """The supplementary SAM lines (FLAG 0x800, no newline) of a batch, read after read in the order of the entries.
-    primary_lines: the lines of sam_lines for the same reads (QNAME, the pair bits of FLAG, RNEXT and PNEXT are taken from them);
-    sup_host: Supplementaries.host(); cigars, mds, mapq: one per entry (Supplementaries.cigars / .mds / .mapq); sa: what sa_strings
-    returned.  A line has FLAG 0x800, plus 0x10 on strand 1, plus the primary's pair bits (0x1, 0x8, 0x20, 0x40, 0x80: not 0x2);
-    RNAME and POS of the part (located=(names, ctg_off): its contig and a contig-local POS, else `rname` and t0 + 1); the entry's
-    MAPQ; the clipped CIGAR with its S runs (soft, not hard: SEQ is the whole read, reverse-complemented on strand 1); RNEXT and
-    PNEXT as on the primary line (= only where the mate lies on the part's own reference); TLEN 0; NM:i:, MD:Z:, AS:i: and SA:Z:.
-    Pure Python / numpy: no device is needed."""
-    table = _letters_table(letters)
-    comp = np.ascontiguousarray(complement, np.uint8)
-    ranks = np.asarray(ranks, np.uint8)
-    roff = np.asarray(roff, np.uint64)
-    sup_off, _, _, strand, _, _, t0, _, score, _, nm, ctg, _ = sup_host
-    if located is None and rname is None:
-        raise ValueError("sam_supplementary_lines: give rname, or located=(names, ctg_off)")
-    if located is not None and ctg is None:
-        raise ValueError("sam_supplementary_lines: located needs the ctg of a Supplementaries made under a contig table")
-    if not (roff.size - 1 == len(primary_lines) == len(sa) == sup_off.size - 1) or not (len(cigars) == len(mds) == len(mapq) == strand.size):
-        raise ValueError("sam_supplementary_lines: the arrays disagree in the number of reads or of entries")
-    lines = []
-    for i in range(sup_off.size - 1):
-        a, b = int(sup_off[i]), int(sup_off[i + 1])
-        if a == b:
-            continue
-        first = primary_lines[i].split("\t")
-        q = ranks[int(roff[i]):int(roff[i + 1])]
-        if (q >= sigma).any():
-            raise ValueError(f"sam_supplementary_lines: read {i} holds a letter outside the alphabet")
-        mate_name = first[2] if first[6] == "=" else first[6]
-        for j, x in enumerate(range(a, b)):
-            if located is not None:
-                names, ctg_off = located
-                name, pos = names[int(ctg[x])], int(t0[x]) - int(ctg_off[int(ctg[x])]) + 1
-            else:
-                name, pos = rname, int(t0[x]) + 1
-            flag = 0x800 | (0x10 if strand[x] == 1 else 0) | (int(first[1]) & (0x1 | 0x8 | 0x20 | 0x40 | 0x80))
-            seq = table[comp[q[::-1]] if strand[x] == 1 else q].tobytes().decode("latin-1") or "*"
-            rnext = "*" if mate_name == "*" else "=" if mate_name == name else mate_name
-            lines.append("\t".join([first[0], str(flag), name, str(pos), str(int(mapq[x])), cigars[x] or "*", rnext, first[7], "0", seq, "*",
-                                    f"NM:i:{int(nm[x])}", f"MD:Z:{mds[x]}", f"AS:i:{int(score[x])}", f"SA:Z:{sa[i][j + 1]}"]))
-    return lines
+        _, strand, _, start = placements_host[:4]
+        tl, nm = clip_fields[:2]
+        ctg, _ = (None, None) if located_host is None else located_host
+        pos = np.asarray(start, np.int64) + np.asarray(tl, np.int64)
+        primary = (pos, np.where(np.asarray(strand) == 1, 1, 0), cigars, mapq, nm, ctg)
+        entries = (h.t0, h.strand, self.cigars(clips), self.mapq(cap), h.nm, h.ctg)
+        return sa_strings(h.sup_off, primary, entries, located, rname, strand_names)
 
 
 class Located(_Handle):
@@ -1317,172 +1174,18 @@ class Rescues(_PerRead, _Handle):
 
     def _entries(self, scripts):
         """the entry of every rescued public read, -1 for every other"""
-        job_off, read, _, _, _, _, _, status = self.host()
-        read_sel_off = scripts.host()[0]
-        out = [-1] * ((job_off.size - 1) // 2)
-        for r, taken in zip(read, status == RESCUE_TAKEN):
+        h = self.host()
+        read_sel_off = scripts.host().read_sel_off
+        out = [-1] * ((h.job_off.size - 1) // 2)
+        for r, taken in zip(h.read, h.status == RESCUE_TAKEN):
             if taken and read_sel_off[int(r) + 1] > read_sel_off[int(r)]:
                 out[int(r) // 2] = int(read_sel_off[int(r)])
         return out
 
 
-def sam_pair_fields(strand, start, cls, tlen):
-    """The SAM fields that a pair decides, per read, from the host arrays of a Placements (strand, start: 2 np entries, mates
-    interleaved) and a Pairs (cls, tlen: np entries): (FLAG u16, POS i64, PNEXT i64, TLEN i32).  FLAG carries 0x1, 0x2 (the pair is
-    concordant), 0x4 / 0x8 (the read / its mate is unplaced), 0x10 / 0x20 (the read / its mate lies on the reverse strand) and
-    0x40 / 0x80 (mate 1 / mate 2); POS is 1-based, an unplaced read takes its mate's and 0 when both are unplaced; PNEXT is the
-    mate's POS; TLEN is tlen for mate 1 and -tlen for mate 2.  Pure numpy: no device is needed."""
-    strand = np.asarray(strand, np.uint8)
-    start = np.asarray(start, np.uint32)
-    cls = np.asarray(cls, np.uint8)
-    tlen = np.asarray(tlen, np.int32)
-    mate = np.arange(strand.size) ^ 1
-    placed = strand != 255
-    flag = np.full(strand.size, 0x1, np.uint16)
-    flag[np.repeat(cls == PAIR_CONCORDANT, 2)] |= 0x2
-    flag[~placed] |= 0x4
-    flag[~placed[mate]] |= 0x8
-    flag[placed & (strand == 1)] |= 0x10
-    flag[placed[mate] & (strand[mate] == 1)] |= 0x20
-    flag[0::2] |= 0x40
-    flag[1::2] |= 0x80
-    own = np.where(placed, start.astype(np.int64) + 1, 0)
-    pos = np.where(placed, own, own[mate])
-    t = np.repeat(tlen, 2)
-    t[1::2] = -t[1::2]
-    return flag, pos, pos[mate], t.astype(np.int32)
-
-
 # what map_reads_strands / map_pairs append with tags=True: the Mapq, the Md of the scripts, and after a rescue the Scripts of the
 # rescued mates and their Md (else None)
 SamTags = collections.namedtuple("SamTags", "mapq md rescue_scripts rescue_md")
-
-
-def _first_given(strings):
-    """A list of strings, or several lists of equal length (the placements', then the rescue's): per read the first that is not empty."""
-    if strings and not isinstance(strings[0], str):
-        return [next((s for s in group if s), "") for group in zip(*strings)]
-    return list(strings)
-
-
-def concat_sequences(seqs):
-    """The text of a multi-sequence reference: (ranks uint8, ctg_off uint64[len(seqs) + 1]) with sequence c at
-    ranks[ctg_off[c]:ctg_off[c + 1]], ready for Index(...) and Index.set_contigs.  An empty sequence is refused (a contig table
-    has none).  Pure numpy: no device is needed."""
-    seqs = [np.ascontiguousarray(q, np.uint8).ravel() for q in seqs]
-    if any(q.size == 0 for q in seqs):
-        raise ValueError("concat_sequences: an empty sequence")
-    ctg_off = np.zeros(len(seqs) + 1, np.uint64)
-    if seqs:
-        ctg_off[1:] = np.cumsum([q.size for q in seqs], dtype=np.uint64)
-    return (np.concatenate(seqs) if seqs else np.zeros(0, np.uint8)), ctg_off
-
-
-def sam_header(names, ctg_off):
-    """The header lines (no newlines) of a SAM file over a contig table: "@HD\tVN:1.6\tSO:unsorted" and one
-    "@SQ\tSN:<name>\tLN:<length>" per contig."""
-    ctg_off = np.asarray(ctg_off, np.uint64)
-    if ctg_off.size != len(names) + 1:
-        raise ValueError("sam_header: ctg_off needs one entry more than there are names")
-    return ["@HD\tVN:1.6\tSO:unsorted"] + [f"@SQ\tSN:{nm}\tLN:{int(b) - int(a)}" for nm, a, b in zip(names, ctg_off[:-1], ctg_off[1:])]
-
-
-def sam_lines(qnames, ranks, roff, letters, complement, sigma, rname, placements_host, cigars, mds, mapq, pairs_host=None, located_host=None,
-              xa=None, clip_fields=None, sa=None):
-    """One SAM line (no newline) per public read from host arrays: the reads (ranks, roff), the rank -> letter table, the rank
-    complement table, Placements.host(), the CIGAR and MD strings per read (Placements.cigars / .mds; a tuple of two lists, the
-    placements' and the rescue's, gives a rescued read those of the rescue), Mapq.host() and, for paired reads, Pairs.host().
-    FLAG / POS / PNEXT / TLEN come from sam_pair_fields when pairs_host is given; otherwise FLAG is 0 / 4 / 16, POS is start + 1 and
-    there is no mate.  CIGAR is * when the read is unplaced, RNEXT = or *, SEQ the reverse complement for a reverse placement,
-    QUAL *; placed reads carry NM:i: (the distance) and MD:Z:.  located_host (Located.host(): ctg, pos) switches to contig
-    coordinates: rname then is a sequence of one name per contig, RNAME the read's contig (an unplaced read with a placed mate takes
-    the mate's), POS and PNEXT are contig-local, RNEXT is = for the same contig and the mate's contig name otherwise.  xa
-    (Secondaries.xa(): one string per read) appends XA:Z:<string> behind MD:Z: to every placed read whose string is not empty; None
-    leaves the lines as they were.  clip_fields (Placements.clip_fields(); a tuple of two, the placements' and the rescue's, like
-    cigars) writes soft-clipped records: cigars and mds then are the clipped ones (Clips.strings(), Clips.md()), a read's POS is
-    start + tl, and so are its contig-local POS and its mate's PNEXT, NM:i: is the clipped nm, and AS:i:<score> follows MD:Z:.  TLEN
-    stays the pair fold's, measured between the UNCLIPPED outer ends.  None leaves every line as it was.  sa (what sa_strings or
-    Supplementaries.sa returned: per read a list whose first value is the primary's) appends SA:Z:<value> behind XA:Z: to every
-    placed read whose value is not empty; None leaves every line as it was (the FLAG 0x800 lines: sam_supplementary_lines).  Pure
-    Python / numpy: no device is needed."""
-    table = _letters_table(letters)
-    comp = np.ascontiguousarray(complement, np.uint8)
-    if table.size < sigma or comp.size < sigma:
-        raise ValueError("sam_lines: letters and complement need sigma entries")
-    ranks = np.asarray(ranks, np.uint8)
-    roff = np.asarray(roff, np.uint64)
-    strand, dist, start = (np.asarray(placements_host[k]) for k in (1, 2, 3))
-    nr = strand.size
-    cigars, mds = _first_given(cigars), _first_given(mds)
-    mapq = np.asarray(mapq, np.uint8)
-    if not (roff.size - 1 == len(qnames) == len(cigars) == len(mds) == mapq.size == nr):
-        raise ValueError("sam_lines: the arrays disagree in the number of reads")
-    if xa is not None and len(xa) != nr:
-        raise ValueError("sam_lines: xa disagrees in the number of reads")
-    if sa is not None and len(sa) != nr:
-        raise ValueError("sam_lines: sa disagrees in the number of reads")
-    placed = strand != 255
-    shift = nm = score = has = None
-    if clip_fields is not None:
-        groups = clip_fields if len(clip_fields) == 2 else (clip_fields,)
-        if any(len(g) != 4 or any(np.asarray(a).size != nr for a in g) for g in groups):
-            raise ValueError("sam_lines: clip_fields is (tl, nm, score, has) per read, or a tuple of two of them")
-        shift, nm, score, has = (np.asarray(a) for a in groups[0])
-        for g in groups[1:]:                                   # a rescued read takes the rescue's
-            take = ~has & np.asarray(g[3], bool)
-            shift, nm, score = (np.where(take, np.asarray(b), a) for a, b in zip((shift, nm, score), g[:3]))
-            has = has | take
-        has = np.asarray(has, bool) & placed
-        shift = np.where(has, shift, 0).astype(np.int64)
-        start = (start.astype(np.int64) + shift).astype(np.uint32)
-    if pairs_host is not None:
-        flag, pos, pnext, tlen = sam_pair_fields(strand, start, pairs_host[0], pairs_host[1])
-    else:
-        flag = np.where(placed, np.where(strand == 1, 0x10, 0), 0x4)
-        pos = np.where(placed, start.astype(np.int64) + 1, 0)
-        pnext, tlen = np.zeros(nr, np.int64), np.zeros(nr, np.int32)
-    names = nextname = None
-    if located_host is not None:
-        ctg, lpos = (np.asarray(a, np.uint32) for a in located_host)
-        if ctg.size != nr or lpos.size != nr:
-            raise ValueError("sam_lines: the located arrays disagree in the number of reads")
-        if (placed & (ctg == NO_CONTIG)).any():
-            raise ValueError("sam_lines: a placed read has no contig (n_mismatched of the Located is not 0)")
-        if (ctg[placed] >= len(rname)).any():
-            raise ValueError("sam_lines: a contig without a name")
-        own = np.where(placed, lpos.astype(np.int64) + 1 + (shift if shift is not None else 0), 0)
-        if pairs_host is not None:
-            mate = np.arange(nr) ^ 1
-            rc = np.where(placed, ctg, ctg[mate])              # an unplaced read takes its mate's contig and POS
-            pos = np.where(placed, own, own[mate])
-            pnext = pos[mate]
-            names = [rname[int(c)] if c != NO_CONTIG else "*" for c in rc]
-            nextname = ["*" if rc[j] == NO_CONTIG else "=" if rc[j] == rc[i] else names[j] for i, j in enumerate(mate)]
-        else:
-            pos = own
-            names = [rname[int(c)] if c != NO_CONTIG else "*" for c in ctg]
-            nextname = ["*"] * nr
-    lines = []
-    for i in range(nr):
-        q = ranks[int(roff[i]):int(roff[i + 1])]
-        if (q >= sigma).any():
-            raise ValueError(f"sam_lines: read {i} holds a letter outside the alphabet")
-        if placed[i] and strand[i] == 1:
-            q = comp[q[::-1]]
-        seq = table[q].tobytes().decode("latin-1") or "*"
-        fields = [str(qnames[i]), str(int(flag[i])), (rname if pos[i] else "*") if names is None else names[i], str(int(pos[i])), str(int(mapq[i])),
-                  (cigars[i] or "*") if placed[i] else "*", ("=" if pnext[i] else "*") if names is None else nextname[i], str(int(pnext[i])),
-                  str(int(tlen[i])), seq, "*"]
-        if placed[i]:
-            fields += [f"NM:i:{int(nm[i]) if has is not None and has[i] else int(dist[i])}", f"MD:Z:{mds[i]}"]
-            if has is not None and has[i]:
-                fields.append(f"AS:i:{int(score[i])}")
-            if xa is not None and xa[i]:
-                fields.append(f"XA:Z:{xa[i]}")
-            if sa is not None and sa[i][0]:
-                fields.append(f"SA:Z:{sa[i][0]}")
-        lines.append("\t".join(fields))
-    return lines
 
 
 class ApproxResult(_Handle):
@@ -1888,18 +1591,17 @@ class Index:
                 into = pileup.get("into")
                 mapq = sam.mapq if opt.get("min_mapq", 0) > 0 else None
                 pu = into if into is not None else keep(Pileup())     # (an `into` handle is the caller's: not closed when a step raises)
-                if cl is not None:
-                    cl.pileup(self, sc, al, reads, mapq=mapq, add=into is not None, stream=stream, pileup=pu, **opt)
-                else:
-                    sc.pileup(self, al, reads, mapq=mapq, add=into is not None, stream=stream, pileup=pu, **opt)
+
+                def piled(s, c, source, add):                          # the scripts s, or their clips c, over `source` into pu
+                    on = dict(mapq=mapq, add=add, stream=stream, pileup=pu, **opt)
+                    return s.pileup(self, source, reads, **on) if c is None else c.pileup(self, s, source, reads, **on)
+
+                piled(sc, cl, al, into is not None)
                 if res is not None:
                     own = rsc is None                                  # made for this alone: closed here
                     rs = rsc if rsc is not None else res.scripts(self, reads)
                     try:
-                        if rcl is not None:
-                            rcl.pileup(self, rs, res, reads, mapq=mapq, add=True, stream=stream, pileup=pu, **opt)
-                        else:
-                            rs.pileup(self, res, reads, mapq=mapq, add=True, stream=stream, pileup=pu, **opt)
+                        piled(rs, rcl, res, True)
                     finally:
                         if own:
                             if pu._h:

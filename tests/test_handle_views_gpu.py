@@ -11,6 +11,8 @@ when kmx_*_view_device hands out NULL, as include/kmx.h words it.  One handle of
 and in every state its counts(), the NULL pattern of device_ptrs(), the length of every array of host() and the bytes at every device
 pointer against the host array are held against a handle of its own that the same batch has filled once.  kmx_windows_vote has no
 refusal that looks at the loci handle (its refusals "after looking" look at the result): state 5 leaves a Loci as it was.
+host() names its fields as _view_of declares them; a field that a class lists in _optional (ctg) is None there when the C view hands
+out NULL for it: under the contig table of these tests only while it is empty, and always on an index without one (a test of its own).
 ApproxResult is not a chain handle (no device view, no refill by a chain stage) and has no row."""
 import collections
 import contextlib
@@ -163,15 +165,24 @@ def check(engine, row, h, state, want=None):
     counts, ptrs, host = views(engine, h)
     fields = h._view_of[1]
     assert len(NULLS[row.cls]) == len(fields) == len(ptrs) == len(host), f"{row.cls}: NULLS has {len(NULLS[row.cls])} rules for {len(fields)} fields"
+    assert host._fields == tuple(name for name, _, _ in fields), f"{row.cls}: the host view names {host._fields}"
+    if row.cls == "Placements":
+        front = h.host(best2=False)
+        assert front._fields == host._fields[:6] and len(front) == 6, f"Placements.host(best2=False) names {front._fields}"
+        assert all(np.array_equal(a, b) for a, b in zip(front, host)), "Placements.host(best2=False) is not the front of host()"
     if state == REFUSED:
         assert not any(counts.values()), f"{row.name}: counts {counts} after a refusal"
     if want is not None:
         w_counts, _, w_host = views(engine, want)
         assert counts == w_counts, f"{row.name}: counts {counts}, want {w_counts}"
         for (name, _, _), g, w in zip(fields, host, w_host):
-            assert g.dtype == w.dtype and np.array_equal(g, w), differ(f"{row.name}.{name}", g, w)
+            assert (g is None) == (w is None), f"{row.name}.{name}: {'no ' if g is None else 'a '}view, want {'none' if w is None else 'one'}"
+            assert g is None or (g.dtype == w.dtype and np.array_equal(g, w)), differ(f"{row.name}.{name}", g, w)
     for (name, dtype, n), rule, p, g in zip(fields, NULLS[row.cls], ptrs, host):
         n = n(counts) if callable(n) else counts[n]
+        if g is None:                                          # an _optional field whose host pointer is NULL: under a contig table, only while it is empty
+            assert name in h._optional and n == 0 and p is None, f"{row.name}.{name} ({state}, {n} elements): no host view, device pointer {p!r}"
+            continue
         assert g.dtype == dtype and g.size == n, f"{row.name}.{name}: the host view is {g.dtype}[{g.size}], want {np.dtype(dtype)}[{n}]"
         null = n == 0 if rule is LIVE else state == REFUSED if rule is FILLED else False
         assert (p is None) == null, f"{row.name}.{name} ({state}, {n} elements): the device pointer is {p!r}; {rule}"
@@ -211,6 +222,36 @@ def without_options(engine, fn):
 def test_every_declared_handle_has_a_row(engine):
     declared = {c.__name__ for c in vars(engine).values() if isinstance(c, type) and issubclass(c, engine._Handle) and c._view_of is not None}
     assert declared - {"ApproxResult"} == {r.cls for r in ROWS} == set(NULLS), "a _Handle subclass with _view_of joins ROWS and NULLS"
+
+
+def test_an_optional_field_is_none_without_a_contig_table(engine):
+    """The Secondaries of the tiny batch on the index before set_contigs: ctg, which the class declares _optional, is None in host() and
+    NULL on the device; every other field is the device array under its name."""
+    declared = {c.__name__: c._optional for c in vars(engine).values() if isinstance(c, type) and issubclass(c, engine._Handle) and c._optional}
+    assert declared == {"Secondaries": ("ctg",), "Supplementaries": ("ctg",), "Sites": ("ctg",)}, declared
+    assert not any("host" in vars(getattr(engine, name)) for name in declared), "a class with _optional has a host() of its own"
+    with contextlib.ExitStack() as opened:
+        keep = lambda h: opened.enter_context(contextlib.closing(h))
+        idx = keep(engine.Index(tiny_text(), 4, [K], table=2))
+        reads = keep(idx.strand_reads(*pack(tiny_pairs()), COMP4))
+        d_ranks2, d_roff2, nr2, stream = reads.device_ptrs()
+        windows = keep(idx.search_windows_device(d_ranks2, d_roff2, nr2, K, 1, stream=stream))
+        loci = keep(windows.vote(TINY_CHAIN["band"], TINY_CHAIN["min_votes"]))
+        al = keep(loci.align_device(idx, d_ranks2, d_roff2, nr2, TINY_E, TINY_CHAIN["max_span"], stream=stream))
+        assert al.contigs_host() is None
+        pl = keep(engine.Placements())
+        al.fold_pairs(loci, **TINY_INSERT, stream=stream, placements=pl, pairs=keep(engine.Pairs()))
+        sec = keep(pl.secondaries(loci, al, 4))
+        counts, ptrs, host = views(engine, sec)
+        fields = sec._view_of[1]
+        assert counts["n_sec"] > 0, "the tiny batch has no secondary place"
+        assert host._fields == sec.host()._fields == tuple(name for name, _, _ in fields)
+        assert host.ctg is None and sec.host().ctg is None and ptrs[host._fields.index("ctg")] is None, "a ctg view without a contig table"
+        for (name, dtype, n), p, g in zip(fields, ptrs, host):
+            if name != "ctg":
+                n = n(counts) if callable(n) else counts[n]
+                assert g is getattr(host, name) and g.dtype == dtype and g.size == n > 0, f"{name}: the host view is {g.dtype}[{g.size}], want {np.dtype(dtype)}[{n}]"
+                assert np.array_equal(dev_array(p, n, dtype), g), differ(f"{name} (device against host)", dev_array(p, n, dtype), g)
 
 
 @pytest.mark.parametrize("row", ROWS, ids=[r.name for r in ROWS])

@@ -78,9 +78,9 @@ def main():
     out["entries"] = sc.counts()
     out["clips"], out["realigned"] = cl.counts(), rl.counts()
     trimmed, again = cl.host(), rl.host()
-    out["entries_with_a_better_score"] = int((again[0] > trimmed[0]).sum())
-    out["entries_with_a_worse_score"] = int((again[0] < trimmed[0]).sum())
-    dist = al.host()[0][sc.host()[1]]
+    out["entries_with_a_better_score"] = int((again.score > trimmed.score).sum())
+    out["entries_with_a_worse_score"] = int((again.score < trimmed.score).sum())
+    dist = al.host().dist[sc.host().sel]
     out["dist_histogram"] = np.bincount(dist, minlength=1).tolist()
     os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
     with open(a.json, "w") as f:
